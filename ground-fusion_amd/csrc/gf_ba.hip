@@ -202,6 +202,8 @@ struct gf_ba {
     bool chain_mode = false; int n_chain = 0, n_dense = 0, chain_nd = 0; size_t yg_stride = 0; Buf<double> Yg;
     bool cost_only = true;   // the last iteration's candidate is linearised cost-only (GF_BA_COST_ONLY=0 when the handle is created: in full, as every other candidate)
     bool upload_kernel = true;
+    // pivot cut and least-squares right-hand side of ba_marg_finish (GF_MARG_PIVOT_EPS, GF_MARG_LS_RHS when the handle is created; note in run_marginalize)
+    double piv_eps = 3e-8; int ls_rhs = 1;
     bool pos_ident = false;
     bool split_jtj = false, split_timed = false;   // gf_ba_set_split_jtj: the visual sweep as two kernels (block rows through HBM, contraction-only MFMA kernel)
     Buf<double> vrows, vpair; hipEvent_t ev_split[2] = {nullptr, nullptr};
@@ -804,8 +806,9 @@ int run_marginalize(gf_ba* h, int mode) {
     // dimension only, so no pivot cut reproduces the eigenvalue cut direction for direction.  Measured on the closed-loop GNSS replays (the states that hang on exactly
     // these directions; worst receiver clock / anchor deviation from the oracle pipeline over W = 10 handed-in, W = 20 handed-in, own initialiser, raw ephemerides,
     // configs[4]): cut 1e-10: 1e-6 1e-8 3e-8 6e-5 1e-6;  1e-9: 1e-6 1e-8 3e-8 6e-5 3e-4;  1e-8: 1e-6 7e-8 3e-8 2e-7 4e-4;  3e-8: 1e-6 3e-7 3e-8 2e-7 1e-6 [m].
-    static const double piv_eps = getenv("GF_MARG_PIVOT_EPS") ? atof(getenv("GF_MARG_PIVOT_EPS")) : 3e-8;
-    static const int ls_rhs = getenv("GF_MARG_LS_RHS") ? atoi(getenv("GF_MARG_LS_RHS")) : 1;
+    // Both are read when the handle is created (gf_ba_create), as every other switch.
+    const double piv_eps = h->piv_eps;
+    const int ls_rhs = h->ls_rhs;
     poison_lds(h);
     if (h->big_marg) ba_marg_finish<true><<<dim3(d.B), 512, 0, h->stream>>>(wm, h->sbufs(), reinterpret_cast<const MargInfo*>(h->minfo[mode].d), mo, mode == 0 ? 1 : 0, piv_eps, ls_rhs, 0);
     else ba_marg_finish<false><<<dim3(d.B), 512, h->marg_lds, h->stream>>>(wm, h->sbufs(), reinterpret_cast<const MargInfo*>(h->minfo[mode].d), mo, mode == 0 ? 1 : 0, piv_eps, ls_rhs, (int)(h->marg_lds / sizeof(double)));
@@ -907,6 +910,8 @@ int gf_ba_create(const gf_ba_cfg* cfg, gf_ba** out) {
     h->step_waves = (getenv("GF_BA_STEP_WAVES") && atoi(getenv("GF_BA_STEP_WAVES")) == 4) ? 4 : 8;
     h->chain_mode = getenv("GF_BA_CHAIN") && atoi(getenv("GF_BA_CHAIN")) != 0 && !h->big_step && !gnss;
     h->cost_only = !(getenv("GF_BA_COST_ONLY") && atoi(getenv("GF_BA_COST_ONLY")) == 0);
+    h->piv_eps = getenv("GF_MARG_PIVOT_EPS") ? atof(getenv("GF_MARG_PIVOT_EPS")) : 3e-8;
+    h->ls_rhs = getenv("GF_MARG_LS_RHS") ? atoi(getenv("GF_MARG_LS_RHS")) : 1;
     if (h->chain_mode) {
         const int nd_max = Rmax - 9 * d.NP;
         if (ch_lds_doubles(nd_max) * sizeof(double) + 20 * 1024 > 160 * 1024) h->chain_mode = false;   // (cannot happen where the dense form fits LDS; kept as the guard it is)

@@ -539,6 +539,7 @@ static int track_core(gf_tracker* h, const double* t, const uint8_t* d_gray, con
         down(h->d_centers, h->h_centers, (size_t)B * cap);
         down(h->d_ncenters, h->h_ncenters, B);
         down(h->d_want, h->h_want, B);
+        down(h->d_out_n, h->h_out_n, B);   // zeros (set above): a sequence that neither selection kernel serves reads 0, not the previous frame's count
         if (int rc = flush()) return rc;
         HIPCHK(hipMemsetAsync(h->d_maxkey.p, 0, B * sizeof(unsigned), h->stream));
         HIPCHK(hipMemsetAsync(h->d_cand_count.p, 0, B * sizeof(int), h->stream));
@@ -585,6 +586,15 @@ static int track_core(gf_tracker* h, const double* t, const uint8_t* d_gray, con
         for (int b = 0; b < B; b++) {
             if (h->h_want.p[b] > 0 && h->h_cand_count.p[b] > h->cand_cap)
                 return set_err(GF_ERR_CAPACITY, "sequence %d: %d corner candidates exceed capacity %d", b, h->h_cand_count.p[b], h->cand_cap);
+            // which branch of the corner selection served the sequence (the kernels' own tests on the same numbers)
+            const int want = h->h_want.p[b], n = std::min(h->h_cand_count.p[b], h->cand_cap);
+            if (want <= 0 || n <= 0) continue;
+            if (h->select_topk && want <= kTopKMax) { if (n > 1024 * kTopKQ) h->stats.select_streamed++; }
+            else {
+                int npow2 = 64;
+                while (npow2 < n) npow2 <<= 1;
+                if (npow2 > h->sort_cap) h->stats.select_global_sort++;
+            }
         }
 
     // ---- addPoints, undistortedPts, ptsVelocity, pack (feature_tracker.cpp:85-93, 210-211, 322-368)

@@ -30,7 +30,7 @@ class TrackerStats(C.Structure):
                 ("ms_host_pre", C.c_double), ("ms_wait_lk", C.c_double), ("ms_host_mid", C.c_double), ("ms_wait_detect", C.c_double), ("ms_host_post", C.c_double),
                 ("frames", C.c_longlong), ("lk_launches", C.c_longlong), ("lk_points", C.c_longlong),
                 ("lk_level_passes", C.c_longlong), ("lk_iterations", C.c_longlong), ("tracked_features", C.c_longlong),
-                ("output_features", C.c_longlong)]
+                ("output_features", C.c_longlong), ("select_streamed", C.c_longlong), ("select_global_sort", C.c_longlong)]
 
 
 OBS_DTYPE = np.dtype([("id", np.int32), ("camera_id", np.int32), ("v", np.float64, (8,))])

@@ -65,6 +65,12 @@ typedef struct gf_tracker_stats {
     long long lk_iterations;     /* sum over points/levels of Gauss-Newton iterations */
     long long tracked_features;  /* features that survived tracking (status==1 after all checks) */
     long long output_features;   /* features returned to the caller (tracked + newly detected) */
+    /* branches of the corner selection, counted on the host from each sequence's candidate count and want:
+     * select_streamed: sequences served by select_topk_kernel (want <= 16) with more than 4 096 candidates (the list past the registers is streamed every round);
+     * select_global_sort: sequences that select_corners_kernel sorted in global memory (candidates beyond the handle's LDS sort area, 16 384 keys or fewer
+     * when min_dist is small) */
+    long long select_streamed;
+    long long select_global_sort;
 } gf_tracker_stats;
 
 int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out);

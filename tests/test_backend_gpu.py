@@ -638,3 +638,224 @@ def test_cost_only_last_linearisation_changes_nothing_but_the_last_bits_of_the_c
         assert abs(sa["final_cost"] - sb["final_cost"]) <= 1e-13 * sb["final_cost"]
         assert all(np.array_equal(wa[key], wb[key]) for key in gw.STATE_KEYS if key in wa), seed
         est_a.close(); est_b.close()
+
+
+# ---------------------------------------------------------------- the kept variants behind GF_BA_* / GF_MARG_* switches (read when a handle is created)
+def _same_state(a, b):
+    return all(np.array_equal(a[k], b[k]) for k in gw.STATE_KEYS if k in a)
+
+
+def _same_prior(p, q):
+    return p["n"] == q["n"] and p["m"] == q["m"] and all(np.array_equal(p[k], q[k]) for k in ("block_id", "J", "r", "x0"))
+
+
+def _solve_and_marginalize(est, wins, cap_n=256):
+    """8 iterations in place, then the next prior (MARGIN_OLD) from the solved states"""
+    sums = est.solve(wins, 8)
+    return sums, est.marginalize(wins, 0, cap_n=cap_n)
+
+
+def _prior_window(gf, oracle, seed, **kw):
+    """the second window of a chain, its prior made by the library's own marginalisation (default handle)"""
+    e0 = gf.Estimator()
+    w = SW.make_window(seed, oracle, **kw)
+    e0.solve([w], 8)
+    pr = e0.marginalize([w], 0)[0]
+    e0.close()
+    return SW.make_window(seed, oracle, frame0=1, prior=pr, **kw)
+
+
+@pytest.mark.parametrize("case", ["plain", "free_td_ex_wheel", "no_wheel", "prior", "global", "gnss"])
+def test_step_on_four_wavefronts_matches_the_dense_form_and_the_oracle(gf, oracle, monkeypatch, case):
+    """GF_BA_STEP_WAVES=4: ba_step on four wavefronts pivots in another order, as the chain form does, and is held to the chain form's contract: iteration counts, accepted
+    steps and termination equal to the eight-wavefront form and the oracle, states within 1e-9 (relative) of it, the oracle's pose bars, and a window alone gives the bits
+    it gives inside a batch.  'global' runs ba_step<true, 4> (the reduced system in global memory, GF_BA_FORCE_GLOBAL=1 on both handles)."""
+    monkeypatch.delenv("GF_BA_CHAIN", raising=False)
+    gnss = case == "gnss"
+    if case == "global":
+        monkeypatch.setenv("GF_BA_FORCE_GLOBAL", "1")
+    kw = {"free_td_ex_wheel": dict(fix_td=0, fix_ex_wheel=1), "no_wheel": dict(use_wheel=False), "gnss": dict(gnss=True)}.get(case, {})
+    w0 = _prior_window(gf, oracle, 9) if case == "prior" else SW.make_window(4 if case == "free_td_ex_wheel" else 1, oracle, **kw)
+    if case == "free_td_ex_wheel":
+        w0["para_Td"][0] = 0.004
+    make = (lambda batch: _gnss_est(gf, batch=batch)) if gnss else (lambda batch: gf.Estimator(batch=batch))
+    wo, w8, w4 = w0.copy(), w0.copy(), w0.copy()
+    so = oracle.ba_solve(wo, 8)
+    est8 = make(1)
+    s8 = est8.solve([w8], 8)[0]
+    monkeypatch.setenv("GF_BA_STEP_WAVES", "4")
+    est4 = make(4)
+    s4 = est4.solve([w4], 8)[0]
+    for k_ in ("iterations", "successful_steps", "termination"):
+        assert s4[k_] == s8[k_] == so[k_], (k_, s4, s8, so)
+    # (GNSS: a sum of squares of pseudorange residuals formed from 2e7-m ranges carries ~1e-9 of its value as rounding, test_golden.check_solve; measured 5e-10)
+    assert abs(s4["final_cost"] - s8["final_cost"]) <= (1e-8 if gnss else 1e-10) * s8["final_cost"]
+    for k_ in gw.STATE_KEYS:
+        if k_ in w8 and np.size(w8[k_]):
+            assert (np.abs(w4[k_] - w8[k_]) / np.maximum(1.0, np.abs(w8[k_]))).max() < 1e-9, k_
+    dp, dr = _pose_diff(wo, w4)
+    assert dp < 1e-6 and dr < 1e-6, (dp, dr)
+    ws = [w0.copy() for _ in range(3)]
+    assert est4.solve(ws, 8) == [s4] * 3
+    assert all(_same_state(w_, w4) for w_ in ws)
+    est8.close(); est4.close()
+
+
+@pytest.mark.parametrize("name", ["ref_solve_free_ex_td", "ref_solve_with_prior", "ref_solve_wheel", "ref_solve_wheel_free_ix_td", "ref_solve_gnss"])
+def test_step_on_four_wavefronts_meets_the_loop_at_60_digits(gf, monkeypatch, name):
+    """test_solve_meets_the_loop_at_60_digits with GF_BA_STEP_WAVES=4, the same bars"""
+    from test_golden import check_solve
+    monkeypatch.delenv("GF_BA_CHAIN", raising=False)
+    monkeypatch.setenv("GF_BA_STEP_WAVES", "4")
+    est = gf.Estimator(max_features=16, max_visual=256, max_gnss=132 if "gnss" in name else 0)
+    print(name, "four wavefronts vs the loop at 60 digits:", check_solve(lambda a: est.solve([a], 8)[0], name))
+    est.close()
+
+
+def test_fused_misc_step_gives_the_bits_of_the_full_last_linearisation(gf, oracle, monkeypatch):
+    """GF_BA_FUSE_MISC=1: ba_misc_step linearises the prior / IMU / wheel factors of the candidate inside the step kernel.  It turns off the cost-only last linearisation,
+    so it is held to GF_BA_COST_ONLY=0 bit for bit -- states, summaries and the next prior -- and to the default handle in the states (bit for bit) and the cost (1e-13).
+    A batch of windows with and without a prior and without wheel factors.  A handle that cannot fuse (GNSS columns) gives the bits it gives without the switch."""
+    monkeypatch.delenv("GF_BA_CHAIN", raising=False)
+    wins = [SW.make_window(41, oracle), _prior_window(gf, oracle, 42), SW.make_window(43, oracle, use_wheel=False), _prior_window(gf, oracle, 44, use_wheel=False)]
+    runs = {}
+    for name, env in (("default", {}), ("full", {"GF_BA_COST_ONLY": "0"}), ("fused", {"GF_BA_FUSE_MISC": "1"})):
+        for k_, v in env.items():
+            monkeypatch.setenv(k_, v)
+        est = gf.Estimator(batch=4)
+        ws = [w.copy() for w in wins]
+        runs[name] = (ws,) + _solve_and_marginalize(est, ws)
+        est.close()
+        for k_ in env:
+            monkeypatch.delenv(k_)
+    (wd, sd, pd_), (wf, sf, pf), (wx, sx, px) = runs["default"], runs["full"], runs["fused"]
+    for b in range(len(wins)):
+        assert sx[b] == sf[b], (b, sx[b], sf[b])
+        assert _same_state(wx[b], wf[b]) and _same_prior(px[b], pf[b]), b
+        assert _same_state(wx[b], wd[b]), b
+        for k_ in ("iterations", "successful_steps", "termination"):
+            assert sx[b][k_] == sd[b][k_], (b, k_)
+        assert abs(sx[b]["final_cost"] - sd[b]["final_cost"]) <= 1e-13 * sd[b]["final_cost"]
+    # a GNSS-enabled handle does not fuse: the switch changes nothing
+    w0 = SW.make_window(1, oracle, gnss=True)
+    out = []
+    for fuse in (False, True):
+        if fuse:
+            monkeypatch.setenv("GF_BA_FUSE_MISC", "1")
+        est = _gnss_est(gf)
+        ws = [w0.copy()]
+        out.append((ws,) + _solve_and_marginalize(est, ws))
+        est.close()
+    assert out[0][1] == out[1][1] and _same_state(out[0][0][0], out[1][0][0]) and _same_prior(out[0][2][0], out[1][2][0])
+
+
+def test_upload_by_per_table_copies_gives_the_bits_of_the_gather_kernel(gf, oracle, monkeypatch):
+    """GF_BA_UPLOAD=copies: one hipMemcpy(2D)Async per table instead of the gather kernel.  The same bytes reach the device, so everything is bit-identical: states,
+    summaries, priors, and gf_ba_linearize's H and g.  A mixed batch on a GNSS-enabled handle (a window with a prior, one with GNSS epochs, one with free extrinsic and td,
+    one without wheel factors), a W = 20 / 500-feature window, and two calls in a row on one handle with fewer features and observations in the second."""
+    monkeypatch.delenv("GF_BA_CHAIN", raising=False)
+    free = SW.make_window(4, oracle, fix_ex_pose=0, fix_td=0)
+    free["para_Td"][0] = 0.004
+    mixed = [_prior_window(gf, oracle, 9), SW.make_window(2, oracle, gnss=True), free, SW.make_window(7, oracle, use_wheel=False)]
+    W, F = 20, 500
+    big = SW.make_window(1, oracle, W=W, n_landmarks=int(F * 1.5), max_features=F)
+    first, second = SW.make_window(51, oracle), SW.make_window(52, oracle, max_features=60, n_landmarks=90)
+    assert second["n_feature"] < first["n_feature"] and second["n_visual"] < first["n_visual"]
+
+    def run_all():
+        res = []
+        est = _gnss_est(gf, batch=4)
+        ws = [w.copy() for w in mixed]
+        res.append((ws,) + _solve_and_marginalize(est, ws))
+        res.append([est.linearize(w.copy()) for w in mixed])
+        est.close()
+        est = gf.Estimator(W, F, F * W)
+        ws = [big.copy()]
+        res.append((ws,) + _solve_and_marginalize(est, ws, cap_n=512))
+        res.append([est.linearize(big.copy())])
+        est.close()
+        est = gf.Estimator(batch=2)
+        for w in (first, second):
+            ws = [w.copy(), w.copy()]
+            res.append((ws,) + _solve_and_marginalize(est, ws))
+            res.append([est.linearize(w.copy())])
+        est.close()
+        return res
+
+    ref = run_all()
+    monkeypatch.setenv("GF_BA_UPLOAD", "copies")
+    got = run_all()
+    for i, (r, g) in enumerate(zip(ref, got)):
+        if isinstance(r, tuple):
+            assert r[1] == g[1], i
+            assert all(_same_state(a, b) for a, b in zip(r[0], g[0])), i
+            assert all(_same_prior(a, b) for a, b in zip(r[2], g[2])), i
+        else:
+            for a, b in zip(r, g):
+                assert np.array_equal(a["H"], b["H"]) and np.array_equal(a["g"], b["g"]) and a["cost"] == b["cost"] and np.array_equal(a["ids"], b["ids"]), i
+
+
+def _nonzero_rows(p):
+    n = p["n"]
+    return int((np.abs(p["J"].reshape(n, n)).max(axis=1) > 0).sum())
+
+
+@pytest.mark.parametrize("seed,kw", [(4, {}), (7, {"use_wheel": False}), (1, {"gnss": True})])
+def test_forward_substituted_right_hand_side_of_the_prior(gf, oracle, monkeypatch, seed, kw):
+    """GF_MARG_LS_RHS=0: the prior's right-hand side by forward substitution instead of the least-squares one (gf_ba_marg.hpp).  Only r changes: J is the default's to the
+    bit, and so is r where the kept system is full rank (m2 = 0, nothing to do).  Where it is rank-deficient, J^T J and J^T r meet the bars of
+    test_marginalisation_matches_oracle (the GNSS window: the bar of test_gnss_marginalization_and_chain).  MARGIN_OLD on a first window and on the next one with a prior,
+    MARGIN_SECOND_NEW on that one."""
+    monkeypatch.delenv("GF_BA_CHAIN", raising=False)
+    gnss = kw.get("gnss", False)
+    make = (lambda: _gnss_est(gf)) if gnss else (lambda: gf.Estimator())
+    w = SW.make_window(seed, oracle, **kw)
+    oracle.ba_solve(w, 4)
+    w2 = SW.make_window(seed, oracle, frame0=1, prior=oracle.ba_marginalize(w, 0), **kw)
+    oracle.ba_solve(w2, 4)
+    cases = [(w, 0), (w2, 0), (w2, 1)]
+    est_d = make()
+    pd_ = [est_d.marginalize([x], mode)[0] for x, mode in cases]
+    est_d.close()
+    monkeypatch.setenv("GF_MARG_LS_RHS", "0")
+    est_f = make()
+    pf = [est_f.marginalize([x], mode)[0] for x, mode in cases]
+    est_f.close()
+    for (x, mode), a, b in zip(cases, pd_, pf):
+        assert np.array_equal(a["block_id"], b["block_id"]) and a["n"] == b["n"] and a["m"] == b["m"] and np.array_equal(a["x0"], b["x0"])
+        assert np.array_equal(a["J"], b["J"]), mode
+        rank = _nonzero_rows(b)
+        print("seed %d mode %d: n %d rank %d" % (seed, mode, b["n"], rank))
+        if rank == b["n"]:
+            assert np.array_equal(a["r"], b["r"])
+            continue
+        po = oracle.ba_marginalize(x, mode)
+        Ao, bo, _ = _prior_invariants(po)
+        Af, bf, _ = _prior_invariants(b)
+        print("   J^T r rel %.3e" % (np.abs(bo - bf).max() / np.abs(bo).max()))
+        # GNSS: the forward-substituted r PREDICTS b in the m2 directions next to the 1e-8 cut (yaw_enu_local, the ECEF anchor) instead of projecting it; the
+        # comment in test_gnss_marginalization_and_chain records 2e-8 .. 4e-7 for it, and this window measures 5.8e-7 -- above that test's 2e-7 (a bar of the
+        # least-squares r, the default), so this variant's GNSS bar is 1e-6.  Every other bar is the default's.
+        _assert_prior_close(Ao, bo, Af, bf, b_tol=1e-6 if gnss else 1e-8)
+
+
+@pytest.mark.parametrize("name", ["ref_marg_old_first_window", "ref_marg_old_with_prior", "ref_marg_second_new", "ref_marg_old_gnss"])
+def test_forward_substituted_right_hand_side_meets_the_reference_route_at_60_digits(gf, monkeypatch, name):
+    """test_marginalisation_meets_the_reference_route_at_60_digits with GF_MARG_LS_RHS=0, the same bars"""
+    from test_golden import load_ref_marg, check_prior_against_ref
+    w, fx, A, b, ids = load_ref_marg(name)
+    make = lambda: gf.Estimator(max_features=16, max_visual=256, max_gnss=132 if w["gnss_enabled"] else 0)
+    est = make()
+    pd_ = est.marginalize([w.copy()], fx["mode"])[0]
+    est.close()
+    monkeypatch.setenv("GF_MARG_LS_RHS", "0")
+    est = make()
+    p = est.marginalize([w.copy()], fx["mode"])[0]
+    rank = _nonzero_rows(p)
+    print(name, "rank %d of %d" % (rank, p["n"]))
+    assert np.array_equal(p["J"], pd_["J"])
+    if name == "ref_marg_old_with_prior":   # the kept system is full rank (m2 = 0): no right-hand side is changed either
+        assert rank == p["n"] and np.array_equal(p["r"], pd_["r"])
+    dev = check_prior_against_ref(p, fx, A, b, ids)
+    print(name, "forward-substituted r vs reference route at 60 digits: J^T J scaled %.1e, J^T r %.1e" % dev)
+    est.close()

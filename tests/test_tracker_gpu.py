@@ -333,6 +333,7 @@ def test_the_older_forms_of_the_pyramid_head_and_the_corner_selection_stay_bit_i
         gi, go = gtr.trackImage(0.0666 * k, f, depth)
         assert np.array_equal(oi, gi) and np.array_equal(oo.view(np.uint64), go.view(np.uint64)), k
     gtr.close()
+    _mixed_wants_batch(gf, oracle, frames=4)   # the batch: sequences that want none, a few, more than kTopKMax and every corner in one launch
     monkeypatch.delenv(switch)
     gtr = gf.FeatureTracker(gf.default_cfg(max_cnt=150, min_dist=30))      # and the default forms on the same frames
     otr = oracle.Tracker(oracle.default_cfg(max_cnt=150, min_dist=30))
@@ -341,3 +342,149 @@ def test_the_older_forms_of_the_pyramid_head_and_the_corner_selection_stay_bit_i
         gi, go = gtr.trackImage(0.0666 * k, f, depth)
         assert np.array_equal(oi, gi) and np.array_equal(oo.view(np.uint64), go.view(np.uint64)), k
     gtr.close()
+
+
+# ---------------------------------------------------------------- the branches of the corner selection and the per-table copies
+def _local_maxima(img, mask=None):
+    """the candidates of the Shi-Tomasi pass, counted on the CPU: non-zero 3x3 local maxima of the oracle's minimum eigenvalue (unmasked)"""
+    from numpy.lib.stride_tricks import sliding_window_view
+    import oracle_py
+    e = oracle_py.min_eigen_val(img)
+    mx = sliding_window_view(np.pad(e, 1, constant_values=-1.0), (3, 3)).max(axis=(2, 3))
+    keep = (e == mx) & (e > 0)
+    if mask is not None:
+        keep &= mask != 0
+    return int(keep.sum())
+
+
+def _noise(seed, w=640, h=480):
+    return np.random.default_rng(seed).integers(0, 256, (h, w)).astype(np.uint8)
+
+
+@pytest.mark.parametrize("topk", ["1", "0"])
+def test_streamed_top_k_over_more_than_4096_candidates(gf, oracle, monkeypatch, topk):
+    """select_topk_kernel holds 4 096 candidates per sequence in registers and streams the rest from global memory every round (streamed = n > 1024 * kTopKQ).  A finely
+    textured sequence with a small min_dist keeps ~19 000 candidates per frame; its tracks survive the small shifts, and removeOutliers drops six of them per frame so that
+    every later frame wants a handful of corners -- the streamed branch (select_streamed counts it).  The first frame wants every corner out of more candidates than the
+    LDS sort area holds: the global-memory sort.  Ids and observations bit for bit against the oracle, with the top-k kernel and with GF_SELECT_TOPK=0 (the sort only)."""
+    monkeypatch.setenv("GF_SELECT_TOPK", topk)
+    tex = synth.make_texture(31, sigma=1.0)
+    frames = [synth.warp_frame(tex, 0.3 * k, -0.2 * k) for k in range(5)]
+    assert min(_local_maxima(f) for f in frames) > 3 * 4096
+    depth = np.full(frames[0].shape, 1500, np.uint16)
+    otr = oracle.Tracker(oracle.default_cfg(max_cnt=150, min_dist=4))
+    gtr = gf.FeatureTracker(gf.default_cfg(max_cnt=150, min_dist=4))
+    rng = np.random.default_rng(1)
+    for k, f in enumerate(frames):
+        oi, oo = otr.track(0.05 * k, f, depth)
+        gi, go = gtr.trackImage(0.05 * k, f, depth)
+        assert np.array_equal(oi, gi) and np.array_equal(oo.view(np.uint64), go.view(np.uint64)), k
+        assert len(gi) == 150, k
+        rm = oi[rng.permutation(len(oi))[:6]]
+        otr.remove_outliers(rm); gtr.removeOutliers(rm)
+    st = gtr.stats()
+    assert st["select_streamed"] == (4 if topk == "1" else 0), st
+    assert st["select_global_sort"] == (1 if topk == "1" else 5), st     # (without the top-k kernel every frame's ~19 000 candidates go through the sort)
+    gtr.close()
+
+
+@pytest.mark.parametrize("max_corners,min_dist,masked", [(150, 3, False), (2000, 3, False), (150, 10, False), (2000, 10, True), (150, 30, False), (2000, 30, False)])
+def test_good_features_sorted_in_global_memory(gf, oracle, max_corners, min_dist, masked):
+    """white noise: more than 16 384 local maxima, more than the LDS sort area of select_corners_kernel holds -- the single-block bitonic sort in global memory.  Noise
+    has many equal eigenvalues, so the tie rule (the larger offset first) decides the order of many candidates."""
+    img = _noise(77)
+    mask = None
+    if masked:
+        mask = np.full(img.shape, 255, np.uint8)
+        for (cx, cy) in [(100, 100), (320, 240), (600, 20)]:
+            oracle.fill_circle(mask, cx, cy, 40)
+        mask[300:320, :] = 0
+    assert _local_maxima(img, mask) > 16384
+    a = oracle.good_features(img, max_corners, min_dist=float(min_dist), mask=mask)
+    b = gf.good_features(img, max_corners, min_dist=min_dist, mask=mask)
+    assert len(a) == len(b) and np.array_equal(a, b)
+    assert len(a) == max_corners or min_dist >= 10     # (larger distances and the mask leave room for fewer)
+
+
+def test_tracker_first_frame_on_white_noise_sorts_in_global_memory(gf, oracle):
+    frames = [_noise(78), _noise(78)]
+    depth = np.full(frames[0].shape, 1500, np.uint16)
+    otr = oracle.Tracker(oracle.default_cfg(max_cnt=300, min_dist=10))
+    gtr = gf.FeatureTracker(gf.default_cfg(max_cnt=300, min_dist=10))
+    for k, f in enumerate(frames):
+        oi, oo = otr.track(0.05 * k, f, depth)
+        gi, go = gtr.trackImage(0.05 * k, f, depth)
+        assert np.array_equal(oi, gi) and np.array_equal(oo.view(np.uint64), go.view(np.uint64)), k
+    assert len(gi) == 300 and gtr.stats()["select_global_sort"] >= 1
+    gtr.close()
+
+
+# wants set by removeOutliers before frame k (ids removed per sequence; "all": every track).  Sequence 5 sees a flat frame at k = 2 (it loses every track and has no
+# candidate); frame 4 wants at most 16 everywhere (select_corners_kernel is not launched); frame 5's largest want is 17, just above kTopKMax.
+_MIXED_REMOVALS = {2: [0, 1, 16, 17, "all", 0], 4: [3, 16, 0, 1, 9, 16], 5: [17, 0, 16, 2, 5, 17]}
+
+
+def _mixed_wants_batch(gf, oracle, frames=6):
+    B = 6
+    imgs = [synth.tracker_sequence(1200 + b, 1)[0] for b in range(B)]
+    flat = np.full(imgs[0].shape, 128, np.uint8)
+    depth = np.full(flat.shape, 1500, np.uint16)
+    gtr = gf.FeatureTracker(gf.default_cfg(batch=B, max_cnt=150, min_dist=20))
+    otrs = [oracle.Tracker(oracle.default_cfg(max_cnt=150, min_dist=20)) for _ in range(B)]
+    for k in range(frames):     # the same image every frame: LK loses nothing, a sequence wants exactly what was removed
+        if k in _MIXED_REMOVALS:
+            for b in range(B):
+                ids = otrs[b].state()[0]
+                r = _MIXED_REMOVALS[k][b]
+                rm = ids if r == "all" else ids[:r]
+                otrs[b].remove_outliers(rm); gtr.removeOutliers(rm, seq=b)
+        fr = [flat if (b == 5 and k == 2) else imgs[b] for b in range(B)]
+        res = gtr.trackImageBatch([0.05 * k] * B, fr, [depth] * B)
+        for b in range(B):
+            oi, oo = otrs[b].track(0.05 * k, fr[b], depth)
+            assert np.array_equal(oi, res[b][0]) and np.array_equal(oo.view(np.uint64), res[b][1].view(np.uint64)), (k, b)
+            assert len(oi) == (0 if (b == 5 and k == 2) else 150), (k, b)
+    gtr.close()
+
+
+@pytest.mark.parametrize("topk", ["1", "0"])
+def test_a_batch_of_sequences_with_mixed_wants(gf, oracle, monkeypatch, topk):
+    """The split between the two selection kernels: sequences of one batch that want 0, 1, 16 (the largest the top-k kernel serves), 17 (the smallest the sort serves),
+    every corner, and every corner without a single candidate -- then a frame in which no sequence wants more than 16 (the sort is not launched) and one whose largest
+    want is 17.  Every sequence bit for bit against its own oracle tracker."""
+    monkeypatch.setenv("GF_SELECT_TOPK", topk)
+    _mixed_wants_batch(gf, oracle)
+
+
+def test_per_table_copies_match_the_copy_lists_and_the_oracle(gf, oracle, monkeypatch):
+    """GF_TRACKER_COPIES=1: one hipMemcpyAsync per table instead of the copy-list kernels.  The same bytes reach the same buffers, so the host-image batch, the device
+    entry point and the prefetched host frames all give the oracle's bits, as the default handles do."""
+    import torch
+    B, K = 3, 4
+    seqs = [synth.tracker_sequence(60 + b, K) for b in range(B)]
+    depth = np.full(seqs[0][0].shape, 1800, np.uint16)
+    ref = []
+    for b in range(B):
+        otr = oracle.Tracker(oracle.default_cfg())
+        ref.append([otr.track(0.0666 * k, seqs[b][k], depth) for k in range(K)])
+
+    def check(k, res):
+        for b in range(B):
+            oi, oo = ref[b][k]
+            assert np.array_equal(oi, res[b][0]) and np.array_equal(oo.view(np.uint64), res[b][1].view(np.uint64)), (k, b)
+
+    for copies in ("0", "1"):
+        monkeypatch.setenv("GF_TRACKER_COPIES", copies)
+        host, dev, pre = (gf.FeatureTracker(gf.default_cfg(batch=B)) for _ in range(3))
+        host_g = [torch.from_numpy(np.stack([seqs[b][k] for b in range(B)])).pin_memory() for k in range(K)]
+        host_d = torch.from_numpy(np.stack([depth] * B).view(np.int16)).pin_memory()
+        pre.prefetchHost(host_g[0].data_ptr(), host_d.data_ptr())
+        for k in range(K):
+            check(k, host.trackImageBatch([0.0666 * k] * B, [seqs[b][k] for b in range(B)], [depth] * B))
+            dg, dd = host_g[k].cuda(), host_d.cuda()
+            torch.cuda.synchronize()
+            check(k, dev.trackImageBatchDevice([0.0666 * k] * B, dg.data_ptr(), dd.data_ptr()))
+            if k + 1 < K:
+                pre.prefetchHost(host_g[k + 1].data_ptr(), host_d.data_ptr())
+            check(k, pre.trackPrefetched([0.0666 * k] * B))
+        host.close(); dev.close(); pre.close()
