@@ -151,7 +151,7 @@ int gf_estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* c) {
     std::string err;
     if (!parse_yaml(config_file, y, err)) return gf::set_err(GF_ERR_INVALID, "%s: %s", config_file, err.c_str());
     // what the build does not carry fails here, loudly, instead of being silently ignored
-    const char* unsupported[] = {"use_line", "use_yolo", "plane", "equalize", "use_motion"};
+    const char* unsupported[] = {"use_line", "use_yolo", "plane", "use_motion"};
     for (const char* k : unsupported)
         if (y.integer(k) != 0) return gf::set_err(GF_ERR_INVALID, "%s: `%s: %d` is outside the built path (DESIGN.md, out of scope)", config_file, k, y.integer(k));
     if (y.integer("num_of_cam") != 1) return gf::set_err(GF_ERR_INVALID, "%s: num_of_cam must be 1 (RGB-D), got %d", config_file, y.integer("num_of_cam"));
@@ -210,6 +210,7 @@ int gf_estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* c) {
     t.batch = 1;
     t.max_cnt = y.integer("max_cnt"); t.min_dist = y.integer("min_dist"); t.flow_back = y.integer("flow_back");
     t.depth_cam = c->depth;
+    t.equalize = y.integer("equalize") != 0;   // EQUALIZE (parameters.cpp:169): CLAHE on every frame before trackImage (rosNodeTest.cpp:256-261)
     c->with_tracker = 1;
     // cam0_calib, relative to the directory of the config file (parameters.cpp:436-443)
     const std::string cf(config_file);

@@ -34,6 +34,12 @@
 
 namespace gf {
 
+// gf_clahe.hip: cv::CLAHE::apply on `batch` contiguous frames (gf_tracker_cfg.equalize)
+size_t clahe_lut_bytes(int batch, int tiles_x, int tiles_y);
+int clahe_launch(const uint8_t* d_src, uint8_t* d_dst, uint8_t* d_lut, int batch, int w, int h, double clip_limit, int tiles_x, int tiles_y, hipStream_t stream);
+constexpr double kClaheClip = 40.0;   // cv::createCLAHE() defaults (rosNodeTest.cpp:258)
+constexpr int kClaheTiles = 8;
+
 static thread_local std::string g_err;
 int set_err(int code, const char* fmt, ...) {
     char buf[512];
@@ -180,12 +186,13 @@ struct gf_tracker {
     int lk_points = 1;        // points per wavefront of the LK kernel: 1 (lk_track_kernel), 2 or 4 (lk_track_mp_kernel, round 6); GF_LK_POINTS
     bool profiling = false;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[8] = {};
+    hipEvent_t ev[8] = {};   // ev[7]: end of the equalisation (cfg.equalize)
     gf_tracker_stats stats{};
     std::vector<SeqState> seq;
     HostPool* pool = nullptr;
     // device
     DevBuf<uint8_t> d_img, d_raw, d_mask, d_status, d_fwd_status, d_seqmask;
+    DevBuf<uint8_t> d_eq, d_eq_lut;   // cfg.equalize: the equalised frames the pyramid reads, and the CLAHE tile LUTs
     DevBuf<int> d_npts, d_cand_count, d_want, d_ncenters, d_out_n;
     DevBuf<uint16_t> d_depth, d_depth_out, d_out_depth;
     // gf_tracker_prefetch_batch: the next frame's images on their way to the second pair of frame buffers while the current frame's kernels run
@@ -210,7 +217,7 @@ struct gf_tracker {
     size_t select_lds = 0;
 
     void release() {
-        d_raw2.release(); d_depth2.release();
+        d_raw2.release(); d_depth2.release(); d_eq.release(); d_eq_lut.release();
         for (auto& e : ev_copy) if (e) (void)hipEventDestroy(e);
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
         d_img.release(); d_raw.release(); d_mask.release(); d_status.release(); d_fwd_status.release(); d_seqmask.release(); d_npts.release();
@@ -415,6 +422,11 @@ static int track_core(gf_tracker* h, const double* t, const uint8_t* d_gray, con
         return GF_OK;
     };
     if (prof) HIPCHK(hipEventRecord(h->ev[0], h->stream));
+    if (h->cfg.equalize) {   // rosNodeTest.cpp:256-261: CLAHE on the gray frame before trackImage, into the handle's buffer (the caller's frames stay as they are)
+        if (int rc = clahe_launch(d_gray, h->d_eq.p, h->d_eq_lut.p, B, W, H, kClaheClip, kClaheTiles, kClaheTiles, h->stream)) return rc;
+        d_gray = h->d_eq.p;
+        if (prof) HIPCHK(hipEventRecord(h->ev[7], h->stream));
+    }
     if (int rc = launch_pyramid(h, d_gray)) return rc;
     if (prof) HIPCHK(hipEventRecord(h->ev[1], h->stream));
 
@@ -577,7 +589,10 @@ static int track_core(gf_tracker* h, const double* t, const uint8_t* d_gray, con
     lap(h->stats.ms_wait_detect);
     if (prof) {
         float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1])); h->stats.ms_pyramid += ms;
+        if (h->cfg.equalize) {
+            HIPCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[7])); h->stats.ms_equalize += ms;
+            HIPCHK(hipEventElapsedTime(&ms, h->ev[7], h->ev[1])); h->stats.ms_pyramid += ms;
+        } else { HIPCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1])); h->stats.ms_pyramid += ms; }
         if (lk_timed) { HIPCHK(hipEventElapsedTime(&ms, h->ev[2], h->ev[3])); h->stats.ms_lk += ms; }
         HIPCHK(hipEventElapsedTime(&ms, h->ev[4], h->ev[5])); h->stats.ms_detect += ms;
         HIPCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[5])); h->stats.ms_total_gpu += ms;
@@ -657,6 +672,7 @@ int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out) {
     *out = nullptr;
     if (cfg->width < 32 || cfg->height < 32 || cfg->width % 4 || cfg->batch < 1 || cfg->max_cnt < 1 || cfg->min_dist < 0 || cfg->min_dist > gf::kMaxRadius)
         return gf::set_err(GF_ERR_INVALID, "unsupported tracker configuration (width %% 4 == 0, width/height >= 32, 0 <= min_dist <= %d)", gf::kMaxRadius);
+    if (cfg->equalize != 0 && cfg->equalize != 1) return gf::set_err(GF_ERR_INVALID, "gf_tracker_cfg.equalize must be 0 or 1, got %d", cfg->equalize);
     if (int rc = gf::require_device()) return rc;
     gf_tracker* h = new gf_tracker();
     h->cfg = *cfg;
@@ -702,6 +718,7 @@ int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out) {
     for (auto& e : h->ev) H_(hipEventCreate(&e));
     A_(h->d_img.alloc((size_t)B * 2 * h->G.img_bytes));
     A_(h->d_raw.alloc((size_t)B * W * H));
+    if (cfg->equalize) { A_(h->d_eq.alloc((size_t)B * W * H)); A_(h->d_eq_lut.alloc(gf::clahe_lut_bytes(B, gf::kClaheTiles, gf::kClaheTiles))); }
     // (no device copy of the depth images: the host entry points sample them on the host, the device entry point reads the caller's device pointer)
     A_(h->d_mask.alloc(h->mask_stride));  // explicit masks exist only in the gf_good_features building block
     A_(h->d_eig.alloc(h->eig_stride));    // response image materialised only by gf_min_eigen_val

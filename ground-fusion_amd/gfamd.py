@@ -18,7 +18,7 @@ class TrackerCfg(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("batch", C.c_int), ("max_cnt", C.c_int), ("min_dist", C.c_int),
                 ("flow_back", C.c_int), ("depth_cam", C.c_int),
                 ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
-                ("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double)]
+                ("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double), ("equalize", C.c_int)]
 
 
 class FeatureObs(C.Structure):
@@ -30,7 +30,8 @@ class TrackerStats(C.Structure):
                 ("ms_host_pre", C.c_double), ("ms_wait_lk", C.c_double), ("ms_host_mid", C.c_double), ("ms_wait_detect", C.c_double), ("ms_host_post", C.c_double),
                 ("frames", C.c_longlong), ("lk_launches", C.c_longlong), ("lk_points", C.c_longlong),
                 ("lk_level_passes", C.c_longlong), ("lk_iterations", C.c_longlong), ("tracked_features", C.c_longlong),
-                ("output_features", C.c_longlong), ("select_streamed", C.c_longlong), ("select_global_sort", C.c_longlong)]
+                ("output_features", C.c_longlong), ("select_streamed", C.c_longlong), ("select_global_sort", C.c_longlong),
+                ("ms_equalize", C.c_double)]
 
 
 OBS_DTYPE = np.dtype([("id", np.int32), ("camera_id", np.int32), ("v", np.float64, (8,))])
@@ -39,7 +40,7 @@ assert OBS_DTYPE.itemsize == C.sizeof(FeatureObs)
 EXPORTS = ["gf_last_error", "gf_device_count", "gf_set_device", "gf_tracker_create", "gf_tracker_destroy", "gf_tracker_track",
            "gf_tracker_track_batch", "gf_tracker_track_batch_device", "gf_tracker_set_prediction", "gf_tracker_remove_outliers",
            "gf_tracker_get_state", "gf_tracker_set_profiling", "gf_tracker_get_stats", "gf_tracker_reset_stats", "gf_lk_track",
-           "gf_good_features", "gf_min_eigen_val", "gf_pyramid_level"]
+           "gf_good_features", "gf_min_eigen_val", "gf_pyramid_level", "gf_clahe_batch", "gf_clahe_batch_device"]
 
 
 def lib():
@@ -74,9 +75,9 @@ def device_count():
     return n.value
 
 
-def default_cfg(width=640, height=480, batch=1, max_cnt=150, min_dist=30, flow_back=1, depth_cam=1):
+def default_cfg(width=640, height=480, batch=1, max_cnt=150, min_dist=30, flow_back=1, depth_cam=1, equalize=0):
     return TrackerCfg(width, height, batch, max_cnt, min_dist, flow_back, depth_cam, 603.95556640625, 603.1257934570312,
-                      324.0858154296875, 232.72303771972656, 0.0, 0.0, 0.0, 0.0)
+                      324.0858154296875, 232.72303771972656, 0.0, 0.0, 0.0, 0.0, equalize)
 
 
 class FeatureTracker:
@@ -186,6 +187,24 @@ class FeatureTracker:
 
     def reset_stats(self):
         _chk(lib().gf_tracker_reset_stats(self.h))
+
+
+def clahe(frames, clip_limit=40.0, tiles=(8, 8)):
+    """cv::createCLAHE(clip_limit, Size(*tiles))->apply on u8 frames ([h, w] or [batch, h, w], host arrays) on the device; tiles = (tiles_x, tiles_y).
+    Returns a new array of the same shape."""
+    a = np.ascontiguousarray(frames, np.uint8)
+    if a.ndim not in (2, 3):
+        raise ValueError("clahe: frames must be [h, w] or [batch, h, w]")
+    b = a.reshape((-1,) + a.shape[-2:])
+    out = np.empty_like(b)
+    _chk(lib().gf_clahe_batch(_p(b, C.c_uint8), _p(out, C.c_uint8), b.shape[0], b.shape[2], b.shape[1], C.c_double(clip_limit), int(tiles[0]), int(tiles[1])))
+    return out.reshape(a.shape)
+
+
+def clahe_device(d_src, d_dst, batch, width, height, clip_limit=40.0, tiles=(8, 8), stream=0):
+    """gf_clahe_batch_device on integer device addresses (e.g. torch tensor .data_ptr()); asynchronous on `stream` (an integer hipStream_t, 0 = null stream)"""
+    _chk(lib().gf_clahe_batch_device(C.c_void_p(d_src), C.c_void_p(d_dst), batch, width, height, C.c_double(clip_limit), int(tiles[0]), int(tiles[1]),
+                                     C.c_void_p(stream) if stream else None))
 
 
 def lk_track(prev, nxt, prev_pts, next_pts=None, max_level=3):

@@ -81,6 +81,12 @@ class FeatureTracker {
     void setIntrinsics(int width, int height, double fx, double fy, double cx, double cy, double k1 = 0, double k2 = 0, double p1 = 0, double p2 = 0) {
         col = width; row = height; fx_ = fx; fy_ = fy; cx_ = cx; cy_ = cy; k1_ = k1; k2_ = k2; p1_ = p1; p2_ = p2;
     }
+    // EQUALIZE (rosNodeTest.cpp:256-261): the reference's node runs cv::createCLAHE()->apply on every frame before trackImage; the FeatureTracker class itself
+    // never does, so it stays off unless asked for.  On: the same CLAHE (clip 40, 8 x 8 tiles) runs on the device ahead of the pyramid.  Before the first frame.
+    void setEqualize(bool on) {
+        if (h_) throw std::runtime_error("setEqualize: call it before the first trackImage");
+        equalize_ = on;
+    }
 
     FeatureFrame trackImage(double _cur_time, const GrayImage& _img, const DepthImage& _img1 = DepthImage()) {
         if (!h_) create(_img.cols, _img.rows);
@@ -118,11 +124,13 @@ class FeatureTracker {
   private:
     gf_tracker* h_ = nullptr;
     double fx_ = 1, fy_ = 1, cx_ = 0, cy_ = 0, k1_ = 0, k2_ = 0, p1_ = 0, p2_ = 0;
+    bool equalize_ = false;
     static void check(int rc) { if (rc != GF_OK) throw std::runtime_error(std::string("groundfusion_hip: ") + gf_last_error()); }
     void create(int w, int h) {
         gf_tracker_cfg c{};
         c.width = col ? col : w; c.height = row ? row : h; c.batch = 1; c.max_cnt = MAX_CNT; c.min_dist = MIN_DIST; c.flow_back = FLOW_BACK; c.depth_cam = depth_cam ? 1 : 0;
         c.fx = fx_; c.fy = fy_; c.cx = cx_; c.cy = cy_; c.k1 = k1_; c.k2 = k2_; c.p1 = p1_; c.p2 = p2_;
+        c.equalize = equalize_ ? 1 : 0;
         row = c.height; col = c.width;
         check(gf_tracker_create(&c, &h_));
     }

@@ -43,6 +43,10 @@ typedef struct gf_tracker_cfg {
     int flow_back;      /* FLOW_BACK m2dgrp.yaml:136 */
     int depth_cam;      /* FeatureTracker::depth_cam, feature_tracker.h:95 */
     double fx, fy, cx, cy, k1, k2, p1, p2; /* camodocal pinhole, config/realsense/wt_cam.yaml */
+    /* EQUALIZE (m2dgrp.yaml `equalize`, rosNodeTest.cpp:256-261): 1 = cv::createCLAHE() with its defaults (clip limit 40, 8 x 8 tiles) applied to every gray
+     * frame on the device before the pyramid, into a buffer of the handle (the caller's frames, device ones included, are never modified; depth images are
+     * not touched); 0 = off (the reference's FeatureTracker itself never equalises: its node does) */
+    int equalize;
 } gf_tracker_cfg;
 
 /* One element of trackImage's return value map<int, vector<pair<int, Matrix<double,8,1>>>>
@@ -71,6 +75,7 @@ typedef struct gf_tracker_stats {
      * when min_dist is small) */
     long long select_streamed;
     long long select_global_sort;
+    double ms_equalize;          /* the CLAHE kernels of gf_tracker_cfg.equalize (hipEvents, like ms_pyramid; part of ms_total_gpu) */
 } gf_tracker_stats;
 
 int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out);
@@ -113,6 +118,14 @@ int gf_tracker_remove_outliers(gf_tracker* h, int seq, const int* ids, int n);
 int gf_tracker_get_state(gf_tracker* h, int seq, int* ids, int* track_cnt, float* prev_pts_xy, int cap, int* n);
 
 int gf_tracker_set_profiling(gf_tracker* h, int enable); /* hipEvent timing of kernels (default off) */
+
+/* Replaces `cv::createCLAHE(clip_limit, cv::Size(tiles_x, tiles_y))->apply(img, img)` on MONO8 frames (rosNodeTest.cpp:256-261, getImageFromMsg with EQUALIZE;
+ * the reference calls it with the defaults, clip 40 and 8 x 8).  `batch` frames of height x width u8, back to back; d_src == d_dst is allowed.  Same bits as
+ * OpenCV 4.2's scalar CV_8UC1 path (clahe.cpp), including the REFLECT_101 padding when the grid does not divide the frame; needs width > tiles_x and
+ * height > tiles_y, clip_limit >= 0 (0: no clipping).  Asynchronous on `stream` (a hipStream_t, NULL = the null stream); device pointers of the current device. */
+int gf_clahe_batch_device(const void* d_src, void* d_dst, int batch, int width, int height, double clip_limit, int tiles_x, int tiles_y, void* stream);
+/* The same on host frames (copies in, equalises, copies out; synchronous): the building block the parity tests call.  src == dst is allowed. */
+int gf_clahe_batch(const uint8_t* src, uint8_t* dst, int batch, int width, int height, double clip_limit, int tiles_x, int tiles_y);
 int gf_tracker_get_stats(gf_tracker* h, gf_tracker_stats* out);
 int gf_tracker_reset_stats(gf_tracker* h);
 
@@ -490,8 +503,8 @@ int gf_estimator_group_stats(gf_estimator_group* g, long long* batches, long lon
 /* readParameters(std::string config_file), vins_estimator/src/estimator/parameters.cpp:138-558, plus the cam0_calib file it names
  * (PinholeCamera::Parameters::readFromYamlFile, camera_models/src/camera_models/PinholeCamera.cc:145-183; path relative to the config
  * file's directory, parameters.cpp:436-443).  Same key names and cv::FileNode defaults (a missing numeric key reads as 0).  Fills the
- * whole cfg including cfg->tracker and sets with_tracker = 1 (gnss_enable and its gnss_* keys are read, parameters.cpp:519-552).  Options
- * outside the built path (use_line, use_yolo, plane, equalize, use_motion, num_of_cam 2, estimate_extrinsic 2,
+ * whole cfg including cfg->tracker and sets with_tracker = 1 (gnss_enable and its gnss_* keys are read, parameters.cpp:519-552).  `equalize`
+ * (EQUALIZE, parameters.cpp:169; any non-zero value switches it on) sets cfg->tracker.equalize to 1.  Options outside the built path (use_line, use_yolo, plane, use_motion, num_of_cam 2, estimate_extrinsic 2,
  * gnss_local_online_sync) return GF_ERR_INVALID instead of being ignored. */
 int gf_estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* cfg);
 /* the line pubOdometry appends to VINS_RESULT_PATH (utility/visualization.cpp:346-357): "t x y z qx qy qz qw", fixed, 9 decimals;
