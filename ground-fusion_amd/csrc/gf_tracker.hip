@@ -281,18 +281,23 @@ static int launch_pyramid(gf_tracker* h, const uint8_t* d_raw_frames) {
     // levels 0 and 1 from one read of the raw frame (pyr_head_kernel) when the sizes allow it; GF_PYR_HEAD=0 keeps the two kernels (A/B and fallback)
     const bool head = h->pyr_head && v16 && vec && G.nlevels >= 2 && !(g0.h & 1) && G.lv[1].h * 2 == g0.h && G.lv[1].w * 2 == g0.w && g0.h > kPad + 2 && g0.w > kPad + 2 &&
                       pyr_head_lds_bytes(g0.w) <= 64 * 1024;
+    gf_tracker_stats& st = h->stats;
     if (head) {
+        st.pyr_head++;
         pyr_head_kernel<<<dim3((G.lv[1].h + kHeadRows - 1) / kHeadRows, h->B), 512, pyr_head_lds_bytes(g0.w), h->stream>>>(d_raw_frames, (size_t)g0.w * g0.h, g0.w, img, seq_img, g0, G.lv[1]);
     } else if (v16) {
+        st.pyr_level0_vec16++;
         const int n = ((g0.w + 2 * kPad) / 16) * (g0.h + 2 * kPad);
         pyr_level0_vec16_kernel<<<dim3((n + 255) / 256, h->B), 256, 0, h->stream>>>(d_raw_frames, (size_t)g0.w * g0.h, g0.w, img, seq_img, g0);
     } else {
+        st.pyr_level0_dword++;
         const int n = ((g0.w + 2 * kPad) / 4) * (g0.h + 2 * kPad);
         pyr_level0_kernel<<<dim3((n + 255) / 256, h->B), 256, 0, h->stream>>>(d_raw_frames, (size_t)g0.w * g0.h, g0.w, img, seq_img, g0);
     }
     if (vec) {
         auto down = [&](int l) {
             const LevelGeom d = G.lv[l];
+            st.pyr_down_pad4++;
             pyr_down_pad4_kernel<<<dim3(((d.w >> 2) * d.h + 255) / 256, h->B), 256, 0, h->stream>>>(img, seq_img, G.lv[l - 1], d);
         };
         if (G.nlevels > 1 && !head) down(1);
@@ -301,13 +306,14 @@ static int launch_pyramid(gf_tracker* h, const uint8_t* d_raw_frames) {
             const LevelGeom d = G.lv[2], e = G.lv[last];
             const int band = last > 2 ? (e.h + parts - 1) / parts + 1 : ((d.h + 1) / 2 + parts - 1) / parts + 1;
             const size_t lds = (size_t)(2 * band + 4) * d.w + (last > 2 ? (size_t)band * e.w : 0);
-            if (G.nlevels <= 4 && lds <= 64 * 1024) pyr_down_tail_kernel<<<dim3(parts, h->B), 512, lds, h->stream>>>(img, seq_img, G, 2);
+            if (G.nlevels <= 4 && lds <= 64 * 1024) { st.pyr_down_tail++; pyr_down_tail_kernel<<<dim3(parts, h->B), 512, lds, h->stream>>>(img, seq_img, G, 2); }
             else for (int l = 2; l < G.nlevels; l++) down(l);
         }
     } else {
         for (int l = 1; l < G.nlevels; l++) {
             const LevelGeom d = G.lv[l];
             const int n = (d.w + 2 * kPad) * (d.h + 2 * kPad);
+            st.pyr_down_bytes++;
             pyr_down_kernel<<<dim3((n + 255) / 256, h->B), 256, 0, h->stream>>>(img, seq_img, G.lv[l - 1], d);
         }
     }

@@ -31,7 +31,8 @@ class TrackerStats(C.Structure):
                 ("frames", C.c_longlong), ("lk_launches", C.c_longlong), ("lk_points", C.c_longlong),
                 ("lk_level_passes", C.c_longlong), ("lk_iterations", C.c_longlong), ("tracked_features", C.c_longlong),
                 ("output_features", C.c_longlong), ("select_streamed", C.c_longlong), ("select_global_sort", C.c_longlong),
-                ("ms_equalize", C.c_double)]
+                ("ms_equalize", C.c_double), ("pyr_head", C.c_longlong), ("pyr_level0_vec16", C.c_longlong), ("pyr_level0_dword", C.c_longlong),
+                ("pyr_down_tail", C.c_longlong), ("pyr_down_pad4", C.c_longlong), ("pyr_down_bytes", C.c_longlong)]
 
 
 OBS_DTYPE = np.dtype([("id", np.int32), ("camera_id", np.int32), ("v", np.float64, (8,))])
@@ -111,19 +112,25 @@ class FeatureTracker:
         """batch == 1 convenience: returns (ids, obs[n,8])."""
         return self.trackImageBatch([t], [img], None if depth is None else [depth])[0]
 
-    def trackImageBatch(self, ts, imgs, depths=None):
+    def _pitched(self, a, dtype, pitch):
+        """a height x width image whose rows lie `pitch` elements apart (a view of a wider array, e.g. a cropped frame): passed as it is, not copied"""
+        assert a.dtype == dtype and a.shape == (self.cfg.height, self.cfg.width) and a.strides == (pitch * a.itemsize, a.itemsize), (a.shape, a.strides, pitch)
+        return a
+
+    def trackImageBatch(self, ts, imgs, depths=None, stride=None, dstride=None):
+        """stride / dstride: row pitch of the gray (bytes) / depth (u16 elements) images, for frames with padded rows (cv::Mat::step); default: contiguous rows"""
         B = self.cfg.batch
         ts = np.ascontiguousarray(ts, np.float64)
-        imgs = [np.ascontiguousarray(i, np.uint8) for i in imgs]
+        imgs = [np.ascontiguousarray(i, np.uint8) for i in imgs] if stride is None else [self._pitched(i, np.uint8, stride) for i in imgs]
         gp = (C.POINTER(C.c_uint8) * B)(*[_p(i, C.c_uint8) for i in imgs])
         if depths is not None:
-            depths = [np.ascontiguousarray(d, np.uint16) for d in depths]
+            depths = [np.ascontiguousarray(d, np.uint16) for d in depths] if dstride is None else [self._pitched(d, np.uint16, dstride) for d in depths]
             dp = (C.POINTER(C.c_uint16) * B)(*[_p(d, C.c_uint16) for d in depths])
         else:
             dp = None
         out = np.zeros((B, self.cap), OBS_DTYPE)
         n = np.zeros(B, np.int32)
-        _chk(lib().gf_tracker_track_batch(self.h, _p(ts, C.c_double), gp, self.cfg.width, dp, self.cfg.width,
+        _chk(lib().gf_tracker_track_batch(self.h, _p(ts, C.c_double), gp, stride or self.cfg.width, dp, dstride or self.cfg.width,
                                           out.ctypes.data_as(C.POINTER(FeatureObs)), self.cap, _p(n, C.c_int)))
         return self._unpack(out, n)
 
@@ -143,13 +150,20 @@ class FeatureTracker:
                                                  out.ctypes.data_as(C.POINTER(FeatureObs)), self.cap, _p(n_out, C.c_int)))
         return self._unpack(out, n_out) if unpack else n_out
 
-    def prefetchHost(self, gray_addr, depth_addr=None):
+    def prefetchHost(self, gray_addr, depth_addr=None, stride=None, dstride=None):
         """gf_tracker_prefetch_batch on a block of `batch` frames lying back to back in (page-locked) host memory: gray_addr / depth_addr = integer host addresses
-        of batch x height x width u8 / u16 images; the copy runs on the tracker's copy stream while the frame in flight is processed"""
-        B, n = self.cfg.batch, self.cfg.width * self.cfg.height
-        gp = (C.POINTER(C.c_uint8) * B)(*[C.cast(gray_addr + b * n, C.POINTER(C.c_uint8)) for b in range(B)])
-        dp = (C.POINTER(C.c_uint16) * B)(*[C.cast(depth_addr + 2 * b * n, C.POINTER(C.c_uint16)) for b in range(B)]) if depth_addr else None
-        _chk(lib().gf_tracker_prefetch_batch(self.h, gp, self.cfg.width, dp, self.cfg.width))
+        of batch x height x width u8 / u16 images; the copy runs on the tracker's copy stream while the frame in flight is processed.  gray_addr / depth_addr may
+        also be lists of `batch` addresses (one image each, anywhere).  stride / dstride: row pitch in bytes / u16 elements (default: the width)"""
+        B, H = self.cfg.batch, self.cfg.height
+        stride, dstride = stride or self.cfg.width, dstride or self.cfg.width
+        ga = list(gray_addr) if isinstance(gray_addr, (list, tuple)) else [gray_addr + b * stride * H for b in range(B)]
+        gp = (C.POINTER(C.c_uint8) * B)(*[C.cast(a, C.POINTER(C.c_uint8)) for a in ga])
+        if depth_addr:
+            da = list(depth_addr) if isinstance(depth_addr, (list, tuple)) else [depth_addr + 2 * b * dstride * H for b in range(B)]
+            dp = (C.POINTER(C.c_uint16) * B)(*[C.cast(a, C.POINTER(C.c_uint16)) for a in da])
+        else:
+            dp = None
+        _chk(lib().gf_tracker_prefetch_batch(self.h, gp, stride, dp, dstride))
 
     def trackPrefetched(self, ts, unpack=True):
         B = self.cfg.batch

@@ -76,6 +76,10 @@ typedef struct gf_tracker_stats {
     long long select_streamed;
     long long select_global_sort;
     double ms_equalize;          /* the CLAHE kernels of gf_tracker_cfg.equalize (hipEvents, like ms_pyramid; part of ms_total_gpu) */
+    /* launches of each pyramid form, counted on the host where the pyramid is launched (the form follows the frame size, the pointers' alignment and GF_PYR_HEAD):
+     * pyr_head: levels 0 + 1 in one kernel; pyr_level0_vec16 / pyr_level0_dword: level 0 alone in 16- / 4-byte pieces; pyr_down_tail: levels 2 .. 3 in one kernel;
+     * pyr_down_pad4: one level >= 1 in four-pixel pieces; pyr_down_bytes: one level >= 1 one byte per thread */
+    long long pyr_head, pyr_level0_vec16, pyr_level0_dword, pyr_down_tail, pyr_down_pad4, pyr_down_bytes;
 } gf_tracker_stats;
 
 int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out);
