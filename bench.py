@@ -7,9 +7,11 @@ independent 640x480 RGBD+IMU+wheel sequences owned by this GPU advances by one f
   back end   Estimator::optimization()    (8 dogleg iterations of the 10-frame / 150-feature window + MARGIN_OLD prior).
 One process per GPU.  Sequences are independent, so they are sharded across ranks with no data-path collective (weak
 scaling); the one exchange north_star names -- the gather of the newest pose of every sequence over RCCL -- is part of every
-timed step.  After the timed region the three roofline kernels are timed again on an otherwise idle GPU (tracker alone, back
-end alone), and rank 0 at N = 1 runs two bounded side measurements: the end-to-end drop-in path (trackImage -> inputFeature ->
-processImage -> solve -> marginalise through gf_estimator_group_*) and the CPU oracle.
+timed step.  A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the JSON line.
+Everything else is measured with --full only: after the timed region the three roofline kernels are timed again on an otherwise
+idle GPU (tracker alone, back end alone), and rank 0 at N = 1 adds a 200-step run, the host-image path, other batch sizes, other
+configurations, the end-to-end drop-in path (trackImage -> inputFeature -> processImage -> solve -> marginalise through
+gf_estimator_group_*) and the CPU oracle.
 """
 import argparse
 import json
@@ -561,7 +563,7 @@ def dump_outputs(path, trk, est, wins, poses):
     print("bench.py: %d arrays, %.1f MB, %d of %d sequences -> %s" % (len(out), total / 2**20, len(seqs), B, path), file=sys.stderr, flush=True)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -575,6 +577,9 @@ def main():
     ap.add_argument("--max-cnt", type=int, default=None)
     ap.add_argument("--min-dist", type=int, default=None)
     ap.add_argument("--ba-iters", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the timed steps: the isolated kernel passes and roofline figures, and at N = 1 the 200-step run, the host-image, "
+                         "batch-size, other-config and end-to-end samples and the CPU baseline (the --no-* options below leave parts of it out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-frontend", action="store_true")
     ap.add_argument("--no-backend", action="store_true")
@@ -588,14 +593,18 @@ def main():
     ap.add_argument("--no-large-batch", action="store_true", help="skip the step times at 512 / 1024 sequences per GPU")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the 20-step kernel-rate samples of configs[2] and configs[4]")
     ap.add_argument("--no-long-run", action="store_true", help="skip the extra 200-step run next to a short timed loop")
-    ap.add_argument("--e2e-device-preint", action="store_true", help="also run the end-to-end sample with the batched device pre-integration of the estimator group")
-    ap.add_argument("--e2e-device-sweeps", action="store_true", help="also run the end-to-end sample with the batched device feature sweeps (triangulateWithDepth, movingConsistencyCheckW) of the estimator group")
+    ap.add_argument("--e2e-device-preint", action="store_true", help="with --full: also run the end-to-end sample with the batched device pre-integration of the estimator group (with --e2e-only: run it that way)")
+    ap.add_argument("--e2e-device-sweeps", action="store_true", help="with --full: also run the end-to-end sample with the batched device feature sweeps (triangulateWithDepth, movingConsistencyCheckW) of the estimator group (with --e2e-only: run it that way)")
     ap.add_argument("--e2e-only", action="store_true", help="only the end-to-end (drop-in path) sample, as one JSON line (used by the default run for its small-host sample)")
     ap.add_argument("--host-threads", type=int, default=0, help="with --e2e-only: confine this process to the first N hardware threads (sched_setaffinity) and size the worker pools for them")
     ap.add_argument("--no-small-host", action="store_true", help="skip the end-to-end sample on 8 hardware threads")
     ap.add_argument("--small-host-all", action="store_true", help="the 8-thread end-to-end sample with one estimator group as well (default: two alternating groups only)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0; see dump_outputs)")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
 
     if args.e2e_only:
         if args.host_threads > 0:   # the host BASELINE.md plans for: everything this process runs (tracker bookkeeping pool, group workers, Python) shares N hardware threads
@@ -618,6 +627,7 @@ def main():
         print(json.dumps(warm))
         return
 
+    t_phase = [time.perf_counter()]     # the phases printed on stderr start here: the setup of the timed steps is the first of them
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -690,14 +700,12 @@ def main():
                 gathered[0] = pose_gather(newest)
         step[0] += 1
 
-    t_phase = [time.perf_counter()]
-
     def phase(name):   # where the wall clock of the whole run goes (stderr; the JSON line stays the only thing on stdout)
         now = time.perf_counter()
         if rank == 0:
             print("bench.py: %-28s %6.1f s" % (name, now - t_phase[0]), file=sys.stderr, flush=True)
         t_phase[0] = now
-    phase("setup (frames, windows)")
+    phase("setup (device, frames, windows)")
     for _ in range(Wm + 1):  # frame 0 only detects; it is part of the warm-up
         do_step()
     trk.reset_stats()
@@ -723,7 +731,7 @@ def main():
     # the driver's command times 20 steps (57 ms): box-to-box and host jitter are larger than that sample resolves (round-5 review), so the same loop once more over 200
     # steps, reported next to `value` (N = 1 only: the driver's own multi-GPU lines stay what its command measures)
     long_run = None
-    if world == 1 and K < 200 and not args.no_long_run and not (args.no_frontend or args.no_backend):
+    if args.full and world == 1 and K < 200 and not args.no_long_run and not (args.no_frontend or args.no_backend):
         s0 = est.stats()["solves"]
         barrier()
         t1 = time.perf_counter()
@@ -736,7 +744,7 @@ def main():
 
     # the roofline kernels once more on an otherwise idle GPU: their hipEvent times without the other half's kernels in between
     iso = {}
-    if not args.no_frontend and not args.no_backend:
+    if args.full and not args.no_frontend and not args.no_backend:
         trk.reset_stats(); est.reset_stats()
         for _ in range(4):
             trk.trackImageBatchDevice([dt * step[0]] * B, frames.data_ptr() + frame_index(step[0]) * frame_bytes, depth.data_ptr(), unpack=False)
@@ -791,6 +799,7 @@ def main():
         jtj_alg = bs["jtj_alg_flops"] / max(bs["jtj_launches"], 1)
         jtj_issued = bs["jtj_flops"] / max(bs["jtj_launches"], 1)
         jtj_t = iso.get("jtj_ms", jtj_ms)      # kernel time on an idle GPU when available (the in-region span includes waiting for CUs held by tracker kernels)
+        ba_roofline = bool(iso) or args.no_frontend or args.no_backend    # a plain run of both halves has no idle-GPU times of the back end: no roofline_jtj / _step
         step_t = iso.get("step_ms", step_ms)
         tf = lambda fl, ms: fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
         lk_pmc = pmc.get("lk_track_kernel", {})
@@ -838,7 +847,7 @@ def main():
                              "algorithmic_flops_per_launch": jtj_alg, "issued_mfma_flops_per_launch": jtj_issued, "frac_issued": tf(jtj_issued, jtj_t) / FP64_MFMA_PEAK_TF,
                              "mfma_utilisation_pmc": pmc.get("ba_linearize_visual_win", {}).get("mfma_utilisation") if args.config == 1 and B == 256 else None,   # the PMC passes ran configs[1] at 256 windows
                              "note": "algorithmic flops = Nv*2*2*91 per window (SURVEY.md 8d); issued = 2048 per v_mfma_f64_16x16x4_f64 (16-column tiles, 13 used); the kernel also "
-                                     "evaluates every factor's residual / Jacobian (FP64 VALU), reduces the pair tiles and builds the E^T F rows; " + pmc.get("ba_linearize_visual_win", {}).get("note", "")},
+                                     "evaluates every factor's residual / Jacobian (FP64 VALU), reduces the pair tiles and builds the E^T F rows; " + pmc.get("ba_linearize_visual_win", {}).get("note", "")} if ba_roofline else None,
             "roofline_jtj_split": None if "split" not in iso else {
                 "kernel": "ba_linearize_visual_win<MODE 2> (contraction only) behind <MODE 1> (sweep -> block rows in HBM)", "bound": "mfma",
                 "achieved": tf(jtj_alg, iso["split"]["contraction_ms"]), "peak": FP64_MFMA_PEAK_TF, "unit": "TFLOP/s", "frac": tf(jtj_alg, iso["split"]["contraction_ms"]) / FP64_MFMA_PEAK_TF,
@@ -854,18 +863,18 @@ def main():
                               "launch_ms": step_t, "launch_ms_in_timed_region": step_ms, "flops_per_launch": step_flops,
                               "mfma_utilisation_pmc": pmc.get("ba_step", {}).get("mfma_utilisation") if args.config == 1 and B == 256 else None,
                               "note": "largest kernel by time; algorithmic flops = Schur SYRK NE*n_c^2 + Cholesky R^3/3 + substitutions 2R^2 per window; one block per window, "
-                                      "bound by the latency of R/16 sequential 16x16 factor+inverse blocks, not by MFMA issue"},
+                                      "bound by the latency of R/16 sequential 16x16 factor+inverse blocks, not by MFMA issue"} if ba_roofline else None,
             "ba_summary_seq0": sums[0],
             "kernel_source_sha16": kernel_source_sha16(), "pmc_summary": pmc.get("_stale", "profiles/pmc_summary.json matches this tree's kernel sources"),
         }
-        phase("isolated passes")
-        if world == 1 and not args.no_pcie and not args.strong and not (args.no_frontend or args.no_backend):
+        phase("isolated passes" if args.full else "result line")
+        if args.full and world == 1 and not args.no_pcie and not args.strong and not (args.no_frontend or args.no_backend):
             res["pcie_inclusive"] = pcie_sample(gfamd, trk, est, args, B, frames, depth, dt, step, frame_index)
             phase("pcie_inclusive")
-        if world == 1 and not args.no_small_batch and not args.strong and not (args.no_frontend or args.no_backend):
+        if args.full and world == 1 and not args.no_small_batch and not args.strong and not (args.no_frontend or args.no_backend):
             res["small_batch"] = small_batch_sample(gfamd, dev, args, WIN, GNSS)
             phase("small_batch")
-        if world == 1 and not args.no_large_batch and not args.strong and args.config == 1 and B == 256 and not (args.no_frontend or args.no_backend):
+        if args.full and world == 1 and not args.no_large_batch and not args.strong and args.config == 1 and B == 256 and not (args.no_frontend or args.no_backend):
             # round-5 review: "256 sequences per GPU is the builder's number" -- the same step with two and four windows per CU resident
             lb = small_batch_sample(gfamd, dev, args, WIN, GNSS, sizes=(512, 1024), K=20, distinct=64)
             for k_, v_ in lb.items():
@@ -888,7 +897,7 @@ def main():
                 else:
                     os.environ["GF_BA_CHAIN"] = had
             phase("large_batch")
-        if world == 1 and not args.no_other_configs and not args.strong and args.config == 1 and not (args.no_frontend or args.no_backend):
+        if args.full and world == 1 and not args.no_other_configs and not args.strong and args.config == 1 and not (args.no_frontend or args.no_backend):
             res["other_configs"] = {}
             for ci in (2, 4):
                 try:
@@ -896,7 +905,7 @@ def main():
                 except Exception as ex:   # a side measurement: its failure must not cost the line
                     res["other_configs"]["configs[%d]" % ci] = {"error": repr(ex)[:300]}
             phase("other_configs")
-        if world == 1 and not args.no_e2e and not args.strong and args.config == 1 and not (args.no_frontend or args.no_backend):
+        if args.full and world == 1 and not args.no_e2e and not args.strong and args.config == 1 and not (args.no_frontend or args.no_backend):
             trk.close(); trk = None
             S = max(1, args.e2e_streams)
             cold = end_to_end_sample(gfamd, args.e2e_seqs, dev, args.max_cnt, args.min_dist, n_streams=S, n_groups=args.e2e_groups, stagger=not args.e2e_same_frames)
@@ -948,8 +957,9 @@ def main():
                                 os.environ.pop(k_, None)
                             else:
                                 os.environ[k_] = v_
-        phase("end_to_end samples")
-        if not args.no_cpu_baseline and world == 1:   # the CPU leg is an N = 1 measurement (the other ranks would sit in the closing barrier meanwhile)
+        if args.full:
+            phase("end_to_end samples")
+        if args.full and not args.no_cpu_baseline and world == 1:   # the CPU leg is an N = 1 measurement (the other ranks would sit in the closing barrier meanwhile)
             nseq = min(8, B)
             cores = min(os.cpu_count() or 1, nseq)
             fh = frames[: min(n_frames, 13), :nseq].cpu().numpy()
@@ -962,7 +972,8 @@ def main():
                                              "(variant a x %d cores); then sequence 0 once more as variant b; %.1f s wall, ~%.0f s of CPU work; box shows %d hardware threads, %d usable under its CPU quota"
                                              % (nseq, cb["repeat"], fh.shape[0], cb["repeat"] * max(1, fh.shape[0] // 4), cb["build"], cores, cores, cb["wall_s"], cb["wall_s"] * cores, os.cpu_count() or 1, usable_cpus()),
                                    "detail": cb}
-        phase("cpu_baseline")
+        if args.full:
+            phase("cpu_baseline")
         print(json.dumps(res))
     if trk is not None:
         trk.close()

@@ -1,14 +1,16 @@
 #!/bin/bash
-# usage: scripts/prof_bench.sh <tag>  -- untraced bench line + rocprofv3 kernel trace of the default bench (run on the GPU box from the repo root)
+# usage: scripts/prof_bench.sh <tag> [out_dir]  -- untraced bench line + rocprofv3 kernel trace of the whole bench (--full), from the repo root on a machine with an MI355X;
+# the files go to out_dir (default: prof_out/ in the repo root)
 tag=$1
 R=${GRAFT_REPO_ROOT:-$(pwd)}
-mkdir -p $R/gpurun_out
+out=$(realpath -m "${2:-$R/prof_out}")
+mkdir -p "$out"
 cd $R
-python bench.py --no-cpu-baseline > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err
+python bench.py --full --no-cpu-baseline > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -- python $R/bench.py --no-cpu-baseline > $R/gpurun_out/${tag}_bench_traced.json 2> $R/gpurun_out/${tag}_prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -- python $R/bench.py --full --no-cpu-baseline > "$out/${tag}_bench_traced.json" 2> "$out/${tag}_prof.err"
 f=$(find /tmp/prof_$tag -name "*kernel_stats.csv" | head -1)
-python - "$f" > $R/gpurun_out/${tag}_kernel_stats.csv <<'P'
+python - "$f" > "$out/${tag}_kernel_stats.csv" <<'P'
 import sys, csv
 rows = list(csv.reader(open(sys.argv[1])))
 print(",".join('"%s"' % c for c in rows[0]))

@@ -5,7 +5,7 @@ running, with one of this library's families running alone, and with both famili
   python scripts/step_timeline.py /tmp/tl [steps]
 
 The timed region is taken as the span of the LAST `steps` launches of lk_track_kernel (one per step) up to the end of the last back-end kernel behind them -- before the
-isolated passes bench.py appends (those run one family at a time and are cut off at the first gap of more than 20 ms)."""
+isolated passes bench.py appends with --full (those run one family at a time and are cut off at the first gap of more than 20 ms)."""
 import csv
 import glob
 import sys
