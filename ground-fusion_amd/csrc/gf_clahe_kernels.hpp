@@ -7,6 +7,8 @@
 //   clahe_apply_kernel  one workgroup per (band of rows, frame): the band's LUT tile rows staged in LDS, bilinear blend of the four tile LUTs around each pixel.
 // Every float expression below is written in the order the OpenCV scalar code evaluates it; the translation unit is compiled with -ffp-contract=off (build.py),
 // so nothing is fused and the results are the same bits.
+// Inside the tracker a "frame" is a position in the call's sequence list (gf_lk_kernels.hpp): source frames, equalised frames and LUTs all belong to the call and
+// none of them is kept per sequence, so both passes run over the first `count` frames of their buffers and need no table to find them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -72,12 +72,15 @@ __host__ __device__ __forceinline__ float f32_from_orderable(unsigned k) {
 // 3x3 local-maximum candidates.  The response image never touches HBM.  The mask is either an explicit
 // u8 image (building-block entry point) or, in trackImage, the union of filled circles of radius MIN_DIST
 // around the kept points, tested analytically with OpenCV's midpoint-circle row table (no rasterised mask).
+// grid.z = position i in the call's sequence list (gf_lk_kernels.hpp); only the image is addressed by sequence, every table is [count] by position.
 struct DetectArgs {
-    const uint8_t* pyr; size_t pyr_seq_stride; LevelGeom g;
+    // all pyramids; frame_of[i]: the one holding the frame to search (2 * sequence + slot, the LK kernels' cur_of[i]), or < 0 for a list position that needs no new
+    // corners.  One table for both questions: a strip is short work and there are 45 000 of them per 256 VGA frames, so a second dependent load at the head of
+    // each (want[i], then the image) cost the kernel 2.6 %.
+    const uint8_t* pyr; size_t pyr_bytes; const int* frame_of; LevelGeom g;
     const uint8_t* mask; size_t mask_seq_stride;            // optional explicit mask (non-zero = allowed)
     const int2* centers; const int* n_centers; int cap;     // else: disks
-    const int* want;                                        // [batch] skip sequences that need no new corners
-    unsigned* maxkey;                                       // [batch] orderable max over unmasked pixels (0 = none)
+    unsigned* maxkey;                                       // [count] orderable max over unmasked pixels (0 = none)
     unsigned long long* cand; size_t cand_seq_stride; int cand_cap; int* cand_count;
 };
 
@@ -113,7 +116,8 @@ __global__ void __launch_bounds__(64) detect_strip_kernel(DetectArgs A, DiskTabl
     __shared__ unsigned long long ckeys[kCap];
     __shared__ short s_hw[kMaxRadius + 1];
     const int b = blockIdx.z;
-    if (A.want[b] <= 0) return;
+    const int cur = list_entry(A.frame_of, b);
+    if (cur < 0) return;
     const LevelGeom g = A.g;
     const int lane = threadIdx.x;
     const int X0 = blockIdx.x * kDS_W, Y0 = blockIdx.y * R;
@@ -167,7 +171,7 @@ __global__ void __launch_bounds__(64) detect_strip_kernel(DetectArgs A, DiskTabl
     const unsigned long long need_prod = need_eig | (need_eig << 1) | (need_eig >> 1);
     const unsigned long long need_raw = need_prod | (need_prod << 1) | (need_prod >> 1);
 
-    const uint8_t* img = A.pyr + b * A.pyr_seq_stride + g.img_off;
+    const uint8_t* img = A.pyr + (size_t)cur * A.pyr_bytes + g.img_off;
     const float f1 = (float)(1.0 * (1.0 / (4.0 * 3.0 * 255.0))), f0 = (float)(2.0 * (1.0 / (4.0 * 3.0 * 255.0)));
     // every raw row of the strip in flight at once: bytes x - 1 .. x + 2 of rows Y0 - 3 ..; columns / rows past the ones an output needs are clamped into the border
     uint32_t raw[NS];
@@ -254,16 +258,18 @@ __global__ void __launch_bounds__(64) detect_strip_kernel(DetectArgs A, DiskTabl
     if (n_cand) strip_flush(cand_b, count_b, A.cand_cap, ckeys, n_cand, lane);
 }
 
+// Both selection kernels run one block per list position and touch only tables of the call ([count], by position): the candidates, want, the output and the
+// call's depth frames.  Nothing here is kept per sequence, so the same list reaches both by construction.
 struct SelectArgs {
     unsigned long long* cand; size_t cand_seq_stride; int cand_cap;
     const int* cand_count;
-    const unsigned* maxkey;  // [batch] orderable masked maximum (threshold = 0.01 * max, THRESH_TOZERO)
-    const int* want;         // [batch] maxCorners for this frame (<=0: none)
+    const unsigned* maxkey;  // [count] orderable masked maximum (threshold = 0.01 * max, THRESH_TOZERO)
+    const int* want;         // [count] maxCorners for this frame (<=0: none)
     int w, h, min_dist, out_cap;
     int sort_cap;            // keys that fit the LDS sort area (power of two <= kSortLds)
-    float2* out_pts;         // [batch][out_cap]
-    uint16_t* out_depth;     // [batch][out_cap]
-    int* out_n;              // [batch]
+    float2* out_pts;         // [count][out_cap]
+    uint16_t* out_depth;     // [count][out_cap]
+    int* out_n;              // [count]
     const uint16_t* depth; size_t depth_seq_stride; int depth_stride;
     int skip_small;          // sequences that want <= kTopKMax corners have been served by select_topk_kernel
 };

@@ -40,10 +40,22 @@ __device__ __forceinline__ int reflect101(int p, int len) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// The sequence list.  A call serves `count` of the handle's sequences; the block coordinate that used to be the sequence (grid.y here and in LK, grid.z in the
+// detector) is the position i in the call's list.  What belongs to the call -- raw frames, depth frames, every hand-over table, the candidate lists -- is indexed
+// by i.  What a sequence keeps between calls is its pair of pyramids, pyr[2 * seq] and pyr[2 * seq + 1] of pyr_bytes each, and which of the two holds its newest
+// frame is that sequence's own bit, flipped only when it takes a frame.  Both travel as one table: cur_of[i] = 2 * seq_of[i] + (slot the new frame of seq_of[i]
+// goes to); the previous frame of the same sequence is cur_of[i] ^ 1.  The index is the same for a whole block, so it is one load and no per-lane work.
+__device__ __forceinline__ int list_entry(const int* __restrict__ table, unsigned i) {
+    // The value is wavefront-uniform; saying so keeps every address derived from it in scalar registers.  Left to itself the compiler loads the entry per lane in
+    // the kernels that also write through a pointer (it cannot use the scalar cache there) and then carries the image base in vector registers: pyr_down_tail_kernel
+    // went from 36 to 94 VGPRs and from 8 to 5 wavefronts per SIMD that way.
+    return __builtin_amdgcn_readfirstlane(table[i]);
+}
+
 // Level 0: copy the raw frame into the padded pyramid and synthesise the REFLECT_101 border.
-// One thread per 4 destination bytes; grid.y = sequence.
+// One thread per 4 destination bytes; grid.y = list position.
 __global__ void __launch_bounds__(256) pyr_level0_kernel(const uint8_t* __restrict__ raw, size_t raw_seq_stride, int raw_stride,
-                                                         uint8_t* __restrict__ pyr, size_t pyr_seq_stride, LevelGeom g) {
+                                                         uint8_t* __restrict__ pyr, size_t pyr_bytes, const int* __restrict__ cur_of, LevelGeom g) {
     const int pw = g.w + 2 * kPad, ph = g.h + 2 * kPad;
     const int qw = pw >> 2;
     int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -56,14 +68,14 @@ __global__ void __launch_bounds__(256) pyr_level0_kernel(const uint8_t* __restri
 #pragma unroll
         for (int k = 0; k < 4; k++) v |= (uint32_t)src[reflect101(px + k - kPad, g.w)] << (8 * k);
     }
-    uint8_t* dst = pyr + blockIdx.y * pyr_seq_stride + g.img_off - kPad * g.stride - kPad;
+    uint8_t* dst = pyr + (size_t)list_entry(cur_of, blockIdx.y) * pyr_bytes + g.img_off - kPad * g.stride - kPad;
     *reinterpret_cast<uint32_t*>(dst + (size_t)py * g.stride + px) = v;
 }
 
 // The same with 16 destination bytes per thread, for frames whose width, row pitch and base address are multiples of 16 (640 x 480: every interior group
 // is one aligned 16-byte load and one aligned 16-byte store; the 2 x 2 border groups of a row gather their mirror bytes).
 __global__ void __launch_bounds__(256) pyr_level0_vec16_kernel(const uint8_t* __restrict__ raw, size_t raw_seq_stride, int raw_stride,
-                                                               uint8_t* __restrict__ pyr, size_t pyr_seq_stride, LevelGeom g) {
+                                                               uint8_t* __restrict__ pyr, size_t pyr_bytes, const int* __restrict__ cur_of, LevelGeom g) {
     const int pw = g.w + 2 * kPad, ph = g.h + 2 * kPad;
     const int qw = pw >> 4;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -78,19 +90,19 @@ __global__ void __launch_bounds__(256) pyr_level0_vec16_kernel(const uint8_t* __
         for (int k = 0; k < 16; k++) w4[k >> 2] |= (uint32_t)src[reflect101(px + k - kPad, g.w)] << (8 * (k & 3));
         v = make_uint4(w4[0], w4[1], w4[2], w4[3]);
     }
-    uint8_t* dst = pyr + blockIdx.y * pyr_seq_stride + g.img_off - kPad * g.stride - kPad;
+    uint8_t* dst = pyr + (size_t)list_entry(cur_of, blockIdx.y) * pyr_bytes + g.img_off - kPad * g.stride - kPad;
     *reinterpret_cast<uint4*>(dst + (size_t)py * g.stride + px) = v;
 }
 
 // pyrDown (5-tap [1 4 6 4 1] separable, (s+128)>>8) from level l to l+1, written over the whole padded
 // domain of level l+1 (border pixels are the REFLECT_101 images of interior ones, recomputed in place).  Any level size.
-__global__ void __launch_bounds__(256) pyr_down_kernel(uint8_t* __restrict__ pyr, size_t pyr_seq_stride, LevelGeom s, LevelGeom d) {
+__global__ void __launch_bounds__(256) pyr_down_kernel(uint8_t* __restrict__ pyr, size_t pyr_bytes, const int* __restrict__ cur_of, LevelGeom s, LevelGeom d) {
     const int pw = d.w + 2 * kPad, ph = d.h + 2 * kPad;
     int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= pw * ph) return;
     int py = t / pw, px = t - py * pw;
     int x = reflect101(px - kPad, d.w), y = reflect101(py - kPad, d.h);
-    uint8_t* base = pyr + blockIdx.y * pyr_seq_stride;
+    uint8_t* base = pyr + (size_t)list_entry(cur_of, blockIdx.y) * pyr_bytes;
     const uint8_t* sp = base + s.img_off + (size_t)(2 * y - 2) * s.stride + (2 * x - 2);
     int acc = 0;
 #pragma unroll
@@ -152,12 +164,12 @@ __device__ __forceinline__ uint32_t pyr_down_one(const uint8_t* __restrict__ bas
 // kPad of an edge is also the source of border pixels (its mirror images across that edge, and across the corner): the thread that computed it
 // stores them too -- row mirrors as dwords, column mirrors as bytes (their dword would straddle an alignment boundary).  No pixel is filtered
 // twice and nothing is read back.  Needs d.w, d.h > kPad (one reflection reaches every border pixel) and d.w a multiple of 4.
-__global__ void __launch_bounds__(256) pyr_down_pad4_kernel(uint8_t* __restrict__ pyr, size_t pyr_seq_stride, LevelGeom s, LevelGeom d) {
+__global__ void __launch_bounds__(256) pyr_down_pad4_kernel(uint8_t* __restrict__ pyr, size_t pyr_bytes, const int* __restrict__ cur_of, LevelGeom s, LevelGeom d) {
     const int qw = d.w >> 2;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= qw * d.h) return;
     const int y = t / qw, x = (t - y * qw) << 2;
-    uint8_t* base = pyr + blockIdx.y * pyr_seq_stride;
+    uint8_t* base = pyr + (size_t)list_entry(cur_of, blockIdx.y) * pyr_bytes;
     const uint32_t v = pyr_down_quad(base, s, y, x);
     uint8_t* img = base + d.img_off;
     // rows this pixel row is mirrored to: y itself, -y (1 <= y <= kPad), 2(h-1)-y (h-1-kPad <= y <= h-2)
@@ -219,9 +231,9 @@ __device__ __forceinline__ void write_padded_rows(uint8_t* __restrict__ base, co
 // the rows of level `first` under it.  It filters the rows of level `first` it needs (band + 2 halo rows, 1.1x the work) from global memory into
 // LDS, writes its own rows of that level with their borders, filters its band of the next level from LDS and writes that with its borders.
 // Global memory is only written, never read back: no fence between the phases (a device-scope fence writes the whole L2 back: 250 us per launch).
-__global__ void __launch_bounds__(512) pyr_down_tail_kernel(uint8_t* __restrict__ pyr, size_t pyr_seq_stride, PyrGeom G, int first) {
+__global__ void __launch_bounds__(512) pyr_down_tail_kernel(uint8_t* __restrict__ pyr, size_t pyr_bytes, const int* __restrict__ cur_of, PyrGeom G, int first) {
     extern __shared__ __attribute__((aligned(16))) uint8_t pyr_sm[];
-    uint8_t* base = pyr + blockIdx.y * pyr_seq_stride;
+    uint8_t* base = pyr + (size_t)list_entry(cur_of, blockIdx.y) * pyr_bytes;
     const LevelGeom s = G.lv[first - 1], d = G.lv[first];
     const bool two = first + 1 < G.nlevels;
     const LevelGeom e = G.lv[two ? first + 1 : first];
@@ -261,7 +273,7 @@ __global__ void __launch_bounds__(512) pyr_down_tail_kernel(uint8_t* __restrict_
 constexpr int kHeadRows = 16;
 __host__ __device__ inline size_t pyr_head_lds_bytes(int w0) { return (size_t)(2 * kHeadRows + 3) * (w0 + 8) + (size_t)kHeadRows * (w0 / 2); }
 __global__ void __launch_bounds__(512) pyr_head_kernel(const uint8_t* __restrict__ raw, size_t raw_seq_stride, int raw_stride,
-                                                       uint8_t* __restrict__ pyr, size_t pyr_seq_stride, LevelGeom g0, LevelGeom g1) {
+                                                       uint8_t* __restrict__ pyr, size_t pyr_bytes, const int* __restrict__ cur_of, LevelGeom g0, LevelGeom g1) {
     extern __shared__ __attribute__((aligned(16))) uint8_t head_sm[];
     const int tid = threadIdx.x;
     const int r0 = blockIdx.x * kHeadRows, r1 = min(g1.h, r0 + kHeadRows);   // this block's rows of level 1
@@ -270,7 +282,7 @@ __global__ void __launch_bounds__(512) pyr_head_kernel(const uint8_t* __restrict
     uint8_t* A = head_sm;
     uint8_t* Bq = head_sm + (size_t)(2 * kHeadRows + 3) * SA;               // the band of level 1, no borders
     const uint8_t* src = raw + blockIdx.y * raw_seq_stride;
-    uint8_t* base = pyr + blockIdx.y * pyr_seq_stride;
+    uint8_t* base = pyr + (size_t)list_entry(cur_of, blockIdx.y) * pyr_bytes;
     {
         const int qi = g0.w >> 4;
         for (int t = tid; t < qi * nrow; t += 512) {
@@ -601,27 +613,27 @@ __device__ __forceinline__ int lk_solve(const PyrGeom& G, const LkImages im, flo
 }
 
 struct LkBatchArgs {
-    const uint8_t* img;   // [batch][2 slots] image pyramids
-    int prev_slot;        // slot holding the previous frame; cur = 1 - prev_slot
+    const uint8_t* img;   // [batch][2 slots] image pyramids, by sequence; every other table below is [count] by list position
+    const int* cur_of;    // [count] pyramid of the new frame: 2 * sequence + its slot; the previous frame is cur_of[i] ^ 1
     int cap;              // per-sequence capacity of the point arrays
-    const int* n_pts;     // [batch]
-    const float2* prev_pts;  // [batch][cap]
-    const float2* init_pts;  // [batch][cap] predicted points (mode 1) or unused
-    float2* cur_pts;      // [batch][cap] out
-    uint8_t* status;      // [batch][cap] out: after fwd, reverse check, inBorder and brightness test
-    uint8_t* fwd_status;  // [batch][cap] out: status of the forward pass alone (feature_tracker.cpp:124-130 counts these)
-    uint16_t* depth_out;  // [batch][cap] out: depth(round(y),round(x)) for status==1 (0 if no depth)
-    const uint16_t* depth;   // [batch] raw depth frames (may be null)
+    const int* n_pts;     // [count]
+    const float2* prev_pts;  // [count][cap]
+    const float2* init_pts;  // [count][cap] predicted points (mode 1) or unused
+    float2* cur_pts;      // [count][cap] out
+    uint8_t* status;      // [count][cap] out: after fwd, reverse check, inBorder and brightness test
+    uint8_t* fwd_status;  // [count][cap] out: status of the forward pass alone (feature_tracker.cpp:124-130 counts these)
+    uint16_t* depth_out;  // [count][cap] out: depth(round(y),round(x)) for status==1 (0 if no depth)
+    const uint16_t* depth;   // [count] raw depth frames (may be null)
     size_t depth_seq_stride; int depth_stride;
-    unsigned* counters;   // [batch][cap][2] out: level passes, iterations
+    unsigned* counters;   // [count][cap][2] out: level passes, iterations
     int fwd_max_level;    // 3 (feature_tracker.cpp:132,135) or 1 (hasPrediction, :121)
     int fwd_use_init;     // OPTFLOW_USE_INITIAL_FLOW from init_pts (hasPrediction)
     int flow_back;        // reverse LK + 0.5 px check (:138-153)
     int post_checks;      // inBorder + brightness test (:155-168)
-    const uint8_t* seq_mask; // optional [batch]: process only sequences with mask!=0 (fallback relaunch)
+    const uint8_t* seq_mask; // optional [count]: process only list positions with mask!=0 (fallback relaunch)
 };
 
-// grid.x = ceil(cap/4) blocks of 4 wavefronts, grid.y = sequence.  Forward LK (feature_tracker.cpp:118-135),
+// grid.x = ceil(cap/4) blocks of 4 wavefronts, grid.y = list position.  Forward LK (feature_tracker.cpp:118-135),
 // reverse LK and flow-back test (:138-153), inBorder and the brightness test with the reference's swapped
 // row/column indexing (:155-168).
 __global__ void __launch_bounds__(256, 7) lk_track_kernel(PyrGeom G, LkBatchArgs A) {
@@ -635,8 +647,9 @@ __global__ void __launch_bounds__(256, 7) lk_track_kernel(PyrGeom G, LkBatchArgs
     const size_t pi = (size_t)b * A.cap + i;
     float2 pp = A.prev_pts[pi];
     pp.x = unif(pp.x); pp.y = unif(pp.y);
-    const uint8_t* prevI = A.img + ((size_t)b * 2 + A.prev_slot) * G.img_bytes;
-    const uint8_t* curI = A.img + ((size_t)b * 2 + (1 - A.prev_slot)) * G.img_bytes;
+    const int cur = list_entry(A.cur_of, b);
+    const uint8_t* prevI = A.img + (size_t)(cur ^ 1) * G.img_bytes;
+    const uint8_t* curI = A.img + (size_t)cur * G.img_bytes;
     unsigned n_levels = 0, n_iters = 0;
     float cx, cy;
     int st;
@@ -909,7 +922,7 @@ __device__ __forceinline__ int lk_solve_mp(const PyrGeom& G, const uint8_t* imI,
     return status;
 }
 
-// P points per wavefront, four wavefronts per block: grid.x = ceil(cap / (4 P)), grid.y = sequence.  Same outputs as lk_track_kernel, bit for bit.
+// P points per wavefront, four wavefronts per block: grid.x = ceil(cap / (4 P)), grid.y = list position.  Same outputs as lk_track_kernel, bit for bit.
 template <int P>
 __global__ void __launch_bounds__(256, P == 4 ? 2 : 3) lk_track_mp_kernel(PyrGeom G, LkBatchArgs A) {
     __shared__ __attribute__((aligned(16))) uint8_t tiles[4 * P * kTileBytes];
@@ -925,8 +938,9 @@ __global__ void __launch_bounds__(256, P == 4 ? 2 : 3) lk_track_mp_kernel(PyrGeo
     uint8_t* tile = tiles + wave * P * kTileBytes;
     const size_t pi = (size_t)b * A.cap + min(i, n - 1);
     const float2 pp = A.prev_pts[pi];
-    const uint8_t* prevI = A.img + ((size_t)b * 2 + A.prev_slot) * G.img_bytes;
-    const uint8_t* curI = A.img + ((size_t)b * 2 + (1 - A.prev_slot)) * G.img_bytes;
+    const int cur = list_entry(A.cur_of, b);
+    const uint8_t* prevI = A.img + (size_t)(cur ^ 1) * G.img_bytes;
+    const uint8_t* curI = A.img + (size_t)cur * G.img_bytes;
     unsigned n_levels = 0, n_iters = 0;
     float cx, cy;
     if (A.fwd_use_init) { const float2 ip = A.init_pts[pi]; cx = ip.x; cy = ip.y; } else { cx = 0.f; cy = 0.f; }

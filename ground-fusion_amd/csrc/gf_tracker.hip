@@ -1,7 +1,7 @@
 // gf_tracker.hip — C-ABI front end (include/groundfusion_hip.h): host orchestration of the HIP tracker.
 //
 // Mirrors FeatureTracker (vins_estimator/src/featureTracker/feature_tracker.{h,cpp}) for `batch`
-// independent sequences driven in lock-step on one GPU stream.  Host keeps exactly the bookkeeping the
+// independent sequences on one GPU stream; a call advances the sequences it lists (track_core), the lock-step entry points list them all.  Host keeps exactly the bookkeeping the
 // reference keeps in C++ (ids, track_cnt, n_id, maps for velocity; setMask's std::sort + greedy keep,
 // feature_tracker.cpp:56-83); all image work (pyramids, Scharr, LK forward/reverse, mask rasterisation,
 // Shi-Tomasi, candidate sort and min-distance selection, depth sampling) runs in the kernels of
@@ -68,6 +68,7 @@ struct SeqState {  // per-sequence FeatureTracker members (feature_tracker.h:76-
     double cur_time = 0, prev_time = 0;
     int n_id = 0;
     bool hasPrediction = false;
+    int slot = 1;   // which of the sequence's two pyramids holds its newest frame; flipped when the sequence takes a frame, and only then (the first frame goes to 0)
 };
 
 // Small persistent pool for the per-sequence host bookkeeping (sequences are independent).  GF_HOST_THREADS overrides the size.
@@ -179,7 +180,7 @@ struct gf_tracker {
     gf_tracker_cfg cfg;
     PyrGeom G;
     DiskTable disk;
-    int B = 0, cap = 0, cand_cap = 0, frame = 0, cur_slot = 0, sort_cap = 0;
+    int B = 0, cap = 0, cand_cap = 0, sort_cap = 0;
     bool copy_lists = true;   // GF_TRACKER_COPIES=1: one hipMemcpyAsync per table instead of the copy-list kernels
     bool pyr_head = true;     // GF_PYR_HEAD=0: levels 0 and 1 of the pyramid as two kernels (read when the tracker is created, as the other switches)
     bool select_topk = true;  // GF_SELECT_TOPK=0: every frame's corners through the sort
@@ -194,11 +195,18 @@ struct gf_tracker {
     DevBuf<uint8_t> d_img, d_raw, d_mask, d_status, d_fwd_status, d_seqmask;
     DevBuf<uint8_t> d_eq, d_eq_lut;   // cfg.equalize: the equalised frames the pyramid reads, and the CLAHE tile LUTs
     DevBuf<int> d_npts, d_cand_count, d_want, d_ncenters, d_out_n;
+    // the call's sequence list as the kernels read it (cur_of, gf_lk_kernels.hpp): written into the page-locked h_cur, which the pyramid kernels read over the bus
+    // (they are launched before anything is copied), and carried to d_cur for LK by the copy list in front of it
+    DevBuf<int> d_cur; PinBuf<int> h_cur;
+    DevBuf<int> d_det; PinBuf<int> h_det;   // the detector's form of the list (DetectArgs::frame_of): the same entry, or -1 where the sequence wants no corners
+    std::vector<int> ident;          // 0 .. batch-1: the list of the lock-step entry points
+    std::vector<uint8_t> listed;     // scratch of check_list
     DevBuf<uint16_t> d_depth, d_depth_out, d_out_depth;
     // gf_tracker_prefetch_batch: the next frame's images on their way to the second pair of frame buffers while the current frame's kernels run
     DevBuf<uint8_t> d_raw2; DevBuf<uint16_t> d_depth2;
     hipStream_t copy_stream = nullptr; hipEvent_t ev_copy[2] = {nullptr, nullptr};
     int pf_head = 0, pf_count = 0;   // FIFO of staged frames over the two pairs (0: d_raw / d_depth, 1: d_raw2 / d_depth2): oldest pair, number staged (0..2)
+    std::vector<int> pf_seq[2];      // the sequences each staged frame holds, in the order of its images (two staged frames may name different sets)
     bool pf_depth[2] = {false, false};
     std::vector<const uint16_t*> pf_hdepth[2]; int pf_hdstride[2] = {0, 0};   // the staged frames' depth images (host; sampled by track_core, never copied)
     DevBuf<float2> d_prev_pts, d_init_pts, d_cur_pts, d_out_pts;
@@ -217,7 +225,7 @@ struct gf_tracker {
     size_t select_lds = 0;
 
     void release() {
-        d_raw2.release(); d_depth2.release(); d_eq.release(); d_eq_lut.release();
+        d_raw2.release(); d_depth2.release(); d_eq.release(); d_eq_lut.release(); d_cur.release(); h_cur.release(); d_det.release(); h_det.release();
         for (auto& e : ev_copy) if (e) (void)hipEventDestroy(e);
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
         d_img.release(); d_raw.release(); d_mask.release(); d_status.release(); d_fwd_status.release(); d_seqmask.release(); d_npts.release();
@@ -268,10 +276,11 @@ template <class V> static void reduce_vector(std::vector<V>& v, const uint8_t* s
 
 // buildOpticalFlowPyramid in three launches: level 0 (copy + REFLECT_101 border), level 1 (interior + border in one pass), and one kernel for
 // all remaining levels.  There is no derivative pyramid: lk_solve evaluates the Scharr derivative of the template window itself.
-static int launch_pyramid(gf_tracker* h, const uint8_t* d_raw_frames) {
+// d_raw_frames: `count` frames back to back, frame i for the sequence at list position i; cur_of[i]: the pyramid it is written to (device-readable, [count]).
+static int launch_pyramid(gf_tracker* h, const uint8_t* d_raw_frames, int count, const int* cur_of) {
     const PyrGeom& G = h->G;
-    const size_t seq_img = 2 * G.img_bytes;
-    uint8_t* img = h->d_img.p + (size_t)h->cur_slot * G.img_bytes;
+    const size_t seq_img = G.img_bytes;   // distance between two pyramids, whichever sequence and slot they belong to
+    uint8_t* img = h->d_img.p;
     const LevelGeom g0 = G.lv[0];
     const bool v16 = !((g0.w | g0.stride | (int)(((size_t)g0.w * g0.h) & 15) | (int)(seq_img & 15) | (int)((g0.img_off - kPad * g0.stride - kPad) & 15)) & 15) &&
                      !((reinterpret_cast<uintptr_t>(d_raw_frames) | reinterpret_cast<uintptr_t>(img)) & 15);
@@ -284,21 +293,21 @@ static int launch_pyramid(gf_tracker* h, const uint8_t* d_raw_frames) {
     gf_tracker_stats& st = h->stats;
     if (head) {
         st.pyr_head++;
-        pyr_head_kernel<<<dim3((G.lv[1].h + kHeadRows - 1) / kHeadRows, h->B), 512, pyr_head_lds_bytes(g0.w), h->stream>>>(d_raw_frames, (size_t)g0.w * g0.h, g0.w, img, seq_img, g0, G.lv[1]);
+        pyr_head_kernel<<<dim3((G.lv[1].h + kHeadRows - 1) / kHeadRows, count), 512, pyr_head_lds_bytes(g0.w), h->stream>>>(d_raw_frames, (size_t)g0.w * g0.h, g0.w, img, seq_img, cur_of, g0, G.lv[1]);
     } else if (v16) {
         st.pyr_level0_vec16++;
         const int n = ((g0.w + 2 * kPad) / 16) * (g0.h + 2 * kPad);
-        pyr_level0_vec16_kernel<<<dim3((n + 255) / 256, h->B), 256, 0, h->stream>>>(d_raw_frames, (size_t)g0.w * g0.h, g0.w, img, seq_img, g0);
+        pyr_level0_vec16_kernel<<<dim3((n + 255) / 256, count), 256, 0, h->stream>>>(d_raw_frames, (size_t)g0.w * g0.h, g0.w, img, seq_img, cur_of, g0);
     } else {
         st.pyr_level0_dword++;
         const int n = ((g0.w + 2 * kPad) / 4) * (g0.h + 2 * kPad);
-        pyr_level0_kernel<<<dim3((n + 255) / 256, h->B), 256, 0, h->stream>>>(d_raw_frames, (size_t)g0.w * g0.h, g0.w, img, seq_img, g0);
+        pyr_level0_kernel<<<dim3((n + 255) / 256, count), 256, 0, h->stream>>>(d_raw_frames, (size_t)g0.w * g0.h, g0.w, img, seq_img, cur_of, g0);
     }
     if (vec) {
         auto down = [&](int l) {
             const LevelGeom d = G.lv[l];
             st.pyr_down_pad4++;
-            pyr_down_pad4_kernel<<<dim3(((d.w >> 2) * d.h + 255) / 256, h->B), 256, 0, h->stream>>>(img, seq_img, G.lv[l - 1], d);
+            pyr_down_pad4_kernel<<<dim3(((d.w >> 2) * d.h + 255) / 256, count), 256, 0, h->stream>>>(img, seq_img, cur_of, G.lv[l - 1], d);
         };
         if (G.nlevels > 1 && !head) down(1);
         if (G.nlevels > 2) {
@@ -306,7 +315,7 @@ static int launch_pyramid(gf_tracker* h, const uint8_t* d_raw_frames) {
             const LevelGeom d = G.lv[2], e = G.lv[last];
             const int band = last > 2 ? (e.h + parts - 1) / parts + 1 : ((d.h + 1) / 2 + parts - 1) / parts + 1;
             const size_t lds = (size_t)(2 * band + 4) * d.w + (last > 2 ? (size_t)band * e.w : 0);
-            if (G.nlevels <= 4 && lds <= 64 * 1024) { st.pyr_down_tail++; pyr_down_tail_kernel<<<dim3(parts, h->B), 512, lds, h->stream>>>(img, seq_img, G, 2); }
+            if (G.nlevels <= 4 && lds <= 64 * 1024) { st.pyr_down_tail++; pyr_down_tail_kernel<<<dim3(parts, count), 512, lds, h->stream>>>(img, seq_img, cur_of, G, 2); }
             else for (int l = 2; l < G.nlevels; l++) down(l);
         }
     } else {
@@ -314,14 +323,22 @@ static int launch_pyramid(gf_tracker* h, const uint8_t* d_raw_frames) {
             const LevelGeom d = G.lv[l];
             const int n = (d.w + 2 * kPad) * (d.h + 2 * kPad);
             st.pyr_down_bytes++;
-            pyr_down_kernel<<<dim3((n + 255) / 256, h->B), 256, 0, h->stream>>>(img, seq_img, G.lv[l - 1], d);
+            pyr_down_kernel<<<dim3((n + 255) / 256, count), 256, 0, h->stream>>>(img, seq_img, cur_of, G.lv[l - 1], d);
         }
     }
     HIPCHK(hipGetLastError());
     return GF_OK;
 }
 
-static void launch_lk(gf_tracker* h, int batch, const LkBatchArgs& A) {   // one LK launch over `batch` sequences in the form the handle was created for (same results in every form)
+// the one-shot building blocks at the end of the file: one frame into pyramid `slot` (0 or 1) of their batch-1 handle; d_cur[0] names it for the kernels that follow
+static int launch_pyramid_one(gf_tracker* h, const uint8_t* d_raw_frame, int slot) {
+    HIPCHK(hipStreamSynchronize(h->stream));   // h_cur may still be read by an earlier launch of the same helper
+    h->h_cur.p[0] = slot;
+    HIPCHK(hipMemcpyAsync(h->d_cur.p, h->h_cur.p, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    return launch_pyramid(h, d_raw_frame, 1, h->d_cur.p);
+}
+
+static void launch_lk(gf_tracker* h, int batch, const LkBatchArgs& A) {   // one LK launch over the `batch` listed sequences in the form the handle was created for (same results in every form)
     const int cap = h->cap;
     if (h->lk_points == 4) lk_track_mp_kernel<4><<<dim3((cap + 15) / 16, batch), 256, 0, h->stream>>>(h->G, A);
     else if (h->lk_points == 2) lk_track_mp_kernel<2><<<dim3((cap + 7) / 8, batch), 256, 0, h->stream>>>(h->G, A);
@@ -331,7 +348,7 @@ static void launch_lk(gf_tracker* h, int batch, const LkBatchArgs& A) {   // one
 static LkBatchArgs lk_args(gf_tracker* h, int fwd_max_level, int use_init, int flow_back, int post_checks, const uint8_t* seqmask,
                            const uint16_t* d_depth) {
     LkBatchArgs A{};
-    A.img = h->d_img.p; A.prev_slot = 1 - h->cur_slot; A.cap = h->cap;
+    A.img = h->d_img.p; A.cur_of = h->d_cur.p; A.cap = h->cap;
     A.n_pts = h->d_npts.p; A.prev_pts = h->d_prev_pts.p; A.init_pts = h->d_init_pts.p; A.cur_pts = h->d_cur_pts.p;
     A.status = h->d_status.p; A.fwd_status = h->d_fwd_status.p; A.depth_out = h->d_depth_out.p; A.depth = d_depth;
     A.depth_seq_stride = (size_t)h->cfg.width * h->cfg.height; A.depth_stride = h->cfg.width;
@@ -395,20 +412,41 @@ static void pts_velocity(SeqState& s) {  // feature_tracker.cpp:810-847
     } else for (size_t i = 0; i < n; i++) s.pts_velocity[i] = {0.f, 0.f};
 }
 
-// hdep (host entry points): the callers' depth images, one pointer per sequence, rows of hdstride pixels.  The reference reads ONE pixel of the depth image per
+// The list of a call: `count` distinct sequences of the handle, in any order.  Checked before anything is copied, launched or changed.
+static int check_list(gf_tracker* h, int count, const int* seq) {
+    if (count < 0 || count > h->B) return set_err(GF_ERR_INVALID, "%d sequences listed for a handle of %d", count, h->B);
+    if (count > 0 && !seq) return set_err(GF_ERR_INVALID, "null sequence list");
+    h->listed.assign(h->B, 0);
+    for (int i = 0; i < count; i++) {
+        if (seq[i] < 0 || seq[i] >= h->B) return set_err(GF_ERR_INVALID, "list entry %d names sequence %d of a handle of %d", i, seq[i], h->B);
+        if (h->listed[seq[i]]) return set_err(GF_ERR_INVALID, "sequence %d is listed twice", seq[i]);
+        h->listed[seq[i]] = 1;
+    }
+    return GF_OK;
+}
+
+// One frame for each of the `count` listed sequences (seq: checked by check_list); sequences that are not listed keep their whole state.  Everything the caller hands
+// in or gets back (t, the frames behind d_gray / d_depth / hdep, out, n_out) and every hand-over table of the handle is indexed by the position i in the list, so the
+// work and the bytes of a call follow `count`; only h->seq[] and the pyramid pairs are indexed by the sequence seq[i].
+//
+// hdep (host entry points): the callers' depth images, one pointer per listed sequence, rows of hdstride pixels.  The reference reads ONE pixel of the depth image per
 // feature (feature_tracker.cpp:360 `rightImg.at<ushort>(round(y), round(x))`), and on the host-image entry points both the image and the feature coordinates are on
 // the host anyway: sampling there keeps 614 KB per frame and sequence (two thirds of an RGB-D VGA frame) off the bus.  d_depth (device entry point) keeps the sample
 // in the kernels.  Same pixel, same rounding (round half away from zero on the float coordinates), same u16.
-static int track_core(gf_tracker* h, const double* t, const uint8_t* d_gray, const uint16_t* d_depth, gf_feature_obs* out, int cap_out,
+static int track_core(gf_tracker* h, int count, const int* seq, const double* t, const uint8_t* d_gray, const uint16_t* d_depth, gf_feature_obs* out, int cap_out,
                       int* n_out, const uint16_t* const* hdep = nullptr, int hdstride = 0) {
-    const int B = h->B, cap = h->cap, W = h->cfg.width, H = h->cfg.height;
+    const int N = count, cap = h->cap, W = h->cfg.width, H = h->cfg.height;
+    if (N == 0) return GF_OK;
     const bool have_depth = d_depth != nullptr || hdep != nullptr;
     const bool prof = h->profiling;
-    h->cur_slot = h->frame & 1;
     using clk = std::chrono::steady_clock;
     auto tp = clk::now();
     auto lap = [&](double& acc) { auto n = clk::now(); acc += std::chrono::duration<double, std::milli>(n - tp).count(); tp = n; };
-    for (int b = 0; b < B; b++) { h->seq[b].cur_time = t[b]; h->seq[b].cur_pts.clear(); h->seq[b].cur_depth.clear(); }
+    for (int i = 0; i < N; i++) {
+        SeqState& s = h->seq[seq[i]];
+        s.cur_time = t[i]; s.cur_pts.clear(); s.cur_depth.clear();
+        h->h_cur.p[i] = 2 * seq[i] + (s.slot ^ 1);   // the new frame goes to the sequence's other pyramid; s.slot itself moves when the frame is done
+    }
     // The hand-overs between the host's bookkeeping and the kernels -- two to four small tables down before LK, five up behind it, three down before the detection, four
     // up behind it -- as one copy-list kernel each (gf_copy_list.hpp) instead of one hipMemcpyAsync per table: sixteen submissions and copy latencies per frame become four.
     gfcopy::Builder CL;
@@ -427,52 +465,60 @@ static int track_core(gf_tracker* h, const double* t, const uint8_t* d_gray, con
         if (lists) { if (!CL.ok) return set_err(GF_ERR_HIP, "copy list: a page-locked buffer is not mapped into the device's address space (GF_TRACKER_COPIES=1 selects plain copies)"); HIPCHK(CL.launch<1>(h->stream)); CL = gfcopy::Builder(); }
         return GF_OK;
     };
+    // The list has to be readable on the device before the pyramid, which is launched before the first copy list so that it runs under the host's table filling.
+    // No extra submission and no synchronisation: the pyramid kernels read the page-locked table itself (one scalar load per block, as the copy-list kernels read
+    // their sources), and the copy list in front of LK brings it to d_cur for that kernel, which is bound by instruction issue and should find it in the L2 (the
+    // detector gets its own form, h_det, with its other tables).  With plain copies (GF_TRACKER_COPIES=1) it is one more copy, in front of the pyramid.
+    const bool over_bus = lists && h->h_cur.hd;
+    if (!over_bus) HIPCHK(hipMemcpyAsync(h->d_cur.p, h->h_cur.p, (size_t)N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    const int* cur_of = over_bus ? h->h_cur.hd : h->d_cur.p;
     if (prof) HIPCHK(hipEventRecord(h->ev[0], h->stream));
-    if (h->cfg.equalize) {   // rosNodeTest.cpp:256-261: CLAHE on the gray frame before trackImage, into the handle's buffer (the caller's frames stay as they are)
-        if (int rc = clahe_launch(d_gray, h->d_eq.p, h->d_eq_lut.p, B, W, H, kClaheClip, kClaheTiles, kClaheTiles, h->stream)) return rc;
+    if (h->cfg.equalize) {   // rosNodeTest.cpp:256-261: CLAHE on the gray frame before trackImage, into the handle's buffer (the caller's frames stay as they are); frames and LUTs by list position
+        if (int rc = clahe_launch(d_gray, h->d_eq.p, h->d_eq_lut.p, N, W, H, kClaheClip, kClaheTiles, kClaheTiles, h->stream)) return rc;
         d_gray = h->d_eq.p;
         if (prof) HIPCHK(hipEventRecord(h->ev[7], h->stream));
     }
-    if (int rc = launch_pyramid(h, d_gray)) return rc;
+    if (int rc = launch_pyramid(h, d_gray, N, cur_of)) return rc;
     if (prof) HIPCHK(hipEventRecord(h->ev[1], h->stream));
 
     // ---- temporal optical flow (feature_tracker.cpp:113-176)
     bool any_prev = false, any_pred = false, any_plain = false;
-    for (int b = 0; b < B; b++) {
-        SeqState& s = h->seq[b];
+    for (int i = 0; i < N; i++) {
+        SeqState& s = h->seq[seq[i]];
         const int n = (int)s.prev_pts.size();
-        h->h_npts.p[b] = n;
-        if (n > cap) return set_err(GF_ERR_CAPACITY, "sequence %d holds %d points > capacity %d", b, n, cap);
-        for (int i = 0; i < n; i++) h->h_prev_pts.p[(size_t)b * cap + i] = make_float2(s.prev_pts[i].x, s.prev_pts[i].y);
+        h->h_npts.p[i] = n;
+        if (n > cap) return set_err(GF_ERR_CAPACITY, "sequence %d holds %d points > capacity %d", seq[i], n, cap);
+        for (int k = 0; k < n; k++) h->h_prev_pts.p[(size_t)i * cap + k] = make_float2(s.prev_pts[k].x, s.prev_pts[k].y);
         if (n > 0) {
             any_prev = true;
-            if (s.hasPrediction && (int)s.predict_pts.size() != n) return set_err(GF_ERR_INVALID, "sequence %d: prediction holds %d points but %d are tracked (call removeOutliers before setPrediction, estimator.cpp:1134-1135)", b, (int)s.predict_pts.size(), n);
-            if (s.hasPrediction) { any_pred = true; for (int i = 0; i < n; i++) h->h_init_pts.p[(size_t)b * cap + i] = make_float2(s.predict_pts[i].x, s.predict_pts[i].y); }
+            if (s.hasPrediction && (int)s.predict_pts.size() != n) return set_err(GF_ERR_INVALID, "sequence %d: prediction holds %d points but %d are tracked (call removeOutliers before setPrediction, estimator.cpp:1134-1135)", seq[i], (int)s.predict_pts.size(), n);
+            if (s.hasPrediction) { any_pred = true; for (int k = 0; k < n; k++) h->h_init_pts.p[(size_t)i * cap + k] = make_float2(s.predict_pts[k].x, s.predict_pts[k].y); }
             else any_plain = true;
         }
     }
     bool lk_timed = false;
     if (any_prev) {
-        down(h->d_npts, h->h_npts, B);
-        down(h->d_prev_pts, h->h_prev_pts, (size_t)B * cap);
+        if (over_bus) down(h->d_cur, h->h_cur, N);
+        down(h->d_npts, h->h_npts, N);
+        down(h->d_prev_pts, h->h_prev_pts, (size_t)N * cap);
         const uint8_t* mask_plain = nullptr; const uint8_t* mask_pred = nullptr;
         if (any_pred) {
-            down(h->d_init_pts, h->h_init_pts, (size_t)B * cap);
-            for (int b = 0; b < B; b++) { h->h_seqmask.p[b] = h->seq[b].hasPrediction ? 0 : 1; h->h_seqmask.p[B + b] = h->seq[b].hasPrediction ? 1 : 0; }
-            down(h->d_seqmask, h->h_seqmask, 2 * (size_t)B);
-            mask_plain = h->d_seqmask.p; mask_pred = h->d_seqmask.p + B;
+            down(h->d_init_pts, h->h_init_pts, (size_t)N * cap);
+            for (int i = 0; i < N; i++) { const bool pred = h->seq[seq[i]].hasPrediction; h->h_seqmask.p[i] = pred ? 0 : 1; h->h_seqmask.p[N + i] = pred ? 1 : 0; }
+            down(h->d_seqmask, h->h_seqmask, 2 * (size_t)N);
+            mask_plain = h->d_seqmask.p; mask_pred = h->d_seqmask.p + N;
         }
         if (int rc = flush()) return rc;
         if (prof) HIPCHK(hipEventRecord(h->ev[2], h->stream));
-        if (any_plain) { launch_lk(h, B, lk_args(h, 3, 0, h->cfg.flow_back, 1, mask_plain, d_depth)); h->stats.lk_launches++; }
-        if (any_pred) { launch_lk(h, B, lk_args(h, 1, 1, h->cfg.flow_back, 1, mask_pred, d_depth)); h->stats.lk_launches++; }
+        if (any_plain) { launch_lk(h, N, lk_args(h, 3, 0, h->cfg.flow_back, 1, mask_plain, d_depth)); h->stats.lk_launches++; }
+        if (any_pred) { launch_lk(h, N, lk_args(h, 1, 1, h->cfg.flow_back, 1, mask_pred, d_depth)); h->stats.lk_launches++; }
         HIPCHK(hipGetLastError());
         if (prof) { HIPCHK(hipEventRecord(h->ev[3], h->stream)); lk_timed = true; }
-        up(h->h_cur_pts, h->d_cur_pts, (size_t)B * cap);
-        up(h->h_status, h->d_status, (size_t)B * cap);
-        up(h->h_fwd_status, h->d_fwd_status, (size_t)B * cap);
-        up(h->h_depth_out, h->d_depth_out, (size_t)B * cap);
-        up(h->h_counters, h->d_counters, (size_t)B * cap * 2);
+        up(h->h_cur_pts, h->d_cur_pts, (size_t)N * cap);
+        up(h->h_status, h->d_status, (size_t)N * cap);
+        up(h->h_fwd_status, h->d_fwd_status, (size_t)N * cap);
+        up(h->h_depth_out, h->d_depth_out, (size_t)N * cap);
+        up(h->h_counters, h->d_counters, (size_t)N * cap * 2);
         if (int rc = flush()) return rc;
     }
     HIPCHK(hipEventRecord(h->ev[6], h->stream));
@@ -480,48 +526,48 @@ static int track_core(gf_tracker* h, const double* t, const uint8_t* d_gray, con
     HIPCHK(hipEventSynchronize(h->ev[6]));
     lap(h->stats.ms_wait_lk);
 
-    if (any_pred) {  // feature_tracker.cpp:124-132: fewer than 10 forward successes -> redo with 3 levels from scratch
+    if (any_pred) {  // feature_tracker.cpp:124-132: fewer than 10 forward successes -> redo with 3 levels from scratch (per listed sequence: its neighbours in the call keep their pass)
         bool need = false;
-        for (int b = 0; b < B; b++) {
-            h->h_seqmask.p[b] = 0;
-            if (!h->seq[b].hasPrediction || h->h_npts.p[b] == 0) continue;
+        for (int i = 0; i < N; i++) {
+            h->h_seqmask.p[i] = 0;
+            if (!h->seq[seq[i]].hasPrediction || h->h_npts.p[i] == 0) continue;
             int succ = 0;
-            for (int i = 0; i < h->h_npts.p[b]; i++) succ += h->h_fwd_status.p[(size_t)b * cap + i] ? 1 : 0;
-            if (succ < 10) { h->h_seqmask.p[b] = 1; need = true; }
+            for (int k = 0; k < h->h_npts.p[i]; k++) succ += h->h_fwd_status.p[(size_t)i * cap + k] ? 1 : 0;
+            if (succ < 10) { h->h_seqmask.p[i] = 1; need = true; }
         }
         if (need) {
-            std::vector<uint8_t> redo(h->h_seqmask.p, h->h_seqmask.p + B);
-            std::vector<uint8_t> keep_status(h->h_status.p, h->h_status.p + (size_t)B * cap);
-            std::vector<float2> keep_pts(h->h_cur_pts.p, h->h_cur_pts.p + (size_t)B * cap);
-            std::vector<uint16_t> keep_depth(h->h_depth_out.p, h->h_depth_out.p + (size_t)B * cap);
-            std::vector<unsigned> keep_cnt(h->h_counters.p, h->h_counters.p + (size_t)B * cap * 2);
-            HIPCHK(hipMemcpyAsync(h->d_seqmask.p, h->h_seqmask.p, B, hipMemcpyHostToDevice, h->stream));
-            launch_lk(h, B, lk_args(h, 3, 0, h->cfg.flow_back, 1, h->d_seqmask.p, d_depth));
+            std::vector<uint8_t> redo(h->h_seqmask.p, h->h_seqmask.p + N);
+            std::vector<uint8_t> keep_status(h->h_status.p, h->h_status.p + (size_t)N * cap);
+            std::vector<float2> keep_pts(h->h_cur_pts.p, h->h_cur_pts.p + (size_t)N * cap);
+            std::vector<uint16_t> keep_depth(h->h_depth_out.p, h->h_depth_out.p + (size_t)N * cap);
+            std::vector<unsigned> keep_cnt(h->h_counters.p, h->h_counters.p + (size_t)N * cap * 2);
+            HIPCHK(hipMemcpyAsync(h->d_seqmask.p, h->h_seqmask.p, N, hipMemcpyHostToDevice, h->stream));
+            launch_lk(h, N, lk_args(h, 3, 0, h->cfg.flow_back, 1, h->d_seqmask.p, d_depth));
             h->stats.lk_launches++;
             HIPCHK(hipGetLastError());
-            up(h->h_cur_pts, h->d_cur_pts, (size_t)B * cap);
-            up(h->h_status, h->d_status, (size_t)B * cap);
-            up(h->h_depth_out, h->d_depth_out, (size_t)B * cap);
-            up(h->h_counters, h->d_counters, (size_t)B * cap * 2);
+            up(h->h_cur_pts, h->d_cur_pts, (size_t)N * cap);
+            up(h->h_status, h->d_status, (size_t)N * cap);
+            up(h->h_depth_out, h->d_depth_out, (size_t)N * cap);
+            up(h->h_counters, h->d_counters, (size_t)N * cap * 2);
             if (int rc = flush()) return rc;
             HIPCHK(hipStreamSynchronize(h->stream));
-            for (int b = 0; b < B; b++) {
-                unsigned* cn = h->h_counters.p + (size_t)b * cap * 2;
-                const unsigned* kc = keep_cnt.data() + (size_t)b * cap * 2;
-                if (redo[b]) { for (int i = 0; i < 2 * cap; i++) cn[i] += kc[i]; continue; }  // both passes did work
-                memcpy(h->h_status.p + (size_t)b * cap, keep_status.data() + (size_t)b * cap, cap);
-                memcpy(h->h_cur_pts.p + (size_t)b * cap, keep_pts.data() + (size_t)b * cap, cap * sizeof(float2));
-                memcpy(h->h_depth_out.p + (size_t)b * cap, keep_depth.data() + (size_t)b * cap, cap * sizeof(uint16_t));
+            for (int i = 0; i < N; i++) {
+                unsigned* cn = h->h_counters.p + (size_t)i * cap * 2;
+                const unsigned* kc = keep_cnt.data() + (size_t)i * cap * 2;
+                if (redo[i]) { for (int k = 0; k < 2 * cap; k++) cn[k] += kc[k]; continue; }  // both passes did work
+                memcpy(h->h_status.p + (size_t)i * cap, keep_status.data() + (size_t)i * cap, cap);
+                memcpy(h->h_cur_pts.p + (size_t)i * cap, keep_pts.data() + (size_t)i * cap, cap * sizeof(float2));
+                memcpy(h->h_depth_out.p + (size_t)i * cap, keep_depth.data() + (size_t)i * cap, cap * sizeof(uint16_t));
                 memcpy(cn, kc, cap * 2 * sizeof(unsigned));
             }
         }
     }
 
-    // ---- host bookkeeping per sequence (feature_tracker.cpp:170-186)
+    // ---- host bookkeeping per listed sequence (feature_tracker.cpp:170-186)
     std::atomic<long long> a_levels{0}, a_iters{0}, a_points{0}, a_tracked{0};
     std::atomic<int> a_want{0};
-    h->pool->parallel_for(B, [&](int b) {
-        SeqState& s = h->seq[b];
+    h->pool->parallel_for(N, [&](int b) {   // b: list position
+        SeqState& s = h->seq[seq[b]];
         const int n = (int)s.prev_pts.size();
         if (n > 0) {
             const uint8_t* st = h->h_status.p + (size_t)b * cap;
@@ -546,6 +592,7 @@ static int track_core(gf_tracker* h, const double* t, const uint8_t* d_gray, con
         h->h_ncenters.p[b] = nc;
         const int want = h->cfg.max_cnt - (int)s.cur_pts.size();
         h->h_want.p[b] = want;
+        h->h_det.p[b] = want > 0 ? h->h_cur.p[b] : -1;
         if (want > 0) a_want = 1;
         h->h_out_n.p[b] = 0;
     });
@@ -554,20 +601,21 @@ static int track_core(gf_tracker* h, const double* t, const uint8_t* d_gray, con
 
     // ---- Shi-Tomasi top-up (feature_tracker.cpp:190-206)
     if (any_want) {
-        down(h->d_centers, h->h_centers, (size_t)B * cap);
-        down(h->d_ncenters, h->h_ncenters, B);
-        down(h->d_want, h->h_want, B);
-        down(h->d_out_n, h->h_out_n, B);   // zeros (set above): a sequence that neither selection kernel serves reads 0, not the previous frame's count
+        down(h->d_det, h->h_det, N);
+        down(h->d_centers, h->h_centers, (size_t)N * cap);
+        down(h->d_ncenters, h->h_ncenters, N);
+        down(h->d_want, h->h_want, N);
+        down(h->d_out_n, h->h_out_n, N);   // zeros (set above): a sequence that neither selection kernel serves reads 0, not an earlier call's count
         if (int rc = flush()) return rc;
-        HIPCHK(hipMemsetAsync(h->d_maxkey.p, 0, B * sizeof(unsigned), h->stream));
-        HIPCHK(hipMemsetAsync(h->d_cand_count.p, 0, B * sizeof(int), h->stream));
+        HIPCHK(hipMemsetAsync(h->d_maxkey.p, 0, N * sizeof(unsigned), h->stream));
+        HIPCHK(hipMemsetAsync(h->d_cand_count.p, 0, N * sizeof(int), h->stream));
         if (prof) HIPCHK(hipEventRecord(h->ev[4], h->stream));
         {
             DetectArgs D{};
-            D.pyr = h->d_img.p + (size_t)h->cur_slot * h->G.img_bytes; D.pyr_seq_stride = 2 * h->G.img_bytes; D.g = h->G.lv[0];
-            D.mask = nullptr; D.mask_seq_stride = 0; D.centers = h->d_centers.p; D.n_centers = h->d_ncenters.p; D.cap = cap; D.want = h->d_want.p;
+            D.pyr = h->d_img.p; D.pyr_bytes = h->G.img_bytes; D.frame_of = h->d_det.p; D.g = h->G.lv[0];
+            D.mask = nullptr; D.mask_seq_stride = 0; D.centers = h->d_centers.p; D.n_centers = h->d_ncenters.p; D.cap = cap;
             D.maxkey = h->d_maxkey.p; D.cand = h->d_cand.p; D.cand_seq_stride = (size_t)h->cand_cap; D.cand_cap = h->cand_cap; D.cand_count = h->d_cand_count.p;
-            detect_strip_kernel<kDS_R><<<dim3((W + kDS_W - 1) / kDS_W, (H + kDS_R - 1) / kDS_R, B), 64, 0, h->stream>>>(D, h->disk);
+            detect_strip_kernel<kDS_R><<<dim3((W + kDS_W - 1) / kDS_W, (H + kDS_R - 1) / kDS_R, N), 64, 0, h->stream>>>(D, h->disk);
         }
         SelectArgs S{};
         S.cand = h->d_cand.p; S.cand_seq_stride = (size_t)h->cand_cap; S.cand_cap = h->cand_cap; S.cand_count = h->d_cand_count.p; S.maxkey = h->d_maxkey.p; S.want = h->d_want.p;
@@ -576,16 +624,16 @@ static int track_core(gf_tracker* h, const double* t, const uint8_t* d_gray, con
         {   // the sequences that want a handful of corners (every frame but the first ones): one maximum per corner instead of a sort (select_topk_kernel; GF_SELECT_TOPK=0: off)
             const bool topk_on = h->select_topk;
             int max_want = 0;
-            for (int b = 0; b < B; b++) max_want = std::max(max_want, h->h_want.p[b]);
+            for (int i = 0; i < N; i++) max_want = std::max(max_want, h->h_want.p[i]);
             S.skip_small = topk_on ? 1 : 0;
-            if (topk_on) select_topk_kernel<<<dim3(B), 1024, 0, h->stream>>>(S);
-            if (!topk_on || max_want > kTopKMax) select_corners_kernel<<<dim3(B), 1024, h->select_lds, h->stream>>>(S);
+            if (topk_on) select_topk_kernel<<<dim3(N), 1024, 0, h->stream>>>(S);
+            if (!topk_on || max_want > kTopKMax) select_corners_kernel<<<dim3(N), 1024, h->select_lds, h->stream>>>(S);
         }
         HIPCHK(hipGetLastError());
-        up(h->h_out_n, h->d_out_n, B);
-        up(h->h_out_pts, h->d_out_pts, (size_t)B * cap);
-        up(h->h_out_depth, h->d_out_depth, (size_t)B * cap);
-        up(h->h_cand_count, h->d_cand_count, B);
+        up(h->h_out_n, h->d_out_n, N);
+        up(h->h_out_pts, h->d_out_pts, (size_t)N * cap);
+        up(h->h_out_depth, h->d_out_depth, (size_t)N * cap);
+        up(h->h_cand_count, h->d_cand_count, N);
         if (int rc = flush()) return rc;
     }
     if (prof && !any_want) HIPCHK(hipEventRecord(h->ev[4], h->stream));
@@ -604,11 +652,11 @@ static int track_core(gf_tracker* h, const double* t, const uint8_t* d_gray, con
         HIPCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[5])); h->stats.ms_total_gpu += ms;
     }
     if (any_want)
-        for (int b = 0; b < B; b++) {
-            if (h->h_want.p[b] > 0 && h->h_cand_count.p[b] > h->cand_cap)
-                return set_err(GF_ERR_CAPACITY, "sequence %d: %d corner candidates exceed capacity %d", b, h->h_cand_count.p[b], h->cand_cap);
+        for (int i = 0; i < N; i++) {
+            if (h->h_want.p[i] > 0 && h->h_cand_count.p[i] > h->cand_cap)
+                return set_err(GF_ERR_CAPACITY, "sequence %d: %d corner candidates exceed capacity %d", seq[i], h->h_cand_count.p[i], h->cand_cap);
             // which branch of the corner selection served the sequence (the kernels' own tests on the same numbers)
-            const int want = h->h_want.p[b], n = std::min(h->h_cand_count.p[b], h->cand_cap);
+            const int want = h->h_want.p[i], n = std::min(h->h_cand_count.p[i], h->cand_cap);
             if (want <= 0 || n <= 0) continue;
             if (h->select_topk && want <= kTopKMax) { if (n > 1024 * kTopKQ) h->stats.select_streamed++; }
             else {
@@ -621,8 +669,8 @@ static int track_core(gf_tracker* h, const double* t, const uint8_t* d_gray, con
     // ---- addPoints, undistortedPts, ptsVelocity, pack (feature_tracker.cpp:85-93, 210-211, 322-368)
     std::atomic<int> a_overflow{-1};
     std::atomic<long long> a_out{0};
-    h->pool->parallel_for(B, [&](int b) {
-        SeqState& s = h->seq[b];
+    h->pool->parallel_for(N, [&](int b) {   // b: list position
+        SeqState& s = h->seq[seq[b]];
         const int nn = h->h_want.p[b] > 0 ? h->h_out_n.p[b] : 0;
         for (int i = 0; i < nn; i++) {
             const float2 p = h->h_out_pts.p[(size_t)b * cap + i];
@@ -634,6 +682,7 @@ static int track_core(gf_tracker* h, const double* t, const uint8_t* d_gray, con
         pts_velocity(s);
         s.prev_pts = s.cur_pts; s.prev_un_pts = s.cur_un_pts; s.prev_un_pts_map.swap(s.cur_un_pts_map); s.prev_time = s.cur_time;
         s.hasPrediction = false;
+        s.slot ^= 1;   // the pyramid written in this call is the sequence's previous frame from here on
         const int n = (int)s.ids.size();
         // depth_cam set but no depth image: neither packing loop of the reference runs (feature_tracker.cpp:320 `depth_cam == 0`, :344 `!_img1.empty()`):
         // the returned featureFrame is empty, the tracker state has advanced all the same
@@ -651,8 +700,8 @@ static int track_core(gf_tracker* h, const double* t, const uint8_t* d_gray, con
     });
     if (a_overflow.load() >= 0) return set_err(GF_ERR_CAPACITY, "output capacity %d < %d features", cap_out, a_overflow.load());
     h->stats.output_features += a_out;
-    h->frame++;
     h->stats.frames++;
+    h->stats.sequence_frames += N;
     lap(h->stats.ms_host_post);
     return GF_OK;
 }
@@ -687,6 +736,8 @@ int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out) {
     gf::build_geom(cfg->width, cfg->height, h->G);
     gf::make_disk_table(cfg->min_dist, h->disk);
     h->seq.resize(h->B);
+    h->ident.resize(h->B);
+    for (int b = 0; b < h->B; b++) h->ident[b] = b;
     {
         // default: up to 16 threads out of this rank's share of the node (a frame of 256 sequences spends 1.3 ms in the bookkeeping with 4 threads, 0.5 ms with 16)
         int share = 1;
@@ -738,6 +789,7 @@ int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out) {
     A_(h->h_prev_pts.alloc((size_t)B * cap)); A_(h->h_init_pts.alloc((size_t)B * cap)); A_(h->h_cur_pts.alloc((size_t)B * cap)); A_(h->h_out_pts.alloc((size_t)B * cap));
     A_(h->h_status.alloc((size_t)B * cap)); A_(h->h_fwd_status.alloc((size_t)B * cap)); A_(h->h_seqmask.alloc(2 * (size_t)B)); A_(h->h_depth_out.alloc((size_t)B * cap)); A_(h->h_out_depth.alloc((size_t)B * cap));
     A_(h->h_counters.alloc((size_t)B * cap * 2)); A_(h->h_centers.alloc((size_t)B * cap));
+    A_(h->d_cur.alloc(B)); A_(h->h_cur.alloc(B)); A_(h->d_det.alloc(B)); A_(h->h_det.alloc(B));   // behind the others, whose places relative to each other stay as measured
     H_(hipMemsetAsync(h->d_img.p, 0, h->d_img.n, h->stream));
     H_(hipFuncSetAttribute(reinterpret_cast<const void*>(gf::select_corners_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->select_lds));
     H_(hipStreamSynchronize(h->stream));
@@ -754,65 +806,96 @@ int gf_tracker_destroy(gf_tracker* h) {
     return GF_OK;
 }
 
-int gf_tracker_track_batch_device(gf_tracker* h, const double* t, const void* d_gray, const void* d_depth, gf_feature_obs* out, int cap,
-                                  int* n_out) {
-    if (!h || !t || !d_gray || !out || !n_out) return gf::set_err(GF_ERR_INVALID, "null argument");
-    return gf::track_core(h, t, (const uint8_t*)d_gray, (const uint16_t*)d_depth, out, cap, n_out);
+// ---- trackImage (feature_tracker.h:47) for the listed sequences of a handle.  t[i], gray[i], depth[i], out[i * cap ..], n_out[i] belong to sequence seq[i].
+int gf_tracker_track_some_device(gf_tracker* h, int count, const int* seq, const double* t, const void* d_gray, const void* d_depth, gf_feature_obs* out, int cap,
+                                 int* n_out) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (int rc = gf::check_list(h, count, seq)) return rc;
+    if (count == 0) return GF_OK;
+    if (!t || !d_gray || !out || !n_out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    return gf::track_core(h, count, seq, t, (const uint8_t*)d_gray, (const uint16_t*)d_depth, out, cap, n_out);
 }
 
-int gf_tracker_track_batch(gf_tracker* h, const double* t, const uint8_t* const* gray, int stride, const uint16_t* const* depth, int dstride,
-                           gf_feature_obs* out, int cap, int* n_out) {
-    if (!h || !t || !gray || !out || !n_out) return gf::set_err(GF_ERR_INVALID, "null argument");
+int gf_tracker_track_some(gf_tracker* h, int count, const int* seq, const double* t, const uint8_t* const* gray, int stride, const uint16_t* const* depth, int dstride,
+                          gf_feature_obs* out, int cap, int* n_out) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (int rc = gf::check_list(h, count, seq)) return rc;
+    if (count == 0) return GF_OK;
+    if (!t || !gray || !out || !n_out) return gf::set_err(GF_ERR_INVALID, "null argument");
     const int W = h->cfg.width, H = h->cfg.height;
     bool have_depth = depth != nullptr;
-    for (int b = 0; b < h->B; b++) {
-        if (!gray[b]) return gf::set_err(GF_ERR_INVALID, "null image for sequence %d", b);
-        HIPCHK(hipMemcpy2DAsync(h->d_raw.p + (size_t)b * W * H, W, gray[b], stride, W, H, hipMemcpyHostToDevice, h->stream));
-        if (have_depth && !depth[b]) have_depth = false;
+    for (int i = 0; i < count; i++) {   // refuse before the first copy
+        if (!gray[i]) return gf::set_err(GF_ERR_INVALID, "null image for sequence %d", seq[i]);
+        if (have_depth && !depth[i]) have_depth = false;
     }
+    for (int i = 0; i < count; i++) HIPCHK(hipMemcpy2DAsync(h->d_raw.p + (size_t)i * W * H, W, gray[i], stride, W, H, hipMemcpyHostToDevice, h->stream));
     // the depth image stays where it is: its <= max_cnt samples are taken on the host (track_core)
-    return gf::track_core(h, t, h->d_raw.p, nullptr, out, cap, n_out, have_depth ? depth : nullptr, dstride);
+    return gf::track_core(h, count, seq, t, h->d_raw.p, nullptr, out, cap, n_out, have_depth ? depth : nullptr, dstride);
 }
 
 // The host-image boundary (trackImage(const cv::Mat&), feature_tracker.h:47) without serialising on the bus: the images of frame k + 1 go to the second pair of
 // frame buffers on a copy stream while frame k's kernels run; gf_tracker_track_prefetched then only waits for that copy.  The host images must stay valid until
-// the matching gf_tracker_track_prefetched returns, and only page-locked memory (gf_host_alloc / hipHostRegister) makes the copy asynchronous.
-int gf_tracker_prefetch_batch(gf_tracker* h, const uint8_t* const* gray, int stride, const uint16_t* const* depth, int dstride) {
-    if (!h || !gray) return gf::set_err(GF_ERR_INVALID, "null argument");
+// the matching gf_tracker_track_prefetched returns, and only page-locked memory (gf_host_alloc / hipHostRegister) makes the copy asynchronous.  The staged frame
+// remembers its list: gf_tracker_track_prefetched advances exactly the sequences whose images were staged.
+int gf_tracker_prefetch_some(gf_tracker* h, int count, const int* seq, const uint8_t* const* gray, int stride, const uint16_t* const* depth, int dstride) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (int rc = gf::check_list(h, count, seq)) return rc;
+    if (count > 0 && !gray) return gf::set_err(GF_ERR_INVALID, "null argument");
     const int W = h->cfg.width, H = h->cfg.height;
+    bool have_depth = depth != nullptr;
+    for (int i = 0; i < count; i++) {
+        if (!gray[i]) return gf::set_err(GF_ERR_INVALID, "null image for sequence %d", seq[i]);
+        if (have_depth && !depth[i]) have_depth = false;
+    }
+    if (h->pf_count >= 2) return gf::set_err(GF_ERR_CAPACITY, "two frames are staged already: gf_tracker_track_prefetched has to consume one first");
     if (!h->copy_stream) {
         HIPCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
         for (auto& e : h->ev_copy) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         if (int rc = h->d_raw2.alloc((size_t)h->B * W * H)) return rc;
     }
-    if (h->pf_count >= 2) return gf::set_err(GF_ERR_CAPACITY, "two frames are staged already: gf_tracker_track_prefetched has to consume one first");
     const int slot = (h->pf_head + h->pf_count) & 1;      // a pair no frame in flight uses: track calls return when their frame is done
     uint8_t* raw = slot ? h->d_raw2.p : h->d_raw.p;
-    bool have_depth = depth != nullptr;
-    for (int b = 0; b < h->B; b++) {
-        if (!gray[b]) return gf::set_err(GF_ERR_INVALID, "null image for sequence %d", b);
-        if (have_depth && !depth[b]) have_depth = false;
-    }
     // images that sit back to back in one allocation (a pinned ring of frames) go as ONE copy per plane: 256 separate 2-D copies cost more host time than the bus needs
     bool contig = stride == W;
-    for (int b = 1; b < h->B && contig; b++) contig = gray[b] == gray[0] + (size_t)b * W * H;
-    if (contig) HIPCHK(hipMemcpyAsync(raw, gray[0], (size_t)h->B * W * H, hipMemcpyHostToDevice, h->copy_stream));
-    else for (int b = 0; b < h->B; b++) HIPCHK(hipMemcpy2DAsync(raw + (size_t)b * W * H, W, gray[b], stride, W, H, hipMemcpyHostToDevice, h->copy_stream));
+    for (int i = 1; i < count && contig; i++) contig = gray[i] == gray[0] + (size_t)i * W * H;
+    if (contig && count > 0) HIPCHK(hipMemcpyAsync(raw, gray[0], (size_t)count * W * H, hipMemcpyHostToDevice, h->copy_stream));
+    else for (int i = 0; i < count; i++) HIPCHK(hipMemcpy2DAsync(raw + (size_t)i * W * H, W, gray[i], stride, W, H, hipMemcpyHostToDevice, h->copy_stream));
     HIPCHK(hipEventRecord(h->ev_copy[slot], h->copy_stream));
     // the depth images do not travel: gf_tracker_track_prefetched samples them on the host (they must stay valid until it returns, like the gray images until the copy is done)
-    h->pf_depth[slot] = have_depth; if (have_depth) h->pf_hdepth[slot].assign(depth, depth + h->B); else h->pf_hdepth[slot].clear();
+    h->pf_depth[slot] = have_depth; if (have_depth) h->pf_hdepth[slot].assign(depth, depth + count); else h->pf_hdepth[slot].clear();
     h->pf_hdstride[slot] = dstride;
+    h->pf_seq[slot].assign(seq, seq + count);   // an empty list is staged too: the caller's prefetch / track_prefetched pairs stay in step
     h->pf_count++;
     return GF_OK;
 }
 
 int gf_tracker_track_prefetched(gf_tracker* h, const double* t, gf_feature_obs* out, int cap, int* n_out) {
-    if (!h || !t || !out || !n_out) return gf::set_err(GF_ERR_INVALID, "null argument");
-    if (!h->pf_count) return gf::set_err(GF_ERR_INVALID, "gf_tracker_track_prefetched without a staged frame (call gf_tracker_prefetch_batch first)");
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (!h->pf_count) return gf::set_err(GF_ERR_INVALID, "gf_tracker_track_prefetched without a staged frame (call gf_tracker_prefetch_batch or _prefetch_some first)");
     const int slot = h->pf_head;
+    const std::vector<int>& seq = h->pf_seq[slot];
+    if (!seq.empty() && (!t || !out || !n_out)) return gf::set_err(GF_ERR_INVALID, "null argument");
     HIPCHK(hipStreamWaitEvent(h->stream, h->ev_copy[slot], 0));
     h->pf_head ^= 1; h->pf_count--;
-    return gf::track_core(h, t, slot ? h->d_raw2.p : h->d_raw.p, nullptr, out, cap, n_out, h->pf_depth[slot] ? h->pf_hdepth[slot].data() : nullptr, h->pf_hdstride[slot]);
+    return gf::track_core(h, (int)seq.size(), seq.data(), t, slot ? h->d_raw2.p : h->d_raw.p, nullptr, out, cap, n_out, h->pf_depth[slot] ? h->pf_hdepth[slot].data() : nullptr, h->pf_hdstride[slot]);
+}
+
+// ---- the lock-step forms: the same calls with every sequence listed in order
+int gf_tracker_track_batch_device(gf_tracker* h, const double* t, const void* d_gray, const void* d_depth, gf_feature_obs* out, int cap,
+                                  int* n_out) {
+    if (!h || !t || !d_gray || !out || !n_out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    return gf_tracker_track_some_device(h, h->B, h->ident.data(), t, d_gray, d_depth, out, cap, n_out);
+}
+
+int gf_tracker_track_batch(gf_tracker* h, const double* t, const uint8_t* const* gray, int stride, const uint16_t* const* depth, int dstride,
+                           gf_feature_obs* out, int cap, int* n_out) {
+    if (!h || !t || !gray || !out || !n_out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    return gf_tracker_track_some(h, h->B, h->ident.data(), t, gray, stride, depth, dstride, out, cap, n_out);
+}
+
+int gf_tracker_prefetch_batch(gf_tracker* h, const uint8_t* const* gray, int stride, const uint16_t* const* depth, int dstride) {
+    if (!h || !gray) return gf::set_err(GF_ERR_INVALID, "null argument");
+    return gf_tracker_prefetch_some(h, h->B, h->ident.data(), gray, stride, depth, dstride);
 }
 
 // page-locked host memory for frames that are handed to gf_tracker_prefetch_batch / gf_tracker_track_batch (pageable memory makes hipMemcpyAsync synchronous)
@@ -823,13 +906,13 @@ int gf_host_alloc(size_t bytes, void** out) {
 }
 int gf_host_free(void* p) { if (p) (void)hipHostFree(p); return GF_OK; }
 
+// the list of one: any sequence of any handle
 int gf_tracker_track(gf_tracker* h, int seq, double t, const uint8_t* gray, int stride, const uint16_t* depth, int dstride, gf_feature_obs* out,
                      int cap, int* n_out) {
     if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
-    if (h->B != 1 || seq != 0) return gf::set_err(GF_ERR_INVALID, "gf_tracker_track drives a batch-1 handle (sequences of a batch advance in lock-step: use gf_tracker_track_batch)");
     const uint8_t* g[1] = {gray};
     const uint16_t* d[1] = {depth};
-    return gf_tracker_track_batch(h, &t, g, stride, depth ? d : nullptr, dstride, out, cap, n_out);
+    return gf_tracker_track_some(h, 1, &seq, &t, g, stride, depth ? d : nullptr, dstride, out, cap, n_out);
 }
 
 int gf_tracker_set_prediction(gf_tracker* h, int seq, const int* ids, const double* xyz, int n) {
@@ -892,12 +975,10 @@ int gf_lk_track(const uint8_t* prev, const uint8_t* next, int width, int height,
     auto body = [&]() -> int {
         const size_t px = (size_t)width * height;
         HIPCHK(hipMemcpyAsync(h->d_raw.p, prev, px, hipMemcpyHostToDevice, h->stream));
-        h->cur_slot = 0;
-        if (int r = gf::launch_pyramid(h, h->d_raw.p)) return r;
+        if (int r = gf::launch_pyramid_one(h, h->d_raw.p, 0)) return r;
         HIPCHK(hipStreamSynchronize(h->stream));
         HIPCHK(hipMemcpyAsync(h->d_raw.p, next, px, hipMemcpyHostToDevice, h->stream));
-        h->cur_slot = 1;
-        if (int r = gf::launch_pyramid(h, h->d_raw.p)) return r;
+        if (int r = gf::launch_pyramid_one(h, h->d_raw.p, 1)) return r;   // LK below: new frame in pyramid 1, previous one in pyramid 0
         h->h_npts.p[0] = n;
         for (int i = 0; i < n; i++) {
             h->h_prev_pts.p[i] = make_float2(prev_pts[2 * i], prev_pts[2 * i + 1]);
@@ -933,8 +1014,7 @@ int gf_pyramid_level(const uint8_t* img, int width, int height, int level, uint8
     auto body = [&]() -> int {
         if (level >= h->G.nlevels) return gf::set_err(GF_ERR_INVALID, "level %d not built (pyramid has %d levels)", level, h->G.nlevels);
         HIPCHK(hipMemcpyAsync(h->d_raw.p, img, (size_t)width * height, hipMemcpyHostToDevice, h->stream));
-        h->cur_slot = 0;
-        if (int r = gf::launch_pyramid(h, h->d_raw.p)) return r;
+        if (int r = gf::launch_pyramid_one(h, h->d_raw.p, 0)) return r;
         HIPCHK(hipStreamSynchronize(h->stream));
         const gf::LevelGeom g = h->G.lv[level];
         if (out) HIPCHK(hipMemcpy2D(out, g.w, h->d_img.p + g.img_off, g.stride, g.w, g.h, hipMemcpyDeviceToHost));
@@ -961,8 +1041,7 @@ int gf_min_eigen_val(const uint8_t* img, int width, int height, float* eig) {
     if (int rc = tmp_handle(width, height, 4, 30, &h)) return rc;
     auto body = [&]() -> int {
         HIPCHK(hipMemcpyAsync(h->d_raw.p, img, (size_t)width * height, hipMemcpyHostToDevice, h->stream));
-        h->cur_slot = 0;
-        if (int r = gf::launch_pyramid(h, h->d_raw.p)) return r;
+        if (int r = gf::launch_pyramid_one(h, h->d_raw.p, 0)) return r;
         gf::min_eig_kernel<<<dim3((width + 31) / 32, (height + 7) / 8, 1), 256, 0, h->stream>>>(h->d_img.p, 2 * h->G.img_bytes, h->G.lv[0], h->d_eig.p, h->eig_stride);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(eig, h->d_eig.p, (size_t)width * height * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -981,8 +1060,7 @@ int gf_good_features(const uint8_t* img, int width, int height, const uint8_t* m
     auto body = [&]() -> int {
         const int W = width, H = height;
         HIPCHK(hipMemcpyAsync(h->d_raw.p, img, (size_t)W * H, hipMemcpyHostToDevice, h->stream));
-        h->cur_slot = 0;
-        if (int r = gf::launch_pyramid(h, h->d_raw.p)) return r;
+        if (int r = gf::launch_pyramid_one(h, h->d_raw.p, 0)) return r;
         if (mask) HIPCHK(hipMemcpyAsync(h->d_mask.p, mask, (size_t)W * H, hipMemcpyHostToDevice, h->stream));
         else HIPCHK(hipMemsetAsync(h->d_mask.p, 255, (size_t)W * H, h->stream));
         h->h_want.p[0] = max_corners;
@@ -991,8 +1069,8 @@ int gf_good_features(const uint8_t* img, int width, int height, const uint8_t* m
         HIPCHK(hipMemsetAsync(h->d_cand_count.p, 0, sizeof(int), h->stream));
         {
             gf::DetectArgs D{};
-            D.pyr = h->d_img.p; D.pyr_seq_stride = 2 * h->G.img_bytes; D.g = h->G.lv[0];
-            D.mask = h->d_mask.p; D.mask_seq_stride = h->mask_stride; D.centers = nullptr; D.n_centers = nullptr; D.cap = h->cap; D.want = h->d_want.p;
+            D.pyr = h->d_img.p; D.pyr_bytes = h->G.img_bytes; D.frame_of = h->d_cur.p; D.g = h->G.lv[0];   // pyramid 0, written above; max_corners >= 1
+            D.mask = h->d_mask.p; D.mask_seq_stride = h->mask_stride; D.centers = nullptr; D.n_centers = nullptr; D.cap = h->cap;
             D.maxkey = h->d_maxkey.p; D.cand = h->d_cand.p; D.cand_seq_stride = (size_t)h->cand_cap; D.cand_cap = h->cand_cap; D.cand_count = h->d_cand_count.p;
             gf::detect_strip_kernel<gf::kDS_R><<<dim3((W + gf::kDS_W - 1) / gf::kDS_W, (H + gf::kDS_R - 1) / gf::kDS_R, 1), 64, 0, h->stream>>>(D, h->disk);
         }

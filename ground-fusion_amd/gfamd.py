@@ -32,14 +32,14 @@ class TrackerStats(C.Structure):
                 ("lk_level_passes", C.c_longlong), ("lk_iterations", C.c_longlong), ("tracked_features", C.c_longlong),
                 ("output_features", C.c_longlong), ("select_streamed", C.c_longlong), ("select_global_sort", C.c_longlong),
                 ("ms_equalize", C.c_double), ("pyr_head", C.c_longlong), ("pyr_level0_vec16", C.c_longlong), ("pyr_level0_dword", C.c_longlong),
-                ("pyr_down_tail", C.c_longlong), ("pyr_down_pad4", C.c_longlong), ("pyr_down_bytes", C.c_longlong)]
+                ("pyr_down_tail", C.c_longlong), ("pyr_down_pad4", C.c_longlong), ("pyr_down_bytes", C.c_longlong), ("sequence_frames", C.c_longlong)]
 
 
 OBS_DTYPE = np.dtype([("id", np.int32), ("camera_id", np.int32), ("v", np.float64, (8,))])
 assert OBS_DTYPE.itemsize == C.sizeof(FeatureObs)
 
 EXPORTS = ["gf_last_error", "gf_device_count", "gf_set_device", "gf_tracker_create", "gf_tracker_destroy", "gf_tracker_track",
-           "gf_tracker_track_batch", "gf_tracker_track_batch_device", "gf_tracker_set_prediction", "gf_tracker_remove_outliers",
+           "gf_tracker_track_batch", "gf_tracker_track_batch_device", "gf_tracker_track_some", "gf_tracker_track_some_device", "gf_tracker_prefetch_some", "gf_tracker_set_prediction", "gf_tracker_remove_outliers",
            "gf_tracker_get_state", "gf_tracker_set_profiling", "gf_tracker_get_stats", "gf_tracker_reset_stats", "gf_lk_track",
            "gf_good_features", "gf_min_eigen_val", "gf_pyramid_level", "gf_clahe_batch", "gf_clahe_batch_device"]
 
@@ -82,7 +82,8 @@ def default_cfg(width=640, height=480, batch=1, max_cnt=150, min_dist=30, flow_b
 
 
 class FeatureTracker:
-    """`batch` independent FeatureTracker instances (feature_tracker.h:43-99) advanced in lock-step on one GPU."""
+    """`batch` independent FeatureTracker instances (feature_tracker.h:43-99) on one GPU.  The *Batch* calls advance all of them, the *Some* calls the
+    sequences they list (the others keep their state); every per-sequence argument and result of a call is in list order."""
 
     def __init__(self, cfg=None):
         self.cfg = cfg or default_cfg()
@@ -103,14 +104,57 @@ class FeatureTracker:
 
     def _unpack(self, out, n):
         res = []
-        for b in range(self.cfg.batch):
+        for b in range(len(n)):
             o = out[b, :n[b]]
             res.append((o["id"].copy(), o["v"].copy()))
         return res
 
-    def trackImage(self, t, img, depth=None):
-        """batch == 1 convenience: returns (ids, obs[n,8])."""
-        return self.trackImageBatch([t], [img], None if depth is None else [depth])[0]
+    def trackImage(self, t, img, depth=None, seq=0):
+        """one frame for sequence `seq` alone (gf_tracker_track; the other sequences of a batch handle keep their state): returns (ids, obs[n,8])."""
+        return self.trackImageSome([seq], [t], [img], None if depth is None else [depth])[0]
+
+    def _seqs(self, seqs):
+        seqs = np.ascontiguousarray(seqs, np.int32).reshape(-1)
+        return seqs, len(seqs)
+
+    def trackImageSome(self, seqs, ts, imgs, depths=None, stride=None, dstride=None):
+        """gf_tracker_track_some: one frame for each listed sequence, ts[i] / imgs[i] / depths[i] for sequence seqs[i]; returns [(ids, obs)] in list order.
+        stride / dstride as in trackImageBatch"""
+        seqs, N = self._seqs(seqs)
+        ts = np.ascontiguousarray(ts, np.float64)
+        assert len(ts) == N and len(imgs) == N and (depths is None or len(depths) == N)
+        imgs = [None if i is None else np.ascontiguousarray(i, np.uint8) if stride is None else self._pitched(i, np.uint8, stride) for i in imgs]
+        gp = (C.POINTER(C.c_uint8) * max(N, 1))(*[None if i is None else _p(i, C.c_uint8) for i in imgs])
+        if depths is not None:
+            depths = [np.ascontiguousarray(d, np.uint16) for d in depths] if dstride is None else [self._pitched(d, np.uint16, dstride) for d in depths]
+            dp = (C.POINTER(C.c_uint16) * max(N, 1))(*[_p(d, C.c_uint16) for d in depths])
+        else:
+            dp = None
+        out = np.zeros((N, self.cap), OBS_DTYPE)
+        n = np.zeros(N, np.int32)
+        _chk(lib().gf_tracker_track_some(self.h, N, _p(seqs, C.c_int), _p(ts, C.c_double), gp, stride or self.cfg.width, dp, dstride or self.cfg.width,
+                                         out.ctypes.data_as(C.POINTER(FeatureObs)), self.cap, _p(n, C.c_int)))
+        return self._unpack(out, n)
+
+    def trackImageSomeDevice(self, seqs, ts, d_gray_ptr, d_depth_ptr=None, unpack=True, out=None, n_out=None):
+        """gf_tracker_track_some_device: d_*_ptr = integer device addresses of len(seqs) contiguous frames, frame i for sequence seqs[i].  out / n_out: the caller's
+        [>= len(seqs)][cap] OBS_DTYPE table and int32 counts (rows in list order: the table gf_estimator_group_submit_features reads with the same list);
+        default: the tracker's own pair."""
+        seqs, N = self._seqs(seqs)
+        ts = np.ascontiguousarray(ts, np.float64)
+        assert len(ts) == N
+        if out is None:
+            if not hasattr(self, "_out"):
+                self._out = np.zeros((self.cfg.batch, self.cap), OBS_DTYPE)
+                self._n = np.zeros(self.cfg.batch, np.int32)
+            out, n_out = self._out, self._n
+        # (a list longer than the batch is the library's to refuse: it checks the list before it touches the tables)
+        assert out.ndim == 2 and out.shape[0] >= min(N, self.cfg.batch) and out.shape[1] == self.cap and out.dtype == OBS_DTYPE and out.flags.c_contiguous
+        assert n_out.shape[0] >= min(N, self.cfg.batch) and n_out.dtype == np.int32 and n_out.flags.c_contiguous
+        _chk(lib().gf_tracker_track_some_device(self.h, N, _p(seqs, C.c_int), _p(ts, C.c_double), C.c_void_p(d_gray_ptr),
+                                                C.c_void_p(d_depth_ptr) if d_depth_ptr else None,
+                                                out.ctypes.data_as(C.POINTER(FeatureObs)), self.cap, _p(n_out, C.c_int)))
+        return self._unpack(out, n_out[:N]) if unpack else n_out[:N]
 
     def _pitched(self, a, dtype, pitch):
         """a height x width image whose rows lie `pitch` elements apart (a view of a wider array, e.g. a cropped frame): passed as it is, not copied"""
@@ -150,12 +194,17 @@ class FeatureTracker:
                                                  out.ctypes.data_as(C.POINTER(FeatureObs)), self.cap, _p(n_out, C.c_int)))
         return self._unpack(out, n_out) if unpack else n_out
 
-    def prefetchHost(self, gray_addr, depth_addr=None, stride=None, dstride=None):
+    def prefetchHost(self, gray_addr, depth_addr=None, stride=None, dstride=None, seqs=None):
         """gf_tracker_prefetch_batch on a block of `batch` frames lying back to back in (page-locked) host memory: gray_addr / depth_addr = integer host addresses
         of batch x height x width u8 / u16 images; the copy runs on the tracker's copy stream while the frame in flight is processed.  gray_addr / depth_addr may
-        also be lists of `batch` addresses (one image each, anywhere).  stride / dstride: row pitch in bytes / u16 elements (default: the width)"""
+        also be lists of `batch` addresses (one image each, anywhere).  stride / dstride: row pitch in bytes / u16 elements (default: the width).
+        seqs: gf_tracker_prefetch_some -- the frames (len(seqs) of them, block or list alike) belong to the listed sequences, and the matching trackPrefetched
+        advances those alone, its ts and results in the same order"""
         B, H = self.cfg.batch, self.cfg.height
         stride, dstride = stride or self.cfg.width, dstride or self.cfg.width
+        if seqs is not None:
+            seqs, B = self._seqs(seqs)
+        self._pf_n = getattr(self, "_pf_n", []) + [B]
         ga = list(gray_addr) if isinstance(gray_addr, (list, tuple)) else [gray_addr + b * stride * H for b in range(B)]
         gp = (C.POINTER(C.c_uint8) * B)(*[C.cast(a, C.POINTER(C.c_uint8)) for a in ga])
         if depth_addr:
@@ -163,16 +212,25 @@ class FeatureTracker:
             dp = (C.POINTER(C.c_uint16) * B)(*[C.cast(a, C.POINTER(C.c_uint16)) for a in da])
         else:
             dp = None
-        _chk(lib().gf_tracker_prefetch_batch(self.h, gp, stride, dp, dstride))
+        try:
+            if seqs is None:
+                _chk(lib().gf_tracker_prefetch_batch(self.h, gp, stride, dp, dstride))
+            else:
+                _chk(lib().gf_tracker_prefetch_some(self.h, B, _p(seqs, C.c_int), gp, stride, dp, dstride))
+        except GfError:
+            self._pf_n.pop()
+            raise
 
     def trackPrefetched(self, ts, unpack=True):
         B = self.cfg.batch
+        N = self._pf_n.pop(0) if getattr(self, "_pf_n", None) else B   # sequences of the oldest staged frame
         ts = np.ascontiguousarray(ts, np.float64)
+        assert len(ts) == N
         if not hasattr(self, "_out"):
             self._out = np.zeros((B, self.cap), OBS_DTYPE)
             self._n = np.zeros(B, np.int32)
         _chk(lib().gf_tracker_track_prefetched(self.h, _p(ts, C.c_double), self._out.ctypes.data_as(C.POINTER(FeatureObs)), self.cap, _p(self._n, C.c_int)))
-        return self._unpack(self._out, self._n) if unpack else self._n
+        return self._unpack(self._out, self._n[:N]) if unpack else self._n[:N]
 
     def setPrediction(self, ids, xyz, seq=0):
         ids = np.ascontiguousarray(ids, np.int32)

@@ -62,7 +62,7 @@ typedef struct gf_tracker_stats {
     double ms_pyramid, ms_lk, ms_detect, ms_total_gpu;
     /* host wall-clock split of the same frames: enqueue/pack, wait for LK, setMask bookkeeping, wait for detector, pack output */
     double ms_host_pre, ms_wait_lk, ms_host_mid, ms_wait_detect, ms_host_post;
-    long long frames;            /* frame-batches processed */
+    long long frames;            /* calls that processed at least one sequence */
     long long lk_launches;       /* launches of the LK kernel */
     long long lk_points;         /* points submitted to LK */
     long long lk_level_passes;   /* sum over points of pyramid levels actually processed (fwd+reverse) */
@@ -80,12 +80,13 @@ typedef struct gf_tracker_stats {
      * pyr_head: levels 0 + 1 in one kernel; pyr_level0_vec16 / pyr_level0_dword: level 0 alone in 16- / 4-byte pieces; pyr_down_tail: levels 2 .. 3 in one kernel;
      * pyr_down_pad4: one level >= 1 in four-pixel pieces; pyr_down_bytes: one level >= 1 one byte per thread */
     long long pyr_head, pyr_level0_vec16, pyr_level0_dword, pyr_down_tail, pyr_down_pad4, pyr_down_bytes;
+    long long sequence_frames;   /* listed sequences summed over the calls (`frames` counts the calls): frames x batch for the lock-step entry points */
 } gf_tracker_stats;
 
 int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out);
 int gf_tracker_destroy(gf_tracker* h);
 
-/* Replaces FeatureTracker::trackImage(t, img, depth) for sequence `seq` (feature_tracker.h:47).
+/* Replaces FeatureTracker::trackImage(t, img, depth) for sequence `seq` (feature_tracker.h:47) of a handle of any batch: the other sequences keep their state.
  * gray: height x width u8 (stride bytes); depth: height x width u16 millimetres (dstride elements) or NULL.
  * out/cap: caller-owned; *n_out = number of observations written (order = the tracker's `ids` vector). */
 int gf_tracker_track(gf_tracker* h, int seq, double t, const uint8_t* gray, int stride, const uint16_t* depth,
@@ -113,6 +114,25 @@ int gf_host_free(void* p);
  * d_depth = batch contiguous height*width u16 images (or NULL).  Device pointers of the current device. */
 int gf_tracker_track_batch_device(gf_tracker* h, const double* t, const void* d_gray, const void* d_depth,
                                   gf_feature_obs* out, int cap, int* n_out);
+
+/* The sequences of a handle advance independently: a call names the `count` sequences that have a frame (seq[count], distinct, any order), and only those run
+ * FeatureTracker::trackImage (feature_tracker.h:47).  A sequence that is not listed keeps its whole state -- tracks, ids, track_cnt, prev_time, its previous
+ * pyramid, a pending prediction -- as if the call had not happened, so cameras that drop frames, start late, stop early or tick at different rates share one
+ * handle.  Everything of the call is indexed by the position in the list: t[i], gray[i], depth[i], out[i * cap ..] and n_out[i] belong to sequence seq[i]
+ * (the layout gf_estimator_group_submit_features reads with the same list), and the kernels, copies and host work of the call follow `count`, not the batch.
+ * gf_tracker_track_batch* are these calls with the list 0 .. batch-1.  A refused call (GF_ERR_INVALID: count < 0 or > batch, an entry out of range, a sequence
+ * named twice, a null image) changes nothing; count == 0 succeeds and does nothing. */
+/* trackImage (feature_tracker.h:47) on host images of the listed sequences; depth as in gf_tracker_track_batch (NULL, or one image per listed sequence) */
+int gf_tracker_track_some(gf_tracker* h, int count, const int* seq, const double* t, const uint8_t* const* gray, int stride,
+                          const uint16_t* const* depth, int dstride, gf_feature_obs* out, int cap, int* n_out);
+/* trackImage (feature_tracker.h:47) on device images: d_gray / d_depth hold the `count` frames of the listed sequences back to back, in list order */
+int gf_tracker_track_some_device(gf_tracker* h, int count, const int* seq, const double* t, const void* d_gray, const void* d_depth,
+                                 gf_feature_obs* out, int cap, int* n_out);
+/* trackImage (feature_tracker.h:47), staged: as gf_tracker_prefetch_batch for the listed sequences.  The staged frame remembers its list, and the matching
+ * gf_tracker_track_prefetched advances exactly those sequences, its t / out / n_out in the staged order; two staged frames may name different sets.  An empty
+ * list is staged as well (its gf_tracker_track_prefetched does nothing), so that prefetch and track calls stay paired. */
+int gf_tracker_prefetch_some(gf_tracker* h, int count, const int* seq, const uint8_t* const* gray, int stride,
+                             const uint16_t* const* depth, int dstride);
 
 /* FeatureTracker::setPrediction (feature_tracker.cpp:1006-1027): ids[n], xyz[3n] camera-frame points. */
 int gf_tracker_set_prediction(gf_tracker* h, int seq, const int* ids, const double* xyz, int n);
