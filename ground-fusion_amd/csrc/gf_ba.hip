@@ -251,12 +251,46 @@ struct gf_ba {
 
 namespace {
 
+// The visual factors k with key(k) >= 0 in ascending order of their frame-pair key (< nkeys <= 32 * 64), factors of one key in their own order (a stable counting sort),
+// every run of one key padded with -1 to even length: each MFMA consumes two factors of one frame pair.  An entry is the key above the factor index; returns their number.
+template <class Key> int pair_order(int n_visual, int nkeys, Key key, std::vector<int>& idx, int* ord) {
+    int cnt[32 * 64 + 1];
+    memset(cnt, 0, (nkeys + 1) * sizeof(int));
+    for (int k = 0; k < n_visual; k++) if (key(k) >= 0) cnt[key(k) + 1]++;
+    for (int q = 0; q < nkeys; q++) cnt[q + 1] += cnt[q];
+    idx.resize(cnt[nkeys]);
+    for (int k = 0; k < n_visual; k++) if (key(k) >= 0) idx[cnt[key(k)]++] = k;
+    int n = 0;
+    for (size_t p = 0; p < idx.size();) {
+        size_t q = p;
+        const int kp = key(idx[p]);
+        while (q < idx.size() && key(idx[q]) == kp) ord[n++] = (kp << 16) | idx[q++];
+        if ((q - p) & 1) ord[n++] = -1;
+        p = q;
+    }
+    return n;
+}
+
+// The parameter blocks of a window into its state vector x (one slot of xs0); what a window does not have (features beyond n_feature, GNSS states) is left as it is.
+void pack_states(const Dims& d, const gf_ba_window& w, double* x) {
+    for (int i = 0; i < d.NP; i++) { memcpy(x + off_pose(i), w.para_Pose + 7 * i, 56); memcpy(x + off_sb(i), w.para_SpeedBias + 9 * i, 72); }
+    memcpy(x + off_ex(d.NP), w.para_Ex_Pose, 56); memcpy(x + off_exw(d.NP), w.para_Ex_Pose_wheel, 56); memcpy(x + off_ix(d.NP), w.para_Ix, 24);
+    x[off_td(d.NP)] = w.para_Td[0]; x[off_tdw(d.NP)] = w.para_Td_wheel[0];
+    for (int f = 0; f < w.n_feature; f++) x[off_feat(d.NP) + f] = w.para_Feature[f];
+    if (d.GO && w.gnss_enabled) {
+        memcpy(x + d.GO, w.para_rcv_dt, 4 * d.NP * 8); memcpy(x + d.GO + 4 * d.NP, w.para_rcv_ddt, d.NP * 8); x[d.GO + 5 * d.NP] = w.para_yaw_enu_local[0];
+        memcpy(x + d.GO + 5 * d.NP + 1, w.para_anc_ecef, 24);
+    }
+    if (w.fix_poses) for (int i = 0; i < d.NP; i++) x[off_sb(i)] = x[off_sb(i) + 1] = x[off_sb(i) + 2] = 0.0;  // estimator.cpp:3233-3246
+}
+
 // One window into slot b of the pinned staging tables (everything the kernels read about it, both marginalisation layouts included).  Touches only
 // slot b: any number of slots may be packed concurrently, one thread per slot.
 int pack_slot(gf_ba* h, int b, const gf_ba_window& w) {
     const Dims& d = h->d;
     gf_ba::SlotMeta& M = h->meta[b];
     M = gf_ba::SlotMeta{};
+    std::vector<int> idx;   // pair_order's scratch, for the solve and for MARGIN_OLD
     {
         if (w.W != d.W) return gf::set_err(GF_ERR_INVALID, "window %d: W=%d, handle built for %d", b, w.W, d.W);
         if (w.n_feature > d.F || w.n_visual > d.NV || w.n_imu > d.W || w.n_wheel > d.W || w.prior_n > d.NPRI || w.prior_nblocks > 64)
@@ -265,19 +299,14 @@ int pack_slot(gf_ba* h, int b, const gf_ba_window& w) {
         if (w.gnss_enabled && (!w.para_rcv_dt || !w.para_rcv_ddt || !w.para_yaw_enu_local || !w.para_anc_ecef || !w.gnss_headers || !w.gnss_iono || (w.n_gnss > 0 && (!w.gnss_frame || !w.gnss_lower || !w.gnss_sys || !w.gnss_ratio || !w.gnss_data))))
             return gf::set_err(GF_ERR_INVALID, "window %d: GNSS enabled but a GNSS array is null", b);
         { double* wp = h->wpar.h + WPAR * (size_t)b; wp[0] = w.G[0]; wp[1] = w.G[1]; wp[2] = w.G[2]; wp[3] = w.vis_sqrt_info; wp[4] = (double)(w.ex_pose_mask & 63); wp[5] = (double)(w.ex_wheel_mask & 63); }   // gravity and visual sqrt_info are per window (estimator.h `g`)
-        double* x = h->xs0.h + (size_t)b * d.XS;
-        memset(x, 0, d.XS * sizeof(double));
-        for (int i = 0; i < d.NP; i++) { memcpy(x + off_pose(i), w.para_Pose + 7 * i, 56); memcpy(x + off_sb(i), w.para_SpeedBias + 9 * i, 72); }
-        memcpy(x + off_ex(d.NP), w.para_Ex_Pose, 56); memcpy(x + off_exw(d.NP), w.para_Ex_Pose_wheel, 56); memcpy(x + off_ix(d.NP), w.para_Ix, 24);
-        x[off_td(d.NP)] = w.para_Td[0]; x[off_tdw(d.NP)] = w.para_Td_wheel[0];
+        memset(h->xs0.h + (size_t)b * d.XS, 0, d.XS * sizeof(double));
+        pack_states(d, w, h->xs0.h + (size_t)b * d.XS);
         if (d.GO) {
             h->ngnss.h[b] = w.gnss_enabled ? w.n_gnss : 0;
             double* ms = h->gn_misc.h + (size_t)b * (GN_MISC + d.NP);
             memset(ms, 0, (GN_MISC + d.NP) * sizeof(double));
             h->gn_gptr.h[(size_t)b * (d.NGRP + 2) + d.NGRP + 1] = 0;
             if (w.gnss_enabled) {
-                memcpy(x + d.GO, w.para_rcv_dt, 4 * d.NP * 8); memcpy(x + d.GO + 4 * d.NP, w.para_rcv_ddt, d.NP * 8); x[d.GO + 5 * d.NP] = w.para_yaw_enu_local[0];
-                memcpy(x + d.GO + 5 * d.NP + 1, w.para_anc_ecef, 24);
                 memcpy(ms, w.gnss_iono, 64); ms[8] = w.gnss_ddt_weight; ms[16] = 1.0; ms[17] = w.gnss_lowspeed ? 0.0 : 1.0;
                 memcpy(ms + GN_MISC, w.gnss_headers, d.NP * 8);
                 for (int k = 0; k < w.n_gnss; k++) {
@@ -305,8 +334,6 @@ int pack_slot(gf_ba* h, int b, const gf_ba_window& w) {
             }
             if (w.has_anchor) { memcpy(ms + 9, w.anchor_value, 56); ms[18] = 1.0; }
         } else if (w.has_anchor) return gf::set_err(GF_ERR_INVALID, "window %d: PoseAnchorFactor needs a handle built with max_gnss > 0", b);
-        for (int f = 0; f < w.n_feature; f++) x[off_feat(d.NP) + f] = w.para_Feature[f];
-        if (w.fix_poses) for (int i = 0; i < d.NP; i++) x[off_sb(i)] = x[off_sb(i) + 1] = x[off_sb(i) + 2] = 0.0;  // estimator.cpp:3233-3246
         // column maps (canonical order: pose0, sb0, pose1, ..., ex, exw, sx, sy, sw, td, tdw)
         int* cf = h->colf.h + (size_t)b * d.NFB;
         int col = 0;
@@ -314,13 +341,13 @@ int pack_slot(gf_ba* h, int b, const gf_ba_window& w) {
         for (int i = 0; i < d.NP; i++) { add(fb_pose(i), w.fix_poses != 0, 6); add(fb_sb(i), w.fix_poses != 0, 9); }
         add(fb_ex(d.NP), w.fix_ex_pose != 0, 6);
         // wheel blocks take part when a wheel factor or the prior mentions them (Ceres drops parameter blocks without residual blocks)
-        auto part = [&](int id) { if (w.n_wheel > 0) return true; for (int q = 0; q < w.prior_nblocks; q++) if (w.prior_block_id[q] == id) return true; return false; };
+        auto inpri = [&](int id) { for (int q = 0; q < w.prior_nblocks; q++) if (w.prior_block_id[q] == id) return true; return false; };
+        auto part = [&](int id) { return w.n_wheel > 0 || inpri(id); };
         add(fb_exw(d.NP), !part(GF_EX_WHEEL * 4096) || w.fix_ex_wheel, 6);
         for (int q = 0; q < 3; q++) add(fb_sx(d.NP) + q, !part((GF_SX + q) * 4096) || w.fix_ix, 1);
         add(fb_td(d.NP), w.fix_td != 0, 1);
         add(fb_tdw(d.NP), !part(GF_TD_WHEEL * 4096) || w.fix_td_wheel, 1);
         if (d.GO) {   // receiver clocks / anchor: free when a residual block or the prior mentions them (estimator.cpp:2904-2941); yaw_enu_local is held constant (:2932)
-            auto inpri = [&](int id) { for (int q = 0; q < w.prior_nblocks; q++) if (w.prior_block_id[q] == id) return true; return false; };
             const bool fac = w.gnss_enabled && !w.gnss_lowspeed;
             for (int i = 0; i < d.NP; i++) for (int q = 0; q < 4; q++) add(fb_rcvdt(d.NP, 4 * i + q), !(w.gnss_enabled && (fac || inpri(GF_RCV_DT * 4096 + 4 * i + q))), 1);
             for (int i = 0; i < d.NP; i++) add(fb_rcvddt(d.NP, i), !(w.gnss_enabled && (fac || inpri(GF_RCV_DDT * 4096 + i))), 1);
@@ -375,24 +402,9 @@ int pack_slot(gf_ba* h, int b, const gf_ba_window& w) {
         { const double R = st.R, nc = 6.0 * d.NP + 8.0; M.step = (long long)(ne * nc * nc + R * R * R / 3.0 + 2.0 * R * R); }
         M.nvis = w.n_visual; M.npri = w.prior_n; M.nfeat = w.n_feature;
         h->nvis.h[b] = w.n_visual; h->nimu.h[b] = w.n_imu; h->nwh.h[b] = w.n_wheel; h->nfeat.h[b] = w.n_feature;
-        {   // pair-sorted order with even padding (each MFMA consumes two factors of one frame pair)
-            // stable counting sort over the pair keys i * 64 + j (i < j <= W <= 30): the factor lists of a window are built and packed on its member's thread every frame
-            std::vector<int> idx(w.n_visual);
-            {
-                int cnt[32 * 64 + 1] = {0};
-                for (int k = 0; k < w.n_visual; k++) cnt[w.vis_i[k] * 64 + w.vis_j[k] + 1]++;
-                for (int q = 0; q < 32 * 64; q++) cnt[q + 1] += cnt[q];
-                for (int k = 0; k < w.n_visual; k++) idx[cnt[w.vis_i[k] * 64 + w.vis_j[k]]++] = k;
-            }
+        {   // pair-sorted order with even padding: the factor lists of a window are built and packed on its member's thread every frame
             int* ord = h->order.h + (size_t)b * d.NVP;
-            int n = 0;
-            for (size_t p = 0; p < idx.size();) {
-                size_t q = p;
-                const int key = w.vis_i[idx[p]] * 64 + w.vis_j[idx[p]];
-                while (q < idx.size() && w.vis_i[idx[q]] * 64 + w.vis_j[idx[q]] == key) ord[n++] = (key << 16) | idx[q++];   // pair key (i * 64 + j) above the factor index
-                if ((q - p) & 1) ord[n++] = -1;
-                p = q;
-            }
+            const int n = pair_order(w.n_visual, 32 * 64, [&](int k) { return w.vis_i[k] * 64 + w.vis_j[k]; }, idx, ord);   // i < j <= W <= 30
             if (n > d.NVP) return gf::set_err(GF_ERR_CAPACITY, "factor order overflow");
             h->norder.h[b] = n;
             for (int i = n; i < d.NVP; i++) ord[i] = -1;
@@ -499,15 +511,10 @@ int pack_slot(gf_ba* h, int b, const gf_ba_window& w) {
             int* me = h->mcole[mode].h + (size_t)b * d.F;
             for (int q = 0; q < d.NFB; q++) mc[q] = -1;
             for (int f = 0; f < d.F; f++) me[f] = -1;
-            auto fblk = [&](int id) {
-                const int kind = id / 4096, i = id % 4096;
-                switch (kind) { case 0: return fb_pose(i); case 1: return fb_sb(i); case 2: return fb_ex(d.NP); case 3: return fb_exw(d.NP); case 4: return fb_sx(d.NP);
-                                case 5: return fb_sx(d.NP) + 1; case 6: return fb_sx(d.NP) + 2; case 7: return fb_td(d.NP); case 10: return fb_rcvdt(d.NP, i); case 11: return fb_rcvddt(d.NP, i);
-                                case 12: return fb_yaw(d.NP); case 13: return fb_anc(d.NP); default: return fb_tdw(d.NP); }
-            };
             int mp = 0, n = 0;
-            for (int id : dropb) { mc[fblk(id)] = mp; mp += lsize_kind(id / 4096); }
-            for (int id : keepb) { mc[fblk(id)] = mp + n; n += lsize_kind(id / 4096); }
+            for (const std::vector<int>* v : {&dropb, &keepb}) for (int id : *v) if (fblock_of(id, d) < 0) return gf::set_err(GF_ERR_INVALID, "window %d: block id %d is no parameter block of this handle", b, id);
+            for (int id : dropb) { mc[fblock_of(id, d)] = mp; mp += lsize_kind(id / 4096); }
+            for (int id : keepb) { mc[fblock_of(id, d)] = mp + n; n += lsize_kind(id / 4096); }
             for (size_t q = 0; q < dropf.size(); q++) me[dropf[q] % 4096] = (int)q;
             if (mp + (int)dropf.size() == 0) valid = false;
             if (valid && (n > h->marg_ncap || mp > gfb::MPMAX || mp + n > d.RP)) return gf::set_err(GF_ERR_CAPACITY, "window %d: marginalisation sizes mp=%d n=%d exceed this build (n <= %d)", b, mp, n, h->marg_ncap);
@@ -516,23 +523,7 @@ int pack_slot(gf_ba* h, int b, const gf_ba_window& w) {
             h->keep_ids[mode][b] = keepb;
             // factor order (mode 0: visual factors of features starting at frame 0)
             int* ord = h->morder[mode].h + (size_t)b * d.NVP;
-            int no = 0;
-            if (mode == 0) {
-                std::vector<int> idx;   // factors of frame 0 by their second frame, stable: counting sort over j
-                {
-                    int cnt[65] = {0};
-                    for (int k = 0; k < w.n_visual; k++) if (w.vis_i[k] == 0) cnt[w.vis_j[k] + 1]++;
-                    for (int q = 0; q < 64; q++) cnt[q + 1] += cnt[q];
-                    idx.resize(cnt[64]);
-                    for (int k = 0; k < w.n_visual; k++) if (w.vis_i[k] == 0) idx[cnt[w.vis_j[k]]++] = k;
-                }
-                for (size_t p = 0; p < idx.size();) {
-                    size_t q = p;
-                    while (q < idx.size() && w.vis_j[idx[q]] == w.vis_j[idx[p]]) ord[no++] = (w.vis_j[idx[p]] << 16) | idx[q++];   // pair (0, j)
-                    if ((q - p) & 1) ord[no++] = -1;
-                    p = q;
-                }
-            }
+            const int no = mode == 0 ? pair_order(w.n_visual, 64, [&](int k) { return w.vis_i[k] == 0 ? w.vis_j[k] : -1; }, idx, ord) : 0;   // pairs (0, j)
             h->mnorder[mode].h[b] = no; M.mno[mode] = no;
             for (int i = no; i < d.NVP; i++) ord[i] = -1;
         }
@@ -1008,6 +999,32 @@ int gf_ba_solve_resident(gf_ba* h, int max_iters, int marginalize_mode, int rese
 }
 
 
+// The prior the last marginalisation (layout `mode`) left for slot b in the host mirrors outJ / outr: kept block ids after the address shift, J (when p.J is given), r,
+// and the linearisation point gathered from the state vector x.  Touches nothing but p: callable concurrently for different slots.
+static int unpack_prior(gf_ba* h, int b, int mode, const double* x, gf_ba_prior& p) {
+    const Dims& d = h->d;
+    const int* inf = h->minfo[mode].h + (size_t)b * 4;
+    p.valid = inf[3]; p.m = inf[0] + inf[1]; p.n = 0; p.nblocks = 0;
+    if (!inf[3]) return GF_OK;
+    const int n = inf[2];
+    const std::vector<int>& keep = h->keep_ids[mode][b];
+    if (n > p.cap_n || (int)keep.size() > p.cap_blocks) return gf::set_err(GF_ERR_CAPACITY, "prior capacity too small (n=%d, blocks=%zu)", n, keep.size());
+    p.n = n; p.nblocks = (int)keep.size();
+    if (p.J) memcpy(p.J, h->outJ.h + (size_t)b * d.NPRI * d.NPRI, (size_t)n * n * sizeof(double));
+    memcpy(p.r, h->outr.h + (size_t)b * d.NPRI, (size_t)n * sizeof(double));
+    int xo = 0;
+    for (size_t q = 0; q < keep.size(); q++) {
+        const int id = keep[q], kind = id / 4096, i = id % 4096;
+        int nid = id;  // addr_shift (estimator.cpp:3471-3500 / :3583-3626)
+        if (kind == GF_POSE || kind == GF_SPEEDBIAS || kind == GF_RCV_DDT) nid = mode == 0 ? kind * 4096 + i - 1 : (i == d.W ? kind * 4096 + d.W - 1 : id);
+        else if (kind == GF_RCV_DT) nid = mode == 0 ? id - 4 : (i / 4 == d.W ? id - 4 : id);
+        p.block_id[q] = nid;
+        const int off = state_off_of(id, d);
+        for (int k = 0; k < gsize_kind(kind); k++) p.x0[xo++] = x[off + k];
+    }
+    return GF_OK;
+}
+
 int gf_ba_download(gf_ba* h, gf_ba_window* windows, int count, gf_ba_summary* summaries, gf_ba_prior* priors) {
     if (!h || count < 1 || count > h->count) return gf::set_err(GF_ERR_INVALID, "bad argument");
     if (int rc = gf_ba_wait(h)) return rc;
@@ -1026,33 +1043,7 @@ int gf_ba_download(gf_ba* h, gf_ba_window* windows, int count, gf_ba_summary* su
         const SolverState& st = h->st.h[b];
         unpack_state(h, b, windows ? windows + b : nullptr, summaries ? summaries + b : nullptr);
         if (priors) {
-            gf_ba_prior& p = priors[b];
-            const int mode = h->last_marg_mode;
-            const int* inf = h->minfo[mode].h + (size_t)b * 4;
-            p.valid = inf[3]; p.m = inf[0] + inf[1]; p.n = 0; p.nblocks = 0;
-            if (inf[3]) {
-                const int n = inf[2];
-                const std::vector<int>& keep = h->keep_ids[mode][b];
-                if (n > p.cap_n || (int)keep.size() > p.cap_blocks) return gf::set_err(GF_ERR_CAPACITY, "prior capacity too small (n=%d, blocks=%zu)", n, keep.size());
-                p.n = n; p.nblocks = (int)keep.size();
-                memcpy(p.J, h->outJ.h + (size_t)b * d.NPRI * d.NPRI, (size_t)n * n * sizeof(double));
-                memcpy(p.r, h->outr.h + (size_t)b * d.NPRI, (size_t)n * sizeof(double));
-                const double* x = h->xs.h + ((size_t)st.cur * d.B + b) * d.XS;
-                int xo = 0;
-                for (size_t q = 0; q < keep.size(); q++) {
-                    const int id = keep[q], kind = id / 4096, i = id % 4096;
-                    int nid = id;  // addr_shift (estimator.cpp:3471-3500 / :3583-3626)
-                    if (kind == GF_POSE || kind == GF_SPEEDBIAS || kind == GF_RCV_DDT) nid = mode == 0 ? kind * 4096 + i - 1 : (i == d.W ? kind * 4096 + d.W - 1 : id);
-                    else if (kind == GF_RCV_DT) nid = mode == 0 ? id - 4 : (i / 4 == d.W ? id - 4 : id);
-                    p.block_id[q] = nid;
-                    int off;
-                    switch (kind) { case 0: off = off_pose(i); break; case 1: off = off_sb(i); break; case 2: off = off_ex(d.NP); break; case 3: off = off_exw(d.NP); break;
-                                    case 4: off = off_ix(d.NP); break; case 5: off = off_ix(d.NP) + 1; break; case 6: off = off_ix(d.NP) + 2; break; case 7: off = off_td(d.NP); break;
-                                    case 10: off = d.GO + i; break; case 11: off = d.GO + 4 * d.NP + i; break; case 12: off = d.GO + 5 * d.NP; break; case 13: off = d.GO + 5 * d.NP + 1; break;
-                                    default: off = off_tdw(d.NP); }
-                    for (int k = 0; k < gsize_kind(kind); k++) p.x0[xo++] = x[off + k];
-                }
-            }
+            if (int rc = unpack_prior(h, b, h->last_marg_mode, h->xs.h + ((size_t)st.cur * d.B + b) * d.XS, priors[b])) return rc;
         }
     }
     return GF_OK;
@@ -1124,13 +1115,7 @@ int gf_ba_marginalize_resident(gf_ba* h, const int* slots, const gf_ba_window* w
         if (w.W != d.W || w.n_feature != h->nfeat.h[b] || w.n_visual != h->nvis.h[b] || w.n_imu != h->nimu.h[b] || w.n_wheel != h->nwh.h[b] || w.prior_n != h->pri_n.h[b])
             return gf::set_err(GF_ERR_INVALID, "window %d does not match the structure resident in slot %d (features %d/%d, visual %d/%d, imu %d/%d, wheel %d/%d, prior %d/%d)", i, b,
                                w.n_feature, h->nfeat.h[b], w.n_visual, h->nvis.h[b], w.n_imu, h->nimu.h[b], w.n_wheel, h->nwh.h[b], w.prior_n, h->pri_n.h[b]);
-        double* x = h->xs0.h + (size_t)b * d.XS;
-        for (int k = 0; k < d.NP; k++) { memcpy(x + off_pose(k), w.para_Pose + 7 * k, 56); memcpy(x + off_sb(k), w.para_SpeedBias + 9 * k, 72); }
-        memcpy(x + off_ex(d.NP), w.para_Ex_Pose, 56); memcpy(x + off_exw(d.NP), w.para_Ex_Pose_wheel, 56); memcpy(x + off_ix(d.NP), w.para_Ix, 24);
-        x[off_td(d.NP)] = w.para_Td[0]; x[off_tdw(d.NP)] = w.para_Td_wheel[0];
-        for (int f = 0; f < w.n_feature; f++) x[off_feat(d.NP) + f] = w.para_Feature[f];
-        if (d.GO && w.gnss_enabled) { memcpy(x + d.GO, w.para_rcv_dt, 4 * d.NP * 8); memcpy(x + d.GO + 4 * d.NP, w.para_rcv_ddt, d.NP * 8); x[d.GO + 5 * d.NP] = w.para_yaw_enu_local[0]; memcpy(x + d.GO + 5 * d.NP + 1, w.para_anc_ecef, 24); }
-        if (w.fix_poses) for (int k = 0; k < d.NP; k++) x[off_sb(k)] = x[off_sb(k) + 1] = x[off_sb(k) + 2] = 0.0;
+        pack_states(d, w, h->xs0.h + (size_t)b * d.XS);
     }
     HIPCHK(h->xs0.up(h->stream));
     {   // only the listed slots are marginalised: the others keep whatever prior their last marginalisation left in the output buffers (their owners may
@@ -1163,37 +1148,10 @@ int gf_ba_unpack_prior_slot(gf_ba* h, int slot, int mode, gf_ba_prior* prior) {
     if (!h || !prior || slot < 0 || slot >= h->d.B || mode < 0 || mode > 1) return gf::set_err(GF_ERR_INVALID, "bad argument");
     const Dims& d = h->d;
     const int b = slot;
-    gf_ba_prior& p = *prior;
-    {
-        const int* inf = h->minfo[mode].h + (size_t)b * 4;
-        p.valid = inf[3]; p.m = inf[0] + inf[1]; p.n = 0; p.nblocks = 0;
-        if (!inf[3]) return GF_OK;
-        const int nn = inf[2];
-        const std::vector<int>& keep = h->keep_ids[mode][b];
-        if (nn > p.cap_n || (int)keep.size() > p.cap_blocks) return gf::set_err(GF_ERR_CAPACITY, "prior capacity too small (n=%d, blocks=%zu)", nn, keep.size());
-        p.n = nn; p.nblocks = (int)keep.size();
-        if (p.J) {   // J == NULL: the prior's J stays on the device (the slot's next gf_ba_pack_slot passes prior_J = NULL)
-            if (h->outJ_host_stale) HIPCHK(hipMemcpy(h->outJ.h + (size_t)b * d.NPRI * d.NPRI, h->outJ.d + (size_t)b * d.NPRI * d.NPRI, (size_t)nn * nn * sizeof(double), hipMemcpyDeviceToHost));
-            memcpy(p.J, h->outJ.h + (size_t)b * d.NPRI * d.NPRI, (size_t)nn * nn * sizeof(double));
-        }
-        memcpy(p.r, h->outr.h + (size_t)b * d.NPRI, (size_t)nn * sizeof(double));
-        const double* x = h->xs0.h + (size_t)b * d.XS;   // the linearisation point of the prior = the states just uploaded
-        int xo = 0;
-        for (size_t q = 0; q < keep.size(); q++) {
-            const int id = keep[q], kind = id / 4096, k = id % 4096;
-            int nid = id;  // addr_shift (estimator.cpp:3471-3500 / :3583-3626)
-            if (kind == GF_POSE || kind == GF_SPEEDBIAS || kind == GF_RCV_DDT) nid = mode == 0 ? kind * 4096 + k - 1 : (k == d.W ? kind * 4096 + d.W - 1 : id);
-            else if (kind == GF_RCV_DT) nid = mode == 0 ? id - 4 : (k / 4 == d.W ? id - 4 : id);
-            p.block_id[q] = nid;
-            int off;
-            switch (kind) { case 0: off = off_pose(k); break; case 1: off = off_sb(k); break; case 2: off = off_ex(d.NP); break; case 3: off = off_exw(d.NP); break;
-                            case 4: off = off_ix(d.NP); break; case 5: off = off_ix(d.NP) + 1; break; case 6: off = off_ix(d.NP) + 2; break; case 7: off = off_td(d.NP); break;
-                            case 10: off = d.GO + k; break; case 11: off = d.GO + 4 * d.NP + k; break; case 12: off = d.GO + 5 * d.NP; break; case 13: off = d.GO + 5 * d.NP + 1; break;
-                            default: off = off_tdw(d.NP); }
-            for (int c = 0; c < gsize_kind(kind); c++) p.x0[xo++] = x[off + c];
-        }
-    }
-    return GF_OK;
+    const int* inf = h->minfo[mode].h + (size_t)b * 4;
+    // the owners fetch J one by one into the host mirror; J == NULL: the prior's J stays on the device (the slot's next gf_ba_pack_slot passes prior_J = NULL)
+    if (prior->J && h->outJ_host_stale && inf[3]) HIPCHK(hipMemcpy(h->outJ.h + (size_t)b * d.NPRI * d.NPRI, h->outJ.d + (size_t)b * d.NPRI * d.NPRI, (size_t)inf[2] * inf[2] * sizeof(double), hipMemcpyDeviceToHost));
+    return unpack_prior(h, b, mode, h->xs0.h + (size_t)b * d.XS, *prior);   // the linearisation point of the prior = the states just uploaded
 }
 
 int gf_ba_debug_upload_bytes(long long* bytes, long long* calls) { if (bytes) *bytes = g_up_bytes; if (calls) *calls = g_up_calls; return GF_OK; }

@@ -448,7 +448,7 @@ __device__ inline void wave_inverse_spd_sqrt(double* M, double* T, int n, int la
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
 }
 
-__device__ __forceinline__ int fblock_of(int id, const Dims& d);
+__host__ __device__ __forceinline__ int fblock_of(int id, const Dims& d);
 __host__ __device__ inline int lsize_kind(int kind);
 __host__ __device__ inline int gsize_kind(int kind);
 
@@ -627,7 +627,7 @@ __device__ __forceinline__ void prior_block_dx(int kind, const double* x, const 
     const double sgn = (dq.w >= 0) ? 2.0 : -2.0;
     dx[3] = sgn * dq.x; dx[4] = sgn * dq.y; dx[5] = sgn * dq.z;
 }
-__device__ __forceinline__ int state_off_of(int id, const Dims& d) {
+__host__ __device__ __forceinline__ int state_off_of(int id, const Dims& d) {
     const int kind = id / 4096, i = id % 4096, NP = d.NP;
     switch (kind) {
         case 0: return off_pose(i); case 1: return off_sb(i); case 2: return off_ex(NP); case 3: return off_exw(NP);
@@ -636,7 +636,7 @@ __device__ __forceinline__ int state_off_of(int id, const Dims& d) {
         default: return off_feat(NP) + i;
     }
 }
-__device__ __forceinline__ int fblock_of(int id, const Dims& d) {
+__host__ __device__ __forceinline__ int fblock_of(int id, const Dims& d) {
     const int kind = id / 4096, i = id % 4096, NP = d.NP;
     switch (kind) {
         case 0: return fb_pose(i); case 1: return fb_sb(i); case 2: return fb_ex(NP); case 3: return fb_exw(NP);

@@ -14,6 +14,8 @@ struct M3 { double m[9]; };  // row-major
 struct Q4 { double w, x, y, z; };
 
 GFD V3 v3(double x, double y, double z) { return V3{x, y, z}; }
+GFD V3 arr3(const double* p) { return v3(p[0], p[1], p[2]); }   // a V3 / an M3 out of a flat table
+GFD M3 arr9(const double* p) { M3 m; for (int i = 0; i < 9; i++) m.m[i] = p[i]; return m; }
 GFD V3 operator+(V3 a, V3 b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
 GFD V3 operator-(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
 GFD V3 operator-(V3 a) { return V3{-a.x, -a.y, -a.z}; }
@@ -38,6 +40,23 @@ GFD M3 operator-(const M3& a, const M3& b) { M3 r; for (int i = 0; i < 9; i++) r
 GFD M3 operator-(const M3& a) { M3 r; for (int i = 0; i < 9; i++) r.m[i] = -a.m[i]; return r; }
 GFD M3 transpose(const M3& a) { M3 r; for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) r.m[3 * i + j] = a.m[3 * j + i]; return r; }
 GFD M3 skew(V3 q) { M3 r = m3_zero(); r.m[1] = -q.z; r.m[2] = q.y; r.m[3] = q.z; r.m[5] = -q.x; r.m[6] = -q.y; r.m[7] = q.x; return r; }  // utility.h:38-46
+
+// Utility::R2ypr / ypr2R in DEGREES (utility/utility.h:78-118)
+GFD V3 R2ypr(const M3& R) {
+    const V3 n = v3(R.m[0], R.m[3], R.m[6]), o = v3(R.m[1], R.m[4], R.m[7]), a = v3(R.m[2], R.m[5], R.m[8]);
+    const double y = atan2(n.y, n.x);
+    const double p = atan2(-n.z, n.x * cos(y) + n.y * sin(y));
+    const double r = atan2(a.x * sin(y) - a.y * cos(y), -o.x * sin(y) + o.y * cos(y));
+    return v3(y / M_PI * 180.0, p / M_PI * 180.0, r / M_PI * 180.0);
+}
+GFD M3 ypr2R(V3 ypr) {
+    const double y = ypr.x / 180.0 * M_PI, p = ypr.y / 180.0 * M_PI, r = ypr.z / 180.0 * M_PI;
+    M3 Rz = m3_zero(), Ry = m3_zero(), Rx = m3_zero();
+    Rz.m[0] = cos(y); Rz.m[1] = -sin(y); Rz.m[3] = sin(y); Rz.m[4] = cos(y); Rz.m[8] = 1;
+    Ry.m[0] = cos(p); Ry.m[2] = sin(p); Ry.m[4] = 1; Ry.m[6] = -sin(p); Ry.m[8] = cos(p);
+    Rx.m[0] = 1; Rx.m[4] = cos(r); Rx.m[5] = -sin(r); Rx.m[7] = sin(r); Rx.m[8] = cos(r);
+    return Rz * Ry * Rx;
+}
 
 GFD Q4 qmul(Q4 a, Q4 b) {
     return Q4{a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y, a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z,

@@ -11,7 +11,7 @@
 //   Estimator::vector2double / double2vector       EST:2276-2353, :2440-2569
 //   Estimator::optimization                        EST:2890-3636 (problem construction -> one gf_ba_window)
 //   Estimator::slideWindow / slideWindowNew / Old  EST:3638-3837
-//   Estimator::predictPtsInNextFrame, movingConsistencyCheckW, reprojectionError(3D)  EST:3862-4010
+//   Estimator::predictPtsInNextFrame, movingConsistencyCheckW  EST:3862-4010 (the arithmetic of a track: gf_featsweep.hpp)
 //   FeatureManager::*                              FM:43-110, :198-302, :669-934, :978-1010
 // Unsupported switches are rejected at create time: ESTIMATE_EXTRINSIC==2, USE_LINE, USE_PLANE, USE_MOTION, STEREO, !USE_IMU.
 #include <algorithm>
@@ -43,6 +43,8 @@
 #include "../../include/groundfusion_hip.h"
 #include "gf_comm.hpp"
 #include "gf_dmath.hpp"
+#include "gf_gnss_models.hpp"
+#include "gf_featsweep.hpp"
 #include "gf_preint.hpp"
 #include "gf_host_cpus.hpp"
 #include "gf_init_sfm.hpp"
@@ -52,27 +54,9 @@ using namespace gfd;
 
 namespace {
 
-V3 arr3(const double* p) { return v3(p[0], p[1], p[2]); }
-M3 arr9(const double* p) { M3 m; for (int i = 0; i < 9; i++) m.m[i] = p[i]; return m; }
 double norm(V3 a) { return sqrt(sqn(a)); }
 V3 normalized(V3 a) { return a / norm(a); }
 
-// Utility::R2ypr / ypr2R in DEGREES (utility/utility.h:78-118)
-V3 R2ypr(const M3& R) {
-    const V3 n = v3(R.m[0], R.m[3], R.m[6]), o = v3(R.m[1], R.m[4], R.m[7]), a = v3(R.m[2], R.m[5], R.m[8]);
-    const double y = atan2(n.y, n.x);
-    const double p = atan2(-n.z, n.x * cos(y) + n.y * sin(y));
-    const double r = atan2(a.x * sin(y) - a.y * cos(y), -o.x * sin(y) + o.y * cos(y));
-    return v3(y / M_PI * 180.0, p / M_PI * 180.0, r / M_PI * 180.0);
-}
-M3 ypr2R(V3 ypr) {
-    const double y = ypr.x / 180.0 * M_PI, p = ypr.y / 180.0 * M_PI, r = ypr.z / 180.0 * M_PI;
-    M3 Rz = m3_zero(), Ry = m3_zero(), Rx = m3_zero();
-    Rz.m[0] = cos(y); Rz.m[1] = -sin(y); Rz.m[3] = sin(y); Rz.m[4] = cos(y); Rz.m[8] = 1;
-    Ry.m[0] = cos(p); Ry.m[2] = sin(p); Ry.m[4] = 1; Ry.m[6] = -sin(p); Ry.m[8] = cos(p);
-    Rx.m[0] = 1; Rx.m[4] = cos(r); Rx.m[5] = -sin(r); Rx.m[7] = sin(r); Rx.m[8] = cos(r);
-    return Rz * Ry * Rx;
-}
 // Utility::g2R (utility/utility.cpp:12-22) with Eigen's Quaterniond::FromTwoVectors (regular branch; the antiparallel branch needs g ≈ -z)
 M3 g2R(V3 g) {
     const V3 v0 = normalized(g), v1 = v3(0, 0, 1);
@@ -122,6 +106,12 @@ struct FeaturePerId {
     int used_num = 0; double estimated_depth = -1.0; int estimate_flag = 0, solve_flag = 0;
     FeaturePerId(int id, int sf) : feature_id(id), start_frame(sf) {}
     int endFrame() const { return start_frame + (int)feature_per_frame.size() - 1; }
+};
+
+struct TrackObs {   // a track's observations as the per-track sweeps read them (gf_featsweep.hpp)
+    const FeaturePerFrame* f;
+    V3 point(int k) const { return f[k].point; }
+    double depth(int k) const { return f[k].depth; }
 };
 
 struct FeatureManager {
@@ -236,28 +226,7 @@ struct FeatureManager {
             it.used_num = (int)it.feature_per_frame.size();
             if (it.used_num < 4) continue;
             if (it.estimated_depth > 0) continue;
-            const int s = it.start_frame, n = (int)it.feature_per_frame.size();
-            double depth_sum = 0.0; size_t cnt = 0;
-            const V3 tr = Ps[s] + Rs[s] * tic; const M3 Rr = Rs[s] * ric;
-            for (int i = 0; i < n; i++) {
-                const V3 t0 = Ps[s + i] + Rs[s + i] * tic; const M3 R0 = Rs[s + i] * ric;
-                const double d = it.feature_per_frame[i].depth;
-                if (d < 0.1 || d > depth_threshold) continue;
-                const V3 point0 = it.feature_per_frame[i].point * d;
-                const V3 t2r = transpose(Rr) * (t0 - tr); const M3 R2r = transpose(Rr) * R0;
-                for (int j = 0; j < n; j++) {
-                    if (i == j) continue;
-                    const V3 t1 = Ps[s + j] + Rs[s + j] * tic; const M3 R1 = Rs[s + j] * ric;
-                    const V3 t20 = transpose(R0) * (t1 - t0); const M3 R20 = transpose(R0) * R1;
-                    const V3 pp = transpose(R20) * point0 - transpose(R20) * t20;
-                    const double rx = it.feature_per_frame[j].point.x - pp.x / pp.z, ry = it.feature_per_frame[j].point.y - pp.y / pp.z;
-                    if (sqrt(rx * rx + ry * ry) < 10.0 / 460) { const V3 pr = R2r * point0 + t2r; depth_sum += pr.z; cnt++; }
-                }
-            }
-            if (cnt == 0) continue;
-            it.estimated_depth = depth_sum / cnt;
-            it.estimate_flag = 1;
-            if (it.estimated_depth < 0.1) { it.estimated_depth = INIT_DEPTH; it.estimate_flag = 0; }
+            track_depth_from_camera(TrackObs{it.feature_per_frame.data()}, it.used_num, it.start_frame, Rs->m, &Ps->x, tic, ric, depth_threshold, INIT_DEPTH, it.estimated_depth, it.estimate_flag);
         }
     }
     void removeOutlier(const std::set<int>& idx) { for (auto it = feature.begin(); it != feature.end();) it = idx.count(it->feature_id) ? feature.erase(it) : std::next(it); }  // FM:801-816
@@ -372,7 +341,6 @@ struct ImageFrame {  // initial/initial_alignment.h:25-40
 // ---------------------------------------------------------------- broadcast ephemerides -> satellite state (gnss_comm eph2pos / geph2pos / eph2svdt / eph2vel,
 // not vendored by the reference: restated from the published broadcast-orbit algorithms, RTKLIB ephemeris.c lineage)
 namespace gnss_eph {
-constexpr double kC = 2.99792458e8;
 constexpr double MU_GPS = 3.9860050e14, MU_GAL = 3.986004418e14, MU_CMP = 3.986004418e14, OMGE_GPS = 7.2921151467e-5, OMGE_GAL = 7.2921151467e-5, OMGE_CMP = 7.292115e-5;
 constexpr double MU_GLO = 3.9860044e14, J2_GLO = 1.0826257e-3, OMGE_GLO = 7.292115e-5, RE_GLO = 6378136.0, TSTEP = 60.0;
 constexpr double SIN_5 = -0.0871557427476582, COS_5 = 0.9961946980917456;   // sin(-5 deg), cos(-5 deg): BeiDou GEO frame
@@ -401,7 +369,7 @@ inline V3 eph2pos(double t, const gf_gnss_ephem& e, double* svdt) {   // IS-GPS-
         const double O = e.OMG0 + (e.OMG_dot - omge) * tk - omge * e.toe_tow, sinO = sin(O), cosO = cos(O);
         rs = v3(x * cosO - y * cosi * sinO, x * sinO + y * cosi * cosO, y * sin(i));
     }
-    if (svdt) { tk = t - e.toc; *svdt = e.af0 + e.af1 * tk + e.af2 * tk * tk - 2.0 * sqrt(mu * e.A) * e.e * sinE / (kC * kC); }
+    if (svdt) { tk = t - e.toc; *svdt = e.af0 + e.af1 * tk + e.af2 * tk * tk - 2.0 * sqrt(mu * e.A) * e.e * sinE / (GN_C * GN_C); }
     return rs;
 }
 inline void glo_deq(const double* x, double* xdot, const double* acc) {
@@ -435,8 +403,8 @@ inline V3 geph2pos(double t, const gf_gnss_glo_ephem& g, double* svdt) {
 // GnssPsrDoppFactor's constructor (gnss_psr_dopp_factor.cpp:3-47)
 inline void sat_state(const gf_gnss_raw_obs& r, const gf_gnss_ephem* e, const gf_gnss_glo_ephem* g, gf_gnss_obs* o) {
     memset(o, 0, sizeof(*o));
-    o->sat = r.sat; o->sys = r.sys; o->time = r.time; o->psr = r.psr; o->dopp = r.dopp; o->psr_std = r.psr_std; o->dopp_std = r.dopp_std; o->wavelength = kC / r.freq; o->tow = r.tow;
-    double sv_tx = r.time - r.psr / kC, svdt, svddt, d1, d2;
+    o->sat = r.sat; o->sys = r.sys; o->time = r.time; o->psr = r.psr; o->dopp = r.dopp; o->psr_std = r.psr_std; o->dopp_std = r.dopp_std; o->wavelength = GN_C / r.freq; o->tow = r.tow;
+    double sv_tx = r.time - r.psr / GN_C, svdt, svddt, d1, d2;
     V3 p, p2;
     const double tt = 1e-3;   // eph2vel / geph2vel: difference quotient over 1 ms, position and clock alike
     if (g) {
@@ -803,57 +771,9 @@ struct gf_estimator {
         GNSSBuf.pop_front();
         return true;
     }
-    static V3 ecef2geo(V3 p) {   // gnss_comm ecef2geo: latitude [deg], longitude [deg], height [m] (the formulas of gf_ba_gnss.hpp, on the host)
-        if (p.x == 0 && p.y == 0) return v3(0, 0, 0);
-        const double a = 6378137.0, e2 = 6.69437999014e-3, a2 = a * a, b2 = a2 * (1 - e2), b = sqrt(b2), ep2 = (a2 - b2) / b2, rho = sqrt(p.x * p.x + p.y * p.y);
-        double s1 = p.z * a, s2 = rho * b, h = sqrt(s1 * s1 + s2 * s2);
-        const double st = s1 / h, ct = s2 / h;
-        s1 = p.z + ep2 * b * st * st * st; s2 = rho - a * e2 * ct * ct * ct; h = sqrt(s1 * s1 + s2 * s2);
-        const double sin_lat = s1 / h, cos_lat = s2 / h, N = a2 / sqrt(a2 * cos_lat * cos_lat + b2 * sin_lat * sin_lat);
-        return v3(atan(s1 / s2) * 180.0 / M_PI, atan2(p.y, p.x) * 180.0 / M_PI, rho / cos_lat - N);
-    }
-    static M3 ecef2rotation(V3 p) {   // gnss_comm ecef2rotation = geo2rotation(ecef2geo(p)): R_ecef_enu
-        const V3 lla = ecef2geo(p);
-        const double lat = lla.x * M_PI / 180.0, lon = lla.y * M_PI / 180.0, sl = sin(lat), cl = cos(lat), so = sin(lon), co = cos(lon);
-        M3 R;
-        R.m[0] = -so; R.m[1] = -sl * co; R.m[2] = cl * co; R.m[3] = co; R.m[4] = -sl * so; R.m[5] = cl * so; R.m[6] = 0; R.m[7] = cl; R.m[8] = sl;
-        return R;
-    }
-    static double sat_elevation(V3 rcv, V3 sat) {   // gnss_comm sat_azel, elevation only
-        V3 dl = sat - rcv; dl = dl / norm(dl);
-        return asin((transpose(ecef2rotation(rcv)) * dl).z);
-    }
     // ---- GNSSVIInitializer (initial/gnss_vi_initializer.cpp) on the satellite states carried by gf_gnss_obs.  Its three gnss_comm callees -- psr_pos, psr_res,
     // dopp_res (gnss_spp.cpp; gnss_comm is not vendored by the reference) -- are restated from their published form with the measurement model of
     // GnssPsrDoppFactor::Evaluate (gnss_psr_dopp_factor.cpp:76-101): unweighted residuals, Jacobian rows [-unit(rcv -> sat), 1 on the system's clock].
-    static double trop_delay(V3 lla, double el) {   // Saastamoinen, standard atmosphere, humidity 0.7 (as gf_ba_gnss.hpp)
-        if (lla.z < -100.0 || 1e4 < lla.z || el <= 0) return 0.0;
-        const double hgt = lla.z < 0.0 ? 0.0 : lla.z;
-        const double pres = 1013.25 * pow(1.0 - 2.2557e-5 * hgt, 5.2568), temp = 15.0 - 6.5e-3 * hgt + 273.16;
-        const double e = 6.108 * 0.7 * exp((17.15 * temp - 4684.0) / (temp - 38.45)), z = M_PI / 2.0 - el;
-        return 0.0022768 * pres / (1.0 - 0.00266 * cos(2.0 * lla.x * M_PI / 180.0) - 0.00028 * hgt / 1e3) / cos(z) + 0.002277 * (1255.0 / temp + 0.05) * e / cos(z);
-    }
-    static double ion_delay(double tow, const double* ion_in, V3 lla, double az, double el) {   // Klobuchar (as gf_ba_gnss.hpp)
-        const double ion_default[8] = {0.1118e-07, -0.7451e-08, -0.5961e-07, 0.1192e-06, 0.1167e+06, -0.2294e+06, -0.1311e+06, 0.1049e+07};
-        if (lla.z < -1e3 || el <= 0) return 0.0;
-        double nrm = 0;
-        for (int i = 0; i < 8; i++) nrm += ion_in[i] * ion_in[i];
-        double ion[8];
-        for (int i = 0; i < 8; i++) ion[i] = nrm <= 0.0 ? ion_default[i] : ion_in[i];
-        const double psi = 0.0137 / (el / M_PI + 0.11) - 0.022;
-        double phi = lla.x / 180.0 + psi * cos(az);
-        if (phi > 0.416) phi = 0.416; else if (phi < -0.416) phi = -0.416;
-        const double lam = lla.y / 180.0 + psi * sin(az) / cos(phi * M_PI);
-        phi += 0.064 * cos((lam - 1.617) * M_PI);
-        double tt = 43200.0 * lam + tow;
-        tt -= floor(tt / 86400.0) * 86400.0;
-        const double f = 1.0 + 16.0 * pow(0.53 - el / M_PI, 3.0);
-        double amp = ion[0] + phi * (ion[1] + phi * (ion[2] + phi * ion[3])), per = ion[4] + phi * (ion[5] + phi * (ion[6] + phi * ion[7]));
-        amp = amp < 0.0 ? 0.0 : amp; per = per < 72000.0 ? 72000.0 : per;
-        const double x = 2.0 * M_PI * (tt - 50400.0) / per;
-        return 2.99792458e8 * f * (fabs(x) < 1.57 ? 5e-9 + amp * (1.0 + x * x * (-0.5 + x * x / 24.0)) : 5e-9);
-    }
-    static constexpr double kC = 2.99792458e8, kOmg = 7.2921151467e-5;
     // psr_res: residual and Jacobian row (7: position 3, clock bias per system 4) of every observation of an epoch at receiver state xyzt
     void psr_res(const double* xyzt, const std::vector<gf_gnss_obs>& meas, std::vector<double>& res, std::vector<double>& J) const {
         const V3 rcv = arr3(xyzt);
@@ -861,17 +781,14 @@ struct gf_estimator {
             const V3 sv = arr3(o.sv_pos);
             double ion = 0, tro = 0;
             if (norm(rcv) > 0) {
-                const V3 lla = ecef2geo(rcv);
-                V3 dl = sv - rcv; dl = dl / norm(dl);
-                const V3 enu = transpose(ecef2rotation(rcv)) * dl;
-                double az = sqrt(dl.x * dl.x + dl.y * dl.y) < 1e-12 ? 0.0 : atan2(enu.x, enu.y);
-                if (az < 0) az += 2 * M_PI;
-                const double el = asin(enu.z);
-                tro = trop_delay(lla, el); ion = ion_delay(o.tow, gnss_iono.data(), lla, az, el);
+                const V3 lla = gn_ecef2geo(rcv);
+                double az, el;
+                gn_sat_azel(rcv, sv, az, el);
+                tro = gn_trop_delay(lla, el); ion = gn_ion_delay(o.tow, gnss_iono.data(), lla, az, el);
             }
             const V3 r2s = sv - rcv;
             const double rg = norm(r2s);
-            const double est = rg + kOmg * (sv.x * rcv.y - sv.y * rcv.x) / kC + xyzt[3 + o.sys] - o.svdt * kC + ion + tro + o.tgd * kC;
+            const double est = rg + GN_OMG * (sv.x * rcv.y - sv.y * rcv.x) / GN_C + xyzt[3 + o.sys] - o.svdt * GN_C + ion + tro + o.tgd * GN_C;
             res.push_back(est - o.psr);
             double row[7] = {-r2s.x / rg, -r2s.y / rg, -r2s.z / rg, 0, 0, 0, 0};
             row[3 + o.sys] = 1.0;
@@ -885,8 +802,8 @@ struct gf_estimator {
             const V3 sv = arr3(o.sv_pos), svv = arr3(o.sv_vel);
             const V3 r2s = sv - rcv;
             const V3 unit = r2s / norm(r2s);
-            const double sag = kOmg / kC * (svv.x * rcv.y + sv.x * vel.y - svv.y * rcv.x - sv.y * vel.x);
-            const double est = dot(svv - vel, unit) + vel_ddt[3] + sag - o.svddt * kC;
+            const double sag = GN_OMG / GN_C * (svv.x * rcv.y + sv.x * vel.y - svv.y * rcv.x - sv.y * vel.x);
+            const double est = dot(svv - vel, unit) + vel_ddt[3] + sag - o.svddt * GN_C;
             res.push_back(est + o.dopp * o.wavelength);
             J.insert(J.end(), {-unit.x, -unit.y, -unit.z, 1.0});
         }
@@ -941,7 +858,7 @@ struct gf_estimator {
         // 2. yaw_alignment (gnss_vi_initializer.cpp:43-104)
         {
             const V3 anchor = arr3(rough_xyzt);
-            const M3 Ree = ecef2rotation(anchor);
+            const M3 Ree = gn_geo2rotation(gn_ecef2geo(anchor));
             double est_yaw = 0, est_ddt = 0, dxn = 1.0; int it = 0;
             while (it < 10 && dxn > 1e-5) {
                 std::vector<double> G, b;
@@ -972,7 +889,7 @@ struct gf_estimator {
             double dxn = 1.0; int it = 0;
             while (it < 10 && dxn > 1e-5) {
                 std::vector<double> G, b;
-                const M3 Ree = ecef2rotation(anchor);
+                const M3 Ree = gn_geo2rotation(gn_ecef2geo(anchor));
                 for (int i = 0; i < NPW; i++) {
                     const V3 p = Ps[i];
                     const V3 pe = Ree * v3(cy * p.x - sy_ * p.y, sy_ * p.x + cy * p.y, p.z) + anchor;
@@ -1012,7 +929,9 @@ struct gf_estimator {
             if (sat_track_status[obs.sat] < cfg.gnss_track_num_thres) continue;                   // :1511-1512
             if (gnss_ready) {                                                                     // :1515-1526: the satellite at the reception time when the ephemeris is here
                 const V3 sat_ecef = m.is_raw ? (geph ? gnss_eph::geph2pos(obs.time, *geph, nullptr) : gnss_eph::eph2pos(obs.time, *eph, nullptr)) : arr3(obs.sv_pos);
-                if (sat_elevation(ecef_pos, sat_ecef) < cfg.gnss_elevation_thres * M_PI / 180.0) continue;
+                double az, el;
+                gn_sat_azel(ecef_pos, sat_ecef, az, el);
+                if (el < cfg.gnss_elevation_thres * M_PI / 180.0) continue;
             }
             if (m.is_raw) { gf_gnss_obs st; gnss_eph::sat_state(m.raw, eph, geph, &st); valid_meas.push_back(st); }   // what the factor's constructor derives (gnss_psr_dopp_factor.cpp:3-47)
             else valid_meas.push_back(obs);
@@ -1037,7 +956,7 @@ struct gf_estimator {
             para_rcv_ddt[i] = ddt;
             for (int k = 0; k < 4; k++) para_rcv_dt[4 * i + k] = (rough[3 + k] == 0 ? (one_observed_sys < 0 ? 0.0 : refined[3 + one_observed_sys]) : refined[3 + k]) + ddt * i;
         }
-        anc_ecef = arr3(refined); R_ecef_enu = ecef2rotation(anc_ecef); yaw_enu_local = yaw;
+        anc_ecef = arr3(refined); R_ecef_enu = gn_geo2rotation(gn_ecef2geo(anc_ecef)); yaw_enu_local = yaw;
         return true;
     }
     void updateGNSSStatistics() {  // EST:2045-2058
@@ -1557,7 +1476,7 @@ struct gf_estimator {
         }
         f_manager.setDepth(para_Feature.data());
         td = para_Td[0];
-        if (gnss_ready) { yaw_enu_local = para_yaw_enu_local[0]; anc_ecef = arr3(para_anc_ecef); R_ecef_enu = ecef2rotation(anc_ecef); }   // :2562-2568
+        if (gnss_ready) { yaw_enu_local = para_yaw_enu_local[0]; anc_ecef = arr3(para_anc_ecef); R_ecef_enu = gn_geo2rotation(gn_ecef2geo(anc_ecef)); }   // :2562-2568
         return GF_OK;
     }
     int optimization() {  // EST:2890-3636
@@ -1796,17 +1715,6 @@ struct gf_estimator {
             f_manager.removeBackShiftDepth(R0, P0, R1, P1);
         } else f_manager.removeBack();
     }
-    double reprojectionError(const M3& Ri, V3 Pi, const M3& Rj, V3 Pj, double depth, V3 uvi, V3 uvj) const {  // EST:3899-3910
-        const V3 pts_w = Ri * (ric * (uvi * depth) + tic) + Pi;
-        const V3 pts_cj = transpose(ric) * (transpose(Rj) * (pts_w - Pj) - tic);
-        const double rx = pts_cj.x / pts_cj.z - uvj.x, ry = pts_cj.y / pts_cj.z - uvj.y;
-        return sqrt(rx * rx + ry * ry);
-    }
-    double reprojectionError3D(const M3& Ri, V3 Pi, const M3& Rj, V3 Pj, double depth, V3 uvi, V3 uvj) const {  // EST:3912-3919
-        const V3 pts_w = Ri * (ric * (uvi * depth) + tic) + Pi;
-        const V3 pts_cj = transpose(ric) * (transpose(Rj) * (pts_w - Pj) - tic);
-        return norm(pts_cj - uvj) / depth;
-    }
     // FeatureManager::triangulateWithDepth (mode 0) or movingConsistencyCheckW (mode 1) of this member as part of the group's batched launch: the window's
     // poses and feature tables go into the member's SweepIn, the rendezvous runs all members' tables at once, the results come back in feature-list order.
     SweepIn sweep_in;
@@ -1845,17 +1753,7 @@ struct gf_estimator {
             if (!(it.used_num >= 2 && it.start_frame < WINDOW_SIZE - 2)) continue;
             const double depth = it.estimated_depth;
             if (depth < 0) continue;
-            double err = 0, err3D = 0; int errCnt = 0;
-            const int wi = it.start_frame; int wj = wi - 1;
-            const V3 pts_i = it.feature_per_frame[0].point;
-            for (auto& fr : it.feature_per_frame) {
-                wj++;
-                if (wi == wj) continue;
-                err += reprojectionError(Rs[wi], Ps[wi], Rs[wj], Ps[wj], depth, pts_i, fr.point);
-                err3D += reprojectionError3D(Rs[wi], Ps[wi], Rs[wj], Ps[wj], depth, pts_i, fr.point);
-                errCnt++;
-            }
-            if (errCnt > 0 && (cfg.focal_length * err / errCnt > 10 || err3D / errCnt > 2.0)) removeIndex.insert(it.feature_id);
+            if (track_is_moving(TrackObs{it.feature_per_frame.data()}, it.used_num, it.start_frame, Rs[0].m, &Ps[0].x, tic, ric, depth, cfg.focal_length)) removeIndex.insert(it.feature_id);
         }
     }
     void predictPtsInNextFrame() {  // EST:3862-3897; nextT = curT * (prevT^-1 * curT) on rigid transforms
@@ -2316,11 +2214,7 @@ int gf_estimator_group_create(const gf_estimator_cfg* c, int n, gf_estimator_gro
     (void)hipGetDevice(&g->device);
     // worker threads: half of the hardware threads this PROCESS may run on (its affinity mask: a process confined by taskset / cgroups to 8 threads sizes its pool for
     // 8, not for the 256 the box has), divided among the ranks that share the node
-    int hw_box = 0, hw = 0;
-    gf::host_cpus(hw_box, hw);   // affinity mask AND the container's CPU quota (gf_host_cpus.hpp): the boxes of round 6 show 256 hardware threads and grant 16
-    int share = 1;
-    // a launcher that pins every rank to its part of the node (numactl, cgroups, torchrun binding) has divided already: the mask IS the rank's share (round-5 advisor)
-    if (const char* e = getenv("LOCAL_WORLD_SIZE")) if (hw_box <= 0 || hw >= hw_box) share = std::max(1, atoi(e));
+    const auto [hw, share] = gf::rank_host_share();   // affinity mask AND the container's CPU quota (gf_host_cpus.hpp): the boxes of round 6 show 256 hardware threads and grant 16
     // Twice as many workers as the rank can run in parallel, at most 32: a group step is three short host phases between two device batches and a worker mostly sleeps on
     // the batch its members wait for, so a modest oversubscription pays; far beyond the quota the threads are throttled, not run (round 6, honest clock, 16-core quota, one
     // group of 256: 8 workers 15.6 k window-solves/s, 16: 22.8 k, 32: 33.3 k, 128: 20.0 k; two groups: 2 x 8: 22.6 k, 2 x 16: 34.6-45.4 k, 2 x 32: 40.6-44.6 k, 2 x 64: 28.3 k)

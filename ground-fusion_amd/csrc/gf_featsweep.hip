@@ -1,7 +1,8 @@
 // gf_featsweep.hip — the per-feature sweeps of the measurement side for many windows at once on the device:
 //   FeatureManager::triangulateWithDepth   feature_manager.cpp:726-799   (depth of a track from its depth-camera observations, cross-checked between frames)
 //   Estimator::movingConsistencyCheckW     estimator.cpp:3955-3995 with reprojectionError / reprojectionError3D :3899-3919
-// One thread per feature, the loops of the host code (gf_estimator.hip) in the same order without contraction: decisions and depths are bit-identical to the host's.
+// One thread per feature.  The arithmetic of a track is gf_featsweep.hpp, the source the estimator's host loops (gf_estimator.hip) compile too, both without
+// contraction: decisions and depths are bit-identical to the host's.
 // Building blocks with their own C-ABI; the estimator keeps these sweeps on its host threads (0.03 ms of one core per frame, and a device launch
 // would need one more rendezvous of the group's threads).
 #include <algorithm>
@@ -10,7 +11,7 @@
 #include <vector>
 #include <hip/hip_runtime.h>
 #include "../../include/groundfusion_hip.h"
-#include "gf_dmath.hpp"
+#include "gf_featsweep.hpp"
 
 namespace gf { int set_err(int code, const char* fmt, ...); }
 using namespace gfd;
@@ -24,8 +25,11 @@ struct SweepArgs {
     double* estimated_depth; int* estimate_flag; int* remove;
     double depth_threshold, init_depth, focal_length;
 };
-__device__ __forceinline__ V3 ld3(const double* p) { return v3(p[0], p[1], p[2]); }
-__device__ __forceinline__ M3 ld9(const double* p) { M3 m; for (int i = 0; i < 9; i++) m.m[i] = p[i]; return m; }
+struct FlatObs {   // a track's rows of the [x, y, z, depth] table
+    const double* p;
+    GFD V3 point(int k) const { return arr3(p + 4 * (size_t)k); }
+    GFD double depth(int k) const { return p[4 * (size_t)k + 3]; }
+};
 __device__ int window_of(const int* first_feature, int B, int f) {   // largest b with first_feature[b] <= f
     int lo = 0, hi = B - 1;
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (first_feature[mid] <= f) lo = mid; else hi = mid - 1; }
@@ -39,34 +43,9 @@ __global__ void __launch_bounds__(128) triangulate_with_depth_kernel(SweepArgs A
     const int o0 = A.first_obs[f], n = A.first_obs[f + 1] - o0, s = A.start_frame[f];
     if (n < 4) return;
     if (A.estimated_depth[f] > 0) return;
-    const double* Rsb = A.Rs + (size_t)b * (A.W + 1) * 9; const double* Psb = A.Ps + (size_t)b * (A.W + 1) * 3;
-    const V3 tic = ld3(A.tic + 3 * b); const M3 ric = ld9(A.ric + 9 * b);
-    double depth_sum = 0.0; unsigned cnt = 0;
-    const M3 Rs_s = ld9(Rsb + 9 * s);
-    const V3 tr = ld3(Psb + 3 * s) + Rs_s * tic; const M3 Rr = Rs_s * ric;
-    for (int i = 0; i < n; i++) {
-        const M3 Rsi = ld9(Rsb + 9 * (s + i));
-        const V3 t0 = ld3(Psb + 3 * (s + i)) + Rsi * tic; const M3 R0 = Rsi * ric;
-        const double* oi = A.obs + 4 * (size_t)(o0 + i);
-        const double d = oi[3];
-        if (d < 0.1 || d > A.depth_threshold) continue;
-        const V3 point0 = ld3(oi) * d;
-        const V3 t2r = transpose(Rr) * (t0 - tr); const M3 R2r = transpose(Rr) * R0;
-        for (int j = 0; j < n; j++) {
-            if (i == j) continue;
-            const M3 Rsj = ld9(Rsb + 9 * (s + j));
-            const V3 t1 = ld3(Psb + 3 * (s + j)) + Rsj * tic; const M3 R1 = Rsj * ric;
-            const V3 t20 = transpose(R0) * (t1 - t0); const M3 R20 = transpose(R0) * R1;
-            const V3 pp = transpose(R20) * point0 - transpose(R20) * t20;
-            const double* oj = A.obs + 4 * (size_t)(o0 + j);
-            const double rx = oj[0] - pp.x / pp.z, ry = oj[1] - pp.y / pp.z;
-            if (sqrt(rx * rx + ry * ry) < 10.0 / 460) { const V3 pr = R2r * point0 + t2r; depth_sum += pr.z; cnt++; }
-        }
-    }
-    if (cnt == 0) return;
-    double e = depth_sum / cnt;
-    int flag = 1;
-    if (e < 0.1) { e = A.init_depth; flag = 0; }
+    double e; int flag;
+    if (!track_depth_from_camera(FlatObs{A.obs + 4 * (size_t)o0}, n, s, A.Rs + (size_t)b * (A.W + 1) * 9, A.Ps + (size_t)b * (A.W + 1) * 3, arr3(A.tic + 3 * b), arr9(A.ric + 9 * b),
+                                 A.depth_threshold, A.init_depth, e, flag)) return;
     A.estimated_depth[f] = e; A.estimate_flag[f] = flag;
 }
 
@@ -79,29 +58,8 @@ __global__ void __launch_bounds__(128) moving_consistency_kernel(SweepArgs A) {
     if (!(n >= 2 && wi < A.W - 2)) return;
     const double depth = A.estimated_depth[f];
     if (depth < 0) return;
-    const double* Rsb = A.Rs + (size_t)b * (A.W + 1) * 9; const double* Psb = A.Ps + (size_t)b * (A.W + 1) * 3;
-    const V3 tic = ld3(A.tic + 3 * b); const M3 ric = ld9(A.ric + 9 * b);
-    const M3 Ri = ld9(Rsb + 9 * wi); const V3 Pi = ld3(Psb + 3 * wi);
-    const V3 uvi = ld3(A.obs + 4 * (size_t)o0);
-    double err = 0, err3D = 0; int errCnt = 0;
-    for (int k = 1; k < n; k++) {
-        const int wj = wi + k;
-        const M3 Rj = ld9(Rsb + 9 * wj); const V3 Pj = ld3(Psb + 3 * wj);
-        const V3 uvj = ld3(A.obs + 4 * (size_t)(o0 + k));
-        {   // reprojectionError
-            const V3 pts_w = Ri * (ric * (uvi * depth) + tic) + Pi;
-            const V3 pts_cj = transpose(ric) * (transpose(Rj) * (pts_w - Pj) - tic);
-            const double rx = pts_cj.x / pts_cj.z - uvj.x, ry = pts_cj.y / pts_cj.z - uvj.y;
-            err += sqrt(rx * rx + ry * ry);
-        }
-        {   // reprojectionError3D
-            const V3 pts_w = Ri * (ric * (uvi * depth) + tic) + Pi;
-            const V3 pts_cj = transpose(ric) * (transpose(Rj) * (pts_w - Pj) - tic);
-            err3D += sqrt(sqn(pts_cj - uvj)) / depth;
-        }
-        errCnt++;
-    }
-    if (errCnt > 0 && (A.focal_length * err / errCnt > 10 || err3D / errCnt > 2.0)) A.remove[f] = 1;
+    if (track_is_moving(FlatObs{A.obs + 4 * (size_t)o0}, n, wi, A.Rs + (size_t)b * (A.W + 1) * 9, A.Ps + (size_t)b * (A.W + 1) * 3, arr3(A.tic + 3 * b), arr9(A.ric + 9 * b), depth,
+                        A.focal_length)) A.remove[f] = 1;
 }
 
 template <class T> struct DevArr {

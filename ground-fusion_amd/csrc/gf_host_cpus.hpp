@@ -36,4 +36,17 @@ inline void host_cpus(int& box, int& usable) {
     usable = std::max(usable, 1);
 }
 
+// What one rank of a multi-rank job may size its thread pools from: hw, the hardware threads this process can use, and share, the number of ranks that divide them.
+// LOCAL_WORLD_SIZE divides only when the mask is the whole machine: a launcher that pins every rank to its part of the node (numactl, cgroups, torchrun binding) has
+// divided already, the mask IS the rank's share.  A cgroup quota below the box also counts as "divided already" here although every rank of the node draws on it:
+// whether a quota should still be divided among the ranks is decided in this one place.
+struct HostShare { int hw, share; };
+inline HostShare rank_host_share() {
+    int box = 0, hw = 0;
+    host_cpus(box, hw);
+    int share = 1;
+    if (const char* e = getenv("LOCAL_WORLD_SIZE")) if (box <= 0 || hw >= box) share = std::max(1, atoi(e));
+    return HostShare{hw, share};
+}
+
 }  // namespace gf

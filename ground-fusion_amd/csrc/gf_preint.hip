@@ -23,26 +23,6 @@ template <int R, int C> struct DM {  // tiny dense row-major matrix on the stack
 template <int R, int K, int C> DM<R, C> mul(const DM<R, K>& x, const DM<K, C>& y) { DM<R, C> o; for (int i = 0; i < R; i++) for (int k = 0; k < K; k++) { const double v = x(i, k); if (v != 0.0) for (int j = 0; j < C; j++) o(i, j) += v * y(k, j); } return o; }
 template <int R, int C> DM<C, R> tr(const DM<R, C>& x) { DM<C, R> o; for (int i = 0; i < R; i++) for (int j = 0; j < C; j++) o(j, i) = x(i, j); return o; }
 template <int R, int C> DM<R, C> add(const DM<R, C>& x, const DM<R, C>& y) { DM<R, C> o; for (int i = 0; i < R * C; i++) o.a[i] = x.a[i] + y.a[i]; return o; }
-V3 arr(const double* p) { return v3(p[0], p[1], p[2]); }
-}  // namespace
-
-namespace {
-// Utility::R2ypr / ypr2R work in DEGREES (utility/utility.h:78-118)
-V3 R2ypr(const M3& R) {
-    const V3 n = v3(R.m[0], R.m[3], R.m[6]), o = v3(R.m[1], R.m[4], R.m[7]), a = v3(R.m[2], R.m[5], R.m[8]);
-    const double y = atan2(n.y, n.x);
-    const double p = atan2(-n.z, n.x * cos(y) + n.y * sin(y));
-    const double r = atan2(a.x * sin(y) - a.y * cos(y), -o.x * sin(y) + o.y * cos(y));
-    return v3(y / M_PI * 180.0, p / M_PI * 180.0, r / M_PI * 180.0);
-}
-M3 ypr2R(V3 ypr) {
-    const double y = ypr.x / 180.0 * M_PI, p = ypr.y / 180.0 * M_PI, r = ypr.z / 180.0 * M_PI;
-    M3 Rz = m3_zero(), Ry = m3_zero(), Rx = m3_zero();
-    Rz.m[0] = cos(y); Rz.m[1] = -sin(y); Rz.m[3] = sin(y); Rz.m[4] = cos(y); Rz.m[8] = 1;
-    Ry.m[0] = cos(p); Ry.m[2] = sin(p); Ry.m[4] = 1; Ry.m[6] = -sin(p); Ry.m[8] = cos(p);
-    Rx.m[0] = 1; Rx.m[4] = cos(r); Rx.m[5] = -sin(r); Rx.m[7] = sin(r); Rx.m[8] = cos(r);
-    return Rz * Ry * Rx;
-}
 }  // namespace
 
 extern "C" {
@@ -53,7 +33,7 @@ int gf_ba_double2vector(int W, const double* R0_before, const double* P0_before,
                         double* Vs, double* Bas, double* Bgs) {
     if (W < 0 || !R0_before || !P0_before || !para_Pose || !para_SpeedBias || !Rs || !Ps || !Vs || !Bas || !Bgs) return gf::set_err(GF_ERR_INVALID, "bad argument");
     M3 R0; for (int i = 0; i < 9; i++) R0.m[i] = R0_before[i];
-    const V3 origin_R0 = R2ypr(R0), origin_P0 = arr(P0_before);
+    const V3 origin_R0 = R2ypr(R0), origin_P0 = arr3(P0_before);
     const M3 R00m = qmat(Q4{para_Pose[6], para_Pose[3], para_Pose[4], para_Pose[5]});
     const V3 origin_R00 = R2ypr(R00m);
     const double y_diff = origin_R0.x - origin_R00.x;
@@ -88,12 +68,12 @@ void imu_preint_reset(ImuPreState& st, const double* acc0, const double* gyr0) {
 // arithmetic (two 15 x 15 x 15 and two 15 x 18 products per sample).  Same operations in the same order as imu_preint_range: the same bits.  For callers that read nothing
 // else -- Estimator::checkimu (estimator.cpp:2173-2216) looks at delta_v / sum_dt of every frame of all_image_frame on every image.
 void imu_preint_state_range(ImuPreState& st, const double* ba, const double* bg, const double* dt, const double* acc, const double* gyr, int s0, int s1) {
-    V3 acc_0 = arr(st.acc_0), gyr_0 = arr(st.gyr_0), lba = arr(ba), lbg = arr(bg), dp = arr(st.dp), dv = arr(st.dv);
+    V3 acc_0 = arr3(st.acc_0), gyr_0 = arr3(st.gyr_0), lba = arr3(ba), lbg = arr3(bg), dp = arr3(st.dp), dv = arr3(st.dv);
     Q4 dq{st.dq[0], st.dq[1], st.dq[2], st.dq[3]};
     double sdt = st.sum_dt;
     for (int s = s0; s < s1; s++) {
         const double t = dt[s];
-        const V3 acc_1 = arr(acc + 3 * s), gyr_1 = arr(gyr + 3 * s);
+        const V3 acc_1 = arr3(acc + 3 * s), gyr_1 = arr3(gyr + 3 * s);
         const V3 un_acc_0 = qrot(dq, acc_0 - lba);
         const V3 un_gyr = (gyr_0 + gyr_1) * 0.5 - lbg;
         const Q4 rq = qmul(dq, Q4{1, un_gyr.x * t / 2, un_gyr.y * t / 2, un_gyr.z * t / 2});
@@ -109,7 +89,7 @@ void imu_preint_state_range(ImuPreState& st, const double* ba, const double* bg,
     st.sum_dt = sdt; st.n_done = s1;
 }
 void imu_preint_range(ImuPreState& st, const double* ba, const double* bg, const double* noise, const double* dt, const double* acc, const double* gyr, int s0, int s1) {
-    V3 acc_0 = arr(st.acc_0), gyr_0 = arr(st.gyr_0), lba = arr(ba), lbg = arr(bg), dp = arr(st.dp), dv = arr(st.dv);
+    V3 acc_0 = arr3(st.acc_0), gyr_0 = arr3(st.gyr_0), lba = arr3(ba), lbg = arr3(bg), dp = arr3(st.dp), dv = arr3(st.dv);
     Q4 dq{st.dq[0], st.dq[1], st.dq[2], st.dq[3]};
     DM<15, 15> J, P; DM<18, 18> N;
     memcpy(J.a, st.J, sizeof J.a); memcpy(P.a, st.P, sizeof P.a);
@@ -120,7 +100,7 @@ void imu_preint_range(ImuPreState& st, const double* ba, const double* bg, const
     double sdt = st.sum_dt;
     for (int s = s0; s < s1; s++) {
         const double t = dt[s];
-        const V3 acc_1 = arr(acc + 3 * s), gyr_1 = arr(gyr + 3 * s);
+        const V3 acc_1 = arr3(acc + 3 * s), gyr_1 = arr3(gyr + 3 * s);
         const V3 un_acc_0 = qrot(dq, acc_0 - lba);
         const V3 un_gyr = (gyr_0 + gyr_1) * 0.5 - lbg;
         const Q4 rq = qmul(dq, Q4{1, un_gyr.x * t / 2, un_gyr.y * t / 2, un_gyr.z * t / 2});
@@ -417,7 +397,7 @@ int gf_imu_preintegrate_state(int n, const double* dt, const double* acc, const 
 int gf_wheel_preintegrate(int n, const double* dt, const double* vel, const double* gyr, const double* vel0, const double* gyr0, const double* lin, const double* noise,
                           double* delta_p, double* delta_q, double* jacobian, double* covariance, double* sum_dt) {
     if (n < 0 || !vel0 || !gyr0 || !lin || !noise) return gf::set_err(GF_ERR_INVALID, "bad argument");
-    V3 vel_0 = arr(vel0), gyr_0 = arr(gyr0), dp = v3(0, 0, 0);
+    V3 vel_0 = arr3(vel0), gyr_0 = arr3(gyr0), dp = v3(0, 0, 0);
     Q4 dq{1, 0, 0, 0};
     const double sx = lin[0], sy = lin[1], sw = lin[2];
     DM<6, 3> Jm; DM<6, 6> P; DM<12, 12> N;
@@ -426,7 +406,7 @@ int gf_wheel_preintegrate(int n, const double* dt, const double* vel, const doub
     const M3 sv = m3_diag(sx, sy, 1), I = m3_identity(), I1 = m3_diag(1, 0, 0), I2 = m3_diag(0, 1, 0);
     for (int s = 0; s < n; s++) {
         const double t = dt[s];
-        const V3 vel_1 = arr(vel + 3 * s), gyr_1 = arr(gyr + 3 * s);
+        const V3 vel_1 = arr3(vel + 3 * s), gyr_1 = arr3(gyr + 3 * s);
         const V3 un_vel_0 = qrot(dq, sv * vel_0);
         const V3 un_gyr = (gyr_0 + gyr_1) * (0.5 * sw);
         const Q4 ddq{1, un_gyr.x * t / 2, un_gyr.y * t / 2, un_gyr.z * t / 2};

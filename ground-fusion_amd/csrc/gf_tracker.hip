@@ -740,11 +740,7 @@ int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out) {
     for (int b = 0; b < h->B; b++) h->ident[b] = b;
     {
         // default: up to 16 threads out of this rank's share of the node (a frame of 256 sequences spends 1.3 ms in the bookkeeping with 4 threads, 0.5 ms with 16)
-        int share = 1;
-        int hw_box = 0, hw = 0;   // ... of the hardware threads this process can really use (its affinity mask and its container's CPU quota, not the box: gf_host_cpus.hpp)
-        gf::host_cpus(hw_box, hw);
-        // divide among the node's ranks only when the mask is the whole machine: a launcher that pins each rank has divided already (round-5 advisor)
-        if (const char* e = getenv("LOCAL_WORLD_SIZE")) if (hw_box <= 0 || hw >= hw_box) share = std::max(1, atoi(e));
+        const auto [hw, share] = gf::rank_host_share();   // ... of the hardware threads this process can really use (its affinity mask and its container's CPU quota, not the box)
         int nthr = std::max(1, std::min(16, hw / (2 * share)));
         if (const char* e = getenv("GF_HOST_THREADS")) nthr = atoi(e);
         nthr = std::max(1, std::min(nthr, std::max(hw, 1)));
