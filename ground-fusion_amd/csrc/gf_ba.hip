@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -25,9 +26,7 @@
 #include "gf_copy_list.hpp"
 #include "gf_ba_marg.hpp"
 #include "gf_ba_gnss.hpp"
-
-namespace gf { int set_err(int code, const char* fmt, ...); }
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return gf::set_err(GF_ERR_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+#include "gf_hip_own.hpp"
 
 using namespace gfb;
 
@@ -59,50 +58,54 @@ namespace {
 std::atomic<int> g_alloc_idx{0}, g_alloc_tix{0}, g_alloc_seq_ctr{0};
 thread_local const char* g_alloc_what = nullptr;   // the allocation statement being executed (GF_BA_ALLOC_TRACE=1 prints it next to the allocation's index: what GF_BA_POISON_RANGE counts)
 std::atomic<long long> g_up_bytes{0}, g_up_calls{0};   // host -> device traffic of this process (GF_GROUP_TIMING prints it)
-template <class T> struct Buf {  // device buffer + pinned host mirror
-    T* d = nullptr; T* h = nullptr; size_t n = 0;
-    T* hd = nullptr;   // the host mirror as kernels address it (page-locked memory is mapped into the device's address space), or null
+// GF_BA_POISON (debugging aid): 1: device buffers and LDS, 2: device buffers only, 3: LDS only, 4: device buffers with plausible stale data, 5: device buffers full of
+// 0xFF (every double a NaN, every int -1: a read "masked" by a multiplication with zero shows)
+int poison_mode() { static const int m = getenv("GF_BA_POISON") ? atoi(getenv("GF_BA_POISON")) : 0; return m; }
+// GF_BA_POISON_ELEMS="lo:hi": only these elements of the selected allocation(s) (default: all; scripts/stale_bisect.py narrows a dependence down to an element)
+void poison_elems(size_t count, size_t& lo, size_t& hi) {
+    lo = 0; hi = count;
+    if (const char* e = getenv("GF_BA_POISON_ELEMS")) { lo = std::min<size_t>(count, strtoull(e, nullptr, 10)); hi = strchr(e, ':') ? std::min<size_t>(count, strtoull(strchr(e, ':') + 1, nullptr, 10)) : count; }
+}
+// Device buffer + page-locked host mirror: the owning pair of gf_hip_own.hpp, and around its allocation the back end's debugging aids.
+template <class T> struct Buf {
+    gf::DevBuf<T> dev; gf::PinBuf<T> pin;
+    T* d = nullptr; T* h = nullptr; size_t n = 0;   // dev.p, pin.p (null: no mirror), dev.n as the rest of the file reads them
+    T* hd = nullptr;   // the host mirror as kernels address it, or null
+    void view() { d = dev.p; n = dev.n; h = pin.p; hd = pin.hd; }
     int alloc(size_t count, bool host) {
-        n = count;
         const int g_alloc_seq = g_alloc_seq_ctr++;
-        if (hipMalloc((void**)&d, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) return gf::set_err(GF_ERR_HIP, "hipMalloc(%zu B) failed", count * sizeof(T));
-        // GF_BA_POISON=1 (debugging aid): fresh device buffers start as 0x5A bytes (2.5e130 as a double -- finite, so that garbage x 0 stays 0 --, 1 515 870 810 as an int) instead of whatever the allocator hands back, so that a kernel reading
-        // what nobody wrote shows as NaN in the results instead of as a dependence on the process's history
-        static const int pmode = getenv("GF_BA_POISON") ? atoi(getenv("GF_BA_POISON")) : 0;   // 1: device buffers and LDS, 2: device buffers only, 3: LDS only, 4: device buffers with plausible stale data, 5: device buffers full of 0xFF (every double a NaN, every int -1: a read "masked" by a multiplication with zero shows)
-        static const bool poison = pmode != 0 && pmode != 3;
-        // Every device buffer starts as zeros, explicitly: parts of them are read before anything of THIS handle wrote them (the GNSS cost part of a handle without
-        // GNSS factors, rows beyond what a batch fills, ...) and hipMalloc hands back whatever the previous owner left -- zeros in a fresh process, another handle's
+        // Every device buffer starts as zeros, explicitly (DevBuf::alloc): parts of them are read before anything of THIS handle wrote them (the GNSS cost part of a handle
+        // without GNSS factors, rows beyond what a batch fills, ...) and hipMalloc hands back whatever the previous owner left -- zeros in a fresh process, another handle's
         // tables later in the same process (round 4: a group member and a stand-alone estimator disagreed once an earlier test had used the memory).
-        bool bad = poison;
+        HIPCHK(dev.alloc(count));
+        view();
+        const int pmode = poison_mode();
+        bool bad = pmode != 0 && pmode != 3;
         if (const char* r = getenv("GF_BA_POISON_RANGE")) {   // "lo:hi": only the allocations lo <= index < hi of the process (to find which buffer a kernel reads unwritten)
             // one counter for every element type (a static inside this template would count doubles and ints separately, as it did in round 4)
             const int i = g_alloc_idx++, lo = atoi(r), hi = strchr(r, ':') ? atoi(strchr(r, ':') + 1) : lo + 1;
             bad = i >= lo && i < hi;
         }
-        // (hipMemset runs on the null stream and the handle's stream is non-blocking: finished here, before anybody can enqueue a copy into the buffer)
-        if (hipMemset(d, (bad && pmode != 4 && pmode != 5) ? 0x5A : 0, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) return gf::set_err(GF_ERR_HIP, "hipMemset failed");
-        if (bad && pmode == 5 && count > 0) {   // 0xFF over the elements GF_BA_POISON_ELEMS names (default: all)
-            size_t lo = 0, hi = count;
-            if (const char* e = getenv("GF_BA_POISON_ELEMS")) { lo = std::min<size_t>(count, strtoull(e, nullptr, 10)); hi = strchr(e, ':') ? std::min<size_t>(count, strtoull(strchr(e, ':') + 1, nullptr, 10)) : count; }
-            if (hi > lo && (hipMemset(reinterpret_cast<char*>(d) + lo * sizeof(T), 0xFF, (hi - lo) * sizeof(T)) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess)) return gf::set_err(GF_ERR_HIP, "hipMemset failed");
-        }
-        if (bad && pmode == 4 && count > 0 && (std::is_same<T, double>::value || std::is_same<T, int>::value)) {
+        // The poison fills run on the null stream like the zero fill before them: finished here, before anybody can enqueue a copy into the buffer.
+        // Modes 1 and 2: 0x5A bytes (2.5e130 as a double -- finite, so that garbage x 0 stays 0 --, 1 515 870 810 as an int), so that a kernel reading what nobody wrote shows
+        // as NaN in the results instead of as a dependence on the process's history
+        if (bad && pmode != 4 && pmode != 5) { HIPCHK(hipMemset(d, 0x5A, std::max<size_t>(count, 1) * sizeof(T))); HIPCHK(hipStreamSynchronize(nullptr)); }
+        size_t lo, hi;
+        poison_elems(count, lo, hi);
+        if (bad && pmode == 5 && hi > lo) { HIPCHK(hipMemset(reinterpret_cast<char*>(d) + lo * sizeof(T), 0xFF, (hi - lo) * sizeof(T))); HIPCHK(hipStreamSynchronize(nullptr)); }
+        if (bad && pmode == 4 && hi > lo && (std::is_same<T, double>::value || std::is_same<T, int>::value)) {
             const unsigned seed = 12345u + 7919u * (unsigned)g_alloc_seq;   // a function of the allocation's index in the process: the same content whichever other allocations are poisoned (the bisection relies on it)
-            size_t lo = 0, hi = count;   // GF_BA_POISON_ELEMS="lo:hi": only these elements of the selected allocation(s) (scripts/stale_bisect.py narrows a dependence down to an element)
-            if (const char* e = getenv("GF_BA_POISON_ELEMS")) { lo = std::min<size_t>(count, strtoull(e, nullptr, 10)); hi = strchr(e, ':') ? std::min<size_t>(count, strtoull(strchr(e, ':') + 1, nullptr, 10)) : count; }
-            if (hi > lo) ba_fill_plausible<<<dim3(256), 256, 0, nullptr>>>(d, lo, hi, std::is_same<T, double>::value ? 1 : 0, seed);
-            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) return gf::set_err(GF_ERR_HIP, "plausible fill failed");
+            ba_fill_plausible<<<dim3(256), 256, 0, nullptr>>>(d, lo, hi, std::is_same<T, double>::value ? 1 : 0, seed);
+            HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(nullptr));
         }
         if (getenv("GF_BA_ALLOC_TRACE")) {   // index, statement, size, and the buffer's first and last 8 bytes as they are now (what a poison mode really left there)
             unsigned long long first = 0, last = 0; const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
             if (bytes >= 8) { (void)hipMemcpy(&first, d, 8, hipMemcpyDeviceToHost); (void)hipMemcpy(&last, reinterpret_cast<char*>(d) + ((bytes - 8) & ~(size_t)7), 8, hipMemcpyDeviceToHost); }
             fprintf(stderr, "gf_ba alloc %d: %s  %zu x %zu B%s  first %016llx last %016llx\n", g_alloc_tix++, g_alloc_what ? g_alloc_what : "?", count, sizeof(T), bad ? "  [poisoned]" : "", first, last);
         }
-        if (host) { if (hipHostMalloc((void**)&h, std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault) != hipSuccess) return gf::set_err(GF_ERR_HIP, "hipHostMalloc failed"); memset(h, 0, std::max<size_t>(count, 1) * sizeof(T));
-            void* p = nullptr; hd = hipHostGetDevicePointer(&p, h, 0) == hipSuccess ? static_cast<T*>(p) : nullptr; (void)hipGetLastError(); }
+        if (host) { HIPCHK(pin.alloc(count)); view(); }
         return GF_OK;
     }
-    void release() { if (d) (void)hipFree(d); if (h) (void)hipHostFree(h); d = nullptr; h = nullptr; }
     hipError_t up(hipStream_t s) { g_up_bytes += (long long)(n * sizeof(T)); g_up_calls++; return hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, s); }
     // `rows` rows of `pitch` elements, only the first `used` of each are live: one strided copy of what the kernels read
     hipError_t up2d(hipStream_t s, size_t rows, size_t pitch, size_t used) {
@@ -142,13 +145,24 @@ struct UpBuilder {
     template <class T> void all(const Buf<T>& b) { add(b, 1, b.n, b.n); }
 };
 
+// One kernel instantiation in one role of the launch schedule, with the block size and the dynamic LDS it is launched with.  Every ba_step form and every
+// ba_linearize_visual_win form has this signature; chosen once, when the handle is created (choose_launch_forms), where the instantiation's LDS limit is raised too.
+struct LaunchForm {
+    void (*fn)(Win, StepBufs, int, int, int) = nullptr;
+    int threads = 0;
+    size_t lds = 0;
+};
+
 struct gf_ba {
     gf_ba_cfg cfg;
     Dims d;
     int count = 0;       // windows currently resident
     bool any_ex = false; // some window estimates the camera extrinsic
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[10] = {};   // 6, 7: around the second ba_step of a solve (the first full dogleg step); 8, 9: around the upload of gf_ba_solve_packed
+    // stream and events in front of every buffer: members are destroyed in reverse order, the buffers before the stream that may still work on them
+    gf::Stream stream;
+    gf::Event ev[10];   // 6, 7: around the second ba_step of a solve (the first full dogleg step); 8, 9: around the upload of gf_ba_solve_packed
+    gf::Event ev_gather, ev_gather_done;   // export -> collective, and collective -> next export (the send buffer is reused)
+    gf::Event ev_split[2];
     bool packed_upload_timed = false;
     bool pending = false;   // an asynchronous solve is in flight
     int pending_iters = 0;
@@ -163,7 +177,7 @@ struct gf_ba {
     // work
     Buf<double> imu_sqrt, wh_sqrt, pri_A, pri_b, pri_c, H, g, Vc, vtile, wpar, cost, efac;
     Buf<double> gather_send;   // [B][7] newest poses, send buffer of gf_pose_gather (allocated on first use)
-    hipEvent_t ev_gather = nullptr, ev_gather_done = nullptr; bool gather_in_flight = false;   // export -> collective, and collective -> next export (the send buffer is reused)
+    bool gather_in_flight = false;
     Buf<double> scale, diag, grad, gn, step, u, Et, Es, ete, etb, rhs, yv, Sg, Mg, gn_data, gn_misc;
     Buf<int> ngnss, gn_idx, gn_gptr, gn_gitem;
     Buf<double> gn_rows;
@@ -173,9 +187,10 @@ struct gf_ba {
     Buf<long long> stamps;
     std::vector<std::vector<int>> keep_ids[2];   // per window: kept block ids (before the address shift), in column order
     size_t marg_lds = 0; int marg_ncap = 0, last_marg_mode = -1;
-    size_t vwin_lds = 0;   // dynamic LDS of the visual sweep (its pair tiles); 0: the tiles live in global memory (vtile)
-    size_t vwinx_lds = 0;  // the same for the variant with camera-extrinsic columns (free extrinsic)
-    size_t vwinm_lds = 0;  // dynamic LDS of the MARGIN_OLD sweep (NP - 1 pair tiles + continuation slots: always fits)
+    // visual sweep with fixed extrinsic (lds: its pair tiles; 0: the tiles live in global memory, vtile), the same with camera-extrinsic columns (free extrinsic), the
+    // MARGIN_OLD sweep (NP - 1 pair tiles + continuation slots: always fits LDS), and the two kernels of the split formulation
+    LaunchForm vis_fixed, vis_free, vis_marg, vis_split1, vis_split2;
+    LaunchForm step_dense, step_chain;   // ba_step in the form the process runs (step_waves, big_step), and the chain form (lds: its capacity; a launch passes what the batch needs)
     size_t vtile_stride = 0;   // doubles per window in vtile (0: both variants keep their tiles in LDS)
     size_t mwin_lds = 0;   // dynamic LDS of the prior / IMU / wheel sweep (ba_linearize_misc_win)
     bool fuse_misc = false, can_fuse_misc = false;
@@ -206,29 +221,11 @@ struct gf_ba {
     double piv_eps = 3e-8; int ls_rhs = 1;
     bool pos_ident = false;
     bool split_jtj = false, split_timed = false;   // gf_ba_set_split_jtj: the visual sweep as two kernels (block rows through HBM, contraction-only MFMA kernel)
-    Buf<double> vrows, vpair; hipEvent_t ev_split[2] = {nullptr, nullptr};
+    Buf<double> vrows, vpair;
     double max_solver_time = 0.0;   // ceres::Solver::Options::max_solver_time_in_seconds; 0 = not honoured (the fixed schedule runs without host round trips)
     long long mfma_per_lin = 0;   // v_mfma_f64_16x16x4 instructions of one visual linearisation of the resident batch
     long long jtj_alg_flops = 0;  // algorithmic flops of the same: Nv * 2 * 2 * (12 * 13 / 2 + 12 + 1) per window
     long long step_flops = 0;     // dense algebra of one ba_step over the resident batch: Schur SYRK NE*n_c^2 + Cholesky R^3/3 + substitutions 2 R^2
-    std::vector<Buf<double>*> dbl() { return {&xs0, &xs, &vis_data, &feat_obs, &imu_data, &wh_data, &pri_J, &pri_r, &pri_x0, &imu_sqrt, &wh_sqrt, &pri_A, &pri_b, &pri_c, &H, &g, &Vc, &vtile, &wpar, &cost, &efac,
-                                              &scale, &diag, &grad, &gn, &step, &u, &Et, &Es, &ete, &etb, &rhs, &yv, &Sg, &Mg, &Yg, &gn_data, &gn_misc, &gn_rows}; }
-    std::vector<Buf<int>*> ints() { return {&colf, &cole, &nvis, &nimu, &nwh, &nfeat, &vis_idx, &order, &norder, &feat_ptr, &vis_pos, &imu_i, &wh_i, &pri_n, &pri_nb, &pri_bid, &ngnss, &gn_idx, &gn_gptr, &gn_gitem}; }
-    void release() {
-        for (auto* b : dbl()) b->release();
-        for (auto* b : ints()) b->release();
-        for (int m = 0; m < 2; m++) { mcolf[m].release(); mcole[m].release(); morder[m].release(); mnorder[m].release(); minfo[m].release(); }
-        minfo_stage.release(); imu_patch.release(); imu_pinfo.release();
-        outJ.release(); outr.release(); stamps.release();
-        st.release(); st0.release();
-        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-        if (ev_gather) (void)hipEventDestroy(ev_gather);
-        if (ev_gather_done) (void)hipEventDestroy(ev_gather_done);
-        for (auto& e : ev_split) if (e) (void)hipEventDestroy(e);
-        vrows.release(); vpair.release();
-        gather_send.release();
-        if (stream) (void)hipStreamDestroy(stream);
-    }
     Win win() {
         Win w{};
         w.d = d; w.xs = xs.d; w.colf = colf.d; w.cole = cole.d; w.nvis = nvis.d; w.nimu = nimu.d; w.nwh = nwh.d; w.nfeat = nfeat.d;
@@ -676,6 +673,13 @@ void unpack_state(gf_ba* h, int b, gf_ba_window* wp, gf_ba_summary* sp) {
     }
 }
 
+// the states and the solver summaries of the whole batch into their host mirrors (what unpack_state reads), on the handle's stream
+int download_state(gf_ba* h) {
+    HIPCHK(h->xs.down(h->stream));
+    HIPCHK(h->st.down(h->stream));
+    return GF_OK;
+}
+
 int reset_state(gf_ba* h) {
     const Dims& d = h->d;
     HIPCHK(hipMemcpyAsync(h->xs.d, h->xs0.d, (size_t)d.B * d.XS * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
@@ -688,12 +692,34 @@ __global__ void __launch_bounds__(256) ba_poison_lds(int ndoubles) {   // GF_BA_
     for (int i = threadIdx.x; i < ndoubles; i += 256) lds_all[i] = __longlong_as_double(-1LL);
 }
 static void poison_lds(gf_ba* h) {
-    static const int pmode = getenv("GF_BA_POISON") ? atoi(getenv("GF_BA_POISON")) : 0;
-    static const bool poison = pmode == 1 || pmode == 3;
-    if (!poison) return;
+    if (poison_mode() != 1 && poison_mode() != 3) return;
     static bool attr = false;
     if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ba_poison_lds), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
     ba_poison_lds<<<dim3(1024), 256, 160 * 1024, h->stream>>>(160 * 1024 / 8);
+}
+
+// The kernel behind every role of the launch schedule (LaunchForm); nd_max: the largest dense part a chain-form window of this handle can have.
+int choose_launch_forms(gf_ba* h, int nd_max) {
+    const Dims& d = h->d;
+    auto set = [](LaunchForm& f, decltype(LaunchForm::fn) fn, int threads, size_t lds) -> int {
+        f.fn = fn; f.threads = threads; f.lds = lds;
+        if (lds) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        return GF_OK;
+    };
+    // window-level sweeps: staging areas of the wavefronts (static LDS) + pair tiles / block rows (dynamic LDS, or global memory for long windows)
+    const bool glob = getenv("GF_BA_GLOBAL_TILES") != nullptr;   // test switch: pair tiles in global memory also where they fit LDS
+    const size_t dyn = vwin_slot_doubles(d.NP, false) * sizeof(double), stat = (size_t)kVW * vwin_sg(false) * vwin_lstr(false) * sizeof(double) + kVW * 64 * sizeof(int) + 512 + 2048;
+    const size_t dynx = vwin_slot_doubles(d.NP, true) * sizeof(double), statx = (size_t)kVWX * vwin_sg(true) * vwin_lstr(true) * sizeof(double) + kVWX * 64 * sizeof(int) + 512 + 2048;
+    const size_t lds = (dyn + stat <= 160 * 1024 && !glob) ? dyn : 0, ldsx = (dynx + statx <= 160 * 1024 && !glob) ? dynx : 0;
+    if (int rc = set(h->vis_marg, ba_linearize_visual_win<true, kVWM>, 64 * kVWM, vwin_marg_slot_doubles(d.NP) * sizeof(double))) return rc;
+    if (int rc = set(h->vis_free, ba_linearize_visual_win<true, kVWX>, 64 * kVWX, ldsx)) return rc;
+    if (int rc = set(h->vis_split1, ba_linearize_visual_win<false, kVW, 1>, 64 * kVW, lds)) return rc;
+    if (int rc = set(h->vis_split2, ba_linearize_visual_win<false, kVW, 2>, 64 * kVW, lds)) return rc;
+    if (int rc = set(h->vis_fixed, ba_linearize_visual_win<false, kVW>, 64 * kVW, lds)) return rc;
+    // ba_step: in global memory where the reduced system exceeds LDS (big_step), on four or eight wavefronts (step_waves)
+    if (h->chain_mode) { if (int rc = set(h->step_chain, ba_step_chain, 256, ch_lds_doubles(nd_max) * sizeof(double))) return rc; }
+    if (h->step_waves == 4) return h->big_step ? set(h->step_dense, ba_step<true, 4>, 256, 0) : set(h->step_dense, ba_step<false, 4>, 256, h->step_lds);
+    return h->big_step ? set(h->step_dense, ba_step<true>, 512, 0) : set(h->step_dense, ba_step<false>, 512, h->step_lds);
 }
 
 // One linearisation of the resident batch at the state buffer `which_state` into the buffers `which` (-1: the candidate's).
@@ -701,23 +727,20 @@ static void poison_lds(gf_ba* h) {
 // has one writing kernel and every sum a fixed order: no zeroing or reset passes, no atomics.
 int launch_visual(gf_ba* h, Win w, bool ex, int which, int which_state, int only_valid, bool timed_split = false) {
     const Dims& d = h->d;
-    const size_t lds = ex ? h->vwinx_lds : h->vwin_lds;
-    w.vtile = lds ? nullptr : h->vtile.d;
+    const StepBufs sb = h->sbufs();
+    auto launch = [&](const LaunchForm& f) { f.fn<<<dim3(d.B), f.threads, f.lds, h->stream>>>(w, sb, which, which_state, only_valid); };
+    const LaunchForm& one = ex ? (only_valid == 2 ? h->vis_marg : h->vis_free) : h->vis_fixed;   // only_valid == 2: the MARGIN_OLD pass (eight wavefronts, NP - 1 pair tiles)
+    w.vtile = one.lds ? nullptr : h->vtile.d;
     w.vpair = h->vpair.d;
-    if (ex && only_valid == 2) {   // MARGIN_OLD pass: eight wavefronts, NP - 1 pair tiles, always in LDS
-        w.vtile = nullptr;
-        ba_linearize_visual_win<true, kVWM><<<dim3(d.B), 64 * kVWM, h->vwinm_lds, h->stream>>>(w, h->sbufs(), which, which_state, only_valid);
-    }
-    else if (ex) ba_linearize_visual_win<true, kVWX><<<dim3(d.B), 64 * kVWX, lds, h->stream>>>(w, h->sbufs(), which, which_state, only_valid);
-    else if (h->split_jtj && only_valid != 2) {   // north_star's formulation, measured next to the fused kernel: the sweep writes block rows to HBM, a second kernel only contracts them
+    if (!ex && h->split_jtj && only_valid != 2) {   // north_star's formulation, measured next to the fused kernel: the sweep writes block rows to HBM, a second kernel only contracts them
         w.vrows = h->vrows.d;
-        ba_linearize_visual_win<false, kVW, 1><<<dim3(d.B), 64 * kVW, lds, h->stream>>>(w, h->sbufs(), which, which_state, only_valid);
+        launch(h->vis_split1);
         HIPCHK(hipGetLastError());
         if (timed_split) HIPCHK(hipEventRecord(h->ev_split[0], h->stream));
-        ba_linearize_visual_win<false, kVW, 2><<<dim3(d.B), 64 * kVW, lds, h->stream>>>(w, h->sbufs(), which, which_state, only_valid);
+        launch(h->vis_split2);
         if (timed_split) { HIPCHK(hipEventRecord(h->ev_split[1], h->stream)); h->split_timed = true; }
     }
-    else ba_linearize_visual_win<false, kVW><<<dim3(d.B), 64 * kVW, lds, h->stream>>>(w, h->sbufs(), which, which_state, only_valid);
+    else launch(one);
     HIPCHK(hipGetLastError());
     return GF_OK;
 }
@@ -757,14 +780,12 @@ int run_solve(gf_ba* h, int max_iters) {
         const bool time_step = it == 1 && max_iters >= 1;
         if (time_step) HIPCHK(hipEventRecord(h->ev[6], h->stream));
         // windows in the chain form first (256 threads, two per CU), then -- if the batch holds any -- the others in the dense form; each kernel leaves the other's windows alone
-        if (h->n_chain > 0) ba_step_chain<<<dim3(d.B), 256, ch_lds_doubles(h->chain_nd) * sizeof(double), h->stream>>>(w, sb, it == 0 ? 1 : 0, max_iters, it == max_iters ? 1 : 0);
+        const int first = it == 0 ? 1 : 0, last = it == max_iters ? 1 : 0;
+        const LaunchForm& ch = h->step_chain; const LaunchForm& de = h->step_dense;
+        if (h->n_chain > 0) ch.fn<<<dim3(d.B), ch.threads, ch_lds_doubles(h->chain_nd) * sizeof(double), h->stream>>>(w, sb, first, max_iters, last);
         if (h->n_chain > 0 && h->n_dense == 0) { }
-        else if (h->step_waves == 4) {
-            if (h->big_step) ba_step<true, 4><<<dim3(d.B), 256, 0, h->stream>>>(w, sb, it == 0 ? 1 : 0, max_iters, it == max_iters ? 1 : 0);
-            else ba_step<false, 4><<<dim3(d.B), 256, h->step_lds, h->stream>>>(w, sb, it == 0 ? 1 : 0, max_iters, it == max_iters ? 1 : 0);
-        } else if (h->big_step) ba_step<true><<<dim3(d.B), 512, 0, h->stream>>>(w, sb, it == 0 ? 1 : 0, max_iters, it == max_iters ? 1 : 0);
-        else if (fuse_misc && it > 0) ba_misc_step<<<dim3(d.B), 512, std::max(h->step_lds, h->mwin_lds), h->stream>>>(w, sb, max_iters, it == max_iters ? 1 : 0);
-        else ba_step<false><<<dim3(d.B), 512, h->step_lds, h->stream>>>(w, sb, it == 0 ? 1 : 0, max_iters, it == max_iters ? 1 : 0);
+        else if (fuse_misc && it > 0 && h->step_waves != 4) ba_misc_step<<<dim3(d.B), 512, std::max(h->step_lds, h->mwin_lds), h->stream>>>(w, sb, max_iters, last);
+        else de.fn<<<dim3(d.B), de.threads, de.lds, h->stream>>>(w, sb, first, max_iters, last);
         HIPCHK(hipGetLastError());
         if (time_step) { HIPCHK(hipEventRecord(h->ev[7], h->stream)); h->stats.step_launches++; h->stats.step_flops += h->step_flops; }
         if (it < max_iters) {
@@ -825,9 +846,8 @@ int gf_ba_create(const gf_ba_cfg* cfg, gf_ba** out) {
     if (!cfg || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
     *out = nullptr;
     if (cfg->window_size < 2 || cfg->window_size > 30 || cfg->max_features < 1 || cfg->max_visual < 1 || cfg->batch < 1) return gf::set_err(GF_ERR_INVALID, "bad gf_ba_cfg");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return gf::set_err(GF_ERR_NO_DEVICE, "no HIP device available; the HIP path has no CPU fallback");
-    gf_ba* h = new gf_ba();
+    if (int rc = gf::require_device()) return rc;
+    std::unique_ptr<gf_ba> h(new gf_ba());
     h->cfg = *cfg;
     Dims& d = h->d;
     d.B = cfg->batch; d.W = cfg->window_size; d.NP = d.W + 1; d.F = cfg->max_features; d.NV = cfg->max_visual;
@@ -838,116 +858,86 @@ int gf_ba_create(const gf_ba_cfg* cfg, gf_ba** out) {
     d.RP = (Rmax + 1 + 15) & ~15; /* one spare column: the Schur GEMM carries the right-hand side in column R */ d.GO = gnss ? ((16 * d.NP + 20 + d.F + 3) & ~3) : 0; d.XS = gnss ? ((d.GO + 5 * d.NP + 4 + 3) & ~3) : ((16 * d.NP + 20 + d.F + 3) & ~3); d.NFB = 2 * d.NP + 7 + (gnss ? 5 * d.NP + 2 : 0); d.FP = (d.F + 3) & ~3; d.NPRI = d.RP; d.ECW = (6 * d.NP + 8 + 15) & ~15; d.NC = 6 * d.NP + 8; d.NVC = (d.NC * (d.NC + 1) / 2 + 3) & ~3;
     h->step_lds = (size_t)(Rmax + 1) * (Rmax + 2) / 2 * sizeof(double);  // packed lower S plus the right-hand-side row
     h->big_step = h->step_lds + 27 * 1024 > 160 * 1024 || getenv("GF_BA_FORCE_GLOBAL") != nullptr;   // reduced system too large for LDS: ba_step<true> keeps it in global memory
-    if (Rmax + 1 > 512) { delete h; return gf::set_err(GF_ERR_INVALID, "window_size %d: reduced system (%d) exceeds 511 columns", d.W, Rmax); }
-    if (d.NV > 65535) { delete h; return gf::set_err(GF_ERR_INVALID, "max_visual %d exceeds 65535", d.NV); }
-    if (misc_win_lds_doubles(d.W) * sizeof(double) > 160 * 1024) { /* the sweep has no static LDS */ delete h; return gf::set_err(GF_ERR_INVALID, "window_size %d: the IMU / wheel block rows exceed LDS (window_size <= 20 in this build)", d.W); }
-#define A_(x) do { g_alloc_what = #x; if (int rc_ = (x)) { h->release(); delete h; return rc_; } } while (0)
-#define H_(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { gf::set_err(GF_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); h->release(); delete h; return GF_ERR_HIP; } } while (0)
+    if (Rmax + 1 > 512) return gf::set_err(GF_ERR_INVALID, "window_size %d: reduced system (%d) exceeds 511 columns", d.W, Rmax);
+    if (d.NV > 65535) return gf::set_err(GF_ERR_INVALID, "max_visual %d exceeds 65535", d.NV);
+    if (misc_win_lds_doubles(d.W) * sizeof(double) > 160 * 1024) /* the sweep has no static LDS */ return gf::set_err(GF_ERR_INVALID, "window_size %d: the IMU / wheel block rows exceed LDS (window_size <= 20 in this build)", d.W);
+    // The allocations are explicit statements in a fixed order: GF_BA_POISON_RANGE counts them, and an allocation's place in the process's sequence decides which
+    // recycled memory it gets.  GF_BA_ALLOC_TRACE=1 prints the statement next to the allocation's index.
+#define TRACED(x) do { g_alloc_what = #x; if (int rc_ = (x)) return rc_; } while (0)
     {   // the solver is a chain of short launches that each want every CU: its queue goes first when the tracker's kernels of the same process compete for them
         int least = 0, greatest = 0;
-        H_(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
         const char* e = getenv("GF_BA_STREAM_PRIORITY");
         const int prio = (e && !strcmp(e, "default")) ? least + (greatest - least) / 2 : greatest;
-        H_(hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, prio));
+        HIPCHK(hipStreamCreateWithPriority(&h->stream.s, hipStreamNonBlocking, prio));
     }
-    for (auto& e : h->ev) H_(hipEventCreate(&e));
-    H_(hipEventCreateWithFlags(&h->ev_gather, hipEventDisableTiming));
-    H_(hipEventCreateWithFlags(&h->ev_gather_done, hipEventDisableTiming));
+    for (auto& e : h->ev) HIPCHK(hipEventCreate(&e.e));
+    HIPCHK(hipEventCreateWithFlags(&h->ev_gather.e, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&h->ev_gather_done.e, hipEventDisableTiming));
     const size_t B = d.B, VS = d.RP + d.FP;
-    A_(h->xs0.alloc(B * d.XS, true)); A_(h->xs.alloc(2 * B * d.XS, true));
-    A_(h->colf.alloc(B * d.NFB, true)); A_(h->cole.alloc(B * d.F, true)); A_(h->nvis.alloc(B, true)); A_(h->nimu.alloc(B, true)); A_(h->nwh.alloc(B, true)); A_(h->nfeat.alloc(B, true));
-    A_(h->vis_idx.alloc(B * d.NV, true)); A_(h->vis_data.alloc(B * d.NV * 5, true)); A_(h->feat_obs.alloc(B * d.F * 6, true));
-    A_(h->order.alloc(B * d.NVP, true)); A_(h->norder.alloc(B, true)); A_(h->feat_ptr.alloc(B * (d.F + 1), true)); A_(h->vis_pos.alloc(B * d.NV, true));
-    A_(h->imu_i.alloc(B * d.W, true)); A_(h->imu_data.alloc(B * d.W * IMU_STRIDE2, true)); A_(h->wh_i.alloc(B * d.W, true)); A_(h->wh_data.alloc(B * d.W * WH_STRIDE, true));
-    A_(h->pri_n.alloc(B, true)); A_(h->pri_nb.alloc(B, true)); A_(h->pri_bid.alloc(B * 64, true)); A_(h->pri_J.alloc(B * d.NPRI * d.NPRI, true));
-    A_(h->pri_r.alloc(B * d.NPRI, true)); A_(h->pri_x0.alloc(B * d.NPRI * 2, true));
-    if (hipMalloc((void**)&h->st.d, B * sizeof(SolverState)) != hipSuccess || hipHostMalloc((void**)&h->st.h, B * sizeof(SolverState), hipHostMallocDefault) != hipSuccess ||
-        hipMalloc((void**)&h->st0.d, B * sizeof(SolverState)) != hipSuccess || hipHostMalloc((void**)&h->st0.h, B * sizeof(SolverState), hipHostMallocDefault) != hipSuccess) {
-        h->release(); delete h; return gf::set_err(GF_ERR_HIP, "allocation of solver state failed");
-    }
-    h->st.n = h->st0.n = B;
-    // page-locked memory is recycled inside the process like device memory: a slot that was never packed would hand the kernels the SolverState of an earlier handle
-    memset(h->st.h, 0, B * sizeof(SolverState)); memset(h->st0.h, 0, B * sizeof(SolverState));
-    H_(hipMemset(h->st.d, 0, B * sizeof(SolverState))); H_(hipMemset(h->st0.d, 0, B * sizeof(SolverState)));
-    { void* p = nullptr; h->st0.hd = hipHostGetDevicePointer(&p, h->st0.h, 0) == hipSuccess ? static_cast<SolverState*>(p) : nullptr; (void)hipGetLastError(); }
+    TRACED(h->xs0.alloc(B * d.XS, true)); TRACED(h->xs.alloc(2 * B * d.XS, true));
+    TRACED(h->colf.alloc(B * d.NFB, true)); TRACED(h->cole.alloc(B * d.F, true)); TRACED(h->nvis.alloc(B, true)); TRACED(h->nimu.alloc(B, true)); TRACED(h->nwh.alloc(B, true)); TRACED(h->nfeat.alloc(B, true));
+    TRACED(h->vis_idx.alloc(B * d.NV, true)); TRACED(h->vis_data.alloc(B * d.NV * 5, true)); TRACED(h->feat_obs.alloc(B * d.F * 6, true));
+    TRACED(h->order.alloc(B * d.NVP, true)); TRACED(h->norder.alloc(B, true)); TRACED(h->feat_ptr.alloc(B * (d.F + 1), true)); TRACED(h->vis_pos.alloc(B * d.NV, true));
+    TRACED(h->imu_i.alloc(B * d.W, true)); TRACED(h->imu_data.alloc(B * d.W * IMU_STRIDE2, true)); TRACED(h->wh_i.alloc(B * d.W, true)); TRACED(h->wh_data.alloc(B * d.W * WH_STRIDE, true));
+    TRACED(h->pri_n.alloc(B, true)); TRACED(h->pri_nb.alloc(B, true)); TRACED(h->pri_bid.alloc(B * 64, true)); TRACED(h->pri_J.alloc(B * d.NPRI * d.NPRI, true));
+    TRACED(h->pri_r.alloc(B * d.NPRI, true)); TRACED(h->pri_x0.alloc(B * d.NPRI * 2, true));
+    // the solver states, outside the poison counter.  (Zeroed like everything else: page-locked memory is recycled inside the process like device memory, and a slot that
+    // was never packed would hand the kernels the SolverState of an earlier handle.)
+    HIPCHK(h->st.dev.alloc(B)); HIPCHK(h->st.pin.alloc(B)); h->st.view();
+    HIPCHK(h->st0.dev.alloc(B)); HIPCHK(h->st0.pin.alloc(B)); h->st0.view();
     // GF_BA_UPLOAD=kernel | copies: a batch's tables through one gather kernel that reads the page-locked mirrors over the bus, or one hipMemcpy(2D)Async per table
     h->upload_kernel = !(getenv("GF_BA_UPLOAD") && !strcmp(getenv("GF_BA_UPLOAD"), "copies"));
-    A_(h->imu_sqrt.alloc(B * d.W * 225, false)); A_(h->wh_sqrt.alloc(B * d.W * 36, false)); A_(h->pri_A.alloc(B * d.NPRI * d.NPRI, false)); A_(h->pri_b.alloc(B * d.NPRI, false));
-    A_(h->pri_c.alloc(B, false)); A_(h->H.alloc(2 * B * d.RP * d.RP, true)); A_(h->g.alloc(2 * B * d.RP, true)); A_(h->Vc.alloc(2 * B * d.NVC, true)); A_(h->wpar.alloc(B * WPAR, true));
-    A_(h->cost.alloc(6 * B, true)); A_(h->efac.alloc(B * d.NV * EF, false));
-    H_(hipMemsetAsync(h->cost.d, 0, 6 * B * sizeof(double), h->stream));
-    A_(h->scale.alloc(B * VS, false)); A_(h->diag.alloc(B * VS, false)); A_(h->grad.alloc(B * VS, false)); A_(h->gn.alloc(B * VS, false)); A_(h->step.alloc(B * VS, false));
-    A_(h->u.alloc(B * VS, false)); A_(h->Et.alloc(2 * B * d.FP * d.ECW, true)); A_(h->Es.alloc(B * d.FP * d.ECW, false)); A_(h->ete.alloc(2 * B * d.FP, true)); A_(h->etb.alloc(2 * B * d.FP, true));
-    A_(h->rhs.alloc(B * d.RP, false)); A_(h->yv.alloc(B * VS, false));
-    if (gnss) { A_(h->ngnss.alloc(B, true)); A_(h->gn_idx.alloc(B * d.NG * 4, true)); A_(h->gn_data.alloc(B * d.NG * GN_STRIDE, true)); A_(h->gn_misc.alloc(B * (GN_MISC + d.NP), true)); A_(h->gn_gptr.alloc(B * (d.NGRP + 2), true)); A_(h->gn_gitem.alloc(B * d.NG, true)); A_(h->gn_rows.alloc(B * d.NG * GN_ROW, false)); }
-    for (int m = 0; m < 2; m++) { A_(h->mcolf[m].alloc(B * d.NFB, true)); A_(h->mcole[m].alloc(B * d.F, true)); A_(h->morder[m].alloc(B * d.NVP, true)); A_(h->mnorder[m].alloc(B, true)); A_(h->minfo[m].alloc(B * 4, true)); }
-    A_(h->minfo_stage.alloc(B * 4, true));
-    A_(h->vpair.alloc(B * (size_t)(d.NP * (d.NP - 1) / 2) * VPG, false));
-    A_(h->outJ.alloc(B * (size_t)d.NPRI * d.NPRI, true)); A_(h->outr.alloc(B * d.NPRI, true)); A_(h->stamps.alloc(128, true));
+    TRACED(h->imu_sqrt.alloc(B * d.W * 225, false)); TRACED(h->wh_sqrt.alloc(B * d.W * 36, false)); TRACED(h->pri_A.alloc(B * d.NPRI * d.NPRI, false)); TRACED(h->pri_b.alloc(B * d.NPRI, false));
+    TRACED(h->pri_c.alloc(B, false)); TRACED(h->H.alloc(2 * B * d.RP * d.RP, true)); TRACED(h->g.alloc(2 * B * d.RP, true)); TRACED(h->Vc.alloc(2 * B * d.NVC, true)); TRACED(h->wpar.alloc(B * WPAR, true));
+    TRACED(h->cost.alloc(6 * B, true)); TRACED(h->efac.alloc(B * d.NV * EF, false));
+    HIPCHK(hipMemsetAsync(h->cost.d, 0, 6 * B * sizeof(double), h->stream));
+    TRACED(h->scale.alloc(B * VS, false)); TRACED(h->diag.alloc(B * VS, false)); TRACED(h->grad.alloc(B * VS, false)); TRACED(h->gn.alloc(B * VS, false)); TRACED(h->step.alloc(B * VS, false));
+    TRACED(h->u.alloc(B * VS, false)); TRACED(h->Et.alloc(2 * B * d.FP * d.ECW, true)); TRACED(h->Es.alloc(B * d.FP * d.ECW, false)); TRACED(h->ete.alloc(2 * B * d.FP, true)); TRACED(h->etb.alloc(2 * B * d.FP, true));
+    TRACED(h->rhs.alloc(B * d.RP, false)); TRACED(h->yv.alloc(B * VS, false));
+    if (gnss) { TRACED(h->ngnss.alloc(B, true)); TRACED(h->gn_idx.alloc(B * d.NG * 4, true)); TRACED(h->gn_data.alloc(B * d.NG * GN_STRIDE, true)); TRACED(h->gn_misc.alloc(B * (GN_MISC + d.NP), true)); TRACED(h->gn_gptr.alloc(B * (d.NGRP + 2), true)); TRACED(h->gn_gitem.alloc(B * d.NG, true)); TRACED(h->gn_rows.alloc(B * d.NG * GN_ROW, false)); }
+    for (int m = 0; m < 2; m++) { TRACED(h->mcolf[m].alloc(B * d.NFB, true)); TRACED(h->mcole[m].alloc(B * d.F, true)); TRACED(h->morder[m].alloc(B * d.NVP, true)); TRACED(h->mnorder[m].alloc(B, true)); TRACED(h->minfo[m].alloc(B * 4, true)); }
+    TRACED(h->minfo_stage.alloc(B * 4, true));
+    TRACED(h->vpair.alloc(B * (size_t)(d.NP * (d.NP - 1) / 2) * VPG, false));
+    TRACED(h->outJ.alloc(B * (size_t)d.NPRI * d.NPRI, true)); TRACED(h->outr.alloc(B * d.NPRI, true)); TRACED(h->stamps.alloc(128, true));
     // kept system of the marginalisation: 6 W poses + speed-bias + extrinsics ...; A and V live in LDS up to 92 columns, else in global memory
     const int nkeep = 6 * d.W + 9 + 17 + (gnss ? 9 : 0);
     h->big_marg = nkeep > 92 || getenv("GF_BA_FORCE_GLOBAL") != nullptr;
     h->meta.assign(d.B, gf_ba::SlotMeta{}); h->outJ_n.assign(d.B, 0); h->imu_dev.assign(d.B, 0); h->imu_rows.assign(d.B, 0);
-    A_(h->imu_patch.alloc(B * d.W * IMU_STRIDE2, true)); A_(h->imu_pinfo.alloc(B * (d.W + 2), true));
+    TRACED(h->imu_patch.alloc(B * d.W * IMU_STRIDE2, true)); TRACED(h->imu_pinfo.alloc(B * (d.W + 2), true));
     for (int mode = 0; mode < 2; mode++) h->keep_ids[mode].assign(d.B, {});
     h->marg_ncap = h->big_marg ? std::min(d.NPRI, nkeep + 16) : 92;
     h->marg_lds = h->big_marg ? 0 : (size_t)2 * h->marg_ncap * h->marg_ncap * sizeof(double);
-    if (h->big_step) { h->sg_stride = (h->step_lds / sizeof(double) + 15) & ~(size_t)15; A_(h->Sg.alloc(B * h->sg_stride, false)); }
-    if (h->big_marg) { h->mg_stride = (size_t)2 * h->marg_ncap * h->marg_ncap + 1024; A_(h->Mg.alloc(B * h->mg_stride, false)); }
-    if (!h->big_step) H_(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_step<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->step_lds));
+    if (h->big_step) { h->sg_stride = (h->step_lds / sizeof(double) + 15) & ~(size_t)15; TRACED(h->Sg.alloc(B * h->sg_stride, false)); }
+    if (h->big_marg) { h->mg_stride = (size_t)2 * h->marg_ncap * h->marg_ncap + 1024; TRACED(h->Mg.alloc(B * h->mg_stride, false)); }
     // GF_BA_STEP_WAVES=4: ba_step on four wavefronts (half of a CU's registers) so that other kernels' blocks -- the tracker's -- can sit next to it; one setting per
     // process (the reductions' order depends on it: a window alone and the same window in a batch must run the same variant)
-    if (getenv("GF_BA_SPLIT_JTJ") && atoi(getenv("GF_BA_SPLIT_JTJ"))) if (int rc = gf_ba_set_split_jtj(h, 1)) { h->release(); delete h; return rc; }
+    if (getenv("GF_BA_SPLIT_JTJ") && atoi(getenv("GF_BA_SPLIT_JTJ"))) if (int rc = gf_ba_set_split_jtj(h.get(), 1)) return rc;
     h->step_waves = (getenv("GF_BA_STEP_WAVES") && atoi(getenv("GF_BA_STEP_WAVES")) == 4) ? 4 : 8;
     h->chain_mode = getenv("GF_BA_CHAIN") && atoi(getenv("GF_BA_CHAIN")) != 0 && !h->big_step && !gnss;
     h->cost_only = !(getenv("GF_BA_COST_ONLY") && atoi(getenv("GF_BA_COST_ONLY")) == 0);
     h->piv_eps = getenv("GF_MARG_PIVOT_EPS") ? atof(getenv("GF_MARG_PIVOT_EPS")) : 3e-8;
     h->ls_rhs = getenv("GF_MARG_LS_RHS") ? atoi(getenv("GF_MARG_LS_RHS")) : 1;
-    if (h->chain_mode) {
-        const int nd_max = Rmax - 9 * d.NP;
-        if (ch_lds_doubles(nd_max) * sizeof(double) + 20 * 1024 > 160 * 1024) h->chain_mode = false;   // (cannot happen where the dense form fits LDS; kept as the guard it is)
-        else {
-            h->yg_stride = ch_y_stride(nd_max);
-            A_(h->Yg.alloc(B * d.NP * h->yg_stride, false));
-            H_(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_step_chain), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(ch_lds_doubles(nd_max) * sizeof(double))));
-        }
-    }
-    if (h->step_waves == 4 && !h->big_step) H_(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_step<false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->step_lds));
+    const int nd_max = Rmax - 9 * d.NP;
+    if (h->chain_mode && ch_lds_doubles(nd_max) * sizeof(double) + 20 * 1024 > 160 * 1024) h->chain_mode = false;   // (cannot happen where the dense form fits LDS; kept as the guard it is)
+    if (int rc = choose_launch_forms(h.get(), nd_max)) return rc;
+    if (h->chain_mode) { h->yg_stride = ch_y_stride(nd_max); TRACED(h->Yg.alloc(B * d.NP * h->yg_stride, false)); }
     // GF_BA_FUSE_MISC=1: the candidate's prior / IMU / wheel sweep in front of the step that judges it, one launch (ba_misc_step).  Same bits; measured 163 us against
     // 123 + 33 us for the two launches and 1.75-1.77 instead of 1.79 ms per solve (-1 %): the sweep's time is its blocks' own latency, not a launch boundary.  Off.
     h->fuse_misc = getenv("GF_BA_FUSE_MISC") != nullptr;
-    {   // window-level sweeps: staging areas of the wavefronts (static LDS) + pair tiles / block rows (dynamic LDS, or global memory for long windows)
-        const bool glob = getenv("GF_BA_GLOBAL_TILES") != nullptr;   // test switch: pair tiles in global memory also where they fit LDS
-        const size_t dyn = vwin_slot_doubles(d.NP, false) * sizeof(double), stat = (size_t)kVW * vwin_sg(false) * vwin_lstr(false) * sizeof(double) + kVW * 64 * sizeof(int) + 512 + 2048;
-        h->vwin_lds = (dyn + stat <= 160 * 1024 && !glob) ? dyn : 0;
-        if (h->vwin_lds) H_(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_linearize_visual_win<false, kVW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->vwin_lds));
-        if (h->vwin_lds) H_(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_linearize_visual_win<false, kVW, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->vwin_lds));
-        if (h->vwin_lds) H_(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_linearize_visual_win<false, kVW, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->vwin_lds));
-        const size_t dynx = vwin_slot_doubles(d.NP, true) * sizeof(double), statx = (size_t)kVWX * vwin_sg(true) * vwin_lstr(true) * sizeof(double) + kVWX * 64 * sizeof(int) + 512 + 2048;
-        h->vwinx_lds = (dynx + statx <= 160 * 1024 && !glob) ? dynx : 0;
-        if (h->vwinx_lds) H_(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_linearize_visual_win<true, kVWX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->vwinx_lds));
-        h->vwinm_lds = vwin_marg_slot_doubles(d.NP) * sizeof(double);
-        H_(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_linearize_visual_win<true, kVWM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->vwinm_lds));
-        if (!h->vwin_lds || !h->vwinx_lds) { h->vtile_stride = (vwin_slot_doubles(d.NP, true) + 3) & ~(size_t)3; A_(h->vtile.alloc(B * h->vtile_stride, false)); }
-        h->mwin_lds = misc_win_lds_doubles(d.W) * sizeof(double);
-        H_(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_linearize_misc_win), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->mwin_lds));
-        h->can_fuse_misc = !h->big_step && std::max(h->step_lds, h->mwin_lds) + 27 * 1024 <= 160 * 1024;
-        if (h->can_fuse_misc) H_(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_misc_step), hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(h->step_lds, h->mwin_lds)));
-    }
-    if (!h->big_marg) H_(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_marg_finish<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->marg_lds));
-    H_(hipStreamSynchronize(h->stream));
-#undef A_
-#undef H_
-    *out = h;
+    if (!h->vis_fixed.lds || !h->vis_free.lds) { h->vtile_stride = (vwin_slot_doubles(d.NP, true) + 3) & ~(size_t)3; TRACED(h->vtile.alloc(B * h->vtile_stride, false)); }
+    h->mwin_lds = misc_win_lds_doubles(d.W) * sizeof(double);
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_linearize_misc_win), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->mwin_lds));
+    h->can_fuse_misc = !h->big_step && std::max(h->step_lds, h->mwin_lds) + 27 * 1024 <= 160 * 1024;
+    if (h->can_fuse_misc) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_misc_step), hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(h->step_lds, h->mwin_lds)));
+    if (!h->big_marg) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_marg_finish<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->marg_lds));
+    HIPCHK(hipStreamSynchronize(h->stream));
+#undef TRACED
+    *out = h.release();
     return GF_OK;
 }
 
-int gf_ba_destroy(gf_ba* h) {
-    if (!h) return GF_OK;
-    h->release();
-    delete h;
-    return GF_OK;
-}
+int gf_ba_destroy(gf_ba* h) { delete h; return GF_OK; }
 
 int gf_ba_upload(gf_ba* h, const gf_ba_window* windows, int count) {
     if (!h || !windows) return gf::set_err(GF_ERR_INVALID, "null argument");
@@ -1034,8 +1024,7 @@ int gf_ba_download(gf_ba* h, gf_ba_window* windows, int count, gf_ba_summary* su
         HIPCHK(h->outJ.down(h->stream)); HIPCHK(h->outr.down(h->stream));
     }
     HIPCHK(hipEventRecord(h->ev[0], h->stream));
-    HIPCHK(h->xs.down(h->stream));
-    HIPCHK(hipMemcpyAsync(h->st.h, h->st.d, (size_t)d.B * sizeof(SolverState), hipMemcpyDeviceToHost, h->stream));
+    if (int rc = download_state(h)) return rc;
     HIPCHK(hipEventRecord(h->ev[1], h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     float ms = 0; HIPCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1])); h->stats.ms_download += ms;
@@ -1072,8 +1061,7 @@ int gf_ba_solve_packed(gf_ba* h, const int* slots, int n, int max_iters) {
     if (int rc = upload(h)) return rc;
     HIPCHK(hipEventRecord(h->ev[9], h->stream));
     if (int rc = gf_ba_solve_resident_async(h, max_iters, -1, 1)) return rc;
-    HIPCHK(h->xs.down(h->stream));
-    HIPCHK(hipMemcpyAsync(h->st.h, h->st.d, (size_t)d.B * sizeof(SolverState), hipMemcpyDeviceToHost, h->stream));
+    if (int rc = download_state(h)) return rc;
     if (int rc = gf_ba_wait(h)) return rc;
     float ms = 0; HIPCHK(hipEventElapsedTime(&ms, h->ev[8], h->ev[9])); h->stats.ms_upload += ms;
     return GF_OK;
@@ -1173,7 +1161,7 @@ int gf_ba_linearize(gf_ba* h, const gf_ba_window* w, int cap, double* Hout, doub
     HIPCHK(hipStreamSynchronize(h->stream));
     {   // H, g <- H + Vc, g + Vc's right-hand-side row: what ba_step assembles
         const int RHSK = 6 * d.NP + 7;
-        auto ccol = [&](int k) -> int { const int* cf = h->colf.h; if (k < 6 * d.NP) { const int c0 = cf[fb_pose(k / 6)]; return c0 >= 0 ? c0 + k % 6 : -1; } if (k < 6 * d.NP + 6) { const int c0 = cf[fb_ex(d.NP)]; return c0 >= 0 ? c0 + k - 6 * d.NP : -1; } return cf[fb_td(d.NP)]; };
+        auto ccol = [&](int k) { return compact_to_col(k, h->colf.h, d.NP, -1); };
         for (int ka = 0; ka < RHSK; ka++) for (int kb = 0; kb <= ka; kb++) { const int r = ccol(ka), c = ccol(kb); if (r >= 0 && c >= 0) h->H.h[(size_t)std::max(r, c) * d.RP + std::min(r, c)] += h->Vc.h[(size_t)ka * (ka + 1) / 2 + kb]; }
         for (int kb = 0; kb < RHSK; kb++) { const int c = ccol(kb); if (c >= 0) h->g.h[c] += h->Vc.h[(size_t)RHSK * (RHSK + 1) / 2 + kb]; }
     }
@@ -1185,11 +1173,7 @@ int gf_ba_linearize(gf_ba* h, const gf_ba_window* w, int cap, double* Hout, doub
     for (int e = 0; e < NE; e++) {
         Hout[(size_t)(R + e) * n + R + e] = h->ete.h[e]; gout[R + e] = h->etb.h[e];
         for (int k = 0; k < 6 * d.NP + 7; k++) {   // compact row -> reduced columns
-            const int* cf = h->colf.h;
-            int c = -1;
-            if (k < 6 * d.NP) { if (cf[fb_pose(k / 6)] >= 0) c = cf[fb_pose(k / 6)] + k % 6; }
-            else if (k < 6 * d.NP + 6) { if (cf[fb_ex(d.NP)] >= 0) c = cf[fb_ex(d.NP)] + k - 6 * d.NP; }
-            else c = cf[fb_td(d.NP)];
+            const int c = compact_to_col(k, h->colf.h, d.NP, -1);
             if (c >= 0) { Hout[(size_t)(R + e) * n + c] = h->Et.h[(size_t)e * d.ECW + k]; Hout[(size_t)c * n + R + e] = h->Et.h[(size_t)e * d.ECW + k]; }
         }
     }
@@ -1250,7 +1234,7 @@ int gf_ba_set_split_jtj(gf_ba* h, int on) {
     if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
     if (on && !h->vrows.d) {
         if (int rc = h->vrows.alloc((size_t)h->d.B * ((h->d.NVP + 63) & ~63) * 32 + 64 * 32, false)) return rc;
-        for (auto& e : h->ev_split) HIPCHK(hipEventCreate(&e));
+        for (auto& e : h->ev_split) HIPCHK(hipEventCreate(&e.e));
     }
     h->split_jtj = on != 0;
     return GF_OK;

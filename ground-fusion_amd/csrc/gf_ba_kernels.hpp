@@ -1415,7 +1415,7 @@ __device__ __forceinline__ void pose_plus(const double* x, const double* dl, dou
 }
 
 // reduced column of compact column k (or -1); the right-hand-side slot maps to `rhs_col`
-__device__ __forceinline__ int compact_to_col(int k, const int* colf, int NP, int rhs_col) {
+__host__ __device__ __forceinline__ int compact_to_col(int k, const int* colf, int NP, int rhs_col) {
     if (k < 6 * NP) { const int c0 = colf[fb_pose(k / 6)]; return c0 >= 0 ? c0 + k % 6 : -1; }
     if (k < 6 * NP + 6) { const int c0 = colf[fb_ex(NP)]; return c0 >= 0 ? c0 + k - 6 * NP : -1; }
     if (k == 6 * NP + 6) return colf[fb_td(NP)];

@@ -6,11 +6,11 @@
 
 #include "../../include/groundfusion_hip.h"
 #include "gf_clahe_kernels.hpp"
+#include "gf_hip_own.hpp"
 
 #pragma clang fp contract(off)   // as -ffp-contract=off (build.py): a fused multiply-add changes the interpolated bits
 
 namespace gf {
-int set_err(int code, const char* fmt, ...);
 
 // the tile geometry, clip limit and scales of CLAHE_Impl::apply (clahe.cpp), or GF_ERR_INVALID
 static int clahe_geom(int w, int h, double clip_limit, int tiles_x, int tiles_y, gfclahe::Geom& g) {
@@ -55,8 +55,7 @@ int clahe_launch(const uint8_t* d_src, uint8_t* d_dst, uint8_t* d_lut, int batch
     else if (lds) clahe_apply_kernel<false, true><<<grid, kThreads, lds_bytes, stream>>>(d_src, d_dst, d_lut, g, band, lds_rows);
     else if (v16) clahe_apply_kernel<true, false><<<grid, kThreads, 0, stream>>>(d_src, d_dst, d_lut, g, band, lds_rows);
     else clahe_apply_kernel<false, false><<<grid, kThreads, 0, stream>>>(d_src, d_dst, d_lut, g, band, lds_rows);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err(GF_ERR_HIP, "clahe launch: %s", hipGetErrorString(e));
+    HIPCHK(hipGetLastError());
     return GF_OK;
 }
 
@@ -71,12 +70,11 @@ int gf_clahe_batch_device(const void* d_src, void* d_dst, int batch, int width, 
     const hipStream_t s = static_cast<hipStream_t>(stream);
     // the LUTs live from the first launch to the second only: stream-ordered scratch keeps the call asynchronous
     uint8_t* lut = nullptr;
-    hipError_t e = hipMallocAsync((void**)&lut, gf::clahe_lut_bytes(batch, tiles_x, tiles_y), s);
-    if (e != hipSuccess) return gf::set_err(GF_ERR_HIP, "hipMallocAsync: %s", hipGetErrorString(e));
+    HIPCHK(hipMallocAsync((void**)&lut, gf::clahe_lut_bytes(batch, tiles_x, tiles_y), s));
     const int rc = gf::clahe_launch(static_cast<const uint8_t*>(d_src), static_cast<uint8_t*>(d_dst), lut, batch, width, height, clip_limit, tiles_x, tiles_y, s);
-    e = hipFreeAsync(lut, s);
+    const hipError_t e = hipFreeAsync(lut, s);
     if (rc) return rc;
-    if (e != hipSuccess) return gf::set_err(GF_ERR_HIP, "hipFreeAsync: %s", hipGetErrorString(e));
+    HIPCHK(e);
     return GF_OK;
 }
 
@@ -85,18 +83,14 @@ int gf_clahe_batch(const uint8_t* src, uint8_t* dst, int batch, int width, int h
     gfclahe::Geom g;
     if (int rc = gf::clahe_geom(width, height, clip_limit, tiles_x, tiles_y, g)) return rc;
     if (batch < 1) return gf::set_err(GF_ERR_INVALID, "clahe: batch %d", batch);
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return gf::set_err(GF_ERR_NO_DEVICE, "no HIP device available; the HIP path has no CPU fallback"); }
+    if (int rc = gf::require_device()) return rc;
     const size_t bytes = (size_t)batch * width * height;
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, bytes);
-    if (e != hipSuccess) return gf::set_err(GF_ERR_HIP, "hipMalloc(%zu B): %s", bytes, hipGetErrorString(e));
-    int rc = GF_OK;
-    if ((e = hipMemcpy(d, src, bytes, hipMemcpyHostToDevice)) != hipSuccess) rc = gf::set_err(GF_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
-    if (!rc) rc = gf_clahe_batch_device(d, d, batch, width, height, clip_limit, tiles_x, tiles_y, nullptr);
-    if (!rc && (e = hipMemcpy(dst, d, bytes, hipMemcpyDeviceToHost)) != hipSuccess) rc = gf::set_err(GF_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
-    (void)hipFree(d);
-    return rc;
+    gf::DevBuf<uint8_t> d;
+    HIPCHK(d.fit(bytes));
+    HIPCHK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+    if (int rc = gf_clahe_batch_device(d.p, d.p, batch, width, height, clip_limit, tiles_x, tiles_y, nullptr)) return rc;
+    HIPCHK(hipMemcpy(dst, d.p, bytes, hipMemcpyDeviceToHost));
+    return GF_OK;
 }
 
 }  // extern "C"

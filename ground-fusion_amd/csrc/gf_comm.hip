@@ -15,14 +15,14 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/groundfusion_hip.h"
 #include "gf_comm.hpp"
-
-namespace gf { int set_err(int code, const char* fmt, ...); }
+#include "gf_hip_own.hpp"
 
 namespace {
 struct Rccl {
@@ -57,7 +57,6 @@ Rccl& rccl() {
     return r;
 }
 #define NCCLCHK(expr) do { const ncclResult_t rc_ = (expr); if (rc_ != ncclSuccess) return gf::set_err(GF_ERR_HIP, "%s: %s", #expr, rccl().errorString(rc_)); } while (0)
-#define HIPCHK_(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return gf::set_err(GF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
 }  // namespace
 
 namespace gf {
@@ -72,9 +71,9 @@ int rccl_allgather_f64(const double* send, double* recv, size_t count, void* com
 
 struct gf_comm {
     ncclComm_t comm = nullptr;
-    hipStream_t stream = nullptr;
+    gf::Stream stream;
     int world = 1, rank = 0, device = 0;
-    double* d_send = nullptr; double* d_recv = nullptr; size_t cap = 0;   // staging of gf_comm_allgather_f64 (doubles per rank)
+    gf::DevBuf<double> d_send, d_recv;   // staging of gf_comm_allgather_f64: n doubles, n doubles per rank
 };
 
 extern "C" {
@@ -94,29 +93,29 @@ int gf_comm_create(const unsigned char* id128, int world, int rank, int device, 
     if (!id128 || !out || world < 1 || rank < 0 || rank >= world) return gf::set_err(GF_ERR_INVALID, "bad argument (world %d, rank %d)", world, rank);
     Rccl& r = rccl();
     if (!r.ok) return gf::set_err(GF_ERR_NO_DEVICE, "%s", r.why.c_str());
+    if (int rc = gf::require_device()) return rc;
     int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return gf::set_err(GF_ERR_NO_DEVICE, "no HIP device");
+    HIPCHK(hipGetDeviceCount(&n));
     if (device < 0 || device >= n) return gf::set_err(GF_ERR_INVALID, "device %d outside 0..%d", device, n - 1);
-    HIPCHK_(hipSetDevice(device));
-    gf_comm* c = new gf_comm;
+    HIPCHK(hipSetDevice(device));
+    std::unique_ptr<gf_comm> c(new gf_comm);
     c->world = world; c->rank = rank; c->device = device;
     ncclUniqueId id;
     memcpy(&id, id128, 128);
     const ncclResult_t rc = r.commInitRank(&c->comm, world, id, rank);
-    if (rc != ncclSuccess) { delete c; return gf::set_err(GF_ERR_HIP, "ncclCommInitRank(world %d, rank %d, device %d): %s", world, rank, device, r.errorString(rc)); }
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { r.commDestroy(c->comm); delete c; return gf::set_err(GF_ERR_HIP, "hipStreamCreate failed"); }
-    *out = c;
+    if (rc != ncclSuccess) return gf::set_err(GF_ERR_HIP, "ncclCommInitRank(world %d, rank %d, device %d): %s", world, rank, device, r.errorString(rc));
+    if (hipStreamCreateWithFlags(&c->stream.s, hipStreamNonBlocking) != hipSuccess) { r.commDestroy(c->comm); return gf::set_err(GF_ERR_HIP, "hipStreamCreate failed"); }
+    *out = c.release();
     return GF_OK;
 }
 
 int gf_comm_destroy(gf_comm* c) {
     if (!c) return GF_OK;
     (void)hipSetDevice(c->device);
-    if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-    if (c->d_send) (void)hipFree(c->d_send);
-    if (c->d_recv) (void)hipFree(c->d_recv);
-    if (c->comm) rccl().commDestroy(c->comm);
-    delete c;
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    const ncclComm_t comm = c->comm;
+    delete c;   // the staging buffers and the stream
+    if (comm) rccl().commDestroy(comm);
     return GF_OK;
 }
 
@@ -126,25 +125,19 @@ int gf_comm_info(gf_comm* c, int* world, int* rank, int* device, void** nccl_com
     if (rank) *rank = c->rank;
     if (device) *device = c->device;
     if (nccl_comm) *nccl_comm = c->comm;
-    if (stream) *stream = c->stream;
+    if (stream) *stream = c->stream.s;
     return GF_OK;
 }
 
 int gf_comm_allgather_f64(gf_comm* c, const double* send_host, int n, double* recv_host) {
     if (!c || !send_host || !recv_host || n < 1) return gf::set_err(GF_ERR_INVALID, "bad argument");
-    HIPCHK_(hipSetDevice(c->device));
-    if ((size_t)n > c->cap) {
-        if (c->d_send) (void)hipFree(c->d_send);
-        if (c->d_recv) (void)hipFree(c->d_recv);
-        c->d_send = c->d_recv = nullptr; c->cap = 0;
-        HIPCHK_(hipMalloc((void**)&c->d_send, (size_t)n * sizeof(double)));
-        HIPCHK_(hipMalloc((void**)&c->d_recv, (size_t)n * c->world * sizeof(double)));
-        c->cap = (size_t)n;
-    }
-    HIPCHK_(hipMemcpyAsync(c->d_send, send_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (int rc = gf::rccl_allgather_f64(c->d_send, c->d_recv, (size_t)n, c->comm, c->stream)) return rc;
-    HIPCHK_(hipMemcpyAsync(recv_host, c->d_recv, (size_t)n * c->world * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK_(hipStreamSynchronize(c->stream));
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(c->d_send.fit((size_t)n));
+    HIPCHK(c->d_recv.fit((size_t)n * c->world));
+    HIPCHK(hipMemcpyAsync(c->d_send.p, send_host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (int rc = gf::rccl_allgather_f64(c->d_send.p, c->d_recv.p, (size_t)n, c->comm, c->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(recv_host, c->d_recv.p, (size_t)n * c->world * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     return GF_OK;
 }
 

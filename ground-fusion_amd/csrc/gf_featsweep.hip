@@ -8,12 +8,13 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <vector>
 #include <hip/hip_runtime.h>
 #include "../../include/groundfusion_hip.h"
 #include "gf_featsweep.hpp"
+#include "gf_hip_own.hpp"
 
-namespace gf { int set_err(int code, const char* fmt, ...); }
 using namespace gfd;
 
 namespace {
@@ -62,30 +63,20 @@ __global__ void __launch_bounds__(128) moving_consistency_kernel(SweepArgs A) {
                         A.focal_length)) A.remove[f] = 1;
 }
 
-template <class T> struct DevArr {
-    T* d = nullptr; size_t cap = 0;
-    int fit(size_t n) {
-        if (n <= cap) return GF_OK;
-        if (d) (void)hipFree(d);
-        d = nullptr; cap = 0;
-        const size_t c = std::max(n, (size_t)64);
-        if (hipMalloc(&d, c * sizeof(T)) != hipSuccess) return gf::set_err(GF_ERR_HIP, "hipMalloc of %zu bytes failed", c * sizeof(T));
-        cap = c;
-        return GF_OK;
-    }
-    ~DevArr() { if (d) (void)hipFree(d); }
-};
+// grown on demand, at least 64 elements at a time
+template <class T> int fit64(gf::DevBuf<T>& b, size_t n) {
+    if (n > b.n) HIPCHK(b.fit(std::max(n, (size_t)64)));
+    return GF_OK;
+}
 }  // namespace
 
 struct gf_featsweep {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    DevArr<double> Rs, Ps, tic, ric, obs, depth;
-    DevArr<int> first_feature, start_frame, first_obs, flag, remove;
+    gf::Stream stream;
+    gf::Event ev0, ev1;
+    gf::DevBuf<double> Rs, Ps, tic, ric, obs, depth;
+    gf::DevBuf<int> first_feature, start_frame, first_obs, flag, remove;
     double kernel_ms = 0; long long launches = 0, features = 0;
 };
-
-#define FS_HIP(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return gf::set_err(GF_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
 
 static int upload_common(gf_featsweep* h, SweepArgs& A, int B, int W, const double* Rs, const double* Ps, const double* tic, const double* ric, const int* first_feature,
                          const int* start_frame, const int* first_obs, const double* obs, const double* estimated_depth) {
@@ -97,53 +88,45 @@ static int upload_common(gf_featsweep* h, SweepArgs& A, int B, int W, const doub
         const int n = first_obs[f + 1] - first_obs[f];
         if (n < 0 || start_frame[f] < 0 || start_frame[f] + n > W + 1) return gf::set_err(GF_ERR_INVALID, "feature %d: %d observations from frame %d do not fit a window of %d frames", f, n, start_frame[f], W + 1);
     }
-    if (int rc = h->Rs.fit((size_t)B * (W + 1) * 9)) return rc;
-    if (int rc = h->Ps.fit((size_t)B * (W + 1) * 3)) return rc;
-    if (int rc = h->tic.fit((size_t)B * 3)) return rc;
-    if (int rc = h->ric.fit((size_t)B * 9)) return rc;
-    if (int rc = h->obs.fit(O * 4)) return rc;
-    if (int rc = h->depth.fit(F)) return rc;
-    if (int rc = h->first_feature.fit(B + 1)) return rc;
-    if (int rc = h->start_frame.fit(F)) return rc;
-    if (int rc = h->first_obs.fit(F + 1)) return rc;
-    if (int rc = h->flag.fit(F)) return rc;
-    if (int rc = h->remove.fit(F)) return rc;
+    if (int rc = fit64(h->Rs, (size_t)B * (W + 1) * 9)) return rc;
+    if (int rc = fit64(h->Ps, (size_t)B * (W + 1) * 3)) return rc;
+    if (int rc = fit64(h->tic, (size_t)B * 3)) return rc;
+    if (int rc = fit64(h->ric, (size_t)B * 9)) return rc;
+    if (int rc = fit64(h->obs, O * 4)) return rc;
+    if (int rc = fit64(h->depth, F)) return rc;
+    if (int rc = fit64(h->first_feature, B + 1)) return rc;
+    if (int rc = fit64(h->start_frame, F)) return rc;
+    if (int rc = fit64(h->first_obs, F + 1)) return rc;
+    if (int rc = fit64(h->flag, F)) return rc;
+    if (int rc = fit64(h->remove, F)) return rc;
     hipStream_t s = h->stream;
-    FS_HIP(hipMemcpyAsync(h->Rs.d, Rs, sizeof(double) * B * (W + 1) * 9, hipMemcpyHostToDevice, s));
-    FS_HIP(hipMemcpyAsync(h->Ps.d, Ps, sizeof(double) * B * (W + 1) * 3, hipMemcpyHostToDevice, s));
-    FS_HIP(hipMemcpyAsync(h->tic.d, tic, sizeof(double) * B * 3, hipMemcpyHostToDevice, s));
-    FS_HIP(hipMemcpyAsync(h->ric.d, ric, sizeof(double) * B * 9, hipMemcpyHostToDevice, s));
-    FS_HIP(hipMemcpyAsync(h->first_feature.d, first_feature, sizeof(int) * (B + 1), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->Rs.p, Rs, sizeof(double) * B * (W + 1) * 9, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->Ps.p, Ps, sizeof(double) * B * (W + 1) * 3, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->tic.p, tic, sizeof(double) * B * 3, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->ric.p, ric, sizeof(double) * B * 9, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->first_feature.p, first_feature, sizeof(int) * (B + 1), hipMemcpyHostToDevice, s));
     if (F > 0) {
-        FS_HIP(hipMemcpyAsync(h->obs.d, obs, sizeof(double) * O * 4, hipMemcpyHostToDevice, s));
-        FS_HIP(hipMemcpyAsync(h->depth.d, estimated_depth, sizeof(double) * F, hipMemcpyHostToDevice, s));
-        FS_HIP(hipMemcpyAsync(h->start_frame.d, start_frame, sizeof(int) * F, hipMemcpyHostToDevice, s));
-        FS_HIP(hipMemcpyAsync(h->first_obs.d, first_obs, sizeof(int) * (F + 1), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h->obs.p, obs, sizeof(double) * O * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h->depth.p, estimated_depth, sizeof(double) * F, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h->start_frame.p, start_frame, sizeof(int) * F, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h->first_obs.p, first_obs, sizeof(int) * (F + 1), hipMemcpyHostToDevice, s));
     }
     A.B = B; A.W = W; A.F = F;
-    A.Rs = h->Rs.d; A.Ps = h->Ps.d; A.tic = h->tic.d; A.ric = h->ric.d; A.first_feature = h->first_feature.d; A.start_frame = h->start_frame.d; A.first_obs = h->first_obs.d;
-    A.obs = h->obs.d; A.estimated_depth = h->depth.d; A.estimate_flag = h->flag.d; A.remove = h->remove.d;
+    A.Rs = h->Rs.p; A.Ps = h->Ps.p; A.tic = h->tic.p; A.ric = h->ric.p; A.first_feature = h->first_feature.p; A.start_frame = h->start_frame.p; A.first_obs = h->first_obs.p;
+    A.obs = h->obs.p; A.estimated_depth = h->depth.p; A.estimate_flag = h->flag.p; A.remove = h->remove.p;
     return GF_OK;
 }
 
 extern "C" {
 int gf_featsweep_create(gf_featsweep** out) {
     if (!out) return gf::set_err(GF_ERR_INVALID, "null argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return gf::set_err(GF_ERR_NO_DEVICE, "no HIP device: the batched feature sweeps have no CPU fallback");
-    gf_featsweep* h = new gf_featsweep();
-    if (hipStreamCreate(&h->stream) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) { delete h; return gf::set_err(GF_ERR_HIP, "stream / event creation failed"); }
-    *out = h;
+    if (int rc = gf::require_device()) return rc;
+    std::unique_ptr<gf_featsweep> h(new gf_featsweep());
+    HIPCHK(hipStreamCreate(&h->stream.s)); HIPCHK(hipEventCreate(&h->ev0.e)); HIPCHK(hipEventCreate(&h->ev1.e));
+    *out = h.release();
     return GF_OK;
 }
-int gf_featsweep_destroy(gf_featsweep* h) {
-    if (!h) return GF_OK;
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-    return GF_OK;
-}
+int gf_featsweep_destroy(gf_featsweep* h) { delete h; return GF_OK; }
 int gf_triangulate_with_depth_batch(gf_featsweep* h, int B, int W, const double* Rs, const double* Ps, const double* tic, const double* ric, const int* first_feature,
                                     const int* start_frame, const int* first_obs, const double* obs, double depth_threshold, double init_depth, double* estimated_depth,
                                     int* estimate_flag) {
@@ -152,14 +135,14 @@ int gf_triangulate_with_depth_batch(gf_featsweep* h, int B, int W, const double*
     if (int rc = upload_common(h, A, B, W, Rs, Ps, tic, ric, first_feature, start_frame, first_obs, obs, estimated_depth)) return rc;
     if (A.F == 0) return GF_OK;
     A.depth_threshold = depth_threshold; A.init_depth = init_depth;
-    FS_HIP(hipMemcpyAsync(h->flag.d, estimate_flag, sizeof(int) * A.F, hipMemcpyHostToDevice, h->stream));
-    FS_HIP(hipEventRecord(h->ev0, h->stream));
+    HIPCHK(hipMemcpyAsync(h->flag.p, estimate_flag, sizeof(int) * A.F, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
     triangulate_with_depth_kernel<<<dim3((A.F + 127) / 128), 128, 0, h->stream>>>(A);
-    FS_HIP(hipGetLastError());
-    FS_HIP(hipEventRecord(h->ev1, h->stream));
-    FS_HIP(hipMemcpyAsync(estimated_depth, h->depth.d, sizeof(double) * A.F, hipMemcpyDeviceToHost, h->stream));
-    FS_HIP(hipMemcpyAsync(estimate_flag, h->flag.d, sizeof(int) * A.F, hipMemcpyDeviceToHost, h->stream));
-    FS_HIP(hipStreamSynchronize(h->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    HIPCHK(hipMemcpyAsync(estimated_depth, h->depth.p, sizeof(double) * A.F, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(estimate_flag, h->flag.p, sizeof(int) * A.F, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     float ms = 0;
     if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) h->kernel_ms += ms;
     h->launches++; h->features += A.F;
@@ -172,12 +155,12 @@ int gf_moving_consistency_batch(gf_featsweep* h, int B, int W, const double* Rs,
     if (int rc = upload_common(h, A, B, W, Rs, Ps, tic, ric, first_feature, start_frame, first_obs, obs, estimated_depth)) return rc;
     if (A.F == 0) return GF_OK;
     A.focal_length = focal_length;
-    FS_HIP(hipEventRecord(h->ev0, h->stream));
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
     moving_consistency_kernel<<<dim3((A.F + 127) / 128), 128, 0, h->stream>>>(A);
-    FS_HIP(hipGetLastError());
-    FS_HIP(hipEventRecord(h->ev1, h->stream));
-    FS_HIP(hipMemcpyAsync(remove, h->remove.d, sizeof(int) * A.F, hipMemcpyDeviceToHost, h->stream));
-    FS_HIP(hipStreamSynchronize(h->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    HIPCHK(hipMemcpyAsync(remove, h->remove.p, sizeof(int) * A.F, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     float ms = 0;
     if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) h->kernel_ms += ms;
     h->launches++; h->features += A.F;

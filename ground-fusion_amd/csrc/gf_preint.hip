@@ -3,13 +3,13 @@
 // WheelIntegrationBase (factor/wheel_integration_base.h:41-178), restated on the small matrix type below.
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <vector>
 #include <hip/hip_runtime.h>
 #include "../../include/groundfusion_hip.h"
 #include "gf_dmath.hpp"
 #include "gf_preint.hpp"
-
-namespace gf { int set_err(int code, const char* fmt, ...); }
+#include "gf_hip_own.hpp"
 using namespace gfd;
 
 namespace {
@@ -240,46 +240,35 @@ __global__ __launch_bounds__(64) void imu_preint_batch_kernel(int n, const Prein
 }
 
 struct PreintBatch {
-    hipStream_t stream = nullptr;
-    PreintJobDev* d_jobs = nullptr; double *d_dt = nullptr, *d_acc = nullptr, *d_gyr = nullptr, *d_out = nullptr;
-    PreintJobDev* h_jobs = nullptr; double *h_dt = nullptr, *h_acc = nullptr, *h_gyr = nullptr, *h_out = nullptr;   // pinned
-    int cap_jobs = 0, cap_samples = 0;
+    gf::Stream stream;
+    gf::Event ev0, ev1;
+    gf::DevBuf<PreintJobDev> d_jobs; gf::DevBuf<double> d_dt, d_acc, d_gyr, d_out;
+    gf::PinBuf<PreintJobDev> h_jobs; gf::PinBuf<double> h_dt, h_acc, h_gyr, h_out;
+    int cap_jobs = 0, cap_samples = 0;   // what every buffer of the two groups holds (0 while a group is incomplete)
     double t_kernel_ms = 0; long long launches = 0, intervals = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ~PreintBatch() {
-        (void)hipFree(d_jobs); (void)hipFree(d_dt); (void)hipFree(d_acc); (void)hipFree(d_gyr); (void)hipFree(d_out);
-        (void)hipHostFree(h_jobs); (void)hipHostFree(h_dt); (void)hipHostFree(h_acc); (void)hipHostFree(h_gyr); (void)hipHostFree(h_out);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
-#define GF_PRE_HIP(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return gf::set_err(e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice ? GF_ERR_NO_DEVICE : GF_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
 int preint_batch_create(PreintBatch** out) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return gf::set_err(GF_ERR_NO_DEVICE, "no HIP device: batched pre-integration has no CPU fallback (use gf_imu_preintegrate on the host)");
-    PreintBatch* b = new PreintBatch();
-    if (hipStreamCreate(&b->stream) != hipSuccess || hipEventCreate(&b->ev0) != hipSuccess || hipEventCreate(&b->ev1) != hipSuccess) { delete b; return gf::set_err(GF_ERR_HIP, "hipStreamCreate / hipEventCreate failed"); }
-    *out = b;
+    if (int rc = require_device()) return rc;   // (gf_imu_preintegrate is the host's form)
+    std::unique_ptr<PreintBatch> b(new PreintBatch());
+    HIPCHK(hipStreamCreate(&b->stream.s)); HIPCHK(hipEventCreate(&b->ev0.e)); HIPCHK(hipEventCreate(&b->ev1.e));
+    *out = b.release();
     return GF_OK;
 }
 void preint_batch_destroy(PreintBatch* b) { delete b; }
 static int preint_reserve(PreintBatch* b, int jobs, int samples) {
     if (jobs > b->cap_jobs) {
-        const int c = std::max(jobs, 2 * b->cap_jobs);
-        (void)hipFree(b->d_jobs); (void)hipFree(b->d_out); (void)hipHostFree(b->h_jobs); (void)hipHostFree(b->h_out);
-        b->d_jobs = nullptr; b->d_out = nullptr; b->h_jobs = nullptr; b->h_out = nullptr; b->cap_jobs = 0;
-        GF_PRE_HIP(hipMalloc(&b->d_jobs, sizeof(PreintJobDev) * c)); GF_PRE_HIP(hipMalloc(&b->d_out, sizeof(double) * PREINT_OUT * c));
-        GF_PRE_HIP(hipHostMalloc(&b->h_jobs, sizeof(PreintJobDev) * c)); GF_PRE_HIP(hipHostMalloc(&b->h_out, sizeof(double) * PREINT_OUT * c));
-        b->cap_jobs = c;
+        const size_t c = std::max(jobs, 2 * b->cap_jobs);   // doubling
+        b->cap_jobs = 0;
+        HIPCHK(b->d_jobs.fit(c)); HIPCHK(b->d_out.fit(PREINT_OUT * c));
+        HIPCHK(b->h_jobs.fit(c)); HIPCHK(b->h_out.fit(PREINT_OUT * c));
+        b->cap_jobs = (int)c;
     }
     if (samples > b->cap_samples) {
-        const int c = std::max(samples, 2 * b->cap_samples);
-        (void)hipFree(b->d_dt); (void)hipFree(b->d_acc); (void)hipFree(b->d_gyr); (void)hipHostFree(b->h_dt); (void)hipHostFree(b->h_acc); (void)hipHostFree(b->h_gyr);
-        b->d_dt = b->d_acc = b->d_gyr = nullptr; b->h_dt = b->h_acc = b->h_gyr = nullptr; b->cap_samples = 0;
-        GF_PRE_HIP(hipMalloc(&b->d_dt, sizeof(double) * c)); GF_PRE_HIP(hipMalloc(&b->d_acc, sizeof(double) * 3 * c)); GF_PRE_HIP(hipMalloc(&b->d_gyr, sizeof(double) * 3 * c));
-        GF_PRE_HIP(hipHostMalloc(&b->h_dt, sizeof(double) * c)); GF_PRE_HIP(hipHostMalloc(&b->h_acc, sizeof(double) * 3 * c)); GF_PRE_HIP(hipHostMalloc(&b->h_gyr, sizeof(double) * 3 * c));
-        b->cap_samples = c;
+        const size_t c = std::max(samples, 2 * b->cap_samples);
+        b->cap_samples = 0;
+        HIPCHK(b->d_dt.fit(c)); HIPCHK(b->d_acc.fit(3 * c)); HIPCHK(b->d_gyr.fit(3 * c));
+        HIPCHK(b->h_dt.fit(c)); HIPCHK(b->h_acc.fit(3 * c)); HIPCHK(b->h_gyr.fit(3 * c));
+        b->cap_samples = (int)c;
     }
     return GF_OK;
 }
@@ -293,30 +282,30 @@ int preint_batch_run(PreintBatch* b, const std::vector<PreintJob>& jobs, const d
     int off = 0;
     for (int i = 0; i < n; i++) {
         const PreintJob& j = jobs[i];
-        PreintJobDev& d = b->h_jobs[i];
+        PreintJobDev& d = b->h_jobs.p[i];
         d.s0 = off; d.s1 = off + j.n;
         for (int k = 0; k < 3; k++) { d.acc0[k] = j.acc0[k]; d.gyr0[k] = j.gyr0[k]; d.ba[k] = j.ba[k]; d.bg[k] = j.bg[k]; }
-        if (j.n > 0) { memcpy(b->h_dt + off, j.dt, sizeof(double) * j.n); memcpy(b->h_acc + 3 * off, j.acc, sizeof(double) * 3 * j.n); memcpy(b->h_gyr + 3 * off, j.gyr, sizeof(double) * 3 * j.n); }
+        if (j.n > 0) { memcpy(b->h_dt.p + off, j.dt, sizeof(double) * j.n); memcpy(b->h_acc.p + 3 * off, j.acc, sizeof(double) * 3 * j.n); memcpy(b->h_gyr.p + 3 * off, j.gyr, sizeof(double) * 3 * j.n); }
         off += j.n;
     }
-    GF_PRE_HIP(hipMemcpyAsync(b->d_jobs, b->h_jobs, sizeof(PreintJobDev) * n, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipMemcpyAsync(b->d_jobs.p, b->h_jobs.p, sizeof(PreintJobDev) * n, hipMemcpyHostToDevice, b->stream));
     if (total > 0) {
-        GF_PRE_HIP(hipMemcpyAsync(b->d_dt, b->h_dt, sizeof(double) * total, hipMemcpyHostToDevice, b->stream));
-        GF_PRE_HIP(hipMemcpyAsync(b->d_acc, b->h_acc, sizeof(double) * 3 * total, hipMemcpyHostToDevice, b->stream));
-        GF_PRE_HIP(hipMemcpyAsync(b->d_gyr, b->h_gyr, sizeof(double) * 3 * total, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(hipMemcpyAsync(b->d_dt.p, b->h_dt.p, sizeof(double) * total, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(hipMemcpyAsync(b->d_acc.p, b->h_acc.p, sizeof(double) * 3 * total, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(hipMemcpyAsync(b->d_gyr.p, b->h_gyr.p, sizeof(double) * 3 * total, hipMemcpyHostToDevice, b->stream));
     }
-    GF_PRE_HIP(hipEventRecord(b->ev0, b->stream));
-    hipLaunchKernelGGL(imu_preint_batch_kernel, dim3(n), dim3(64), 0, b->stream, n, b->d_jobs, b->d_dt, b->d_acc, b->d_gyr, noise[0], noise[1], noise[2], noise[3], b->d_out);
-    GF_PRE_HIP(hipGetLastError());
-    GF_PRE_HIP(hipEventRecord(b->ev1, b->stream));
-    GF_PRE_HIP(hipMemcpyAsync(b->h_out, b->d_out, sizeof(double) * PREINT_OUT * n, hipMemcpyDeviceToHost, b->stream));
-    GF_PRE_HIP(hipStreamSynchronize(b->stream));
+    HIPCHK(hipEventRecord(b->ev0, b->stream));
+    hipLaunchKernelGGL(imu_preint_batch_kernel, dim3(n), dim3(64), 0, b->stream, n, b->d_jobs.p, b->d_dt.p, b->d_acc.p, b->d_gyr.p, noise[0], noise[1], noise[2], noise[3], b->d_out.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(b->ev1, b->stream));
+    HIPCHK(hipMemcpyAsync(b->h_out.p, b->d_out.p, sizeof(double) * PREINT_OUT * n, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
     float ms = 0;
     if (hipEventElapsedTime(&ms, b->ev0, b->ev1) == hipSuccess) b->t_kernel_ms += ms;
     b->launches++; b->intervals += n;
     for (int i = 0; i < n; i++) {
         ImuPreState& st = *jobs[i].st;
-        const double* o = b->h_out + (size_t)i * PREINT_OUT;
+        const double* o = b->h_out.p + (size_t)i * PREINT_OUT;
         memcpy(st.dp, o, 24); memcpy(st.dq, o + 3, 32); memcpy(st.dv, o + 7, 24);
         st.sum_dt = o[10];
         const int last = jobs[i].n - 1;

@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <set>
 #include <string>
 #include <vector>
@@ -31,6 +32,7 @@
 #include "gf_lk_kernels.hpp"
 #include "gf_copy_list.hpp"
 #include "gf_host_cpus.hpp"
+#include "gf_hip_own.hpp"
 
 namespace gf {
 
@@ -46,14 +48,6 @@ int set_err(int code, const char* fmt, ...) {
     va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
     g_err = buf;
     return code;
-}
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return gf::set_err(GF_ERR_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
-
-static int require_device() {
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0) return set_err(GF_ERR_NO_DEVICE, "no HIP device available (%s); the HIP path has no CPU fallback", hipGetErrorString(e));
-    return GF_OK;
 }
 
 struct P2f { float x, y; };
@@ -113,32 +107,6 @@ class HostPool {
     bool stop_ = false;
 };
 
-template <class T> struct DevBuf {
-    T* p = nullptr; size_t n = 0;
-    int alloc(size_t count) {
-        n = count;
-        hipError_t e = hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e != hipSuccess) return set_err(GF_ERR_HIP, "hipMalloc(%zu B) failed: %s", count * sizeof(T), hipGetErrorString(e));
-        // zeros, explicitly and finished before the handle's non-blocking stream can touch the buffer: hipMalloc returns whatever the previous owner left
-        if (hipMemset(p, 0, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) return set_err(GF_ERR_HIP, "hipMemset failed");
-        return GF_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-};
-template <class T> struct PinBuf {
-    T* p = nullptr; size_t n = 0;
-    T* hd = nullptr;   // the same memory as kernels address it (page-locked memory is mapped into the device's address space), or null
-    int alloc(size_t count) {
-        n = count;
-        hipError_t e = hipHostMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault);
-        if (e != hipSuccess) return set_err(GF_ERR_HIP, "hipHostMalloc failed: %s", hipGetErrorString(e));
-        memset(p, 0, std::max<size_t>(count, 1) * sizeof(T));
-        void* q = nullptr; hd = hipHostGetDevicePointer(&q, p, 0) == hipSuccess ? static_cast<T*>(q) : nullptr; (void)hipGetLastError();
-        return GF_OK;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; }
-};
-
 static void make_disk_table(int radius, DiskTable& T) {  // drawing.cpp Circle(): union of the h-lines per row offset
     T.radius = radius;
     for (int i = 0; i <= kMaxRadius; i++) T.hw[i] = -1;
@@ -186,11 +154,12 @@ struct gf_tracker {
     bool select_topk = true;  // GF_SELECT_TOPK=0: every frame's corners through the sort
     int lk_points = 1;        // points per wavefront of the LK kernel: 1 (lk_track_kernel), 2 or 4 (lk_track_mp_kernel, round 6); GF_LK_POINTS
     bool profiling = false;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[8] = {};   // ev[7]: end of the equalisation (cfg.equalize)
+    // Members are destroyed in reverse order: the pool (last member) is joined before anything its threads could touch goes, the buffers go before the events and streams.
+    Stream stream, copy_stream;   // copy_stream, ev_copy: gf_tracker_prefetch_batch (created on first use)
+    Event ev[8];   // ev[7]: end of the equalisation (cfg.equalize)
+    Event ev_copy[2];
     gf_tracker_stats stats{};
     std::vector<SeqState> seq;
-    HostPool* pool = nullptr;
     // device
     DevBuf<uint8_t> d_img, d_raw, d_mask, d_status, d_fwd_status, d_seqmask;
     DevBuf<uint8_t> d_eq, d_eq_lut;   // cfg.equalize: the equalised frames the pyramid reads, and the CLAHE tile LUTs
@@ -204,7 +173,6 @@ struct gf_tracker {
     DevBuf<uint16_t> d_depth, d_depth_out, d_out_depth;
     // gf_tracker_prefetch_batch: the next frame's images on their way to the second pair of frame buffers while the current frame's kernels run
     DevBuf<uint8_t> d_raw2; DevBuf<uint16_t> d_depth2;
-    hipStream_t copy_stream = nullptr; hipEvent_t ev_copy[2] = {nullptr, nullptr};
     int pf_head = 0, pf_count = 0;   // FIFO of staged frames over the two pairs (0: d_raw / d_depth, 1: d_raw2 / d_depth2): oldest pair, number staged (0..2)
     std::vector<int> pf_seq[2];      // the sequences each staged frame holds, in the order of its images (two staged frames may name different sets)
     bool pf_depth[2] = {false, false};
@@ -224,21 +192,7 @@ struct gf_tracker {
     size_t eig_stride = 0, mask_stride = 0;
     size_t select_lds = 0;
 
-    void release() {
-        d_raw2.release(); d_depth2.release(); d_eq.release(); d_eq_lut.release(); d_cur.release(); h_cur.release(); d_det.release(); h_det.release();
-        for (auto& e : ev_copy) if (e) (void)hipEventDestroy(e);
-        if (copy_stream) (void)hipStreamDestroy(copy_stream);
-        d_img.release(); d_raw.release(); d_mask.release(); d_status.release(); d_fwd_status.release(); d_seqmask.release(); d_npts.release();
-        d_cand_count.release(); d_want.release(); d_ncenters.release(); d_out_n.release(); d_depth.release(); d_depth_out.release();
-        d_out_depth.release(); d_prev_pts.release(); d_init_pts.release(); d_cur_pts.release(); d_out_pts.release(); d_counters.release();
-        d_maxkey.release(); d_eig.release(); d_cand.release(); d_centers.release();
-        h_npts.release(); h_want.release(); h_ncenters.release(); h_out_n.release(); h_cand_count.release(); h_prev_pts.release();
-        h_init_pts.release(); h_cur_pts.release(); h_out_pts.release(); h_status.release(); h_fwd_status.release(); h_seqmask.release(); h_depth_out.release();
-        h_out_depth.release(); h_counters.release(); h_centers.release();
-        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-        delete pool; pool = nullptr;
-    }
+    std::unique_ptr<HostPool> pool;
 };
 
 namespace gf {
@@ -729,7 +683,7 @@ int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out) {
         return gf::set_err(GF_ERR_INVALID, "unsupported tracker configuration (width %% 4 == 0, width/height >= 32, 0 <= min_dist <= %d)", gf::kMaxRadius);
     if (cfg->equalize != 0 && cfg->equalize != 1) return gf::set_err(GF_ERR_INVALID, "gf_tracker_cfg.equalize must be 0 or 1, got %d", cfg->equalize);
     if (int rc = gf::require_device()) return rc;
-    gf_tracker* h = new gf_tracker();
+    std::unique_ptr<gf_tracker> h(new gf_tracker());
     h->cfg = *cfg;
     h->B = cfg->batch;
     h->cap = (cfg->max_cnt + 3) & ~3;
@@ -746,7 +700,7 @@ int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out) {
         nthr = std::max(1, std::min(nthr, std::max(hw, 1)));
         int dev = 0;
         (void)hipGetDevice(&dev);
-        h->pool = new gf::HostPool(h->B >= 8 ? nthr - 1 : 0, dev);
+        h->pool.reset(new gf::HostPool(h->B >= 8 ? nthr - 1 : 0, dev));
         h->copy_lists = !(getenv("GF_TRACKER_COPIES") && atoi(getenv("GF_TRACKER_COPIES")) != 0);
         h->pyr_head = !(getenv("GF_PYR_HEAD") && atoi(getenv("GF_PYR_HEAD")) == 0);
         h->select_topk = !(getenv("GF_SELECT_TOPK") && atoi(getenv("GF_SELECT_TOPK")) == 0);
@@ -764,43 +718,35 @@ int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out) {
     h->sort_cap = gf::kSortLds;
     while (h->sort_cap > 64 && (size_t)h->sort_cap * 8 + grid_lds > 160 * 1024) h->sort_cap >>= 1;
     h->select_lds = (size_t)h->sort_cap * 8 + grid_lds;
-    if (h->select_lds > 160 * 1024) { delete h; return gf::set_err(GF_ERR_INVALID, "min_dist %d too small for the selection grid at %dx%d", cfg->min_dist, W, H); }
-#define A_(x) do { if (int rc_ = (x)) { h->release(); delete h; return rc_; } } while (0)
-#define H_(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { gf::set_err(GF_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); h->release(); delete h; return GF_ERR_HIP; } } while (0)
-    H_(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    for (auto& e : h->ev) H_(hipEventCreate(&e));
-    A_(h->d_img.alloc((size_t)B * 2 * h->G.img_bytes));
-    A_(h->d_raw.alloc((size_t)B * W * H));
-    if (cfg->equalize) { A_(h->d_eq.alloc((size_t)B * W * H)); A_(h->d_eq_lut.alloc(gf::clahe_lut_bytes(B, gf::kClaheTiles, gf::kClaheTiles))); }
+    if (h->select_lds > 160 * 1024) return gf::set_err(GF_ERR_INVALID, "min_dist %d too small for the selection grid at %dx%d", cfg->min_dist, W, H);
+    HIPCHK(hipStreamCreateWithFlags(&h->stream.s, hipStreamNonBlocking));
+    for (auto& e : h->ev) HIPCHK(hipEventCreate(&e.e));
+    // The allocations as explicit statements, in this order: a buffer's place in the sequence decides which memory it gets.
+    HIPCHK(h->d_img.alloc((size_t)B * 2 * h->G.img_bytes));
+    HIPCHK(h->d_raw.alloc((size_t)B * W * H));
+    if (cfg->equalize) { HIPCHK(h->d_eq.alloc((size_t)B * W * H)); HIPCHK(h->d_eq_lut.alloc(gf::clahe_lut_bytes(B, gf::kClaheTiles, gf::kClaheTiles))); }
     // (no device copy of the depth images: the host entry points sample them on the host, the device entry point reads the caller's device pointer)
-    A_(h->d_mask.alloc(h->mask_stride));  // explicit masks exist only in the gf_good_features building block
-    A_(h->d_eig.alloc(h->eig_stride));    // response image materialised only by gf_min_eigen_val
-    A_(h->d_cand.alloc((size_t)B * h->cand_cap));
-    A_(h->d_status.alloc((size_t)B * cap)); A_(h->d_fwd_status.alloc((size_t)B * cap)); A_(h->d_seqmask.alloc(2 * (size_t)B));
-    A_(h->d_npts.alloc(B)); A_(h->d_cand_count.alloc(B)); A_(h->d_want.alloc(B)); A_(h->d_ncenters.alloc(B)); A_(h->d_out_n.alloc(B));
-    A_(h->d_depth_out.alloc((size_t)B * cap)); A_(h->d_out_depth.alloc((size_t)B * cap));
-    A_(h->d_prev_pts.alloc((size_t)B * cap)); A_(h->d_init_pts.alloc((size_t)B * cap)); A_(h->d_cur_pts.alloc((size_t)B * cap)); A_(h->d_out_pts.alloc((size_t)B * cap));
-    A_(h->d_counters.alloc((size_t)B * cap * 2)); A_(h->d_maxkey.alloc(B)); A_(h->d_centers.alloc((size_t)B * cap));
-    A_(h->h_npts.alloc(B)); A_(h->h_want.alloc(B)); A_(h->h_ncenters.alloc(B)); A_(h->h_out_n.alloc(B)); A_(h->h_cand_count.alloc(B));
-    A_(h->h_prev_pts.alloc((size_t)B * cap)); A_(h->h_init_pts.alloc((size_t)B * cap)); A_(h->h_cur_pts.alloc((size_t)B * cap)); A_(h->h_out_pts.alloc((size_t)B * cap));
-    A_(h->h_status.alloc((size_t)B * cap)); A_(h->h_fwd_status.alloc((size_t)B * cap)); A_(h->h_seqmask.alloc(2 * (size_t)B)); A_(h->h_depth_out.alloc((size_t)B * cap)); A_(h->h_out_depth.alloc((size_t)B * cap));
-    A_(h->h_counters.alloc((size_t)B * cap * 2)); A_(h->h_centers.alloc((size_t)B * cap));
-    A_(h->d_cur.alloc(B)); A_(h->h_cur.alloc(B)); A_(h->d_det.alloc(B)); A_(h->h_det.alloc(B));   // behind the others, whose places relative to each other stay as measured
-    H_(hipMemsetAsync(h->d_img.p, 0, h->d_img.n, h->stream));
-    H_(hipFuncSetAttribute(reinterpret_cast<const void*>(gf::select_corners_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->select_lds));
-    H_(hipStreamSynchronize(h->stream));
-#undef A_
-#undef H_
-    *out = h;
+    HIPCHK(h->d_mask.alloc(h->mask_stride));  // explicit masks exist only in the gf_good_features building block
+    HIPCHK(h->d_eig.alloc(h->eig_stride));    // response image materialised only by gf_min_eigen_val
+    HIPCHK(h->d_cand.alloc((size_t)B * h->cand_cap));
+    HIPCHK(h->d_status.alloc((size_t)B * cap)); HIPCHK(h->d_fwd_status.alloc((size_t)B * cap)); HIPCHK(h->d_seqmask.alloc(2 * (size_t)B));
+    HIPCHK(h->d_npts.alloc(B)); HIPCHK(h->d_cand_count.alloc(B)); HIPCHK(h->d_want.alloc(B)); HIPCHK(h->d_ncenters.alloc(B)); HIPCHK(h->d_out_n.alloc(B));
+    HIPCHK(h->d_depth_out.alloc((size_t)B * cap)); HIPCHK(h->d_out_depth.alloc((size_t)B * cap));
+    HIPCHK(h->d_prev_pts.alloc((size_t)B * cap)); HIPCHK(h->d_init_pts.alloc((size_t)B * cap)); HIPCHK(h->d_cur_pts.alloc((size_t)B * cap)); HIPCHK(h->d_out_pts.alloc((size_t)B * cap));
+    HIPCHK(h->d_counters.alloc((size_t)B * cap * 2)); HIPCHK(h->d_maxkey.alloc(B)); HIPCHK(h->d_centers.alloc((size_t)B * cap));
+    HIPCHK(h->h_npts.alloc(B)); HIPCHK(h->h_want.alloc(B)); HIPCHK(h->h_ncenters.alloc(B)); HIPCHK(h->h_out_n.alloc(B)); HIPCHK(h->h_cand_count.alloc(B));
+    HIPCHK(h->h_prev_pts.alloc((size_t)B * cap)); HIPCHK(h->h_init_pts.alloc((size_t)B * cap)); HIPCHK(h->h_cur_pts.alloc((size_t)B * cap)); HIPCHK(h->h_out_pts.alloc((size_t)B * cap));
+    HIPCHK(h->h_status.alloc((size_t)B * cap)); HIPCHK(h->h_fwd_status.alloc((size_t)B * cap)); HIPCHK(h->h_seqmask.alloc(2 * (size_t)B)); HIPCHK(h->h_depth_out.alloc((size_t)B * cap)); HIPCHK(h->h_out_depth.alloc((size_t)B * cap));
+    HIPCHK(h->h_counters.alloc((size_t)B * cap * 2)); HIPCHK(h->h_centers.alloc((size_t)B * cap));
+    HIPCHK(h->d_cur.alloc(B)); HIPCHK(h->h_cur.alloc(B)); HIPCHK(h->d_det.alloc(B)); HIPCHK(h->h_det.alloc(B));   // behind the others, whose places relative to each other stay as measured
+    HIPCHK(hipMemsetAsync(h->d_img.p, 0, h->d_img.n, h->stream));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(gf::select_corners_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->select_lds));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *out = h.release();
     return GF_OK;
 }
 
-int gf_tracker_destroy(gf_tracker* h) {
-    if (!h) return GF_OK;
-    h->release();
-    delete h;
-    return GF_OK;
-}
+int gf_tracker_destroy(gf_tracker* h) { delete h; return GF_OK; }
 
 // ---- trackImage (feature_tracker.h:47) for the listed sequences of a handle.  t[i], gray[i], depth[i], out[i * cap ..], n_out[i] belong to sequence seq[i].
 int gf_tracker_track_some_device(gf_tracker* h, int count, const int* seq, const double* t, const void* d_gray, const void* d_depth, gf_feature_obs* out, int cap,
@@ -845,9 +791,9 @@ int gf_tracker_prefetch_some(gf_tracker* h, int count, const int* seq, const uin
     }
     if (h->pf_count >= 2) return gf::set_err(GF_ERR_CAPACITY, "two frames are staged already: gf_tracker_track_prefetched has to consume one first");
     if (!h->copy_stream) {
-        HIPCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-        for (auto& e : h->ev_copy) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        if (int rc = h->d_raw2.alloc((size_t)h->B * W * H)) return rc;
+        HIPCHK(hipStreamCreateWithFlags(&h->copy_stream.s, hipStreamNonBlocking));
+        for (auto& e : h->ev_copy) HIPCHK(hipEventCreateWithFlags(&e.e, hipEventDisableTiming));
+        HIPCHK(h->d_raw2.alloc((size_t)h->B * W * H));
     }
     const int slot = (h->pf_head + h->pf_count) & 1;      // a pair no frame in flight uses: track calls return when their frame is done
     uint8_t* raw = slot ? h->d_raw2.p : h->d_raw.p;
@@ -900,7 +846,7 @@ int gf_host_alloc(size_t bytes, void** out) {
     if (hipHostMalloc(out, bytes, hipHostMallocDefault) != hipSuccess) return gf::set_err(GF_ERR_HIP, "hipHostMalloc(%zu) failed", bytes);
     return GF_OK;
 }
-int gf_host_free(void* p) { if (p) (void)hipHostFree(p); return GF_OK; }
+int gf_host_free(void* p) { gf::pinned_free(p); return GF_OK; }
 
 // the list of one: any sequence of any handle
 int gf_tracker_track(gf_tracker* h, int seq, double t, const uint8_t* gray, int stride, const uint16_t* depth, int dstride, gf_feature_obs* out,
@@ -954,137 +900,121 @@ int gf_tracker_get_stats(gf_tracker* h, gf_tracker_stats* out) { if (!h || !out)
 int gf_tracker_reset_stats(gf_tracker* h) { if (!h) return gf::set_err(GF_ERR_INVALID, "null handle"); h->stats = gf_tracker_stats{}; return GF_OK; }
 
 // ------------------------------------------------------------------ building blocks for parity tests
-static int tmp_handle(int width, int height, int max_cnt, int min_dist, gf_tracker** h) {
+static int tmp_handle(int width, int height, int max_cnt, int min_dist, std::unique_ptr<gf_tracker>& own) {
     gf_tracker_cfg c{};
     c.width = width; c.height = height; c.batch = 1; c.max_cnt = max_cnt; c.min_dist = min_dist; c.flow_back = 0; c.depth_cam = 0;
     c.fx = c.fy = 1; c.cx = c.cy = 0;
-    return gf_tracker_create(&c, h);
+    gf_tracker* h = nullptr;
+    const int rc = gf_tracker_create(&c, &h);
+    own.reset(h);
+    return rc;
 }
 
 int gf_lk_track(const uint8_t* prev, const uint8_t* next, int width, int height, const float* prev_pts, float* next_pts, uint8_t* status, int n,
                 int max_level, int use_initial_flow, long long* iterations) {
     if (!prev || !next || !prev_pts || !next_pts || !status || n < 0) return gf::set_err(GF_ERR_INVALID, "bad argument");
     if (n == 0) return GF_OK;
-    gf_tracker* h = nullptr;
-    if (int rc = tmp_handle(width, height, n, 30, &h)) return rc;
-    int rc = GF_OK;
-    auto body = [&]() -> int {
-        const size_t px = (size_t)width * height;
-        HIPCHK(hipMemcpyAsync(h->d_raw.p, prev, px, hipMemcpyHostToDevice, h->stream));
-        if (int r = gf::launch_pyramid_one(h, h->d_raw.p, 0)) return r;
-        HIPCHK(hipStreamSynchronize(h->stream));
-        HIPCHK(hipMemcpyAsync(h->d_raw.p, next, px, hipMemcpyHostToDevice, h->stream));
-        if (int r = gf::launch_pyramid_one(h, h->d_raw.p, 1)) return r;   // LK below: new frame in pyramid 1, previous one in pyramid 0
-        h->h_npts.p[0] = n;
-        for (int i = 0; i < n; i++) {
-            h->h_prev_pts.p[i] = make_float2(prev_pts[2 * i], prev_pts[2 * i + 1]);
-            h->h_init_pts.p[i] = make_float2(next_pts[2 * i], next_pts[2 * i + 1]);
-        }
-        HIPCHK(hipMemcpyAsync(h->d_npts.p, h->h_npts.p, sizeof(int), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->d_prev_pts.p, h->h_prev_pts.p, (size_t)h->cap * sizeof(float2), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->d_init_pts.p, h->h_init_pts.p, (size_t)h->cap * sizeof(float2), hipMemcpyHostToDevice, h->stream));
-        gf::launch_lk(h, 1, gf::lk_args(h, max_level, use_initial_flow ? 1 : 0, 0, 0, nullptr, nullptr));
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(h->h_cur_pts.p, h->d_cur_pts.p, (size_t)h->cap * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(h->h_status.p, h->d_status.p, (size_t)h->cap, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(h->h_counters.p, h->d_counters.p, (size_t)h->cap * 2 * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        long long it = 0;
-        for (int i = 0; i < n; i++) {
-            next_pts[2 * i] = h->h_cur_pts.p[i].x; next_pts[2 * i + 1] = h->h_cur_pts.p[i].y;
-            status[i] = h->h_status.p[i];
-            it += h->h_counters.p[2 * i + 1];
-        }
-        if (iterations) *iterations = it;
-        return GF_OK;
-    };
-    rc = body();
-    gf_tracker_destroy(h);
-    return rc;
+    std::unique_ptr<gf_tracker> own;   // the handle lives for this call
+    if (int rc = tmp_handle(width, height, n, 30, own)) return rc;
+    gf_tracker* h = own.get();
+    const size_t px = (size_t)width * height;
+    HIPCHK(hipMemcpyAsync(h->d_raw.p, prev, px, hipMemcpyHostToDevice, h->stream));
+    if (int r = gf::launch_pyramid_one(h, h->d_raw.p, 0)) return r;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_raw.p, next, px, hipMemcpyHostToDevice, h->stream));
+    if (int r = gf::launch_pyramid_one(h, h->d_raw.p, 1)) return r;   // LK below: new frame in pyramid 1, previous one in pyramid 0
+    h->h_npts.p[0] = n;
+    for (int i = 0; i < n; i++) {
+        h->h_prev_pts.p[i] = make_float2(prev_pts[2 * i], prev_pts[2 * i + 1]);
+        h->h_init_pts.p[i] = make_float2(next_pts[2 * i], next_pts[2 * i + 1]);
+    }
+    HIPCHK(hipMemcpyAsync(h->d_npts.p, h->h_npts.p, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_prev_pts.p, h->h_prev_pts.p, (size_t)h->cap * sizeof(float2), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_init_pts.p, h->h_init_pts.p, (size_t)h->cap * sizeof(float2), hipMemcpyHostToDevice, h->stream));
+    gf::launch_lk(h, 1, gf::lk_args(h, max_level, use_initial_flow ? 1 : 0, 0, 0, nullptr, nullptr));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h->h_cur_pts.p, h->d_cur_pts.p, (size_t)h->cap * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->h_status.p, h->d_status.p, (size_t)h->cap, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->h_counters.p, h->d_counters.p, (size_t)h->cap * 2 * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    long long it = 0;
+    for (int i = 0; i < n; i++) {
+        next_pts[2 * i] = h->h_cur_pts.p[i].x; next_pts[2 * i + 1] = h->h_cur_pts.p[i].y;
+        status[i] = h->h_status.p[i];
+        it += h->h_counters.p[2 * i + 1];
+    }
+    if (iterations) *iterations = it;
+    return GF_OK;
 }
 
 int gf_pyramid_level(const uint8_t* img, int width, int height, int level, uint8_t* out, int16_t* deriv_xy) {
     if (!img || level < 0) return gf::set_err(GF_ERR_INVALID, "bad argument");
-    gf_tracker* h = nullptr;
-    if (int rc = tmp_handle(width, height, 4, 30, &h)) return rc;
-    auto body = [&]() -> int {
-        if (level >= h->G.nlevels) return gf::set_err(GF_ERR_INVALID, "level %d not built (pyramid has %d levels)", level, h->G.nlevels);
-        HIPCHK(hipMemcpyAsync(h->d_raw.p, img, (size_t)width * height, hipMemcpyHostToDevice, h->stream));
-        if (int r = gf::launch_pyramid_one(h, h->d_raw.p, 0)) return r;
+    std::unique_ptr<gf_tracker> own;   // the handle lives for this call
+    if (int rc = tmp_handle(width, height, 4, 30, own)) return rc;
+    gf_tracker* h = own.get();
+    if (level >= h->G.nlevels) return gf::set_err(GF_ERR_INVALID, "level %d not built (pyramid has %d levels)", level, h->G.nlevels);
+    HIPCHK(hipMemcpyAsync(h->d_raw.p, img, (size_t)width * height, hipMemcpyHostToDevice, h->stream));
+    if (int r = gf::launch_pyramid_one(h, h->d_raw.p, 0)) return r;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const gf::LevelGeom g = h->G.lv[level];
+    if (out) HIPCHK(hipMemcpy2D(out, g.w, h->d_img.p + g.img_off, g.stride, g.w, g.h, hipMemcpyDeviceToHost));
+    if (deriv_xy) {   // the derivative as lk_solve evaluates it (deriv_probe_kernel calls the same device functions)
+        gf::DevBuf<int> d;
+        HIPCHK(d.alloc((size_t)g.w * g.h));
+        gf::deriv_probe_kernel<<<dim3((((g.w + 7) >> 3) * g.h + 255) / 256), 256, 0, h->stream>>>(h->d_img.p, g, d.p);
+        HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(h->stream));
-        const gf::LevelGeom g = h->G.lv[level];
-        if (out) HIPCHK(hipMemcpy2D(out, g.w, h->d_img.p + g.img_off, g.stride, g.w, g.h, hipMemcpyDeviceToHost));
-        if (deriv_xy) {   // the derivative as lk_solve evaluates it (deriv_probe_kernel calls the same device functions)
-            gf::DevBuf<int> d;
-            if (int r = d.alloc((size_t)g.w * g.h)) return r;
-            gf::deriv_probe_kernel<<<dim3((((g.w + 7) >> 3) * g.h + 255) / 256), 256, 0, h->stream>>>(h->d_img.p, g, d.p);
-            hipError_t e = hipGetLastError();
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-            if (e == hipSuccess) e = hipMemcpy(deriv_xy, d.p, (size_t)g.w * g.h * 4, hipMemcpyDeviceToHost);
-            d.release();
-            HIPCHK(e);
-        }
-        return GF_OK;
-    };
-    int rc = body();
-    gf_tracker_destroy(h);
-    return rc;
+        HIPCHK(hipMemcpy(deriv_xy, d.p, (size_t)g.w * g.h * 4, hipMemcpyDeviceToHost));
+    }
+    return GF_OK;
 }
 
 int gf_min_eigen_val(const uint8_t* img, int width, int height, float* eig) {
     if (!img || !eig) return gf::set_err(GF_ERR_INVALID, "bad argument");
-    gf_tracker* h = nullptr;
-    if (int rc = tmp_handle(width, height, 4, 30, &h)) return rc;
-    auto body = [&]() -> int {
-        HIPCHK(hipMemcpyAsync(h->d_raw.p, img, (size_t)width * height, hipMemcpyHostToDevice, h->stream));
-        if (int r = gf::launch_pyramid_one(h, h->d_raw.p, 0)) return r;
-        gf::min_eig_kernel<<<dim3((width + 31) / 32, (height + 7) / 8, 1), 256, 0, h->stream>>>(h->d_img.p, 2 * h->G.img_bytes, h->G.lv[0], h->d_eig.p, h->eig_stride);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(eig, h->d_eig.p, (size_t)width * height * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        return GF_OK;
-    };
-    int rc = body();
-    gf_tracker_destroy(h);
-    return rc;
+    std::unique_ptr<gf_tracker> own;   // the handle lives for this call
+    if (int rc = tmp_handle(width, height, 4, 30, own)) return rc;
+    gf_tracker* h = own.get();
+    HIPCHK(hipMemcpyAsync(h->d_raw.p, img, (size_t)width * height, hipMemcpyHostToDevice, h->stream));
+    if (int r = gf::launch_pyramid_one(h, h->d_raw.p, 0)) return r;
+    gf::min_eig_kernel<<<dim3((width + 31) / 32, (height + 7) / 8, 1), 256, 0, h->stream>>>(h->d_img.p, 2 * h->G.img_bytes, h->G.lv[0], h->d_eig.p, h->eig_stride);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(eig, h->d_eig.p, (size_t)width * height * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return GF_OK;
 }
 
 int gf_good_features(const uint8_t* img, int width, int height, const uint8_t* mask, int max_corners, int min_dist, float* corners_xy, int* n_out) {
     if (!img || !corners_xy || !n_out || max_corners < 1) return gf::set_err(GF_ERR_INVALID, "bad argument");
-    gf_tracker* h = nullptr;
-    if (int rc = tmp_handle(width, height, max_corners, min_dist, &h)) return rc;
-    auto body = [&]() -> int {
-        const int W = width, H = height;
-        HIPCHK(hipMemcpyAsync(h->d_raw.p, img, (size_t)W * H, hipMemcpyHostToDevice, h->stream));
-        if (int r = gf::launch_pyramid_one(h, h->d_raw.p, 0)) return r;
-        if (mask) HIPCHK(hipMemcpyAsync(h->d_mask.p, mask, (size_t)W * H, hipMemcpyHostToDevice, h->stream));
-        else HIPCHK(hipMemsetAsync(h->d_mask.p, 255, (size_t)W * H, h->stream));
-        h->h_want.p[0] = max_corners;
-        HIPCHK(hipMemcpyAsync(h->d_want.p, h->h_want.p, sizeof(int), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemsetAsync(h->d_maxkey.p, 0, sizeof(unsigned), h->stream));
-        HIPCHK(hipMemsetAsync(h->d_cand_count.p, 0, sizeof(int), h->stream));
-        {
-            gf::DetectArgs D{};
-            D.pyr = h->d_img.p; D.pyr_bytes = h->G.img_bytes; D.frame_of = h->d_cur.p; D.g = h->G.lv[0];   // pyramid 0, written above; max_corners >= 1
-            D.mask = h->d_mask.p; D.mask_seq_stride = h->mask_stride; D.centers = nullptr; D.n_centers = nullptr; D.cap = h->cap;
-            D.maxkey = h->d_maxkey.p; D.cand = h->d_cand.p; D.cand_seq_stride = (size_t)h->cand_cap; D.cand_cap = h->cand_cap; D.cand_count = h->d_cand_count.p;
-            gf::detect_strip_kernel<gf::kDS_R><<<dim3((W + gf::kDS_W - 1) / gf::kDS_W, (H + gf::kDS_R - 1) / gf::kDS_R, 1), 64, 0, h->stream>>>(D, h->disk);
-        }
-        gf::SelectArgs S{};
-        S.cand = h->d_cand.p; S.cand_seq_stride = (size_t)h->cand_cap; S.cand_cap = h->cand_cap; S.cand_count = h->d_cand_count.p; S.maxkey = h->d_maxkey.p; S.want = h->d_want.p;
-        S.w = W; S.h = H; S.min_dist = min_dist; S.out_cap = h->cap; S.sort_cap = h->sort_cap; S.out_pts = h->d_out_pts.p; S.out_depth = h->d_out_depth.p; S.out_n = h->d_out_n.p;
-        gf::select_corners_kernel<<<dim3(1), 1024, h->select_lds, h->stream>>>(S);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(h->h_out_n.p, h->d_out_n.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(h->h_out_pts.p, h->d_out_pts.p, (size_t)h->cap * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        *n_out = h->h_out_n.p[0];
-        for (int i = 0; i < *n_out; i++) { corners_xy[2 * i] = h->h_out_pts.p[i].x; corners_xy[2 * i + 1] = h->h_out_pts.p[i].y; }
-        return GF_OK;
-    };
-    int rc = body();
-    gf_tracker_destroy(h);
-    return rc;
+    std::unique_ptr<gf_tracker> own;   // the handle lives for this call
+    if (int rc = tmp_handle(width, height, max_corners, min_dist, own)) return rc;
+    gf_tracker* h = own.get();
+    const int W = width, H = height;
+    HIPCHK(hipMemcpyAsync(h->d_raw.p, img, (size_t)W * H, hipMemcpyHostToDevice, h->stream));
+    if (int r = gf::launch_pyramid_one(h, h->d_raw.p, 0)) return r;
+    if (mask) HIPCHK(hipMemcpyAsync(h->d_mask.p, mask, (size_t)W * H, hipMemcpyHostToDevice, h->stream));
+    else HIPCHK(hipMemsetAsync(h->d_mask.p, 255, (size_t)W * H, h->stream));
+    h->h_want.p[0] = max_corners;
+    HIPCHK(hipMemcpyAsync(h->d_want.p, h->h_want.p, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_maxkey.p, 0, sizeof(unsigned), h->stream));
+    HIPCHK(hipMemsetAsync(h->d_cand_count.p, 0, sizeof(int), h->stream));
+    {
+        gf::DetectArgs D{};
+        D.pyr = h->d_img.p; D.pyr_bytes = h->G.img_bytes; D.frame_of = h->d_cur.p; D.g = h->G.lv[0];   // pyramid 0, written above; max_corners >= 1
+        D.mask = h->d_mask.p; D.mask_seq_stride = h->mask_stride; D.centers = nullptr; D.n_centers = nullptr; D.cap = h->cap;
+        D.maxkey = h->d_maxkey.p; D.cand = h->d_cand.p; D.cand_seq_stride = (size_t)h->cand_cap; D.cand_cap = h->cand_cap; D.cand_count = h->d_cand_count.p;
+        gf::detect_strip_kernel<gf::kDS_R><<<dim3((W + gf::kDS_W - 1) / gf::kDS_W, (H + gf::kDS_R - 1) / gf::kDS_R, 1), 64, 0, h->stream>>>(D, h->disk);
+    }
+    gf::SelectArgs S{};
+    S.cand = h->d_cand.p; S.cand_seq_stride = (size_t)h->cand_cap; S.cand_cap = h->cand_cap; S.cand_count = h->d_cand_count.p; S.maxkey = h->d_maxkey.p; S.want = h->d_want.p;
+    S.w = W; S.h = H; S.min_dist = min_dist; S.out_cap = h->cap; S.sort_cap = h->sort_cap; S.out_pts = h->d_out_pts.p; S.out_depth = h->d_out_depth.p; S.out_n = h->d_out_n.p;
+    gf::select_corners_kernel<<<dim3(1), 1024, h->select_lds, h->stream>>>(S);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h->h_out_n.p, h->d_out_n.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->h_out_pts.p, h->d_out_pts.p, (size_t)h->cap * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *n_out = h->h_out_n.p[0];
+    for (int i = 0; i < *n_out; i++) { corners_xy[2 * i] = h->h_out_pts.p[i].x; corners_xy[2 * i + 1] = h->h_out_pts.p[i].y; }
+    return GF_OK;
 }
 
 
@@ -1113,11 +1043,11 @@ __global__ void __launch_bounds__(256) calib_tile_kernel(const uint8_t* __restri
 }  // namespace gf
 int gf_calib_fetch(int mode, size_t buffer_bytes, double* requested_bytes, double* lines64, double* ms) {
     if (mode < 0 || mode > 2 || buffer_bytes < (1u << 20)) return gf::set_err(GF_ERR_INVALID, "bad argument");
-    uint8_t* buf = nullptr; unsigned* sink = nullptr;
-    if (hipMalloc((void**)&buf, buffer_bytes) != hipSuccess) return gf::set_err(GF_ERR_HIP, "hipMalloc failed");
-    if (hipMalloc((void**)&sink, 64) != hipSuccess) { (void)hipFree(buf); return gf::set_err(GF_ERR_HIP, "hipMalloc failed"); }
+    gf::DevBuf<uint8_t> dbuf; gf::DevBuf<unsigned> dsink;
+    HIPCHK(dbuf.fit(buffer_bytes)); HIPCHK(dsink.fit(16));
+    uint8_t* buf = dbuf.p; unsigned* sink = dsink.p;
     (void)hipMemset(buf, 1, buffer_bytes); (void)hipMemset(sink, 0, 64);
-    hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    gf::Event e0, e1; HIPCHK(hipEventCreate(&e0.e)); HIPCHK(hipEventCreate(&e1.e));
     (void)hipDeviceSynchronize();
     (void)hipEventRecord(e0, 0);
     if (mode == 0) {
@@ -1136,7 +1066,6 @@ int gf_calib_fetch(int mode, size_t buffer_bytes, double* requested_bytes, doubl
     const hipError_t err = hipDeviceSynchronize();
     float t = 0; (void)hipEventElapsedTime(&t, e0, e1);
     if (ms) *ms = t;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(buf); (void)hipFree(sink);
     if (err != hipSuccess) return gf::set_err(GF_ERR_HIP, "calibration kernel failed: %s", hipGetErrorString(err));
     return GF_OK;
 }

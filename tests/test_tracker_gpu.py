@@ -488,3 +488,24 @@ def test_per_table_copies_match_the_copy_lists_and_the_oracle(gf, oracle, monkey
                 pre.prefetchHost(host_g[k + 1].data_ptr(), host_d.data_ptr())
             check(k, pre.trackPrefetched([0.0666 * k] * B))
         host.close(); dev.close(); pre.close()
+
+
+def _thread_count():
+    with open("/proc/self/status") as f:
+        return int(next(line for line in f if line.startswith("Threads:")).split()[1])
+
+
+def test_a_refused_create_leaves_no_threads_behind(gf, monkeypatch):
+    """gf_tracker_create starts the handle's host pool before it knows whether the selection grid fits LDS.  320 x 256 with min_dist = 1 is the smallest frame it
+    refuses ("too small for the selection grid": 320 * 256 cells of two bytes are the 160 KB of a CU's LDS by themselves); with batch = 8 and GF_HOST_THREADS=4 the pool
+    has three threads by then.  A refused create must take them down again: thirty refusals leave the process with the threads it had after the first."""
+    monkeypatch.setenv("GF_HOST_THREADS", "4")
+    cfg = gf.default_cfg(width=320, height=256, batch=8, min_dist=1)
+    counts = []
+    for _ in range(30):
+        with pytest.raises(gf.GfError, match="too small for the selection grid"):
+            gf.FeatureTracker(cfg)
+        counts.append(_thread_count())
+    print("threads after each refused create:", counts)
+    assert counts[-1] == counts[0], counts
+
