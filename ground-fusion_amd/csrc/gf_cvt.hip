@@ -1,0 +1,76 @@
+// gf_cvt.hip — cv_bridge::toCvCopy(img_msg, MONO8) on batches of u8 frames on the device (getImageFromMsg, rosNodeTest.cpp:238-254: the step of the reference's
+// node ahead of CLAHE and trackImage).  Kernels: gf_cvt_kernels.hpp; arithmetic and channel layouts: gf_pixfmt.hpp, shared with the host decoder.  Used by the
+// tracker (gf_tracker_cfg.pixel_format) and exported as its own C-ABI.
+#include <hip/hip_runtime.h>
+#include <climits>
+
+#include "../../include/groundfusion_hip.h"
+#include "gf_cvt_kernels.hpp"
+#include "gf_hip_own.hpp"
+
+namespace gf {
+
+// format, sizes and pitch of a conversion, or GF_ERR_INVALID
+static int cvt_check(size_t src_pitch, int format, int batch, int w, int h) {
+    if (!gfpix::valid(format)) return set_err(GF_ERR_INVALID, "cvt_gray: unknown pixel format %d (GF_PIX_MONO8 .. GF_PIX_BGRA8)", format);
+    if (batch < 1 || w < 1 || h < 1) return set_err(GF_ERR_INVALID, "cvt_gray: %d frames of %dx%d (all must be >= 1)", batch, w, h);
+    if ((long long)w * h > INT_MAX) return set_err(GF_ERR_INVALID, "cvt_gray: %dx%d frames have more than 2^31 - 1 pixels", w, h);
+    if (src_pitch < (size_t)w * gfpix::channels(format)) return set_err(GF_ERR_INVALID, "cvt_gray: a pitch of %zu bytes is shorter than a row of %d pixels of %d bytes", src_pitch, w, gfpix::channels(format));
+    return GF_OK;
+}
+
+// bytes from the first the conversion reads to behind the last: the last row ends with its pixels, not with its padding
+static size_t cvt_src_bytes(size_t src_pitch, int format, int batch, int w, int h) { return ((size_t)batch * h - 1) * src_pitch + (size_t)w * gfpix::channels(format); }
+
+template <int CH> static void cvt_launch_ch(const uint8_t* d_src, size_t src_pitch, int red_at, uint8_t* d_dst, int batch, int w, int h, hipStream_t stream) {
+    using namespace gfcvt;
+    const unsigned gy = (unsigned)std::min(batch, 65535);
+    const bool dwords = !((reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst) | src_pitch | (size_t)w) & 3);
+    auto blocks = [&](int per_row) { return (unsigned)(((size_t)per_row * h + kThreads - 1) / kThreads); };
+    if (dwords && !(w & 15)) cvt_gray_vec_kernel<CH, 16><<<dim3(blocks(w / 16), gy), kThreads, 0, stream>>>(d_src, src_pitch, d_dst, batch, w, h, red_at);
+    else if (dwords) cvt_gray_vec_kernel<CH, 4><<<dim3(blocks(w / 4), gy), kThreads, 0, stream>>>(d_src, src_pitch, d_dst, batch, w, h, red_at);
+    else cvt_gray_byte_kernel<CH><<<dim3(blocks(w), gy), kThreads, 0, stream>>>(d_src, src_pitch, d_dst, batch, w, h, red_at);
+}
+
+// `batch` frames of h rows, src_pitch bytes apart, in `format` -> tight h x w u8 frames; the ranges must not overlap (the callers see to it)
+int cvt_launch(const uint8_t* d_src, size_t src_pitch, int format, uint8_t* d_dst, int batch, int w, int h, hipStream_t stream) {
+    if (int rc = cvt_check(src_pitch, format, batch, w, h)) return rc;
+    const int ch = gfpix::channels(format), red_at = gfpix::red_at(format);
+    if (ch == 1) cvt_launch_ch<1>(d_src, src_pitch, red_at, d_dst, batch, w, h, stream);
+    else if (ch == 3) cvt_launch_ch<3>(d_src, src_pitch, red_at, d_dst, batch, w, h, stream);
+    else cvt_launch_ch<4>(d_src, src_pitch, red_at, d_dst, batch, w, h, stream);
+    HIPCHK(hipGetLastError());
+    return GF_OK;
+}
+
+}  // namespace gf
+
+extern "C" {
+
+int gf_cvt_gray_batch_device(const void* d_src, size_t src_pitch, int format, void* d_dst, int batch, int width, int height, void* stream) {
+    if (!d_src || !d_dst) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (int rc = gf::cvt_check(src_pitch, format, batch, width, height)) return rc;
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), s1 = s0 + gf::cvt_src_bytes(src_pitch, format, batch, width, height);
+    const uintptr_t d0 = reinterpret_cast<uintptr_t>(d_dst), d1 = d0 + (size_t)batch * width * height;
+    const bool same_tight_mono = format == GF_PIX_MONO8 && s0 == d0 && src_pitch == (size_t)width;   // every lane writes back what it read
+    if (s0 < d1 && d0 < s1 && !same_tight_mono)
+        return gf::set_err(GF_ERR_INVALID, "cvt_gray: source and destination overlap (the conversion shrinks the frames: a lane would read what another has written)");
+    return gf::cvt_launch(static_cast<const uint8_t*>(d_src), src_pitch, format, static_cast<uint8_t*>(d_dst), batch, width, height, static_cast<hipStream_t>(stream));
+}
+
+int gf_cvt_gray_batch(const uint8_t* src, size_t src_pitch, int format, uint8_t* dst, int batch, int width, int height) {
+    if (!src || !dst) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (int rc = gf::cvt_check(src_pitch, format, batch, width, height)) return rc;
+    const size_t in = gf::cvt_src_bytes(src_pitch, format, batch, width, height), out = (size_t)batch * width * height;
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), d0 = reinterpret_cast<uintptr_t>(dst);
+    if (format != GF_PIX_MONO8 && s0 < d0 + out && d0 < s0 + in) return gf::set_err(GF_ERR_INVALID, "cvt_gray: source and destination overlap");
+    if (int rc = gf::require_device()) return rc;
+    gf::DevBuf<uint8_t> d_in, d_out;
+    HIPCHK(d_in.fit(in)); HIPCHK(d_out.fit(out));
+    HIPCHK(hipMemcpy(d_in.p, src, in, hipMemcpyHostToDevice));
+    if (int rc = gf_cvt_gray_batch_device(d_in.p, src_pitch, format, d_out.p, batch, width, height, nullptr)) return rc;
+    HIPCHK(hipMemcpy(dst, d_out.p, out, hipMemcpyDeviceToHost));
+    return GF_OK;
+}
+
+}  // extern "C"

@@ -211,6 +211,7 @@ int gf_estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* c) {
     t.max_cnt = y.integer("max_cnt"); t.min_dist = y.integer("min_dist"); t.flow_back = y.integer("flow_back");
     t.depth_cam = c->depth;
     t.equalize = y.integer("equalize") != 0;   // EQUALIZE (parameters.cpp:169): CLAHE on every frame before trackImage (rosNodeTest.cpp:256-261)
+    t.pixel_format = GF_PIX_MONO8;             // no key: the reference's node converts every message to MONO8 itself (rosNodeTest.cpp:238-254); a caller with colour frames sets it
     c->with_tracker = 1;
     // cam0_calib, relative to the directory of the config file (parameters.cpp:436-443)
     const std::string cf(config_file);

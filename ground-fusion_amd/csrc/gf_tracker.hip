@@ -33,12 +33,15 @@
 #include "gf_copy_list.hpp"
 #include "gf_host_cpus.hpp"
 #include "gf_hip_own.hpp"
+#include "gf_pixfmt.hpp"
 
 namespace gf {
 
 // gf_clahe.hip: cv::CLAHE::apply on `batch` contiguous frames (gf_tracker_cfg.equalize)
 size_t clahe_lut_bytes(int batch, int tiles_x, int tiles_y);
 int clahe_launch(const uint8_t* d_src, uint8_t* d_dst, uint8_t* d_lut, int batch, int w, int h, double clip_limit, int tiles_x, int tiles_y, hipStream_t stream);
+// gf_cvt.hip: cv_bridge::toCvCopy(msg, MONO8) on `batch` frames, src_pitch bytes from row to row (gf_tracker_cfg.pixel_format)
+int cvt_launch(const uint8_t* d_src, size_t src_pitch, int format, uint8_t* d_dst, int batch, int w, int h, hipStream_t stream);
 constexpr double kClaheClip = 40.0;   // cv::createCLAHE() defaults (rosNodeTest.cpp:258)
 constexpr int kClaheTiles = 8;
 
@@ -156,13 +159,15 @@ struct gf_tracker {
     bool profiling = false;
     // Members are destroyed in reverse order: the pool (last member) is joined before anything its threads could touch goes, the buffers go before the events and streams.
     Stream stream, copy_stream;   // copy_stream, ev_copy: gf_tracker_prefetch_batch (created on first use)
-    Event ev[8];   // ev[7]: end of the equalisation (cfg.equalize)
+    Event ev[9];   // ev[7]: end of the equalisation (cfg.equalize); ev[8]: end of the colour conversion (cfg.pixel_format)
+    int ch = 1;    // bytes per pixel of the frames the handle is given (cfg.pixel_format); d_raw / d_raw2 hold them in that format
     Event ev_copy[2];
     gf_tracker_stats stats{};
     std::vector<SeqState> seq;
     // device
     DevBuf<uint8_t> d_img, d_raw, d_mask, d_status, d_fwd_status, d_seqmask;
     DevBuf<uint8_t> d_eq, d_eq_lut;   // cfg.equalize: the equalised frames the pyramid reads, and the CLAHE tile LUTs
+    DevBuf<uint8_t> d_cvt;            // cfg.pixel_format: the MONO8 frames converted from the caller's colour frames, which equalisation and pyramid read
     DevBuf<int> d_npts, d_cand_count, d_want, d_ncenters, d_out_n;
     // the call's sequence list as the kernels read it (cur_of, gf_lk_kernels.hpp): written into the page-locked h_cur, which the pyramid kernels read over the bus
     // (they are launched before anything is copied), and carried to d_cur for LK by the copy list in front of it
@@ -379,6 +384,13 @@ static int check_list(gf_tracker* h, int count, const int* seq) {
     return GF_OK;
 }
 
+// The row step of host frames on a handle that takes colour: refused before anything is copied.  (A MONO8 handle hands its stride to the copy as it always did.)
+static int check_stride(gf_tracker* h, int stride) {
+    if (h->cfg.pixel_format && (stride < 0 || (size_t)stride < (size_t)h->cfg.width * h->ch))
+        return set_err(GF_ERR_INVALID, "a stride of %d bytes is shorter than a row of %d pixels of %d bytes (gf_tracker_cfg.pixel_format %d)", stride, h->cfg.width, h->ch, h->cfg.pixel_format);
+    return GF_OK;
+}
+
 // One frame for each of the `count` listed sequences (seq: checked by check_list); sequences that are not listed keep their whole state.  Everything the caller hands
 // in or gets back (t, the frames behind d_gray / d_depth / hdep, out, n_out) and every hand-over table of the handle is indexed by the position i in the list, so the
 // work and the bytes of a call follow `count`; only h->seq[] and the pyramid pairs are indexed by the sequence seq[i].
@@ -427,6 +439,11 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
     if (!over_bus) HIPCHK(hipMemcpyAsync(h->d_cur.p, h->h_cur.p, (size_t)N * sizeof(int), hipMemcpyHostToDevice, h->stream));
     const int* cur_of = over_bus ? h->h_cur.hd : h->d_cur.p;
     if (prof) HIPCHK(hipEventRecord(h->ev[0], h->stream));
+    if (h->cfg.pixel_format) {   // rosNodeTest.cpp:238-254: toCvCopy(msg, MONO8) ahead of CLAHE and trackImage; d_gray holds tight colour frames by list position, never written
+        if (int rc = cvt_launch(d_gray, (size_t)W * h->ch, h->cfg.pixel_format, h->d_cvt.p, N, W, H, h->stream)) return rc;
+        d_gray = h->d_cvt.p;
+        if (prof) HIPCHK(hipEventRecord(h->ev[8], h->stream));
+    }
     if (h->cfg.equalize) {   // rosNodeTest.cpp:256-261: CLAHE on the gray frame before trackImage, into the handle's buffer (the caller's frames stay as they are); frames and LUTs by list position
         if (int rc = clahe_launch(d_gray, h->d_eq.p, h->d_eq_lut.p, N, W, H, kClaheClip, kClaheTiles, kClaheTiles, h->stream)) return rc;
         d_gray = h->d_eq.p;
@@ -597,10 +614,10 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
     lap(h->stats.ms_wait_detect);
     if (prof) {
         float ms = 0;
-        if (h->cfg.equalize) {
-            HIPCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[7])); h->stats.ms_equalize += ms;
-            HIPCHK(hipEventElapsedTime(&ms, h->ev[7], h->ev[1])); h->stats.ms_pyramid += ms;
-        } else { HIPCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1])); h->stats.ms_pyramid += ms; }
+        hipEvent_t from = h->ev[0];   // the stages ahead of the pyramid, each from where the one before it ended
+        if (h->cfg.pixel_format) { HIPCHK(hipEventElapsedTime(&ms, from, h->ev[8])); h->stats.ms_convert += ms; from = h->ev[8]; }
+        if (h->cfg.equalize) { HIPCHK(hipEventElapsedTime(&ms, from, h->ev[7])); h->stats.ms_equalize += ms; from = h->ev[7]; }
+        HIPCHK(hipEventElapsedTime(&ms, from, h->ev[1])); h->stats.ms_pyramid += ms;
         if (lk_timed) { HIPCHK(hipEventElapsedTime(&ms, h->ev[2], h->ev[3])); h->stats.ms_lk += ms; }
         HIPCHK(hipEventElapsedTime(&ms, h->ev[4], h->ev[5])); h->stats.ms_detect += ms;
         HIPCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[5])); h->stats.ms_total_gpu += ms;
@@ -682,9 +699,11 @@ int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out) {
     if (cfg->width < 32 || cfg->height < 32 || cfg->width % 4 || cfg->batch < 1 || cfg->max_cnt < 1 || cfg->min_dist < 0 || cfg->min_dist > gf::kMaxRadius)
         return gf::set_err(GF_ERR_INVALID, "unsupported tracker configuration (width %% 4 == 0, width/height >= 32, 0 <= min_dist <= %d)", gf::kMaxRadius);
     if (cfg->equalize != 0 && cfg->equalize != 1) return gf::set_err(GF_ERR_INVALID, "gf_tracker_cfg.equalize must be 0 or 1, got %d", cfg->equalize);
+    if (!gfpix::valid(cfg->pixel_format)) return gf::set_err(GF_ERR_INVALID, "gf_tracker_cfg.pixel_format must be one of GF_PIX_MONO8 (0) .. GF_PIX_BGRA8 (4), got %d", cfg->pixel_format);
     if (int rc = gf::require_device()) return rc;
     std::unique_ptr<gf_tracker> h(new gf_tracker());
     h->cfg = *cfg;
+    h->ch = gfpix::channels(cfg->pixel_format);
     h->B = cfg->batch;
     h->cap = (cfg->max_cnt + 3) & ~3;
     gf::build_geom(cfg->width, cfg->height, h->G);
@@ -723,7 +742,8 @@ int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out) {
     for (auto& e : h->ev) HIPCHK(hipEventCreate(&e.e));
     // The allocations as explicit statements, in this order: a buffer's place in the sequence decides which memory it gets.
     HIPCHK(h->d_img.alloc((size_t)B * 2 * h->G.img_bytes));
-    HIPCHK(h->d_raw.alloc((size_t)B * W * H));
+    HIPCHK(h->d_raw.alloc((size_t)B * W * H * h->ch));
+    if (cfg->pixel_format) HIPCHK(h->d_cvt.alloc((size_t)B * W * H));
     if (cfg->equalize) { HIPCHK(h->d_eq.alloc((size_t)B * W * H)); HIPCHK(h->d_eq_lut.alloc(gf::clahe_lut_bytes(B, gf::kClaheTiles, gf::kClaheTiles))); }
     // (no device copy of the depth images: the host entry points sample them on the host, the device entry point reads the caller's device pointer)
     HIPCHK(h->d_mask.alloc(h->mask_stride));  // explicit masks exist only in the gf_good_features building block
@@ -765,12 +785,14 @@ int gf_tracker_track_some(gf_tracker* h, int count, const int* seq, const double
     if (count == 0) return GF_OK;
     if (!t || !gray || !out || !n_out) return gf::set_err(GF_ERR_INVALID, "null argument");
     const int W = h->cfg.width, H = h->cfg.height;
+    const size_t row = (size_t)W * h->ch;   // bytes of a row of the handle's pixel format
+    if (int rc = gf::check_stride(h, stride)) return rc;
     bool have_depth = depth != nullptr;
     for (int i = 0; i < count; i++) {   // refuse before the first copy
         if (!gray[i]) return gf::set_err(GF_ERR_INVALID, "null image for sequence %d", seq[i]);
         if (have_depth && !depth[i]) have_depth = false;
     }
-    for (int i = 0; i < count; i++) HIPCHK(hipMemcpy2DAsync(h->d_raw.p + (size_t)i * W * H, W, gray[i], stride, W, H, hipMemcpyHostToDevice, h->stream));
+    for (int i = 0; i < count; i++) HIPCHK(hipMemcpy2DAsync(h->d_raw.p + (size_t)i * row * H, row, gray[i], stride, row, H, hipMemcpyHostToDevice, h->stream));
     // the depth image stays where it is: its <= max_cnt samples are taken on the host (track_core)
     return gf::track_core(h, count, seq, t, h->d_raw.p, nullptr, out, cap, n_out, have_depth ? depth : nullptr, dstride);
 }
@@ -784,6 +806,8 @@ int gf_tracker_prefetch_some(gf_tracker* h, int count, const int* seq, const uin
     if (int rc = gf::check_list(h, count, seq)) return rc;
     if (count > 0 && !gray) return gf::set_err(GF_ERR_INVALID, "null argument");
     const int W = h->cfg.width, H = h->cfg.height;
+    const size_t row = (size_t)W * h->ch;   // bytes of a row of the handle's pixel format
+    if (int rc = gf::check_stride(h, stride)) return rc;
     bool have_depth = depth != nullptr;
     for (int i = 0; i < count; i++) {
         if (!gray[i]) return gf::set_err(GF_ERR_INVALID, "null image for sequence %d", seq[i]);
@@ -793,15 +817,15 @@ int gf_tracker_prefetch_some(gf_tracker* h, int count, const int* seq, const uin
     if (!h->copy_stream) {
         HIPCHK(hipStreamCreateWithFlags(&h->copy_stream.s, hipStreamNonBlocking));
         for (auto& e : h->ev_copy) HIPCHK(hipEventCreateWithFlags(&e.e, hipEventDisableTiming));
-        HIPCHK(h->d_raw2.alloc((size_t)h->B * W * H));
+        HIPCHK(h->d_raw2.alloc((size_t)h->B * row * H));
     }
     const int slot = (h->pf_head + h->pf_count) & 1;      // a pair no frame in flight uses: track calls return when their frame is done
     uint8_t* raw = slot ? h->d_raw2.p : h->d_raw.p;
     // images that sit back to back in one allocation (a pinned ring of frames) go as ONE copy per plane: 256 separate 2-D copies cost more host time than the bus needs
-    bool contig = stride == W;
-    for (int i = 1; i < count && contig; i++) contig = gray[i] == gray[0] + (size_t)i * W * H;
-    if (contig && count > 0) HIPCHK(hipMemcpyAsync(raw, gray[0], (size_t)count * W * H, hipMemcpyHostToDevice, h->copy_stream));
-    else for (int i = 0; i < count; i++) HIPCHK(hipMemcpy2DAsync(raw + (size_t)i * W * H, W, gray[i], stride, W, H, hipMemcpyHostToDevice, h->copy_stream));
+    bool contig = (size_t)stride == row;
+    for (int i = 1; i < count && contig; i++) contig = gray[i] == gray[0] + (size_t)i * row * H;
+    if (contig && count > 0) HIPCHK(hipMemcpyAsync(raw, gray[0], (size_t)count * row * H, hipMemcpyHostToDevice, h->copy_stream));
+    else for (int i = 0; i < count; i++) HIPCHK(hipMemcpy2DAsync(raw + (size_t)i * row * H, row, gray[i], stride, row, H, hipMemcpyHostToDevice, h->copy_stream));
     HIPCHK(hipEventRecord(h->ev_copy[slot], h->copy_stream));
     // the depth images do not travel: gf_tracker_track_prefetched samples them on the host (they must stay valid until it returns, like the gray images until the copy is done)
     h->pf_depth[slot] = have_depth; if (have_depth) h->pf_hdepth[slot].assign(depth, depth + count); else h->pf_hdepth[slot].clear();

@@ -18,7 +18,13 @@ class TrackerCfg(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("batch", C.c_int), ("max_cnt", C.c_int), ("min_dist", C.c_int),
                 ("flow_back", C.c_int), ("depth_cam", C.c_int),
                 ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
-                ("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double), ("equalize", C.c_int)]
+                ("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double), ("equalize", C.c_int), ("pixel_format", C.c_int)]
+
+
+# GF_PIX_*: the formats of the frames a tracker handle takes and of cvt_gray (rosNodeTest.cpp:238-254), and their bytes per pixel
+PIX_MONO8, PIX_RGB8, PIX_BGR8, PIX_RGBA8, PIX_BGRA8 = range(5)
+PIX_CHANNELS = (1, 3, 3, 4, 4)
+PIX_OF_ENCODING = {"mono8": PIX_MONO8, "8UC1": PIX_MONO8, "rgb8": PIX_RGB8, "bgr8": PIX_BGR8, "rgba8": PIX_RGBA8, "bgra8": PIX_BGRA8}
 
 
 class FeatureObs(C.Structure):
@@ -32,7 +38,8 @@ class TrackerStats(C.Structure):
                 ("lk_level_passes", C.c_longlong), ("lk_iterations", C.c_longlong), ("tracked_features", C.c_longlong),
                 ("output_features", C.c_longlong), ("select_streamed", C.c_longlong), ("select_global_sort", C.c_longlong),
                 ("ms_equalize", C.c_double), ("pyr_head", C.c_longlong), ("pyr_level0_vec16", C.c_longlong), ("pyr_level0_dword", C.c_longlong),
-                ("pyr_down_tail", C.c_longlong), ("pyr_down_pad4", C.c_longlong), ("pyr_down_bytes", C.c_longlong), ("sequence_frames", C.c_longlong)]
+                ("pyr_down_tail", C.c_longlong), ("pyr_down_pad4", C.c_longlong), ("pyr_down_bytes", C.c_longlong), ("ms_convert", C.c_double),
+                ("sequence_frames", C.c_longlong)]
 
 
 OBS_DTYPE = np.dtype([("id", np.int32), ("camera_id", np.int32), ("v", np.float64, (8,))])
@@ -41,7 +48,7 @@ assert OBS_DTYPE.itemsize == C.sizeof(FeatureObs)
 EXPORTS = ["gf_last_error", "gf_device_count", "gf_set_device", "gf_tracker_create", "gf_tracker_destroy", "gf_tracker_track",
            "gf_tracker_track_batch", "gf_tracker_track_batch_device", "gf_tracker_track_some", "gf_tracker_track_some_device", "gf_tracker_prefetch_some", "gf_tracker_set_prediction", "gf_tracker_remove_outliers",
            "gf_tracker_get_state", "gf_tracker_set_profiling", "gf_tracker_get_stats", "gf_tracker_reset_stats", "gf_lk_track",
-           "gf_good_features", "gf_min_eigen_val", "gf_pyramid_level", "gf_clahe_batch", "gf_clahe_batch_device"]
+           "gf_good_features", "gf_min_eigen_val", "gf_pyramid_level", "gf_clahe_batch", "gf_clahe_batch_device", "gf_cvt_gray_batch", "gf_cvt_gray_batch_device"]
 
 
 def lib():
@@ -76,9 +83,9 @@ def device_count():
     return n.value
 
 
-def default_cfg(width=640, height=480, batch=1, max_cnt=150, min_dist=30, flow_back=1, depth_cam=1, equalize=0):
+def default_cfg(width=640, height=480, batch=1, max_cnt=150, min_dist=30, flow_back=1, depth_cam=1, equalize=0, pixel_format=0):
     return TrackerCfg(width, height, batch, max_cnt, min_dist, flow_back, depth_cam, 603.95556640625, 603.1257934570312,
-                      324.0858154296875, 232.72303771972656, 0.0, 0.0, 0.0, 0.0, equalize)
+                      324.0858154296875, 232.72303771972656, 0.0, 0.0, 0.0, 0.0, equalize, pixel_format)
 
 
 class FeatureTracker:
@@ -90,6 +97,8 @@ class FeatureTracker:
         self.h = C.c_void_p()
         _chk(lib().gf_tracker_create(C.byref(self.cfg), C.byref(self.h)))
         self.cap = 4 * ((self.cfg.max_cnt + 3) // 4)
+        self.channels = PIX_CHANNELS[self.cfg.pixel_format]   # a colour handle takes [height, width, channels] u8 frames wherever a MONO8 handle takes [height, width]
+        self.row_bytes = self.cfg.width * self.channels
 
     def close(self):
         if getattr(self, "h", None):
@@ -132,7 +141,7 @@ class FeatureTracker:
             dp = None
         out = np.zeros((N, self.cap), OBS_DTYPE)
         n = np.zeros(N, np.int32)
-        _chk(lib().gf_tracker_track_some(self.h, N, _p(seqs, C.c_int), _p(ts, C.c_double), gp, stride or self.cfg.width, dp, dstride or self.cfg.width,
+        _chk(lib().gf_tracker_track_some(self.h, N, _p(seqs, C.c_int), _p(ts, C.c_double), gp, stride or self.row_bytes, dp, dstride or self.cfg.width,
                                          out.ctypes.data_as(C.POINTER(FeatureObs)), self.cap, _p(n, C.c_int)))
         return self._unpack(out, n)
 
@@ -158,6 +167,9 @@ class FeatureTracker:
 
     def _pitched(self, a, dtype, pitch):
         """a height x width image whose rows lie `pitch` elements apart (a view of a wider array, e.g. a cropped frame): passed as it is, not copied"""
+        if dtype == np.uint8 and self.channels > 1:   # colour rows: [height, width, channels], `pitch` bytes from row to row
+            assert a.dtype == dtype and a.shape == (self.cfg.height, self.cfg.width, self.channels) and a.strides == (pitch, self.channels, 1), (a.shape, a.strides, pitch)
+            return a
         assert a.dtype == dtype and a.shape == (self.cfg.height, self.cfg.width) and a.strides == (pitch * a.itemsize, a.itemsize), (a.shape, a.strides, pitch)
         return a
 
@@ -174,7 +186,7 @@ class FeatureTracker:
             dp = None
         out = np.zeros((B, self.cap), OBS_DTYPE)
         n = np.zeros(B, np.int32)
-        _chk(lib().gf_tracker_track_batch(self.h, _p(ts, C.c_double), gp, stride or self.cfg.width, dp, dstride or self.cfg.width,
+        _chk(lib().gf_tracker_track_batch(self.h, _p(ts, C.c_double), gp, stride or self.row_bytes, dp, dstride or self.cfg.width,
                                           out.ctypes.data_as(C.POINTER(FeatureObs)), self.cap, _p(n, C.c_int)))
         return self._unpack(out, n)
 
@@ -201,7 +213,7 @@ class FeatureTracker:
         seqs: gf_tracker_prefetch_some -- the frames (len(seqs) of them, block or list alike) belong to the listed sequences, and the matching trackPrefetched
         advances those alone, its ts and results in the same order"""
         B, H = self.cfg.batch, self.cfg.height
-        stride, dstride = stride or self.cfg.width, dstride or self.cfg.width
+        stride, dstride = stride or self.row_bytes, dstride or self.cfg.width
         if seqs is not None:
             seqs, B = self._seqs(seqs)
         self._pf_n = getattr(self, "_pf_n", []) + [B]
@@ -277,6 +289,40 @@ def clahe_device(d_src, d_dst, batch, width, height, clip_limit=40.0, tiles=(8, 
     """gf_clahe_batch_device on integer device addresses (e.g. torch tensor .data_ptr()); asynchronous on `stream` (an integer hipStream_t, 0 = null stream)"""
     _chk(lib().gf_clahe_batch_device(C.c_void_p(d_src), C.c_void_p(d_dst), batch, width, height, C.c_double(clip_limit), int(tiles[0]), int(tiles[1]),
                                      C.c_void_p(stream) if stream else None))
+
+
+def _cvt_rows(frames, pixel_format):
+    """[h, w(, ch)] or [batch, h, w(, ch)] u8 frames of one format as (array, batch, h, w, row pitch in bytes): rows may be padded (a view of a wider array), the
+    frames of a batch lie h rows apart"""
+    if not 0 <= pixel_format < len(PIX_CHANNELS):
+        return np.ascontiguousarray(frames, np.uint8), 1, 1, 1, 1   # the library's to refuse
+    ch = PIX_CHANNELS[pixel_format]
+    a = np.asarray(frames)
+    nd = 2 if ch == 1 else 3
+    if a.dtype != np.uint8 or a.ndim not in (nd, nd + 1) or (ch > 1 and a.shape[-1] != ch):
+        raise ValueError("cvt_gray: frames must be u8 [h, w%s] or [batch, h, w%s]" % ((", %d" % ch,) * 2 if ch > 1 else ("", "")))
+    if a.ndim == nd:
+        a = a[None]
+    h, w = a.shape[1], a.shape[2]
+    inner = (ch, 1) if ch > 1 else (1,)
+    if a.strides[2:] != inner or a.strides[0] != h * a.strides[1] or a.strides[1] < w * ch:
+        a = np.ascontiguousarray(a)
+    return a, a.shape[0], h, w, a.strides[1]
+
+
+def cvt_gray(frames, pixel_format):
+    """cv_bridge::toCvCopy(msg, MONO8) (rosNodeTest.cpp:238-254) on host frames of format PIX_* on the device (gf_cvt_gray_batch): [h, w, ch] or [batch, h, w, ch]
+    u8 ([h, w] / [batch, h, w] for PIX_MONO8); a view with padded rows is read through its pitch.  Returns new tight [h, w] / [batch, h, w] frames."""
+    a, b, h, w, pitch = _cvt_rows(frames, pixel_format)
+    out = np.empty((b, h, w), np.uint8)
+    _chk(lib().gf_cvt_gray_batch(C.c_void_p(a.ctypes.data), C.c_size_t(pitch), int(pixel_format), _p(out, C.c_uint8), b, w, h))
+    return out[0] if np.asarray(frames).ndim == (2 if PIX_CHANNELS[pixel_format] == 1 else 3) else out
+
+
+def cvt_gray_device(d_src, src_pitch, pixel_format, d_dst, batch, width, height, stream=0):
+    """gf_cvt_gray_batch_device on integer device addresses (e.g. torch tensor .data_ptr()); asynchronous on `stream` (an integer hipStream_t, 0 = null stream)"""
+    _chk(lib().gf_cvt_gray_batch_device(C.c_void_p(d_src), C.c_size_t(src_pitch), int(pixel_format), C.c_void_p(d_dst), batch, width, height,
+                                        C.c_void_p(stream) if stream else None))
 
 
 def lk_track(prev, nxt, prev_pts, next_pts=None, max_level=3):
@@ -775,7 +821,8 @@ class SlidingWindowEstimator:
             dp, ds = _p(depth, C.c_uint16), depth.shape[1]
         else:
             dp, ds = None, 0
-        _chk(lib().gf_estimator_input_image(self.h, C.c_double(t), _p(img, C.c_uint8), img.shape[1], dp, ds, out, cap, C.byref(n)))
+        # (a colour-configured estimator, cfg.tracker.pixel_format, takes [h, w, channels] frames: the stride is bytes per row)
+        _chk(lib().gf_estimator_input_image(self.h, C.c_double(t), _p(img, C.c_uint8), img.strides[0], dp, ds, out, cap, C.byref(n)))
         return {out[k].id: np.array(out[k].v[:]) for k in range(n.value)}
 
     def state(self):

@@ -133,15 +133,17 @@ class Estimator {
         check(gf_estimator_input_feature(h_, t, obs.data(), (int)obs.size()));
         refresh();
     }
-    // needs cfg.with_tracker = 1 and cfg.tracker filled before setParameter()
+    // needs cfg.with_tracker = 1 and cfg.tracker filled before setParameter(); a colour image (GrayImage::pixel_format, its stride the row step in bytes) needs
+    // cfg.tracker.pixel_format set to its format: the tracker then converts on the device what getImageFromMsg converts on the host (rosNodeTest.cpp:238-254)
     void inputImage(double t, const GrayImage& _img, const DepthImage& _img1 = DepthImage()) {
         need();
+        if (_img.pixel_format != cfg.tracker.pixel_format) throw std::runtime_error("inputImage: the image's pixel format differs from cfg.tracker.pixel_format");
         check(gf_estimator_input_image(h_, t, _img.data, _img.stride, _img1.empty() ? nullptr : _img1.data, _img1.stride, nullptr, 0, nullptr));
         refresh();
     }
 #ifdef GF_WITH_OPENCV
-    void inputImage(double t, const cv::Mat& _img, const cv::Mat& _img1 = cv::Mat()) {
-        GrayImage g{_img.ptr<uint8_t>(), _img.rows, _img.cols, (int)_img.step};
+    void inputImage(double t, const cv::Mat& _img, const cv::Mat& _img1 = cv::Mat(), bool rgb_order = false) {   // rgb_order: FeatureTracker::viewOf
+        const GrayImage g = FeatureTracker::viewOf(_img, rgb_order);
         DepthImage d;
         if (!_img1.empty()) d = DepthImage{_img1.ptr<uint16_t>(), _img1.rows, _img1.cols, (int)(_img1.step / 2)};
         inputImage(t, g, d);

@@ -3,7 +3,7 @@
 //
 // Same member names, argument meaning and return type as the reference, so that Estimator::inputImage
 // (estimator.cpp:213-240) and the ROS plumbing compile against it unchanged once cv::Mat / Eigen are present:
-//   * build with -DGF_WITH_OPENCV to take cv::Mat arguments directly (CV_8UC1 image, CV_16UC1 depth);
+//   * build with -DGF_WITH_OPENCV to take cv::Mat arguments directly (CV_8UC1 image, or CV_8UC3 / CV_8UC4 with a stated channel order; CV_16UC1 depth);
 //   * build with -DGF_WITH_EIGEN to return Eigen::Matrix<double,8,1> observations;
 //   * without them (this container has neither) the light gf::Image view and std::array<double,8> stand in.
 // Errors: the reference logs and carries on; here a failing C-ABI call throws std::runtime_error with gf_last_error().
@@ -30,6 +30,9 @@ namespace gf {
 
 template <class T> struct ImageView {  // stands in for cv::Mat when OpenCV is absent
     const T* data = nullptr; int rows = 0, cols = 0, stride = 0;  // stride in elements
+    // GF_PIX_* of a u8 image (rosNodeTest.cpp:238-254, what getImageFromMsg accepts): a colour image holds cols x 3 or 4 bytes per row, `stride` is its row step
+    // in bytes, and the tracker converts it to MONO8 on the device as the node's cv_bridge::toCvCopy(msg, MONO8) does on the host
+    int pixel_format = GF_PIX_MONO8;
     bool empty() const { return data == nullptr; }
 };
 typedef ImageView<uint8_t> GrayImage;
@@ -89,7 +92,9 @@ class FeatureTracker {
     }
 
     FeatureFrame trackImage(double _cur_time, const GrayImage& _img, const DepthImage& _img1 = DepthImage()) {
-        if (!h_) create(_img.cols, _img.rows);
+        if (!h_) { pixel_format_ = _img.pixel_format; create(_img.cols, _img.rows); }
+        // one handle has one format (a camera does not change its encoding): the first frame decides, as it decides the size
+        if (_img.pixel_format != pixel_format_) throw std::runtime_error("trackImage: the image's pixel format differs from the first frame's");
         std::vector<gf_feature_obs> out((size_t)((MAX_CNT + 3) & ~3));
         int n = 0;
         check(gf_tracker_track(h_, 0, _cur_time, _img.data, _img.stride, _img1.empty() ? nullptr : _img1.data, _img1.stride, out.data(), (int)out.size(), &n));
@@ -103,8 +108,16 @@ class FeatureTracker {
         return featureFrame;
     }
 #ifdef GF_WITH_OPENCV
-    FeatureFrame trackImage(double _cur_time, const cv::Mat& _img, const cv::Mat& _img1 = cv::Mat()) {
-        GrayImage g{_img.ptr<uint8_t>(), _img.rows, _img.cols, (int)_img.step};
+    // rgb_order: the channel order of a CV_8UC3 / CV_8UC4 image -- false: OpenCV's own B, G, R(, A) (bgr8 / bgra8), true: R, G, B(, A) (rgb8 / rgba8, what a RealSense
+    // colour topic carries and cv_bridge::toCvShare hands on unconverted).  A cv::Mat does not record it, so the caller states it.
+    static GrayImage viewOf(const cv::Mat& m, bool rgb_order = false) {
+        if (m.depth() != CV_8U || (m.channels() != 1 && m.channels() != 3 && m.channels() != 4)) throw std::runtime_error("trackImage: the image must be CV_8UC1, CV_8UC3 or CV_8UC4");
+        GrayImage g{m.ptr<uint8_t>(), m.rows, m.cols, (int)m.step};
+        g.pixel_format = m.channels() == 1 ? GF_PIX_MONO8 : m.channels() == 3 ? (rgb_order ? GF_PIX_RGB8 : GF_PIX_BGR8) : (rgb_order ? GF_PIX_RGBA8 : GF_PIX_BGRA8);
+        return g;
+    }
+    FeatureFrame trackImage(double _cur_time, const cv::Mat& _img, const cv::Mat& _img1 = cv::Mat(), bool rgb_order = false) {
+        const GrayImage g = viewOf(_img, rgb_order);
         DepthImage d;
         if (!_img1.empty()) d = DepthImage{_img1.ptr<uint16_t>(), _img1.rows, _img1.cols, (int)(_img1.step / 2)};
         return trackImage(_cur_time, g, d);
@@ -125,12 +138,14 @@ class FeatureTracker {
     gf_tracker* h_ = nullptr;
     double fx_ = 1, fy_ = 1, cx_ = 0, cy_ = 0, k1_ = 0, k2_ = 0, p1_ = 0, p2_ = 0;
     bool equalize_ = false;
+    int pixel_format_ = GF_PIX_MONO8;
     static void check(int rc) { if (rc != GF_OK) throw std::runtime_error(std::string("groundfusion_hip: ") + gf_last_error()); }
     void create(int w, int h) {
         gf_tracker_cfg c{};
         c.width = col ? col : w; c.height = row ? row : h; c.batch = 1; c.max_cnt = MAX_CNT; c.min_dist = MIN_DIST; c.flow_back = FLOW_BACK; c.depth_cam = depth_cam ? 1 : 0;
         c.fx = fx_; c.fy = fy_; c.cx = cx_; c.cy = cy_; c.k1 = k1_; c.k2 = k2_; c.p1 = p1_; c.p2 = p2_;
         c.equalize = equalize_ ? 1 : 0;
+        c.pixel_format = pixel_format_;
         row = c.height; col = c.width;
         check(gf_tracker_create(&c, &h_));
     }

@@ -42,6 +42,10 @@ template <class Est> class ReplayNode {
     std::deque<ImageMsg> img0_buf, img1_buf;
     long n_pairs = 0, n_thrown0 = 0, n_thrown1 = 0, n_gnss = 0;
     double gnss_local_time_diff = 0;   // config key `gnss_local_time_diff`: GNSS messages are merged at their local time
+    // run_bag only, off by default: the image0 messages' payload rows go to inputImage as they are -- the message's step, its encoding as the pixel format -- and
+    // the tracker converts them to MONO8 on the device, where getImageFromMsg's cv_bridge::toCvCopy(msg, MONO8) (rosNodeTest.cpp:238-254) runs on the host.  The
+    // estimator's tracker must have been created for the topic's encoding (bag_image_format below tells it).  Same pixels, so the same trajectory.
+    bool device_gray = false;
 
     explicit ReplayNode(Est& e) : estimator(e) {}
 
@@ -92,7 +96,7 @@ template <class Est> class ReplayNode {
             load_frame(dir, img1_buf.front(), true);
             img0_buf.pop_front(); img1_buf.pop_front();
             if (gw_ != dw_ || gh_ != dh_) throw std::runtime_error("replay: gray and depth frames differ in size");
-            GrayImage g; g.data = gray_.data(); g.rows = gh_; g.cols = gw_; g.stride = gw_;
+            GrayImage g; g.data = gray_.data(); g.rows = gh_; g.cols = gw_; g.stride = gstep_; g.pixel_format = gfmt_;
             DepthImage d; d.data = (const uint16_t*)depth_.data(); d.rows = dh_; d.cols = dw_; d.stride = dw_;
             estimator.inputImage(time, g, d);
             n_pairs++;
@@ -160,6 +164,16 @@ template <class Est> class ReplayNode {
         } catch (...) { bag_ = nullptr; throw; }
         bag_ = nullptr;
     }
+    // GF_PIX_* of the first message on `topic` (what a tracker that takes the payload undecoded has to be created for); -1: no message, or an encoding the node refuses
+    static int bag_image_format(const std::string& bag_path, const std::string& topic) {
+        BagReader bag(bag_path);
+        for (const BagMessageRef& m : bag.select({topic})) {
+            size_t len = 0;
+            const uint8_t* d = bag.payload(m, &len);
+            return gfpix::format_of_encoding(ros_image(d, len).encoding.c_str());
+        }
+        return -1;
+    }
     // gnss.csv / gnss_align.csv are optional: a dataset without them replays as before
     static void load_gnss(const std::string& dir, std::vector<GnssMsg>& gn, std::vector<GnssAlignMsg>& al) {
         if (std::ifstream(dir + "/gnss.csv"))
@@ -192,16 +206,24 @@ template <class Est> class ReplayNode {
   private:
     std::vector<uint8_t> gray_, depth_;
     int gw_ = 0, gh_ = 0, dw_ = 0, dh_ = 0;
+    int gstep_ = 0, gfmt_ = GF_PIX_MONO8;   // row step [bytes] and format of gray_: tight MONO8 unless device_gray
     BagReader* bag_ = nullptr;
     std::vector<uint16_t> depth16_;
 
     void load_frame(const std::string& dir, const ImageMsg& m, bool depth) {
-        if (!m.in_bag) { if (depth) load_pgm(dir + "/" + m.file, depth_, sizeof(uint16_t), dw_, dh_); else load_pgm(dir + "/" + m.file, gray_, sizeof(uint8_t), gw_, gh_); return; }
+        if (!m.in_bag) { if (depth) load_pgm(dir + "/" + m.file, depth_, sizeof(uint16_t), dw_, dh_); else { load_pgm(dir + "/" + m.file, gray_, sizeof(uint8_t), gw_, gh_); gstep_ = gw_; gfmt_ = GF_PIX_MONO8; } return; }
         size_t len = 0;
         const uint8_t* d = bag_->payload(m.ref, &len);
         const RosImage im = ros_image(d, len);
         if (depth) { ros_image_to_mono16(im, depth16_); depth_.resize(depth16_.size() * 2); memcpy(depth_.data(), depth16_.data(), depth_.size()); dw_ = (int)im.width; dh_ = (int)im.height; }
-        else { ros_image_to_mono8(im, gray_); gw_ = (int)im.width; gh_ = (int)im.height; }
+        else if (device_gray) {   // the rows as the message carries them (copied: the payload is the bag's until the next message is read)
+            const int fmt = gfpix::format_of_encoding(im.encoding.c_str());
+            if (fmt < 0) throw BagError("bag: image encoding '" + im.encoding + "' -> MONO8 is not built (mono8, 8UC1, rgb8, bgr8, rgba8, bgra8 are)");
+            if ((uint64_t)im.width * gfpix::channels(fmt) > im.step) throw BagError("bag: Image.step shorter than a row");
+            gray_.assign(im.data, im.data + (size_t)im.step * im.height);
+            gw_ = (int)im.width; gh_ = (int)im.height; gstep_ = (int)im.step; gfmt_ = fmt;
+        }
+        else { ros_image_to_mono8(im, gray_); gw_ = (int)im.width; gh_ = (int)im.height; gstep_ = gw_; gfmt_ = GF_PIX_MONO8; }
     }
 
     static double num(const std::string& s) {

@@ -25,6 +25,8 @@
 #include <string>
 #include <vector>
 
+#include "../csrc/gf_pixfmt.hpp"   // the gray formula and the channel layouts, shared with the conversion kernels
+
 namespace gf {
 
 struct BagError : std::runtime_error { using std::runtime_error::runtime_error; };
@@ -334,21 +336,16 @@ inline RosImage ros_image(const uint8_t* d, size_t n) {
 // getImageFromMsg (rosNodeTest.cpp:238-263): 8UC1 is relabelled mono8, everything else goes through cv_bridge::toCvCopy(msg, MONO8).  EQUALIZE (CLAHE) is outside the built path.
 inline void ros_image_to_mono8(const RosImage& m, std::vector<uint8_t>& out) {
     const std::string& e = m.encoding;
-    int ch = 0, r = 0, g = 1, b = 2;
-    if (e == "mono8" || e == "8UC1") ch = 1;
-    else if (e == "rgb8") ch = 3;
-    else if (e == "bgr8") { ch = 3; r = 2; b = 0; }
-    else if (e == "rgba8") ch = 4;
-    else if (e == "bgra8") { ch = 4; r = 2; b = 0; }
-    else throw BagError("bag: image encoding '" + e + "' -> MONO8 is not built (mono8, 8UC1, rgb8, bgr8, rgba8, bgra8 are)");
+    const int fmt = gfpix::format_of_encoding(e.c_str());
+    if (fmt < 0) throw BagError("bag: image encoding '" + e + "' -> MONO8 is not built (mono8, 8UC1, rgb8, bgr8, rgba8, bgra8 are)");
+    const int ch = gfpix::channels(fmt), r = gfpix::red_at(fmt), g = 1, b = gfpix::blue_at(fmt);
     if ((uint64_t)m.width * ch > m.step) throw BagError("bag: Image.step shorter than a row");
     out.resize((size_t)m.width * m.height);
     for (uint32_t y = 0; y < m.height; y++) {
         const uint8_t* s = m.data + (size_t)y * m.step;
         uint8_t* o = out.data() + (size_t)y * m.width;
         if (ch == 1) memcpy(o, s, m.width);
-        else for (uint32_t x = 0; x < m.width; x++, s += ch)   // OpenCV 4.2 color_rgb.cpp RGB2Gray<uchar>: CV_DESCALE(b B2Y + g G2Y + r R2Y, 14), B2Y 1868, G2Y 9617, R2Y 4899
-            o[x] = (uint8_t)((s[b] * 1868 + s[g] * 9617 + s[r] * 4899 + (1 << 13)) >> 14);
+        else for (uint32_t x = 0; x < m.width; x++, s += ch) o[x] = gfpix::gray(s[r], s[g], s[b]);   // the formula the device conversion uses too (csrc/gf_pixfmt.hpp)
     }
 }
 // getDepthImageFromMsg (rosNodeTest.cpp:265-286): the payload is relabelled MONO16 whatever the message says: two bytes per pixel, in the message's byte order

@@ -5,6 +5,8 @@
 //                                                                   pose of their sequences with ncclAllGather over RCCL (gf_comm_*); rank 0 prints all of them
 //   gf_replay <config.yaml> --bag <recording.bag> [<vio.txt>]      the recording itself (ROS bag format 2.0, host/rosbag_reader.h); topics = the config's
 //                                                                   imu_topic / wheel_topic / image0_topic / image1_topic (parameters.cpp:156-157, :211, :230)
+//   gf_replay --device-gray <config.yaml> --bag <recording.bag> [<vio.txt>]   the same, but the image0 messages go to the tracker undecoded (their step, their
+//                                                                   encoding) and cv_bridge::toCvCopy(msg, MONO8) (rosNodeTest.cpp:238-254) runs on the device; same vio.txt
 // reads the reference's own YAML configuration (parameters.cpp key names), replays the recorded IMU / wheel / RGB / depth messages of
 // <dataset dir> (layout in host/replay_node.h) through FeatureTracker::trackImage and Estimator::processImage on the GPU, and writes the
 // trajectory file the reference writes (output_path/vio.txt, TUM format) — to <vio.txt> when given, else to `output_path` of the config.
@@ -35,8 +37,13 @@ static std::string yaml_string(const std::string& file, const std::string& key) 
     return std::string();
 }
 
-static void replay_one(const char* config, const std::string& source, bool from_bag, const std::string& out, gf::Estimator& estimator, bool quiet) {
+static void replay_one(const char* config, const std::string& source, bool from_bag, const std::string& out, gf::Estimator& estimator, bool quiet, bool device_gray = false) {
     estimator.readParameters(config);
+    if (device_gray) {   // the tracker is created for the encoding of the colour topic: one handle has one format
+        const int fmt = gf::ReplayNode<gf::Estimator>::bag_image_format(source, yaml_string(config, "image0_topic"));
+        if (fmt < 0) throw std::runtime_error("--device-gray: no image0_topic message with an encoding the node converts to MONO8 in " + source);
+        estimator.cfg.tracker.pixel_format = fmt;
+    }
     // `max_solver_time` (a wall-clock cap on ceres::Solve) makes a replay depend on the machine and on what else it is doing: honoured only on request
     if (!getenv("GF_HONOUR_SOLVER_TIME")) estimator.cfg.max_solver_time = 0.0;
     estimator.setParameter();
@@ -45,6 +52,7 @@ static void replay_one(const char* config, const std::string& source, bool from_
     const std::string wr = yaml_string(config, "w_replace");
     node.w_replace = wr.empty() ? 0 : atoi(wr.c_str());
     node.gnss_local_time_diff = estimator.cfg.gnss_enable ? estimator.cfg.gnss_local_time_diff : 0.0;   // rosNodeTest.cpp:703-708
+    node.device_gray = device_gray;
     if (from_bag) node.run_bag(source, yaml_string(config, "imu_topic"), yaml_string(config, "wheel_topic"), yaml_string(config, "image0_topic"), yaml_string(config, "image1_topic"));
     else node.run(source);
     if (!quiet)
@@ -144,6 +152,9 @@ static int run_rank(int rank, int world, const char* config, const std::vector<s
 }
 
 int main(int argc, char** argv) {
+    bool device_gray = false;   // --device-gray, anywhere on the line: taken out before the positional arguments are read
+    for (int i = 1; i < argc; i++)
+        if (std::string(argv[i]) == "--device-gray") { device_gray = true; for (int j = i; j + 1 < argc; j++) argv[j] = argv[j + 1]; argc--; i--; }
     if (argc >= 5 && std::string(argv[1]) == "--ranks") {
         const int world = atoi(argv[2]);
         if (world < 1 || world > 64) { fprintf(stderr, "gf_replay: --ranks must be in 1..64\n"); return 2; }
@@ -180,12 +191,13 @@ int main(int argc, char** argv) {
         return rc;
     }
     const bool from_bag = argc >= 4 && std::string(argv[2]) == "--bag";
-    if (argc < 3 || (from_bag && argc < 4)) { fprintf(stderr, "usage: %s <config.yaml> <dataset dir> [<vio.txt>]\n       %s <config.yaml> --bag <recording.bag> [<vio.txt>]\n       %s --ranks N <config.yaml> <dataset dir> ...\n", argv[0], argv[0], argv[0]); return 2; }
+    if (argc < 3 || (from_bag && argc < 4)) { fprintf(stderr, "usage: %s <config.yaml> <dataset dir> [<vio.txt>]\n       %s [--device-gray] <config.yaml> --bag <recording.bag> [<vio.txt>]\n       %s --ranks N <config.yaml> <dataset dir> ...\n", argv[0], argv[0], argv[0]); return 2; }
+    if (device_gray && !from_bag) { fprintf(stderr, "gf_replay: --device-gray goes with --bag (PGM frames are MONO8 already)\n"); return 2; }
     const int out_arg = from_bag ? 4 : 3;
     try {
         gf::Estimator estimator;
         const std::string out = argc > out_arg ? argv[out_arg] : yaml_string(argv[1], "output_path") + "/vio.txt";
-        replay_one(argv[1], from_bag ? argv[3] : argv[2], from_bag, out, estimator, false);
+        replay_one(argv[1], from_bag ? argv[3] : argv[2], from_bag, out, estimator, false, device_gray);
         if (estimator.cfg.gnss_enable) {   // gnss_result.txt of the reference carries the ECEF / ENU position; here as one closing line
             int gi[8]; double yaw, anc[3], ecef[3], enu[3];
             if (gf_estimator_get_gnss_state(estimator.handle(), gi, nullptr, nullptr, &yaw, anc, ecef, enu) == GF_OK) {
