@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "gf_lk_kernels.hpp"
+#include "gf_roi.hpp"
 
 namespace gf {
 
@@ -80,6 +81,10 @@ struct DetectArgs {
     const uint8_t* pyr; size_t pyr_bytes; const int* frame_of; LevelGeom g;
     const uint8_t* mask; size_t mask_seq_stride;            // optional explicit mask (non-zero = allowed)
     const int2* centers; const int* n_centers; int cap;     // else: disks
+    // ... inside the sequences' regions of interest (gf_roi.hpp): the handle's table, roi_seq_words words per SEQUENCE (the sequence is frame_of[i] >> 1, the entry
+    // the strip has loaded anyway), or null on a handle that never set one -- then the kernel is the one it was, a scalar compare aside.  A sequence of such a
+    // handle that has none holds all-ones words.
+    const uint32_t* roi; size_t roi_seq_words;
     unsigned* maxkey;                                       // [count] orderable max over unmasked pixels (0 = none)
     unsigned long long* cand; size_t cand_seq_stride; int cand_cap; int* cand_count;
 };
@@ -91,6 +96,7 @@ struct DetectArgs {
 // min_eig_kernel above (same operations in the same order; the box sums are exact -- nine float products spanning < 2^52 -- so their order is free).
 constexpr int kDS_W = 60;   // output columns per wavefront
 constexpr int kDS_R = 30;   // rows per strip in trackImage: 36 raw rows for 30 output rows (16: 0.31 ms, 30: 0.27 ms, 32: 0.27 ms per 256 VGA frames)
+static_assert(kDS_R == gfroi::kRows && kDS_R <= 32, "a band of the region-of-interest table is a strip of the detector: one bit per strip row in a 32-bit word");
 typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
 __device__ __forceinline__ float dpp_from_left(float v) {   // lane l <- lane l - 1
     return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x138 /* wave_shr:1 */, 0xf, 0xf, true));   // lane 0 reads 0: halo, never used
@@ -133,6 +139,10 @@ __global__ void __launch_bounds__(64) detect_strip_kernel(DetectArgs A, DiskTabl
             for (int r = 0; r < nrows; r++)
                 if (A.mask[b * A.mask_seq_stride + (size_t)(Y0 + r) * g.w + x]) allow |= 1u << r;
     } else {
+        // the region of interest is the image setMask starts from: this lane's column of this band, one word, 64 neighbouring words per wavefront.  Asked for
+        // first, so that it arrives under the circles.  Lanes with col_out have 0 <= x < w, and blockIdx.y is a band of the table (same R, same rounding).
+        uint32_t roi_word = ~0u;
+        if (A.roi && col_out) roi_word = A.roi[(size_t)(cur >> 1) * A.roi_seq_words + gfroi::word_at(g.w, blockIdx.y, x)];
 #pragma unroll
         for (int q = 0; q < (kMaxRadius + 64) / 64; q++)
             if (lane + 64 * q <= T.radius) s_hw[lane + 64 * q] = T.hw[lane + 64 * q];
@@ -156,7 +166,7 @@ __global__ void __launch_bounds__(64) detect_strip_kernel(DetectArgs A, DiskTabl
                 }
             }
         }
-        if (col_out) allow = ~covered & rows_all;
+        if (col_out) allow = ~covered & rows_all & roi_word;
     }
     if (!__ballot(allow != 0)) return;   // nothing of this strip may hold a corner: no contribution to the masked maximum, no candidate
     // Which rows the strip has to work on at all.  With the window's tracks alive the circles cover most of the image (150 points at MIN_DIST 30: ~90 %), and an output
@@ -256,6 +266,15 @@ __global__ void __launch_bounds__(64) detect_strip_kernel(DetectArgs A, DiskTabl
     for (int o = 32; o > 0; o >>= 1) best = max(best, (unsigned)__shfl_xor((int)best, o));
     if (lane == 0 && best) atomicMax(A.maxkey + b, best);
     if (n_cand) strip_flush(cand_b, count_b, A.cand_cap, ckeys, n_cand, lane);
+}
+
+// The device setter of the region of interest (gf_tracker_set_roi_some_device): `count` tight h x w byte masks, back to back in list order -> the tables of the
+// sequences seq_of[i].  One thread per word: thread x of band blockIdx.y of mask blockIdx.z walks its column down the band (gfroi::pack_thread, the function the
+// host setter runs), so a wavefront reads 64 neighbouring bytes per row and writes 64 neighbouring words.  Any w and h: the guard is x < w, the last band is
+// rows_of_band() rows, and nothing outside [0, count * h * w) is read.
+__global__ void __launch_bounds__(256) roi_pack_kernel(const uint8_t* __restrict__ masks, const int* __restrict__ seq_of, int w, int h, uint32_t* __restrict__ table,
+                                                       size_t seq_words) {
+    gfroi::pack_thread(masks + (size_t)blockIdx.z * h * w, (size_t)w, w, h, blockIdx.y, blockIdx.x * 256 + threadIdx.x, table + (size_t)list_entry(seq_of, blockIdx.z) * seq_words);
 }
 
 // Both selection kernels run one block per list position and touch only tables of the call ([count], by position): the candidates, want, the output and the

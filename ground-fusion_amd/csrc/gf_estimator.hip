@@ -1953,6 +1953,12 @@ int gf_estimator_input_image(gf_estimator* e, double t, const uint8_t* gray, int
     return gf_estimator_input_feature(e, t, out, n);
 }
 
+// the region of interest of the estimator's own tracker (gf_tracker_set_roi on its one sequence): from the next gf_estimator_input_image on
+int gf_estimator_set_roi(gf_estimator* e, const uint8_t* mask, int stride) {
+    if (!e || !e->tracker) return gf::set_err(GF_ERR_INVALID, "estimator was created without a tracker (cfg.with_tracker)");
+    return gf_tracker_set_roi(e->tracker, 0, mask, stride);
+}
+
 int gf_estimator_get_state(gf_estimator* e, double* Ps, double* Rs, double* Vs, double* Bas, double* Bgs, double* Headers, int* info, double* extr) {
     if (!e) return gf::set_err(GF_ERR_INVALID, "null handle");
     for (int i = 0; i <= e->WINDOW_SIZE; i++) {

@@ -34,6 +34,7 @@
 #include "gf_host_cpus.hpp"
 #include "gf_hip_own.hpp"
 #include "gf_pixfmt.hpp"
+#include "gf_roi.hpp"
 
 namespace gf {
 
@@ -196,6 +197,13 @@ struct gf_tracker {
     PinBuf<int2> h_centers;
     size_t eig_stride = 0, mask_stride = 0;
     size_t select_lds = 0;
+    // The sequences' regions of interest (gf_roi.hpp; gf_tracker_set_roi*), addressed by SEQUENCE like seq[] and the pyramid pairs.  Everything here is obtained by the
+    // first setter of the handle, never by gf_tracker_create: a handle that sets none allocates, copies and launches exactly what it did before there were any.
+    // d_roi: [B][roi_words] words the detector ANDs into its allow word, all-ones for a sequence that has no region (the AND changes nothing).  roi_bits: the same
+    // words on the host, which setMask's walk reads (set_mask_host); roi_has[seq]: whether the sequence has one (0: the walk skips the test).
+    DevBuf<uint32_t> d_roi; DevBuf<int> d_roi_seq;
+    std::vector<uint32_t> roi_bits; std::vector<uint8_t> roi_has;
+    size_t roi_words = 0;
 
     std::unique_ptr<HostPool> pool;
 };
@@ -318,7 +326,9 @@ static LkBatchArgs lk_args(gf_tracker* h, int fwd_max_level, int use_init, int f
 
 // setMask (feature_tracker.cpp:56-83): std::sort by track count (same comparator, same libstdc++ algorithm as
 // the reference) and greedy keep of points not covered by an earlier kept point's filled circle.
-static void set_mask_host(gf_tracker* h, SeqState& s, int2* centers, int& n_centers) {
+// roi: the sequence's region of interest (gf_roi.hpp) or null.  With one, the walk starts from `mask = R` instead of an all-255 image: a point whose rounded pixel
+// is excluded fails `mask.at(pt) == 255` like a covered one -- not kept, no circle, gone from ids / track_cnt / cur_pts.
+static void set_mask_host(gf_tracker* h, SeqState& s, const uint32_t* roi, int2* centers, int& n_centers) {
     struct E { int cnt; P2f pt; int id; uint16_t depth; };
     static thread_local std::vector<E> v;
     v.clear();
@@ -335,6 +345,7 @@ static void set_mask_host(gf_tracker* h, SeqState& s, int2* centers, int& n_cent
     s.grid_next.clear();
     for (auto& it : v) {
         const int x = cvRoundf(it.pt.x), y = cvRoundf(it.pt.y);
+        if (roi && !gfroi::allowed(roi, h->cfg.width, x, y)) continue;   // tracked points are inside the image (inBorder, feature_tracker.cpp:14-20)
         const int cx = x / cell, cy = y / cell;
         bool covered = false;
         for (int yy = std::max(cy - 1, 0); yy <= std::min(cy + 1, gh - 1) && !covered; yy++)
@@ -381,6 +392,31 @@ static int check_list(gf_tracker* h, int count, const int* seq) {
         if (h->listed[seq[i]]) return set_err(GF_ERR_INVALID, "sequence %d is listed twice", seq[i]);
         h->listed[seq[i]] = 1;
     }
+    return GF_OK;
+}
+
+// ---- region of interest (gf_roi.hpp).  The setters run between frames: every track call returns with the handle's stream drained, so the table is never written
+// under a detector that reads it; they leave on the same stream, in front of the next frame's kernels.
+static int roi_ready(gf_tracker* h) {   // the first setter of a handle: the table, all-ones (no sequence has a region yet), and its host copy
+    if (h->d_roi.p) return GF_OK;
+    const size_t words = gfroi::words(h->cfg.width, h->cfg.height), all = (size_t)h->B * words;
+    DevBuf<uint32_t> table; DevBuf<int> list;
+    HIPCHK(table.alloc(all)); HIPCHK(list.alloc(h->B));
+    HIPCHK(hipMemset(table.p, 0xff, all * sizeof(uint32_t)));
+    HIPCHK(hipStreamSynchronize(nullptr));
+    h->roi_bits.assign(all, ~0u); h->roi_has.assign(h->B, 0);
+    h->roi_words = words;
+    h->d_roi = std::move(table); h->d_roi_seq = std::move(list);
+    return GF_OK;
+}
+static void roi_clear_host(gf_tracker* h, int seq) {
+    std::fill_n(h->roi_bits.begin() + (size_t)seq * h->roi_words, h->roi_words, ~0u);
+    h->roi_has[seq] = 0;
+}
+static int roi_upload(gf_tracker* h, int seq) {   // the host copy of one sequence's words -> the table
+    const size_t off = (size_t)seq * h->roi_words;
+    HIPCHK(hipMemcpyAsync(h->d_roi.p + off, h->roi_bits.data() + off, h->roi_words * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));   // roi_bits is pageable
     return GF_OK;
 }
 
@@ -559,7 +595,8 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
         }
         for (auto& c : s.track_cnt) c++;
         int nc = 0;
-        set_mask_host(h, s, h->h_centers.p + (size_t)b * cap, nc);
+        const uint32_t* roi = !h->roi_has.empty() && h->roi_has[seq[b]] ? h->roi_bits.data() + (size_t)seq[b] * h->roi_words : nullptr;
+        set_mask_host(h, s, roi, h->h_centers.p + (size_t)b * cap, nc);
         h->h_ncenters.p[b] = nc;
         const int want = h->cfg.max_cnt - (int)s.cur_pts.size();
         h->h_want.p[b] = want;
@@ -585,6 +622,7 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
             DetectArgs D{};
             D.pyr = h->d_img.p; D.pyr_bytes = h->G.img_bytes; D.frame_of = h->d_det.p; D.g = h->G.lv[0];
             D.mask = nullptr; D.mask_seq_stride = 0; D.centers = h->d_centers.p; D.n_centers = h->d_ncenters.p; D.cap = cap;
+            D.roi = h->d_roi.p; D.roi_seq_words = h->roi_words;   // null on a handle no setter has touched
             D.maxkey = h->d_maxkey.p; D.cand = h->d_cand.p; D.cand_seq_stride = (size_t)h->cand_cap; D.cand_cap = h->cand_cap; D.cand_count = h->d_cand_count.p;
             detect_strip_kernel<kDS_R><<<dim3((W + kDS_W - 1) / kDS_W, (H + kDS_R - 1) / kDS_R, N), 64, 0, h->stream>>>(D, h->disk);
         }
@@ -893,6 +931,58 @@ int gf_tracker_set_prediction(gf_tracker* h, int seq, const int* ids, const doub
         if (it != m.end()) { double u, v; gf::space_to_plane(h->cfg, it->second, u, v); s.predict_pts.push_back({(float)u, (float)v}); }
         else s.predict_pts.push_back(s.prev_pts[i]);
     }
+    return GF_OK;
+}
+
+int gf_tracker_set_roi(gf_tracker* h, int seq, const uint8_t* mask, int stride) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    const int W = h->cfg.width, H = h->cfg.height;
+    if (mask && stride < W) return gf::set_err(GF_ERR_INVALID, "a mask stride of %d bytes is shorter than a row of %d pixels", stride, W);
+    if (!mask && !h->d_roi.p) return GF_OK;   // nothing to clear: the handle stays one that never had a region
+    if (int rc = gf::roi_ready(h)) return rc;
+    if (mask) {
+        uint32_t* t = h->roi_bits.data() + (size_t)seq * h->roi_words;
+        for (int band = 0; band < gfroi::bands(H); band++)
+            for (int x = 0; x < W; x++)
+                gfroi::pack_thread(mask, (size_t)stride, W, H, band, x, t);
+        h->roi_has[seq] = 1;
+    } else gf::roi_clear_host(h, seq);
+    return gf::roi_upload(h, seq);
+}
+
+int gf_tracker_set_roi_some_device(gf_tracker* h, int count, const int* seq, const void* d_masks) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (int rc = gf::check_list(h, count, seq)) return rc;
+    if (count == 0 || (!d_masks && !h->d_roi.p)) return GF_OK;
+    if (int rc = gf::roi_ready(h)) return rc;
+    if (!d_masks) {
+        for (int i = 0; i < count; i++) { gf::roi_clear_host(h, seq[i]); if (int rc = gf::roi_upload(h, seq[i])) return rc; }
+        return GF_OK;
+    }
+    const int W = h->cfg.width, H = h->cfg.height;
+    HIPCHK(hipMemcpyAsync(h->d_roi_seq.p, seq, (size_t)count * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    gf::roi_pack_kernel<<<dim3((W + 255) / 256, gfroi::bands(H), count), 256, 0, h->stream>>>((const uint8_t*)d_masks, h->d_roi_seq.p, W, H, h->d_roi.p, h->roi_words);
+    HIPCHK(hipGetLastError());
+    for (int i = 0; i < count; i++) {   // the words come back: setMask's walk reads them on the host
+        const size_t off = (size_t)seq[i] * h->roi_words;
+        HIPCHK(hipMemcpyAsync(h->roi_bits.data() + off, h->d_roi.p + off, h->roi_words * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < count; i++) h->roi_has[seq[i]] = 1;
+    return GF_OK;
+}
+
+int gf_tracker_get_roi(gf_tracker* h, int seq, uint8_t* mask, int stride, int* has) {
+    if (!h || !has) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    const int W = h->cfg.width, H = h->cfg.height;
+    if (mask && stride < W) return gf::set_err(GF_ERR_INVALID, "a mask stride of %d bytes is shorter than a row of %d pixels", stride, W);
+    *has = !h->roi_has.empty() && h->roi_has[seq] ? 1 : 0;
+    if (!*has || !mask) return GF_OK;
+    const uint32_t* t = h->roi_bits.data() + (size_t)seq * h->roi_words;
+    for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++) mask[(size_t)y * stride + x] = gfroi::allowed(t, W, x, y) ? 255 : 0;
     return GF_OK;
 }
 

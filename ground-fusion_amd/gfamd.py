@@ -47,6 +47,7 @@ assert OBS_DTYPE.itemsize == C.sizeof(FeatureObs)
 
 EXPORTS = ["gf_last_error", "gf_device_count", "gf_set_device", "gf_tracker_create", "gf_tracker_destroy", "gf_tracker_track",
            "gf_tracker_track_batch", "gf_tracker_track_batch_device", "gf_tracker_track_some", "gf_tracker_track_some_device", "gf_tracker_prefetch_some", "gf_tracker_set_prediction", "gf_tracker_remove_outliers",
+           "gf_tracker_set_roi", "gf_tracker_set_roi_some_device", "gf_tracker_get_roi",
            "gf_tracker_get_state", "gf_tracker_set_profiling", "gf_tracker_get_stats", "gf_tracker_reset_stats", "gf_lk_track",
            "gf_good_features", "gf_min_eigen_val", "gf_pyramid_level", "gf_clahe_batch", "gf_clahe_batch_device", "gf_cvt_gray_batch", "gf_cvt_gray_batch_device"]
 
@@ -252,6 +253,31 @@ class FeatureTracker:
     def removeOutliers(self, ids, seq=0):
         ids = np.ascontiguousarray(ids, np.int32)
         _chk(lib().gf_tracker_remove_outliers(self.h, seq, _p(ids, C.c_int), len(ids)))
+
+    def set_roi(self, mask, seq=0):
+        """gf_tracker_set_roi: the region of interest of sequence `seq` from a [height, width] u8 image (non-zero = allowed; its rows may be pitched), None clears.
+        It stays until replaced or cleared and holds from the sequence's next frame on, through every entry point."""
+        if mask is None:
+            _chk(lib().gf_tracker_set_roi(self.h, seq, None, 0))
+            return
+        mask = np.asarray(mask)
+        assert mask.dtype == np.uint8 and mask.shape == (self.cfg.height, self.cfg.width), (mask.dtype, mask.shape)
+        if mask.strides[1] != 1 or mask.strides[0] < self.cfg.width:
+            mask = np.ascontiguousarray(mask)
+        _chk(lib().gf_tracker_set_roi(self.h, seq, _p(mask, C.c_uint8), mask.strides[0]))
+
+    def set_roi_device(self, seqs, d_masks_ptr):
+        """gf_tracker_set_roi_some_device: d_masks_ptr = integer device address of len(seqs) tight [height, width] u8 masks back to back, mask i for sequence
+        seqs[i] (complete when the call is made); None / 0 clears the listed sequences"""
+        seqs, N = self._seqs(seqs)
+        _chk(lib().gf_tracker_set_roi_some_device(self.h, N, _p(seqs, C.c_int), C.c_void_p(d_masks_ptr) if d_masks_ptr else None))
+
+    def get_roi(self, seq=0):
+        """gf_tracker_get_roi: the stored region of sequence `seq` as a [height, width] u8 image of 0 / 255, or None if it has none"""
+        mask = np.zeros((self.cfg.height, self.cfg.width), np.uint8)
+        has = C.c_int(0)
+        _chk(lib().gf_tracker_get_roi(self.h, seq, _p(mask, C.c_uint8), self.cfg.width, C.byref(has)))
+        return mask if has.value else None
 
     def state(self, seq=0):
         ids = np.zeros(self.cap, np.int32)
@@ -810,6 +836,14 @@ class SlidingWindowEstimator:
                                                _p(ecef, C.c_double), _p(enu, C.c_double)))
         return dict(gnss_ready=int(info[0]), lowspeed=int(info[1]), n_newest=int(info[2]), first_optimization=int(info[3]), queued=int(info[4]),
                     rcv_dt=dt, rcv_ddt=ddt, yaw_enu_local=yaw.value, anc_ecef=anc, ecef_pos=ecef, enu_pos=enu)
+
+    def set_roi(self, mask):
+        """gf_estimator_set_roi: the region of interest of the estimator's own tracker ([height, width] u8, non-zero = allowed; None clears)"""
+        if mask is None:
+            _chk(lib().gf_estimator_set_roi(self.h, None, 0))
+            return
+        mask = np.ascontiguousarray(mask, np.uint8)
+        _chk(lib().gf_estimator_set_roi(self.h, _p(mask, C.c_uint8), mask.shape[1]))
 
     def inputImage(self, t, img, depth=None):
         img = np.ascontiguousarray(img, np.uint8)

@@ -141,6 +141,16 @@ class Estimator {
         check(gf_estimator_input_image(h_, t, _img.data, _img.stride, _img1.empty() ? nullptr : _img1.data, _img1.stride, nullptr, 0, nullptr));
         refresh();
     }
+    // the region of interest of the estimator's own tracker (FeatureTracker::setRegionOfInterest, gf_estimator_set_roi): rows x cols bytes of cfg.tracker's frame
+    // size, non-zero = allowed, nullptr clears; from the next inputImage on
+    void setRegionOfInterest(const uint8_t* mask, int stride) { need(); check(gf_estimator_set_roi(h_, mask, stride)); }
+#ifdef GF_WITH_OPENCV
+    void setRegionOfInterest(const cv::Mat& mask) {
+        if (mask.empty()) { setRegionOfInterest(nullptr, 0); return; }
+        if (mask.type() != CV_8UC1 || mask.rows != cfg.tracker.height || mask.cols != cfg.tracker.width) throw std::runtime_error("setRegionOfInterest: the mask must be CV_8UC1 of the frame size");
+        setRegionOfInterest(mask.ptr<uint8_t>(), (int)mask.step);
+    }
+#endif
 #ifdef GF_WITH_OPENCV
     void inputImage(double t, const cv::Mat& _img, const cv::Mat& _img1 = cv::Mat(), bool rgb_order = false) {   // rgb_order: FeatureTracker::viewOf
         const GrayImage g = FeatureTracker::viewOf(_img, rgb_order);

@@ -91,6 +91,31 @@ class FeatureTracker {
         equalize_ = on;
     }
 
+    // The region of interest: the image setMask() (feature_tracker.cpp:56-83, private there as here) starts from instead of an all-255 one -- VINS-Mono's
+    // fisheye_mask, which the reference dropped (feature_tracker.cpp:58).  rows x cols bytes of the frame size, `stride` bytes from row to row, non-zero =
+    // allowed; nullptr clears.  Tracks that end up on an excluded pixel are dropped in setMask's walk and new corners are sought inside it only
+    // (gf_tracker_set_roi).  Any time: it holds from the next trackImage on, and may be replaced between any two frames.  Before the first frame the size must
+    // be known (readIntrinsicParameter / setIntrinsics).
+    void setRegionOfInterest(const uint8_t* mask, int stride) {
+        if (!mask && !h_) { roi_.clear(); return; }
+        if (!h_) {   // kept until the handle exists (the first frame decides the pixel format)
+            if (!row || !col) throw std::runtime_error("setRegionOfInterest: the frame size is not known yet (readIntrinsicParameter / setIntrinsics)");
+            if (stride < col) throw std::runtime_error("setRegionOfInterest: stride < width");
+            roi_.resize((size_t)row * col);
+            for (int y = 0; y < row; y++) for (int x = 0; x < col; x++) roi_[(size_t)y * col + x] = mask[(size_t)y * stride + x];
+            return;
+        }
+        check(gf_tracker_set_roi(h_, 0, mask, stride));
+    }
+#ifdef GF_WITH_OPENCV
+    void setRegionOfInterest(const cv::Mat& mask) {   // CV_8UC1 of the frame size; an empty Mat clears
+        if (mask.empty()) { setRegionOfInterest(nullptr, 0); return; }
+        if (mask.type() != CV_8UC1 || (row && (mask.rows != row || mask.cols != col))) throw std::runtime_error("setRegionOfInterest: the mask must be CV_8UC1 of the frame size");
+        if (!row) { row = mask.rows; col = mask.cols; }
+        setRegionOfInterest(mask.ptr<uint8_t>(), (int)mask.step);
+    }
+#endif
+
     FeatureFrame trackImage(double _cur_time, const GrayImage& _img, const DepthImage& _img1 = DepthImage()) {
         if (!h_) { pixel_format_ = _img.pixel_format; create(_img.cols, _img.rows); }
         // one handle has one format (a camera does not change its encoding): the first frame decides, as it decides the size
@@ -139,6 +164,7 @@ class FeatureTracker {
     double fx_ = 1, fy_ = 1, cx_ = 0, cy_ = 0, k1_ = 0, k2_ = 0, p1_ = 0, p2_ = 0;
     bool equalize_ = false;
     int pixel_format_ = GF_PIX_MONO8;
+    std::vector<uint8_t> roi_;   // a region of interest set before the handle exists (tight rows)
     static void check(int rc) { if (rc != GF_OK) throw std::runtime_error(std::string("groundfusion_hip: ") + gf_last_error()); }
     void create(int w, int h) {
         gf_tracker_cfg c{};
@@ -148,6 +174,7 @@ class FeatureTracker {
         c.pixel_format = pixel_format_;
         row = c.height; col = c.width;
         check(gf_tracker_create(&c, &h_));
+        if (!roi_.empty()) { check(gf_tracker_set_roi(h_, 0, roi_.data(), col)); roi_.clear(); }
     }
     void refresh() {
         const int cap = (MAX_CNT + 3) & ~3;

@@ -150,6 +150,29 @@ int gf_tracker_prefetch_some(gf_tracker* h, int count, const int* seq, const uin
 
 /* FeatureTracker::setPrediction (feature_tracker.cpp:1006-1027): ids[n], xyz[3n] camera-frame points. */
 int gf_tracker_set_prediction(gf_tracker* h, int seq, const int* ids, const double* xyz, int n);
+/* Region of interest: where in the image a sequence may hold features.  A sequence has either none (the default; every result as without these calls, bit for
+ * bit) or a height x width binary image R (on intake non-zero = allowed, 0 = excluded).  With R set, a tracker call for that sequence is
+ * FeatureTracker::trackImage (feature_tracker.cpp:103-372) with the first line of setMask() (:58, `mask = cv::Mat(row, col, CV_8UC1, cv::Scalar(255))`) replaced
+ * by `mask = R` with R in {0, 255} -- VINS-Mono's `fisheye_mask.clone()`:
+ *   1. a tracked point whose rounded pixel has R == 0 is dropped in setMask's walk (in track-count order, after LK and its checks): not kept, no circle painted,
+ *      not reported, gone from ids / track_cnt / prev_pts; its id never comes back;
+ *   2. new corners are sought in R minus the circles of the kept points: the quality threshold is 0.01 x the largest eigenvalue over THAT set (minMaxLoc with
+ *      mask), while the 3 x 3 local-maximum test still looks at excluded neighbours, as goodFeaturesToTrack does;
+ *   3. everything else -- LK, the reverse check, the border and grey checks, setPrediction, removeOutliers, depth sampling, velocities, the min-distance
+ *      greedy -- is unchanged.  (trackImagebox's filter of the OUTPUT, which keeps boxed features alive inside the tracker, is not what this is.)
+ * R belongs to the SEQUENCE, not to a call or a list position; it stays until it is replaced or cleared, and a setter takes effect with the next frame the
+ * sequence is given, through every entry point (host, prefetched and device frames, the _some forms, colour and equalize handles alike).  A region that
+ * excludes everything is no error: the sequence reports no features.  The table (one bit per pixel) is allocated when the first region of a handle is set; a
+ * handle that sets none allocates and launches nothing for it.  Refused with GF_ERR_INVALID, nothing changed: a null handle, seq out of range or named twice
+ * in a list, count < 0 or > batch, stride < width.  Like the track calls, one caller thread per handle. */
+/* R from a host image, rows `stride` bytes apart (>= width); mask == NULL clears the sequence's region */
+int gf_tracker_set_roi(gf_tracker* h, int seq, const uint8_t* mask, int stride);
+/* R for the `count` listed sequences from device memory: d_masks = count tight height x width byte images back to back, in list order (a segmentation that
+ * lives on the GPU).  Ordered on the handle's stream like the device frame entry points (the masks must be complete when the call is made); returns when the
+ * table is written.  d_masks == NULL clears the listed sequences.  Leaves the very bits gf_tracker_set_roi leaves for the same image. */
+int gf_tracker_set_roi_some_device(gf_tracker* h, int count, const int* seq, const void* d_masks);
+/* *has = whether the sequence has a region; if so and mask != NULL, the stored region as 0 / 255 bytes, rows `stride` bytes apart (>= width) */
+int gf_tracker_get_roi(gf_tracker* h, int seq, uint8_t* mask, int stride, int* has);
 /* FeatureTracker::removeOutliers (feature_tracker.cpp:1029-1045) */
 int gf_tracker_remove_outliers(gf_tracker* h, int seq, const int* ids, int n);
 /* public members ids / track_cnt / prev_pts (feature_tracker.h:85-88) */
@@ -505,6 +528,10 @@ int gf_estimator_input_image(gf_estimator* h, double t, const uint8_t* gray, int
  * last_track_num, long_track_num, new_feature_num, sum_of_back, sum_of_front.  extr[32]: tic 3, ric 9, tio 3, rio 9, sx, sy, sw, td,
  * td_wheel, last initial cost, last final cost, last_average_parallax */
 int gf_estimator_get_state(gf_estimator* h, double* Ps, double* Rs, double* Vs, double* Bas, double* Bgs, double* Headers, int* info, double* extr);
+/* The region of interest of an estimator that owns its tracker (cfg.with_tracker): gf_tracker_set_roi on that tracker's one sequence -- mask = height x width
+ * bytes of the tracker's frame size, rows `stride` bytes apart, non-zero = allowed, NULL clears; it holds from the next gf_estimator_input_image on.
+ * GF_ERR_INVALID without a tracker, and as gf_tracker_set_roi refuses. */
+int gf_estimator_set_roi(gf_estimator* h, const uint8_t* mask, int stride);
 int gf_estimator_set_state(gf_estimator* h, int frame_count, int solver_flag, const double* Ps, const double* Rs, const double* Vs,
                            const double* Bas, const double* Bgs);
 int gf_estimator_get_features(gf_estimator* h, int cap, int* id, int* start_frame, int* n_obs, double* estimated_depth, int* estimate_flag,

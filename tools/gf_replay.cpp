@@ -7,6 +7,8 @@
 //                                                                   imu_topic / wheel_topic / image0_topic / image1_topic (parameters.cpp:156-157, :211, :230)
 //   gf_replay --device-gray <config.yaml> --bag <recording.bag> [<vio.txt>]   the same, but the image0 messages go to the tracker undecoded (their step, their
 //                                                                   encoding) and cv_bridge::toCvCopy(msg, MONO8) (rosNodeTest.cpp:238-254) runs on the device; same vio.txt
+//   --roi <mask.pgm>                                                with any single-process form: a region of interest for the tracker (8-bit PGM of the configured
+//                                                                   frame size, non-zero = allowed; gf_estimator_set_roi).  No YAML key: the reference has none
 // reads the reference's own YAML configuration (parameters.cpp key names), replays the recorded IMU / wheel / RGB / depth messages of
 // <dataset dir> (layout in host/replay_node.h) through FeatureTracker::trackImage and Estimator::processImage on the GPU, and writes the
 // trajectory file the reference writes (output_path/vio.txt, TUM format) — to <vio.txt> when given, else to `output_path` of the config.
@@ -37,7 +39,21 @@ static std::string yaml_string(const std::string& file, const std::string& key) 
     return std::string();
 }
 
-static void replay_one(const char* config, const std::string& source, bool from_bag, const std::string& out, gf::Estimator& estimator, bool quiet, bool device_gray = false) {
+// --roi: the mask file -> the estimator's tracker; refused unless it is an 8-bit PGM of the configured frame size
+static void set_roi_from_pgm(gf::Estimator& estimator, const std::string& path) {
+    int w = 0, h = 0, mv = 0;
+    if (gf_pgm_read(path.c_str(), &w, &h, &mv, nullptr, 0) != GF_OK) throw std::runtime_error(std::string("--roi: ") + gf_last_error());
+    const int W = estimator.cfg.tracker.width, H = estimator.cfg.tracker.height;
+    if (mv > 255) throw std::runtime_error("--roi: " + path + " is a 16-bit PGM; the mask is 8-bit (non-zero = allowed)");
+    if (w != W || h != H)
+        throw std::runtime_error("--roi: " + path + " is " + std::to_string(w) + " x " + std::to_string(h) + ", the configured frames are " + std::to_string(W) + " x " + std::to_string(H));
+    std::vector<uint8_t> mask((size_t)w * h);
+    if (gf_pgm_read(path.c_str(), &w, &h, &mv, mask.data(), mask.size()) != GF_OK) throw std::runtime_error(std::string("--roi: ") + gf_last_error());
+    estimator.setRegionOfInterest(mask.data(), w);
+}
+
+static void replay_one(const char* config, const std::string& source, bool from_bag, const std::string& out, gf::Estimator& estimator, bool quiet, bool device_gray = false,
+                       const std::string& roi = std::string()) {
     estimator.readParameters(config);
     if (device_gray) {   // the tracker is created for the encoding of the colour topic: one handle has one format
         const int fmt = gf::ReplayNode<gf::Estimator>::bag_image_format(source, yaml_string(config, "image0_topic"));
@@ -48,6 +64,7 @@ static void replay_one(const char* config, const std::string& source, bool from_
     if (!getenv("GF_HONOUR_SOLVER_TIME")) estimator.cfg.max_solver_time = 0.0;
     estimator.setParameter();
     estimator.setResultPath(out);
+    if (!roi.empty()) set_roi_from_pgm(estimator, roi);
     gf::ReplayNode<gf::Estimator> node(estimator);
     const std::string wr = yaml_string(config, "w_replace");
     node.w_replace = wr.empty() ? 0 : atoi(wr.c_str());
@@ -155,6 +172,15 @@ int main(int argc, char** argv) {
     bool device_gray = false;   // --device-gray, anywhere on the line: taken out before the positional arguments are read
     for (int i = 1; i < argc; i++)
         if (std::string(argv[i]) == "--device-gray") { device_gray = true; for (int j = i; j + 1 < argc; j++) argv[j] = argv[j + 1]; argc--; i--; }
+    std::string roi;   // --roi <mask.pgm>, anywhere on the line
+    for (int i = 1; i < argc; i++)
+        if (std::string(argv[i]) == "--roi") {
+            if (i + 1 >= argc) { fprintf(stderr, "gf_replay: --roi needs a PGM file\n"); return 2; }
+            roi = argv[i + 1];
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2; i--;
+        }
+    if (!roi.empty() && argc >= 2 && std::string(argv[1]) == "--ranks") { fprintf(stderr, "gf_replay: --roi goes with the single-process forms (one mask, one camera)\n"); return 2; }
     if (argc >= 5 && std::string(argv[1]) == "--ranks") {
         const int world = atoi(argv[2]);
         if (world < 1 || world > 64) { fprintf(stderr, "gf_replay: --ranks must be in 1..64\n"); return 2; }
@@ -191,13 +217,13 @@ int main(int argc, char** argv) {
         return rc;
     }
     const bool from_bag = argc >= 4 && std::string(argv[2]) == "--bag";
-    if (argc < 3 || (from_bag && argc < 4)) { fprintf(stderr, "usage: %s <config.yaml> <dataset dir> [<vio.txt>]\n       %s [--device-gray] <config.yaml> --bag <recording.bag> [<vio.txt>]\n       %s --ranks N <config.yaml> <dataset dir> ...\n", argv[0], argv[0], argv[0]); return 2; }
+    if (argc < 3 || (from_bag && argc < 4)) { fprintf(stderr, "usage: %s [--roi <mask.pgm>] <config.yaml> <dataset dir> [<vio.txt>]\n       %s [--device-gray] [--roi <mask.pgm>] <config.yaml> --bag <recording.bag> [<vio.txt>]\n       %s --ranks N <config.yaml> <dataset dir> ...\n", argv[0], argv[0], argv[0]); return 2; }
     if (device_gray && !from_bag) { fprintf(stderr, "gf_replay: --device-gray goes with --bag (PGM frames are MONO8 already)\n"); return 2; }
     const int out_arg = from_bag ? 4 : 3;
     try {
         gf::Estimator estimator;
         const std::string out = argc > out_arg ? argv[out_arg] : yaml_string(argv[1], "output_path") + "/vio.txt";
-        replay_one(argv[1], from_bag ? argv[3] : argv[2], from_bag, out, estimator, false, device_gray);
+        replay_one(argv[1], from_bag ? argv[3] : argv[2], from_bag, out, estimator, false, device_gray, roi);
         if (estimator.cfg.gnss_enable) {   // gnss_result.txt of the reference carries the ECEF / ENU position; here as one closing line
             int gi[8]; double yaw, anc[3], ecef[3], enu[3];
             if (gf_estimator_get_gnss_state(estimator.handle(), gi, nullptr, nullptr, &yaw, anc, ecef, enu) == GF_OK) {
