@@ -1,4 +1,4 @@
-// gf_cvt.hip — cv_bridge::toCvCopy(img_msg, MONO8) on batches of u8 frames on the device (getImageFromMsg, rosNodeTest.cpp:238-254: the step of the reference's
+// gf_cvt.hip — cv_bridge::toCvCopy(img_msg, MONO8) on batches of colour, Bayer, YUV 4:2:2, 16-bit and u8 frames on the device (getImageFromMsg, rosNodeTest.cpp:238-254: the step of the reference's
 // node ahead of CLAHE and trackImage).  Kernels: gf_cvt_kernels.hpp; arithmetic and channel layouts: gf_pixfmt.hpp, shared with the host decoder.  Used by the
 // tracker (gf_tracker_cfg.pixel_format) and exported as its own C-ABI.
 #include <hip/hip_runtime.h>
@@ -12,8 +12,9 @@ namespace gf {
 
 // format, sizes and pitch of a conversion, or GF_ERR_INVALID
 static int cvt_check(size_t src_pitch, int format, int batch, int w, int h) {
-    if (!gfpix::valid(format)) return set_err(GF_ERR_INVALID, "cvt_gray: unknown pixel format %d (GF_PIX_MONO8 .. GF_PIX_BGRA8)", format);
+    if (!gfpix::valid(format)) return set_err(GF_ERR_INVALID, "cvt_gray: unknown pixel format %d (GF_PIX_MONO8 .. GF_PIX_BGRA8, GF_PIX_BAYER_RGGB8 .. GF_PIX_MONO16)", format);
     if (batch < 1 || w < 1 || h < 1) return set_err(GF_ERR_INVALID, "cvt_gray: %d frames of %dx%d (all must be >= 1)", batch, w, h);
+    if (w < gfpix::min_side(format) || h < gfpix::min_side(format)) return set_err(GF_ERR_INVALID, "cvt_gray: a Bayer frame of %dx%d has no interior pixel (width and height must be >= 3)", w, h);
     if ((long long)w * h > INT_MAX) return set_err(GF_ERR_INVALID, "cvt_gray: %dx%d frames have more than 2^31 - 1 pixels", w, h);
     if (src_pitch < (size_t)w * gfpix::channels(format)) return set_err(GF_ERR_INVALID, "cvt_gray: a pitch of %zu bytes is shorter than a row of %d pixels of %d bytes", src_pitch, w, gfpix::channels(format));
     return GF_OK;
@@ -32,11 +33,30 @@ template <int CH> static void cvt_launch_ch(const uint8_t* d_src, size_t src_pit
     else cvt_gray_byte_kernel<CH><<<dim3(blocks(w), gy), kThreads, 0, stream>>>(d_src, src_pitch, d_dst, batch, w, h, red_at);
 }
 
+// YUV 4:2:2 and MONO16 (two bytes per pixel) and Bayer: form and grid from gfcvt::raw_plan
+template <bool M16> static void cvt_launch_pair(const uint8_t* d_src, size_t src_pitch, int luma_at, uint8_t* d_dst, int batch, int w, int h, hipStream_t stream) {
+    using namespace gfcvt;
+    const RawPlan pl = raw_plan(false, d_src, src_pitch, d_dst, batch, w, h);
+    if (pl.form == 16) cvt_pair_vec_kernel<M16, 16><<<dim3(pl.gx, pl.gy), kThreads, 0, stream>>>(d_src, src_pitch, d_dst, batch, w, h, luma_at);
+    else if (pl.form == 4) cvt_pair_vec_kernel<M16, 4><<<dim3(pl.gx, pl.gy), kThreads, 0, stream>>>(d_src, src_pitch, d_dst, batch, w, h, luma_at);
+    else cvt_pair_byte_kernel<M16><<<dim3(pl.gx, pl.gy), kThreads, 0, stream>>>(d_src, src_pitch, d_dst, batch, w, h, luma_at);
+}
+static void cvt_launch_bayer(const uint8_t* d_src, size_t src_pitch, int format, uint8_t* d_dst, int batch, int w, int h, hipStream_t stream) {
+    using namespace gfcvt;
+    const RawPlan pl = raw_plan(true, d_src, src_pitch, d_dst, batch, w, h);
+    const int gf = gfpix::bayer_green_first(format), br = gfpix::bayer_blue_row0(format);
+    if (pl.form == 4) cvt_bayer_vec_kernel<<<dim3(pl.gx, pl.gy), kThreads, 0, stream>>>(d_src, src_pitch, d_dst, batch, w, h, gf, br);
+    else cvt_bayer_byte_kernel<<<dim3(pl.gx, pl.gy), kThreads, 0, stream>>>(d_src, src_pitch, d_dst, batch, w, h, gf, br);
+}
+
 // `batch` frames of h rows, src_pitch bytes apart, in `format` -> tight h x w u8 frames; the ranges must not overlap (the callers see to it)
 int cvt_launch(const uint8_t* d_src, size_t src_pitch, int format, uint8_t* d_dst, int batch, int w, int h, hipStream_t stream) {
     if (int rc = cvt_check(src_pitch, format, batch, w, h)) return rc;
     const int ch = gfpix::channels(format), red_at = gfpix::red_at(format);
-    if (ch == 1) cvt_launch_ch<1>(d_src, src_pitch, red_at, d_dst, batch, w, h, stream);
+    if (gfpix::is_bayer(format)) cvt_launch_bayer(d_src, src_pitch, format, d_dst, batch, w, h, stream);
+    else if (format == GF_PIX_MONO16) cvt_launch_pair<true>(d_src, src_pitch, 0, d_dst, batch, w, h, stream);
+    else if (ch == 2) cvt_launch_pair<false>(d_src, src_pitch, gfpix::luma_at(format), d_dst, batch, w, h, stream);
+    else if (ch == 1) cvt_launch_ch<1>(d_src, src_pitch, red_at, d_dst, batch, w, h, stream);
     else if (ch == 3) cvt_launch_ch<3>(d_src, src_pitch, red_at, d_dst, batch, w, h, stream);
     else cvt_launch_ch<4>(d_src, src_pitch, red_at, d_dst, batch, w, h, stream);
     HIPCHK(hipGetLastError());

@@ -1,12 +1,17 @@
-// gf_cvt_kernels.hpp — colour -> MONO8 on batches of u8 frames: cv_bridge::toCvCopy(msg, MONO8) of getImageFromMsg (rosNodeTest.cpp:238-254), the arithmetic
-// of gf_pixfmt.hpp.  Included by gf_cvt.hip only.
+// gf_cvt_kernels.hpp — colour and raw frames -> MONO8 on batches of u8 frames: cv_bridge::toCvCopy(msg, MONO8) of getImageFromMsg (rosNodeTest.cpp:238-254), the
+// arithmetic of gf_pixfmt.hpp.  Included by gf_cvt.hip (and by tests/native/raw_gray_host.hip, which walks the raw kernels' threads on the CPU).
 //
-// A pure stream: CH bytes in, one byte out per pixel, nothing is read twice.
+// Colour and MONO8, a pure stream: CH bytes in, one byte out per pixel, nothing is read twice.
 //   cvt_gray_vec_kernel<CH, NPX>  a lane takes NPX (4 or 16) consecutive pixels of a row: NPX * CH / 4 source dwords in, NPX / 4 dwords out; consecutive lanes take
 //                                 consecutive pieces of a row, so a wavefront reads one contiguous span and writes one.  Needs every row base of source and
 //                                 destination on a 4-byte boundary (both pointers, the pitch and the width multiples of 4) and NPX | width.
 //   cvt_gray_byte_kernel<CH>      one pixel per lane, byte loads and a byte store: any pointer, any pitch, any width.
+// YUV 4:2:2 and MONO16, the same stream with two bytes in (cvt_pair_*): NPX = 16 is two 16-byte loads and one 16-byte store per lane.
+// Bayer, a 3 x 3 stencil on bytes (cvt_bayer_*): see there.
 // blockIdx.y walks the frames (strided, for batches beyond the grid limit).
+//
+// The raw kernels keep their per-thread work in __host__ __device__ functions of (block, thread) that hold nothing but plain loads and stores, and the choice of
+// form and grid in raw_plan(): a host program can run every thread of a launch on heap buffers of exactly the frames' sizes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -60,6 +65,160 @@ __global__ __launch_bounds__(kThreads) void cvt_gray_byte_kernel(const uint8_t* 
         const uint8_t* s = src + ((size_t)b * h + y) * src_pitch + (size_t)x * CH;
         dst[((size_t)b * h + y) * w + x] = CH == 1 ? s[0] : gfpix::gray(s[red_at], s[1], s[2 - red_at]);
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- raw formats
+// which form a conversion of a raw format takes and the grid it is launched with (blocks of kThreads lanes)
+struct RawPlan { int form; unsigned gx, gy; };   // form: pixels a lane takes per row (16, 4 or 1)
+constexpr int kBayerBand = 16;   // rows of a Bayer band
+
+// the dispatch rule of cvt_launch_ch: whole dwords where every row base of source and destination lies on a 4-byte boundary
+inline bool raw_dwords(const void* src, size_t src_pitch, const void* dst, int w) { return !((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | src_pitch | (size_t)w) & 3); }
+inline unsigned raw_blocks(size_t per_row, size_t rows) { return (unsigned)((per_row * rows + kThreads - 1) / kThreads); }
+inline RawPlan raw_plan(bool bayer, const void* src, size_t src_pitch, const void* dst, int batch, int w, int h) {
+    const unsigned gy = (unsigned)(batch < 65535 ? batch : 65535);
+    const bool dwords = raw_dwords(src, src_pitch, dst, w);
+    if (bayer) {   // dwords of four columns walking bands of rows; below eight columns the one-pixel form
+        if (dwords && w >= 8) return {4, raw_blocks((size_t)w / 4, ((size_t)h + kBayerBand - 1) / kBayerBand), gy};
+        return {1, raw_blocks((size_t)w, (size_t)h), gy};
+    }
+    if (dwords && !(w & 15)) return {16, raw_blocks((size_t)w / 16, (size_t)h), gy};
+    if (dwords) return {4, raw_blocks((size_t)w / 4, (size_t)h), gy};
+    return {1, raw_blocks((size_t)w, (size_t)h), gy};
+}
+
+// ---- two-byte pixels.  M16: the pixel is a little-endian u16 -> gfpix::mono16_gray; else its byte luma_at (0 or 1) is the result.
+template <bool M16> GF_PIX_HD unsigned pair_gray(unsigned lo, unsigned hi, int luma_at) { return M16 ? gfpix::mono16_gray(lo | (hi << 8)) : (luma_at ? hi : lo); }
+
+template <bool M16, int NPX>
+GF_PIX_HD void cvt_pair_vec_thread(unsigned bx, unsigned tx, unsigned by, unsigned gy, const uint8_t* src, size_t src_pitch, uint8_t* dst, int batch, int w, int h, int luma_at) {
+    const int per_row = w / NPX;
+    const unsigned p = bx * kThreads + tx;   // piece of the frame; the host keeps w * h below 2^31
+    if (p >= (unsigned)per_row * (unsigned)h) return;
+    const int y = p / per_row, xp = p - y * per_row;
+    for (int b = by; b < batch; b += gy) {
+        const Dwords<NPX / 2> s = *reinterpret_cast<const Dwords<NPX / 2>*>(src + ((size_t)b * h + y) * src_pitch + (size_t)xp * (NPX * 2));
+        Dwords<NPX / 4> o;
+#pragma unroll
+        for (int q = 0; q < NPX / 4; q++) {
+            unsigned out = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const unsigned px = s.v[2 * q + (j >> 1)] >> (16 * (j & 1));   // pixel 4 q + j in the low 16 bits
+                out |= pair_gray<M16>(px & 255u, (px >> 8) & 255u, luma_at) << (8 * j);
+            }
+            o.v[q] = out;
+        }
+        *reinterpret_cast<Dwords<NPX / 4>*>(dst + ((size_t)b * h + y) * w + (size_t)xp * NPX) = o;
+    }
+}
+
+template <bool M16>
+GF_PIX_HD void cvt_pair_byte_thread(unsigned bx, unsigned tx, unsigned by, unsigned gy, const uint8_t* src, size_t src_pitch, uint8_t* dst, int batch, int w, int h, int luma_at) {
+    const unsigned p = bx * kThreads + tx;   // pixel of the frame
+    if (p >= (unsigned)w * (unsigned)h) return;
+    const int y = p / w, x = p - y * w;
+    for (int b = by; b < batch; b += gy) {
+        const uint8_t* s = src + ((size_t)b * h + y) * src_pitch + (size_t)x * 2;
+        dst[((size_t)b * h + y) * w + x] = (uint8_t)pair_gray<M16>(s[0], s[1], luma_at);
+    }
+}
+
+template <bool M16, int NPX>
+__global__ __launch_bounds__(kThreads) void cvt_pair_vec_kernel(const uint8_t* __restrict__ src, size_t src_pitch, uint8_t* __restrict__ dst, int batch, int w, int h, int luma_at) {
+    cvt_pair_vec_thread<M16, NPX>(blockIdx.x, threadIdx.x, blockIdx.y, gridDim.y, src, src_pitch, dst, batch, w, h, luma_at);
+}
+template <bool M16>
+__global__ __launch_bounds__(kThreads) void cvt_pair_byte_kernel(const uint8_t* __restrict__ src, size_t src_pitch, uint8_t* __restrict__ dst, int batch, int w, int h, int luma_at) {
+    cvt_pair_byte_thread<M16>(blockIdx.x, threadIdx.x, blockIdx.y, gridDim.y, src, src_pitch, dst, batch, w, h, luma_at);
+}
+
+// ---- Bayer: out(y, x) = f(clamp(y, 1, h - 2), clamp(x, 1, w - 2)), f the bilinear demosaic fused with the luma sum (gfpix::bayer_rb / bayer_g).
+//   cvt_bayer_vec_kernel   a lane owns the four output columns of one dword (x0 = a multiple of 4) and walks a band of kBayerBand rows; consecutive lanes own
+//                          consecutive dwords, so a wavefront reads and writes contiguous spans.  The three source rows of the stencil stay in registers as a
+//                          sliding window: every source row is loaded once per band (its own dword, and the byte to its left and the byte to its right, which
+//                          are the neighbouring lanes' bytes and come from the cache), bands overlap by one row above and one below.  The column parities of
+//                          the four pixels are compile-time; the walk goes two rows at a time from a row whose even columns are green, so each of the 2 x 2
+//                          site kinds is straight-line code, and the pattern enters as two kernel-argument bits that choose the row to start on and the two
+//                          weights.  The border clamp is on the output: the lane of column 0 / w - 1 repeats its neighbouring pixel, row 1 / h - 2 is stored
+//                          to row 0 / h - 1 as well.  Rows and columns that are loaded for a window position nothing is computed from are clamped into the
+//                          frame, so no address outside the frame is ever formed.  Needs what the dword forms above need, and w >= 8.
+//   cvt_bayer_byte_kernel  one pixel per lane, nine byte loads: any pointer, pitch and width.
+struct BayerRow { unsigned v[6]; };   // columns x0 - 1 .. x0 + 4 of a source row
+
+GF_PIX_HD BayerRow bayer_row_load(const uint8_t* frame, size_t src_pitch, int y, int x0, int w, int h) {
+    const uint8_t* row = frame + (size_t)(y < 0 ? 0 : y > h - 1 ? h - 1 : y) * src_pitch;
+    const uint32_t d = *reinterpret_cast<const uint32_t*>(row + x0);
+    BayerRow r;
+    r.v[0] = row[x0 > 0 ? x0 - 1 : 0];
+    r.v[1] = d & 255u; r.v[2] = (d >> 8) & 255u; r.v[3] = (d >> 16) & 255u; r.v[4] = d >> 24;
+    r.v[5] = row[x0 + 4 < w ? x0 + 4 : w - 1];
+    return r;
+}
+
+// the four pixels of a row between its neighbours n and s.  EVEN_GREEN: the even columns of this row are green.  k_row: the weight of the row's other colour
+// (red or blue), k_other: of the remaining one.
+template <bool EVEN_GREEN> GF_PIX_HD uint32_t bayer_row4(const BayerRow& n, const BayerRow& c, const BayerRow& s, unsigned k_row, unsigned k_other) {
+    uint32_t out = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int i = j + 1;
+        const unsigned ns = n.v[i] + s.v[i], we = c.v[i - 1] + c.v[i + 1];
+        unsigned g;
+        if (((j & 1) == 0) == EVEN_GREEN) g = gfpix::bayer_g(k_row, k_other, c.v[i], we, ns);
+        else g = gfpix::bayer_rb(k_row, k_other, c.v[i], we + ns, n.v[i - 1] + n.v[i + 1] + s.v[i - 1] + s.v[i + 1]);
+        out |= g << (8 * j);
+    }
+    return out;
+}
+
+// stores the computed row yc (1 .. h - 2) of a band [r0, r1) wherever the band holds an output row that takes its value
+GF_PIX_HD void bayer_row_store(uint8_t* frame, uint32_t out, int yc, int x0, int w, int h, int r0, int r1) {
+    if (x0 == 0) out = (out & 0xffffff00u) | ((out >> 8) & 255u);                   // column 0 takes column 1
+    if (x0 + 4 == w) out = (out & 0x00ffffffu) | ((out << 8) & 0xff000000u);        // column w - 1 takes column w - 2
+    if (yc >= r0 && yc < r1) *reinterpret_cast<uint32_t*>(frame + (size_t)yc * w + x0) = out;
+    if (yc == 1 && r0 == 0) *reinterpret_cast<uint32_t*>(frame + x0) = out;
+    if (yc == h - 2 && r1 == h) *reinterpret_cast<uint32_t*>(frame + (size_t)(h - 1) * w + x0) = out;
+}
+
+GF_PIX_HD void cvt_bayer_vec_thread(unsigned bx, unsigned tx, unsigned by, unsigned gy, const uint8_t* src, size_t src_pitch, uint8_t* dst, int batch, int w, int h, int green_first, int blue_row0) {
+    const int cols = w / 4, bands = (h + kBayerBand - 1) / kBayerBand;
+    const unsigned p = bx * kThreads + tx;   // (band, dword column) of the frame
+    if (p >= (unsigned)cols * (unsigned)bands) return;
+    const int band = p / cols, x0 = 4 * (int)(p - (unsigned)band * cols);
+    const int r0 = band * kBayerBand, r1 = r0 + kBayerBand < h ? r0 + kBayerBand : h;
+    const int c0 = gfpix::bayer_clamp(r0, h), c1 = gfpix::bayer_clamp(r1 - 1, h);   // the computed rows the band's output rows stand for
+    const int e0 = c0 - (((c0 ^ green_first) & 1) ? 0 : 1);                           // the walk starts on a row whose even columns are green (gfpix::bayer_is_green at x = 0): c0 or the row above it
+    // weights of the even-green rows' other colour and of the rows between them
+    const unsigned k_a = gfpix::bayer_row_is_blue(blue_row0, e0) ? 1868u : 4899u, k_b = 4899u + 1868u - k_a;
+    for (int b = by; b < batch; b += gy) {
+        const uint8_t* sf = src + (size_t)b * h * src_pitch;
+        uint8_t* df = dst + (size_t)b * h * w;
+        BayerRow r_m = bayer_row_load(sf, src_pitch, e0 - 1, x0, w, h), r_0 = bayer_row_load(sf, src_pitch, e0, x0, w, h);
+        for (int e = e0; e <= c1; e += 2) {
+            const BayerRow r_1 = bayer_row_load(sf, src_pitch, e + 1, x0, w, h), r_2 = bayer_row_load(sf, src_pitch, e + 2, x0, w, h);
+            if (e >= c0) bayer_row_store(df, bayer_row4<true>(r_m, r_0, r_1, k_a, k_b), e, x0, w, h, r0, r1);
+            if (e + 1 <= c1) bayer_row_store(df, bayer_row4<false>(r_0, r_1, r_2, k_b, k_a), e + 1, x0, w, h, r0, r1);
+            r_m = r_1; r_0 = r_2;
+        }
+    }
+}
+
+GF_PIX_HD void cvt_bayer_byte_thread(unsigned bx, unsigned tx, unsigned by, unsigned gy, const uint8_t* src, size_t src_pitch, uint8_t* dst, int batch, int w, int h, int green_first, int blue_row0) {
+    const unsigned p = bx * kThreads + tx;   // pixel of the frame
+    if (p >= (unsigned)w * (unsigned)h) return;
+    const int y = p / w, x = p - y * w, yc = gfpix::bayer_clamp(y, h), xc = gfpix::bayer_clamp(x, w);
+    for (int b = by; b < batch; b += gy) {
+        const uint8_t* c = src + ((size_t)b * h + yc) * src_pitch;
+        dst[((size_t)b * h + y) * w + x] = gfpix::bayer_gray(green_first, blue_row0, yc, xc, c - src_pitch, c, c + src_pitch);
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void cvt_bayer_vec_kernel(const uint8_t* __restrict__ src, size_t src_pitch, uint8_t* __restrict__ dst, int batch, int w, int h, int green_first, int blue_row0) {
+    cvt_bayer_vec_thread(blockIdx.x, threadIdx.x, blockIdx.y, gridDim.y, src, src_pitch, dst, batch, w, h, green_first, blue_row0);
+}
+__global__ __launch_bounds__(kThreads) void cvt_bayer_byte_kernel(const uint8_t* __restrict__ src, size_t src_pitch, uint8_t* __restrict__ dst, int batch, int w, int h, int green_first, int blue_row0) {
+    cvt_bayer_byte_thread(blockIdx.x, threadIdx.x, blockIdx.y, gridDim.y, src, src_pitch, dst, batch, w, h, green_first, blue_row0);
 }
 
 }  // namespace gfcvt

@@ -160,7 +160,7 @@ struct gf_tracker {
     bool profiling = false;
     // Members are destroyed in reverse order: the pool (last member) is joined before anything its threads could touch goes, the buffers go before the events and streams.
     Stream stream, copy_stream;   // copy_stream, ev_copy: gf_tracker_prefetch_batch (created on first use)
-    Event ev[9];   // ev[7]: end of the equalisation (cfg.equalize); ev[8]: end of the colour conversion (cfg.pixel_format)
+    Event ev[9];   // ev[7]: end of the equalisation (cfg.equalize); ev[8]: end of the colour / raw conversion (cfg.pixel_format)
     int ch = 1;    // bytes per pixel of the frames the handle is given (cfg.pixel_format); d_raw / d_raw2 hold them in that format
     Event ev_copy[2];
     gf_tracker_stats stats{};
@@ -168,7 +168,7 @@ struct gf_tracker {
     // device
     DevBuf<uint8_t> d_img, d_raw, d_mask, d_status, d_fwd_status, d_seqmask;
     DevBuf<uint8_t> d_eq, d_eq_lut;   // cfg.equalize: the equalised frames the pyramid reads, and the CLAHE tile LUTs
-    DevBuf<uint8_t> d_cvt;            // cfg.pixel_format: the MONO8 frames converted from the caller's colour frames, which equalisation and pyramid read
+    DevBuf<uint8_t> d_cvt;            // cfg.pixel_format: the MONO8 frames converted from the caller's colour or raw frames, which equalisation and pyramid read
     DevBuf<int> d_npts, d_cand_count, d_want, d_ncenters, d_out_n;
     // the call's sequence list as the kernels read it (cur_of, gf_lk_kernels.hpp): written into the page-locked h_cur, which the pyramid kernels read over the bus
     // (they are launched before anything is copied), and carried to d_cur for LK by the copy list in front of it
@@ -420,7 +420,7 @@ static int roi_upload(gf_tracker* h, int seq) {   // the host copy of one sequen
     return GF_OK;
 }
 
-// The row step of host frames on a handle that takes colour: refused before anything is copied.  (A MONO8 handle hands its stride to the copy as it always did.)
+// The row step of host frames on a handle that takes colour or raw frames: refused before anything is copied.  (A MONO8 handle hands its stride to the copy as it always did.)
 static int check_stride(gf_tracker* h, int stride) {
     if (h->cfg.pixel_format && (stride < 0 || (size_t)stride < (size_t)h->cfg.width * h->ch))
         return set_err(GF_ERR_INVALID, "a stride of %d bytes is shorter than a row of %d pixels of %d bytes (gf_tracker_cfg.pixel_format %d)", stride, h->cfg.width, h->ch, h->cfg.pixel_format);
@@ -475,7 +475,7 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
     if (!over_bus) HIPCHK(hipMemcpyAsync(h->d_cur.p, h->h_cur.p, (size_t)N * sizeof(int), hipMemcpyHostToDevice, h->stream));
     const int* cur_of = over_bus ? h->h_cur.hd : h->d_cur.p;
     if (prof) HIPCHK(hipEventRecord(h->ev[0], h->stream));
-    if (h->cfg.pixel_format) {   // rosNodeTest.cpp:238-254: toCvCopy(msg, MONO8) ahead of CLAHE and trackImage; d_gray holds tight colour frames by list position, never written
+    if (h->cfg.pixel_format) {   // rosNodeTest.cpp:238-254: toCvCopy(msg, MONO8) ahead of CLAHE and trackImage; d_gray holds tight frames of the handle's format by list position, never written
         if (int rc = cvt_launch(d_gray, (size_t)W * h->ch, h->cfg.pixel_format, h->d_cvt.p, N, W, H, h->stream)) return rc;
         d_gray = h->d_cvt.p;
         if (prof) HIPCHK(hipEventRecord(h->ev[8], h->stream));
@@ -737,7 +737,7 @@ int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out) {
     if (cfg->width < 32 || cfg->height < 32 || cfg->width % 4 || cfg->batch < 1 || cfg->max_cnt < 1 || cfg->min_dist < 0 || cfg->min_dist > gf::kMaxRadius)
         return gf::set_err(GF_ERR_INVALID, "unsupported tracker configuration (width %% 4 == 0, width/height >= 32, 0 <= min_dist <= %d)", gf::kMaxRadius);
     if (cfg->equalize != 0 && cfg->equalize != 1) return gf::set_err(GF_ERR_INVALID, "gf_tracker_cfg.equalize must be 0 or 1, got %d", cfg->equalize);
-    if (!gfpix::valid(cfg->pixel_format)) return gf::set_err(GF_ERR_INVALID, "gf_tracker_cfg.pixel_format must be one of GF_PIX_MONO8 (0) .. GF_PIX_BGRA8 (4), got %d", cfg->pixel_format);
+    if (!gfpix::valid(cfg->pixel_format)) return gf::set_err(GF_ERR_INVALID, "gf_tracker_cfg.pixel_format must be one of GF_PIX_MONO8 (0) .. GF_PIX_BGRA8 (4) or GF_PIX_BAYER_RGGB8 (8) .. GF_PIX_MONO16 (14), got %d", cfg->pixel_format);
     if (int rc = gf::require_device()) return rc;
     std::unique_ptr<gf_tracker> h(new gf_tracker());
     h->cfg = *cfg;

@@ -25,6 +25,25 @@ class TrackerCfg(C.Structure):
 PIX_MONO8, PIX_RGB8, PIX_BGR8, PIX_RGBA8, PIX_BGRA8 = range(5)
 PIX_CHANNELS = (1, 3, 3, 4, 4)
 PIX_OF_ENCODING = {"mono8": PIX_MONO8, "8UC1": PIX_MONO8, "rgb8": PIX_RGB8, "bgr8": PIX_BGR8, "rgba8": PIX_RGBA8, "bgra8": PIX_BGRA8}
+# the raw formats (cameras that do not debayer on board): Bayer mosaics are [h, w] u8 frames like MONO8; YUV 4:2:2 and MONO16 are [h, w, 2] u8 (MONO16: the
+# little-endian bytes of the pixel, `a.astype("<u2").view(np.uint8).reshape(h, w, 2)`)
+PIX_BAYER_RGGB8, PIX_BAYER_BGGR8, PIX_BAYER_GBRG8, PIX_BAYER_GRBG8, PIX_YUV422_UYVY, PIX_YUV422_YUY2, PIX_MONO16 = range(8, 15)
+PIX_RAW = tuple(range(8, 15))
+PIX_RAW_BYTES = {PIX_BAYER_RGGB8: 1, PIX_BAYER_BGGR8: 1, PIX_BAYER_GBRG8: 1, PIX_BAYER_GRBG8: 1, PIX_YUV422_UYVY: 2, PIX_YUV422_YUY2: 2, PIX_MONO16: 2}
+PIX_RAW_OF_ENCODING = {"bayer_rggb8": PIX_BAYER_RGGB8, "bayer_bggr8": PIX_BAYER_BGGR8, "bayer_gbrg8": PIX_BAYER_GBRG8, "bayer_grbg8": PIX_BAYER_GRBG8,
+                       "yuv422": PIX_YUV422_UYVY, "yuv422_yuy2": PIX_YUV422_YUY2, "mono16": PIX_MONO16}
+
+
+def pix_bytes(pixel_format):
+    """bytes per pixel of a GF_PIX_* value, None if it is no format"""
+    if 0 <= pixel_format < len(PIX_CHANNELS):
+        return PIX_CHANNELS[pixel_format]
+    return PIX_RAW_BYTES.get(pixel_format)
+
+
+def pix_of_encoding(encoding):
+    """GF_PIX_* of a sensor_msgs/Image encoding of an image topic, None if the node's conversion to MONO8 is not built for it"""
+    return PIX_OF_ENCODING.get(encoding, PIX_RAW_OF_ENCODING.get(encoding))
 
 
 class FeatureObs(C.Structure):
@@ -98,7 +117,7 @@ class FeatureTracker:
         self.h = C.c_void_p()
         _chk(lib().gf_tracker_create(C.byref(self.cfg), C.byref(self.h)))
         self.cap = 4 * ((self.cfg.max_cnt + 3) // 4)
-        self.channels = PIX_CHANNELS[self.cfg.pixel_format]   # a colour handle takes [height, width, channels] u8 frames wherever a MONO8 handle takes [height, width]
+        self.channels = pix_bytes(self.cfg.pixel_format)   # a handle of a format with more than one byte per pixel takes [height, width, bytes] u8 frames wherever a MONO8 handle takes [height, width]
         self.row_bytes = self.cfg.width * self.channels
 
     def close(self):
@@ -318,31 +337,35 @@ def clahe_device(d_src, d_dst, batch, width, height, clip_limit=40.0, tiles=(8, 
 
 
 def _cvt_rows(frames, pixel_format):
-    """[h, w(, ch)] or [batch, h, w(, ch)] u8 frames of one format as (array, batch, h, w, row pitch in bytes): rows may be padded (a view of a wider array), the
-    frames of a batch lie h rows apart"""
-    if not 0 <= pixel_format < len(PIX_CHANNELS):
-        return np.ascontiguousarray(frames, np.uint8), 1, 1, 1, 1   # the library's to refuse
-    ch = PIX_CHANNELS[pixel_format]
+    """[h, w(, ch)] or [batch, h, w(, ch)] u8 frames of one format as (array, batch, h, w, row pitch in bytes, whether it was one frame without a batch axis):
+    rows may be padded (a view of a wider array), the frames of a batch lie h rows apart"""
+    ch = pix_bytes(pixel_format)
+    if ch is None:
+        return np.ascontiguousarray(frames, np.uint8), 1, 1, 1, 1, False   # the library's to refuse
     a = np.asarray(frames)
+    if pixel_format == PIX_MONO16 and a.dtype == np.uint16:      # [h, w] / [batch, h, w] u16 pixels: their little-endian bytes
+        a = np.ascontiguousarray(a, "<u2").view(np.uint8).reshape(a.shape + (2,))
     nd = 2 if ch == 1 else 3
     if a.dtype != np.uint8 or a.ndim not in (nd, nd + 1) or (ch > 1 and a.shape[-1] != ch):
         raise ValueError("cvt_gray: frames must be u8 [h, w%s] or [batch, h, w%s]" % ((", %d" % ch,) * 2 if ch > 1 else ("", "")))
-    if a.ndim == nd:
+    single = a.ndim == nd
+    if single:
         a = a[None]
     h, w = a.shape[1], a.shape[2]
     inner = (ch, 1) if ch > 1 else (1,)
     if a.strides[2:] != inner or a.strides[0] != h * a.strides[1] or a.strides[1] < w * ch:
         a = np.ascontiguousarray(a)
-    return a, a.shape[0], h, w, a.strides[1]
+    return a, a.shape[0], h, w, a.strides[1], single
 
 
 def cvt_gray(frames, pixel_format):
     """cv_bridge::toCvCopy(msg, MONO8) (rosNodeTest.cpp:238-254) on host frames of format PIX_* on the device (gf_cvt_gray_batch): [h, w, ch] or [batch, h, w, ch]
-    u8 ([h, w] / [batch, h, w] for PIX_MONO8); a view with padded rows is read through its pitch.  Returns new tight [h, w] / [batch, h, w] frames."""
-    a, b, h, w, pitch = _cvt_rows(frames, pixel_format)
+    u8 ([h, w] / [batch, h, w] for PIX_MONO8 and the Bayer formats; PIX_MONO16 also as u16 [h, w] / [batch, h, w]); a view with padded rows is read through its
+    pitch.  Returns new tight [h, w] / [batch, h, w] frames."""
+    a, b, h, w, pitch, single = _cvt_rows(frames, pixel_format)
     out = np.empty((b, h, w), np.uint8)
     _chk(lib().gf_cvt_gray_batch(C.c_void_p(a.ctypes.data), C.c_size_t(pitch), int(pixel_format), _p(out, C.c_uint8), b, w, h))
-    return out[0] if np.asarray(frames).ndim == (2 if PIX_CHANNELS[pixel_format] == 1 else 3) else out
+    return out[0] if single else out
 
 
 def cvt_gray_device(d_src, src_pitch, pixel_format, d_dst, batch, width, height, stream=0):

@@ -133,7 +133,7 @@ class Estimator {
         check(gf_estimator_input_feature(h_, t, obs.data(), (int)obs.size()));
         refresh();
     }
-    // needs cfg.with_tracker = 1 and cfg.tracker filled before setParameter(); a colour image (GrayImage::pixel_format, its stride the row step in bytes) needs
+    // needs cfg.with_tracker = 1 and cfg.tracker filled before setParameter(); a colour or raw (Bayer, YUV 4:2:2, MONO16) image (GrayImage::pixel_format, its stride the row step in bytes) needs
     // cfg.tracker.pixel_format set to its format: the tracker then converts on the device what getImageFromMsg converts on the host (rosNodeTest.cpp:238-254)
     void inputImage(double t, const GrayImage& _img, const DepthImage& _img1 = DepthImage()) {
         need();

@@ -30,8 +30,9 @@ namespace gf {
 
 template <class T> struct ImageView {  // stands in for cv::Mat when OpenCV is absent
     const T* data = nullptr; int rows = 0, cols = 0, stride = 0;  // stride in elements
-    // GF_PIX_* of a u8 image (rosNodeTest.cpp:238-254, what getImageFromMsg accepts): a colour image holds cols x 3 or 4 bytes per row, `stride` is its row step
-    // in bytes, and the tracker converts it to MONO8 on the device as the node's cv_bridge::toCvCopy(msg, MONO8) does on the host
+    // GF_PIX_* of a u8 image (rosNodeTest.cpp:238-254, what getImageFromMsg accepts): a colour image holds cols x 3 or 4 bytes per row, a YUV 4:2:2 or MONO16
+    // (little-endian) image cols x 2, a Bayer mosaic cols; `stride` is its row step in bytes, and the tracker converts it to MONO8 on the device as the node's
+    // cv_bridge::toCvCopy(msg, MONO8) does on the host
     int pixel_format = GF_PIX_MONO8;
     bool empty() const { return data == nullptr; }
 };

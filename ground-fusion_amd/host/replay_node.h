@@ -217,10 +217,10 @@ template <class Est> class ReplayNode {
         const RosImage im = ros_image(d, len);
         if (depth) { ros_image_to_mono16(im, depth16_); depth_.resize(depth16_.size() * 2); memcpy(depth_.data(), depth16_.data(), depth_.size()); dw_ = (int)im.width; dh_ = (int)im.height; }
         else if (device_gray) {   // the rows as the message carries them (copied: the payload is the bag's until the next message is read)
-            const int fmt = gfpix::format_of_encoding(im.encoding.c_str());
-            if (fmt < 0) throw BagError("bag: image encoding '" + im.encoding + "' -> MONO8 is not built (mono8, 8UC1, rgb8, bgr8, rgba8, bgra8 are)");
-            if ((uint64_t)im.width * gfpix::channels(fmt) > im.step) throw BagError("bag: Image.step shorter than a row");
+            const int fmt = ros_image_format(im);
             gray_.assign(im.data, im.data + (size_t)im.step * im.height);
+            if (fmt == GF_PIX_MONO16 && im.is_bigendian)   // the tracker takes little-endian pixels: swapped in the copy that is made anyway
+                for (uint32_t y = 0; y < im.height; y++) { uint8_t* r = gray_.data() + (size_t)y * im.step; for (uint32_t x = 0; x < im.width; x++) std::swap(r[2 * x], r[2 * x + 1]); }
             gw_ = (int)im.width; gh_ = (int)im.height; gstep_ = (int)im.step; gfmt_ = fmt;
         }
         else { ros_image_to_mono8(im, gray_); gw_ = (int)im.width; gh_ = (int)im.height; gstep_ = gw_; gfmt_ = GF_PIX_MONO8; }

@@ -334,18 +334,32 @@ inline RosImage ros_image(const uint8_t* d, size_t n) {
     return m;
 }
 // getImageFromMsg (rosNodeTest.cpp:238-263): 8UC1 is relabelled mono8, everything else goes through cv_bridge::toCvCopy(msg, MONO8).  EQUALIZE (CLAHE) is outside the built path.
+// The format of an image message, refused where the node's conversion is not built or the message cannot hold its rows.
+inline int ros_image_format(const RosImage& m) {
+    const int fmt = gfpix::format_of_encoding(m.encoding.c_str());
+    if (fmt < 0) throw BagError("bag: image encoding '" + m.encoding + "' -> MONO8 is not built (" GF_PIX_ENCODINGS " are)");
+    if ((uint64_t)m.width * gfpix::channels(fmt) > m.step) throw BagError("bag: Image.step shorter than a row");
+    if (gfpix::is_bayer(fmt) && (m.width < 3 || m.height < 3)) throw BagError("bag: a '" + m.encoding + "' image smaller than 3 x 3 has no interior pixel to demosaic");
+    return fmt;
+}
+// Every formula is the one the device conversion uses too (csrc/gf_pixfmt.hpp).
 inline void ros_image_to_mono8(const RosImage& m, std::vector<uint8_t>& out) {
-    const std::string& e = m.encoding;
-    const int fmt = gfpix::format_of_encoding(e.c_str());
-    if (fmt < 0) throw BagError("bag: image encoding '" + e + "' -> MONO8 is not built (mono8, 8UC1, rgb8, bgr8, rgba8, bgra8 are)");
+    const int fmt = ros_image_format(m);
     const int ch = gfpix::channels(fmt), r = gfpix::red_at(fmt), g = 1, b = gfpix::blue_at(fmt);
-    if ((uint64_t)m.width * ch > m.step) throw BagError("bag: Image.step shorter than a row");
+    const int w = (int)m.width, h = (int)m.height;
     out.resize((size_t)m.width * m.height);
-    for (uint32_t y = 0; y < m.height; y++) {
+    for (int y = 0; y < h; y++) {
         const uint8_t* s = m.data + (size_t)y * m.step;
         uint8_t* o = out.data() + (size_t)y * m.width;
-        if (ch == 1) memcpy(o, s, m.width);
-        else for (uint32_t x = 0; x < m.width; x++, s += ch) o[x] = gfpix::gray(s[r], s[g], s[b]);   // the formula the device conversion uses too (csrc/gf_pixfmt.hpp)
+        if (gfpix::is_bayer(fmt)) {   // border pixels stand for the nearest interior pixel
+            const int gf = gfpix::bayer_green_first(fmt), br = gfpix::bayer_blue_row0(fmt), yc = gfpix::bayer_clamp(y, h);
+            const uint8_t* c = m.data + (size_t)yc * m.step;
+            for (int x = 0; x < w; x++) o[x] = gfpix::bayer_gray(gf, br, yc, gfpix::bayer_clamp(x, w), c - m.step, c, c + m.step);
+        }
+        else if (fmt == GF_PIX_MONO16) for (int x = 0; x < w; x++) o[x] = gfpix::mono16_gray(m.is_bigendian ? (unsigned)((s[2 * x] << 8) | s[2 * x + 1]) : (unsigned)(s[2 * x] | (s[2 * x + 1] << 8)));
+        else if (ch == 2) { const int l = gfpix::luma_at(fmt); for (int x = 0; x < w; x++) o[x] = s[2 * x + l]; }
+        else if (ch == 1) memcpy(o, s, m.width);
+        else for (uint32_t x = 0; x < m.width; x++, s += ch) o[x] = gfpix::gray(s[r], s[g], s[b]);
     }
 }
 // getDepthImageFromMsg (rosNodeTest.cpp:265-286): the payload is relabelled MONO16 whatever the message says: two bytes per pixel, in the message's byte order

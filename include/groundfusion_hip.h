@@ -36,8 +36,11 @@ int gf_set_device(int device);
 typedef struct gf_tracker gf_tracker;
 
 /* Pixel formats of the frames a tracker handle is given and of gf_cvt_gray_batch*: what getImageFromMsg (rosNodeTest.cpp:238-254) accepts before
- * cv_bridge::toCvCopy(msg, MONO8) -- mono8 / 8UC1, rgb8, bgr8, rgba8, bgra8 -- with 1, 3, 3, 4, 4 bytes per pixel. */
-enum { GF_PIX_MONO8 = 0, GF_PIX_RGB8, GF_PIX_BGR8, GF_PIX_RGBA8, GF_PIX_BGRA8 };
+ * cv_bridge::toCvCopy(msg, MONO8) -- mono8 / 8UC1, rgb8, bgr8, rgba8, bgra8 -- with 1, 3, 3, 4, 4 bytes per pixel, and the raw formats of cameras that do not
+ * debayer on board: bayer_rggb8 / _bggr8 / _gbrg8 / _grbg8 (1 byte per pixel; the four letters are the colours of pixels (0,0), (0,1), (1,0), (1,1); at least
+ * 3 x 3), yuv422 (UYVY) and yuv422_yuy2 (2 bytes per pixel), mono16 of an image topic (2 bytes per pixel, little-endian).  5, 6 and 7 are no formats. */
+enum { GF_PIX_MONO8 = 0, GF_PIX_RGB8, GF_PIX_BGR8, GF_PIX_RGBA8, GF_PIX_BGRA8,
+       GF_PIX_BAYER_RGGB8 = 8, GF_PIX_BAYER_BGGR8, GF_PIX_BAYER_GBRG8, GF_PIX_BAYER_GRBG8, GF_PIX_YUV422_UYVY, GF_PIX_YUV422_YUY2, GF_PIX_MONO16 };
 
 typedef struct gf_tracker_cfg {
     int width, height;  /* ROW/COL, parameters.cpp:138ff (image_height/image_width) */
@@ -55,10 +58,12 @@ typedef struct gf_tracker_cfg {
      * the handle as it always was -- no further buffer, no further launch.  A colour format: every entry point that takes frames (gf_tracker_track, _track_batch,
      * _track_some, _prefetch_batch, _prefetch_some / _track_prefetched, _track_batch_device, _track_some_device) reads them in that format and the handle converts
      * them to MONO8 on the device, into a buffer of its own, ahead of the equalisation and the pyramid: (R 4899 + G 9617 + B 1868 + 2^13) >> 14, alpha ignored,
-     * the bits of OpenCV 4.2's cvtColor.  The caller's frames are never written.  Host entry points: `stride` is bytes per row and must be >= width x channels;
-     * the staged path copies the colour frame under the previous frame's kernels and converts on the tracking stream once the copy has landed.  Device entry
-     * points: the frames are tight height x width x channels, back to back in list order.  One handle has one format: a fleet of cameras with mixed encodings
-     * uses one handle per encoding.  Anything outside GF_PIX_MONO8 .. GF_PIX_BGRA8 is refused by gf_tracker_create. */
+     * the bits of OpenCV 4.2's cvtColor.  A raw format (GF_PIX_BAYER_*, GF_PIX_YUV422_*, GF_PIX_MONO16) is converted at the same place: Bayer by the bilinear
+     * demosaic fused with that luma sum (cvtColor(COLOR_Bayer??2GRAY), generic loop), YUV 4:2:2 by taking the luma bytes, MONO16 by (v + 128) / 257 on
+     * little-endian pixels.  The caller's frames are never written.  Host entry points: `stride` is bytes per row and must be >= width x bytes per pixel;
+     * the staged path copies the frame as it is under the previous frame's kernels and converts on the tracking stream once the copy has landed.  Device entry
+     * points: the frames are tight height x width x bytes per pixel, back to back in list order.  One handle has one format: a fleet of cameras with mixed
+     * encodings uses one handle per encoding.  Anything outside GF_PIX_MONO8 .. GF_PIX_BGRA8 and GF_PIX_BAYER_RGGB8 .. GF_PIX_MONO16 is refused by gf_tracker_create. */
     int pixel_format;
 } gf_tracker_cfg;
 
@@ -93,7 +98,7 @@ typedef struct gf_tracker_stats {
      * pyr_head: levels 0 + 1 in one kernel; pyr_level0_vec16 / pyr_level0_dword: level 0 alone in 16- / 4-byte pieces; pyr_down_tail: levels 2 .. 3 in one kernel;
      * pyr_down_pad4: one level >= 1 in four-pixel pieces; pyr_down_bytes: one level >= 1 one byte per thread */
     long long pyr_head, pyr_level0_vec16, pyr_level0_dword, pyr_down_tail, pyr_down_pad4, pyr_down_bytes;
-    double ms_convert;           /* the colour -> MONO8 kernel of gf_tracker_cfg.pixel_format (hipEvents, like ms_equalize; part of ms_total_gpu); 0 on a MONO8 handle */
+    double ms_convert;           /* the colour / raw -> MONO8 kernel of gf_tracker_cfg.pixel_format (hipEvents, like ms_equalize; part of ms_total_gpu); 0 on a MONO8 handle */
     long long sequence_frames;   /* listed sequences summed over the calls (`frames` counts the calls): frames x batch for the lock-step entry points; stays the last member */
 } gf_tracker_stats;
 
@@ -188,12 +193,14 @@ int gf_clahe_batch_device(const void* d_src, void* d_dst, int batch, int width, 
 /* The same on host frames (copies in, equalises, copies out; synchronous): the building block the parity tests call.  src == dst is allowed. */
 int gf_clahe_batch(const uint8_t* src, uint8_t* dst, int batch, int width, int height, double clip_limit, int tiles_x, int tiles_y);
 /* Replaces `cv_bridge::toCvCopy(img_msg, sensor_msgs::image_encodings::MONO8)` of getImageFromMsg (rosNodeTest.cpp:238-254) on frames that are on the device:
- * `batch` frames of `height` rows, `src_pitch` bytes from row to row (>= width x channels; frame b starts at d_src + b x height x src_pitch), `format` one of
- * GF_PIX_* -> `batch` tight height x width u8 frames at d_dst.  Colour: (R 4899 + G 9617 + B 1868 + 2^13) >> 14, alpha ignored (OpenCV 4.2 cvtColor);
- * GF_PIX_MONO8: a copy that removes the pitch.  Any byte alignment of d_src, d_dst and src_pitch is accepted (rows whose bases, pitch and width are multiples
- * of 4 move as whole dwords).  d_src is never written; source and destination ranges that overlap are refused (GF_ERR_INVALID; GF_PIX_MONO8 alone may name the
- * same tight frames as both), as are an unknown format, src_pitch < width x channels and sizes < 1.  Asynchronous on `stream` (a hipStream_t, NULL = the null
- * stream); device pointers of the current device. */
+ * `batch` frames of `height` rows, `src_pitch` bytes from row to row (>= width x bytes per pixel; frame b starts at d_src + b x height x src_pitch), `format` one
+ * of GF_PIX_* -> `batch` tight height x width u8 frames at d_dst.  Colour: (R 4899 + G 9617 + B 1868 + 2^13) >> 14, alpha ignored (OpenCV 4.2 cvtColor);
+ * GF_PIX_MONO8: a copy that removes the pitch; GF_PIX_BAYER_*: the bilinear demosaic fused with the same luma sum, border pixels equal to the nearest interior
+ * pixel (cvtColor(COLOR_Bayer??2GRAY), generic loop; width and height >= 3); GF_PIX_YUV422_*: the luma byte of every pixel; GF_PIX_MONO16: (v + 128) / 257 on
+ * little-endian pixels.  Any byte alignment of d_src, d_dst and src_pitch is accepted (rows whose bases, pitch and width are multiples of 4 move as whole
+ * dwords).  d_src is never written; source and destination ranges that overlap are refused (GF_ERR_INVALID; GF_PIX_MONO8 alone may name the same tight frames
+ * as both), as are an unknown format, src_pitch < width x bytes per pixel and sizes < 1.  Asynchronous on `stream` (a hipStream_t, NULL = the null stream);
+ * device pointers of the current device. */
 int gf_cvt_gray_batch_device(const void* d_src, size_t src_pitch, int format, void* d_dst, int batch, int width, int height, void* stream);
 /* The same conversion (rosNodeTest.cpp:238-254) on host frames (copies in, converts, copies out; synchronous): the building block the parity tests call. */
 int gf_cvt_gray_batch(const uint8_t* src, size_t src_pitch, int format, uint8_t* dst, int batch, int width, int height);
@@ -519,8 +526,8 @@ int gf_estimator_input_feature(gf_estimator* h, double t, const gf_feature_obs* 
  * (inputFeature does this for the frames it takes off the queue).  Needs at least one processed IMU sample when use_imu is set. */
 int gf_estimator_process_image(gf_estimator* h, double header, const gf_feature_obs* obs, int n);
 /* inputImage: trackImage on the owned tracker, then inputFeature (every second frame when multiple_thread, estimator.cpp:226).  The frame is in the format of
- * cfg.tracker.pixel_format (gf_estimator_default_cfg: GF_PIX_MONO8; no YAML key, the reference has none): with a colour format `gray` holds colour pixels and
- * `stride` >= width x channels bytes, and the tracker converts on the device what the node's getImageFromMsg converts on the host (rosNodeTest.cpp:238-254) */
+ * cfg.tracker.pixel_format (gf_estimator_default_cfg: GF_PIX_MONO8; no YAML key, the reference has none): with a colour or raw format `gray` holds pixels of that format and
+ * `stride` >= width x bytes per pixel, and the tracker converts on the device what the node's getImageFromMsg converts on the host (rosNodeTest.cpp:238-254) */
 int gf_estimator_input_image(gf_estimator* h, double t, const uint8_t* gray, int stride, const uint16_t* depth, int dstride,
                              gf_feature_obs* out, int cap, int* n_out);
 /* window state; arrays of (window_size+1) entries, any pointer may be NULL.  info[16]: frame_count, solver_flag, marginalization_flag,

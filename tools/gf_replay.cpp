@@ -6,7 +6,7 @@
 //   gf_replay <config.yaml> --bag <recording.bag> [<vio.txt>]      the recording itself (ROS bag format 2.0, host/rosbag_reader.h); topics = the config's
 //                                                                   imu_topic / wheel_topic / image0_topic / image1_topic (parameters.cpp:156-157, :211, :230)
 //   gf_replay --device-gray <config.yaml> --bag <recording.bag> [<vio.txt>]   the same, but the image0 messages go to the tracker undecoded (their step, their
-//                                                                   encoding) and cv_bridge::toCvCopy(msg, MONO8) (rosNodeTest.cpp:238-254) runs on the device; same vio.txt
+//                                                                   encoding: colour, Bayer, yuv422, mono16) and cv_bridge::toCvCopy(msg, MONO8) (rosNodeTest.cpp:238-254) runs on the device; same vio.txt
 //   --roi <mask.pgm>                                                with any single-process form: a region of interest for the tracker (8-bit PGM of the configured
 //                                                                   frame size, non-zero = allowed; gf_estimator_set_roi).  No YAML key: the reference has none
 // reads the reference's own YAML configuration (parameters.cpp key names), replays the recorded IMU / wheel / RGB / depth messages of
