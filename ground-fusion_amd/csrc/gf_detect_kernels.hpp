@@ -8,12 +8,9 @@
 #include <stdint.h>
 #include "gf_lk_kernels.hpp"
 #include "gf_roi.hpp"
+#include "gf_seq_cfg.hpp"   // kMaxRadius, DiskTable
 
 namespace gf {
-
-constexpr int kMaxRadius = 128;  // largest MIN_DIST supported by the disk table
-
-struct DiskTable { short hw[kMaxRadius + 1]; int radius; };  // half-width of row |dy| of OpenCV's filled midpoint circle
 
 // cornerMinEigenVal(block 3, Sobel 3): 32x8 output tile per 256-thread block, 34x10 covariance halo in LDS
 // evaluated at REFLECT_101 coordinates (the box filter's border mode), image read from the padded level 0.
@@ -85,6 +82,10 @@ struct DetectArgs {
     // the strip has loaded anyway), or null on a handle that never set one -- then the kernel is the one it was, a scalar compare aside.  A sequence of such a
     // handle that has none holds all-ones words.
     const uint32_t* roi; size_t roi_seq_words;
+    // ... of the radius of the sequence's own MIN_DIST (gf_tracker_set_seq_cfg): the handle's table of circles, one row per SEQUENCE like the region of interest,
+    // or null on a handle that never set any parameters -- then the by-value table of the launch holds for every strip, and the kernel is the one it was, a
+    // scalar compare aside.  A sequence of such a handle that was never set holds the handle's own row.
+    const DiskTable* disk_of;
     unsigned* maxkey;                                       // [count] orderable max over unmasked pixels (0 = none)
     unsigned long long* cand; size_t cand_seq_stride; int cand_cap; int* cand_count;
 };
@@ -143,23 +144,32 @@ __global__ void __launch_bounds__(64) detect_strip_kernel(DetectArgs A, DiskTabl
         // first, so that it arrives under the circles.  Lanes with col_out have 0 <= x < w, and blockIdx.y is a band of the table (same R, same rounding).
         uint32_t roi_word = ~0u;
         if (A.roi && col_out) roi_word = A.roi[(size_t)(cur >> 1) * A.roi_seq_words + gfroi::word_at(g.w, blockIdx.y, x)];
+        int radius = T.radius;
+        if (A.disk_of) {   // the row of this strip's sequence: its radius in the hit test and the row walk below
+            const DiskTable* row = A.disk_of + (cur >> 1);
+            radius = __builtin_amdgcn_readfirstlane(row->radius);
 #pragma unroll
-        for (int q = 0; q < (kMaxRadius + 64) / 64; q++)
-            if (lane + 64 * q <= T.radius) s_hw[lane + 64 * q] = T.hw[lane + 64 * q];
+            for (int q = 0; q < (kMaxRadius + 64) / 64; q++)
+                if (lane + 64 * q <= radius) s_hw[lane + 64 * q] = row->hw[lane + 64 * q];
+        } else {
+#pragma unroll
+            for (int q = 0; q < (kMaxRadius + 64) / 64; q++)
+                if (lane + 64 * q <= radius) s_hw[lane + 64 * q] = T.hw[lane + 64 * q];
+        }
         __syncthreads();
         uint32_t covered = 0;
         const int n = A.n_centers[b];
         for (int i0 = 0; i0 < n; i0 += 64) {
             int2 c = make_int2(-(1 << 20), -(1 << 20));
             if (i0 + lane < n) c = A.centers[(size_t)b * A.cap + i0 + lane];
-            const bool hit = c.x + T.radius >= X0 && c.x - T.radius < X0 + kDS_W && c.y + T.radius >= Y0 && c.y - T.radius < Y0 + R;
+            const bool hit = c.x + radius >= X0 && c.x - radius < X0 + kDS_W && c.y + radius >= Y0 && c.y - radius < Y0 + R;
             unsigned long long hb = __ballot(hit);
             while (hb) {
                 const int j = __builtin_ctzll(hb);
                 hb &= hb - 1;
                 const int cx = __builtin_amdgcn_readlane(c.x, j), cy = __builtin_amdgcn_readlane(c.y, j);
                 const int dx = abs(x - cx);
-                if (dx <= T.radius) {
+                if (dx <= radius) {
                     const int k = s_hw[dx];
                     const int lo = max(cy - k - Y0, 0), hi = min(cy + k - Y0, R - 1);
                     if (lo <= hi) covered |= (hi - lo >= 31 ? ~0u : ((1u << (hi - lo + 1)) - 1u)) << lo;
@@ -285,6 +295,7 @@ struct SelectArgs {
     const unsigned* maxkey;  // [count] orderable masked maximum (threshold = 0.01 * max, THRESH_TOZERO)
     const int* want;         // [count] maxCorners for this frame (<=0: none)
     int w, h, min_dist, out_cap;
+    const int* min_dist_of;  // [count] the MIN_DIST of the sequence at each list position (gf_tracker_set_seq_cfg; travels next to `want`), or null: min_dist above for all
     int sort_cap;            // keys that fit the LDS sort area (power of two <= kSortLds)
     float2* out_pts;         // [count][out_cap]
     uint16_t* out_depth;     // [count][out_cap]
@@ -332,7 +343,8 @@ __global__ void __launch_bounds__(1024) select_topk_kernel(SelectArgs A) {
     const unsigned mk = A.maxkey[b];
     const double maxVal = mk ? (double)f32_from_orderable(mk) : 0.0;
     const float thresh = (float)(maxVal * 0.01);
-    const int md2 = A.min_dist * A.min_dist;
+    const int min_dist = A.min_dist_of ? A.min_dist_of[b] : A.min_dist;
+    const int md2 = min_dist * min_dist;
     if (tid < 3) s_best[tid] = 0ull;
     // this thread's candidates above the quality threshold, with their coordinates (0: none / decided)
     unsigned long long kq[kTopKQ];
@@ -455,7 +467,9 @@ __global__ void __launch_bounds__(1024) select_corners_kernel(SelectArgs A) {
     // ---- greedy selection (featureselect.cpp: grid of cell_size = min_dist, 3x3 neighbourhood test)
     const unsigned long long* keys = in_lds ? lk : gk;
     const int lane = tid;
-    const int cell = A.min_dist >= 1 ? A.min_dist : 1;
+    // the sequence's own spacing: a larger cell than the one the handle's min_dist sized the area for needs less of it
+    const int min_dist = A.min_dist_of ? A.min_dist_of[b] : A.min_dist;
+    const int cell = min_dist >= 1 ? min_dist : 1;
     const int gw = (A.w + cell - 1) / cell, gh = (A.h + cell - 1) / cell;
     // accepted corners live after the key area: head[gw*gh] (int16 index or -1), then (x,y,next) records
     short* head = reinterpret_cast<short*>(smem + (size_t)A.sort_cap * 8);
@@ -463,7 +477,7 @@ __global__ void __launch_bounds__(1024) select_corners_kernel(SelectArgs A) {
     for (int i = lane; i < gw * gh; i += 64) head[i] = -1;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    const int md2 = A.min_dist * A.min_dist;
+    const int md2 = min_dist * min_dist;
     int naccept = 0;
     for (int base = 0; base < n && naccept < want; base += 64) {
         const int ci = base + lane;
@@ -474,7 +488,7 @@ __global__ void __launch_bounds__(1024) select_corners_kernel(SelectArgs A) {
         const int y = (int)(off / (unsigned)A.w), x = (int)(off - (unsigned)y * A.w);
         const int xc = x / cell, yc = y / cell;
         bool good = valid;
-        if (good && A.min_dist >= 1) {
+        if (good && min_dist >= 1) {
             const int x1 = max(0, xc - 1), y1 = max(0, yc - 1), x2 = min(gw - 1, xc + 1), y2 = min(gh - 1, yc + 1);
             for (int yy = y1; yy <= y2 && good; yy++)
                 for (int xx = x1; xx <= x2 && good; xx++)
@@ -495,7 +509,7 @@ __global__ void __launch_bounds__(1024) select_corners_kernel(SelectArgs A) {
                 A.out_depth[(size_t)b * A.out_cap + naccept] = A.depth ? A.depth[b * A.depth_seq_stride + (size_t)ay * A.depth_stride + ax] : (uint16_t)0;
             }
             naccept++;
-            if (A.min_dist >= 1 && lane > l && good) {
+            if (min_dist >= 1 && lane > l && good) {
                 const int dx = x - ax, dy = y - ay;
                 if (dx * dx + dy * dy < md2) good = false;
             }

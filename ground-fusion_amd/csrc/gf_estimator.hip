@@ -556,12 +556,13 @@ struct BatchSolver {
             if (grp.empty()) continue;
             const auto tc0 = std::chrono::steady_clock::now();
             const int B = (int)grp.size(), W = grp[0]->sweep->W;
-            std::vector<double> Rs, Ps, tic, ric, obs, depth;
+            std::vector<double> Rs, Ps, tic, ric, obs, depth, depth_threshold, init_depth, focal_length;   // the last three per member: members may differ in them
             std::vector<int> first_feature(1, 0), start_frame, first_obs(1, 0), flag;
             for (Req* r : grp) {
                 const SweepIn& in = *r->sweep;
                 Rs.insert(Rs.end(), in.Rs.begin(), in.Rs.end()); Ps.insert(Ps.end(), in.Ps.begin(), in.Ps.end());
                 tic.insert(tic.end(), in.tic, in.tic + 3); ric.insert(ric.end(), in.ric, in.ric + 9);
+                depth_threshold.push_back(in.depth_threshold); init_depth.push_back(in.init_depth); focal_length.push_back(in.focal_length);
                 const int o0 = first_obs.back();
                 for (int f = 0; f < in.nf; f++) first_obs.push_back(o0 + in.first_obs[f + 1]);
                 start_frame.insert(start_frame.end(), in.start_frame.begin(), in.start_frame.end());
@@ -573,11 +574,10 @@ struct BatchSolver {
             std::vector<int> remove(std::max(F, 1), 0);
             int rc = GF_OK;
             if (F > 0) {
-                const SweepIn& c0 = *grp[0]->sweep;   // members of a group share their configuration
-                if (mode == 0) rc = gf_triangulate_with_depth_batch(sweeps, B, W, Rs.data(), Ps.data(), tic.data(), ric.data(), first_feature.data(), start_frame.data(), first_obs.data(),
-                                                                    obs.data(), c0.depth_threshold, c0.init_depth, depth.data(), flag.data());
-                else rc = gf_moving_consistency_batch(sweeps, B, W, Rs.data(), Ps.data(), tic.data(), ric.data(), first_feature.data(), start_frame.data(), first_obs.data(), obs.data(),
-                                                      depth.data(), c0.focal_length, remove.data());
+                if (mode == 0) rc = gf_triangulate_with_depth_batch_each(sweeps, B, W, Rs.data(), Ps.data(), tic.data(), ric.data(), first_feature.data(), start_frame.data(), first_obs.data(),
+                                                                         obs.data(), depth_threshold.data(), init_depth.data(), depth.data(), flag.data());
+                else rc = gf_moving_consistency_batch_each(sweeps, B, W, Rs.data(), Ps.data(), tic.data(), ric.data(), first_feature.data(), start_frame.data(), first_obs.data(), obs.data(),
+                                                           depth.data(), focal_length.data(), remove.data());
             }
             const std::string err = rc == GF_OK ? std::string() : std::string(gf_last_error());
             for (int b = 0; b < B; b++) {
@@ -600,7 +600,7 @@ struct BatchSolver {
                 std::vector<gf::PreintJob> jobs;
                 for (Req* r : grp)
                     for (ImuPre* p : r->pres) {
-                        gf::PreintJob j{&p->st, &p->lin_ba.x, &p->lin_bg.x, p->dt.data(), p->acc.data(), p->gyr.data(), (int)p->dt.size(), {p->acc0.x, p->acc0.y, p->acc0.z}, {p->gyr0.x, p->gyr0.y, p->gyr0.z}};
+                        gf::PreintJob j{&p->st, &p->lin_ba.x, &p->lin_bg.x, p->dt.data(), p->acc.data(), p->gyr.data(), (int)p->dt.size(), {p->acc0.x, p->acc0.y, p->acc0.z}, {p->gyr0.x, p->gyr0.y, p->gyr0.z}, r->noise};   // the member's own noise: members may differ in it
                         jobs.push_back(j);
                     }
                 const int rc = gf::preint_batch_run(pre, jobs, grp[0]->noise);
@@ -2203,18 +2203,30 @@ struct gf_estimator_group {
     }
 };
 
-int gf_estimator_group_create(const gf_estimator_cfg* c, int n, gf_estimator_group** out) {
-    if (!c || !out || n < 1 || n > 4096) return gf::set_err(GF_ERR_INVALID, "bad argument (1 <= n <= 4096)");
-    if (c->with_tracker) return gf::set_err(GF_ERR_INVALID, "group members take feature frames (cfg.with_tracker = 0); run one batched gf_tracker next to the group");
-    if (c->max_solver_time > 0) return gf::set_err(GF_ERR_INVALID, "max_solver_time %.3g s: the wall-clock cut of ceres::Solve is per solve, not per batch; set it to 0 for a group (iteration cap only)", c->max_solver_time);
+// Member i is an Estimator built from cfgs[i].  What sizes or schedules the shared solver has to agree (checked before anything is created); everything else is the
+// member's own: its windows carry their switches, masks and weights (gf_ba_window), and the shared gf_ba handle is sized for the largest member.
+int gf_estimator_group_create_each(const gf_estimator_cfg* cfgs, int n, gf_estimator_group** out) {
+    if (!cfgs || !out || n < 1 || n > 4096) return gf::set_err(GF_ERR_INVALID, "bad argument (1 <= n <= 4096)");
+    const gf_estimator_cfg* c = cfgs;   // member 0: the values the others have to agree with
+    int max_features = 0, max_visual = 0, max_gnss = 0;
+    for (int i = 0; i < n; i++) {
+        const gf_estimator_cfg& m = cfgs[i];
+        if (m.with_tracker) return gf::set_err(GF_ERR_INVALID, "member %d: group members take feature frames (cfg.with_tracker = 0); run one batched gf_tracker next to the group", i);
+        if (m.max_solver_time > 0) return gf::set_err(GF_ERR_INVALID, "member %d: max_solver_time %.3g s: the wall-clock cut of ceres::Solve is per solve, not per batch; set it to 0 for a group (iteration cap only)", i, m.max_solver_time);
+        const struct { const char* name; int a, b; } same[] = {{"window_size", c->window_size, m.window_size}, {"gnss_enable", c->gnss_enable, m.gnss_enable},
+            {"num_iterations", c->num_iterations, m.num_iterations}, {"use_imu", c->use_imu, m.use_imu}, {"use_wheel", c->use_wheel, m.use_wheel}, {"depth", c->depth, m.depth}};
+        for (const auto& f : same)
+            if (f.a != f.b) return gf::set_err(GF_ERR_INVALID, "member %d: %s %d differs from member 0's %d (the members of a group share one solver: it has to be the same for all)", i, f.name, f.b, f.a);
+        max_features = std::max(max_features, m.max_features); max_visual = std::max(max_visual, m.max_visual); max_gnss = std::max(max_gnss, m.max_gnss_per_frame);
+    }
     gf_estimator_group* g = new gf_estimator_group();
     for (int i = 0; i < n; i++) {
         gf_estimator* e = nullptr;
-        if (int rc = gf_estimator_create(c, &e)) { delete g; return rc; }
+        if (int rc = gf_estimator_create(cfgs + i, &e)) { delete g; return rc; }
         e->group = &g->solver; e->group_slot = i;
         g->mem.push_back(e);
     }
-    gf_ba_cfg bc{c->window_size, c->max_features, c->max_visual, n, c->gnss_enable ? c->max_gnss_per_frame * (c->window_size + 1) : 0};
+    gf_ba_cfg bc{c->window_size, max_features, max_visual, n, c->gnss_enable ? max_gnss * (c->window_size + 1) : 0};
     if (int rc = gf_ba_create(&bc, &g->solver.ba)) { delete g; return rc; }
     g->solver.mem_count = (size_t)n;
     (void)hipGetDevice(&g->device);
@@ -2252,6 +2264,11 @@ int gf_estimator_group_create(const gf_estimator_cfg* c, int n, gf_estimator_gro
     }
     *out = g;
     return GF_OK;
+}
+int gf_estimator_group_create(const gf_estimator_cfg* c, int n, gf_estimator_group** out) {
+    if (!c || !out || n < 1 || n > 4096) return gf::set_err(GF_ERR_INVALID, "bad argument (1 <= n <= 4096)");
+    const std::vector<gf_estimator_cfg> each((size_t)n, *c);
+    return gf_estimator_group_create_each(each.data(), n, out);
 }
 int gf_estimator_group_destroy(gf_estimator_group* g) {
     if (g && g->in_flight) (void)gf_estimator_group_wait(g);

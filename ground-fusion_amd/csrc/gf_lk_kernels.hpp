@@ -631,6 +631,7 @@ struct LkBatchArgs {
     int flow_back;        // reverse LK + 0.5 px check (:138-153)
     int post_checks;      // inBorder + brightness test (:155-168)
     const uint8_t* seq_mask; // optional [count]: process only list positions with mask!=0 (fallback relaunch)
+    const uint8_t* flow_back_of; // optional [count]: FLOW_BACK of the sequence at each list position (gf_tracker_set_seq_cfg); null: flow_back above for all
 };
 
 // grid.x = ceil(cap/4) blocks of 4 wavefronts, grid.y = list position.  Forward LK (feature_tracker.cpp:118-135),
@@ -643,6 +644,8 @@ __global__ void __launch_bounds__(256, 7) lk_track_kernel(PyrGeom G, LkBatchArgs
     const int i = blockIdx.x * 4 + wave;
     if (A.seq_mask && !A.seq_mask[b]) return;
     if (i >= A.n_pts[b]) return;
+    int flow_back = A.flow_back;   // wave-uniform: the block row is one list position
+    if (A.flow_back_of) flow_back = __builtin_amdgcn_readfirstlane(A.flow_back_of[b]);
     uint8_t* tile = tiles + wave * kTileBytes;
     const size_t pi = (size_t)b * A.cap + i;
     float2 pp = A.prev_pts[pi];
@@ -660,7 +663,7 @@ __global__ void __launch_bounds__(256, 7) lk_track_kernel(PyrGeom G, LkBatchArgs
     st = lk_solve(G, LkImages{prevI, curI}, pp.x, pp.y, cx, cy, min(A.fwd_max_level, G.nlevels - 1), A.fwd_use_init != 0, tile, lane,
                   n_levels, n_iters);
     const int fwd_st = st;
-    if (A.flow_back && st) {
+    if (flow_back && st) {
         float rx = pp.x, ry = pp.y;
         int rst = lk_solve(G, LkImages{curI, prevI}, cx, cy, rx, ry, min(1, G.nlevels - 1), true, tile, lane, n_levels, n_iters);
         const double ddx = (double)(pp.x - rx), ddy = (double)(pp.y - ry);
@@ -933,6 +936,8 @@ __global__ void __launch_bounds__(256, P == 4 ? 2 : 3) lk_track_mp_kernel(PyrGeo
     if (A.seq_mask && !A.seq_mask[b]) return;
     const int n = A.n_pts[b];
     if (i0 >= n) return;
+    int flow_back = A.flow_back;   // wave-uniform: the block row is one list position
+    if (A.flow_back_of) flow_back = __builtin_amdgcn_readfirstlane(A.flow_back_of[b]);
     const int i = i0 + (lane >> SH);
     const bool valid = i < n;
     uint8_t* tile = tiles + wave * P * kTileBytes;
@@ -946,7 +951,7 @@ __global__ void __launch_bounds__(256, P == 4 ? 2 : 3) lk_track_mp_kernel(PyrGeo
     if (A.fwd_use_init) { const float2 ip = A.init_pts[pi]; cx = ip.x; cy = ip.y; } else { cx = 0.f; cy = 0.f; }
     int st = lk_solve_mp<P>(G, prevI, curI, pp.x, pp.y, cx, cy, valid, min(A.fwd_max_level, G.nlevels - 1), A.fwd_use_init != 0, tile, lane, n_levels, n_iters);
     const int fwd_st = st;
-    if (A.flow_back) {
+    if (flow_back) {
         const bool back = valid && st != 0;
         if (__ballot(back)) {
             float rx = pp.x, ry = pp.y;

@@ -147,11 +147,11 @@ void imu_preint_range(ImuPreState& st, const double* ba, const double* bg, const
 // order, no contraction, structural zeros skipped the way mul() skips them -- so that a device interval is bit-identical to gf::imu_preint_range of the same
 // samples (tests/test_preint_gpu.py).  The 3-vector / quaternion part of a sample and the 3 x 3 blocks of F and V are evaluated by every lane (uniform).
 namespace gf {
-struct PreintJobDev { int s0, s1; double acc0[3], gyr0[3], ba[3], bg[3]; };
+struct PreintJobDev { int s0, s1; double acc0[3], gyr0[3], ba[3], bg[3], noise[4]; };   // noise: acc_n, gyr_n, acc_w, gyr_w of the estimator the interval belongs to
 constexpr int PREINT_OUT = 16 + 225 + 225;   // dp 3, dq 4, dv 3, sum_dt, pad 5 | jacobian | covariance
 
 __global__ __launch_bounds__(64) void imu_preint_batch_kernel(int n, const PreintJobDev* __restrict__ jobs, const double* __restrict__ dt, const double* __restrict__ acc,
-                                                              const double* __restrict__ gyr, double n0, double n1, double n2, double n3, double* __restrict__ out) {
+                                                              const double* __restrict__ gyr, double* __restrict__ out) {
     __shared__ double sJ[225], sP[225], sF[225], sV[270], sT[225], sVN[270];
     const int b = blockIdx.x, lane = threadIdx.x;
     if (b >= n) return;
@@ -162,6 +162,7 @@ __global__ __launch_bounds__(64) void imu_preint_batch_kernel(int n, const Prein
     V3 dp = v3(0, 0, 0), dv = v3(0, 0, 0);
     Q4 dq{1, 0, 0, 0};
     double sdt = 0;
+    const double n0 = jb.noise[0], n1 = jb.noise[1], n2 = jb.noise[2], n3 = jb.noise[3];   // per job: block-uniform
     const double Nd[6] = {n0 * n0, n1 * n1, n0 * n0, n1 * n1, n2 * n2, n3 * n3};   // diagonal of the 18 x 18 noise matrix, 3 entries each
     __syncthreads();
     for (int s = jb.s0; s < jb.s1; s++) {
@@ -285,6 +286,7 @@ int preint_batch_run(PreintBatch* b, const std::vector<PreintJob>& jobs, const d
         PreintJobDev& d = b->h_jobs.p[i];
         d.s0 = off; d.s1 = off + j.n;
         for (int k = 0; k < 3; k++) { d.acc0[k] = j.acc0[k]; d.gyr0[k] = j.gyr0[k]; d.ba[k] = j.ba[k]; d.bg[k] = j.bg[k]; }
+        for (int k = 0; k < 4; k++) d.noise[k] = (j.noise ? j.noise : noise)[k];
         if (j.n > 0) { memcpy(b->h_dt.p + off, j.dt, sizeof(double) * j.n); memcpy(b->h_acc.p + 3 * off, j.acc, sizeof(double) * 3 * j.n); memcpy(b->h_gyr.p + 3 * off, j.gyr, sizeof(double) * 3 * j.n); }
         off += j.n;
     }
@@ -295,7 +297,7 @@ int preint_batch_run(PreintBatch* b, const std::vector<PreintJob>& jobs, const d
         HIPCHK(hipMemcpyAsync(b->d_gyr.p, b->h_gyr.p, sizeof(double) * 3 * total, hipMemcpyHostToDevice, b->stream));
     }
     HIPCHK(hipEventRecord(b->ev0, b->stream));
-    hipLaunchKernelGGL(imu_preint_batch_kernel, dim3(n), dim3(64), 0, b->stream, n, b->d_jobs.p, b->d_dt.p, b->d_acc.p, b->d_gyr.p, noise[0], noise[1], noise[2], noise[3], b->d_out.p);
+    hipLaunchKernelGGL(imu_preint_batch_kernel, dim3(n), dim3(64), 0, b->stream, n, b->d_jobs.p, b->d_dt.p, b->d_acc.p, b->d_gyr.p, b->d_out.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(b->ev1, b->stream));
     HIPCHK(hipMemcpyAsync(b->h_out.p, b->d_out.p, sizeof(double) * PREINT_OUT * n, hipMemcpyDeviceToHost, b->stream));

@@ -12,9 +12,10 @@ void imu_preint_range(ImuPreState& st, const double* ba, const double* bg, const
 // delta_p / delta_q / delta_v / sum_dt only (J and P of `st` are left alone): the same bits as imu_preint_range gives for them
 void imu_preint_state_range(ImuPreState& st, const double* ba, const double* bg, const double* dt, const double* acc, const double* gyr, int s0, int s1);
 // many intervals at once on the device (gf_preint.hip): every job is integrated from scratch over its n samples and fills *st with the bits the two calls
-// above would produce
+// above would produce.  The noise parameters (acc_n, gyr_n, acc_w, gyr_w) travel with the job: the intervals of one launch may belong to estimators that
+// differ in them (gf_estimator_group_create_each).  noise == nullptr: the four values preint_batch_run was called with.
 struct PreintBatch;
-struct PreintJob { ImuPreState* st; const double *ba, *bg, *dt, *acc, *gyr; int n; double acc0[3], gyr0[3]; };
+struct PreintJob { ImuPreState* st; const double *ba, *bg, *dt, *acc, *gyr; int n; double acc0[3], gyr0[3]; const double* noise = nullptr; };
 int preint_batch_create(PreintBatch** out);
 void preint_batch_destroy(PreintBatch* b);
 int preint_batch_run(PreintBatch* b, const std::vector<PreintJob>& jobs, const double* noise);

@@ -35,6 +35,7 @@
 #include "gf_hip_own.hpp"
 #include "gf_pixfmt.hpp"
 #include "gf_roi.hpp"
+#include "gf_seq_cfg.hpp"
 
 namespace gf {
 
@@ -66,6 +67,7 @@ struct SeqState {  // per-sequence FeatureTracker members (feature_tracker.h:76-
     double cur_time = 0, prev_time = 0;
     int n_id = 0;
     bool hasPrediction = false;
+    bool started = false;   // the sequence has taken a frame since gf_tracker_create / gf_tracker_reset_seq: its parameters are fixed (gf_tracker_set_seq_cfg)
     int slot = 1;   // which of the sequence's two pyramids holds its newest frame; flipped when the sequence takes a frame, and only then (the first frame goes to 0)
 };
 
@@ -110,19 +112,6 @@ class HostPool {
     unsigned long long gen_ = 0;
     bool stop_ = false;
 };
-
-static void make_disk_table(int radius, DiskTable& T) {  // drawing.cpp Circle(): union of the h-lines per row offset
-    T.radius = radius;
-    for (int i = 0; i <= kMaxRadius; i++) T.hw[i] = -1;
-    int err = 0, dx = radius, dy = 0, plus = 1, minus = (radius << 1) - 1;
-    while (dx >= dy) {
-        T.hw[dy] = std::max<short>(T.hw[dy], (short)dx);
-        T.hw[dx] = std::max<short>(T.hw[dx], (short)dy);
-        dy++; err += plus; plus += 2;
-        int mask = (err <= 0) - 1;
-        err -= minus & mask; dx += mask; minus -= mask & 2;
-    }
-}
 
 static int build_geom(int w, int h, PyrGeom& G) {
     memset(&G, 0, sizeof G);
@@ -204,6 +193,14 @@ struct gf_tracker {
     DevBuf<uint32_t> d_roi; DevBuf<int> d_roi_seq;
     std::vector<uint32_t> roi_bits; std::vector<uint8_t> roi_has;
     size_t roi_words = 0;
+    // The sequences' own parameters (gf_seq_cfg.hpp; gf_tracker_set_seq_cfg), the fourth thing addressed by SEQUENCE.  par[seq] is what is in force, the handle's cfg
+    // until a setter says otherwise (host memory only).  The rest is obtained by the first setter of the handle, as the region of interest's tables are: the circle
+    // tables of the sequences' min_dist -- seq_disk on the host for setMask's walk, d_seq_disk for the detector -- and the two lists that carry min_dist and
+    // flow_back to the selection and LK kernels by list position with the call's other hand-over tables.
+    std::vector<gf_tracker_seq_cfg> par;
+    std::vector<DiskTable> seq_disk; DevBuf<DiskTable> d_seq_disk;
+    DevBuf<int> d_seq_md; PinBuf<int> h_seq_md;
+    DevBuf<uint8_t> d_seq_fb; PinBuf<uint8_t> h_seq_fb;
 
     std::unique_ptr<HostPool> pool;
 };
@@ -213,13 +210,13 @@ namespace gf {
 static inline int cvRoundf(float v) { return (int)lrintf(v); }
 
 // camodocal PinholeCamera (camera_models/src/camera_models/PinholeCamera.cc:450-510, :520-542, :646-662)
-static void distortion(const gf_tracker_cfg& c, double x, double y, double& dx, double& dy) {
+static void distortion(const gf_tracker_seq_cfg& c, double x, double y, double& dx, double& dy) {
     double mx2 = x * x, my2 = y * y, mxy = x * y, rho2 = mx2 + my2, rad = c.k1 * rho2 + c.k2 * rho2 * rho2;
     dx = x * rad + 2.0 * c.p1 * mxy + c.p2 * (rho2 + 2.0 * mx2);
     dy = y * rad + 2.0 * c.p2 * mxy + c.p1 * (rho2 + 2.0 * my2);
 }
-static bool no_distortion(const gf_tracker_cfg& c) { return c.k1 == 0.0 && c.k2 == 0.0 && c.p1 == 0.0 && c.p2 == 0.0; }
-static void lift_projective(const gf_tracker_cfg& c, double u, double v, double& X, double& Y) {
+static bool no_distortion(const gf_tracker_seq_cfg& c) { return c.k1 == 0.0 && c.k2 == 0.0 && c.p1 == 0.0 && c.p2 == 0.0; }
+static void lift_projective(const gf_tracker_seq_cfg& c, double u, double v, double& X, double& Y) {
     const double i11 = 1.0 / c.fx, i13 = -c.cx / c.fx, i22 = 1.0 / c.fy, i23 = -c.cy / c.fy;
     const double mx_d = i11 * u + i13, my_d = i22 * v + i23;
     if (no_distortion(c)) { X = mx_d; Y = my_d; return; }
@@ -229,7 +226,7 @@ static void lift_projective(const gf_tracker_cfg& c, double u, double v, double&
     for (int i = 1; i < 8; ++i) { distortion(c, mx_u, my_u, dux, duy); mx_u = mx_d - dux; my_u = my_d - duy; }
     X = mx_u; Y = my_u;
 }
-static void space_to_plane(const gf_tracker_cfg& c, const double* P, double& u, double& v) {
+static void space_to_plane(const gf_tracker_seq_cfg& c, const double* P, double& u, double& v) {
     double xu = P[0] / P[2], yu = P[1] / P[2], xd = xu, yd = yu;
     if (!no_distortion(c)) { double dx, dy; distortion(c, xu, yu, dx, dy); xd = xu + dx; yd = yu + dy; }
     u = c.fx * xd + c.cx; v = c.fy * yd + c.cy;
@@ -321,6 +318,7 @@ static LkBatchArgs lk_args(gf_tracker* h, int fwd_max_level, int use_init, int f
     A.depth_seq_stride = (size_t)h->cfg.width * h->cfg.height; A.depth_stride = h->cfg.width;
     A.counters = h->d_counters.p; A.fwd_max_level = fwd_max_level; A.fwd_use_init = use_init; A.flow_back = flow_back;
     A.post_checks = post_checks; A.seq_mask = seqmask;
+    A.flow_back_of = h->d_seq_fb.p;   // null on a handle no setter has touched; written by the copy list in front of the call's first LK launch
     return A;
 }
 
@@ -328,7 +326,8 @@ static LkBatchArgs lk_args(gf_tracker* h, int fwd_max_level, int use_init, int f
 // the reference) and greedy keep of points not covered by an earlier kept point's filled circle.
 // roi: the sequence's region of interest (gf_roi.hpp) or null.  With one, the walk starts from `mask = R` instead of an all-255 image: a point whose rounded pixel
 // is excluded fails `mask.at(pt) == 255` like a covered one -- not kept, no circle, gone from ids / track_cnt / cur_pts.
-static void set_mask_host(gf_tracker* h, SeqState& s, const uint32_t* roi, int2* centers, int& n_centers) {
+// T: the circle of the sequence's min_dist.
+static void set_mask_host(gf_tracker* h, SeqState& s, const DiskTable& T, const uint32_t* roi, int2* centers, int& n_centers) {
     struct E { int cnt; P2f pt; int id; uint16_t depth; };
     static thread_local std::vector<E> v;
     v.clear();
@@ -336,7 +335,6 @@ static void set_mask_host(gf_tracker* h, SeqState& s, const uint32_t* roi, int2*
     std::sort(v.begin(), v.end(), [](const E& a, const E& b) { return a.cnt > b.cnt; });
     s.cur_pts.clear(); s.ids.clear(); s.track_cnt.clear(); s.cur_depth.clear();
     n_centers = 0;
-    const DiskTable& T = h->disk;
     // `mask.at(pt) == 255` <=> pt is inside no earlier kept point's filled circle; circles reach at most `radius`
     // pixels, so only centres in the 3x3 neighbourhood of radius-sized cells can cover pt.
     const int cell = std::max(T.radius, 1);
@@ -447,6 +445,7 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
     for (int i = 0; i < N; i++) {
         SeqState& s = h->seq[seq[i]];
         s.cur_time = t[i]; s.cur_pts.clear(); s.cur_depth.clear();
+        s.started = true;
         h->h_cur.p[i] = 2 * seq[i] + (s.slot ^ 1);   // the new frame goes to the sequence's other pyramid; s.slot itself moves when the frame is done
     }
     // The hand-overs between the host's bookkeeping and the kernels -- two to four small tables down before LK, five up behind it, three down before the detection, four
@@ -507,6 +506,7 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
     if (any_prev) {
         if (over_bus) down(h->d_cur, h->h_cur, N);
         down(h->d_npts, h->h_npts, N);
+        if (h->d_seq_fb.p) { for (int i = 0; i < N; i++) h->h_seq_fb.p[i] = (uint8_t)h->par[seq[i]].flow_back; down(h->d_seq_fb, h->h_seq_fb, N); }
         down(h->d_prev_pts, h->h_prev_pts, (size_t)N * cap);
         const uint8_t* mask_plain = nullptr; const uint8_t* mask_pred = nullptr;
         if (any_pred) {
@@ -575,6 +575,8 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
     std::atomic<int> a_want{0};
     h->pool->parallel_for(N, [&](int b) {   // b: list position
         SeqState& s = h->seq[seq[b]];
+        const gf_tracker_seq_cfg& par = h->par[seq[b]];
+        const uint16_t* dimg = hdep && par.depth_cam ? hdep[b] : nullptr;   // a sequence without a depth camera: its image is not read (its samples are never reported) and may be null
         const int n = (int)s.prev_pts.size();
         if (n > 0) {
             const uint8_t* st = h->h_status.p + (size_t)b * cap;
@@ -583,7 +585,8 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
             for (int i = 0; i < n; i++) {
                 const float2 c = h->h_cur_pts.p[(size_t)b * cap + i];
                 s.cur_pts[i] = {c.x, c.y};
-                if (hdep) { const int ry = (int)std::round((double)c.y), rx = (int)std::round((double)c.x); s.cur_depth[i] = st[i] ? hdep[b][(size_t)ry * hdstride + rx] : (uint16_t)0; }   // st: inside the image (post checks)
+                if (dimg) { const int ry = (int)std::round((double)c.y), rx = (int)std::round((double)c.x); s.cur_depth[i] = st[i] ? dimg[(size_t)ry * hdstride + rx] : (uint16_t)0; }   // st: inside the image (post checks)
+                else if (hdep) s.cur_depth[i] = 0;
                 else s.cur_depth[i] = h->h_depth_out.p[(size_t)b * cap + i];
                 lv += h->h_counters.p[2 * ((size_t)b * cap + i)];
                 it += h->h_counters.p[2 * ((size_t)b * cap + i) + 1];
@@ -596,10 +599,11 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
         for (auto& c : s.track_cnt) c++;
         int nc = 0;
         const uint32_t* roi = !h->roi_has.empty() && h->roi_has[seq[b]] ? h->roi_bits.data() + (size_t)seq[b] * h->roi_words : nullptr;
-        set_mask_host(h, s, roi, h->h_centers.p + (size_t)b * cap, nc);
+        set_mask_host(h, s, h->seq_disk.empty() ? h->disk : h->seq_disk[seq[b]], roi, h->h_centers.p + (size_t)b * cap, nc);
         h->h_ncenters.p[b] = nc;
-        const int want = h->cfg.max_cnt - (int)s.cur_pts.size();
+        const int want = par.max_cnt - (int)s.cur_pts.size();
         h->h_want.p[b] = want;
+        if (h->h_seq_md.p) h->h_seq_md.p[b] = par.min_dist;
         h->h_det.p[b] = want > 0 ? h->h_cur.p[b] : -1;
         if (want > 0) a_want = 1;
         h->h_out_n.p[b] = 0;
@@ -613,6 +617,7 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
         down(h->d_centers, h->h_centers, (size_t)N * cap);
         down(h->d_ncenters, h->h_ncenters, N);
         down(h->d_want, h->h_want, N);
+        if (h->d_seq_md.p) down(h->d_seq_md, h->h_seq_md, N);
         down(h->d_out_n, h->h_out_n, N);   // zeros (set above): a sequence that neither selection kernel serves reads 0, not an earlier call's count
         if (int rc = flush()) return rc;
         HIPCHK(hipMemsetAsync(h->d_maxkey.p, 0, N * sizeof(unsigned), h->stream));
@@ -623,12 +628,13 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
             D.pyr = h->d_img.p; D.pyr_bytes = h->G.img_bytes; D.frame_of = h->d_det.p; D.g = h->G.lv[0];
             D.mask = nullptr; D.mask_seq_stride = 0; D.centers = h->d_centers.p; D.n_centers = h->d_ncenters.p; D.cap = cap;
             D.roi = h->d_roi.p; D.roi_seq_words = h->roi_words;   // null on a handle no setter has touched
+            D.disk_of = h->d_seq_disk.p;                          // likewise
             D.maxkey = h->d_maxkey.p; D.cand = h->d_cand.p; D.cand_seq_stride = (size_t)h->cand_cap; D.cand_cap = h->cand_cap; D.cand_count = h->d_cand_count.p;
             detect_strip_kernel<kDS_R><<<dim3((W + kDS_W - 1) / kDS_W, (H + kDS_R - 1) / kDS_R, N), 64, 0, h->stream>>>(D, h->disk);
         }
         SelectArgs S{};
         S.cand = h->d_cand.p; S.cand_seq_stride = (size_t)h->cand_cap; S.cand_cap = h->cand_cap; S.cand_count = h->d_cand_count.p; S.maxkey = h->d_maxkey.p; S.want = h->d_want.p;
-        S.w = W; S.h = H; S.min_dist = h->cfg.min_dist; S.out_cap = cap; S.sort_cap = h->sort_cap; S.out_pts = h->d_out_pts.p; S.out_depth = h->d_out_depth.p; S.out_n = h->d_out_n.p;
+        S.w = W; S.h = H; S.min_dist = h->cfg.min_dist; S.min_dist_of = h->d_seq_md.p; S.out_cap = cap; S.sort_cap = h->sort_cap; S.out_pts = h->d_out_pts.p; S.out_depth = h->d_out_depth.p; S.out_n = h->d_out_n.p;
         S.depth = d_depth; S.depth_seq_stride = (size_t)W * H; S.depth_stride = W;
         {   // the sequences that want a handful of corners (every frame but the first ones): one maximum per corner instead of a sort (select_topk_kernel; GF_SELECT_TOPK=0: off)
             const bool topk_on = h->select_topk;
@@ -680,14 +686,16 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
     std::atomic<long long> a_out{0};
     h->pool->parallel_for(N, [&](int b) {   // b: list position
         SeqState& s = h->seq[seq[b]];
+        const gf_tracker_seq_cfg& par = h->par[seq[b]];
+        const uint16_t* dimg = hdep && par.depth_cam ? hdep[b] : nullptr;
         const int nn = h->h_want.p[b] > 0 ? h->h_out_n.p[b] : 0;
         for (int i = 0; i < nn; i++) {
             const float2 p = h->h_out_pts.p[(size_t)b * cap + i];
             s.cur_pts.push_back({p.x, p.y}); s.ids.push_back(s.n_id++); s.track_cnt.push_back(1);
-            s.cur_depth.push_back(hdep ? hdep[b][(size_t)(int)p.y * hdstride + (int)p.x] : h->h_out_depth.p[(size_t)b * cap + i]);   // corners sit on pixel centres
+            s.cur_depth.push_back(dimg ? dimg[(size_t)(int)p.y * hdstride + (int)p.x] : hdep ? (uint16_t)0 : h->h_out_depth.p[(size_t)b * cap + i]);   // corners sit on pixel centres
         }
         s.cur_un_pts.clear();
-        for (auto& p : s.cur_pts) { double X, Y; lift_projective(h->cfg, (double)p.x, (double)p.y, X, Y); s.cur_un_pts.push_back({(float)(X / 1.0), (float)(Y / 1.0)}); }
+        for (auto& p : s.cur_pts) { double X, Y; lift_projective(par, (double)p.x, (double)p.y, X, Y); s.cur_un_pts.push_back({(float)(X / 1.0), (float)(Y / 1.0)}); }
         pts_velocity(s);
         s.prev_pts = s.cur_pts; s.prev_un_pts = s.cur_un_pts; s.prev_un_pts_map.swap(s.cur_un_pts_map); s.prev_time = s.cur_time;
         s.hasPrediction = false;
@@ -695,14 +703,14 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
         const int n = (int)s.ids.size();
         // depth_cam set but no depth image: neither packing loop of the reference runs (feature_tracker.cpp:320 `depth_cam == 0`, :344 `!_img1.empty()`):
         // the returned featureFrame is empty, the tracker state has advanced all the same
-        if (h->cfg.depth_cam && !have_depth) { n_out[b] = 0; return; }
+        if (par.depth_cam && !have_depth) { n_out[b] = 0; return; }
         if (n > cap_out) { a_overflow = n; n_out[b] = 0; return; }
         gf_feature_obs* o = out + (size_t)b * cap_out;
         for (int i = 0; i < n; i++) {
             o[i].id = s.ids[i]; o[i].camera_id = 0;
             o[i].v[0] = s.cur_un_pts[i].x; o[i].v[1] = s.cur_un_pts[i].y; o[i].v[2] = 1; o[i].v[3] = s.cur_pts[i].x; o[i].v[4] = s.cur_pts[i].y;
             o[i].v[5] = s.pts_velocity[i].x; o[i].v[6] = s.pts_velocity[i].y;
-            o[i].v[7] = h->cfg.depth_cam ? (double)(int)s.cur_depth[i] / 1000 : -2.4;
+            o[i].v[7] = par.depth_cam ? (double)(int)s.cur_depth[i] / 1000 : -2.4;
         }
         n_out[b] = n;
         a_out += n;
@@ -747,6 +755,7 @@ int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out) {
     gf::build_geom(cfg->width, cfg->height, h->G);
     gf::make_disk_table(cfg->min_dist, h->disk);
     h->seq.resize(h->B);
+    h->par.assign(h->B, gfseq::of_handle(*cfg));
     h->ident.resize(h->B);
     for (int b = 0; b < h->B; b++) h->ident[b] = b;
     {
@@ -828,7 +837,7 @@ int gf_tracker_track_some(gf_tracker* h, int count, const int* seq, const double
     bool have_depth = depth != nullptr;
     for (int i = 0; i < count; i++) {   // refuse before the first copy
         if (!gray[i]) return gf::set_err(GF_ERR_INVALID, "null image for sequence %d", seq[i]);
-        if (have_depth && !depth[i]) have_depth = false;
+        if (have_depth && !depth[i] && h->par[seq[i]].depth_cam) have_depth = false;
     }
     for (int i = 0; i < count; i++) HIPCHK(hipMemcpy2DAsync(h->d_raw.p + (size_t)i * row * H, row, gray[i], stride, row, H, hipMemcpyHostToDevice, h->stream));
     // the depth image stays where it is: its <= max_cnt samples are taken on the host (track_core)
@@ -849,7 +858,7 @@ int gf_tracker_prefetch_some(gf_tracker* h, int count, const int* seq, const uin
     bool have_depth = depth != nullptr;
     for (int i = 0; i < count; i++) {
         if (!gray[i]) return gf::set_err(GF_ERR_INVALID, "null image for sequence %d", seq[i]);
-        if (have_depth && !depth[i]) have_depth = false;
+        if (have_depth && !depth[i] && h->par[seq[i]].depth_cam) have_depth = false;
     }
     if (h->pf_count >= 2) return gf::set_err(GF_ERR_CAPACITY, "two frames are staged already: gf_tracker_track_prefetched has to consume one first");
     if (!h->copy_stream) {
@@ -928,7 +937,7 @@ int gf_tracker_set_prediction(gf_tracker* h, int seq, const int* ids, const doub
     for (int i = 0; i < n; i++) m[ids[i]] = xyz + 3 * i;
     for (size_t i = 0; i < s.ids.size(); i++) {
         auto it = m.find(s.ids[i]);
-        if (it != m.end()) { double u, v; gf::space_to_plane(h->cfg, it->second, u, v); s.predict_pts.push_back({(float)u, (float)v}); }
+        if (it != m.end()) { double u, v; gf::space_to_plane(h->par[seq], it->second, u, v); s.predict_pts.push_back({(float)u, (float)v}); }
         else s.predict_pts.push_back(s.prev_pts[i]);
     }
     return GF_OK;
@@ -983,6 +992,61 @@ int gf_tracker_get_roi(gf_tracker* h, int seq, uint8_t* mask, int stride, int* h
     const uint32_t* t = h->roi_bits.data() + (size_t)seq * h->roi_words;
     for (int y = 0; y < H; y++)
         for (int x = 0; x < W; x++) mask[(size_t)y * stride + x] = gfroi::allowed(t, W, x, y) ? 255 : 0;
+    return GF_OK;
+}
+
+// ---- parameters per sequence (gf_seq_cfg.hpp).  Like the region of interest's setters these run between frames, with the handle's stream drained.
+namespace gf {
+static int seq_cfg_ready(gf_tracker* h) {   // the first setter of a handle: every sequence's row is the handle's own circle
+    if (h->d_seq_disk.p) return GF_OK;
+    DevBuf<DiskTable> table; DevBuf<int> md; PinBuf<int> hmd; DevBuf<uint8_t> fb; PinBuf<uint8_t> hfb;
+    HIPCHK(table.alloc(h->B)); HIPCHK(md.alloc(h->B)); HIPCHK(hmd.alloc(h->B)); HIPCHK(fb.alloc(h->B)); HIPCHK(hfb.alloc(h->B));
+    std::vector<DiskTable> rows((size_t)h->B, h->disk);
+    HIPCHK(hipMemcpy(table.p, rows.data(), rows.size() * sizeof(DiskTable), hipMemcpyHostToDevice));
+    h->seq_disk = std::move(rows);
+    h->d_seq_disk = std::move(table); h->d_seq_md = std::move(md); h->h_seq_md = std::move(hmd); h->d_seq_fb = std::move(fb); h->h_seq_fb = std::move(hfb);
+    return GF_OK;
+}
+// a frame staged by gf_tracker_prefetch_* that lists the sequence: its depth pointers were judged with the parameters in force when it was staged
+static bool seq_is_staged(const gf_tracker* h, int seq) {
+    for (int k = 0; k < h->pf_count; k++) {
+        const std::vector<int>& l = h->pf_seq[(h->pf_head + k) & 1];
+        if (std::find(l.begin(), l.end(), seq) != l.end()) return true;
+    }
+    return false;
+}
+}  // namespace gf
+
+int gf_tracker_set_seq_cfg(gf_tracker* h, int seq, const gf_tracker_seq_cfg* c) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    if (h->seq[seq].started) return gf::set_err(GF_ERR_INVALID, "sequence %d has taken a frame: its parameters are fixed until gf_tracker_reset_seq", seq);
+    if (gf::seq_is_staged(h, seq)) return gf::set_err(GF_ERR_INVALID, "sequence %d is listed by a staged frame: gf_tracker_track_prefetched has to consume it first", seq);
+    const gf_tracker_seq_cfg want = c ? *c : gfseq::of_handle(h->cfg);
+    char msg[256];
+    if (c && !gfseq::fits(h->cfg, want, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "sequence %d: %s", seq, msg);
+    if (!c && !h->d_seq_disk.p) return GF_OK;   // nothing to take back: the handle stays one that never set any
+    if (int rc = gf::seq_cfg_ready(h)) return rc;
+    gf::DiskTable row;
+    gf::make_disk_table(want.min_dist, row);
+    HIPCHK(hipMemcpy(h->d_seq_disk.p + seq, &row, sizeof row, hipMemcpyHostToDevice));
+    h->seq_disk[seq] = row;
+    h->par[seq] = want;
+    return GF_OK;
+}
+
+int gf_tracker_get_seq_cfg(gf_tracker* h, int seq, gf_tracker_seq_cfg* out) {
+    if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    *out = h->par[seq];
+    return GF_OK;
+}
+
+int gf_tracker_reset_seq(gf_tracker* h, int seq) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    if (gf::seq_is_staged(h, seq)) return gf::set_err(GF_ERR_INVALID, "sequence %d is listed by a staged frame: gf_tracker_track_prefetched has to consume it first", seq);
+    h->seq[seq] = gf::SeqState{};   // no tracks, no previous frame: LK has nothing to read in the sequence's pyramids, whatever they hold
     return GF_OK;
 }
 

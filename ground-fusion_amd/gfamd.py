@@ -21,6 +21,13 @@ class TrackerCfg(C.Structure):
                 ("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double), ("equalize", C.c_int), ("pixel_format", C.c_int)]
 
 
+class TrackerSeqCfg(C.Structure):
+    """gf_tracker_seq_cfg: the parameters a sequence of a tracker handle may have of its own (the reference's per-FeatureTracker members)"""
+    _fields_ = [("max_cnt", C.c_int), ("min_dist", C.c_int), ("flow_back", C.c_int), ("depth_cam", C.c_int),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double)]
+
+
 # GF_PIX_*: the formats of the frames a tracker handle takes and of cvt_gray (rosNodeTest.cpp:238-254), and their bytes per pixel
 PIX_MONO8, PIX_RGB8, PIX_BGR8, PIX_RGBA8, PIX_BGRA8 = range(5)
 PIX_CHANNELS = (1, 3, 3, 4, 4)
@@ -67,6 +74,7 @@ assert OBS_DTYPE.itemsize == C.sizeof(FeatureObs)
 EXPORTS = ["gf_last_error", "gf_device_count", "gf_set_device", "gf_tracker_create", "gf_tracker_destroy", "gf_tracker_track",
            "gf_tracker_track_batch", "gf_tracker_track_batch_device", "gf_tracker_track_some", "gf_tracker_track_some_device", "gf_tracker_prefetch_some", "gf_tracker_set_prediction", "gf_tracker_remove_outliers",
            "gf_tracker_set_roi", "gf_tracker_set_roi_some_device", "gf_tracker_get_roi",
+           "gf_tracker_set_seq_cfg", "gf_tracker_get_seq_cfg", "gf_tracker_reset_seq",
            "gf_tracker_get_state", "gf_tracker_set_profiling", "gf_tracker_get_stats", "gf_tracker_reset_stats", "gf_lk_track",
            "gf_good_features", "gf_min_eigen_val", "gf_pyramid_level", "gf_clahe_batch", "gf_clahe_batch_device", "gf_cvt_gray_batch", "gf_cvt_gray_batch_device"]
 
@@ -155,8 +163,9 @@ class FeatureTracker:
         imgs = [None if i is None else np.ascontiguousarray(i, np.uint8) if stride is None else self._pitched(i, np.uint8, stride) for i in imgs]
         gp = (C.POINTER(C.c_uint8) * max(N, 1))(*[None if i is None else _p(i, C.c_uint8) for i in imgs])
         if depths is not None:
-            depths = [np.ascontiguousarray(d, np.uint16) for d in depths] if dstride is None else [self._pitched(d, np.uint16, dstride) for d in depths]
-            dp = (C.POINTER(C.c_uint16) * max(N, 1))(*[_p(d, C.c_uint16) for d in depths])
+            # (an entry may be None for a sequence whose own depth_cam is 0, set_seq_cfg: its image is not read)
+            depths = [None if d is None else np.ascontiguousarray(d, np.uint16) if dstride is None else self._pitched(d, np.uint16, dstride) for d in depths]
+            dp = (C.POINTER(C.c_uint16) * max(N, 1))(*[None if d is None else _p(d, C.c_uint16) for d in depths])
         else:
             dp = None
         out = np.zeros((N, self.cap), OBS_DTYPE)
@@ -297,6 +306,33 @@ class FeatureTracker:
         has = C.c_int(0)
         _chk(lib().gf_tracker_get_roi(self.h, seq, _p(mask, C.c_uint8), self.cfg.width, C.byref(has)))
         return mask if has.value else None
+
+    def set_seq_cfg(self, seq, **fields):
+        """gf_tracker_set_seq_cfg: sequence `seq` gets parameters of its own -- any of max_cnt, min_dist, flow_back, depth_cam, fx, fy, cx, cy, k1, k2, p1, p2; the
+        fields that are not named keep the value in force.  Without fields: back to the handle's cfg.  Refused (GfError) once the sequence has taken a frame,
+        until reset_seq, and outside the handle's capacity (max_cnt <= cfg.max_cnt, min_dist >= cfg.min_dist)."""
+        if not fields:
+            _chk(lib().gf_tracker_set_seq_cfg(self.h, seq, None))
+            return
+        names = [k for k, _ in TrackerSeqCfg._fields_]
+        unknown = [k for k in fields if k not in names]
+        if unknown:
+            raise TypeError("gf_tracker_seq_cfg has no field %s" % ", ".join(unknown))
+        c = TrackerSeqCfg()
+        _chk(lib().gf_tracker_get_seq_cfg(self.h, seq, C.byref(c)))
+        for k, v in fields.items():
+            setattr(c, k, v)
+        _chk(lib().gf_tracker_set_seq_cfg(self.h, seq, C.byref(c)))
+
+    def get_seq_cfg(self, seq):
+        """gf_tracker_get_seq_cfg: the parameters in force for sequence `seq`, as a dict of the twelve fields"""
+        c = TrackerSeqCfg()
+        _chk(lib().gf_tracker_get_seq_cfg(self.h, seq, C.byref(c)))
+        return {k: getattr(c, k) for k, _ in TrackerSeqCfg._fields_}
+
+    def reset_seq(self, seq):
+        """gf_tracker_reset_seq: sequence `seq` as after create (no tracks, ids from 0, no previous frame); its parameters and region of interest stay"""
+        _chk(lib().gf_tracker_reset_seq(self.h, seq))
 
     def state(self, seq=0):
         ids = np.zeros(self.cap, np.int32)
@@ -977,12 +1013,24 @@ def write_pgm(path, img):
 
 # ------------------------------------------------------------------ many sequences on one batched solver (gf_estimator_group_*)
 class EstimatorGroup:
-    """n Estimators sharing one batched back-end handle; members are SlidingWindowEstimator views (IMU / wheel input, state queries)."""
+    """n Estimators sharing one batched back-end handle; members are SlidingWindowEstimator views (IMU / wheel input, state queries).
+    EstimatorGroup(cfg, n): n members of one configuration.  EstimatorGroup(cfgs=[...]): member i is built from cfgs[i] (gf_estimator_group_create_each); the
+    members may differ in everything but what sizes or schedules the shared solver (window_size, gnss_enable, num_iterations, use_imu, use_wheel, depth)."""
 
-    def __init__(self, cfg, n, device_preint=None, device_sweeps=None):
-        self.cfg, self.n = cfg, n
+    def __init__(self, cfg=None, n=None, device_preint=None, device_sweeps=None, cfgs=None):
         self.g = C.c_void_p()
-        _chk(lib().gf_estimator_group_create(C.byref(cfg), n, C.byref(self.g)))
+        if cfgs is not None:
+            if cfg is not None or n not in (None, len(cfgs)):
+                raise TypeError("EstimatorGroup takes either (cfg, n) or cfgs=[...]")
+            cfgs = list(cfgs)
+            n = len(cfgs)
+            arr = (EstimatorCfg * max(n, 1))(*cfgs)
+            _chk(lib().gf_estimator_group_create_each(arr, n, C.byref(self.g)))
+            cfg = cfgs[0]
+        else:
+            cfgs = [cfg] * n
+            _chk(lib().gf_estimator_group_create(C.byref(cfg), n, C.byref(self.g)))
+        self.cfg, self.n, self.cfgs = cfg, n, cfgs
         if device_preint is not None:   # SURVEY.md 8(f)4: one pre-integration launch per step instead of the members' host loops
             _chk(lib().gf_estimator_group_set_device_preint(self.g, int(bool(device_preint))))
         if device_sweeps is not None:   # SURVEY.md 8(f)4: triangulateWithDepth / movingConsistencyCheckW of all members as one launch each per step
@@ -990,7 +1038,7 @@ class EstimatorGroup:
         self.members = []
         for i in range(n):
             m = SlidingWindowEstimator.__new__(SlidingWindowEstimator)
-            m.cfg, m.W, m.h = cfg, cfg.window_size, C.c_void_p()
+            m.cfg, m.W, m.h = cfgs[i], cfgs[i].window_size, C.c_void_p()
             _chk(lib().gf_estimator_group_member(self.g, i, C.byref(m.h)))
             m.close = lambda: None          # owned by the group
             self.members.append(m)

@@ -178,6 +178,34 @@ int gf_tracker_set_roi(gf_tracker* h, int seq, const uint8_t* mask, int stride);
 int gf_tracker_set_roi_some_device(gf_tracker* h, int count, const int* seq, const void* d_masks);
 /* *has = whether the sequence has a region; if so and mask != NULL, the stored region as 0 / 255 bytes, rows `stride` bytes apart (>= width) */
 int gf_tracker_get_roi(gf_tracker* h, int seq, uint8_t* mask, int stride, int* has);
+/* Parameters per sequence: what the reference keeps per FeatureTracker object (MAX_CNT, MIN_DIST, FLOW_BACK, depth_cam, m_camera; feature_tracker.h:76-98).
+ * A sequence that was never set runs with the handle's gf_tracker_cfg, every result as without these calls, bit for bit.  With its parameters set, a tracker
+ * call for that sequence is FeatureTracker::trackImage of an object constructed with them: setMask's circles and goodFeaturesToTrack's minimum distance use its
+ * min_dist, it tops up to its max_cnt, runs the reverse check or not by its flow_back, liftProjective / spaceToPlane (gf_tracker_set_prediction) and the
+ * velocities use its camera, and the output packing and the "depth_cam set but no depth image" rule use its depth_cam -- through every entry point (host,
+ * prefetched and device frames, the _some forms, region-of-interest, colour and equalize handles alike), in the launches it shares with its neighbours.  On the
+ * host entry points the depth[i] of a listed sequence with depth_cam == 0 is not read and may be NULL.
+ * The handle's cfg is also the capacity: 1 <= max_cnt <= cfg.max_cnt (the point arrays are that wide), cfg.min_dist <= min_dist <= 128 (the handle's min_dist
+ * sized the selection grid and the sort area when it was created), fx, fy > 0, flow_back and depth_cam 0 or 1.  So a mixed handle is created with the largest
+ * count and the tightest spacing of its fleet, and allocates nothing further for the point tables.  Width, height, equalize and pixel_format stay per handle.
+ * The parameters are fixed while a sequence holds tracking state, as they are in the reference after construction: once the sequence has taken a frame the
+ * setter is refused until gf_tracker_reset_seq.  The tables (one circle table row per sequence, two small lists per call) are allocated when the first
+ * parameters of a handle are set; a handle that sets none allocates and launches nothing for them.  Refused with GF_ERR_INVALID, a message that names the
+ * field, and nothing changed: a null handle, seq out of range, a value outside the limits above, a sequence that has taken a frame, a sequence that a
+ * frame staged by gf_tracker_prefetch_* lists (setter and gf_tracker_reset_seq alike: gf_tracker_track_prefetched consumes it first).  One caller thread per
+ * handle, between frames. */
+typedef struct gf_tracker_seq_cfg {
+    int max_cnt, min_dist, flow_back, depth_cam;
+    double fx, fy, cx, cy, k1, k2, p1, p2;
+} gf_tracker_seq_cfg;
+/* c == NULL: back to the handle's cfg */
+int gf_tracker_set_seq_cfg(gf_tracker* h, int seq, const gf_tracker_seq_cfg* c);
+/* what is in force for seq (the handle's values for a sequence that was never set) */
+int gf_tracker_get_seq_cfg(gf_tracker* h, int seq, gf_tracker_seq_cfg* out);
+/* The sequence as it was after gf_tracker_create -- no tracks, n_id = 0, no previous frame, no pending prediction, prev_time = 0 -- for a slot that another
+ * unit takes over.  Keeps the sequence's parameters and its region of interest (they are settings), allows gf_tracker_set_seq_cfg again, touches no other
+ * sequence. */
+int gf_tracker_reset_seq(gf_tracker* h, int seq);
 /* FeatureTracker::removeOutliers (feature_tracker.cpp:1029-1045) */
 int gf_tracker_remove_outliers(gf_tracker* h, int seq, const int* ids, int n);
 /* public members ids / track_cnt / prev_pts (feature_tracker.h:85-88) */
@@ -406,7 +434,9 @@ int gf_preint_stats(gf_preint* h, long long* launches, long long* intervals, dou
  *   gf_triangulate_with_depth_batch  FeatureManager::triangulateWithDepth, feature_manager.cpp:726-799 (estimated_depth / estimate_flag updated in place)
  *   gf_moving_consistency_batch      Estimator::movingConsistencyCheckW, estimator.cpp:3955-3995 (remove[f] = 1 for the ids the reference puts into removeIndex)
  * Window b: Rs / Ps ((W+1) x 9 row-major / (W+1) x 3), tic (3), ric (9), features first_feature[b] .. first_feature[b+1]-1 (feature_manager's list order);
- * feature f: start_frame[f], observations first_obs[f] .. first_obs[f+1]-1, each x, y, z of the normalised point and the depth-camera depth. */
+ * feature f: start_frame[f], observations first_obs[f] .. first_obs[f+1]-1, each x, y, z of the normalised point and the depth-camera depth.
+ * The _each forms take depth_threshold / init_depth / focal_length as arrays of B values, one per window, for windows of estimators that differ in them
+ * (gf_estimator_group_create_each); with equal values they leave the bits of the scalar forms. */
 typedef struct gf_featsweep gf_featsweep;
 int gf_featsweep_create(gf_featsweep** out);
 int gf_featsweep_destroy(gf_featsweep* h);
@@ -415,6 +445,11 @@ int gf_triangulate_with_depth_batch(gf_featsweep* h, int B, int W, const double*
                                     double* estimated_depth, int* estimate_flag);
 int gf_moving_consistency_batch(gf_featsweep* h, int B, int W, const double* Rs, const double* Ps, const double* tic, const double* ric, const int* first_feature,
                                 const int* start_frame, const int* first_obs, const double* obs, const double* estimated_depth, double focal_length, int* remove);
+int gf_triangulate_with_depth_batch_each(gf_featsweep* h, int B, int W, const double* Rs, const double* Ps, const double* tic, const double* ric, const int* first_feature,
+                                         const int* start_frame, const int* first_obs, const double* obs, const double* depth_threshold, const double* init_depth,
+                                         double* estimated_depth, int* estimate_flag);
+int gf_moving_consistency_batch_each(gf_featsweep* h, int B, int W, const double* Rs, const double* Ps, const double* tic, const double* ric, const int* first_feature,
+                                     const int* start_frame, const int* first_obs, const double* obs, const double* estimated_depth, const double* focal_length, int* remove);
 int gf_featsweep_stats(gf_featsweep* h, long long* launches, long long* features, double* kernel_ms);
 /* WheelIntegrationBase::push_back loop (factor/wheel_integration_base.h:41-178); noise = VEL_N_wheel, GYR_N_wheel; lin = sx, sy, sw */
 int gf_wheel_preintegrate(int n, const double* dt, const double* vel, const double* gyr, const double* vel0, const double* gyr0, const double* lin,
@@ -561,6 +596,15 @@ int gf_estimator_debug(gf_estimator* h, const char* op, const double* in, int n_
  * feature frames (run one batched gf_tracker next to the group); IMU / wheel samples and state queries go through the member handles. */
 typedef struct gf_estimator_group gf_estimator_group;
 int gf_estimator_group_create(const gf_estimator_cfg* cfg, int n, gf_estimator_group** out);
+/* The same group with a configuration per member: member i is an Estimator built from cfgs[i] (gf_estimator_group_create is this call with n copies of one
+ * cfg).  Members may differ in everything the reference keeps per Estimator -- extrinsics tic / ric / tio / rio, sx / sy / sw, the noise parameters (acc_n,
+ * gyr_n, acc_w, gyr_w and the wheel's), td*, estimate_*, extrinsic_type*, use_mcc, wdetect, stationary_detect, only_initial_with_wheel, depth_threshold,
+ * init_depth, focal_length, min_parallax_px, g_norm, the GNSS thresholds -- and must agree in what sizes or schedules the shared solver: window_size,
+ * gnss_enable, num_iterations, use_imu, use_wheel, depth (GF_ERR_INVALID with a message that names member and field, nothing created).  Every member needs
+ * with_tracker == 0 and max_solver_time == 0.  The shared solver takes the largest max_features, max_visual and max_gnss_per_frame of the members.
+ * What differs stays the member's own in the batched launches too: the device pre-integration carries the noise parameters per interval and the device
+ * feature sweeps depth_threshold / init_depth / focal_length per window, so a member is the stand-alone Estimator of its cfg with either switched on. */
+int gf_estimator_group_create_each(const gf_estimator_cfg* cfgs, int n, gf_estimator_group** out);
 int gf_estimator_group_destroy(gf_estimator_group* g);
 /* the IMU intervals a camera frame completes (the frame's own IntegrationBase and the window's, estimator.cpp:760-768, :866-869) are integrated
  * by one device launch per group step (gf_imu_preintegrate_batch's kernel) instead of on the members' host threads; results are bit-identical either way.
