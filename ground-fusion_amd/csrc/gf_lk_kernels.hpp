@@ -335,6 +335,8 @@ __global__ void __launch_bounds__(512) pyr_head_kernel(const uint8_t* __restrict
 // ---------------------------------------------------------------------------------------------
 // Wave-level exact integer sum.  Per-lane |v| < 2^28 so 8-lane partial sums fit int32; the eight group
 // sums are combined on the scalar unit in 64 bits.  Result is wave-uniform.
+// Where the bound comes from: a lane adds seven pixels, and a product is at most 8160 x 4080 -- |diff| <= 255 * 32 (two grey values with 5 fractional bits) times a Scharr
+// derivative |d| <= 16 * 255; the structure tensor's 4080 x 4080 is smaller -- so |v| <= 7 x 8160 x 4080 = 2^27.8 and an 8-lane group holds at most 2^30.8.
 // Exact sum of one int32 per lane over the wavefront (|sum| < 2^53): three DPP adds inside 8-lane groups (no overflow: 8 x 2^28), then eight
 // v_readlane + scalar 64-bit adds.  (Two v_mfma_f64_16x16x4_f64 against a matrix of ones give the same exact sum on the matrix pipe; measured
 // 15 % slower here -- the dependent MFMA latency sits on the per-iteration critical path.)
@@ -348,7 +350,8 @@ __device__ __forceinline__ double wave_sum_exact(int v) {
     return (double)s;
 }
 
-// the same sum as the float the reference makes of it: (float)(int64), one rounding.  Three DPP adds inside the 8-lane groups (no overflow: 8 x 2^28); the group
+// the same sum as the float the reference makes of it: (float)(int64), one rounding.  Three DPP adds inside the 8-lane groups (no overflow: 8 x 2^28, and a lane holds at
+// most 7 pixels x 8160 x 4080 = 2^27.8); the group
 // sums are then split into a signed upper and an unsigned lower half-word, and each half goes through the remaining three levels (row_mirror, row_bcast:15,
 // row_bcast:31: sums of 8 half-words, < 2^19) to lane 63; the scalar unit puts the two together and normalises for the conversion (find the leading bit, shift,
 // sticky bit), two vector instructions finish it (v_cvt_f32_i32, v_ldexp_f32).  Per sum 15 vector + ~12 scalar instructions; reading the eight group sums with
@@ -730,7 +733,7 @@ __device__ __forceinline__ int row16_sum(int v) {   // every lane of a 16-lane r
     v += __builtin_amdgcn_mov_dpp(v, 0x140, 0xf, 0xf, true);   // row_mirror
     return v;
 }
-// exact sums over the wavefront of P per-lane partials (|v| < 2^28), each delivered to the lanes of its point's group as the float the reference makes of the int64 sum
+// exact sums over the wavefront of P per-lane partials (|v| < 2^28: 7 pixels x 8160 x 4080 = 2^27.8 at most, see wave_sum_exact), each delivered to the lanes of its point's group as the float the reference makes of the int64 sum
 // ((float)(int64): one rounding).  Signed upper / unsigned lower half-words are summed separately (64 x 2^16 fits an int32) and put together in double, where the sum is
 // exact; the conversion to float then rounds once.
 template <int P> __device__ __forceinline__ float multi_sum_f32(const int (&v)[P]) {

@@ -36,6 +36,14 @@ void gfo_pyr_down(const uint8_t* src, int w, int h, uint8_t* dst);
 void gfo_scharr(const uint8_t* src, int w, int h, int16_t* dst);
 void gfo_lk(const uint8_t* prev, const uint8_t* next, int w, int h, const float* prevPts, float* nextPts, uint8_t* status, int n,
             int maxLevel, int maxCount, double eps, int useInitialFlow, long long* iters);
+/* gfo_lk with a census beside it (same arguments, same nextPts / status / iters, bit for bit; runs on one thread whatever gfo_set_threads says):
+ * exits[4 p + level]: the way point p left lk_level at that pyramid level, one of GFO_LK_EXIT_* (0: the call ran no such level, maxLevel or the image too small);
+ * recheck[p]: 1 when the bounds re-check after the level-0 loop (lkpyramid.cpp's err block) cleared a status that was still 1;
+ * max_sums[0] = max |iA11|, |iA12|, |iA22|, max_sums[1] = max |ib1|, |ib2| over every point, level and iteration of the call, as int64. */
+enum { GFO_LK_EXIT_NONE = 0, GFO_LK_EXIT_TEMPLATE_OUT = 1, GFO_LK_EXIT_MIN_EIG = 2, GFO_LK_EXIT_START_OUTSIDE = 3, GFO_LK_EXIT_LEFT_IMAGE = 4,
+       GFO_LK_EXIT_EPS = 5, GFO_LK_EXIT_OSCILLATION = 6, GFO_LK_EXIT_MAX_COUNT = 7 };
+void gfo_lk_census(const uint8_t* prev, const uint8_t* next, int w, int h, const float* prevPts, float* nextPts, uint8_t* status, int n,
+                   int maxLevel, int maxCount, double eps, int useInitialFlow, long long* iters, uint8_t* exits, uint8_t* recheck, long long* max_sums);
 void gfo_fill_circle(uint8_t* img, int w, int h, int cx, int cy, int radius, int color);
 void gfo_min_eigen_val(const uint8_t* img, int w, int h, float* eig);
 int gfo_good_features(const uint8_t* img, int w, int h, float* corners, int maxCorners, double quality, double minDist, const uint8_t* mask);

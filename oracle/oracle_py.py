@@ -140,6 +140,28 @@ def lk(prev, nxt, prev_pts, next_pts=None, max_level=3, max_count=30, eps=0.01):
     return npnts, st, it.value
 
 
+LK_EXITS = ("none", "template_out", "min_eig", "start_outside", "left_image", "eps", "oscillation", "max_count")   # GFO_LK_EXIT_* of gf_oracle.h
+
+
+def lk_census(prev, nxt, prev_pts, next_pts=None, max_level=3, max_count=30, eps=0.01):
+    """lk() with the census of gfo_lk_census beside it: (next_pts, status, iters, exits[n, 4] by level as indices into LK_EXITS, recheck[n], max |A|, max |b|)"""
+    prev = np.ascontiguousarray(prev, np.uint8)
+    nxt = np.ascontiguousarray(nxt, np.uint8)
+    h, w = prev.shape
+    pp = np.ascontiguousarray(prev_pts, np.float32)
+    use_init = next_pts is not None
+    npnts = np.ascontiguousarray(next_pts, np.float32).copy() if use_init else np.zeros_like(pp)
+    st = np.zeros(len(pp), np.uint8)
+    exits = np.zeros((len(pp), 4), np.uint8)
+    recheck = np.zeros(len(pp), np.uint8)
+    sums = np.zeros(2, np.int64)
+    it = C.c_longlong(0)
+    lib().gfo_lk_census(_p(prev, C.c_uint8), _p(nxt, C.c_uint8), w, h, _p(pp, C.c_float), _p(npnts, C.c_float), _p(st, C.c_uint8),
+                        len(pp), max_level, max_count, C.c_double(eps), int(use_init), C.byref(it), _p(exits, C.c_uint8), _p(recheck, C.c_uint8),
+                        _p(sums, C.c_longlong))
+    return npnts, st, it.value, exits, recheck, int(sums[0]), int(sums[1])
+
+
 def fill_circle(img, cx, cy, r, color=0):
     h, w = img.shape
     lib().gfo_fill_circle(_p(img, C.c_uint8), w, h, cx, cy, r, color)

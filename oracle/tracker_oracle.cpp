@@ -155,18 +155,29 @@ static inline float i64_to_f32(int64_t v) { return (float)(double)v; }  // |v| <
 // scalar float tail x = 16..20; lanes added horizontally at the end.  Mode 1 exists to MEASURE how much the documented int64 choice can
 // change feature ids / status flags / coordinates (tests/test_tracker_oracle.py); it does not pin anything.
 static int g_lk_accum = 0;
+// gfo_lk_census: which exit of lk_level every point took at every level, and how large the exact sums became.  Written beside the arithmetic (every write sits
+// under `if (cs)`), never read by it: gfo_lk and Tracker::track pass no census and compute what they computed before.
+struct Census {
+    uint8_t* exits;     // [npts][4], indexed by pyramid level: GFO_LK_EXIT_*; levels the call did not run stay 0
+    uint8_t* recheck;   // [npts]: the bounds re-check after the loop cleared the status
+    int64_t max_A = 0, max_b = 0;   // max |iA11|, |iA12|, |iA22| and max |ib1|, |ib2| over the call
+    void exit(int p, int level, int code) { exits[4 * p + level] = (uint8_t)code; }
+    static int64_t mag(int64_t v) { return v < 0 ? -v : v; }
+    void sums_A(int64_t a, int64_t b, int64_t c) { max_A = std::max(max_A, std::max(mag(a), std::max(mag(b), mag(c)))); }
+    void sums_b(int64_t a, int64_t b) { max_b = std::max(max_b, std::max(mag(a), mag(b))); }
+};
 int g_threads = 1;   // gfo_set_threads: per-point parallel LK here, 4 marginalisation threads in backend_oracle.cpp (CPU-baseline variant (b))
 
 // lkpyramid.cpp LKTrackerInvoker::operator() for one pyramid level, all points.
 static void lk_level(const Img8& I, const Deriv& dI, const Img8& J, const P2f* prevPts, P2f* nextPts,
                      uint8_t* status, int npts, int win, int maxCount, double epsilon, int level,
-                     int maxLevel, bool useInitialFlow, float minEigThreshold, int64_t* iters_out) {
+                     int maxLevel, bool useInitialFlow, float minEigThreshold, int64_t* iters_out, Census* cs = nullptr) {
     const float half = (win - 1) * 0.5f;
     const int stepI = I.stride, stepJ = J.stride, dstep = dI.stride;
     int64_t iters_total = 0;
     // OpenCV runs this loop as parallel_for_ over the points (lkpyramid.cpp: LKTrackerInvoker); points are independent, so the thread count
-    // (gfo_set_threads, CPU-baseline variant (b) of BASELINE.md section 2; default 1) cannot change a result.
-#pragma omp parallel num_threads(g_threads) if (g_threads > 1) reduction(+ : iters_total)
+    // (gfo_set_threads, CPU-baseline variant (b) of BASELINE.md section 2; default 1) cannot change a result.  A census runs on one thread: its maxima are plain members.
+#pragma omp parallel num_threads(g_threads) if (g_threads > 1 && !cs) reduction(+ : iters_total)
     {
     std::vector<int16_t> Ibuf(win * win), dbuf(win * win * 2);
     int64_t* iters_out_l = iters_out ? &iters_total : nullptr;
@@ -184,6 +195,7 @@ static void lk_level(const Img8& I, const Deriv& dI, const Img8& J, const P2f* p
         int ipx = cvFloorf(prevPt.x), ipy = cvFloorf(prevPt.y);
         if (ipx < -win || ipx >= dI.cols || ipy < -win || ipy >= dI.rows) {
             if (level == 0) status[p] = 0;
+            if (cs) cs->exit(p, level, GFO_LK_EXIT_TEMPLATE_OUT);
             continue;
         }
         float a = prevPt.x - ipx, b = prevPt.y - ipy;
@@ -211,6 +223,7 @@ static void lk_level(const Img8& I, const Deriv& dI, const Img8& J, const P2f* p
                 }
             }
         }
+        if (cs) cs->sums_A(iA11, iA12, iA22);
         float A11 = i64_to_f32(iA11) * FLT_SCALE, A12 = i64_to_f32(iA12) * FLT_SCALE, A22 = i64_to_f32(iA22) * FLT_SCALE;
         if (g_lk_accum == 1) {
             fA11 += qA11[0] + qA11[1] + qA11[2] + qA11[3]; fA12 += qA12[0] + qA12[1] + qA12[2] + qA12[3]; fA22 += qA22[0] + qA22[1] + qA22[2] + qA22[3];
@@ -220,15 +233,18 @@ static void lk_level(const Img8& I, const Deriv& dI, const Img8& J, const P2f* p
         float minEig = (A22 + A11 - std::sqrt((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (2 * win * win);
         if (minEig < minEigThreshold || D < FLT_EPSILON) {
             if (level == 0) status[p] = 0;
+            if (cs) cs->exit(p, level, GFO_LK_EXIT_MIN_EIG);
             continue;
         }
         D = 1.f / D;
         nextPt.x -= half; nextPt.y -= half;
         P2f prevDelta = {0.f, 0.f};
+        if (cs) cs->exit(p, level, GFO_LK_EXIT_MAX_COUNT);   // stands unless one of the breaks below is taken
         for (int j = 0; j < maxCount; j++) {
             int inx = cvFloorf(nextPt.x), iny = cvFloorf(nextPt.y);
             if (inx < -win || inx >= J.cols || iny < -win || iny >= J.rows) {
                 if (level == 0) status[p] = 0;
+                if (cs) cs->exit(p, level, j == 0 ? GFO_LK_EXIT_START_OUTSIDE : GFO_LK_EXIT_LEFT_IMAGE);
                 break;
             }
             if (iters_out_l) (*iters_out_l)++;
@@ -253,6 +269,7 @@ static void lk_level(const Img8& I, const Deriv& dI, const Img8& J, const P2f* p
                     }
                 }
             }
+            if (cs) cs->sums_b(ib1, ib2);
             float b1 = i64_to_f32(ib1) * FLT_SCALE, b2 = i64_to_f32(ib2) * FLT_SCALE;
             if (g_lk_accum == 1) {
                 const float s0 = qb0[0] + qb1[0], s1 = qb0[1] + qb1[1], s2 = qb0[2] + qb1[2], s3 = qb0[3] + qb1[3];
@@ -262,9 +279,13 @@ static void lk_level(const Img8& I, const Deriv& dI, const Img8& J, const P2f* p
             P2f delta = {(float)((A12 * b2 - A22 * b1) * D), (float)((A12 * b1 - A11 * b2) * D)};
             nextPt.x += delta.x; nextPt.y += delta.y;
             nextPts[p] = {nextPt.x + half, nextPt.y + half};
-            if ((double)delta.x * delta.x + (double)delta.y * delta.y <= epsilon) break;
+            if ((double)delta.x * delta.x + (double)delta.y * delta.y <= epsilon) {
+                if (cs) cs->exit(p, level, GFO_LK_EXIT_EPS);
+                break;
+            }
             if (j > 0 && std::abs(delta.x + prevDelta.x) < 0.01 && std::abs(delta.y + prevDelta.y) < 0.01) {
                 nextPts[p].x -= delta.x * 0.5f; nextPts[p].y -= delta.y * 0.5f;
+                if (cs) cs->exit(p, level, GFO_LK_EXIT_OSCILLATION);
                 break;
             }
             prevDelta = delta;
@@ -274,7 +295,10 @@ static void lk_level(const Img8& I, const Deriv& dI, const Img8& J, const P2f* p
         if (status[p] && level == 0) {
             P2f np = {nextPts[p].x - half, nextPts[p].y - half};
             int inx = cvFloorf(np.x), iny = cvFloorf(np.y);
-            if (inx < -win || inx >= J.cols || iny < -win || iny >= J.rows) status[p] = 0;
+            if (inx < -win || inx >= J.cols || iny < -win || iny >= J.rows) {
+                status[p] = 0;
+                if (cs) cs->recheck[p] = 1;
+            }
         }
     }
     }
@@ -284,7 +308,7 @@ static void lk_level(const Img8& I, const Deriv& dI, const Img8& J, const P2f* p
 // lkpyramid.cpp SparsePyrLKOpticalFlowImpl::calc, winSize 21x21, minEigThreshold 1e-4
 static void calc_optical_flow_pyr_lk(const uint8_t* prev, const uint8_t* next, int w, int h, int stride,
                                      const P2f* prevPts, P2f* nextPts, uint8_t* status, int npts, int maxLevel,
-                                     int maxCount, double eps, bool useInitialFlow, int64_t* iters_out) {
+                                     int maxCount, double eps, bool useInitialFlow, int64_t* iters_out, Census* cs = nullptr) {
     const int win = 21;
     if (npts == 0) return;
     for (int i = 0; i < npts; i++) status[i] = 1;
@@ -299,7 +323,7 @@ static void calc_optical_flow_pyr_lk(const uint8_t* prev, const uint8_t* next, i
         Deriv dI;
         scharr_deriv(prevPyr[level], dI, win);
         lk_level(prevPyr[level], dI, nextPyr[level], prevPts, nextPts, status, npts, win, maxCount, eps, level,
-                 maxLevel, useInitialFlow, 1e-4f, iters_out);
+                 maxLevel, useInitialFlow, 1e-4f, iters_out, cs);
     }
 }
 
@@ -634,6 +658,17 @@ void gfo_lk(const uint8_t* prev, const uint8_t* next, int w, int h, const float*
     int64_t it = 0;
     calc_optical_flow_pyr_lk(prev, next, w, h, w, (const P2f*)prevPts, (P2f*)nextPts, status, n, maxLevel, maxCount, eps, useInitialFlow != 0, &it);
     if (iters) *iters = it;
+}
+void gfo_lk_census(const uint8_t* prev, const uint8_t* next, int w, int h, const float* prevPts, float* nextPts, uint8_t* status, int n,
+                   int maxLevel, int maxCount, double eps, int useInitialFlow, long long* iters, uint8_t* exits, uint8_t* recheck, long long* max_sums) {
+    int64_t it = 0;
+    Census cs;
+    cs.exits = exits; cs.recheck = recheck;
+    memset(exits, 0, (size_t)n * 4);
+    memset(recheck, 0, (size_t)n);
+    calc_optical_flow_pyr_lk(prev, next, w, h, w, (const P2f*)prevPts, (P2f*)nextPts, status, n, maxLevel, maxCount, eps, useInitialFlow != 0, &it, &cs);
+    if (iters) *iters = it;
+    max_sums[0] = cs.max_A; max_sums[1] = cs.max_b;
 }
 void gfo_fill_circle(uint8_t* img, int w, int h, int cx, int cy, int radius, int color) { fill_circle(img, w, h, w, cx, cy, radius, (uint8_t)color); }
 void gfo_min_eigen_val(const uint8_t* img, int w, int h, float* eig) {
