@@ -33,13 +33,17 @@ static int clahe_geom(int w, int h, double clip_limit, int tiles_x, int tiles_y,
 size_t clahe_lut_bytes(int batch, int tiles_x, int tiles_y) { return (size_t)batch * tiles_x * tiles_y * 256; }
 
 // d_lut: clahe_lut_bytes(batch, tiles_x, tiles_y) bytes of the caller's scratch
-int clahe_launch(const uint8_t* d_src, uint8_t* d_dst, uint8_t* d_lut, int batch, int w, int h, double clip_limit, int tiles_x, int tiles_y, hipStream_t stream) {
+// d_refs == nullptr: d_src holds `batch` tight frames back to back.  Otherwise (the table form) d_src is not read and frame b lies at d_refs[b] (device-readable
+// gf_frame_ref, checked by the caller): the vector forms follow the sizes and d_dst here, and each block falls back to bytes when its own frame's pointer or
+// pitch misses their alignment.
+static int clahe_launch_any(const uint8_t* d_src, const gf_frame_ref* d_refs, uint8_t* d_dst, uint8_t* d_lut, int batch, int w, int h, double clip_limit, int tiles_x, int tiles_y, hipStream_t stream) {
     using namespace gfclahe;
     Geom g;
     if (int rc = clahe_geom(w, h, clip_limit, tiles_x, tiles_y, g)) return rc;
     if (batch < 1 || batch > 65535) return set_err(GF_ERR_INVALID, "clahe: batch %d (1 .. 65535)", batch);
-    const int vec4 = !(w & 3) && !(g.tw & 3) && !(reinterpret_cast<uintptr_t>(d_src) & 3);
-    clahe_lut_kernel<<<dim3(g.tx * g.ty, batch), kThreads, 0, stream>>>(d_src, d_lut, g, vec4);
+    const int vec4 = !(w & 3) && !(g.tw & 3) && (d_refs || !(reinterpret_cast<uintptr_t>(d_src) & 3));
+    if (d_refs) clahe_lut_refs_kernel<<<dim3(g.tx * g.ty, batch), kThreads, 0, stream>>>(d_refs, d_lut, g, vec4);
+    else clahe_lut_kernel<<<dim3(g.tx * g.ty, batch), kThreads, 0, stream>>>(d_src, d_lut, g, vec4);
     // bands: about a thousand workgroups in all, 8 .. 64 rows each, and at most 32 KB of LUT rows in LDS
     const int want_bands = std::max(1, (1024 + batch - 1) / batch);
     int band = std::min(64, std::max(8, (h + want_bands - 1) / want_bands));
@@ -50,13 +54,25 @@ int clahe_launch(const uint8_t* d_src, uint8_t* d_dst, uint8_t* d_lut, int batch
     const int lds_rows = rows_for(band);
     const size_t lds_bytes = lds ? lds_rows * plane : 0;
     const dim3 grid((h + band - 1) / band, batch);
-    const bool v16 = !(w & 15) && !((reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst)) & 15);
-    if (v16 && lds) clahe_apply_kernel<true, true><<<grid, kThreads, lds_bytes, stream>>>(d_src, d_dst, d_lut, g, band, lds_rows);
+    const bool v16 = !(w & 15) && !(((d_refs ? 0 : reinterpret_cast<uintptr_t>(d_src)) | reinterpret_cast<uintptr_t>(d_dst)) & 15);
+    if (d_refs) {
+        if (v16 && lds) clahe_apply_refs_kernel<true, true><<<grid, kThreads, lds_bytes, stream>>>(d_refs, d_dst, d_lut, g, band, lds_rows);
+        else if (lds) clahe_apply_refs_kernel<false, true><<<grid, kThreads, lds_bytes, stream>>>(d_refs, d_dst, d_lut, g, band, lds_rows);
+        else if (v16) clahe_apply_refs_kernel<true, false><<<grid, kThreads, 0, stream>>>(d_refs, d_dst, d_lut, g, band, lds_rows);
+        else clahe_apply_refs_kernel<false, false><<<grid, kThreads, 0, stream>>>(d_refs, d_dst, d_lut, g, band, lds_rows);
+    }
+    else if (v16 && lds) clahe_apply_kernel<true, true><<<grid, kThreads, lds_bytes, stream>>>(d_src, d_dst, d_lut, g, band, lds_rows);
     else if (lds) clahe_apply_kernel<false, true><<<grid, kThreads, lds_bytes, stream>>>(d_src, d_dst, d_lut, g, band, lds_rows);
     else if (v16) clahe_apply_kernel<true, false><<<grid, kThreads, 0, stream>>>(d_src, d_dst, d_lut, g, band, lds_rows);
     else clahe_apply_kernel<false, false><<<grid, kThreads, 0, stream>>>(d_src, d_dst, d_lut, g, band, lds_rows);
     HIPCHK(hipGetLastError());
     return GF_OK;
+}
+int clahe_launch(const uint8_t* d_src, uint8_t* d_dst, uint8_t* d_lut, int batch, int w, int h, double clip_limit, int tiles_x, int tiles_y, hipStream_t stream) {
+    return clahe_launch_any(d_src, nullptr, d_dst, d_lut, batch, w, h, clip_limit, tiles_x, tiles_y, stream);
+}
+int clahe_launch_refs(const gf_frame_ref* d_refs, uint8_t* d_dst, uint8_t* d_lut, int batch, int w, int h, double clip_limit, int tiles_x, int tiles_y, hipStream_t stream) {
+    return clahe_launch_any(nullptr, d_refs, d_dst, d_lut, batch, w, h, clip_limit, tiles_x, tiles_y, stream);
 }
 
 }  // namespace gf

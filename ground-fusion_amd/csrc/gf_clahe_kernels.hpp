@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "gf_frame_ref.hpp"
+
 namespace gfclahe {
 
 constexpr int kThreads = 256;   // = the number of histogram bins: thread t owns bin t in the clip and the scan
@@ -36,20 +38,24 @@ __device__ __forceinline__ int wave_sum(int v) {
 }
 
 // vec4: w % 4 == 0, tw % 4 == 0 and src 4-byte aligned (every in-image quad is then one aligned u32)
-__global__ __launch_bounds__(kThreads) void clahe_lut_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ lut, Geom g, int vec4) {
-    __shared__ unsigned hist[kThreads / 64][256];
-    __shared__ int red[kThreads / 64];
+// REFS (both passes): false -- the source frames are tight and back to back from src; true -- src is the call's table of gf_frame_ref (gfref::frame_at), and a
+// frame whose pointer or pitch misses the alignment of the vector form is read byte by byte, block by block.  The LUTs and the equalised frames are the
+// caller's tight buffers either way.
+template <bool REFS>
+__device__ __forceinline__ void clahe_lut_body(const uint8_t* __restrict__ src, uint8_t* __restrict__ lut, const Geom& g, int vec4, unsigned (*hist)[256], int* red) {
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
     const int tile = blockIdx.x, b = blockIdx.y;
     for (int k = 0; k < kThreads / 64; k++) hist[k][t] = 0;
     __syncthreads();
     const int X0 = (tile % g.tx) * g.tw, Y0 = (tile / g.tx) * g.th;
-    const uint8_t* f = src + (size_t)b * g.w * g.h;
+    const gfref::Frame fr = gfref::frame_at<REFS>(src, (size_t)g.w * g.h, (size_t)g.w, b);
+    const uint8_t* f = fr.data;
+    if (REFS) vec4 = vec4 && gfref::form(reinterpret_cast<uintptr_t>(fr.data), fr.pitch) >= 4;
     unsigned* hw = hist[wave];
     const int qw = (g.tw + 3) >> 2, n = qw * g.th;
     for (int i = t; i < n; i += kThreads) {
         const int r = i / qw, q = i - r * qw;
-        const uint8_t* row = f + (size_t)reflect_hi(Y0 + r, g.h) * g.w;
+        const uint8_t* row = REFS ? f + (size_t)reflect_hi(Y0 + r, g.h) * fr.pitch : f + (size_t)reflect_hi(Y0 + r, g.h) * g.w;
         const int x0 = X0 + 4 * q;
         if (vec4 && x0 + 3 < g.w && 4 * q + 3 < g.tw) {
             const unsigned v = *reinterpret_cast<const unsigned*>(row + x0);
@@ -92,6 +98,16 @@ __global__ __launch_bounds__(kThreads) void clahe_lut_kernel(const uint8_t* __re
     const int v = __float2int_rn((float)s * g.lut_scale);
     lut[((size_t)b * g.tx * g.ty + tile) * 256 + t] = (uint8_t)min(max(v, 0), 255);
 }
+__global__ __launch_bounds__(kThreads) void clahe_lut_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ lut, Geom g, int vec4) {
+    __shared__ unsigned hist[kThreads / 64][256];
+    __shared__ int red[kThreads / 64];
+    clahe_lut_body<false>(src, lut, g, vec4, hist, red);
+}
+__global__ __launch_bounds__(kThreads) void clahe_lut_refs_kernel(const gf_frame_ref* __restrict__ refs, uint8_t* __restrict__ lut, Geom g, int vec4) {
+    __shared__ unsigned hist[kThreads / 64][256];
+    __shared__ int red[kThreads / 64];
+    clahe_lut_body<true>(reinterpret_cast<const uint8_t*>(refs), lut, g, vec4, hist, red);
+}
 
 struct RowLut {   // what one row needs: the two tile-row LUT planes and the row weights
     const uint8_t *p1, *p2;
@@ -124,8 +140,8 @@ __device__ __forceinline__ uint8_t clahe_px(const RowLut& R, int x, int v, const
 
 // kVec16: w % 16 == 0 and src / dst 16-byte aligned: 16 pixels per load and store.  kLds: the band's tile rows of LUTs (at most lds_rows of them) go to LDS first;
 // otherwise the LUTs are read from global memory (grids too wide for LDS).  src == dst is allowed: every pixel is read and written by the same thread.
-template <bool kVec16, bool kLds>
-__global__ __launch_bounds__(kThreads) void clahe_apply_kernel(const uint8_t* src, uint8_t* dst, const uint8_t* __restrict__ lut, Geom g, int band, int lds_rows) {
+template <bool kVec16, bool kLds, bool REFS>
+__device__ __forceinline__ void clahe_apply_body(const uint8_t* src, uint8_t* dst, const uint8_t* __restrict__ lut, const Geom& g, int band, int lds_rows) {
     extern __shared__ __align__(16) uint8_t slut[];
     const int b = blockIdx.y, y0 = blockIdx.x * band, y1 = min(y0 + band, g.h);
     const size_t plane = (size_t)g.tx * 256;
@@ -144,13 +160,14 @@ __global__ __launch_bounds__(kThreads) void clahe_apply_kernel(const uint8_t* sr
         L = slut;
     }
     const size_t fo = (size_t)b * g.w * g.h;
-    if (kVec16) {
+    const gfref::Frame fr = gfref::frame_at<REFS>(src, (size_t)g.w * g.h, (size_t)g.w, b);   // the source frame; the destination stays dst + fo, rows g.w apart
+    if (kVec16 && (!REFS || gfref::form(reinterpret_cast<uintptr_t>(fr.data), fr.pitch) == 16)) {
         const int upr = g.w >> 4, n = (y1 - y0) * upr;
         for (int i = threadIdx.x; i < n; i += kThreads) {
             const int r = i / upr, u = i - r * upr, y = y0 + r;
             const RowLut R = row_lut(y, g, L, row0, nrows);
             const size_t o = fo + (size_t)y * g.w + 16 * u;
-            uint4 v = *reinterpret_cast<const uint4*>(src + o);
+            uint4 v = *reinterpret_cast<const uint4*>(REFS ? fr.data + (size_t)y * fr.pitch + 16 * u : src + o);
             unsigned* w = reinterpret_cast<unsigned*>(&v);
             for (int k = 0; k < 4; k++) {
                 unsigned in = w[k], out = 0;
@@ -165,9 +182,17 @@ __global__ __launch_bounds__(kThreads) void clahe_apply_kernel(const uint8_t* sr
             const int r = i / g.w, x = i - r * g.w, y = y0 + r;
             const RowLut R = row_lut(y, g, L, row0, nrows);
             const size_t o = fo + (size_t)y * g.w + x;
-            dst[o] = clahe_px(R, x, src[o], g);
+            dst[o] = clahe_px(R, x, REFS ? fr.data[(size_t)y * fr.pitch + x] : src[o], g);
         }
     }
+}
+template <bool kVec16, bool kLds>
+__global__ __launch_bounds__(kThreads) void clahe_apply_kernel(const uint8_t* src, uint8_t* dst, const uint8_t* __restrict__ lut, Geom g, int band, int lds_rows) {
+    clahe_apply_body<kVec16, kLds, false>(src, dst, lut, g, band, lds_rows);
+}
+template <bool kVec16, bool kLds>
+__global__ __launch_bounds__(kThreads) void clahe_apply_refs_kernel(const gf_frame_ref* refs, uint8_t* dst, const uint8_t* __restrict__ lut, Geom g, int band, int lds_rows) {
+    clahe_apply_body<kVec16, kLds, true>(reinterpret_cast<const uint8_t*>(refs), dst, lut, g, band, lds_rows);
 }
 
 }  // namespace gfclahe

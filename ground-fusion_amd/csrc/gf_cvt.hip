@@ -3,6 +3,7 @@
 // tracker (gf_tracker_cfg.pixel_format) and exported as its own C-ABI.
 #include <hip/hip_runtime.h>
 #include <climits>
+#include <type_traits>
 
 #include "../../include/groundfusion_hip.h"
 #include "gf_cvt_kernels.hpp"
@@ -59,6 +60,49 @@ int cvt_launch(const uint8_t* d_src, size_t src_pitch, int format, uint8_t* d_ds
     else if (ch == 1) cvt_launch_ch<1>(d_src, src_pitch, red_at, d_dst, batch, w, h, stream);
     else if (ch == 3) cvt_launch_ch<3>(d_src, src_pitch, red_at, d_dst, batch, w, h, stream);
     else cvt_launch_ch<4>(d_src, src_pitch, red_at, d_dst, batch, w, h, stream);
+    HIPCHK(hipGetLastError());
+    return GF_OK;
+}
+
+// The same conversion with the frames where the caller keeps them: d_refs[b] (device-readable, [batch]) names frame b, h_refs is the same table as the host reads
+// it (the caller has checked its entries: gfref::check).  Each frame takes the form its own pointer and pitch allow; the launch of a form is left out when no
+// frame of the call takes it.  *n_bytes (optional): the frames that took a byte form although the size has a dword form.
+int cvt_launch_refs(const gf_frame_ref* d_refs, const gf_frame_ref* h_refs, int format, uint8_t* d_dst, int batch, int w, int h, hipStream_t stream, int* n_bytes) {
+    using namespace gfcvt;
+    if (int rc = cvt_check((size_t)w * gfpix::channels(format), format, batch, w, h)) return rc;
+    const int ch = gfpix::channels(format), red_at = gfpix::red_at(format);
+    const bool bayer = gfpix::is_bayer(format);
+    const bool dst_dwords = !((reinterpret_cast<uintptr_t>(d_dst) | (size_t)w) & 3) && (!bayer || w >= 8);   // the part of raw_dwords() that is not the frame's
+    int n_dw = 0;
+    for (int b = 0; b < batch; b++) n_dw += gfref::form(reinterpret_cast<uintptr_t>(h_refs[b].data), h_refs[b].pitch) >= 4 ? 1 : 0;
+    if (!dst_dwords) n_dw = 0;
+    const int n_by = batch - n_dw;
+    if (n_bytes) *n_bytes = dst_dwords ? n_by : 0;
+    const int byte_want = dst_dwords ? 0 : -1;
+    const unsigned gy = (unsigned)std::min(batch, 65535);
+    const int npx = bayer ? 4 : !(w & 15) ? 16 : 4;
+    const dim3 gv(bayer ? raw_blocks((size_t)w / 4, ((size_t)h + kBayerBand - 1) / kBayerBand) : raw_blocks((size_t)w / npx, (size_t)h), gy), gb(raw_blocks((size_t)w, (size_t)h), gy);
+    auto gray = [&](auto chc) {
+        constexpr int CH = decltype(chc)::value;
+        if (n_dw && npx == 16) cvt_gray_vec_refs_kernel<CH, 16><<<gv, kThreads, 0, stream>>>(d_refs, 1, d_dst, batch, w, h, red_at);
+        else if (n_dw) cvt_gray_vec_refs_kernel<CH, 4><<<gv, kThreads, 0, stream>>>(d_refs, 1, d_dst, batch, w, h, red_at);
+        if (n_by) cvt_gray_byte_refs_kernel<CH><<<gb, kThreads, 0, stream>>>(d_refs, byte_want, d_dst, batch, w, h, red_at);
+    };
+    auto pair = [&](auto m16c, int luma_at) {
+        constexpr bool M16 = decltype(m16c)::value;
+        if (n_dw && npx == 16) cvt_pair_vec_refs_kernel<M16, 16><<<gv, kThreads, 0, stream>>>(d_refs, 1, d_dst, batch, w, h, luma_at);
+        else if (n_dw) cvt_pair_vec_refs_kernel<M16, 4><<<gv, kThreads, 0, stream>>>(d_refs, 1, d_dst, batch, w, h, luma_at);
+        if (n_by) cvt_pair_byte_refs_kernel<M16><<<gb, kThreads, 0, stream>>>(d_refs, byte_want, d_dst, batch, w, h, luma_at);
+    };
+    if (bayer) {
+        const int gf = gfpix::bayer_green_first(format), br = gfpix::bayer_blue_row0(format);
+        if (n_dw) cvt_bayer_vec_refs_kernel<<<gv, kThreads, 0, stream>>>(d_refs, 1, d_dst, batch, w, h, gf, br);
+        if (n_by) cvt_bayer_byte_refs_kernel<<<gb, kThreads, 0, stream>>>(d_refs, byte_want, d_dst, batch, w, h, gf, br);
+    } else if (format == GF_PIX_MONO16) pair(std::true_type{}, 0);
+    else if (ch == 2) pair(std::false_type{}, gfpix::luma_at(format));
+    else if (ch == 1) gray(std::integral_constant<int, 1>{});
+    else if (ch == 3) gray(std::integral_constant<int, 3>{});
+    else gray(std::integral_constant<int, 4>{});
     HIPCHK(hipGetLastError());
     return GF_OK;
 }

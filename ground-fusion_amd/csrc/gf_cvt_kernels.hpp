@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "gf_pixfmt.hpp"
+#include "gf_frame_ref.hpp"
 
 namespace gfcvt {
 
@@ -28,12 +29,12 @@ template <int N> struct __attribute__((packed, aligned(4))) Dwords { uint32_t v[
 template <int CH, int NPX> __device__ __forceinline__ unsigned byte_of(const Dwords<NPX * CH / 4>& s, int k) { return (s.v[k >> 2] >> (8 * (k & 3))) & 255u; }
 
 template <int CH, int NPX>
-__global__ __launch_bounds__(kThreads) void cvt_gray_vec_kernel(const uint8_t* __restrict__ src, size_t src_pitch, uint8_t* __restrict__ dst, int batch, int w, int h, int red_at) {
+__device__ __forceinline__ void cvt_gray_vec_thread(unsigned bx, unsigned tx, unsigned by, unsigned gy, const uint8_t* __restrict__ src, size_t src_pitch, uint8_t* __restrict__ dst, int batch, int w, int h, int red_at) {
     const int per_row = w / NPX;
-    const unsigned p = blockIdx.x * kThreads + threadIdx.x;   // piece of the frame; the host keeps per_row * h below 2^31
+    const unsigned p = bx * kThreads + tx;   // piece of the frame; the host keeps per_row * h below 2^31
     if (p >= (unsigned)per_row * (unsigned)h) return;
     const int y = p / per_row, xp = p - y * per_row;
-    for (int b = blockIdx.y; b < batch; b += gridDim.y) {
+    for (int b = by; b < batch; b += gy) {
         const Dwords<NPX * CH / 4> s = *reinterpret_cast<const Dwords<NPX * CH / 4>*>(src + ((size_t)b * h + y) * src_pitch + (size_t)xp * (NPX * CH));
         Dwords<NPX / 4> o;
 #pragma unroll
@@ -55,16 +56,24 @@ __global__ __launch_bounds__(kThreads) void cvt_gray_vec_kernel(const uint8_t* _
         *reinterpret_cast<Dwords<NPX / 4>*>(dst + ((size_t)b * h + y) * w + (size_t)xp * NPX) = o;
     }
 }
+template <int CH, int NPX>
+__global__ __launch_bounds__(kThreads) void cvt_gray_vec_kernel(const uint8_t* __restrict__ src, size_t src_pitch, uint8_t* __restrict__ dst, int batch, int w, int h, int red_at) {
+    cvt_gray_vec_thread<CH, NPX>(blockIdx.x, threadIdx.x, blockIdx.y, gridDim.y, src, src_pitch, dst, batch, w, h, red_at);
+}
 
 template <int CH>
-__global__ __launch_bounds__(kThreads) void cvt_gray_byte_kernel(const uint8_t* __restrict__ src, size_t src_pitch, uint8_t* __restrict__ dst, int batch, int w, int h, int red_at) {
-    const unsigned p = blockIdx.x * kThreads + threadIdx.x;   // pixel of the frame; the host keeps w * h below 2^31
+__device__ __forceinline__ void cvt_gray_byte_thread(unsigned bx, unsigned tx, unsigned by, unsigned gy, const uint8_t* __restrict__ src, size_t src_pitch, uint8_t* __restrict__ dst, int batch, int w, int h, int red_at) {
+    const unsigned p = bx * kThreads + tx;   // pixel of the frame; the host keeps w * h below 2^31
     if (p >= (unsigned)w * (unsigned)h) return;
     const int y = p / w, x = p - y * w;
-    for (int b = blockIdx.y; b < batch; b += gridDim.y) {
+    for (int b = by; b < batch; b += gy) {
         const uint8_t* s = src + ((size_t)b * h + y) * src_pitch + (size_t)x * CH;
         dst[((size_t)b * h + y) * w + x] = CH == 1 ? s[0] : gfpix::gray(s[red_at], s[1], s[2 - red_at]);
     }
+}
+template <int CH>
+__global__ __launch_bounds__(kThreads) void cvt_gray_byte_kernel(const uint8_t* __restrict__ src, size_t src_pitch, uint8_t* __restrict__ dst, int batch, int w, int h, int red_at) {
+    cvt_gray_byte_thread<CH>(blockIdx.x, threadIdx.x, blockIdx.y, gridDim.y, src, src_pitch, dst, batch, w, h, red_at);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- raw formats
@@ -220,5 +229,46 @@ __global__ __launch_bounds__(kThreads) void cvt_bayer_vec_kernel(const uint8_t* 
 __global__ __launch_bounds__(kThreads) void cvt_bayer_byte_kernel(const uint8_t* __restrict__ src, size_t src_pitch, uint8_t* __restrict__ dst, int batch, int w, int h, int green_first, int blue_row0) {
     cvt_bayer_byte_thread(blockIdx.x, threadIdx.x, blockIdx.y, gridDim.y, src, src_pitch, dst, batch, w, h, green_first, blue_row0);
 }
+
+
+// ---------------------------------------------------------------------------------------------------------------- frames by reference
+// The six kernels above with the source frames where the caller keeps them: frame b is refs[b] (gf_frame_ref: pointer of row 0, bytes from row to row), the
+// destination stays `batch` tight h x w frames.  The form is the frame's own, decided block by block from its entry: a launch of a dword form (want_dwords = 1)
+// serves the frames whose pointer and pitch are multiples of 4 and skips the others, a launch of a byte form with want_dwords = 0 serves exactly those others,
+// with want_dwords < 0 every frame (sizes that have no dword form).  The host launches the forms the call's frames need (cvt_launch_refs): one launch when they
+// agree, two when they are mixed.  Each frame runs the thread function of the tight kernel as a batch of one, so the arithmetic and the loads are the same.
+__device__ __forceinline__ bool refs_serves(const gfref::Frame& f, int want_dwords) {
+    return want_dwords < 0 || (gfref::form(reinterpret_cast<uintptr_t>(f.data), f.pitch) >= 4) == (want_dwords != 0);
+}
+#define GF_CVT_REFS_LOOP(CALL)                                                       \
+    for (int b = blockIdx.y; b < batch; b += gridDim.y) {                            \
+        const gfref::Frame f = gfref::entry(refs, b);                                \
+        if (!refs_serves(f, want_dwords)) continue;                                  \
+        uint8_t* d = dst + (size_t)b * h * w;                                        \
+        CALL;                                                                        \
+    }
+template <int CH, int NPX>
+__global__ __launch_bounds__(kThreads) void cvt_gray_vec_refs_kernel(const gf_frame_ref* __restrict__ refs, int want_dwords, uint8_t* __restrict__ dst, int batch, int w, int h, int red_at) {
+    GF_CVT_REFS_LOOP((cvt_gray_vec_thread<CH, NPX>(blockIdx.x, threadIdx.x, 0, 1, f.data, f.pitch, d, 1, w, h, red_at)))
+}
+template <int CH>
+__global__ __launch_bounds__(kThreads) void cvt_gray_byte_refs_kernel(const gf_frame_ref* __restrict__ refs, int want_dwords, uint8_t* __restrict__ dst, int batch, int w, int h, int red_at) {
+    GF_CVT_REFS_LOOP((cvt_gray_byte_thread<CH>(blockIdx.x, threadIdx.x, 0, 1, f.data, f.pitch, d, 1, w, h, red_at)))
+}
+template <bool M16, int NPX>
+__global__ __launch_bounds__(kThreads) void cvt_pair_vec_refs_kernel(const gf_frame_ref* __restrict__ refs, int want_dwords, uint8_t* __restrict__ dst, int batch, int w, int h, int luma_at) {
+    GF_CVT_REFS_LOOP((cvt_pair_vec_thread<M16, NPX>(blockIdx.x, threadIdx.x, 0, 1, f.data, f.pitch, d, 1, w, h, luma_at)))
+}
+template <bool M16>
+__global__ __launch_bounds__(kThreads) void cvt_pair_byte_refs_kernel(const gf_frame_ref* __restrict__ refs, int want_dwords, uint8_t* __restrict__ dst, int batch, int w, int h, int luma_at) {
+    GF_CVT_REFS_LOOP((cvt_pair_byte_thread<M16>(blockIdx.x, threadIdx.x, 0, 1, f.data, f.pitch, d, 1, w, h, luma_at)))
+}
+__global__ __launch_bounds__(kThreads) void cvt_bayer_vec_refs_kernel(const gf_frame_ref* __restrict__ refs, int want_dwords, uint8_t* __restrict__ dst, int batch, int w, int h, int green_first, int blue_row0) {
+    GF_CVT_REFS_LOOP((cvt_bayer_vec_thread(blockIdx.x, threadIdx.x, 0, 1, f.data, f.pitch, d, 1, w, h, green_first, blue_row0)))
+}
+__global__ __launch_bounds__(kThreads) void cvt_bayer_byte_refs_kernel(const gf_frame_ref* __restrict__ refs, int want_dwords, uint8_t* __restrict__ dst, int batch, int w, int h, int green_first, int blue_row0) {
+    GF_CVT_REFS_LOOP((cvt_bayer_byte_thread(blockIdx.x, threadIdx.x, 0, 1, f.data, f.pitch, d, 1, w, h, green_first, blue_row0)))
+}
+#undef GF_CVT_REFS_LOOP
 
 }  // namespace gfcvt

@@ -286,6 +286,12 @@ __global__ void __launch_bounds__(256) roi_pack_kernel(const uint8_t* __restrict
                                                        size_t seq_words) {
     gfroi::pack_thread(masks + (size_t)blockIdx.z * h * w, (size_t)w, w, h, blockIdx.y, blockIdx.x * 256 + threadIdx.x, table + (size_t)list_entry(seq_of, blockIdx.z) * seq_words);
 }
+// The same from masks that lie where the caller keeps them (gf_tracker_set_roi_some_device_refs): mask i is refs[i], any pointer, any pitch >= w (byte loads).
+__global__ void __launch_bounds__(256) roi_pack_refs_kernel(const gf_frame_ref* __restrict__ refs, const int* __restrict__ seq_of, int w, int h, uint32_t* __restrict__ table,
+                                                            size_t seq_words) {
+    const gfref::Frame f = gfref::entry(refs, blockIdx.z);
+    gfroi::pack_thread(f.data, f.pitch, w, h, blockIdx.y, blockIdx.x * 256 + threadIdx.x, table + (size_t)list_entry(seq_of, blockIdx.z) * seq_words);
+}
 
 // Both selection kernels run one block per list position and touch only tables of the call ([count], by position): the candidates, want, the output and the
 // call's depth frames.  Nothing here is kept per sequence, so the same list reaches both by construction.
@@ -330,8 +336,9 @@ __device__ __forceinline__ void bitonic_desc(P keys, int npow2, int tid, int nth
 // LDS from the back end's kernels.  Sequences that want more than kTopKMax corners (the first frame, a lost scene) are left to select_corners_kernel.
 constexpr int kTopKMax = 16;
 constexpr int kTopKQ = 4;   // candidates per thread held in registers (4 096 per sequence; more are streamed from global memory every round)
-__global__ void __launch_bounds__(1024) select_topk_kernel(SelectArgs A) {
-    __shared__ unsigned long long s_best[3];
+// REFS (here and in select_corners_body): A.depth is the call's table of gf_frame_ref instead of tight frames (gfref::depth_at).
+template <bool REFS>
+__device__ __forceinline__ void select_topk_body(const SelectArgs& A, unsigned long long* s_best) {
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int want = A.want[b];
     if (want <= 0) { if (tid == 0) A.out_n[b] = 0; return; }
@@ -405,17 +412,26 @@ __global__ void __launch_bounds__(1024) select_topk_kernel(SelectArgs A) {
         }
         if (tid == 0) {
             A.out_pts[(size_t)b * A.out_cap + nacc] = make_float2((float)x, (float)y);
-            A.out_depth[(size_t)b * A.out_cap + nacc] = A.depth ? A.depth[b * A.depth_seq_stride + (size_t)y * A.depth_stride + x] : (uint16_t)0;
+            A.out_depth[(size_t)b * A.out_cap + nacc] = A.depth ? gfref::depth_at<REFS>(A.depth, A.depth_seq_stride, A.depth_stride, b, y, x) : (uint16_t)0;
         }
         nacc++;
         last = best;
     }
     if (tid == 0) A.out_n[b] = nacc;
 }
+__global__ void __launch_bounds__(1024) select_topk_kernel(SelectArgs A) {
+    __shared__ unsigned long long s_best[3];
+    select_topk_body<false>(A, s_best);
+}
+__global__ void __launch_bounds__(1024) select_topk_refs_kernel(SelectArgs A) {
+    __shared__ unsigned long long s_best[3];
+    select_topk_body<true>(A, s_best);
+}
 
 // One 1024-thread block per sequence: sort candidates (value desc, address desc), then wavefront 0 runs the
 // greedy minimum-distance selection 64 candidates at a time against a cell grid of accepted corners.
-__global__ void __launch_bounds__(1024) select_corners_kernel(SelectArgs A) {
+template <bool REFS>
+__device__ __forceinline__ void select_corners_body(const SelectArgs& A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int want = A.want[b];
@@ -506,7 +522,7 @@ __global__ void __launch_bounds__(1024) select_corners_kernel(SelectArgs A) {
                 rec[3 * naccept + 2] = head[yc * gw + xc];
                 head[yc * gw + xc] = (short)naccept;
                 A.out_pts[(size_t)b * A.out_cap + naccept] = make_float2((float)ax, (float)ay);
-                A.out_depth[(size_t)b * A.out_cap + naccept] = A.depth ? A.depth[b * A.depth_seq_stride + (size_t)ay * A.depth_stride + ax] : (uint16_t)0;
+                A.out_depth[(size_t)b * A.out_cap + naccept] = A.depth ? gfref::depth_at<REFS>(A.depth, A.depth_seq_stride, A.depth_stride, b, ay, ax) : (uint16_t)0;
             }
             naccept++;
             if (min_dist >= 1 && lane > l && good) {
@@ -521,5 +537,7 @@ __global__ void __launch_bounds__(1024) select_corners_kernel(SelectArgs A) {
     }
     if (lane == 0) A.out_n[b] = naccept;
 }
+__global__ void __launch_bounds__(1024) select_corners_kernel(SelectArgs A) { select_corners_body<false>(A); }
+__global__ void __launch_bounds__(1024) select_corners_refs_kernel(SelectArgs A) { select_corners_body<true>(A); }
 
 }  // namespace gf

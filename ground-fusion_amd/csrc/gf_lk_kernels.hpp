@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gf_frame_ref.hpp"
+
 namespace gf {
 
 constexpr int kPad = 32;        // border (pixels) around every pyramid level; rows stay 16-byte aligned
@@ -54,16 +56,21 @@ __device__ __forceinline__ int list_entry(const int* __restrict__ table, unsigne
 
 // Level 0: copy the raw frame into the padded pyramid and synthesise the REFLECT_101 border.
 // One thread per 4 destination bytes; grid.y = list position.
-__global__ void __launch_bounds__(256) pyr_level0_kernel(const uint8_t* __restrict__ raw, size_t raw_seq_stride, int raw_stride,
-                                                         uint8_t* __restrict__ pyr, size_t pyr_bytes, const int* __restrict__ cur_of, LevelGeom g) {
+// REFS (here and in the two kernels that follow): where the frames lie, gfref::frame_at -- false: back to back from `raw` (the handle's own buffers and the tight
+// entry points), true: `raw` is the call's table of gf_frame_ref, and the piece a frame is loaded in follows that frame's own pointer and pitch, block by block.
+template <bool REFS>
+__device__ __forceinline__ void pyr_level0_body(const uint8_t* __restrict__ raw, size_t raw_seq_stride, int raw_stride,
+                                                uint8_t* __restrict__ pyr, size_t pyr_bytes, const int* __restrict__ cur_of, LevelGeom g) {
     const int pw = g.w + 2 * kPad, ph = g.h + 2 * kPad;
     const int qw = pw >> 2;
     int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= qw * ph) return;
     int py = t / qw, px = (t - py * qw) << 2;
-    const uint8_t* src = raw + blockIdx.y * raw_seq_stride + (size_t)reflect101(py - kPad, g.h) * raw_stride;
+    const gfref::Frame f = gfref::frame_at<REFS>(raw, raw_seq_stride, (size_t)raw_stride, blockIdx.y);
+    const uint8_t* src = f.data + (size_t)reflect101(py - kPad, g.h) * f.pitch;
+    const bool dwords = REFS ? !((reinterpret_cast<uintptr_t>(f.data) | f.pitch | (size_t)g.w) & 3) : !((raw_stride | g.w) & 3);
     uint32_t v = 0;
-    if (px >= kPad && px + 3 < kPad + g.w && !((raw_stride | g.w) & 3)) v = *reinterpret_cast<const uint32_t*>(src + (px - kPad));   // interior: one aligned dword
+    if (px >= kPad && px + 3 < kPad + g.w && dwords) v = *reinterpret_cast<const uint32_t*>(src + (px - kPad));   // interior: one aligned dword
     else {
 #pragma unroll
         for (int k = 0; k < 4; k++) v |= (uint32_t)src[reflect101(px + k - kPad, g.w)] << (8 * k);
@@ -71,19 +78,30 @@ __global__ void __launch_bounds__(256) pyr_level0_kernel(const uint8_t* __restri
     uint8_t* dst = pyr + (size_t)list_entry(cur_of, blockIdx.y) * pyr_bytes + g.img_off - kPad * g.stride - kPad;
     *reinterpret_cast<uint32_t*>(dst + (size_t)py * g.stride + px) = v;
 }
+__global__ void __launch_bounds__(256) pyr_level0_kernel(const uint8_t* __restrict__ raw, size_t raw_seq_stride, int raw_stride,
+                                                         uint8_t* __restrict__ pyr, size_t pyr_bytes, const int* __restrict__ cur_of, LevelGeom g) {
+    pyr_level0_body<false>(raw, raw_seq_stride, raw_stride, pyr, pyr_bytes, cur_of, g);
+}
+__global__ void __launch_bounds__(256) pyr_level0_refs_kernel(const gf_frame_ref* __restrict__ refs, uint8_t* __restrict__ pyr, size_t pyr_bytes, const int* __restrict__ cur_of, LevelGeom g) {
+    pyr_level0_body<true>(reinterpret_cast<const uint8_t*>(refs), 0, 0, pyr, pyr_bytes, cur_of, g);
+}
 
 // The same with 16 destination bytes per thread, for frames whose width, row pitch and base address are multiples of 16 (640 x 480: every interior group
-// is one aligned 16-byte load and one aligned 16-byte store; the 2 x 2 border groups of a row gather their mirror bytes).
-__global__ void __launch_bounds__(256) pyr_level0_vec16_kernel(const uint8_t* __restrict__ raw, size_t raw_seq_stride, int raw_stride,
-                                                               uint8_t* __restrict__ pyr, size_t pyr_bytes, const int* __restrict__ cur_of, LevelGeom g) {
+// is one aligned 16-byte load and one aligned 16-byte store; the 2 x 2 border groups of a row gather their mirror bytes).  By reference the width decides the
+// launch and a frame that is not 16-byte aligned gathers its interior groups byte by byte as well.
+template <bool REFS>
+__device__ __forceinline__ void pyr_level0_vec16_body(const uint8_t* __restrict__ raw, size_t raw_seq_stride, int raw_stride,
+                                                      uint8_t* __restrict__ pyr, size_t pyr_bytes, const int* __restrict__ cur_of, LevelGeom g) {
     const int pw = g.w + 2 * kPad, ph = g.h + 2 * kPad;
     const int qw = pw >> 4;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= qw * ph) return;
     const int py = t / qw, px = (t - py * qw) << 4;
-    const uint8_t* src = raw + blockIdx.y * raw_seq_stride + (size_t)reflect101(py - kPad, g.h) * raw_stride;
+    const gfref::Frame f = gfref::frame_at<REFS>(raw, raw_seq_stride, (size_t)raw_stride, blockIdx.y);
+    const uint8_t* src = f.data + (size_t)reflect101(py - kPad, g.h) * f.pitch;
+    const bool al16 = !REFS || gfref::form(reinterpret_cast<uintptr_t>(f.data), f.pitch) == 16;
     uint4 v;
-    if (px >= kPad && px + 15 < kPad + g.w) v = *reinterpret_cast<const uint4*>(src + (px - kPad));
+    if (px >= kPad && px + 15 < kPad + g.w && al16) v = *reinterpret_cast<const uint4*>(src + (px - kPad));
     else {
         uint32_t w4[4] = {0, 0, 0, 0};
 #pragma unroll
@@ -92,6 +110,13 @@ __global__ void __launch_bounds__(256) pyr_level0_vec16_kernel(const uint8_t* __
     }
     uint8_t* dst = pyr + (size_t)list_entry(cur_of, blockIdx.y) * pyr_bytes + g.img_off - kPad * g.stride - kPad;
     *reinterpret_cast<uint4*>(dst + (size_t)py * g.stride + px) = v;
+}
+__global__ void __launch_bounds__(256) pyr_level0_vec16_kernel(const uint8_t* __restrict__ raw, size_t raw_seq_stride, int raw_stride,
+                                                               uint8_t* __restrict__ pyr, size_t pyr_bytes, const int* __restrict__ cur_of, LevelGeom g) {
+    pyr_level0_vec16_body<false>(raw, raw_seq_stride, raw_stride, pyr, pyr_bytes, cur_of, g);
+}
+__global__ void __launch_bounds__(256) pyr_level0_vec16_refs_kernel(const gf_frame_ref* __restrict__ refs, uint8_t* __restrict__ pyr, size_t pyr_bytes, const int* __restrict__ cur_of, LevelGeom g) {
+    pyr_level0_vec16_body<true>(reinterpret_cast<const uint8_t*>(refs), 0, 0, pyr, pyr_bytes, cur_of, g);
 }
 
 // pyrDown (5-tap [1 4 6 4 1] separable, (s+128)>>8) from level l to l+1, written over the whole padded
@@ -272,8 +297,11 @@ __global__ void __launch_bounds__(512) pyr_down_tail_kernel(uint8_t* __restrict_
 // (32 us).  Needs an even height and a width that is a multiple of 16; other sizes keep the two kernels.
 constexpr int kHeadRows = 16;
 __host__ __device__ inline size_t pyr_head_lds_bytes(int w0) { return (size_t)(2 * kHeadRows + 3) * (w0 + 8) + (size_t)kHeadRows * (w0 / 2); }
-__global__ void __launch_bounds__(512) pyr_head_kernel(const uint8_t* __restrict__ raw, size_t raw_seq_stride, int raw_stride,
-                                                       uint8_t* __restrict__ pyr, size_t pyr_bytes, const int* __restrict__ cur_of, LevelGeom g0, LevelGeom g1) {
+// By reference (REFS) the load phase follows the frame: 16-byte pieces as above, dwords for rows on 4-byte boundaries, single bytes for any other pointer or pitch;
+// LDS holds the same bytes afterwards and the rest of the kernel is the same code.
+template <bool REFS>
+__device__ __forceinline__ void pyr_head_body(const uint8_t* __restrict__ raw, size_t raw_seq_stride, int raw_stride,
+                                              uint8_t* __restrict__ pyr, size_t pyr_bytes, const int* __restrict__ cur_of, LevelGeom g0, LevelGeom g1) {
     extern __shared__ __attribute__((aligned(16))) uint8_t head_sm[];
     const int tid = threadIdx.x;
     const int r0 = blockIdx.x * kHeadRows, r1 = min(g1.h, r0 + kHeadRows);   // this block's rows of level 1
@@ -281,15 +309,28 @@ __global__ void __launch_bounds__(512) pyr_head_kernel(const uint8_t* __restrict
     const int SA = g0.w + 8;                                                // LDS row: 4 mirrored bytes, w pixels, 4 mirrored bytes (a multiple of 8)
     uint8_t* A = head_sm;
     uint8_t* Bq = head_sm + (size_t)(2 * kHeadRows + 3) * SA;               // the band of level 1, no borders
-    const uint8_t* src = raw + blockIdx.y * raw_seq_stride;
+    const gfref::Frame f = gfref::frame_at<REFS>(raw, raw_seq_stride, (size_t)raw_stride, blockIdx.y);
+    const uint8_t* src = f.data;
+    const int piece = REFS ? gfref::form(reinterpret_cast<uintptr_t>(f.data), f.pitch) : 16;   // block-uniform
     uint8_t* base = pyr + (size_t)list_entry(cur_of, blockIdx.y) * pyr_bytes;
-    {
+    if (piece == 16) {
         const int qi = g0.w >> 4;
         for (int t = tid; t < qi * nrow; t += 512) {
             const int yy = t / qi, u = t - yy * qi;
-            const uint4 v = *reinterpret_cast<const uint4*>(src + (size_t)reflect101(ya + yy, g0.h) * raw_stride + 16 * u);
+            const uint4 v = *reinterpret_cast<const uint4*>(src + (size_t)reflect101(ya + yy, g0.h) * f.pitch + 16 * u);
             uint32_t* dst = reinterpret_cast<uint32_t*>(A + (size_t)yy * SA + 4 + 16 * u);
             dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
+        }
+    } else if (piece == 4) {
+        const int qi = g0.w >> 2;
+        for (int t = tid; t < qi * nrow; t += 512) {
+            const int yy = t / qi, u = t - yy * qi;
+            *reinterpret_cast<uint32_t*>(A + (size_t)yy * SA + 4 + 4 * u) = *reinterpret_cast<const uint32_t*>(src + (size_t)reflect101(ya + yy, g0.h) * f.pitch + 4 * u);
+        }
+    } else {
+        for (int t = tid; t < g0.w * nrow; t += 512) {
+            const int yy = t / g0.w, x = t - yy * g0.w;
+            A[(size_t)yy * SA + 4 + x] = src[(size_t)reflect101(ya + yy, g0.h) * f.pitch + x];
         }
     }
     __syncthreads();
@@ -330,6 +371,13 @@ __global__ void __launch_bounds__(512) pyr_head_kernel(const uint8_t* __restrict
     }
     __syncthreads();
     write_padded_rows(base, g1, Bq, r0, r0, r1);
+}
+__global__ void __launch_bounds__(512) pyr_head_kernel(const uint8_t* __restrict__ raw, size_t raw_seq_stride, int raw_stride,
+                                                       uint8_t* __restrict__ pyr, size_t pyr_bytes, const int* __restrict__ cur_of, LevelGeom g0, LevelGeom g1) {
+    pyr_head_body<false>(raw, raw_seq_stride, raw_stride, pyr, pyr_bytes, cur_of, g0, g1);
+}
+__global__ void __launch_bounds__(512) pyr_head_refs_kernel(const gf_frame_ref* __restrict__ refs, uint8_t* __restrict__ pyr, size_t pyr_bytes, const int* __restrict__ cur_of, LevelGeom g0, LevelGeom g1) {
+    pyr_head_body<true>(reinterpret_cast<const uint8_t*>(refs), 0, 0, pyr, pyr_bytes, cur_of, g0, g1);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -626,7 +674,7 @@ struct LkBatchArgs {
     uint8_t* status;      // [count][cap] out: after fwd, reverse check, inBorder and brightness test
     uint8_t* fwd_status;  // [count][cap] out: status of the forward pass alone (feature_tracker.cpp:124-130 counts these)
     uint16_t* depth_out;  // [count][cap] out: depth(round(y),round(x)) for status==1 (0 if no depth)
-    const uint16_t* depth;   // [count] raw depth frames (may be null)
+    const uint16_t* depth;   // [count] raw depth frames (may be null); in the _refs kernels the call's table of gf_frame_ref, [count], in its place
     size_t depth_seq_stride; int depth_stride;
     unsigned* counters;   // [count][cap][2] out: level passes, iterations
     int fwd_max_level;    // 3 (feature_tracker.cpp:132,135) or 1 (hasPrediction, :121)
@@ -640,8 +688,9 @@ struct LkBatchArgs {
 // grid.x = ceil(cap/4) blocks of 4 wavefronts, grid.y = list position.  Forward LK (feature_tracker.cpp:118-135),
 // reverse LK and flow-back test (:138-153), inBorder and the brightness test with the reference's swapped
 // row/column indexing (:155-168).
-__global__ void __launch_bounds__(256, 7) lk_track_kernel(PyrGeom G, LkBatchArgs A) {
-    __shared__ __attribute__((aligned(16))) uint8_t tiles[4 * kTileBytes];
+// REFS (here and in lk_track_mp_body): A.depth is the call's table of gf_frame_ref instead of tight frames (gfref::depth_at).
+template <bool REFS>
+__device__ __forceinline__ void lk_track_body(const PyrGeom& G, const LkBatchArgs& A, uint8_t* tiles) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int b = blockIdx.y;
     const int i = blockIdx.x * 4 + wave;
@@ -690,12 +739,20 @@ __global__ void __launch_bounds__(256, 7) lk_track_kernel(PyrGeom G, LkBatchArgs
         uint16_t d = 0;
         if (st && A.depth && A.post_checks) {
             const int ry = (int)round((double)cy), rx = (int)round((double)cx);
-            d = A.depth[b * A.depth_seq_stride + (size_t)ry * A.depth_stride + rx];
+            d = gfref::depth_at<REFS>(A.depth, A.depth_seq_stride, A.depth_stride, b, ry, rx);
         }
         A.depth_out[pi] = d;
         A.counters[2 * pi] = n_levels;
         A.counters[2 * pi + 1] = n_iters;
     }
+}
+__global__ void __launch_bounds__(256, 7) lk_track_kernel(PyrGeom G, LkBatchArgs A) {
+    __shared__ __attribute__((aligned(16))) uint8_t tiles[4 * kTileBytes];
+    lk_track_body<false>(G, A, tiles);
+}
+__global__ void __launch_bounds__(256, 7) lk_track_refs_kernel(PyrGeom G, LkBatchArgs A) {
+    __shared__ __attribute__((aligned(16))) uint8_t tiles[4 * kTileBytes];
+    lk_track_body<true>(G, A, tiles);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -929,9 +986,8 @@ __device__ __forceinline__ int lk_solve_mp(const PyrGeom& G, const uint8_t* imI,
 }
 
 // P points per wavefront, four wavefronts per block: grid.x = ceil(cap / (4 P)), grid.y = list position.  Same outputs as lk_track_kernel, bit for bit.
-template <int P>
-__global__ void __launch_bounds__(256, P == 4 ? 2 : 3) lk_track_mp_kernel(PyrGeom G, LkBatchArgs A) {
-    __shared__ __attribute__((aligned(16))) uint8_t tiles[4 * P * kTileBytes];
+template <int P, bool REFS>
+__device__ __forceinline__ void lk_track_mp_body(const PyrGeom& G, const LkBatchArgs& A, uint8_t* tiles) {
     constexpr int SH = LkGroup<P>::SH;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int b = blockIdx.y;
@@ -984,12 +1040,22 @@ __global__ void __launch_bounds__(256, P == 4 ? 2 : 3) lk_track_mp_kernel(PyrGeo
         uint16_t d = 0;
         if (st && A.depth && A.post_checks) {
             const int ry = (int)round((double)cy), rx = (int)round((double)cx);
-            d = A.depth[b * A.depth_seq_stride + (size_t)ry * A.depth_stride + rx];
+            d = gfref::depth_at<REFS>(A.depth, A.depth_seq_stride, A.depth_stride, b, ry, rx);
         }
         A.depth_out[po] = d;
         A.counters[2 * po] = n_levels;
         A.counters[2 * po + 1] = n_iters;
     }
+}
+template <int P>
+__global__ void __launch_bounds__(256, P == 4 ? 2 : 3) lk_track_mp_kernel(PyrGeom G, LkBatchArgs A) {
+    __shared__ __attribute__((aligned(16))) uint8_t tiles[4 * P * kTileBytes];
+    lk_track_mp_body<P, false>(G, A, tiles);
+}
+template <int P>
+__global__ void __launch_bounds__(256, P == 4 ? 2 : 3) lk_track_mp_refs_kernel(PyrGeom G, LkBatchArgs A) {
+    __shared__ __attribute__((aligned(16))) uint8_t tiles[4 * P * kTileBytes];
+    lk_track_mp_body<P, true>(G, A, tiles);
 }
 
 // The derivative image of one level as lk_solve evaluates it (same device functions), for gf_pyramid_level's parity check against calcSharrDeriv:

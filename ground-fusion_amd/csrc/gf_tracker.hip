@@ -31,6 +31,7 @@
 #include "gf_detect_kernels.hpp"
 #include "gf_lk_kernels.hpp"
 #include "gf_copy_list.hpp"
+#include "gf_frame_ref.hpp"
 #include "gf_host_cpus.hpp"
 #include "gf_hip_own.hpp"
 #include "gf_pixfmt.hpp"
@@ -44,6 +45,9 @@ size_t clahe_lut_bytes(int batch, int tiles_x, int tiles_y);
 int clahe_launch(const uint8_t* d_src, uint8_t* d_dst, uint8_t* d_lut, int batch, int w, int h, double clip_limit, int tiles_x, int tiles_y, hipStream_t stream);
 // gf_cvt.hip: cv_bridge::toCvCopy(msg, MONO8) on `batch` frames, src_pitch bytes from row to row (gf_tracker_cfg.pixel_format)
 int cvt_launch(const uint8_t* d_src, size_t src_pitch, int format, uint8_t* d_dst, int batch, int w, int h, hipStream_t stream);
+// the table forms of the two (gf_frame_ref.hpp): frame b of the source lies at refs[b]
+int clahe_launch_refs(const gf_frame_ref* d_refs, uint8_t* d_dst, uint8_t* d_lut, int batch, int w, int h, double clip_limit, int tiles_x, int tiles_y, hipStream_t stream);
+int cvt_launch_refs(const gf_frame_ref* d_refs, const gf_frame_ref* h_refs, int format, uint8_t* d_dst, int batch, int w, int h, hipStream_t stream, int* n_bytes);
 constexpr double kClaheClip = 40.0;   // cv::createCLAHE() defaults (rosNodeTest.cpp:258)
 constexpr int kClaheTiles = 8;
 
@@ -201,6 +205,10 @@ struct gf_tracker {
     std::vector<DiskTable> seq_disk; DevBuf<DiskTable> d_seq_disk;
     DevBuf<int> d_seq_md; PinBuf<int> h_seq_md;
     DevBuf<uint8_t> d_seq_fb; PinBuf<uint8_t> h_seq_fb;
+    // Frames by reference (gf_frame_ref.hpp; the _refs entry points): the call's table, [0, B) the gray frames and [B, 2 B) the depth frames by list position.
+    // Obtained by the first _refs call of the handle, like the tables above.  It travels like the list: the first kernel of a call reads the page-locked h_refs
+    // over the bus, the copy list in front of LK / the detection carries it to d_refs for the depth samples of those kernels.
+    DevBuf<gf_frame_ref> d_refs; PinBuf<gf_frame_ref> h_refs;
 
     std::unique_ptr<HostPool> pool;
 };
@@ -241,13 +249,15 @@ template <class V> static void reduce_vector(std::vector<V>& v, const uint8_t* s
 // buildOpticalFlowPyramid in three launches: level 0 (copy + REFLECT_101 border), level 1 (interior + border in one pass), and one kernel for
 // all remaining levels.  There is no derivative pyramid: lk_solve evaluates the Scharr derivative of the template window itself.
 // d_raw_frames: `count` frames back to back, frame i for the sequence at list position i; cur_of[i]: the pyramid it is written to (device-readable, [count]).
-static int launch_pyramid(gf_tracker* h, const uint8_t* d_raw_frames, int count, const int* cur_of) {
+// refs (the _refs entry points, MONO8 without equalisation): the frames lie at refs[i] instead (device-readable table; d_raw_frames is not read).  The kernel
+// follows the sizes as before and each block takes the load form its own frame's pointer and pitch allow.  *widest: the widest piece of the launched first reader.
+static int launch_pyramid(gf_tracker* h, const uint8_t* d_raw_frames, int count, const int* cur_of, const gf_frame_ref* refs = nullptr, int* widest = nullptr) {
     const PyrGeom& G = h->G;
     const size_t seq_img = G.img_bytes;   // distance between two pyramids, whichever sequence and slot they belong to
     uint8_t* img = h->d_img.p;
     const LevelGeom g0 = G.lv[0];
     const bool v16 = !((g0.w | g0.stride | (int)(((size_t)g0.w * g0.h) & 15) | (int)(seq_img & 15) | (int)((g0.img_off - kPad * g0.stride - kPad) & 15)) & 15) &&
-                     !((reinterpret_cast<uintptr_t>(d_raw_frames) | reinterpret_cast<uintptr_t>(img)) & 15);
+                     !(((refs ? 0 : reinterpret_cast<uintptr_t>(d_raw_frames)) | reinterpret_cast<uintptr_t>(img)) & 15);
     bool vec = true;   // four-pixel kernels need level widths (and with them strides, offsets) that are multiples of 4
     for (int l = 0; l < G.nlevels; l++) vec = vec && !(G.lv[l].w & 3) && !(G.lv[l].img_off & 3);
     for (int l = 1; l < G.nlevels; l++) vec = vec && G.lv[l].w > kPad + 1 && G.lv[l].h > kPad + 1;   // one reflection reaches every border pixel
@@ -257,16 +267,21 @@ static int launch_pyramid(gf_tracker* h, const uint8_t* d_raw_frames, int count,
     gf_tracker_stats& st = h->stats;
     if (head) {
         st.pyr_head++;
-        pyr_head_kernel<<<dim3((G.lv[1].h + kHeadRows - 1) / kHeadRows, count), 512, pyr_head_lds_bytes(g0.w), h->stream>>>(d_raw_frames, (size_t)g0.w * g0.h, g0.w, img, seq_img, cur_of, g0, G.lv[1]);
+        const dim3 grid((G.lv[1].h + kHeadRows - 1) / kHeadRows, count);
+        if (refs) pyr_head_refs_kernel<<<grid, 512, pyr_head_lds_bytes(g0.w), h->stream>>>(refs, img, seq_img, cur_of, g0, G.lv[1]);
+        else pyr_head_kernel<<<grid, 512, pyr_head_lds_bytes(g0.w), h->stream>>>(d_raw_frames, (size_t)g0.w * g0.h, g0.w, img, seq_img, cur_of, g0, G.lv[1]);
     } else if (v16) {
         st.pyr_level0_vec16++;
         const int n = ((g0.w + 2 * kPad) / 16) * (g0.h + 2 * kPad);
-        pyr_level0_vec16_kernel<<<dim3((n + 255) / 256, count), 256, 0, h->stream>>>(d_raw_frames, (size_t)g0.w * g0.h, g0.w, img, seq_img, cur_of, g0);
+        if (refs) pyr_level0_vec16_refs_kernel<<<dim3((n + 255) / 256, count), 256, 0, h->stream>>>(refs, img, seq_img, cur_of, g0);
+        else pyr_level0_vec16_kernel<<<dim3((n + 255) / 256, count), 256, 0, h->stream>>>(d_raw_frames, (size_t)g0.w * g0.h, g0.w, img, seq_img, cur_of, g0);
     } else {
         st.pyr_level0_dword++;
         const int n = ((g0.w + 2 * kPad) / 4) * (g0.h + 2 * kPad);
-        pyr_level0_kernel<<<dim3((n + 255) / 256, count), 256, 0, h->stream>>>(d_raw_frames, (size_t)g0.w * g0.h, g0.w, img, seq_img, cur_of, g0);
+        if (refs) pyr_level0_refs_kernel<<<dim3((n + 255) / 256, count), 256, 0, h->stream>>>(refs, img, seq_img, cur_of, g0);
+        else pyr_level0_kernel<<<dim3((n + 255) / 256, count), 256, 0, h->stream>>>(d_raw_frames, (size_t)g0.w * g0.h, g0.w, img, seq_img, cur_of, g0);
     }
+    if (widest) *widest = head || v16 ? 16 : 4;
     if (vec) {
         auto down = [&](int l) {
             const LevelGeom d = G.lv[l];
@@ -302,8 +317,15 @@ static int launch_pyramid_one(gf_tracker* h, const uint8_t* d_raw_frame, int slo
     return launch_pyramid(h, d_raw_frame, 1, h->d_cur.p);
 }
 
-static void launch_lk(gf_tracker* h, int batch, const LkBatchArgs& A) {   // one LK launch over the `batch` listed sequences in the form the handle was created for (same results in every form)
+// depth_refs: A.depth is the call's table of gf_frame_ref (the _refs entry points with depth), read by the _refs forms of the same kernels
+static void launch_lk(gf_tracker* h, int batch, const LkBatchArgs& A, bool depth_refs = false) {   // one LK launch over the `batch` listed sequences in the form the handle was created for (same results in every form)
     const int cap = h->cap;
+    if (depth_refs) {
+        if (h->lk_points == 4) lk_track_mp_refs_kernel<4><<<dim3((cap + 15) / 16, batch), 256, 0, h->stream>>>(h->G, A);
+        else if (h->lk_points == 2) lk_track_mp_refs_kernel<2><<<dim3((cap + 7) / 8, batch), 256, 0, h->stream>>>(h->G, A);
+        else lk_track_refs_kernel<<<dim3((cap + 3) / 4, batch), 256, 0, h->stream>>>(h->G, A);
+        return;
+    }
     if (h->lk_points == 4) lk_track_mp_kernel<4><<<dim3((cap + 15) / 16, batch), 256, 0, h->stream>>>(h->G, A);
     else if (h->lk_points == 2) lk_track_mp_kernel<2><<<dim3((cap + 7) / 8, batch), 256, 0, h->stream>>>(h->G, A);
     else lk_track_kernel<<<dim3((cap + 3) / 4, batch), 256, 0, h->stream>>>(h->G, A);
@@ -433,11 +455,19 @@ static int check_stride(gf_tracker* h, int stride) {
 // feature (feature_tracker.cpp:360 `rightImg.at<ushort>(round(y), round(x))`), and on the host-image entry points both the image and the feature coordinates are on
 // the host anyway: sampling there keeps 614 KB per frame and sequence (two thirds of an RGB-D VGA frame) off the bus.  d_depth (device entry point) keeps the sample
 // in the kernels.  Same pixel, same rounding (round half away from zero on the float coordinates), same u16.
+//
+// gray_refs / depth_refs (the _refs entry points; checked by the caller, d_gray and d_depth null): the frames lie where the caller's tables say, one entry per
+// list position.  The tables go into h_refs with the list and only the first kernel that reads a caller's frame -- conversion, CLAHE or the pyramid's level-0
+// reader, and the depth samples of LK and the selection -- addresses it through them; the tight entry points build nothing and run the kernels of before.
 static int track_core(gf_tracker* h, int count, const int* seq, const double* t, const uint8_t* d_gray, const uint16_t* d_depth, gf_feature_obs* out, int cap_out,
-                      int* n_out, const uint16_t* const* hdep = nullptr, int hdstride = 0) {
+                      int* n_out, const uint16_t* const* hdep = nullptr, int hdstride = 0, const gf_frame_ref* gray_refs = nullptr, const gf_frame_ref* depth_refs = nullptr) {
     const int N = count, cap = h->cap, W = h->cfg.width, H = h->cfg.height;
     if (N == 0) return GF_OK;
-    const bool have_depth = d_depth != nullptr || hdep != nullptr;
+    const bool have_depth = d_depth != nullptr || hdep != nullptr || depth_refs != nullptr;
+    if (gray_refs) {
+        for (int i = 0; i < N; i++) { h->h_refs.p[i] = gray_refs[i]; h->h_refs.p[h->B + i] = depth_refs ? depth_refs[i] : gf_frame_ref{nullptr, 0}; }
+        if (depth_refs) d_depth = reinterpret_cast<const uint16_t*>(h->d_refs.p + h->B);   // what the _refs forms of LK and the selection read in the place of tight frames
+    }
     const bool prof = h->profiling;
     using clk = std::chrono::steady_clock;
     auto tp = clk::now();
@@ -473,19 +503,37 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
     const bool over_bus = lists && h->h_cur.hd;
     if (!over_bus) HIPCHK(hipMemcpyAsync(h->d_cur.p, h->h_cur.p, (size_t)N * sizeof(int), hipMemcpyHostToDevice, h->stream));
     const int* cur_of = over_bus ? h->h_cur.hd : h->d_cur.p;
+    // the frame table goes the same two ways; its depth half is wanted on the device by LK and the selection (refs_down: with the first copy list that leaves)
+    const bool refs_bus = gray_refs && over_bus && h->h_refs.hd;
+    if (gray_refs && !refs_bus) HIPCHK(hipMemcpyAsync(h->d_refs.p, h->h_refs.p, (size_t)2 * h->B * sizeof(gf_frame_ref), hipMemcpyHostToDevice, h->stream));
+    const gf_frame_ref* refs = !gray_refs ? nullptr : refs_bus ? h->h_refs.hd : h->d_refs.p;
+    bool refs_down = refs_bus && depth_refs;
+    int refs_widest = 16, refs_narrow = -1;   // the widest piece of the first reader of the caller's frames; frames it counted itself
     if (prof) HIPCHK(hipEventRecord(h->ev[0], h->stream));
-    if (h->cfg.pixel_format) {   // rosNodeTest.cpp:238-254: toCvCopy(msg, MONO8) ahead of CLAHE and trackImage; d_gray holds tight frames of the handle's format by list position, never written
+    if (h->cfg.pixel_format && refs) {
+        if (int rc = cvt_launch_refs(refs, h->h_refs.p, h->cfg.pixel_format, h->d_cvt.p, N, W, H, h->stream, &refs_narrow)) return rc;
+        d_gray = h->d_cvt.p; refs = nullptr;
+        if (prof) HIPCHK(hipEventRecord(h->ev[8], h->stream));
+    } else if (h->cfg.pixel_format) {   // rosNodeTest.cpp:238-254: toCvCopy(msg, MONO8) ahead of CLAHE and trackImage; d_gray holds tight frames of the handle's format by list position, never written
         if (int rc = cvt_launch(d_gray, (size_t)W * h->ch, h->cfg.pixel_format, h->d_cvt.p, N, W, H, h->stream)) return rc;
         d_gray = h->d_cvt.p;
         if (prof) HIPCHK(hipEventRecord(h->ev[8], h->stream));
     }
-    if (h->cfg.equalize) {   // rosNodeTest.cpp:256-261: CLAHE on the gray frame before trackImage, into the handle's buffer (the caller's frames stay as they are); frames and LUTs by list position
+    if (h->cfg.equalize && refs) {
+        if (int rc = clahe_launch_refs(refs, h->d_eq.p, h->d_eq_lut.p, N, W, H, kClaheClip, kClaheTiles, kClaheTiles, h->stream)) return rc;
+        d_gray = h->d_eq.p; refs = nullptr; refs_widest = (W & 15) ? 4 : 16;
+        if (prof) HIPCHK(hipEventRecord(h->ev[7], h->stream));
+    } else if (h->cfg.equalize) {   // rosNodeTest.cpp:256-261: CLAHE on the gray frame before trackImage, into the handle's buffer (the caller's frames stay as they are); frames and LUTs by list position
         if (int rc = clahe_launch(d_gray, h->d_eq.p, h->d_eq_lut.p, N, W, H, kClaheClip, kClaheTiles, kClaheTiles, h->stream)) return rc;
         d_gray = h->d_eq.p;
         if (prof) HIPCHK(hipEventRecord(h->ev[7], h->stream));
     }
-    if (int rc = launch_pyramid(h, d_gray, N, cur_of)) return rc;
+    if (int rc = launch_pyramid(h, d_gray, N, cur_of, refs, refs ? &refs_widest : nullptr)) return rc;
     if (prof) HIPCHK(hipEventRecord(h->ev[1], h->stream));
+    if (gray_refs) {
+        if (refs_narrow < 0) { refs_narrow = 0; for (int i = 0; i < N; i++) refs_narrow += gfref::unaligned(reinterpret_cast<uintptr_t>(gray_refs[i].data), gray_refs[i].pitch, refs_widest) ? 1 : 0; }
+        h->stats.frames_unaligned += refs_narrow;
+    }
 
     // ---- temporal optical flow (feature_tracker.cpp:113-176)
     bool any_prev = false, any_pred = false, any_plain = false;
@@ -505,6 +553,7 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
     bool lk_timed = false;
     if (any_prev) {
         if (over_bus) down(h->d_cur, h->h_cur, N);
+        if (refs_down) { down(h->d_refs, h->h_refs, (size_t)2 * h->B); refs_down = false; }
         down(h->d_npts, h->h_npts, N);
         if (h->d_seq_fb.p) { for (int i = 0; i < N; i++) h->h_seq_fb.p[i] = (uint8_t)h->par[seq[i]].flow_back; down(h->d_seq_fb, h->h_seq_fb, N); }
         down(h->d_prev_pts, h->h_prev_pts, (size_t)N * cap);
@@ -517,8 +566,8 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
         }
         if (int rc = flush()) return rc;
         if (prof) HIPCHK(hipEventRecord(h->ev[2], h->stream));
-        if (any_plain) { launch_lk(h, N, lk_args(h, 3, 0, h->cfg.flow_back, 1, mask_plain, d_depth)); h->stats.lk_launches++; }
-        if (any_pred) { launch_lk(h, N, lk_args(h, 1, 1, h->cfg.flow_back, 1, mask_pred, d_depth)); h->stats.lk_launches++; }
+        if (any_plain) { launch_lk(h, N, lk_args(h, 3, 0, h->cfg.flow_back, 1, mask_plain, d_depth), depth_refs != nullptr); h->stats.lk_launches++; }
+        if (any_pred) { launch_lk(h, N, lk_args(h, 1, 1, h->cfg.flow_back, 1, mask_pred, d_depth), depth_refs != nullptr); h->stats.lk_launches++; }
         HIPCHK(hipGetLastError());
         if (prof) { HIPCHK(hipEventRecord(h->ev[3], h->stream)); lk_timed = true; }
         up(h->h_cur_pts, h->d_cur_pts, (size_t)N * cap);
@@ -549,7 +598,7 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
             std::vector<uint16_t> keep_depth(h->h_depth_out.p, h->h_depth_out.p + (size_t)N * cap);
             std::vector<unsigned> keep_cnt(h->h_counters.p, h->h_counters.p + (size_t)N * cap * 2);
             HIPCHK(hipMemcpyAsync(h->d_seqmask.p, h->h_seqmask.p, N, hipMemcpyHostToDevice, h->stream));
-            launch_lk(h, N, lk_args(h, 3, 0, h->cfg.flow_back, 1, h->d_seqmask.p, d_depth));
+            launch_lk(h, N, lk_args(h, 3, 0, h->cfg.flow_back, 1, h->d_seqmask.p, d_depth), depth_refs != nullptr);
             h->stats.lk_launches++;
             HIPCHK(hipGetLastError());
             up(h->h_cur_pts, h->d_cur_pts, (size_t)N * cap);
@@ -614,6 +663,7 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
     // ---- Shi-Tomasi top-up (feature_tracker.cpp:190-206)
     if (any_want) {
         down(h->d_det, h->h_det, N);
+        if (refs_down) { down(h->d_refs, h->h_refs, (size_t)2 * h->B); refs_down = false; }
         down(h->d_centers, h->h_centers, (size_t)N * cap);
         down(h->d_ncenters, h->h_ncenters, N);
         down(h->d_want, h->h_want, N);
@@ -641,8 +691,13 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
             int max_want = 0;
             for (int i = 0; i < N; i++) max_want = std::max(max_want, h->h_want.p[i]);
             S.skip_small = topk_on ? 1 : 0;
-            if (topk_on) select_topk_kernel<<<dim3(N), 1024, 0, h->stream>>>(S);
-            if (!topk_on || max_want > kTopKMax) select_corners_kernel<<<dim3(N), 1024, h->select_lds, h->stream>>>(S);
+            if (depth_refs) {   // S.depth is the call's table: the _refs forms of the same two kernels
+                if (topk_on) select_topk_refs_kernel<<<dim3(N), 1024, 0, h->stream>>>(S);
+                if (!topk_on || max_want > kTopKMax) select_corners_refs_kernel<<<dim3(N), 1024, h->select_lds, h->stream>>>(S);
+            } else {
+                if (topk_on) select_topk_kernel<<<dim3(N), 1024, 0, h->stream>>>(S);
+                if (!topk_on || max_want > kTopKMax) select_corners_kernel<<<dim3(N), 1024, h->select_lds, h->stream>>>(S);
+            }
         }
         HIPCHK(hipGetLastError());
         up(h->h_out_n, h->d_out_n, N);
@@ -825,6 +880,45 @@ int gf_tracker_track_some_device(gf_tracker* h, int count, const int* seq, const
     return gf::track_core(h, count, seq, t, (const uint8_t*)d_gray, (const uint16_t*)d_depth, out, cap, n_out);
 }
 
+// ---- the same with one gf_frame_ref per listed sequence (gf_frame_ref.hpp)
+namespace gf {
+static int refs_ready(gf_tracker* h) {   // the first _refs call of a handle: the table and its device copy, and the _refs form of the sort kernel gets the LDS the handle's own got
+    if (h->h_refs.p) return GF_OK;
+    DevBuf<gf_frame_ref> dev; PinBuf<gf_frame_ref> pin;
+    HIPCHK(dev.alloc((size_t)2 * h->B)); HIPCHK(pin.alloc((size_t)2 * h->B));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(select_corners_refs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->select_lds));
+    h->d_refs = std::move(dev); h->h_refs = std::move(pin);
+    return GF_OK;
+}
+// every entry of a table of `count`, or GF_ERR_INVALID naming the list position; what: "gray", "depth" or "mask"
+static int check_refs(const gf_tracker* h, int count, const int* seq, const gf_frame_ref* refs, size_t row_bytes, bool u16, const char* what) {
+    for (int i = 0; i < count; i++) {
+        const gfref::Verdict v = gfref::check(refs[i], row_bytes, u16, u16 && !h->par[seq[i]].depth_cam);
+        if (v != gfref::kOk)
+            return set_err(GF_ERR_INVALID, "%s frame at list position %d (sequence %d): %s (data %p, pitch %zu bytes, a row is %zu bytes)", what, i, seq[i], gfref::verdict_text(v), refs[i].data, refs[i].pitch, row_bytes);
+    }
+    return GF_OK;
+}
+}  // namespace gf
+
+int gf_tracker_track_some_device_refs(gf_tracker* h, int count, const int* seq, const double* t, const gf_frame_ref* gray, const gf_frame_ref* depth,
+                                      gf_feature_obs* out, int cap, int* n_out) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (int rc = gf::check_list(h, count, seq)) return rc;
+    if (count == 0) return GF_OK;
+    if (!gray) return gf::set_err(GF_ERR_INVALID, "null table of gray frames");
+    if (!t || !out || !n_out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (int rc = gf::check_refs(h, count, seq, gray, (size_t)h->cfg.width * h->ch, false, "gray")) return rc;
+    if (depth) if (int rc = gf::check_refs(h, count, seq, depth, (size_t)h->cfg.width * 2, true, "depth")) return rc;
+    if (int rc = gf::refs_ready(h)) return rc;
+    return gf::track_core(h, count, seq, t, nullptr, nullptr, out, cap, n_out, nullptr, 0, gray, depth);
+}
+
+int gf_tracker_track_batch_device_refs(gf_tracker* h, const double* t, const gf_frame_ref* gray, const gf_frame_ref* depth, gf_feature_obs* out, int cap, int* n_out) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    return gf_tracker_track_some_device_refs(h, h->B, h->ident.data(), t, gray, depth, out, cap, n_out);
+}
+
 int gf_tracker_track_some(gf_tracker* h, int count, const int* seq, const double* t, const uint8_t* const* gray, int stride, const uint16_t* const* depth, int dstride,
                           gf_feature_obs* out, int cap, int* n_out) {
     if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
@@ -972,6 +1066,29 @@ int gf_tracker_set_roi_some_device(gf_tracker* h, int count, const int* seq, con
     const int W = h->cfg.width, H = h->cfg.height;
     HIPCHK(hipMemcpyAsync(h->d_roi_seq.p, seq, (size_t)count * sizeof(int), hipMemcpyHostToDevice, h->stream));
     gf::roi_pack_kernel<<<dim3((W + 255) / 256, gfroi::bands(H), count), 256, 0, h->stream>>>((const uint8_t*)d_masks, h->d_roi_seq.p, W, H, h->d_roi.p, h->roi_words);
+    HIPCHK(hipGetLastError());
+    for (int i = 0; i < count; i++) {   // the words come back: setMask's walk reads them on the host
+        const size_t off = (size_t)seq[i] * h->roi_words;
+        HIPCHK(hipMemcpyAsync(h->roi_bits.data() + off, h->d_roi.p + off, h->roi_words * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < count; i++) h->roi_has[seq[i]] = 1;
+    return GF_OK;
+}
+
+int gf_tracker_set_roi_some_device_refs(gf_tracker* h, int count, const int* seq, const gf_frame_ref* masks) {
+    if (!masks) return gf_tracker_set_roi_some_device(h, count, seq, nullptr);   // clears, as there
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (int rc = gf::check_list(h, count, seq)) return rc;
+    if (count == 0) return GF_OK;
+    const int W = h->cfg.width, H = h->cfg.height;
+    if (int rc = gf::check_refs(h, count, seq, masks, (size_t)W, false, "mask")) return rc;
+    if (int rc = gf::roi_ready(h)) return rc;
+    if (int rc = gf::refs_ready(h)) return rc;
+    for (int i = 0; i < count; i++) h->h_refs.p[i] = masks[i];
+    HIPCHK(hipMemcpyAsync(h->d_refs.p, h->h_refs.p, (size_t)count * sizeof(gf_frame_ref), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_roi_seq.p, seq, (size_t)count * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    gf::roi_pack_refs_kernel<<<dim3((W + 255) / 256, gfroi::bands(H), count), 256, 0, h->stream>>>(h->d_refs.p, h->d_roi_seq.p, W, H, h->d_roi.p, h->roi_words);
     HIPCHK(hipGetLastError());
     for (int i = 0; i < count; i++) {   // the words come back: setMask's walk reads them on the host
         const size_t off = (size_t)seq[i] * h->roi_words;

@@ -53,6 +53,23 @@ def pix_of_encoding(encoding):
     return PIX_OF_ENCODING.get(encoding, PIX_RAW_OF_ENCODING.get(encoding))
 
 
+class FrameRef(C.Structure):
+    """gf_frame_ref: a frame where it lives on the device -- the address of row 0 and the bytes from row to row"""
+    _fields_ = [("data", C.c_void_p), ("pitch", C.c_size_t)]
+
+
+def frame_refs(refs):
+    """a gf_frame_ref table from (address, pitch) pairs; None or address 0 = a null entry.  torch: (t.data_ptr(), t.stride(0) * t.element_size()).
+    A table made earlier is handed back as it is: a caller whose surfaces stay where they are builds it once."""
+    if isinstance(refs, C.Array):
+        return refs
+    table = (FrameRef * max(len(refs), 1))()
+    for i, r in enumerate(refs):
+        if r is not None:
+            table[i].data, table[i].pitch = (int(r[0]) or None), int(r[1])
+    return table
+
+
 class FeatureObs(C.Structure):
     _fields_ = [("id", C.c_int), ("camera_id", C.c_int), ("v", C.c_double * 8)]
 
@@ -64,7 +81,7 @@ class TrackerStats(C.Structure):
                 ("lk_level_passes", C.c_longlong), ("lk_iterations", C.c_longlong), ("tracked_features", C.c_longlong),
                 ("output_features", C.c_longlong), ("select_streamed", C.c_longlong), ("select_global_sort", C.c_longlong),
                 ("ms_equalize", C.c_double), ("pyr_head", C.c_longlong), ("pyr_level0_vec16", C.c_longlong), ("pyr_level0_dword", C.c_longlong),
-                ("pyr_down_tail", C.c_longlong), ("pyr_down_pad4", C.c_longlong), ("pyr_down_bytes", C.c_longlong), ("ms_convert", C.c_double),
+                ("pyr_down_tail", C.c_longlong), ("pyr_down_pad4", C.c_longlong), ("pyr_down_bytes", C.c_longlong), ("frames_unaligned", C.c_longlong), ("ms_convert", C.c_double),
                 ("sequence_frames", C.c_longlong)]
 
 
@@ -72,7 +89,8 @@ OBS_DTYPE = np.dtype([("id", np.int32), ("camera_id", np.int32), ("v", np.float6
 assert OBS_DTYPE.itemsize == C.sizeof(FeatureObs)
 
 EXPORTS = ["gf_last_error", "gf_device_count", "gf_set_device", "gf_tracker_create", "gf_tracker_destroy", "gf_tracker_track",
-           "gf_tracker_track_batch", "gf_tracker_track_batch_device", "gf_tracker_track_some", "gf_tracker_track_some_device", "gf_tracker_prefetch_some", "gf_tracker_set_prediction", "gf_tracker_remove_outliers",
+           "gf_tracker_track_batch", "gf_tracker_track_batch_device", "gf_tracker_track_some", "gf_tracker_track_some_device", "gf_tracker_prefetch_some",
+           "gf_tracker_track_some_device_refs", "gf_tracker_track_batch_device_refs", "gf_tracker_set_roi_some_device_refs", "gf_tracker_set_prediction", "gf_tracker_remove_outliers",
            "gf_tracker_set_roi", "gf_tracker_set_roi_some_device", "gf_tracker_get_roi",
            "gf_tracker_set_seq_cfg", "gf_tracker_get_seq_cfg", "gf_tracker_reset_seq",
            "gf_tracker_get_state", "gf_tracker_set_profiling", "gf_tracker_get_stats", "gf_tracker_reset_stats", "gf_lk_track",
@@ -194,6 +212,40 @@ class FeatureTracker:
                                                 out.ctypes.data_as(C.POINTER(FeatureObs)), self.cap, _p(n_out, C.c_int)))
         return self._unpack(out, n_out[:N]) if unpack else n_out[:N]
 
+    def trackImageSomeDeviceRefs(self, seqs, ts, gray_refs, depth_refs=None, unpack=True, out=None, n_out=None):
+        """gf_tracker_track_some_device_refs: gray_refs[i] = (device address of row 0, bytes from row to row) of the frame of sequence seqs[i], wherever it lies
+        and however it is aligned (its own allocation, the luma plane of an NV12 surface, a crop); depth_refs likewise for u16 depth frames (None: no depth; an
+        entry None for a sequence whose own depth_cam is 0).  Nothing behind a ref is written.  unpack / out / n_out as trackImageSomeDevice."""
+        seqs, N = self._seqs(seqs)
+        ts = np.ascontiguousarray(ts, np.float64)
+        assert len(ts) == N and (gray_refs is None or len(gray_refs) == N) and (depth_refs is None or len(depth_refs) == N)
+        if out is None:
+            if not hasattr(self, "_out"):
+                self._out = np.zeros((self.cfg.batch, self.cap), OBS_DTYPE)
+                self._n = np.zeros(self.cfg.batch, np.int32)
+            out, n_out = self._out, self._n
+        assert out.ndim == 2 and out.shape[0] >= min(N, self.cfg.batch) and out.shape[1] == self.cap and out.dtype == OBS_DTYPE and out.flags.c_contiguous
+        assert n_out.shape[0] >= min(N, self.cfg.batch) and n_out.dtype == np.int32 and n_out.flags.c_contiguous
+        _chk(lib().gf_tracker_track_some_device_refs(self.h, N, _p(seqs, C.c_int), _p(ts, C.c_double), None if gray_refs is None else frame_refs(gray_refs),
+                                                     None if depth_refs is None else frame_refs(depth_refs),
+                                                     out.ctypes.data_as(C.POINTER(FeatureObs)), self.cap, _p(n_out, C.c_int)))
+        return self._unpack(out, n_out[:N]) if unpack else n_out[:N]
+
+    def trackImageBatchDeviceRefs(self, ts, gray_refs, depth_refs=None, unpack=True, out=None, n_out=None):
+        """gf_tracker_track_batch_device_refs: trackImageSomeDeviceRefs for every sequence, refs in sequence order"""
+        B = self.cfg.batch
+        ts = np.ascontiguousarray(ts, np.float64)
+        assert len(ts) == B and len(gray_refs) == B and (depth_refs is None or len(depth_refs) == B)
+        if out is None:
+            if not hasattr(self, "_out"):
+                self._out = np.zeros((B, self.cap), OBS_DTYPE)
+                self._n = np.zeros(B, np.int32)
+            out, n_out = self._out, self._n
+        assert out.shape == (B, self.cap) and out.dtype == OBS_DTYPE and out.flags.c_contiguous and n_out.shape == (B,) and n_out.dtype == np.int32
+        _chk(lib().gf_tracker_track_batch_device_refs(self.h, _p(ts, C.c_double), frame_refs(gray_refs), None if depth_refs is None else frame_refs(depth_refs),
+                                                      out.ctypes.data_as(C.POINTER(FeatureObs)), self.cap, _p(n_out, C.c_int)))
+        return self._unpack(out, n_out) if unpack else n_out
+
     def _pitched(self, a, dtype, pitch):
         """a height x width image whose rows lie `pitch` elements apart (a view of a wider array, e.g. a cropped frame): passed as it is, not copied"""
         if dtype == np.uint8 and self.channels > 1:   # colour rows: [height, width, channels], `pitch` bytes from row to row
@@ -299,6 +351,13 @@ class FeatureTracker:
         seqs[i] (complete when the call is made); None / 0 clears the listed sequences"""
         seqs, N = self._seqs(seqs)
         _chk(lib().gf_tracker_set_roi_some_device(self.h, N, _p(seqs, C.c_int), C.c_void_p(d_masks_ptr) if d_masks_ptr else None))
+
+    def set_roi_device_refs(self, seqs, mask_refs):
+        """gf_tracker_set_roi_some_device_refs: mask_refs[i] = (device address of row 0, bytes from row to row) of the [height, width] u8 mask of sequence
+        seqs[i], e.g. a crop of a larger tensor (complete when the call is made); None clears the listed sequences"""
+        seqs, N = self._seqs(seqs)
+        assert mask_refs is None or len(mask_refs) == N
+        _chk(lib().gf_tracker_set_roi_some_device_refs(self.h, N, _p(seqs, C.c_int), None if mask_refs is None else frame_refs(mask_refs)))
 
     def get_roi(self, seq=0):
         """gf_tracker_get_roi: the stored region of sequence `seq` as a [height, width] u8 image of 0 / 255, or None if it has none"""

@@ -133,6 +133,26 @@ class FeatureTracker {
         refresh();
         return featureFrame;
     }
+    // The same frame where it already lives on the device (gf_tracker_track_some_device_refs): _img = device pointer of row 0 and bytes from row to row of a
+    // row x col image in pixel_format (any alignment: the luma plane of a decoder's NV12 surface, a crop of a wider image), _img1 = the u16 depth image likewise
+    // or {nullptr, 0}.  The frame size must be known (readIntrinsicParameter / setIntrinsics): a device pointer carries none.  Neither image is ever written.
+    FeatureFrame trackImage(double _cur_time, const gf_frame_ref& _img, const gf_frame_ref& _img1 = gf_frame_ref{nullptr, 0}, int pixel_format = GF_PIX_MONO8) {
+        if (!row || !col) throw std::runtime_error("trackImage: the frame size is not known yet (readIntrinsicParameter / setIntrinsics)");
+        if (!h_) { pixel_format_ = pixel_format; create(col, row); }
+        if (pixel_format != pixel_format_) throw std::runtime_error("trackImage: the image's pixel format differs from the first frame's");
+        std::vector<gf_feature_obs> out((size_t)((MAX_CNT + 3) & ~3));
+        int n = 0;
+        const int seq = 0;
+        check(gf_tracker_track_some_device_refs(h_, 1, &seq, &_cur_time, &_img, _img1.data ? &_img1 : nullptr, out.data(), (int)out.size(), &n));
+        FeatureFrame featureFrame;
+        for (int i = 0; i < n; i++) {
+            Obs8 o;
+            for (int k = 0; k < 8; k++) o[k] = out[i].v[k];
+            featureFrame[out[i].id].emplace_back(out[i].camera_id, o);
+        }
+        refresh();
+        return featureFrame;
+    }
 #ifdef GF_WITH_OPENCV
     // rgb_order: the channel order of a CV_8UC3 / CV_8UC4 image -- false: OpenCV's own B, G, R(, A) (bgr8 / bgra8), true: R, G, B(, A) (rgb8 / rgba8, what a RealSense
     // colour topic carries and cv_bridge::toCvShare hands on unconverted).  A cv::Mat does not record it, so the caller states it.

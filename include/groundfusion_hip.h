@@ -62,7 +62,8 @@ typedef struct gf_tracker_cfg {
      * demosaic fused with that luma sum (cvtColor(COLOR_Bayer??2GRAY), generic loop), YUV 4:2:2 by taking the luma bytes, MONO16 by (v + 128) / 257 on
      * little-endian pixels.  The caller's frames are never written.  Host entry points: `stride` is bytes per row and must be >= width x bytes per pixel;
      * the staged path copies the frame as it is under the previous frame's kernels and converts on the tracking stream once the copy has landed.  Device entry
-     * points: the frames are tight height x width x bytes per pixel, back to back in list order.  One handle has one format: a fleet of cameras with mixed
+     * points: the frames are tight height x width x bytes per pixel, back to back in list order, or -- the _refs forms -- one pointer and row pitch per listed
+     * sequence (gf_frame_ref).  One handle has one format: a fleet of cameras with mixed
      * encodings uses one handle per encoding.  Anything outside GF_PIX_MONO8 .. GF_PIX_BGRA8 and GF_PIX_BAYER_RGGB8 .. GF_PIX_MONO16 is refused by gf_tracker_create. */
     int pixel_format;
 } gf_tracker_cfg;
@@ -98,6 +99,10 @@ typedef struct gf_tracker_stats {
      * pyr_head: levels 0 + 1 in one kernel; pyr_level0_vec16 / pyr_level0_dword: level 0 alone in 16- / 4-byte pieces; pyr_down_tail: levels 2 .. 3 in one kernel;
      * pyr_down_pad4: one level >= 1 in four-pixel pieces; pyr_down_bytes: one level >= 1 one byte per thread */
     long long pyr_head, pyr_level0_vec16, pyr_level0_dword, pyr_down_tail, pyr_down_pad4, pyr_down_bytes;
+    /* frames handed over by reference (gf_frame_ref) that missed the widest load form of the first kernel that read them, summed over the listed sequences of
+     * the _refs calls: pointer or pitch no multiple of 16 where the pyramid or CLAHE reads the caller's frame, no multiple of 4 where a conversion kernel does;
+     * 0 on a handle that only uses the other entry points */
+    long long frames_unaligned;
     double ms_convert;           /* the colour / raw -> MONO8 kernel of gf_tracker_cfg.pixel_format (hipEvents, like ms_equalize; part of ms_total_gpu); 0 on a MONO8 handle */
     long long sequence_frames;   /* listed sequences summed over the calls (`frames` counts the calls): frames x batch for the lock-step entry points; stays the last member */
 } gf_tracker_stats;
@@ -147,6 +152,25 @@ int gf_tracker_track_some(gf_tracker* h, int count, const int* seq, const double
 /* trackImage (feature_tracker.h:47) on device images: d_gray / d_depth hold the `count` frames of the listed sequences back to back, in list order */
 int gf_tracker_track_some_device(gf_tracker* h, int count, const int* seq, const double* t, const void* d_gray, const void* d_depth,
                                  gf_feature_obs* out, int cap, int* n_out);
+/* A frame that already lives on the device, where its producer keeps it: the device pointer (current device) of the first byte of row 0 and the bytes from one
+ * row to the next.  Any byte alignment of both; pitch >= width x bytes per pixel of the handle's pixel_format.  Frames of one call may lie in different
+ * allocations, be views into larger surfaces (the luma plane of an NV12 / I420 surface, a crop of a wider image) and may alias each other.  Nothing behind a
+ * gf_frame_ref is ever written. */
+typedef struct gf_frame_ref { const void* data; size_t pitch; } gf_frame_ref;
+/* trackImage (feature_tracker.h:47) on device images that are handed over by reference: gray[i] is the frame of seq[i] in the handle's pixel_format (height rows
+ * of width x bytes per pixel), depth is NULL or one entry per listed sequence of u16 millimetres (data and pitch even; an entry with data == NULL is allowed
+ * exactly for a sequence whose depth_cam is 0).  Every other property of the call -- list semantics, count == 0, sequences that sit out, setPrediction /
+ * removeOutliers, parameters per sequence, region of interest, equalize, statistics, synchronisation -- is that of gf_tracker_track_some_device, which is the
+ * case "frame i at base + i x frame bytes, pitch = row bytes" of the same path and gives the same bits for the same pixels.  Only the first kernel that reads the
+ * caller's memory addresses it through the table (16-byte pieces for a frame whose pointer and pitch are multiples of 16, dwords or bytes otherwise; one call may
+ * mix them; gf_tracker_stats.frames_unaligned counts the others); the handle's first such call allocates the table.  Refused with GF_ERR_INVALID, the message
+ * naming the list position, and nothing changed: a null table, a null data pointer where one is needed, a pitch shorter than a row, an odd depth pointer or
+ * pitch, and everything gf_tracker_track_some_device refuses.  The pointers are not validated beyond that. */
+int gf_tracker_track_some_device_refs(gf_tracker* h, int count, const int* seq, const double* t, const gf_frame_ref* gray, const gf_frame_ref* depth,
+                                      gf_feature_obs* out, int cap, int* n_out);
+/* trackImage (feature_tracker.h:47) on device images by reference for every sequence: the call above with the list 0 .. batch-1 */
+int gf_tracker_track_batch_device_refs(gf_tracker* h, const double* t, const gf_frame_ref* gray, const gf_frame_ref* depth,
+                                       gf_feature_obs* out, int cap, int* n_out);
 /* trackImage (feature_tracker.h:47), staged: as gf_tracker_prefetch_batch for the listed sequences.  The staged frame remembers its list, and the matching
  * gf_tracker_track_prefetched advances exactly those sequences, its t / out / n_out in the staged order; two staged frames may name different sets.  An empty
  * list is staged as well (its gf_tracker_track_prefetched does nothing), so that prefetch and track calls stay paired. */
@@ -176,6 +200,11 @@ int gf_tracker_set_roi(gf_tracker* h, int seq, const uint8_t* mask, int stride);
  * lives on the GPU).  Ordered on the handle's stream like the device frame entry points (the masks must be complete when the call is made); returns when the
  * table is written.  d_masks == NULL clears the listed sequences.  Leaves the very bits gf_tracker_set_roi leaves for the same image. */
 int gf_tracker_set_roi_some_device(gf_tracker* h, int count, const int* seq, const void* d_masks);
+/* The same with the masks where they lie, for the next FeatureTracker::trackImage (feature_tracker.h:47) of each listed sequence: masks[i] = pointer and pitch
+ * (>= width, any alignment) of the height x width byte image of seq[i], e.g. a channel or a crop of a segmentation network's output tensor; never written.
+ * masks == NULL clears the listed sequences.  Refusals as above plus a null data pointer or a pitch shorter than a row (the message names the list position);
+ * leaves the bits of the tight setter. */
+int gf_tracker_set_roi_some_device_refs(gf_tracker* h, int count, const int* seq, const gf_frame_ref* masks);
 /* *has = whether the sequence has a region; if so and mask != NULL, the stored region as 0 / 255 bytes, rows `stride` bytes apart (>= width) */
 int gf_tracker_get_roi(gf_tracker* h, int seq, uint8_t* mask, int stride, int* has);
 /* Parameters per sequence: what the reference keeps per FeatureTracker object (MAX_CNT, MIN_DIST, FLOW_BACK, depth_cam, m_camera; feature_tracker.h:76-98).
