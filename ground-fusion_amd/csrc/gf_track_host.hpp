@@ -1,0 +1,257 @@
+// gf_track_host.hpp — the host bookkeeping of ONE tracker sequence: what FeatureTracker (vins_estimator/src/featureTracker/feature_tracker.{h,cpp}) keeps in C++
+// around its image calls -- ids, track_cnt, n_id, the id -> point maps of the velocities, setMask's std::sort + greedy keep, the camera model, setPrediction and
+// removeOutliers -- and the per-sequence stages of a frame between the kernels of gf_tracker.hip.  Plain C++17 on host memory, no HIP header: the part of the
+// front end that must equal oracle/tracker_oracle.cpp's Tracker bit for bit builds into a stand-alone CPU program (tests/native/track_host.cpp) as it builds into
+// the library.  A stage works on one list position's rows of the hand-over tables, given by pointer; gf_tracker.hip owns the tables, the pool and the counters.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+#include <map>
+#include <set>
+#include <utility>
+#include <vector>
+
+#include "gf_roi.hpp"
+#include "gf_seq_cfg.hpp"
+
+namespace gf {
+
+struct P2f { float x, y; };   // a point, in SeqState and in the rows of the hand-over tables (the device side's float2)
+struct P2i { int x, y; };     // a circle centre of setMask (the device side's int2)
+
+struct SeqState {  // per-sequence FeatureTracker members (feature_tracker.h:76-98)
+    std::vector<P2f> prev_pts, cur_pts, predict_pts, prev_un_pts, cur_un_pts, pts_velocity;
+    std::vector<int> ids, track_cnt;
+    std::vector<uint16_t> cur_depth;
+    // cur_un_pts_map / prev_un_pts_map (feature_tracker.h:89): id -> point, kept as id-sorted vectors (ids are unique)
+    std::vector<std::pair<int, P2f>> cur_un_pts_map, prev_un_pts_map;
+    std::vector<int> grid_head, grid_next;  // scratch of set_mask_host
+    double cur_time = 0, prev_time = 0;
+    int n_id = 0;
+    bool hasPrediction = false;
+    bool started = false;   // the sequence has taken a frame since gf_tracker_create / gf_tracker_reset_seq: its parameters are fixed (gf_tracker_set_seq_cfg)
+    int slot = 1;   // which of the sequence's two pyramids holds its newest frame; flipped when the sequence takes a frame, and only then (the first frame goes to 0)
+};
+
+static inline int cvRoundf(float v) { return (int)lrintf(v); }
+
+// camodocal PinholeCamera (camera_models/src/camera_models/PinholeCamera.cc:450-510, :520-542, :646-662)
+inline void distortion(const gf_tracker_seq_cfg& c, double x, double y, double& dx, double& dy) {
+    double mx2 = x * x, my2 = y * y, mxy = x * y, rho2 = mx2 + my2, rad = c.k1 * rho2 + c.k2 * rho2 * rho2;
+    dx = x * rad + 2.0 * c.p1 * mxy + c.p2 * (rho2 + 2.0 * mx2);
+    dy = y * rad + 2.0 * c.p2 * mxy + c.p1 * (rho2 + 2.0 * my2);
+}
+inline bool no_distortion(const gf_tracker_seq_cfg& c) { return c.k1 == 0.0 && c.k2 == 0.0 && c.p1 == 0.0 && c.p2 == 0.0; }
+inline void lift_projective(const gf_tracker_seq_cfg& c, double u, double v, double& X, double& Y) {
+    const double i11 = 1.0 / c.fx, i13 = -c.cx / c.fx, i22 = 1.0 / c.fy, i23 = -c.cy / c.fy;
+    const double mx_d = i11 * u + i13, my_d = i22 * v + i23;
+    if (no_distortion(c)) { X = mx_d; Y = my_d; return; }
+    double dux, duy;
+    distortion(c, mx_d, my_d, dux, duy);
+    double mx_u = mx_d - dux, my_u = my_d - duy;
+    for (int i = 1; i < 8; ++i) { distortion(c, mx_u, my_u, dux, duy); mx_u = mx_d - dux; my_u = my_d - duy; }
+    X = mx_u; Y = my_u;
+}
+inline void space_to_plane(const gf_tracker_seq_cfg& c, const double* P, double& u, double& v) {
+    double xu = P[0] / P[2], yu = P[1] / P[2], xd = xu, yd = yu;
+    if (!no_distortion(c)) { double dx, dy; distortion(c, xu, yu, dx, dy); xd = xu + dx; yd = yu + dy; }
+    u = c.fx * xd + c.cx; v = c.fy * yd + c.cy;
+}
+
+template <class V> inline void reduce_vector(std::vector<V>& v, const uint8_t* st) {  // feature_tracker.cpp:30-46
+    int j = 0;
+    for (int i = 0; i < (int)v.size(); i++) if (st[i]) v[j++] = v[i];
+    v.resize(j);
+}
+
+// setMask (feature_tracker.cpp:56-83): std::sort by track count (same comparator, same libstdc++ algorithm as
+// the reference) and greedy keep of points not covered by an earlier kept point's filled circle.
+// roi: the sequence's region of interest (gf_roi.hpp) or null.  With one, the walk starts from `mask = R` instead of an all-255 image: a point whose rounded pixel
+// is excluded fails `mask.at(pt) == 255` like a covered one -- not kept, no circle, gone from ids / track_cnt / cur_pts.
+// T: the circle of the sequence's min_dist.  width, height: the frame's.
+inline void set_mask_host(int width, int height, SeqState& s, const DiskTable& T, const uint32_t* roi, P2i* centers, int& n_centers) {
+    struct E { int cnt; P2f pt; int id; uint16_t depth; };
+    static thread_local std::vector<E> v;
+    v.clear();
+    for (size_t i = 0; i < s.cur_pts.size(); i++) v.push_back({s.track_cnt[i], s.cur_pts[i], s.ids[i], s.cur_depth[i]});
+    std::sort(v.begin(), v.end(), [](const E& a, const E& b) { return a.cnt > b.cnt; });
+    s.cur_pts.clear(); s.ids.clear(); s.track_cnt.clear(); s.cur_depth.clear();
+    n_centers = 0;
+    // `mask.at(pt) == 255` <=> pt is inside no earlier kept point's filled circle; circles reach at most `radius`
+    // pixels, so only centres in the 3x3 neighbourhood of radius-sized cells can cover pt.
+    const int cell = std::max(T.radius, 1);
+    const int gw = width / cell + 1, gh = height / cell + 1;
+    s.grid_head.assign((size_t)gw * gh, -1);
+    s.grid_next.clear();
+    for (auto& it : v) {
+        const int x = cvRoundf(it.pt.x), y = cvRoundf(it.pt.y);
+        if (roi && !gfroi::allowed(roi, width, x, y)) continue;   // tracked points are inside the image (inBorder, feature_tracker.cpp:14-20)
+        const int cx = x / cell, cy = y / cell;
+        bool covered = false;
+        for (int yy = std::max(cy - 1, 0); yy <= std::min(cy + 1, gh - 1) && !covered; yy++)
+            for (int xx = std::max(cx - 1, 0); xx <= std::min(cx + 1, gw - 1) && !covered; xx++)
+                for (int k = s.grid_head[(size_t)yy * gw + xx]; k >= 0; k = s.grid_next[k]) {
+                    const int dy = std::abs(y - centers[k].y), dx = std::abs(x - centers[k].x);
+                    if (dy <= T.radius && dx <= T.hw[dy]) { covered = true; break; }
+                }
+        if (!covered) {
+            s.cur_pts.push_back(it.pt); s.ids.push_back(it.id); s.track_cnt.push_back(it.cnt); s.cur_depth.push_back(it.depth);
+            centers[n_centers] = P2i{x, y};
+            s.grid_next.push_back(s.grid_head[(size_t)cy * gw + cx]);
+            s.grid_head[(size_t)cy * gw + cx] = n_centers++;
+        }
+    }
+}
+
+inline void pts_velocity(SeqState& s) {  // feature_tracker.cpp:810-847
+    const size_t n = s.ids.size();
+    s.pts_velocity.resize(n);
+    s.cur_un_pts_map.resize(n);
+    for (size_t i = 0; i < n; i++) s.cur_un_pts_map[i] = {s.ids[i], s.cur_un_pts[i]};
+    std::sort(s.cur_un_pts_map.begin(), s.cur_un_pts_map.end(), [](const std::pair<int, P2f>& a, const std::pair<int, P2f>& b) { return a.first < b.first; });
+    if (!s.prev_un_pts_map.empty()) {
+        const double dt = s.cur_time - s.prev_time;
+        for (size_t i = 0; i < n; i++) {
+            const int id = s.ids[i];
+            auto it = std::lower_bound(s.prev_un_pts_map.begin(), s.prev_un_pts_map.end(), id, [](const std::pair<int, P2f>& a, int v) { return a.first < v; });
+            if (it != s.prev_un_pts_map.end() && it->first == id) {
+                const double vx = (s.cur_un_pts[i].x - it->second.x) / dt, vy = (s.cur_un_pts[i].y - it->second.y) / dt;
+                s.pts_velocity[i] = {(float)vx, (float)vy};
+            } else s.pts_velocity[i] = {0.f, 0.f};
+        }
+    } else for (size_t i = 0; i < n; i++) s.pts_velocity[i] = {0.f, 0.f};
+}
+
+inline void set_prediction(SeqState& s, const gf_tracker_seq_cfg& par, const int* ids, const double* xyz, int n) {  // feature_tracker.cpp:1006-1027
+    s.hasPrediction = true;
+    s.predict_pts.clear();
+    std::map<int, const double*> m;
+    for (int i = 0; i < n; i++) m[ids[i]] = xyz + 3 * i;
+    for (size_t i = 0; i < s.ids.size(); i++) {
+        auto it = m.find(s.ids[i]);
+        if (it != m.end()) { double u, v; space_to_plane(par, it->second, u, v); s.predict_pts.push_back({(float)u, (float)v}); }
+        else s.predict_pts.push_back(s.prev_pts[i]);
+    }
+}
+
+inline void remove_outliers(SeqState& s, const int* ids, int n) {  // feature_tracker.cpp:1029-1045
+    std::set<int> rm(ids, ids + n);
+    std::vector<uint8_t> st;
+    for (size_t i = 0; i < s.ids.size(); i++) st.push_back(rm.count(s.ids[i]) ? 0 : 1);
+    reduce_vector(s.prev_pts, st.data()); reduce_vector(s.ids, st.data()); reduce_vector(s.track_cnt, st.data());
+}
+
+// ---- the stages of one frame of one sequence, in the order a call runs them.  b is the sequence's position in the call's list; every *_row is row b of a table.
+
+// The sequence takes a frame stamped t.  Returns the pyramid slot (0 or 1) the frame goes to; s.slot itself moves when the frame is done (after_detect).
+inline int begin_frame(SeqState& s, double t) {
+    s.cur_time = t; s.cur_pts.clear(); s.cur_depth.clear();
+    s.started = true;
+    return s.slot ^ 1;
+}
+
+// Before LK (feature_tracker.cpp:113-122): the tracked points into prev_row, the prediction, if the sequence has one, into init_row, their number into *n_pts.
+// *has_pts: LK has work for the sequence; *predicted: in the form that starts from init_row.  GF_OK, or a refusal with its text in msg; `seq` only names the
+// sequence there.
+inline int stage_points(const SeqState& s, int seq, int cap, P2f* prev_row, P2f* init_row, int* n_pts, bool* has_pts, bool* predicted, char* msg, size_t msg_len) {
+    const int n = (int)s.prev_pts.size();
+    *n_pts = n; *has_pts = n > 0; *predicted = false;
+    if (n > cap) { snprintf(msg, msg_len, "sequence %d holds %d points > capacity %d", seq, n, cap); return GF_ERR_CAPACITY; }
+    for (int k = 0; k < n; k++) prev_row[k] = s.prev_pts[k];
+    if (n == 0 || !s.hasPrediction) return GF_OK;
+    if ((int)s.predict_pts.size() != n) {
+        snprintf(msg, msg_len, "sequence %d: prediction holds %d points but %d are tracked (call removeOutliers before setPrediction, estimator.cpp:1134-1135)", seq, (int)s.predict_pts.size(), n);
+        return GF_ERR_INVALID;
+    }
+    for (int k = 0; k < n; k++) init_row[k] = s.predict_pts[k];
+    *predicted = true;
+    return GF_OK;
+}
+
+// feature_tracker.cpp:124-132: fewer than 10 forward successes of a predicted sequence -> LK again with 3 levels from scratch.  fwd_status_row: the forward pass alone.
+inline bool prediction_failed(const SeqState& s, const uint8_t* fwd_status_row, int n_pts) {
+    if (!s.hasPrediction || n_pts == 0) return false;
+    int succ = 0;
+    for (int k = 0; k < n_pts; k++) succ += fwd_status_row[k] ? 1 : 0;
+    return succ < 10;
+}
+
+// What LK left for the sequence.  depth_out: the kernels' depth samples, or null on the entry points that hand in host depth images: there `host_depth` is the
+// sequence's image, rows of host_dstride pixels, sampled here (null: the sequence has no depth camera or the call no depth; every sample is 0).
+struct LkRows {
+    const P2f* cur_pts; const uint8_t* status; const uint16_t* depth_out; const unsigned* counters;   // counters: [cap][2] level passes, iterations
+    const uint16_t* host_depth; int host_dstride;
+};
+struct LkTally { long long level_passes = 0, iterations = 0, points = 0, tracked = 0; };   // what the sequence adds to gf_tracker_stats
+
+// After LK (feature_tracker.cpp:170-186): the reduction by status, track_cnt++, setMask and the number of corners the sequence wants.
+// T: the circle of par.min_dist; roi: the sequence's region of interest or null; centers_row / *n_centers: setMask's kept points for the detector.
+inline LkTally after_lk(SeqState& s, const gf_tracker_seq_cfg& par, int width, int height, const DiskTable& T, const uint32_t* roi, const LkRows& r,
+                        P2i* centers_row, int* n_centers, int* want) {
+    LkTally tally;
+    const int n = (int)s.prev_pts.size();
+    if (n > 0) {
+        const uint8_t* st = r.status;
+        s.cur_pts.resize(n); s.cur_depth.resize(n);
+        for (int i = 0; i < n; i++) {
+            const P2f c = r.cur_pts[i];
+            s.cur_pts[i] = c;
+            if (r.host_depth) { const int ry = (int)std::round((double)c.y), rx = (int)std::round((double)c.x); s.cur_depth[i] = st[i] ? r.host_depth[(size_t)ry * r.host_dstride + rx] : (uint16_t)0; }   // st: inside the image (post checks)
+            else if (!r.depth_out) s.cur_depth[i] = 0;
+            else s.cur_depth[i] = r.depth_out[i];
+            tally.level_passes += r.counters[2 * i];
+            tally.iterations += r.counters[2 * i + 1];
+        }
+        tally.points = n;
+        reduce_vector(s.prev_pts, st); reduce_vector(s.cur_pts, st); reduce_vector(s.ids, st); reduce_vector(s.track_cnt, st);
+        reduce_vector(s.cur_depth, st);
+        tally.tracked = (long long)s.cur_pts.size();
+    }
+    for (auto& c : s.track_cnt) c++;
+    int nc = 0;   // counted here and stored once: the tables are page-locked memory that neighbouring sequences' threads write too
+    set_mask_host(width, height, s, T, roi, centers_row, nc);
+    *n_centers = nc;
+    *want = par.max_cnt - (int)s.cur_pts.size();
+    return tally;
+}
+
+// What the detection left for the sequence: out_n corners (0 for a sequence that wanted none).  out_depth / host_depth as in LkRows.
+struct DetectRows {
+    const P2f* out_pts; const uint16_t* out_depth; int out_n;
+    const uint16_t* host_depth; int host_dstride;
+};
+struct Packed { int written; int overflow; };   // observations written; or overflow >= 0: that many features did not fit cap_out, none written
+
+// After the detection (feature_tracker.cpp:85-93, 210-211, 322-368): addPoints, undistortedPts, ptsVelocity, the roll-over of prev_* and of the pyramid slot,
+// and the featureFrame into out[0 .. cap_out).  have_depth: the call came with depth images.
+inline Packed after_detect(SeqState& s, const gf_tracker_seq_cfg& par, const DetectRows& r, bool have_depth, gf_feature_obs* out, int cap_out) {
+    for (int i = 0; i < r.out_n; i++) {
+        const P2f p = r.out_pts[i];
+        s.cur_pts.push_back(p); s.ids.push_back(s.n_id++); s.track_cnt.push_back(1);
+        s.cur_depth.push_back(r.host_depth ? r.host_depth[(size_t)(int)p.y * r.host_dstride + (int)p.x] : !r.out_depth ? (uint16_t)0 : r.out_depth[i]);   // corners sit on pixel centres
+    }
+    s.cur_un_pts.clear();
+    for (auto& p : s.cur_pts) { double X, Y; lift_projective(par, (double)p.x, (double)p.y, X, Y); s.cur_un_pts.push_back({(float)(X / 1.0), (float)(Y / 1.0)}); }
+    pts_velocity(s);
+    s.prev_pts = s.cur_pts; s.prev_un_pts = s.cur_un_pts; s.prev_un_pts_map.swap(s.cur_un_pts_map); s.prev_time = s.cur_time;
+    s.hasPrediction = false;
+    s.slot ^= 1;   // the pyramid written in this call is the sequence's previous frame from here on
+    const int n = (int)s.ids.size();
+    // depth_cam set but no depth image: neither packing loop of the reference runs (feature_tracker.cpp:320 `depth_cam == 0`, :344 `!_img1.empty()`):
+    // the returned featureFrame is empty, the tracker state has advanced all the same
+    if (par.depth_cam && !have_depth) return {0, -1};
+    if (n > cap_out) return {0, n};
+    for (int i = 0; i < n; i++) {
+        gf_feature_obs* o = out + i;
+        o->id = s.ids[i]; o->camera_id = 0;
+        o->v[0] = s.cur_un_pts[i].x; o->v[1] = s.cur_un_pts[i].y; o->v[2] = 1; o->v[3] = s.cur_pts[i].x; o->v[4] = s.cur_pts[i].y;
+        o->v[5] = s.pts_velocity[i].x; o->v[6] = s.pts_velocity[i].y;
+        o->v[7] = par.depth_cam ? (double)(int)s.cur_depth[i] / 1000 : -2.4;
+    }
+    return {n, -1};
+}
+
+}  // namespace gf

@@ -1,12 +1,19 @@
 // gf_tracker.hip — C-ABI front end (include/groundfusion_hip.h): host orchestration of the HIP tracker.
 //
 // Mirrors FeatureTracker (vins_estimator/src/featureTracker/feature_tracker.{h,cpp}) for `batch`
-// independent sequences on one GPU stream; a call advances the sequences it lists (track_core), the lock-step entry points list them all.  Host keeps exactly the bookkeeping the
-// reference keeps in C++ (ids, track_cnt, n_id, maps for velocity; setMask's std::sort + greedy keep,
-// feature_tracker.cpp:56-83); all image work (pyramids, Scharr, LK forward/reverse, mask rasterisation,
-// Shi-Tomasi, candidate sort and min-distance selection, depth sampling) runs in the kernels of
-// gf_lk_kernels.hpp / gf_detect_kernels.hpp.  There is no CPU fallback: without a HIP device every entry
-// point fails with GF_ERR_NO_DEVICE.
+// independent sequences on one GPU stream; a call advances the sequences it lists (track_core), the lock-step entry points list them all.  The bookkeeping the
+// reference keeps in C++ (ids, track_cnt, n_id, maps for velocity, setMask's walk, the camera model) is gf_track_host.hpp, plain C++ per sequence; all image work
+// (pyramids, Scharr, LK forward/reverse, mask rasterisation, Shi-Tomasi, candidate sort and min-distance selection, depth sampling) runs in the kernels of
+// gf_lk_kernels.hpp / gf_detect_kernels.hpp.  This file owns the handle, its tables and streams, and the order of a frame.  track_core runs these stages:
+//   publish        the call's list and frame table where the first kernels read them, over the bus or by copy
+//   launch_front   conversion, equalisation, pyramid; the frames_unaligned count
+//   run_lk         stage_points per sequence, tables down, one or two LK launches, tables up; the host waits
+//   redo_fallback  LK from scratch for the predicted sequences with fewer than 10 forward successes
+//   book_after_lk  per sequence on the pool (after_lk): reduction by status, setMask, the corners wanted
+//   run_detect     tables down, detector, selection, tables up; the host waits
+//   read_profile, check_candidates   event times; the candidate capacity and the selection-branch counters
+//   book_after_detect  per sequence on the pool (after_detect): addPoints, lift, velocities, roll-over, packing; then the stats
+// There is no CPU fallback: without a HIP device every entry point fails with GF_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 #include <sched.h>
 #include <algorithm>
@@ -16,13 +23,10 @@
 #include <functional>
 #include <mutex>
 #include <thread>
-#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <memory>
-#include <set>
 #include <string>
 #include <vector>
 
@@ -37,6 +41,7 @@
 #include "gf_pixfmt.hpp"
 #include "gf_roi.hpp"
 #include "gf_seq_cfg.hpp"
+#include "gf_track_host.hpp"
 
 namespace gf {
 
@@ -58,22 +63,6 @@ int set_err(int code, const char* fmt, ...) {
     g_err = buf;
     return code;
 }
-
-struct P2f { float x, y; };
-
-struct SeqState {  // per-sequence FeatureTracker members (feature_tracker.h:76-98)
-    std::vector<P2f> prev_pts, cur_pts, predict_pts, prev_un_pts, cur_un_pts, pts_velocity;
-    std::vector<int> ids, track_cnt;
-    std::vector<uint16_t> cur_depth;
-    // cur_un_pts_map / prev_un_pts_map (feature_tracker.h:89): id -> point, kept as id-sorted vectors (ids are unique)
-    std::vector<std::pair<int, P2f>> cur_un_pts_map, prev_un_pts_map;
-    std::vector<int> grid_head, grid_next;  // scratch of set_mask_host
-    double cur_time = 0, prev_time = 0;
-    int n_id = 0;
-    bool hasPrediction = false;
-    bool started = false;   // the sequence has taken a frame since gf_tracker_create / gf_tracker_reset_seq: its parameters are fixed (gf_tracker_set_seq_cfg)
-    int slot = 1;   // which of the sequence's two pyramids holds its newest frame; flipped when the sequence takes a frame, and only then (the first frame goes to 0)
-};
 
 // Small persistent pool for the per-sequence host bookkeeping (sequences are independent).  GF_HOST_THREADS overrides the size.
 class HostPool {
@@ -215,37 +204,6 @@ struct gf_tracker {
 
 namespace gf {
 
-static inline int cvRoundf(float v) { return (int)lrintf(v); }
-
-// camodocal PinholeCamera (camera_models/src/camera_models/PinholeCamera.cc:450-510, :520-542, :646-662)
-static void distortion(const gf_tracker_seq_cfg& c, double x, double y, double& dx, double& dy) {
-    double mx2 = x * x, my2 = y * y, mxy = x * y, rho2 = mx2 + my2, rad = c.k1 * rho2 + c.k2 * rho2 * rho2;
-    dx = x * rad + 2.0 * c.p1 * mxy + c.p2 * (rho2 + 2.0 * mx2);
-    dy = y * rad + 2.0 * c.p2 * mxy + c.p1 * (rho2 + 2.0 * my2);
-}
-static bool no_distortion(const gf_tracker_seq_cfg& c) { return c.k1 == 0.0 && c.k2 == 0.0 && c.p1 == 0.0 && c.p2 == 0.0; }
-static void lift_projective(const gf_tracker_seq_cfg& c, double u, double v, double& X, double& Y) {
-    const double i11 = 1.0 / c.fx, i13 = -c.cx / c.fx, i22 = 1.0 / c.fy, i23 = -c.cy / c.fy;
-    const double mx_d = i11 * u + i13, my_d = i22 * v + i23;
-    if (no_distortion(c)) { X = mx_d; Y = my_d; return; }
-    double dux, duy;
-    distortion(c, mx_d, my_d, dux, duy);
-    double mx_u = mx_d - dux, my_u = my_d - duy;
-    for (int i = 1; i < 8; ++i) { distortion(c, mx_u, my_u, dux, duy); mx_u = mx_d - dux; my_u = my_d - duy; }
-    X = mx_u; Y = my_u;
-}
-static void space_to_plane(const gf_tracker_seq_cfg& c, const double* P, double& u, double& v) {
-    double xu = P[0] / P[2], yu = P[1] / P[2], xd = xu, yd = yu;
-    if (!no_distortion(c)) { double dx, dy; distortion(c, xu, yu, dx, dy); xd = xu + dx; yd = yu + dy; }
-    u = c.fx * xd + c.cx; v = c.fy * yd + c.cy;
-}
-
-template <class V> static void reduce_vector(std::vector<V>& v, const uint8_t* st) {  // feature_tracker.cpp:30-46
-    int j = 0;
-    for (int i = 0; i < (int)v.size(); i++) if (st[i]) v[j++] = v[i];
-    v.resize(j);
-}
-
 // buildOpticalFlowPyramid in three launches: level 0 (copy + REFLECT_101 border), level 1 (interior + border in one pass), and one kernel for
 // all remaining levels.  There is no derivative pyramid: lk_solve evaluates the Scharr derivative of the template window itself.
 // d_raw_frames: `count` frames back to back, frame i for the sequence at list position i; cur_of[i]: the pyramid it is written to (device-readable, [count]).
@@ -317,18 +275,16 @@ static int launch_pyramid_one(gf_tracker* h, const uint8_t* d_raw_frame, int slo
     return launch_pyramid(h, d_raw_frame, 1, h->d_cur.p);
 }
 
-// depth_refs: A.depth is the call's table of gf_frame_ref (the _refs entry points with depth), read by the _refs forms of the same kernels
-static void launch_lk(gf_tracker* h, int batch, const LkBatchArgs& A, bool depth_refs = false) {   // one LK launch over the `batch` listed sequences in the form the handle was created for (same results in every form)
+// One LK launch over the `batch` listed sequences in the form the handle was created for (same results in every form).
+// REFS: A.depth is the call's table of gf_frame_ref (the _refs entry points with depth), read by the _refs forms of the same kernels.
+template <bool REFS> static void launch_lk_form(gf_tracker* h, int batch, const LkBatchArgs& A) {
     const int cap = h->cap;
-    if (depth_refs) {
-        if (h->lk_points == 4) lk_track_mp_refs_kernel<4><<<dim3((cap + 15) / 16, batch), 256, 0, h->stream>>>(h->G, A);
-        else if (h->lk_points == 2) lk_track_mp_refs_kernel<2><<<dim3((cap + 7) / 8, batch), 256, 0, h->stream>>>(h->G, A);
-        else lk_track_refs_kernel<<<dim3((cap + 3) / 4, batch), 256, 0, h->stream>>>(h->G, A);
-        return;
-    }
-    if (h->lk_points == 4) lk_track_mp_kernel<4><<<dim3((cap + 15) / 16, batch), 256, 0, h->stream>>>(h->G, A);
-    else if (h->lk_points == 2) lk_track_mp_kernel<2><<<dim3((cap + 7) / 8, batch), 256, 0, h->stream>>>(h->G, A);
-    else lk_track_kernel<<<dim3((cap + 3) / 4, batch), 256, 0, h->stream>>>(h->G, A);
+    if (h->lk_points == 4) (REFS ? lk_track_mp_refs_kernel<4> : lk_track_mp_kernel<4>)<<<dim3((cap + 15) / 16, batch), 256, 0, h->stream>>>(h->G, A);
+    else if (h->lk_points == 2) (REFS ? lk_track_mp_refs_kernel<2> : lk_track_mp_kernel<2>)<<<dim3((cap + 7) / 8, batch), 256, 0, h->stream>>>(h->G, A);
+    else (REFS ? lk_track_refs_kernel : lk_track_kernel)<<<dim3((cap + 3) / 4, batch), 256, 0, h->stream>>>(h->G, A);
+}
+static void launch_lk(gf_tracker* h, int batch, const LkBatchArgs& A, bool depth_refs = false) {
+    if (depth_refs) launch_lk_form<true>(h, batch, A); else launch_lk_form<false>(h, batch, A);
 }
 
 static LkBatchArgs lk_args(gf_tracker* h, int fwd_max_level, int use_init, int flow_back, int post_checks, const uint8_t* seqmask,
@@ -342,64 +298,6 @@ static LkBatchArgs lk_args(gf_tracker* h, int fwd_max_level, int use_init, int f
     A.post_checks = post_checks; A.seq_mask = seqmask;
     A.flow_back_of = h->d_seq_fb.p;   // null on a handle no setter has touched; written by the copy list in front of the call's first LK launch
     return A;
-}
-
-// setMask (feature_tracker.cpp:56-83): std::sort by track count (same comparator, same libstdc++ algorithm as
-// the reference) and greedy keep of points not covered by an earlier kept point's filled circle.
-// roi: the sequence's region of interest (gf_roi.hpp) or null.  With one, the walk starts from `mask = R` instead of an all-255 image: a point whose rounded pixel
-// is excluded fails `mask.at(pt) == 255` like a covered one -- not kept, no circle, gone from ids / track_cnt / cur_pts.
-// T: the circle of the sequence's min_dist.
-static void set_mask_host(gf_tracker* h, SeqState& s, const DiskTable& T, const uint32_t* roi, int2* centers, int& n_centers) {
-    struct E { int cnt; P2f pt; int id; uint16_t depth; };
-    static thread_local std::vector<E> v;
-    v.clear();
-    for (size_t i = 0; i < s.cur_pts.size(); i++) v.push_back({s.track_cnt[i], s.cur_pts[i], s.ids[i], s.cur_depth[i]});
-    std::sort(v.begin(), v.end(), [](const E& a, const E& b) { return a.cnt > b.cnt; });
-    s.cur_pts.clear(); s.ids.clear(); s.track_cnt.clear(); s.cur_depth.clear();
-    n_centers = 0;
-    // `mask.at(pt) == 255` <=> pt is inside no earlier kept point's filled circle; circles reach at most `radius`
-    // pixels, so only centres in the 3x3 neighbourhood of radius-sized cells can cover pt.
-    const int cell = std::max(T.radius, 1);
-    const int gw = h->cfg.width / cell + 1, gh = h->cfg.height / cell + 1;
-    s.grid_head.assign((size_t)gw * gh, -1);
-    s.grid_next.clear();
-    for (auto& it : v) {
-        const int x = cvRoundf(it.pt.x), y = cvRoundf(it.pt.y);
-        if (roi && !gfroi::allowed(roi, h->cfg.width, x, y)) continue;   // tracked points are inside the image (inBorder, feature_tracker.cpp:14-20)
-        const int cx = x / cell, cy = y / cell;
-        bool covered = false;
-        for (int yy = std::max(cy - 1, 0); yy <= std::min(cy + 1, gh - 1) && !covered; yy++)
-            for (int xx = std::max(cx - 1, 0); xx <= std::min(cx + 1, gw - 1) && !covered; xx++)
-                for (int k = s.grid_head[(size_t)yy * gw + xx]; k >= 0; k = s.grid_next[k]) {
-                    const int dy = std::abs(y - centers[k].y), dx = std::abs(x - centers[k].x);
-                    if (dy <= T.radius && dx <= T.hw[dy]) { covered = true; break; }
-                }
-        if (!covered) {
-            s.cur_pts.push_back(it.pt); s.ids.push_back(it.id); s.track_cnt.push_back(it.cnt); s.cur_depth.push_back(it.depth);
-            centers[n_centers] = make_int2(x, y);
-            s.grid_next.push_back(s.grid_head[(size_t)cy * gw + cx]);
-            s.grid_head[(size_t)cy * gw + cx] = n_centers++;
-        }
-    }
-}
-
-static void pts_velocity(SeqState& s) {  // feature_tracker.cpp:810-847
-    const size_t n = s.ids.size();
-    s.pts_velocity.resize(n);
-    s.cur_un_pts_map.resize(n);
-    for (size_t i = 0; i < n; i++) s.cur_un_pts_map[i] = {s.ids[i], s.cur_un_pts[i]};
-    std::sort(s.cur_un_pts_map.begin(), s.cur_un_pts_map.end(), [](const std::pair<int, P2f>& a, const std::pair<int, P2f>& b) { return a.first < b.first; });
-    if (!s.prev_un_pts_map.empty()) {
-        const double dt = s.cur_time - s.prev_time;
-        for (size_t i = 0; i < n; i++) {
-            const int id = s.ids[i];
-            auto it = std::lower_bound(s.prev_un_pts_map.begin(), s.prev_un_pts_map.end(), id, [](const std::pair<int, P2f>& a, int v) { return a.first < v; });
-            if (it != s.prev_un_pts_map.end() && it->first == id) {
-                const double vx = (s.cur_un_pts[i].x - it->second.x) / dt, vy = (s.cur_un_pts[i].y - it->second.y) / dt;
-                s.pts_velocity[i] = {(float)vx, (float)vy};
-            } else s.pts_velocity[i] = {0.f, 0.f};
-        }
-    } else for (size_t i = 0; i < n; i++) s.pts_velocity[i] = {0.f, 0.f};
 }
 
 // The list of a call: `count` distinct sequences of the handle, in any order.  Checked before anything is copied, launched or changed.
@@ -433,6 +331,15 @@ static void roi_clear_host(gf_tracker* h, int seq) {
     std::fill_n(h->roi_bits.begin() + (size_t)seq * h->roi_words, h->roi_words, ~0u);
     h->roi_has[seq] = 0;
 }
+static int roi_packed(gf_tracker* h, int count, const int* seq) {   // behind a packing kernel: the words come back (setMask's walk reads them on the host) and the sequences have a region
+    for (int i = 0; i < count; i++) {
+        const size_t off = (size_t)seq[i] * h->roi_words;
+        HIPCHK(hipMemcpyAsync(h->roi_bits.data() + off, h->d_roi.p + off, h->roi_words * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < count; i++) h->roi_has[seq[i]] = 1;
+    return GF_OK;
+}
 static int roi_upload(gf_tracker* h, int seq) {   // the host copy of one sequence's words -> the table
     const size_t off = (size_t)seq * h->roi_words;
     HIPCHK(hipMemcpyAsync(h->d_roi.p + off, h->roi_bits.data() + off, h->roi_words * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
@@ -446,335 +353,395 @@ static int check_stride(gf_tracker* h, int stride) {
         return set_err(GF_ERR_INVALID, "a stride of %d bytes is shorter than a row of %d pixels of %d bytes (gf_tracker_cfg.pixel_format %d)", stride, h->cfg.width, h->ch, h->cfg.pixel_format);
     return GF_OK;
 }
+// The host frames of the `count` listed sequences (gf_tracker_track_some, gf_tracker_prefetch_some), refused before anything is copied.
+// *have_depth: the call has depth images, one for every listed sequence with a depth camera.
+static int check_host_frames(gf_tracker* h, int count, const int* seq, const uint8_t* const* gray, int stride, const uint16_t* const* depth, bool* have_depth) {
+    if (int rc = check_stride(h, stride)) return rc;
+    *have_depth = depth != nullptr;
+    for (int i = 0; i < count; i++) {
+        if (!gray[i]) return set_err(GF_ERR_INVALID, "null image for sequence %d", seq[i]);
+        if (*have_depth && !depth[i] && h->par[seq[i]].depth_cam) *have_depth = false;
+    }
+    return GF_OK;
+}
 
-// One frame for each of the `count` listed sequences (seq: checked by check_list); sequences that are not listed keep their whole state.  Everything the caller hands
-// in or gets back (t, the frames behind d_gray / d_depth / hdep, out, n_out) and every hand-over table of the handle is indexed by the position i in the list, so the
-// work and the bytes of a call follow `count`; only h->seq[] and the pyramid pairs are indexed by the sequence seq[i].
+// The detector and the selection over `count` list positions as the tracker runs them: kept points as circle centres, no explicit mask, the handle's tables of
+// regions, circles and min_dist where a setter has made them (null otherwise).  gf_good_features overrides what it sets differently.
+static DetectArgs detect_args(gf_tracker* h) {
+    DetectArgs D{};
+    D.pyr = h->d_img.p; D.pyr_bytes = h->G.img_bytes; D.frame_of = h->d_det.p; D.g = h->G.lv[0];
+    D.mask = nullptr; D.mask_seq_stride = 0; D.centers = h->d_centers.p; D.n_centers = h->d_ncenters.p; D.cap = h->cap;
+    D.roi = h->d_roi.p; D.roi_seq_words = h->roi_words;   // null on a handle no setter has touched
+    D.disk_of = h->d_seq_disk.p;                          // likewise
+    D.maxkey = h->d_maxkey.p; D.cand = h->d_cand.p; D.cand_seq_stride = (size_t)h->cand_cap; D.cand_cap = h->cand_cap; D.cand_count = h->d_cand_count.p;
+    return D;
+}
+static void launch_detect(gf_tracker* h, int count, const DetectArgs& D) {
+    const int W = h->cfg.width, H = h->cfg.height;
+    detect_strip_kernel<kDS_R><<<dim3((W + kDS_W - 1) / kDS_W, (H + kDS_R - 1) / kDS_R, count), 64, 0, h->stream>>>(D, h->disk);
+}
+static SelectArgs select_args(gf_tracker* h, const uint16_t* depth, int skip_small) {   // depth: tight device frames, the call's table of gf_frame_ref (launch_select<true>) or null
+    const int W = h->cfg.width, H = h->cfg.height;
+    SelectArgs S{};
+    S.cand = h->d_cand.p; S.cand_seq_stride = (size_t)h->cand_cap; S.cand_cap = h->cand_cap; S.cand_count = h->d_cand_count.p; S.maxkey = h->d_maxkey.p; S.want = h->d_want.p;
+    S.w = W; S.h = H; S.min_dist = h->cfg.min_dist; S.min_dist_of = h->d_seq_md.p; S.out_cap = h->cap; S.sort_cap = h->sort_cap; S.out_pts = h->d_out_pts.p; S.out_depth = h->d_out_depth.p; S.out_n = h->d_out_n.p;
+    S.depth = depth; S.depth_seq_stride = (size_t)W * H; S.depth_stride = W; S.skip_small = skip_small;
+    return S;
+}
+// topk: one maximum per corner for the sequences that want a handful (select_topk_kernel); sort: the others, or all of them, through the sort
+template <bool REFS> static void launch_select(gf_tracker* h, int count, const SelectArgs& S, bool topk, bool sort) {
+    if (topk) (REFS ? select_topk_refs_kernel : select_topk_kernel)<<<dim3(count), 1024, 0, h->stream>>>(S);
+    if (sort) (REFS ? select_corners_refs_kernel : select_corners_kernel)<<<dim3(count), 1024, h->select_lds, h->stream>>>(S);
+}
+
+// Where the frames of a call lie, one per list position, in one of three forms: tight device frames with or without tight device depth frames (device());
+// tight device frames and the callers' depth images on the host (with_host_depth()); or wherever the caller's tables of gf_frame_ref say (by_refs()).
 //
-// hdep (host entry points): the callers' depth images, one pointer per listed sequence, rows of hdstride pixels.  The reference reads ONE pixel of the depth image per
-// feature (feature_tracker.cpp:360 `rightImg.at<ushort>(round(y), round(x))`), and on the host-image entry points both the image and the feature coordinates are on
-// the host anyway: sampling there keeps 614 KB per frame and sequence (two thirds of an RGB-D VGA frame) off the bus.  d_depth (device entry point) keeps the sample
-// in the kernels.  Same pixel, same rounding (round half away from zero on the float coordinates), same u16.
+// host_depth: one pointer per listed sequence, rows of host_dstride pixels.  The reference reads ONE pixel of the depth image per feature (feature_tracker.cpp:360
+// `rightImg.at<ushort>(round(y), round(x))`), and on the host-image entry points both the image and the feature coordinates are on the host anyway: sampling there
+// keeps 614 KB per frame and sequence (two thirds of an RGB-D VGA frame) off the bus.  Device depth keeps the sample in the kernels.  Same pixel, same rounding
+// (round half away from zero on the float coordinates), same u16.
 //
-// gray_refs / depth_refs (the _refs entry points; checked by the caller, d_gray and d_depth null): the frames lie where the caller's tables say, one entry per
-// list position.  The tables go into h_refs with the list and only the first kernel that reads a caller's frame -- conversion, CLAHE or the pyramid's level-0
-// reader, and the depth samples of LK and the selection -- addresses it through them; the tight entry points build nothing and run the kernels of before.
-static int track_core(gf_tracker* h, int count, const int* seq, const double* t, const uint8_t* d_gray, const uint16_t* d_depth, gf_feature_obs* out, int cap_out,
-                      int* n_out, const uint16_t* const* hdep = nullptr, int hdstride = 0, const gf_frame_ref* gray_refs = nullptr, const gf_frame_ref* depth_refs = nullptr) {
-    const int N = count, cap = h->cap, W = h->cfg.width, H = h->cfg.height;
-    if (N == 0) return GF_OK;
-    const bool have_depth = d_depth != nullptr || hdep != nullptr || depth_refs != nullptr;
-    if (gray_refs) {
-        for (int i = 0; i < N; i++) { h->h_refs.p[i] = gray_refs[i]; h->h_refs.p[h->B + i] = depth_refs ? depth_refs[i] : gf_frame_ref{nullptr, 0}; }
-        if (depth_refs) d_depth = reinterpret_cast<const uint16_t*>(h->d_refs.p + h->B);   // what the _refs forms of LK and the selection read in the place of tight frames
-    }
-    const bool prof = h->profiling;
-    using clk = std::chrono::steady_clock;
-    auto tp = clk::now();
-    auto lap = [&](double& acc) { auto n = clk::now(); acc += std::chrono::duration<double, std::milli>(n - tp).count(); tp = n; };
-    for (int i = 0; i < N; i++) {
-        SeqState& s = h->seq[seq[i]];
-        s.cur_time = t[i]; s.cur_pts.clear(); s.cur_depth.clear();
-        s.started = true;
-        h->h_cur.p[i] = 2 * seq[i] + (s.slot ^ 1);   // the new frame goes to the sequence's other pyramid; s.slot itself moves when the frame is done
-    }
-    // The hand-overs between the host's bookkeeping and the kernels -- two to four small tables down before LK, five up behind it, three down before the detection, four
-    // up behind it -- as one copy-list kernel each (gf_copy_list.hpp) instead of one hipMemcpyAsync per table: sixteen submissions and copy latencies per frame become four.
-    gfcopy::Builder CL;
-    const bool lists = h->copy_lists;
-    hipError_t cerr = hipSuccess;
-    auto down = [&](auto& dev, auto& pin, size_t count) {   // host -> device
+// gray_refs / depth_refs (checked by the caller): the tables go into h_refs with the list and only the first kernel that reads a caller's frame -- conversion, CLAHE
+// or the pyramid's level-0 reader, and the depth samples of LK and the selection -- addresses it through them; the tight forms build nothing and run the kernels of before.
+struct FrameInput {
+    const uint8_t* gray = nullptr;   // tight frames of the handle's format, never written
+    const uint16_t* depth = nullptr;
+    const uint16_t* const* host_depth = nullptr; int host_dstride = 0;
+    const gf_frame_ref* gray_refs = nullptr; const gf_frame_ref* depth_refs = nullptr;
+    static FrameInput device(const uint8_t* gray, const uint16_t* depth) { FrameInput f; f.gray = gray; f.depth = depth; return f; }
+    static FrameInput with_host_depth(const uint8_t* gray, const uint16_t* const* depth, int dstride) { FrameInput f; f.gray = gray; f.host_depth = depth; f.host_dstride = dstride; return f; }
+    static FrameInput by_refs(const gf_frame_ref* gray, const gf_frame_ref* depth) { FrameInput f; f.gray_refs = gray; f.depth_refs = depth; return f; }
+    bool have_depth() const { return depth || host_depth || depth_refs; }
+    bool depth_by_refs() const { return depth_refs != nullptr; }
+    // the image the host samples for list position b; a sequence without a depth camera: its image is not read (its samples are never reported) and may be null
+    const uint16_t* host_image(int b, const gf_tracker_seq_cfg& par) const { return host_depth && par.depth_cam ? host_depth[b] : nullptr; }
+    // row b of a table of the kernels' depth samples, or null in the form whose samples the host takes itself
+    const uint16_t* kernel_samples(const PinBuf<uint16_t>& table, int b, int cap) const { return host_depth ? nullptr : table.p + (size_t)b * cap; }
+};
+
+// The hand-overs between the host's bookkeeping and the kernels -- two to four small tables down before LK, five up behind it, three down before the detection, four
+// up behind it -- as one copy-list kernel each (gf_copy_list.hpp) instead of one hipMemcpyAsync per table: sixteen submissions and copy latencies per frame become four.
+// GF_TRACKER_COPIES=1 (lists off): the plain copies, each where it is added.
+class HandOver {
+  public:
+    HandOver(bool lists, hipStream_t stream) : lists_(lists), stream_(stream) {}
+    template <class D, class P> void down(D& dev, P& pin, size_t count) {   // host -> device
         const size_t bytes = count * sizeof(*pin.p);
-        if (lists) CL.add(pin.hd, dev.p, 1, bytes, bytes); else if (cerr == hipSuccess) cerr = hipMemcpyAsync(dev.p, pin.p, bytes, hipMemcpyHostToDevice, h->stream);
-    };
-    auto up = [&](auto& pin, auto& dev, size_t count) {     // device -> host
+        if (lists_) cl_.add(pin.hd, dev.p, 1, bytes, bytes); else if (err_ == hipSuccess) err_ = hipMemcpyAsync(dev.p, pin.p, bytes, hipMemcpyHostToDevice, stream_);
+    }
+    template <class P, class D> void up(P& pin, D& dev, size_t count) {     // device -> host
         const size_t bytes = count * sizeof(*pin.p);
-        if (lists) CL.add(dev.p, pin.hd, 1, bytes, bytes); else if (cerr == hipSuccess) cerr = hipMemcpyAsync(pin.p, dev.p, bytes, hipMemcpyDeviceToHost, h->stream);
-    };
-    auto flush = [&]() -> int {
-        HIPCHK(cerr);
-        if (lists) { if (!CL.ok) return set_err(GF_ERR_HIP, "copy list: a page-locked buffer is not mapped into the device's address space (GF_TRACKER_COPIES=1 selects plain copies)"); HIPCHK(CL.launch<1>(h->stream)); CL = gfcopy::Builder(); }
+        if (lists_) cl_.add(dev.p, pin.hd, 1, bytes, bytes); else if (err_ == hipSuccess) err_ = hipMemcpyAsync(pin.p, dev.p, bytes, hipMemcpyDeviceToHost, stream_);
+    }
+    int flush() {   // what was added since the last one leaves as one launch
+        HIPCHK(err_);
+        if (!lists_) return GF_OK;
+        if (!cl_.ok) return set_err(GF_ERR_HIP, "copy list: a page-locked buffer is not mapped into the device's address space (GF_TRACKER_COPIES=1 selects plain copies)");
+        HIPCHK(cl_.launch<1>(stream_));
+        cl_ = gfcopy::Builder();
         return GF_OK;
-    };
-    // The list has to be readable on the device before the pyramid, which is launched before the first copy list so that it runs under the host's table filling.
-    // No extra submission and no synchronisation: the pyramid kernels read the page-locked table itself (one scalar load per block, as the copy-list kernels read
-    // their sources), and the copy list in front of LK brings it to d_cur for that kernel, which is bound by instruction issue and should find it in the L2 (the
-    // detector gets its own form, h_det, with its other tables).  With plain copies (GF_TRACKER_COPIES=1) it is one more copy, in front of the pyramid.
-    const bool over_bus = lists && h->h_cur.hd;
-    if (!over_bus) HIPCHK(hipMemcpyAsync(h->d_cur.p, h->h_cur.p, (size_t)N * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    const int* cur_of = over_bus ? h->h_cur.hd : h->d_cur.p;
-    // the frame table goes the same two ways; its depth half is wanted on the device by LK and the selection (refs_down: with the first copy list that leaves)
-    const bool refs_bus = gray_refs && over_bus && h->h_refs.hd;
-    if (gray_refs && !refs_bus) HIPCHK(hipMemcpyAsync(h->d_refs.p, h->h_refs.p, (size_t)2 * h->B * sizeof(gf_frame_ref), hipMemcpyHostToDevice, h->stream));
-    const gf_frame_ref* refs = !gray_refs ? nullptr : refs_bus ? h->h_refs.hd : h->d_refs.p;
-    bool refs_down = refs_bus && depth_refs;
+    }
+  private:
+    gfcopy::Builder cl_;
+    const bool lists_;
+    const hipStream_t stream_;
+    hipError_t err_ = hipSuccess;
+};
+
+// the rows of the hand-over tables as gf_track_host.hpp takes them
+static_assert(sizeof(float2) == sizeof(P2f) && alignof(float2) >= alignof(P2f) && offsetof(float2, x) == offsetof(P2f, x) && offsetof(float2, y) == offsetof(P2f, y), "float2 rows are passed as P2f rows");
+static_assert(sizeof(int2) == sizeof(P2i) && alignof(int2) >= alignof(P2i) && offsetof(int2, x) == offsetof(P2i, x) && offsetof(int2, y) == offsetof(P2i, y), "int2 rows are passed as P2i rows");
+static P2f* row(const PinBuf<float2>& t, size_t b, int cap) { return reinterpret_cast<P2f*>(t.p + b * cap); }
+static P2i* row(const PinBuf<int2>& t, size_t b, int cap) { return reinterpret_cast<P2i*>(t.p + b * cap); }
+
+// One call of track_core: what its stages share.  N, seq: the list; every hand-over table of the handle is indexed by the position in it.
+struct Call {
+    gf_tracker* h; int N; const int* seq; FrameInput in;
+    HandOver ho;
+    std::chrono::steady_clock::time_point tp = std::chrono::steady_clock::now();
+    const int* cur_of = nullptr;          // the list where the kernels ahead of the first copy list read it (publish): d_cur, or over the bus the page-locked table itself
+    const gf_frame_ref* refs = nullptr;   // the frame table likewise; null: tight frames
+    bool refs_down = false;               // its depth half is still wanted on the device: with the first copy list that leaves
+    const uint16_t* kdepth = nullptr;     // what LK and the selection sample: tight device depth frames, the device table's depth half (depth_by_refs) or null
+    bool any_prev = false, any_pred = false, any_plain = false, any_want = false;
+    void lap(double& acc) { const auto n = std::chrono::steady_clock::now(); acc += std::chrono::duration<double, std::milli>(n - tp).count(); tp = n; }
+    void add_refs() { if (refs_down) { ho.down(h->d_refs, h->h_refs, (size_t)2 * h->B); refs_down = false; } }
+};
+
+// The list has to be readable on the device before the pyramid, which is launched before the first copy list so that it runs under the host's table filling.
+// No extra submission and no synchronisation: the pyramid kernels read the page-locked table itself (one scalar load per block, as the copy-list kernels read
+// their sources), and the copy list in front of LK brings it to d_cur for that kernel, which is bound by instruction issue and should find it in the L2 (the
+// detector gets its own form, h_det, with its other tables).  With plain copies (GF_TRACKER_COPIES=1) it is one more copy, in front of the pyramid.
+// The frame table goes the same two ways; its depth half is wanted on the device by LK and the selection.
+static int publish(Call& c) {
+    gf_tracker* h = c.h;
+    const FrameInput& in = c.in;
+    c.kdepth = in.depth;
+    if (in.gray_refs) {
+        for (int i = 0; i < c.N; i++) { h->h_refs.p[i] = in.gray_refs[i]; h->h_refs.p[h->B + i] = in.depth_refs ? in.depth_refs[i] : gf_frame_ref{nullptr, 0}; }
+        if (in.depth_refs) c.kdepth = reinterpret_cast<const uint16_t*>(h->d_refs.p + h->B);   // what the _refs forms of LK and the selection read in the place of tight frames
+    }
+    const bool over_bus = h->copy_lists && h->h_cur.hd;
+    if (!over_bus) HIPCHK(hipMemcpyAsync(h->d_cur.p, h->h_cur.p, (size_t)c.N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    c.cur_of = over_bus ? h->h_cur.hd : h->d_cur.p;
+    const bool refs_bus = in.gray_refs && over_bus && h->h_refs.hd;
+    if (in.gray_refs && !refs_bus) HIPCHK(hipMemcpyAsync(h->d_refs.p, h->h_refs.p, (size_t)2 * h->B * sizeof(gf_frame_ref), hipMemcpyHostToDevice, h->stream));
+    c.refs = !in.gray_refs ? nullptr : refs_bus ? h->h_refs.hd : h->d_refs.p;
+    c.refs_down = refs_bus && in.depth_refs;
+    return GF_OK;
+}
+
+// Conversion to MONO8, equalisation and the pyramid, each reading what the stage before it left; only the first of them reads the caller's frames.
+static int launch_front(Call& c) {
+    gf_tracker* h = c.h;
+    const int N = c.N, W = h->cfg.width, H = h->cfg.height;
+    const bool prof = h->profiling;
+    const uint8_t* gray = c.in.gray;
+    const gf_frame_ref* refs = c.refs;
     int refs_widest = 16, refs_narrow = -1;   // the widest piece of the first reader of the caller's frames; frames it counted itself
     if (prof) HIPCHK(hipEventRecord(h->ev[0], h->stream));
-    if (h->cfg.pixel_format && refs) {
-        if (int rc = cvt_launch_refs(refs, h->h_refs.p, h->cfg.pixel_format, h->d_cvt.p, N, W, H, h->stream, &refs_narrow)) return rc;
-        d_gray = h->d_cvt.p; refs = nullptr;
-        if (prof) HIPCHK(hipEventRecord(h->ev[8], h->stream));
-    } else if (h->cfg.pixel_format) {   // rosNodeTest.cpp:238-254: toCvCopy(msg, MONO8) ahead of CLAHE and trackImage; d_gray holds tight frames of the handle's format by list position, never written
-        if (int rc = cvt_launch(d_gray, (size_t)W * h->ch, h->cfg.pixel_format, h->d_cvt.p, N, W, H, h->stream)) return rc;
-        d_gray = h->d_cvt.p;
+    if (h->cfg.pixel_format) {   // rosNodeTest.cpp:238-254: toCvCopy(msg, MONO8) ahead of CLAHE and trackImage
+        if (int rc = refs ? cvt_launch_refs(refs, h->h_refs.p, h->cfg.pixel_format, h->d_cvt.p, N, W, H, h->stream, &refs_narrow)
+                          : cvt_launch(gray, (size_t)W * h->ch, h->cfg.pixel_format, h->d_cvt.p, N, W, H, h->stream)) return rc;
+        gray = h->d_cvt.p; refs = nullptr;
         if (prof) HIPCHK(hipEventRecord(h->ev[8], h->stream));
     }
-    if (h->cfg.equalize && refs) {
-        if (int rc = clahe_launch_refs(refs, h->d_eq.p, h->d_eq_lut.p, N, W, H, kClaheClip, kClaheTiles, kClaheTiles, h->stream)) return rc;
-        d_gray = h->d_eq.p; refs = nullptr; refs_widest = (W & 15) ? 4 : 16;
-        if (prof) HIPCHK(hipEventRecord(h->ev[7], h->stream));
-    } else if (h->cfg.equalize) {   // rosNodeTest.cpp:256-261: CLAHE on the gray frame before trackImage, into the handle's buffer (the caller's frames stay as they are); frames and LUTs by list position
-        if (int rc = clahe_launch(d_gray, h->d_eq.p, h->d_eq_lut.p, N, W, H, kClaheClip, kClaheTiles, kClaheTiles, h->stream)) return rc;
-        d_gray = h->d_eq.p;
+    if (h->cfg.equalize) {   // rosNodeTest.cpp:256-261: CLAHE on the gray frame before trackImage, into the handle's buffer (the caller's frames stay as they are); frames and LUTs by list position
+        if (int rc = refs ? clahe_launch_refs(refs, h->d_eq.p, h->d_eq_lut.p, N, W, H, kClaheClip, kClaheTiles, kClaheTiles, h->stream)
+                          : clahe_launch(gray, h->d_eq.p, h->d_eq_lut.p, N, W, H, kClaheClip, kClaheTiles, kClaheTiles, h->stream)) return rc;
+        if (refs) refs_widest = (W & 15) ? 4 : 16;
+        gray = h->d_eq.p; refs = nullptr;
         if (prof) HIPCHK(hipEventRecord(h->ev[7], h->stream));
     }
-    if (int rc = launch_pyramid(h, d_gray, N, cur_of, refs, refs ? &refs_widest : nullptr)) return rc;
+    if (int rc = launch_pyramid(h, gray, N, c.cur_of, refs, refs ? &refs_widest : nullptr)) return rc;
     if (prof) HIPCHK(hipEventRecord(h->ev[1], h->stream));
-    if (gray_refs) {
-        if (refs_narrow < 0) { refs_narrow = 0; for (int i = 0; i < N; i++) refs_narrow += gfref::unaligned(reinterpret_cast<uintptr_t>(gray_refs[i].data), gray_refs[i].pitch, refs_widest) ? 1 : 0; }
+    if (c.in.gray_refs) {
+        if (refs_narrow < 0) { refs_narrow = 0; for (int i = 0; i < N; i++) refs_narrow += gfref::unaligned(reinterpret_cast<uintptr_t>(c.in.gray_refs[i].data), c.in.gray_refs[i].pitch, refs_widest) ? 1 : 0; }
         h->stats.frames_unaligned += refs_narrow;
     }
+    return GF_OK;
+}
 
-    // ---- temporal optical flow (feature_tracker.cpp:113-176)
-    bool any_prev = false, any_pred = false, any_plain = false;
+// Temporal optical flow (feature_tracker.cpp:113-176): the sequences without a prediction in one launch from scratch, those with one in a second from their
+// predictions.  Returns when LK's tables are on the host.
+static int run_lk(Call& c) {
+    gf_tracker* h = c.h;
+    const int N = c.N, cap = h->cap;
+    const int* seq = c.seq;
+    HandOver& ho = c.ho;
     for (int i = 0; i < N; i++) {
-        SeqState& s = h->seq[seq[i]];
-        const int n = (int)s.prev_pts.size();
-        h->h_npts.p[i] = n;
-        if (n > cap) return set_err(GF_ERR_CAPACITY, "sequence %d holds %d points > capacity %d", seq[i], n, cap);
-        for (int k = 0; k < n; k++) h->h_prev_pts.p[(size_t)i * cap + k] = make_float2(s.prev_pts[k].x, s.prev_pts[k].y);
-        if (n > 0) {
-            any_prev = true;
-            if (s.hasPrediction && (int)s.predict_pts.size() != n) return set_err(GF_ERR_INVALID, "sequence %d: prediction holds %d points but %d are tracked (call removeOutliers before setPrediction, estimator.cpp:1134-1135)", seq[i], (int)s.predict_pts.size(), n);
-            if (s.hasPrediction) { any_pred = true; for (int k = 0; k < n; k++) h->h_init_pts.p[(size_t)i * cap + k] = make_float2(s.predict_pts[k].x, s.predict_pts[k].y); }
-            else any_plain = true;
-        }
+        bool has = false, pred = false;
+        char msg[256];
+        if (int rc = stage_points(h->seq[seq[i]], seq[i], cap, row(h->h_prev_pts, i, cap), row(h->h_init_pts, i, cap), h->h_npts.p + i, &has, &pred, msg, sizeof msg)) return set_err(rc, "%s", msg);
+        c.any_prev |= has; c.any_pred |= pred; c.any_plain |= has && !pred;
     }
-    bool lk_timed = false;
-    if (any_prev) {
-        if (over_bus) down(h->d_cur, h->h_cur, N);
-        if (refs_down) { down(h->d_refs, h->h_refs, (size_t)2 * h->B); refs_down = false; }
-        down(h->d_npts, h->h_npts, N);
-        if (h->d_seq_fb.p) { for (int i = 0; i < N; i++) h->h_seq_fb.p[i] = (uint8_t)h->par[seq[i]].flow_back; down(h->d_seq_fb, h->h_seq_fb, N); }
-        down(h->d_prev_pts, h->h_prev_pts, (size_t)N * cap);
+    if (c.any_prev) {
+        if (c.cur_of != h->d_cur.p) ho.down(h->d_cur, h->h_cur, N);   // read over the bus so far
+        c.add_refs();
+        ho.down(h->d_npts, h->h_npts, N);
+        if (h->d_seq_fb.p) { for (int i = 0; i < N; i++) h->h_seq_fb.p[i] = (uint8_t)h->par[seq[i]].flow_back; ho.down(h->d_seq_fb, h->h_seq_fb, N); }
+        ho.down(h->d_prev_pts, h->h_prev_pts, (size_t)N * cap);
         const uint8_t* mask_plain = nullptr; const uint8_t* mask_pred = nullptr;
-        if (any_pred) {
-            down(h->d_init_pts, h->h_init_pts, (size_t)N * cap);
+        if (c.any_pred) {
+            ho.down(h->d_init_pts, h->h_init_pts, (size_t)N * cap);
             for (int i = 0; i < N; i++) { const bool pred = h->seq[seq[i]].hasPrediction; h->h_seqmask.p[i] = pred ? 0 : 1; h->h_seqmask.p[N + i] = pred ? 1 : 0; }
-            down(h->d_seqmask, h->h_seqmask, 2 * (size_t)N);
+            ho.down(h->d_seqmask, h->h_seqmask, 2 * (size_t)N);
             mask_plain = h->d_seqmask.p; mask_pred = h->d_seqmask.p + N;
         }
-        if (int rc = flush()) return rc;
-        if (prof) HIPCHK(hipEventRecord(h->ev[2], h->stream));
-        if (any_plain) { launch_lk(h, N, lk_args(h, 3, 0, h->cfg.flow_back, 1, mask_plain, d_depth), depth_refs != nullptr); h->stats.lk_launches++; }
-        if (any_pred) { launch_lk(h, N, lk_args(h, 1, 1, h->cfg.flow_back, 1, mask_pred, d_depth), depth_refs != nullptr); h->stats.lk_launches++; }
+        if (int rc = ho.flush()) return rc;
+        if (h->profiling) HIPCHK(hipEventRecord(h->ev[2], h->stream));
+        if (c.any_plain) { launch_lk(h, N, lk_args(h, 3, 0, h->cfg.flow_back, 1, mask_plain, c.kdepth), c.in.depth_by_refs()); h->stats.lk_launches++; }
+        if (c.any_pred) { launch_lk(h, N, lk_args(h, 1, 1, h->cfg.flow_back, 1, mask_pred, c.kdepth), c.in.depth_by_refs()); h->stats.lk_launches++; }
         HIPCHK(hipGetLastError());
-        if (prof) { HIPCHK(hipEventRecord(h->ev[3], h->stream)); lk_timed = true; }
-        up(h->h_cur_pts, h->d_cur_pts, (size_t)N * cap);
-        up(h->h_status, h->d_status, (size_t)N * cap);
-        up(h->h_fwd_status, h->d_fwd_status, (size_t)N * cap);
-        up(h->h_depth_out, h->d_depth_out, (size_t)N * cap);
-        up(h->h_counters, h->d_counters, (size_t)N * cap * 2);
-        if (int rc = flush()) return rc;
+        if (h->profiling) HIPCHK(hipEventRecord(h->ev[3], h->stream));
+        ho.up(h->h_cur_pts, h->d_cur_pts, (size_t)N * cap);
+        ho.up(h->h_status, h->d_status, (size_t)N * cap);
+        ho.up(h->h_fwd_status, h->d_fwd_status, (size_t)N * cap);
+        ho.up(h->h_depth_out, h->d_depth_out, (size_t)N * cap);
+        ho.up(h->h_counters, h->d_counters, (size_t)N * cap * 2);
+        if (int rc = ho.flush()) return rc;
     }
     HIPCHK(hipEventRecord(h->ev[6], h->stream));
-    lap(h->stats.ms_host_pre);
+    c.lap(h->stats.ms_host_pre);
     HIPCHK(hipEventSynchronize(h->ev[6]));
-    lap(h->stats.ms_wait_lk);
+    c.lap(h->stats.ms_wait_lk);
+    return GF_OK;
+}
 
-    if (any_pred) {  // feature_tracker.cpp:124-132: fewer than 10 forward successes -> redo with 3 levels from scratch (per listed sequence: its neighbours in the call keep their pass)
-        bool need = false;
-        for (int i = 0; i < N; i++) {
-            h->h_seqmask.p[i] = 0;
-            if (!h->seq[seq[i]].hasPrediction || h->h_npts.p[i] == 0) continue;
-            int succ = 0;
-            for (int k = 0; k < h->h_npts.p[i]; k++) succ += h->h_fwd_status.p[(size_t)i * cap + k] ? 1 : 0;
-            if (succ < 10) { h->h_seqmask.p[i] = 1; need = true; }
-        }
-        if (need) {
-            std::vector<uint8_t> redo(h->h_seqmask.p, h->h_seqmask.p + N);
-            std::vector<uint8_t> keep_status(h->h_status.p, h->h_status.p + (size_t)N * cap);
-            std::vector<float2> keep_pts(h->h_cur_pts.p, h->h_cur_pts.p + (size_t)N * cap);
-            std::vector<uint16_t> keep_depth(h->h_depth_out.p, h->h_depth_out.p + (size_t)N * cap);
-            std::vector<unsigned> keep_cnt(h->h_counters.p, h->h_counters.p + (size_t)N * cap * 2);
-            HIPCHK(hipMemcpyAsync(h->d_seqmask.p, h->h_seqmask.p, N, hipMemcpyHostToDevice, h->stream));
-            launch_lk(h, N, lk_args(h, 3, 0, h->cfg.flow_back, 1, h->d_seqmask.p, d_depth), depth_refs != nullptr);
-            h->stats.lk_launches++;
-            HIPCHK(hipGetLastError());
-            up(h->h_cur_pts, h->d_cur_pts, (size_t)N * cap);
-            up(h->h_status, h->d_status, (size_t)N * cap);
-            up(h->h_depth_out, h->d_depth_out, (size_t)N * cap);
-            up(h->h_counters, h->d_counters, (size_t)N * cap * 2);
-            if (int rc = flush()) return rc;
-            HIPCHK(hipStreamSynchronize(h->stream));
-            for (int i = 0; i < N; i++) {
-                unsigned* cn = h->h_counters.p + (size_t)i * cap * 2;
-                const unsigned* kc = keep_cnt.data() + (size_t)i * cap * 2;
-                if (redo[i]) { for (int k = 0; k < 2 * cap; k++) cn[k] += kc[k]; continue; }  // both passes did work
-                memcpy(h->h_status.p + (size_t)i * cap, keep_status.data() + (size_t)i * cap, cap);
-                memcpy(h->h_cur_pts.p + (size_t)i * cap, keep_pts.data() + (size_t)i * cap, cap * sizeof(float2));
-                memcpy(h->h_depth_out.p + (size_t)i * cap, keep_depth.data() + (size_t)i * cap, cap * sizeof(uint16_t));
-                memcpy(cn, kc, cap * 2 * sizeof(unsigned));
-            }
-        }
+// feature_tracker.cpp:124-132: fewer than 10 forward successes -> redo with 3 levels from scratch (per listed sequence: its neighbours in the call keep their pass)
+static int redo_fallback(Call& c) {
+    gf_tracker* h = c.h;
+    const int N = c.N, cap = h->cap;
+    if (!c.any_pred) return GF_OK;
+    bool need = false;
+    for (int i = 0; i < N; i++) {
+        h->h_seqmask.p[i] = prediction_failed(h->seq[c.seq[i]], h->h_fwd_status.p + (size_t)i * cap, h->h_npts.p[i]) ? 1 : 0;
+        need |= h->h_seqmask.p[i] != 0;
     }
+    if (!need) return GF_OK;
+    std::vector<uint8_t> redo(h->h_seqmask.p, h->h_seqmask.p + N);
+    std::vector<uint8_t> keep_status(h->h_status.p, h->h_status.p + (size_t)N * cap);
+    std::vector<float2> keep_pts(h->h_cur_pts.p, h->h_cur_pts.p + (size_t)N * cap);
+    std::vector<uint16_t> keep_depth(h->h_depth_out.p, h->h_depth_out.p + (size_t)N * cap);
+    std::vector<unsigned> keep_cnt(h->h_counters.p, h->h_counters.p + (size_t)N * cap * 2);
+    HIPCHK(hipMemcpyAsync(h->d_seqmask.p, h->h_seqmask.p, N, hipMemcpyHostToDevice, h->stream));
+    launch_lk(h, N, lk_args(h, 3, 0, h->cfg.flow_back, 1, h->d_seqmask.p, c.kdepth), c.in.depth_by_refs());
+    h->stats.lk_launches++;
+    HIPCHK(hipGetLastError());
+    c.ho.up(h->h_cur_pts, h->d_cur_pts, (size_t)N * cap);
+    c.ho.up(h->h_status, h->d_status, (size_t)N * cap);
+    c.ho.up(h->h_depth_out, h->d_depth_out, (size_t)N * cap);
+    c.ho.up(h->h_counters, h->d_counters, (size_t)N * cap * 2);
+    if (int rc = c.ho.flush()) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < N; i++) {
+        unsigned* cn = h->h_counters.p + (size_t)i * cap * 2;
+        const unsigned* kc = keep_cnt.data() + (size_t)i * cap * 2;
+        if (redo[i]) { for (int k = 0; k < 2 * cap; k++) cn[k] += kc[k]; continue; }  // both passes did work
+        memcpy(h->h_status.p + (size_t)i * cap, keep_status.data() + (size_t)i * cap, cap);
+        memcpy(h->h_cur_pts.p + (size_t)i * cap, keep_pts.data() + (size_t)i * cap, cap * sizeof(float2));
+        memcpy(h->h_depth_out.p + (size_t)i * cap, keep_depth.data() + (size_t)i * cap, cap * sizeof(uint16_t));
+        memcpy(cn, kc, cap * 2 * sizeof(unsigned));
+    }
+    return GF_OK;
+}
 
-    // ---- host bookkeeping per listed sequence (feature_tracker.cpp:170-186)
+// Host bookkeeping behind LK (after_lk, gf_track_host.hpp) per listed sequence on the pool, and the detector's form of the list.
+static void book_after_lk(Call& c) {
+    gf_tracker* h = c.h;
+    const int cap = h->cap;
     std::atomic<long long> a_levels{0}, a_iters{0}, a_points{0}, a_tracked{0};
     std::atomic<int> a_want{0};
-    h->pool->parallel_for(N, [&](int b) {   // b: list position
-        SeqState& s = h->seq[seq[b]];
-        const gf_tracker_seq_cfg& par = h->par[seq[b]];
-        const uint16_t* dimg = hdep && par.depth_cam ? hdep[b] : nullptr;   // a sequence without a depth camera: its image is not read (its samples are never reported) and may be null
-        const int n = (int)s.prev_pts.size();
-        if (n > 0) {
-            const uint8_t* st = h->h_status.p + (size_t)b * cap;
-            s.cur_pts.resize(n); s.cur_depth.resize(n);
-            long long lv = 0, it = 0;
-            for (int i = 0; i < n; i++) {
-                const float2 c = h->h_cur_pts.p[(size_t)b * cap + i];
-                s.cur_pts[i] = {c.x, c.y};
-                if (dimg) { const int ry = (int)std::round((double)c.y), rx = (int)std::round((double)c.x); s.cur_depth[i] = st[i] ? dimg[(size_t)ry * hdstride + rx] : (uint16_t)0; }   // st: inside the image (post checks)
-                else if (hdep) s.cur_depth[i] = 0;
-                else s.cur_depth[i] = h->h_depth_out.p[(size_t)b * cap + i];
-                lv += h->h_counters.p[2 * ((size_t)b * cap + i)];
-                it += h->h_counters.p[2 * ((size_t)b * cap + i) + 1];
-            }
-            a_levels += lv; a_iters += it; a_points += n;
-            reduce_vector(s.prev_pts, st); reduce_vector(s.cur_pts, st); reduce_vector(s.ids, st); reduce_vector(s.track_cnt, st);
-            reduce_vector(s.cur_depth, st);
-            a_tracked += (long long)s.cur_pts.size();
-        }
-        for (auto& c : s.track_cnt) c++;
-        int nc = 0;
-        const uint32_t* roi = !h->roi_has.empty() && h->roi_has[seq[b]] ? h->roi_bits.data() + (size_t)seq[b] * h->roi_words : nullptr;
-        set_mask_host(h, s, h->seq_disk.empty() ? h->disk : h->seq_disk[seq[b]], roi, h->h_centers.p + (size_t)b * cap, nc);
-        h->h_ncenters.p[b] = nc;
-        const int want = par.max_cnt - (int)s.cur_pts.size();
+    h->pool->parallel_for(c.N, [&](int b) {   // b: list position
+        const int q = c.seq[b];
+        const gf_tracker_seq_cfg& par = h->par[q];
+        const size_t at = (size_t)b * cap;
+        const LkRows r{row(h->h_cur_pts, b, cap), h->h_status.p + at, c.in.kernel_samples(h->h_depth_out, b, cap), h->h_counters.p + 2 * at, c.in.host_image(b, par), c.in.host_dstride};
+        const uint32_t* roi = !h->roi_has.empty() && h->roi_has[q] ? h->roi_bits.data() + (size_t)q * h->roi_words : nullptr;
+        int want = 0;
+        const LkTally n = after_lk(h->seq[q], par, h->cfg.width, h->cfg.height, h->seq_disk.empty() ? h->disk : h->seq_disk[q], roi, r, row(h->h_centers, b, cap), h->h_ncenters.p + b, &want);
+        a_levels += n.level_passes; a_iters += n.iterations; a_points += n.points; a_tracked += n.tracked;
         h->h_want.p[b] = want;
         if (h->h_seq_md.p) h->h_seq_md.p[b] = par.min_dist;
         h->h_det.p[b] = want > 0 ? h->h_cur.p[b] : -1;
         if (want > 0) a_want = 1;
         h->h_out_n.p[b] = 0;
     });
-    const bool any_want = a_want.load() != 0;
+    c.any_want = a_want.load() != 0;
     h->stats.lk_level_passes += a_levels; h->stats.lk_iterations += a_iters; h->stats.lk_points += a_points; h->stats.tracked_features += a_tracked;
+}
 
-    // ---- Shi-Tomasi top-up (feature_tracker.cpp:190-206)
-    if (any_want) {
-        down(h->d_det, h->h_det, N);
-        if (refs_down) { down(h->d_refs, h->h_refs, (size_t)2 * h->B); refs_down = false; }
-        down(h->d_centers, h->h_centers, (size_t)N * cap);
-        down(h->d_ncenters, h->h_ncenters, N);
-        down(h->d_want, h->h_want, N);
-        if (h->d_seq_md.p) down(h->d_seq_md, h->h_seq_md, N);
-        down(h->d_out_n, h->h_out_n, N);   // zeros (set above): a sequence that neither selection kernel serves reads 0, not an earlier call's count
-        if (int rc = flush()) return rc;
+// Shi-Tomasi top-up (feature_tracker.cpp:190-206) for the sequences that want corners.  Returns with the stream drained.
+static int run_detect(Call& c) {
+    gf_tracker* h = c.h;
+    const int N = c.N, cap = h->cap;
+    const bool prof = h->profiling;
+    HandOver& ho = c.ho;
+    if (c.any_want) {
+        ho.down(h->d_det, h->h_det, N);
+        c.add_refs();
+        ho.down(h->d_centers, h->h_centers, (size_t)N * cap);
+        ho.down(h->d_ncenters, h->h_ncenters, N);
+        ho.down(h->d_want, h->h_want, N);
+        if (h->d_seq_md.p) ho.down(h->d_seq_md, h->h_seq_md, N);
+        ho.down(h->d_out_n, h->h_out_n, N);   // zeros (book_after_lk): a sequence that neither selection kernel serves reads 0, not an earlier call's count
+        if (int rc = ho.flush()) return rc;
         HIPCHK(hipMemsetAsync(h->d_maxkey.p, 0, N * sizeof(unsigned), h->stream));
         HIPCHK(hipMemsetAsync(h->d_cand_count.p, 0, N * sizeof(int), h->stream));
         if (prof) HIPCHK(hipEventRecord(h->ev[4], h->stream));
-        {
-            DetectArgs D{};
-            D.pyr = h->d_img.p; D.pyr_bytes = h->G.img_bytes; D.frame_of = h->d_det.p; D.g = h->G.lv[0];
-            D.mask = nullptr; D.mask_seq_stride = 0; D.centers = h->d_centers.p; D.n_centers = h->d_ncenters.p; D.cap = cap;
-            D.roi = h->d_roi.p; D.roi_seq_words = h->roi_words;   // null on a handle no setter has touched
-            D.disk_of = h->d_seq_disk.p;                          // likewise
-            D.maxkey = h->d_maxkey.p; D.cand = h->d_cand.p; D.cand_seq_stride = (size_t)h->cand_cap; D.cand_cap = h->cand_cap; D.cand_count = h->d_cand_count.p;
-            detect_strip_kernel<kDS_R><<<dim3((W + kDS_W - 1) / kDS_W, (H + kDS_R - 1) / kDS_R, N), 64, 0, h->stream>>>(D, h->disk);
-        }
-        SelectArgs S{};
-        S.cand = h->d_cand.p; S.cand_seq_stride = (size_t)h->cand_cap; S.cand_cap = h->cand_cap; S.cand_count = h->d_cand_count.p; S.maxkey = h->d_maxkey.p; S.want = h->d_want.p;
-        S.w = W; S.h = H; S.min_dist = h->cfg.min_dist; S.min_dist_of = h->d_seq_md.p; S.out_cap = cap; S.sort_cap = h->sort_cap; S.out_pts = h->d_out_pts.p; S.out_depth = h->d_out_depth.p; S.out_n = h->d_out_n.p;
-        S.depth = d_depth; S.depth_seq_stride = (size_t)W * H; S.depth_stride = W;
-        {   // the sequences that want a handful of corners (every frame but the first ones): one maximum per corner instead of a sort (select_topk_kernel; GF_SELECT_TOPK=0: off)
-            const bool topk_on = h->select_topk;
-            int max_want = 0;
-            for (int i = 0; i < N; i++) max_want = std::max(max_want, h->h_want.p[i]);
-            S.skip_small = topk_on ? 1 : 0;
-            if (depth_refs) {   // S.depth is the call's table: the _refs forms of the same two kernels
-                if (topk_on) select_topk_refs_kernel<<<dim3(N), 1024, 0, h->stream>>>(S);
-                if (!topk_on || max_want > kTopKMax) select_corners_refs_kernel<<<dim3(N), 1024, h->select_lds, h->stream>>>(S);
-            } else {
-                if (topk_on) select_topk_kernel<<<dim3(N), 1024, 0, h->stream>>>(S);
-                if (!topk_on || max_want > kTopKMax) select_corners_kernel<<<dim3(N), 1024, h->select_lds, h->stream>>>(S);
-            }
-        }
+        launch_detect(h, N, detect_args(h));
+        // the sequences that want a handful of corners (every frame but the first ones): one maximum per corner instead of a sort (select_topk_kernel; GF_SELECT_TOPK=0: off)
+        int max_want = 0;
+        for (int i = 0; i < N; i++) max_want = std::max(max_want, h->h_want.p[i]);
+        const bool topk = h->select_topk, sort = !topk || max_want > kTopKMax;
+        const SelectArgs S = select_args(h, c.kdepth, topk ? 1 : 0);
+        if (c.in.depth_by_refs()) launch_select<true>(h, N, S, topk, sort); else launch_select<false>(h, N, S, topk, sort);
         HIPCHK(hipGetLastError());
-        up(h->h_out_n, h->d_out_n, N);
-        up(h->h_out_pts, h->d_out_pts, (size_t)N * cap);
-        up(h->h_out_depth, h->d_out_depth, (size_t)N * cap);
-        up(h->h_cand_count, h->d_cand_count, N);
-        if (int rc = flush()) return rc;
+        ho.up(h->h_out_n, h->d_out_n, N);
+        ho.up(h->h_out_pts, h->d_out_pts, (size_t)N * cap);
+        ho.up(h->h_out_depth, h->d_out_depth, (size_t)N * cap);
+        ho.up(h->h_cand_count, h->d_cand_count, N);
+        if (int rc = ho.flush()) return rc;
     }
-    if (prof && !any_want) HIPCHK(hipEventRecord(h->ev[4], h->stream));
+    if (prof && !c.any_want) HIPCHK(hipEventRecord(h->ev[4], h->stream));
     if (prof) HIPCHK(hipEventRecord(h->ev[5], h->stream));
-    lap(h->stats.ms_host_mid);
+    c.lap(h->stats.ms_host_mid);
     HIPCHK(hipStreamSynchronize(h->stream));
-    lap(h->stats.ms_wait_detect);
-    if (prof) {
-        float ms = 0;
-        hipEvent_t from = h->ev[0];   // the stages ahead of the pyramid, each from where the one before it ended
-        if (h->cfg.pixel_format) { HIPCHK(hipEventElapsedTime(&ms, from, h->ev[8])); h->stats.ms_convert += ms; from = h->ev[8]; }
-        if (h->cfg.equalize) { HIPCHK(hipEventElapsedTime(&ms, from, h->ev[7])); h->stats.ms_equalize += ms; from = h->ev[7]; }
-        HIPCHK(hipEventElapsedTime(&ms, from, h->ev[1])); h->stats.ms_pyramid += ms;
-        if (lk_timed) { HIPCHK(hipEventElapsedTime(&ms, h->ev[2], h->ev[3])); h->stats.ms_lk += ms; }
-        HIPCHK(hipEventElapsedTime(&ms, h->ev[4], h->ev[5])); h->stats.ms_detect += ms;
-        HIPCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[5])); h->stats.ms_total_gpu += ms;
-    }
-    if (any_want)
-        for (int i = 0; i < N; i++) {
-            if (h->h_want.p[i] > 0 && h->h_cand_count.p[i] > h->cand_cap)
-                return set_err(GF_ERR_CAPACITY, "sequence %d: %d corner candidates exceed capacity %d", seq[i], h->h_cand_count.p[i], h->cand_cap);
-            // which branch of the corner selection served the sequence (the kernels' own tests on the same numbers)
-            const int want = h->h_want.p[i], n = std::min(h->h_cand_count.p[i], h->cand_cap);
-            if (want <= 0 || n <= 0) continue;
-            if (h->select_topk && want <= kTopKMax) { if (n > 1024 * kTopKQ) h->stats.select_streamed++; }
-            else {
-                int npow2 = 64;
-                while (npow2 < n) npow2 <<= 1;
-                if (npow2 > h->sort_cap) h->stats.select_global_sort++;
-            }
-        }
+    c.lap(h->stats.ms_wait_detect);
+    return GF_OK;
+}
 
-    // ---- addPoints, undistortedPts, ptsVelocity, pack (feature_tracker.cpp:85-93, 210-211, 322-368)
+static int read_profile(Call& c) {   // gf_tracker_set_profiling: the stages' times from the events of this call
+    gf_tracker* h = c.h;
+    float ms = 0;
+    hipEvent_t from = h->ev[0];   // the stages ahead of the pyramid, each from where the one before it ended
+    if (h->cfg.pixel_format) { HIPCHK(hipEventElapsedTime(&ms, from, h->ev[8])); h->stats.ms_convert += ms; from = h->ev[8]; }
+    if (h->cfg.equalize) { HIPCHK(hipEventElapsedTime(&ms, from, h->ev[7])); h->stats.ms_equalize += ms; from = h->ev[7]; }
+    HIPCHK(hipEventElapsedTime(&ms, from, h->ev[1])); h->stats.ms_pyramid += ms;
+    if (c.any_prev) { HIPCHK(hipEventElapsedTime(&ms, h->ev[2], h->ev[3])); h->stats.ms_lk += ms; }
+    HIPCHK(hipEventElapsedTime(&ms, h->ev[4], h->ev[5])); h->stats.ms_detect += ms;
+    HIPCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[5])); h->stats.ms_total_gpu += ms;
+    return GF_OK;
+}
+
+// The candidate capacity, and which branch of the corner selection served each sequence (the kernels' own tests on the same numbers).
+static int check_candidates(Call& c) {
+    gf_tracker* h = c.h;
+    for (int i = 0; i < c.N; i++) {
+        if (h->h_want.p[i] > 0 && h->h_cand_count.p[i] > h->cand_cap)
+            return set_err(GF_ERR_CAPACITY, "sequence %d: %d corner candidates exceed capacity %d", c.seq[i], h->h_cand_count.p[i], h->cand_cap);
+        const int want = h->h_want.p[i], n = std::min(h->h_cand_count.p[i], h->cand_cap);
+        if (want <= 0 || n <= 0) continue;
+        if (h->select_topk && want <= kTopKMax) { if (n > 1024 * kTopKQ) h->stats.select_streamed++; }
+        else {
+            int npow2 = 64;
+            while (npow2 < n) npow2 <<= 1;
+            if (npow2 > h->sort_cap) h->stats.select_global_sort++;
+        }
+    }
+    return GF_OK;
+}
+
+// Host bookkeeping behind the detection (after_detect, gf_track_host.hpp) per listed sequence on the pool: the sequences' new state and the caller's featureFrames.
+static int book_after_detect(Call& c, gf_feature_obs* out, int cap_out, int* n_out) {
+    gf_tracker* h = c.h;
+    const int cap = h->cap;
+    const bool have_depth = c.in.have_depth();
     std::atomic<int> a_overflow{-1};
     std::atomic<long long> a_out{0};
-    h->pool->parallel_for(N, [&](int b) {   // b: list position
-        SeqState& s = h->seq[seq[b]];
-        const gf_tracker_seq_cfg& par = h->par[seq[b]];
-        const uint16_t* dimg = hdep && par.depth_cam ? hdep[b] : nullptr;
-        const int nn = h->h_want.p[b] > 0 ? h->h_out_n.p[b] : 0;
-        for (int i = 0; i < nn; i++) {
-            const float2 p = h->h_out_pts.p[(size_t)b * cap + i];
-            s.cur_pts.push_back({p.x, p.y}); s.ids.push_back(s.n_id++); s.track_cnt.push_back(1);
-            s.cur_depth.push_back(dimg ? dimg[(size_t)(int)p.y * hdstride + (int)p.x] : hdep ? (uint16_t)0 : h->h_out_depth.p[(size_t)b * cap + i]);   // corners sit on pixel centres
-        }
-        s.cur_un_pts.clear();
-        for (auto& p : s.cur_pts) { double X, Y; lift_projective(par, (double)p.x, (double)p.y, X, Y); s.cur_un_pts.push_back({(float)(X / 1.0), (float)(Y / 1.0)}); }
-        pts_velocity(s);
-        s.prev_pts = s.cur_pts; s.prev_un_pts = s.cur_un_pts; s.prev_un_pts_map.swap(s.cur_un_pts_map); s.prev_time = s.cur_time;
-        s.hasPrediction = false;
-        s.slot ^= 1;   // the pyramid written in this call is the sequence's previous frame from here on
-        const int n = (int)s.ids.size();
-        // depth_cam set but no depth image: neither packing loop of the reference runs (feature_tracker.cpp:320 `depth_cam == 0`, :344 `!_img1.empty()`):
-        // the returned featureFrame is empty, the tracker state has advanced all the same
-        if (par.depth_cam && !have_depth) { n_out[b] = 0; return; }
-        if (n > cap_out) { a_overflow = n; n_out[b] = 0; return; }
-        gf_feature_obs* o = out + (size_t)b * cap_out;
-        for (int i = 0; i < n; i++) {
-            o[i].id = s.ids[i]; o[i].camera_id = 0;
-            o[i].v[0] = s.cur_un_pts[i].x; o[i].v[1] = s.cur_un_pts[i].y; o[i].v[2] = 1; o[i].v[3] = s.cur_pts[i].x; o[i].v[4] = s.cur_pts[i].y;
-            o[i].v[5] = s.pts_velocity[i].x; o[i].v[6] = s.pts_velocity[i].y;
-            o[i].v[7] = par.depth_cam ? (double)(int)s.cur_depth[i] / 1000 : -2.4;
-        }
-        n_out[b] = n;
-        a_out += n;
+    h->pool->parallel_for(c.N, [&](int b) {   // b: list position
+        const int q = c.seq[b];
+        const DetectRows r{row(h->h_out_pts, b, cap), c.in.kernel_samples(h->h_out_depth, b, cap), h->h_want.p[b] > 0 ? h->h_out_n.p[b] : 0, c.in.host_image(b, h->par[q]), c.in.host_dstride};
+        const Packed p = after_detect(h->seq[q], h->par[q], r, have_depth, out + (size_t)b * cap_out, cap_out);
+        if (p.overflow >= 0) a_overflow = p.overflow;
+        n_out[b] = p.written;
+        a_out += p.written;
     });
     if (a_overflow.load() >= 0) return set_err(GF_ERR_CAPACITY, "output capacity %d < %d features", cap_out, a_overflow.load());
     h->stats.output_features += a_out;
+    return GF_OK;
+}
+
+// One frame for each of the `count` listed sequences (seq: checked by check_list); sequences that are not listed keep their whole state.  Everything the caller hands
+// in or gets back (t, the frames of `in`, out, n_out) and every hand-over table of the handle is indexed by the position i in the list, so the work and the bytes of
+// a call follow `count`; only h->seq[], h->par[] and the pyramid pairs are indexed by the sequence seq[i].
+static int track_core(gf_tracker* h, int count, const int* seq, const double* t, const FrameInput& in, gf_feature_obs* out, int cap_out, int* n_out) {
+    if (count == 0) return GF_OK;
+    Call c{h, count, seq, in, HandOver(h->copy_lists, h->stream)};
+    for (int i = 0; i < count; i++) h->h_cur.p[i] = 2 * seq[i] + begin_frame(h->seq[seq[i]], t[i]);   // the new frame goes to the sequence's other pyramid
+    if (int rc = publish(c)) return rc;
+    if (int rc = launch_front(c)) return rc;
+    if (int rc = run_lk(c)) return rc;
+    if (int rc = redo_fallback(c)) return rc;
+    book_after_lk(c);
+    if (int rc = run_detect(c)) return rc;
+    if (h->profiling) if (int rc = read_profile(c)) return rc;
+    if (c.any_want) if (int rc = check_candidates(c)) return rc;
+    if (int rc = book_after_detect(c, out, cap_out, n_out)) return rc;
     h->stats.frames++;
-    h->stats.sequence_frames += N;
-    lap(h->stats.ms_host_post);
+    h->stats.sequence_frames += count;
+    c.lap(h->stats.ms_host_post);
     return GF_OK;
 }
 
@@ -877,7 +844,7 @@ int gf_tracker_track_some_device(gf_tracker* h, int count, const int* seq, const
     if (int rc = gf::check_list(h, count, seq)) return rc;
     if (count == 0) return GF_OK;
     if (!t || !d_gray || !out || !n_out) return gf::set_err(GF_ERR_INVALID, "null argument");
-    return gf::track_core(h, count, seq, t, (const uint8_t*)d_gray, (const uint16_t*)d_depth, out, cap, n_out);
+    return gf::track_core(h, count, seq, t, gf::FrameInput::device((const uint8_t*)d_gray, (const uint16_t*)d_depth), out, cap, n_out);
 }
 
 // ---- the same with one gf_frame_ref per listed sequence (gf_frame_ref.hpp)
@@ -911,7 +878,7 @@ int gf_tracker_track_some_device_refs(gf_tracker* h, int count, const int* seq, 
     if (int rc = gf::check_refs(h, count, seq, gray, (size_t)h->cfg.width * h->ch, false, "gray")) return rc;
     if (depth) if (int rc = gf::check_refs(h, count, seq, depth, (size_t)h->cfg.width * 2, true, "depth")) return rc;
     if (int rc = gf::refs_ready(h)) return rc;
-    return gf::track_core(h, count, seq, t, nullptr, nullptr, out, cap, n_out, nullptr, 0, gray, depth);
+    return gf::track_core(h, count, seq, t, gf::FrameInput::by_refs(gray, depth), out, cap, n_out);
 }
 
 int gf_tracker_track_batch_device_refs(gf_tracker* h, const double* t, const gf_frame_ref* gray, const gf_frame_ref* depth, gf_feature_obs* out, int cap, int* n_out) {
@@ -925,17 +892,13 @@ int gf_tracker_track_some(gf_tracker* h, int count, const int* seq, const double
     if (int rc = gf::check_list(h, count, seq)) return rc;
     if (count == 0) return GF_OK;
     if (!t || !gray || !out || !n_out) return gf::set_err(GF_ERR_INVALID, "null argument");
-    const int W = h->cfg.width, H = h->cfg.height;
-    const size_t row = (size_t)W * h->ch;   // bytes of a row of the handle's pixel format
-    if (int rc = gf::check_stride(h, stride)) return rc;
-    bool have_depth = depth != nullptr;
-    for (int i = 0; i < count; i++) {   // refuse before the first copy
-        if (!gray[i]) return gf::set_err(GF_ERR_INVALID, "null image for sequence %d", seq[i]);
-        if (have_depth && !depth[i] && h->par[seq[i]].depth_cam) have_depth = false;
-    }
+    bool have_depth = false;
+    if (int rc = gf::check_host_frames(h, count, seq, gray, stride, depth, &have_depth)) return rc;   // refuse before the first copy
+    const size_t row = (size_t)h->cfg.width * h->ch;   // bytes of a row of the handle's pixel format
+    const int H = h->cfg.height;
     for (int i = 0; i < count; i++) HIPCHK(hipMemcpy2DAsync(h->d_raw.p + (size_t)i * row * H, row, gray[i], stride, row, H, hipMemcpyHostToDevice, h->stream));
-    // the depth image stays where it is: its <= max_cnt samples are taken on the host (track_core)
-    return gf::track_core(h, count, seq, t, h->d_raw.p, nullptr, out, cap, n_out, have_depth ? depth : nullptr, dstride);
+    // the depth image stays where it is: its <= max_cnt samples are taken on the host (after_lk, after_detect)
+    return gf::track_core(h, count, seq, t, gf::FrameInput::with_host_depth(h->d_raw.p, have_depth ? depth : nullptr, dstride), out, cap, n_out);
 }
 
 // The host-image boundary (trackImage(const cv::Mat&), feature_tracker.h:47) without serialising on the bus: the images of frame k + 1 go to the second pair of
@@ -946,14 +909,10 @@ int gf_tracker_prefetch_some(gf_tracker* h, int count, const int* seq, const uin
     if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
     if (int rc = gf::check_list(h, count, seq)) return rc;
     if (count > 0 && !gray) return gf::set_err(GF_ERR_INVALID, "null argument");
-    const int W = h->cfg.width, H = h->cfg.height;
-    const size_t row = (size_t)W * h->ch;   // bytes of a row of the handle's pixel format
-    if (int rc = gf::check_stride(h, stride)) return rc;
-    bool have_depth = depth != nullptr;
-    for (int i = 0; i < count; i++) {
-        if (!gray[i]) return gf::set_err(GF_ERR_INVALID, "null image for sequence %d", seq[i]);
-        if (have_depth && !depth[i] && h->par[seq[i]].depth_cam) have_depth = false;
-    }
+    bool have_depth = false;
+    if (int rc = gf::check_host_frames(h, count, seq, gray, stride, depth, &have_depth)) return rc;
+    const size_t row = (size_t)h->cfg.width * h->ch;   // bytes of a row of the handle's pixel format
+    const int H = h->cfg.height;
     if (h->pf_count >= 2) return gf::set_err(GF_ERR_CAPACITY, "two frames are staged already: gf_tracker_track_prefetched has to consume one first");
     if (!h->copy_stream) {
         HIPCHK(hipStreamCreateWithFlags(&h->copy_stream.s, hipStreamNonBlocking));
@@ -984,7 +943,7 @@ int gf_tracker_track_prefetched(gf_tracker* h, const double* t, gf_feature_obs* 
     if (!seq.empty() && (!t || !out || !n_out)) return gf::set_err(GF_ERR_INVALID, "null argument");
     HIPCHK(hipStreamWaitEvent(h->stream, h->ev_copy[slot], 0));
     h->pf_head ^= 1; h->pf_count--;
-    return gf::track_core(h, (int)seq.size(), seq.data(), t, slot ? h->d_raw2.p : h->d_raw.p, nullptr, out, cap, n_out, h->pf_depth[slot] ? h->pf_hdepth[slot].data() : nullptr, h->pf_hdstride[slot]);
+    return gf::track_core(h, (int)seq.size(), seq.data(), t, gf::FrameInput::with_host_depth(slot ? h->d_raw2.p : h->d_raw.p, h->pf_depth[slot] ? h->pf_hdepth[slot].data() : nullptr, h->pf_hdstride[slot]), out, cap, n_out);
 }
 
 // ---- the lock-step forms: the same calls with every sequence listed in order
@@ -1024,16 +983,7 @@ int gf_tracker_track(gf_tracker* h, int seq, double t, const uint8_t* gray, int 
 
 int gf_tracker_set_prediction(gf_tracker* h, int seq, const int* ids, const double* xyz, int n) {
     if (!h || seq < 0 || seq >= h->B || (n > 0 && (!ids || !xyz))) return gf::set_err(GF_ERR_INVALID, "bad argument");
-    gf::SeqState& s = h->seq[seq];
-    s.hasPrediction = true;
-    s.predict_pts.clear();
-    std::map<int, const double*> m;
-    for (int i = 0; i < n; i++) m[ids[i]] = xyz + 3 * i;
-    for (size_t i = 0; i < s.ids.size(); i++) {
-        auto it = m.find(s.ids[i]);
-        if (it != m.end()) { double u, v; gf::space_to_plane(h->par[seq], it->second, u, v); s.predict_pts.push_back({(float)u, (float)v}); }
-        else s.predict_pts.push_back(s.prev_pts[i]);
-    }
+    gf::set_prediction(h->seq[seq], h->par[seq], ids, xyz, n);
     return GF_OK;
 }
 
@@ -1067,13 +1017,7 @@ int gf_tracker_set_roi_some_device(gf_tracker* h, int count, const int* seq, con
     HIPCHK(hipMemcpyAsync(h->d_roi_seq.p, seq, (size_t)count * sizeof(int), hipMemcpyHostToDevice, h->stream));
     gf::roi_pack_kernel<<<dim3((W + 255) / 256, gfroi::bands(H), count), 256, 0, h->stream>>>((const uint8_t*)d_masks, h->d_roi_seq.p, W, H, h->d_roi.p, h->roi_words);
     HIPCHK(hipGetLastError());
-    for (int i = 0; i < count; i++) {   // the words come back: setMask's walk reads them on the host
-        const size_t off = (size_t)seq[i] * h->roi_words;
-        HIPCHK(hipMemcpyAsync(h->roi_bits.data() + off, h->d_roi.p + off, h->roi_words * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < count; i++) h->roi_has[seq[i]] = 1;
-    return GF_OK;
+    return gf::roi_packed(h, count, seq);
 }
 
 int gf_tracker_set_roi_some_device_refs(gf_tracker* h, int count, const int* seq, const gf_frame_ref* masks) {
@@ -1090,13 +1034,7 @@ int gf_tracker_set_roi_some_device_refs(gf_tracker* h, int count, const int* seq
     HIPCHK(hipMemcpyAsync(h->d_roi_seq.p, seq, (size_t)count * sizeof(int), hipMemcpyHostToDevice, h->stream));
     gf::roi_pack_refs_kernel<<<dim3((W + 255) / 256, gfroi::bands(H), count), 256, 0, h->stream>>>(h->d_refs.p, h->d_roi_seq.p, W, H, h->d_roi.p, h->roi_words);
     HIPCHK(hipGetLastError());
-    for (int i = 0; i < count; i++) {   // the words come back: setMask's walk reads them on the host
-        const size_t off = (size_t)seq[i] * h->roi_words;
-        HIPCHK(hipMemcpyAsync(h->roi_bits.data() + off, h->d_roi.p + off, h->roi_words * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < count; i++) h->roi_has[seq[i]] = 1;
-    return GF_OK;
+    return gf::roi_packed(h, count, seq);
 }
 
 int gf_tracker_get_roi(gf_tracker* h, int seq, uint8_t* mask, int stride, int* has) {
@@ -1169,11 +1107,7 @@ int gf_tracker_reset_seq(gf_tracker* h, int seq) {
 
 int gf_tracker_remove_outliers(gf_tracker* h, int seq, const int* ids, int n) {
     if (!h || seq < 0 || seq >= h->B || (n > 0 && !ids)) return gf::set_err(GF_ERR_INVALID, "bad argument");
-    gf::SeqState& s = h->seq[seq];
-    std::set<int> rm(ids, ids + n);
-    std::vector<uint8_t> st;
-    for (size_t i = 0; i < s.ids.size(); i++) st.push_back(rm.count(s.ids[i]) ? 0 : 1);
-    gf::reduce_vector(s.prev_pts, st.data()); gf::reduce_vector(s.ids, st.data()); gf::reduce_vector(s.track_cnt, st.data());
+    gf::remove_outliers(h->seq[seq], ids, n);
     return GF_OK;
 }
 
@@ -1292,17 +1226,13 @@ int gf_good_features(const uint8_t* img, int width, int height, const uint8_t* m
     HIPCHK(hipMemcpyAsync(h->d_want.p, h->h_want.p, sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(h->d_maxkey.p, 0, sizeof(unsigned), h->stream));
     HIPCHK(hipMemsetAsync(h->d_cand_count.p, 0, sizeof(int), h->stream));
-    {
-        gf::DetectArgs D{};
-        D.pyr = h->d_img.p; D.pyr_bytes = h->G.img_bytes; D.frame_of = h->d_cur.p; D.g = h->G.lv[0];   // pyramid 0, written above; max_corners >= 1
-        D.mask = h->d_mask.p; D.mask_seq_stride = h->mask_stride; D.centers = nullptr; D.n_centers = nullptr; D.cap = h->cap;
-        D.maxkey = h->d_maxkey.p; D.cand = h->d_cand.p; D.cand_seq_stride = (size_t)h->cand_cap; D.cand_cap = h->cand_cap; D.cand_count = h->d_cand_count.p;
-        gf::detect_strip_kernel<gf::kDS_R><<<dim3((W + gf::kDS_W - 1) / gf::kDS_W, (H + gf::kDS_R - 1) / gf::kDS_R, 1), 64, 0, h->stream>>>(D, h->disk);
-    }
-    gf::SelectArgs S{};
-    S.cand = h->d_cand.p; S.cand_seq_stride = (size_t)h->cand_cap; S.cand_cap = h->cand_cap; S.cand_count = h->d_cand_count.p; S.maxkey = h->d_maxkey.p; S.want = h->d_want.p;
-    S.w = W; S.h = H; S.min_dist = min_dist; S.out_cap = h->cap; S.sort_cap = h->sort_cap; S.out_pts = h->d_out_pts.p; S.out_depth = h->d_out_depth.p; S.out_n = h->d_out_n.p;
-    gf::select_corners_kernel<<<dim3(1), 1024, h->select_lds, h->stream>>>(S);
+    gf::DetectArgs D = gf::detect_args(h);
+    D.frame_of = h->d_cur.p;   // pyramid 0, written above; max_corners >= 1
+    D.mask = h->d_mask.p; D.mask_seq_stride = h->mask_stride; D.centers = nullptr; D.n_centers = nullptr;
+    gf::launch_detect(h, 1, D);
+    gf::SelectArgs S = gf::select_args(h, nullptr, 0);
+    S.min_dist = min_dist;
+    gf::launch_select<false>(h, 1, S, false, true);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h->h_out_n.p, h->d_out_n.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(h->h_out_pts.p, h->d_out_pts.p, (size_t)h->cap * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
