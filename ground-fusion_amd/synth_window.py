@@ -69,8 +69,9 @@ class Trajectory:
 
 
 def make_window(seed, pre, W=10, n_landmarks=220, max_features=150, use_wheel=True, frame0=0, perturb=True, prior=None,
-                fix_ex_pose=1, fix_ex_wheel=0, fix_ix=1, fix_td=1, fix_td_wheel=1, gnss=False, gnss_lowspeed=0, anchor=False):
-    """Window over frames frame0 .. frame0+W of trajectory `seed`."""
+                fix_ex_pose=1, fix_ex_wheel=0, fix_ix=1, fix_td=1, fix_td_wheel=1, gnss=False, gnss_lowspeed=0, anchor=False, gnss_kw=None):
+    """Window over frames frame0 .. frame0+W of trajectory `seed`.  gnss_kw: keyword parameters of add_gnss (site, time of week, ionosphere table, elevation bands,
+    satellites per constellation, visibility rule)."""
     rng = np.random.default_rng(seed * 7919 + 13 + frame0)
     traj = Trajectory(seed, T=(frame0 + W + 3) / 15.0 + 0.5)
     dt_f = 1.0 / 15.0
@@ -177,7 +178,7 @@ def make_window(seed, pre, W=10, n_landmarks=220, max_features=150, use_wheel=Tr
     w["fix_ex_pose"], w["fix_ex_wheel"], w["fix_ix"], w["fix_td"], w["fix_td_wheel"], w["fix_poses"] = fix_ex_pose, fix_ex_wheel, fix_ix, fix_td, fix_td_wheel, 0
     w["G"] = G
     if gnss:
-        add_gnss(w, seed, traj, times, frame0, perturb, gnss_lowspeed)
+        add_gnss(w, seed, traj, times, frame0, perturb, gnss_lowspeed, **(gnss_kw or {}))
     if anchor:
         w["has_anchor"] = 1
         w["anchor_value"] = np.concatenate([Ps[0], quat_from_R(Rs[0])])
@@ -202,10 +203,15 @@ def R_ecef_enu(lat_deg, lon_deg):
                      [0, np.cos(lat), np.sin(lat)]])
 
 
-def add_gnss(w, seed, traj, times, frame0, perturb, lowspeed, sats_per_sys=3, lat=31.03, lon=121.44, alt=20.0, yaw=0.3):
+def add_gnss(w, seed, traj, times, frame0, perturb, lowspeed, sats_per_sys=3, lat=31.03, lon=121.44, alt=20.0, yaw=0.3, tow0=345600.0, iono=None, el_range=(32.0, 80.0),
+             visible=None):
     """4 constellations x sats_per_sys satellites above 30 deg elevation, one pseudorange + Doppler pair per satellite and frame, observation epochs
     a few ms off the frame stamps (so the interpolation ratio of estimator.cpp:3187-3198 is exercised).  Delays (iono / tropo) are left out of
-    the synthetic pseudoranges: they only shift the residuals by a few metres, which the clock states absorb."""
+    the synthetic pseudoranges: they only shift the residuals by a few metres, which the clock states absorb.
+    The site (lat, lon [deg], alt [m]), the time of week of the window's time 0 (tow0), the Klobuchar table (iono, 8 numbers; None: the YAML's) and the elevation band
+    are parameters: el_range is one (lo, hi) pair in degrees, or a list of pairs that the satellites of a constellation take in turn (satellite q the pair q modulo
+    the list's length).  visible(frame, constellation, satellite) -> bool says which observations exist (None: all).  An observation that is left out still takes its
+    random draws, so the ones that stay are those of the full list; with the defaults every draw and every number is what it was before these parameters existed."""
     W = w["W"]
     rng = np.random.default_rng(seed * 6007 + 11)      # constellation: fixed per seed
     orng = np.random.default_rng(seed * 6011 + 17 + frame0)
@@ -214,19 +220,21 @@ def add_gnss(w, seed, traj, times, frame0, perturb, lowspeed, sats_per_sys=3, la
     Ry = np.array([[np.cos(yaw), -np.sin(yaw), 0], [np.sin(yaw), np.cos(yaw), 0], [0, 0, 1.0]])
     R_el = Re @ Ry
     sats = []
+    bands = [el_range] if np.ndim(el_range) == 1 else list(el_range)
     for sys in range(4):
-        for _ in range(sats_per_sys):
-            az, el, rg = rng.uniform(0, 2 * np.pi), rng.uniform(np.radians(32), np.radians(80)), rng.uniform(2.0e7, 2.5e7)
+        for q in range(sats_per_sys):
+            el_lo, el_hi = bands[q % len(bands)]
+            az, el, rg = rng.uniform(0, 2 * np.pi), rng.uniform(np.radians(el_lo), np.radians(el_hi)), rng.uniform(2.0e7, 2.5e7)
             d_enu = np.array([np.sin(az) * np.cos(el), np.cos(az) * np.cos(el), np.sin(el)])
             pos = anc + Re @ (d_enu * rg)
             vel = Re @ (np.cross(d_enu, rng.normal(0, 1, 3)) * 1.5e3)
-            sats.append((sys, pos, vel, rng.uniform(-2e-4, 2e-4), rng.uniform(-1e-11, 1e-11), rng.uniform(-8e-9, 8e-9)))
+            sats.append((sys, pos, vel, rng.uniform(-2e-4, 2e-4), rng.uniform(-1e-11, 1e-11), rng.uniform(-8e-9, 8e-9), q))
     dt_true = np.array([150.0, 180.0, 120.0, 200.0])   # receiver clock bias per constellation [m]
     ddt_true = 2.0                                       # drift [m/s]
     frames, lowers, syss, ratios, data = [], [], [], [], []
     wl = C_LIGHT / 1575.42e6
     for i in range(W + 1):
-        for (sys, pos, vel, svdt, svddt, tgd) in sats:
+        for (sys, pos, vel, svdt, svddt, tgd, q) in sats:
             ts = times[i] + orng.uniform(-0.02, 0.02)
             if times[i] > ts:
                 lower = 0 if i == 0 else i - 1
@@ -243,11 +251,13 @@ def add_gnss(w, seed, traj, times, frame0, perturb, lowspeed, sats_per_sys=3, la
             psr = rg + OMG_E * (sp[0] * P_e[1] - sp[1] * P_e[0]) / C_LIGHT + clk - svdt * C_LIGHT + tgd * C_LIGHT + orng.normal(0, 0.5)
             dop_est = (vel - V_e) @ unit + OMG_E / C_LIGHT * (vel[0] * P_e[1] + sp[0] * V_e[1] - vel[1] * P_e[0] - sp[1] * V_e[0]) + ddt_true - svddt * C_LIGHT
             dopp = -(dop_est + orng.normal(0, 0.05)) / wl
+            if visible is not None and not visible(i, sys, q):
+                continue
             frames.append(i); lowers.append(lower); syss.append(sys); ratios.append(ratio)
-            data.append([*sp, *vel, svdt, svddt, tgd, 2.0, 2.0, psr, dopp, wl, 345600.0 + ts, 0.0])
+            data.append([*sp, *vel, svdt, svddt, tgd, 2.0, 2.0, psr, dopp, wl, tow0 + ts, 0.0])
     w["gnss_enabled"], w["gnss_lowspeed"] = 1, lowspeed
     w["gnss_frame"], w["gnss_lower"], w["gnss_sys"], w["gnss_ratio"], w["gnss_data"] = frames, lowers, syss, np.array(ratios), np.array(data)
-    w["gnss_iono"], w["gnss_headers"], w["gnss_ddt_weight"] = IONO.copy(), np.array(times), 10.0
+    w["gnss_iono"], w["gnss_headers"], w["gnss_ddt_weight"] = (IONO.copy() if iono is None else np.array(iono, np.float64)), np.array(times), 10.0
     prng = np.random.default_rng(seed * 6029 + 5 + frame0)
     clk0 = np.array([[dt_true[q] + ddt_true * (times[i] - times[0] + frame0 / 15.0) for q in range(4)] for i in range(W + 1)])
     w["para_rcv_dt"] = clk0 + (prng.normal(0, 3.0, clk0.shape) if perturb else 0.0)

@@ -8,6 +8,8 @@ Scenarios
                           must give the digest of plain / gnss
   slots, slots_fresh      gf_ba_pack_slot / gf_ba_solve_packed with slots that sit batches out, behind other windows in the same slots / in a fresh handle:
                           must give the same digest
+  gnss_thinned, gnss_thinned_after   the thinned GNSS list of tests/gnss_hard_cases.py (a frame without observations, groups of one, a constellation absent) in a fresh handle /
+                          behind the 352-factor list in the same slot (the scratch rows and group tables keep the longer list's tail): must give the same digest
   group, group_gnss       gf_estimator_group_* on staggered streams (members initialise at different times: batches with inactive and never-packed slots)"""
 import hashlib
 import os
@@ -98,6 +100,22 @@ def sc_gnss(after):
     return d.hex()
 
 
+def sc_gnss_thinned(after):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import gnss_hard_cases as GH
+    est = gfamd.Estimator(max_features=16, max_visual=256, max_gnss=352)
+    d = Digest()
+    for name in (["polar_north_352"] if after else []) + ["night_thinned"]:
+        w = GH.window_of(name, O)
+        lin = est.linearize(w.copy())
+        s = est.solve([w], 8)[0]
+        p0 = est.marginalize([w], 0)[0]
+        if name == "night_thinned":
+            d.add(lin["H"], lin["g"], lin["cost"], {k: w[k] for k in gw.STATE_KEYS}, s, p0["J"], p0["r"], list(p0["block_id"]))
+    est.close()
+    return d.hex()
+
+
 def sc_slots(behind=True):
     """the estimator group's route into the solver, driven by hand: slots packed one by one, batches in which some slots sit out, marginalisation of listed slots;
     the windows of the second round must not see what the first round left in their slots"""
@@ -169,6 +187,7 @@ def sc_group(gnss):
 SCENARIOS = {
     "plain": lambda: sc_plain(False), "plain_after": lambda: sc_plain(True),
     "gnss": lambda: sc_gnss(False), "gnss_after": lambda: sc_gnss(True),
+    "gnss_thinned": lambda: sc_gnss_thinned(False), "gnss_thinned_after": lambda: sc_gnss_thinned(True),
     "slots": lambda: sc_slots(True), "slots_fresh": lambda: sc_slots(False),
     "group": lambda: sc_group(False), "group_gnss": lambda: sc_group(True),
 }

@@ -726,7 +726,8 @@ def marg_golden(w, mode=0):
                gw.SX: ("para_Ix", 0), gw.SY: ("para_Ix", 1), gw.SW: ("para_Ix", 2), gw.TD: ("para_Td", 0), gw.TD_WHEEL: ("para_Td_wheel", 0),
                gw.RCV_DT: ("para_rcv_dt", i), gw.RCV_DDT: ("para_rcv_ddt", i), gw.YAW: ("para_yaw_enu_local", 0), gw.ANC: ("para_anc_ecef", 0)}[kind]
         x0 += [float(v) for v in w[off[0]][off[1]:off[1] + gs]]
-    return {"kept": kept, "m": m, "n": n, "JtJ": JtJ, "Jtr": Jtr, "J": Jlin, "r": rlin, "x0": x0, "eigenvalues_kept": evs, "eigenvalues_dropped": sorted(float(x) for x in ev)}
+    return {"kept": kept, "m": m, "n": n, "JtJ": JtJ, "Jtr": Jtr, "J": Jlin, "r": rlin, "x0": x0, "eigenvalues_kept": evs, "eigenvalues_dropped": sorted(float(x) for x in ev),
+            "diag_kept_unreduced": [float(A[m + k, m + k]) for k in range(n)]}
 
 
 def first_step_golden(w, ids, H, g):
@@ -862,5 +863,132 @@ def main():
         print("   wrote", path, os.path.getsize(path), "bytes")
 
 
+# ---------------------------------------------------------------- GNSS hard cases (tests/gnss_hard_cases.py): new fixtures only, the formulas are the ones above
+def gnss_own_columns(w, ids):
+    """single-factor windows: the one GnssPsrDoppFactor's r (2) and J (2 x 18: P_lo 3, V_lo 3, P_hi 3, V_hi 3, rcv_dt, rcv_ddt, yaw_enu_local, anc_ecef 3), and for each column
+    only GNSS blocks feed -- its rcv_dt, its rcv_ddt, the anchor, yaw_enu_local where it is a column -- every term J_k,col r_k of g (the factor's two rows, the clock
+    factors' rows), their sum at 60 digits and the sum of their absolute values"""
+    import gfwindow as gw
+    assert int(w["n_gnss"]) == 1
+    fac = gnss_factors(w)
+    r, blocks = fac[0]
+    J = dict(blocks)
+    i, lo, sys_ = int(w["gnss_frame"][0]), int(w["gnss_lower"][0]), int(w["gnss_sys"][0])
+    parts = [J[gw.bid(gw.POSE, lo)][:, 0:3], J[gw.bid(gw.SPEEDBIAS, lo)][:, 0:3], J[gw.bid(gw.POSE, lo + 1)][:, 0:3], J[gw.bid(gw.SPEEDBIAS, lo + 1)][:, 0:3],
+             J[gw.bid(gw.RCV_DT, 4 * i + sys_)], J[gw.bid(gw.RCV_DDT, i)], J[gw.bid(gw.YAW)], J[gw.bid(gw.ANC)]]
+    J18 = [[float(P[row, c]) for P in parts for c in range(P.cols)] for row in range(2)]
+    cols = []
+    for b, width in ((gw.bid(gw.RCV_DT, 4 * i + sys_), 1), (gw.bid(gw.RCV_DDT, i), 1), (gw.bid(gw.YAW), 1), (gw.bid(gw.ANC), 3)):
+        if b not in ids:
+            continue
+        for q in range(width):
+            terms = [Jm[row, q] * rk[row] for rk, bl in fac for bb, Jm in bl if bb == b for row in range(Jm.rows)]
+            cols.append({"block": int(b), "offset": q, "column": ids.index(b) + q, "g": float(sum(terms)), "abs_sum": float(sum(abs(t) for t in terms)), "terms": [float(t) for t in terms]})
+    return {"frame": i, "lower": lo, "sys": sys_, "r": [float(r[0]), float(r[1])], "J": J18, "own_columns": cols}
+
+
+def main_gnss_hard(names):
+    """python tests/golden/make_ref_golden.py gnss_hard [case ...]: ref_window_gnss_<case>, ref_marg_old_gnss_<case> and the single-factor windows of tests/gnss_hard_cases.py.
+    The oracle's distance from every new fixture goes into profiles/gnss_model_census.json (`measured`)."""
+    import gzip
+    import oracle_py as O
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import gnss_hard_cases as GH
+    measured = {}
+    for case in (names or list(GH.ALL)):
+        kind = GH.ALL[case][3]
+        w = GH.window_of(case, O)
+        if kind == "marg":
+            O.ba_solve(w, 4)
+            w.finalize()
+            g = marg_golden(w, 0)
+            n = g["n"]
+            JtJ = np.array([[float(g["JtJ"][a, c]) for c in range(n)] for a in range(n)])
+            Jtr = np.array([float(g["Jtr"][a]) for a in range(n)])
+            po = O.ba_marginalize(w.copy(), 0)
+            Jo = po["J"].reshape(n, n)
+            sc2 = np.diag(JtJ).copy()
+            unred = np.array(g["diag_kept_unreduced"])
+            sc2 = np.where(sc2 < 1e-30 * unred, unred, sc2)      # as tests/test_golden.py check_prior_against_ref
+            sc = np.sqrt(sc2)
+            dev = (float(np.abs((Jo.T @ Jo - JtJ) / np.outer(sc, sc)).max()), float(np.abs(Jo.T @ po["r"] - Jtr).max() / np.abs(Jtr).max()))
+            near = [x for x in g["eigenvalues_kept"] if 1e-12 < abs(x) < 1e-4][:8]
+            print("%s: %d dropped + %d kept columns; kept eigenvalues around the 1e-8 cut: %s; oracle vs 60 digits: J^T J scaled %.2e, J^T r rel %.2e" % (case, g["m"], n, ["%.1e" % x for x in near], dev[0], dev[1]), flush=True)
+            fx = {"about": "MARGIN_OLD prior of a GNSS window of tests/gnss_hard_cases.py by the reference's route at 60 digits (tests/golden/make_ref_golden.py gnss_hard); layout as ref_marg_old_gnss",
+                  "window": {k: (to_list(v) if isinstance(v, np.ndarray) else v) for k, v in dict(w).items()}, "mode": 0, "kept": [int(x) for x in g["kept"]], "m": int(g["m"]), "n": int(n),
+                  "JtJ_lower": [float(JtJ[a, c]) for a in range(n) for c in range(a + 1)], "Jtr": Jtr.tolist(), "eigenvalues_kept": g["eigenvalues_kept"],
+                  "diag_kept_unreduced": g["diag_kept_unreduced"]}     # the kept columns' diagonal BEFORE the dropped block is eliminated: the scale of a column the elimination leaves with no information
+            path = os.path.join(HERE, "ref_marg_old_gnss_" + case[5:] + ".json.gz")
+            measured[case] = {"oracle_JtJ_scaled": float("%.3g" % dev[0]), "oracle_Jtr_rel": float("%.3g" % dev[1]), "kept_eigenvalues_near_cut": [float("%.3g" % x) for x in near]}
+        else:
+            lin = O.ba_linearize(w.copy())
+            ids = [int(x) for x in lin["ids"]]
+            H, g, cost = window_normal_equations(w, ids)
+            n = len(ids)
+            Hd = np.array([[float(H[a, c]) for c in range(n)] for a in range(n)])
+            gd = np.array([float(g[a]) for a in range(n)])
+            hs = np.sqrt(np.outer(np.abs(np.diag(Hd)), np.abs(np.diag(Hd)))) + 1e-300
+            dev = (abs(lin["cost"] - float(cost)) / float(cost), float(np.abs((lin["H"] - Hd) / hs).max()), float(np.abs(lin["g"] - gd).max() / np.abs(gd).max()))
+            print("%s: %d columns, %d GNSS factors; oracle vs 60 digits: cost rel %.2e, H scaled %.2e, g rel %.2e" % (case, n, w["n_gnss"], dev[0], dev[1], dev[2]), flush=True)
+            fx = {"about": "normal equations of a GNSS window of tests/gnss_hard_cases.py from the reference's formulas at 60 digits (tests/golden/make_ref_golden.py gnss_hard); layout as ref_window_gnss",
+                  "window": {k: (to_list(v) if isinstance(v, np.ndarray) else v) for k, v in dict(w).items()},
+                  "ids": ids, "n_f": int(lin["n_f"]), "n_e": int(lin["n_e"]), "H_lower": [float(Hd[a, c]) for a in range(n) for c in range(a + 1)], "g": gd.tolist(), "cost": float(cost),
+                  "cost_30_digits": mp.nstr(cost, 30)}
+            measured[case] = {"oracle_cost_rel": float("%.3g" % dev[0]), "oracle_H_scaled": float("%.3g" % dev[1]), "oracle_g_rel": float("%.3g" % dev[2])}
+            if kind == "single":
+                fx["factor"] = gnss_own_columns(w, ids)
+                worst = 0.0
+                for c in fx["factor"]["own_columns"]:
+                    worst = max(worst, abs(lin["g"][c["column"]] - c["g"]) / c["abs_sum"])
+                measured[case]["oracle_g_own_columns_rel_abs_sum"] = float("%.3g" % worst)
+                print("   the factor's own columns of g, oracle vs 60 digits relative to the sum of absolute terms: %.2e" % worst, flush=True)
+            path = os.path.join(HERE, "ref_window_gnss_" + case + ".json.gz")
+        with gzip.GzipFile(path, "wb", mtime=0) as f:
+            f.write(json.dumps(fx).encode())
+        print("   wrote", path, os.path.getsize(path), "bytes", flush=True)
+    m = GH.committed().get("measured", {})       # figures of cases not regenerated in this call stay
+    m.setdefault("oracle_vs_60_digits", {}).update(measured)
+    GH.write(GH.census_document(O, measured=m))
+
+
+def main_gnss_models():
+    """python tests/golden/make_ref_golden.py gnss_models: tests/golden/ref_gnss_models.json.gz -- (receiver, satellite, time of week, table) tuples taken from the factors of
+    tests/gnss_hard_cases.py's windows (about a dozen per case, spread over the list) and ecef2geo / geo2rotation / sat_azel / the two delays of each at 60 digits.  The
+    azimuth and elevation are also given as the direction cosines (east, north, up) they stand for: what a comparison of angles should measure."""
+    import gzip
+    import oracle_py as O
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import gnss_hard_cases as GH
+    tuples = []
+    for case in GH.ALL:
+        w = GH.window_of(case, O)
+        ng = int(w["n_gnss"])
+        for k in range(0, ng, max(1, ng // 12)):
+            lo, ratio = int(w["gnss_lower"][k]), float(w["gnss_ratio"][k])
+            d = w["gnss_data"][16 * k:16 * k + 16]
+            P = ratio * w["para_Pose"][7 * lo:7 * lo + 3] + (1 - ratio) * w["para_Pose"][7 * lo + 7:7 * lo + 10]
+            yaw = float(w["para_yaw_enu_local"][0])
+            Rz = np.array([[np.cos(yaw), -np.sin(yaw), 0], [np.sin(yaw), np.cos(yaw), 0], [0, 0, 1.0]])
+            rcv = GH._rot(GH._ecef2geo(w["para_anc_ecef"])) @ Rz @ P + w["para_anc_ecef"]      # any doubles will do as input: these are next to where the factor stands
+            rc, sat, tow, tab = vec(rcv), vec(d[0:3]), mpf(d[14]), [mpf(x) for x in w["gnss_iono"]]
+            lla = gn_ecef2geo(rc)
+            R = gn_geo2rotation(lla)
+            az, el = gn_sat_azel(rc, sat)
+            tuples.append({"case": case, "factor": k, "rcv": [float(x) for x in rcv], "sat": [float(x) for x in d[0:3]], "tow": float(d[14]), "iono": [float(x) for x in w["gnss_iono"]],
+                           "lla": [float(x) for x in lla], "R": [float(R[a, c]) for a in range(3) for c in range(3)], "az": float(az), "el": float(el),
+                           "cosines": [float(mp.sin(az) * mp.cos(el)), float(mp.cos(az) * mp.cos(el)), float(mp.sin(el))],
+                           "trop": float(gn_trop_delay(lla, el)), "ion": float(gn_ion_delay(tow, tab, lla, az, el))})
+    path = os.path.join(HERE, "ref_gnss_models.json.gz")
+    with gzip.GzipFile(path, "wb", mtime=0) as f:
+        f.write(json.dumps({"about": "gf_gnss_models.hpp's functions at 60 digits (tests/golden/make_ref_golden.py gnss_models): inputs rcv, sat [m, ECEF], tow [s], iono; expected lla "
+                                     "[deg, deg, m], R_ecef_enu (row-major), az, el [rad], their direction cosines (east, north, up), trop, ion [m]", "tuples": tuples}).encode())
+    print("wrote", path, os.path.getsize(path), "bytes,", len(tuples), "tuples")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:2] == ["gnss_models"]:
+        main_gnss_models()
+    elif sys.argv[1:2] == ["gnss_hard"]:
+        main_gnss_hard(sys.argv[2:])
+    else:
+        main()

@@ -185,7 +185,12 @@ def check_prior_against_ref(p, fx, A, b, ids, tol_a=2e-6, tol_b=2e-8):
     n = fx["n"]
     assert p["n"] == n and p["m"] == fx["m"] and [int(x) for x in p["block_id"]] == ids
     J = p["J"].reshape(n, n)
-    sc = np.sqrt(np.maximum(np.diag(A), 1e-300))
+    sc2 = np.maximum(np.diag(A), 1e-300)
+    if "diag_kept_unreduced" in fx:        # a kept column the elimination leaves with NO information (frame 0 without observations: the frame-1 clocks hang on the dropped frame-0
+        unred = np.array(fx["diag_kept_unreduced"])   # clocks alone): its exact diagonal is 0, what double precision leaves there is rounding of the diagonal it had before
+        sc2 = np.where(sc2 < 1e-30 * unred, unred, sc2)     # 1e-30: an exact zero at 60 digits (measured 1e-103 .. 1e-106 of `unred`), ten orders below anything double precision
+                                                                # can leave of a diagonal (1e-16 of it); a column with any information at all keeps its own diagonal as the scale
+    sc = np.sqrt(sc2)
     dev_a = float(np.abs((J.T @ J - A) / np.outer(sc, sc)).max())
     dev_b = float(np.abs(J.T @ p["r"] - b).max() / np.abs(b).max())
     assert dev_a < tol_a and dev_b < tol_b, (dev_a, dev_b)

@@ -16,7 +16,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCENARIOS = ["plain", "plain_after", "gnss", "gnss_after", "slots", "slots_fresh", "group", "group_gnss"]
+SCENARIOS = ["plain", "plain_after", "gnss", "gnss_after", "gnss_thinned", "gnss_thinned_after", "slots", "slots_fresh", "group", "group_gnss"]
 
 
 def _probe(**env):
@@ -39,6 +39,7 @@ def zeroed():
 def test_a_window_behind_other_windows_in_the_same_handle_gives_the_same_bits(zeroed):
     assert zeroed["plain_after"] == zeroed["plain"]
     assert zeroed["gnss_after"] == zeroed["gnss"]
+    assert zeroed["gnss_thinned_after"] == zeroed["gnss_thinned"]      # a shorter GNSS list behind a longer one in the same slot
     assert zeroed["slots"] == zeroed["slots_fresh"]
 
 
