@@ -1958,6 +1958,16 @@ int gf_estimator_set_roi(gf_estimator* e, const uint8_t* mask, int stride) {
     if (!e || !e->tracker) return gf::set_err(GF_ERR_INVALID, "estimator was created without a tracker (cfg.with_tracker)");
     return gf_tracker_set_roi(e->tracker, 0, mask, stride);
 }
+// SHOW_TRACK and getTrackImage (feature_tracker.cpp:849-905, :1047) of the estimator's own tracker, on its one sequence
+int gf_estimator_set_show_track(gf_estimator* e, int on) {
+    if (!e || !e->tracker) return gf::set_err(GF_ERR_INVALID, "estimator was created without a tracker (cfg.with_tracker)");
+    const int seq = 0;
+    return gf_tracker_set_show_track(e->tracker, 1, &seq, on);
+}
+int gf_estimator_get_track_image(gf_estimator* e, uint8_t* dst, int stride) {
+    if (!e || !e->tracker) return gf::set_err(GF_ERR_INVALID, "estimator was created without a tracker (cfg.with_tracker)");
+    return gf_tracker_track_image(e->tracker, 0, dst, stride);
+}
 
 int gf_estimator_get_state(gf_estimator* e, double* Ps, double* Rs, double* Vs, double* Bas, double* Bgs, double* Headers, int* info, double* extr) {
     if (!e) return gf::set_err(GF_ERR_INVALID, "null handle");

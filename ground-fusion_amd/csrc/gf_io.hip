@@ -145,6 +145,16 @@ bool take_transform(const YamlDoc& doc, const char* key, double* R, double* t, s
 
 extern "C" {
 
+// SHOW_TRACK (parameters.cpp:202), with the reader of gf_estimator_cfg_from_yaml: a missing key reads as 0 like every cv::FileNode
+int gf_show_track_from_yaml(const char* config_file, int* show_track) {
+    if (!config_file || !show_track) return gf::set_err(GF_ERR_INVALID, "null argument");
+    YamlDoc y;
+    std::string err;
+    if (!parse_yaml(config_file, y, err)) return gf::set_err(GF_ERR_INVALID, "%s: %s", config_file, err.c_str());
+    *show_track = y.integer("show_track");
+    return GF_OK;
+}
+
 int gf_estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* c) {
     if (!config_file || !c) return gf::set_err(GF_ERR_INVALID, "null argument");
     YamlDoc y;

@@ -11,11 +11,13 @@
 #include <cstdio>
 #include <map>
 #include <set>
+#include <string>
 #include <utility>
 #include <vector>
 
 #include "gf_roi.hpp"
 #include "gf_seq_cfg.hpp"
+#include "gf_track_draw.hpp"
 
 namespace gf {
 
@@ -34,6 +36,14 @@ struct SeqState {  // per-sequence FeatureTracker members (feature_tracker.h:76-
     bool hasPrediction = false;
     bool started = false;   // the sequence has taken a frame since gf_tracker_create / gf_tracker_reset_seq: its parameters are fixed (gf_tracker_set_seq_cfg)
     int slot = 1;   // which of the sequence's two pyramids holds its newest frame; flipped when the sequence takes a frame, and only then (the first frame goes to 0)
+    // SHOW_TRACK (gf_tracker_set_show_track; drawTrack, feature_tracker.cpp:304-305, :849-905).  Nothing below is touched while the switch is off.
+    // draw_from: prevLeftPtsMap for the features LK carried into the frame being taken -- id -> the point it was tracked from, id-sorted; written by after_lk ahead
+    // of setMask, which reorders the features but not prev_pts.  draw_list: the primitives of the newest frame (record_track), valid while draw_have; the picture
+    // of the moment trackImage returned, which setPrediction / removeOutliers do not change.  draw_sent: the list is on the device as it is here.
+    bool show_track = false, draw_have = false, draw_sent = false;
+    std::vector<std::pair<int, P2f>> draw_from;
+    std::vector<gfdraw::Prim> draw_list;
+    std::string draw_why;   // why the builder refused the newest frame's list (then draw_have is false); empty otherwise
 };
 
 static inline int cvRoundf(float v) { return (int)lrintf(v); }
@@ -210,6 +220,11 @@ inline LkTally after_lk(SeqState& s, const gf_tracker_seq_cfg& par, int width, i
         reduce_vector(s.cur_depth, st);
         tally.tracked = (long long)s.cur_pts.size();
     }
+    if (s.show_track) {   // the arrows' far ends, while prev_pts and ids still go by the same index
+        s.draw_from.clear();
+        if (n > 0) for (size_t i = 0; i < s.ids.size(); i++) s.draw_from.push_back({s.ids[i], s.prev_pts[i]});
+        std::sort(s.draw_from.begin(), s.draw_from.end(), [](const std::pair<int, P2f>& a, const std::pair<int, P2f>& b) { return a.first < b.first; });
+    }
     for (auto& c : s.track_cnt) c++;
     int nc = 0;   // counted here and stored once: the tables are page-locked memory that neighbouring sequences' threads write too
     set_mask_host(width, height, s, T, roi, centers_row, nc);
@@ -252,6 +267,29 @@ inline Packed after_detect(SeqState& s, const gf_tracker_seq_cfg& par, const Det
         o->v[7] = par.depth_cam ? (double)(int)s.cur_depth[i] / 1000 : -2.4;
     }
     return {n, -1};
+}
+
+// After after_detect, for a sequence whose show_track is on (drawTrack, feature_tracker.cpp:849-905): the frame's primitive list from what the frame left -- a dot
+// per feature at its current point, coloured by track_cnt, and an arrow for every feature whose id was in the previous frame, back to the point LK tracked it from
+// (draw_from; a newly detected corner has none).  False if the builder refuses a point; the sequence then has no picture and keeps the reason in draw_why.
+inline bool record_track(SeqState& s) {
+    const size_t n = s.ids.size();
+    static thread_local std::vector<float> cur, prev;
+    static thread_local std::vector<uint8_t> has;
+    cur.resize(2 * n); prev.assign(2 * n, 0.f); has.assign(n, 0);
+    for (size_t i = 0; i < n; i++) {
+        cur[2 * i] = s.prev_pts[i].x; cur[2 * i + 1] = s.prev_pts[i].y;   // after the roll-over prev_pts holds the frame's points
+        auto it = std::lower_bound(s.draw_from.begin(), s.draw_from.end(), s.ids[i], [](const std::pair<int, P2f>& a, int v) { return a.first < v; });
+        if (it != s.draw_from.end() && it->first == s.ids[i]) { has[i] = 1; prev[2 * i] = it->second.x; prev[2 * i + 1] = it->second.y; }
+    }
+    s.draw_list.resize(gfdraw::list_capacity(n));
+    char msg[160] = "";
+    const int m = gfdraw::build_list((int)n, cur.data(), s.track_cnt.data(), prev.data(), has.data(), s.draw_list.data(), msg, sizeof msg);
+    s.draw_sent = false;
+    s.draw_have = m >= 0;
+    s.draw_list.resize(m >= 0 ? (size_t)m : 0);
+    s.draw_why = m >= 0 ? "" : msg;
+    return s.draw_have;
 }
 
 }  // namespace gf

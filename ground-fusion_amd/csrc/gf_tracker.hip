@@ -41,6 +41,7 @@
 #include "gf_pixfmt.hpp"
 #include "gf_roi.hpp"
 #include "gf_seq_cfg.hpp"
+#include "gf_track_draw.hpp"
 #include "gf_track_host.hpp"
 
 namespace gf {
@@ -53,6 +54,8 @@ int cvt_launch(const uint8_t* d_src, size_t src_pitch, int format, uint8_t* d_ds
 // the table forms of the two (gf_frame_ref.hpp): frame b of the source lies at refs[b]
 int clahe_launch_refs(const gf_frame_ref* d_refs, uint8_t* d_dst, uint8_t* d_lut, int batch, int w, int h, double clip_limit, int tiles_x, int tiles_y, hipStream_t stream);
 int cvt_launch_refs(const gf_frame_ref* d_refs, const gf_frame_ref* h_refs, int format, uint8_t* d_dst, int batch, int w, int h, hipStream_t stream, int* n_bytes);
+// gf_track_draw.hip: the track image of `count` frames, one per entry of d_jobs (gf_track_draw.hpp), in one launch
+int draw_track_launch(const gfdraw::DrawJob* d_jobs, int count, int w, int h, hipStream_t stream);
 constexpr double kClaheClip = 40.0;   // cv::createCLAHE() defaults (rosNodeTest.cpp:258)
 constexpr int kClaheTiles = 8;
 
@@ -198,6 +201,12 @@ struct gf_tracker {
     // Obtained by the first _refs call of the handle, like the tables above.  It travels like the list: the first kernel of a call reads the page-locked h_refs
     // over the bus, the copy list in front of LK / the detection carries it to d_refs for the depth samples of those kernels.
     DevBuf<gf_frame_ref> d_refs; PinBuf<gf_frame_ref> h_refs;
+    // The track image (gf_track_draw.hpp; gf_tracker_set_show_track), obtained by the first call that turns a sequence's switch on.  d_draw_prims: [B][4 cap]
+    // primitives by SEQUENCE, a sequence's row written when its picture is first asked for after a frame (SeqState::draw_sent) through its row of the page-locked
+    // h_draw_prims.  The jobs of a call by list position.  d_draw_host: the staging image of gf_tracker_track_image, obtained by its first call.
+    DevBuf<gfdraw::Prim> d_draw_prims; PinBuf<gfdraw::Prim> h_draw_prims;
+    DevBuf<gfdraw::DrawJob> d_draw_jobs; PinBuf<gfdraw::DrawJob> h_draw_jobs;
+    DevBuf<uint8_t> d_draw_host;
 
     std::unique_ptr<HostPool> pool;
 };
@@ -714,6 +723,7 @@ static int book_after_detect(Call& c, gf_feature_obs* out, int cap_out, int* n_o
         const int q = c.seq[b];
         const DetectRows r{row(h->h_out_pts, b, cap), c.in.kernel_samples(h->h_out_depth, b, cap), h->h_want.p[b] > 0 ? h->h_out_n.p[b] : 0, c.in.host_image(b, h->par[q]), c.in.host_dstride};
         const Packed p = after_detect(h->seq[q], h->par[q], r, have_depth, out + (size_t)b * cap_out, cap_out);
+        if (h->seq[q].show_track) (void)record_track(h->seq[q]);   // a refused list: the sequence has no picture of this frame, and keeps the reason (draw_why)
         if (p.overflow >= 0) a_overflow = p.overflow;
         n_out[b] = p.written;
         a_out += p.written;
@@ -1101,7 +1111,89 @@ int gf_tracker_reset_seq(gf_tracker* h, int seq) {
     if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
     if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
     if (gf::seq_is_staged(h, seq)) return gf::set_err(GF_ERR_INVALID, "sequence %d is listed by a staged frame: gf_tracker_track_prefetched has to consume it first", seq);
+    const bool show = h->seq[seq].show_track;   // a setting, like the region of interest: it stays; the recorded picture goes
     h->seq[seq] = gf::SeqState{};   // no tracks, no previous frame: LK has nothing to read in the sequence's pyramids, whatever they hold
+    h->seq[seq].show_track = show;
+    return GF_OK;
+}
+
+// ---- the track image (gf_track_draw.hpp; drawTrack / getTrackImage, feature_tracker.cpp:849-905, :1047)
+int gf_tracker_set_show_track(gf_tracker* h, int count, const int* seq, int on) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (int rc = gf::check_list(h, count, seq)) return rc;
+    if (on && count > 0 && !h->d_draw_prims.p) {   // the first switch of the handle that goes on
+        const size_t row = gfdraw::list_capacity(h->cap);
+        gf::DevBuf<gfdraw::Prim> dp; gf::PinBuf<gfdraw::Prim> hp; gf::DevBuf<gfdraw::DrawJob> dj; gf::PinBuf<gfdraw::DrawJob> hj;
+        HIPCHK(dp.alloc((size_t)h->B * row)); HIPCHK(hp.alloc((size_t)h->B * row)); HIPCHK(dj.alloc(h->B)); HIPCHK(hj.alloc(h->B));
+        h->d_draw_prims = std::move(dp); h->h_draw_prims = std::move(hp); h->d_draw_jobs = std::move(dj); h->h_draw_jobs = std::move(hj);
+    }
+    for (int i = 0; i < count; i++) {
+        gf::SeqState& s = h->seq[seq[i]];
+        s.show_track = on != 0;
+        if (!on) { s.draw_have = s.draw_sent = false; s.draw_list.clear(); s.draw_from.clear(); s.draw_why.clear(); }
+    }
+    return GF_OK;
+}
+
+namespace gf {
+// everything a picture call refuses, before anything is copied or launched.  dst[i].data is only asked whether it is null.
+static int draw_check(gf_tracker* h, int count, const int* seq, const gf_frame_ref* dst) {
+    if (int rc = check_list(h, count, seq)) return rc;
+    if (count > 0 && !dst) return set_err(GF_ERR_INVALID, "null table of destinations");
+    const size_t row_bytes = 3 * (size_t)h->cfg.width, room = gfdraw::list_capacity(h->cap);
+    for (int i = 0; i < count; i++) {
+        const SeqState& s = h->seq[seq[i]];
+        if (!s.show_track) return set_err(GF_ERR_INVALID, "list position %d (sequence %d): show_track is off (gf_tracker_set_show_track)", i, seq[i]);
+        if (!s.draw_have && !s.draw_why.empty()) return set_err(GF_ERR_INVALID, "list position %d (sequence %d): the list of its last frame was refused: %s", i, seq[i], s.draw_why.c_str());
+        if (!s.draw_have) return set_err(GF_ERR_INVALID, "list position %d (sequence %d): no frame recorded since the switch went on, the handle was created or the sequence reset", i, seq[i]);
+        if (s.draw_list.size() > room) return set_err(GF_ERR_CAPACITY, "list position %d (sequence %d): %zu primitives > capacity %zu", i, seq[i], s.draw_list.size(), room);
+        const gfref::Verdict v = gfref::check(dst[i], row_bytes, false, false);
+        if (v != gfref::kOk)
+            return set_err(GF_ERR_INVALID, "destination at list position %d (sequence %d): %s (data %p, pitch %zu bytes, a row is %zu bytes)", i, seq[i], gfref::verdict_text(v), dst[i].data, dst[i].pitch, row_bytes);
+    }
+    return GF_OK;
+}
+// the checked call: lists that are new since the sequence's last picture go down, then the jobs, one launch, and the host waits
+static int draw_run(gf_tracker* h, int count, const int* seq, const gf_frame_ref* dst) {
+    const size_t room = gfdraw::list_capacity(h->cap);
+    const LevelGeom g0 = h->G.lv[0];
+    for (int i = 0; i < count; i++) {
+        const int q = seq[i];
+        SeqState& s = h->seq[q];
+        if (!s.draw_sent && !s.draw_list.empty()) {
+            memcpy(h->h_draw_prims.p + (size_t)q * room, s.draw_list.data(), s.draw_list.size() * sizeof(gfdraw::Prim));
+            HIPCHK(hipMemcpyAsync(h->d_draw_prims.p + (size_t)q * room, h->h_draw_prims.p + (size_t)q * room, s.draw_list.size() * sizeof(gfdraw::Prim), hipMemcpyHostToDevice, h->stream));
+        }
+        // the background: level 0 of the sequence's newest pyramid, the MONO8 image trackImage tracked on (converted, equalised)
+        h->h_draw_jobs.p[i] = gfdraw::DrawJob{h->d_img.p + (size_t)(2 * q + s.slot) * h->G.img_bytes + g0.img_off, (size_t)g0.stride,
+                                              static_cast<uint8_t*>(const_cast<void*>(dst[i].data)), dst[i].pitch, h->d_draw_prims.p + (size_t)q * room, (int)s.draw_list.size(), 0};
+    }
+    HIPCHK(hipMemcpyAsync(h->d_draw_jobs.p, h->h_draw_jobs.p, (size_t)count * sizeof(gfdraw::DrawJob), hipMemcpyHostToDevice, h->stream));
+    if (int rc = draw_track_launch(h->d_draw_jobs.p, count, h->cfg.width, h->cfg.height, h->stream)) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));   // the images are complete, and the page-locked tables free for the next call
+    for (int i = 0; i < count; i++) h->seq[seq[i]].draw_sent = true;   // only now: a call that failed on the way sends its lists again
+    return GF_OK;
+}
+}  // namespace gf
+
+int gf_tracker_track_image_some_device(gf_tracker* h, int count, const int* seq, const gf_frame_ref* dst) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (int rc = gf::draw_check(h, count, seq, dst)) return rc;
+    if (count == 0) return GF_OK;
+    return gf::draw_run(h, count, seq, dst);
+}
+
+int gf_tracker_track_image(gf_tracker* h, int seq, uint8_t* dst, int stride) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (!dst) return gf::set_err(GF_ERR_INVALID, "null destination");
+    const size_t row = 3 * (size_t)h->cfg.width;
+    if (stride < 0 || (size_t)stride < row) return gf::set_err(GF_ERR_INVALID, "a stride of %d bytes is shorter than a row of %d pixels of 3 bytes", stride, h->cfg.width);
+    gf_frame_ref ref{dst, row};   // checked as the caller's; rendered into the handle's staging image
+    if (int rc = gf::draw_check(h, 1, &seq, &ref)) return rc;
+    HIPCHK(h->d_draw_host.fit(row * h->cfg.height));
+    ref.data = h->d_draw_host.p;
+    if (int rc = gf::draw_run(h, 1, &seq, &ref)) return rc;
+    HIPCHK(hipMemcpy2D(dst, (size_t)stride, h->d_draw_host.p, row, row, h->cfg.height, hipMemcpyDeviceToHost));
     return GF_OK;
 }
 

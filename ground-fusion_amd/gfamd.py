@@ -94,7 +94,9 @@ EXPORTS = ["gf_last_error", "gf_device_count", "gf_set_device", "gf_tracker_crea
            "gf_tracker_set_roi", "gf_tracker_set_roi_some_device", "gf_tracker_get_roi",
            "gf_tracker_set_seq_cfg", "gf_tracker_get_seq_cfg", "gf_tracker_reset_seq",
            "gf_tracker_get_state", "gf_tracker_set_profiling", "gf_tracker_get_stats", "gf_tracker_reset_stats", "gf_lk_track",
-           "gf_good_features", "gf_min_eigen_val", "gf_pyramid_level", "gf_clahe_batch", "gf_clahe_batch_device", "gf_cvt_gray_batch", "gf_cvt_gray_batch_device"]
+           "gf_good_features", "gf_min_eigen_val", "gf_pyramid_level", "gf_clahe_batch", "gf_clahe_batch_device", "gf_cvt_gray_batch", "gf_cvt_gray_batch_device",
+           "gf_tracker_set_show_track", "gf_tracker_track_image_some_device", "gf_tracker_track_image", "gf_draw_track_batch",
+           "gf_estimator_set_show_track", "gf_estimator_get_track_image", "gf_show_track_from_yaml"]
 
 
 def lib():
@@ -393,6 +395,25 @@ class FeatureTracker:
         """gf_tracker_reset_seq: sequence `seq` as after create (no tracks, ids from 0, no previous frame); its parameters and region of interest stay"""
         _chk(lib().gf_tracker_reset_seq(self.h, seq))
 
+    def set_show_track(self, on=True, seqs=None):
+        """gf_tracker_set_show_track: SHOW_TRACK of the listed sequences (default: all).  On: every frame a sequence takes leaves the picture track_image returns"""
+        seqs, N = self._seqs(range(self.cfg.batch) if seqs is None else seqs)
+        _chk(lib().gf_tracker_set_show_track(self.h, N, _p(seqs, C.c_int), int(bool(on))))
+
+    def track_image(self, seq=0):
+        """gf_tracker_track_image: getTrackImage() of sequence `seq` as a [height, width, 3] u8 array in the reference's channel order (bgr8) -- the frame it
+        last took with a dot per feature and an arrow back to where LK tracked it from"""
+        out = np.empty((self.cfg.height, self.cfg.width, 3), np.uint8)
+        _chk(lib().gf_tracker_track_image(self.h, seq, _p(out, C.c_uint8), 3 * self.cfg.width))
+        return out
+
+    def track_image_device(self, seqs, dst_refs):
+        """gf_tracker_track_image_some_device: the pictures of the listed sequences into device memory, dst_refs[i] = (device address of row 0, bytes from row to
+        row >= 3 * width, any alignment) of the image of seqs[i]; WRITTEN in place, complete when the call returns"""
+        seqs, N = self._seqs(seqs)
+        assert dst_refs is None or len(dst_refs) == N
+        _chk(lib().gf_tracker_track_image_some_device(self.h, N, _p(seqs, C.c_int), None if dst_refs is None else frame_refs(dst_refs)))
+
     def state(self, seq=0):
         ids = np.zeros(self.cap, np.int32)
         cnt = np.zeros(self.cap, np.int32)
@@ -411,6 +432,45 @@ class FeatureTracker:
 
     def reset_stats(self):
         _chk(lib().gf_tracker_reset_stats(self.h))
+
+
+def draw_track(gray, lists, dst=None):
+    """gf_draw_track_batch: drawTrack (feature_tracker.cpp:849-905) on host frames with the tracker's kernel.  gray: [h, w] or [batch, h, w] u8 (rows may be
+    padded: a view of a wider array whose frames lie h rows apart).  lists: per frame (cur [n, 2], track_cnt [n], prev [n, 2] or None, has_prev [n] or None).
+    dst: None -> returns new [batch, h, w, 3] pictures ([h, w, 3] for one frame without a batch axis); or a u8 [batch, h, >= 3 w] array whose rows lie one
+    pitch >= 3 w apart and whose frames lie h rows apart, starting at any address (a view into a larger buffer, a crop of a wider image), which is written in
+    place -- 3 w bytes per row -- and returned.  Neither array is touched behind the last pixel of its last row."""
+    a = np.asarray(gray)
+    single = a.ndim == 2
+    if single:
+        a, lists = a[None], [lists]
+    if a.dtype != np.uint8 or a.ndim != 3:
+        raise ValueError("draw_track: gray must be u8 [h, w] or [batch, h, w]")
+    b, h, w = a.shape
+    if a.strides[2] != 1 or a.strides[0] != h * a.strides[1] or a.strides[1] < w:
+        a = np.ascontiguousarray(a)
+    assert len(lists) == b
+    cap = max([len(l[1]) for l in lists] + [1])
+    n = np.array([len(l[1]) for l in lists], np.int32)
+    cur, prev = np.zeros((b, cap, 2), np.float32), np.zeros((b, cap, 2), np.float32)
+    cnt, has = np.zeros((b, cap), np.int32), np.zeros((b, cap), np.uint8)
+    for k, l in enumerate(lists):
+        if n[k]:
+            cur[k, :n[k]] = np.asarray(l[0], np.float32).reshape(-1, 2)
+            cnt[k, :n[k]] = l[1]
+            if len(l) > 3 and l[2] is not None and l[3] is not None:
+                prev[k, :n[k]] = np.asarray(l[2], np.float32).reshape(-1, 2)
+                has[k, :n[k]] = np.asarray(l[3]).astype(bool)
+    out = np.zeros((b, h, 3 * w), np.uint8) if dst is None else dst
+    pitch = out.strides[1] if out.ndim == 3 else 0
+    if out.dtype != np.uint8 or out.ndim != 3 or out.shape[:2] != (b, h) or out.shape[2] < 3 * w or out.strides[2] != 1 or pitch < 3 * w or (b > 1 and out.strides[0] != h * pitch):
+        raise ValueError("draw_track: dst must be u8 [batch, h, >= 3 w] with rows of one pitch >= 3 w and frames h rows apart")
+    _chk(lib().gf_draw_track_batch(C.c_void_p(a.ctypes.data), C.c_size_t(a.strides[1]), b, w, h, _p(n, C.c_int), _p(cur, C.c_float), _p(cnt, C.c_int),
+                                   _p(prev, C.c_float), _p(has, C.c_uint8), cap, C.c_void_p(out.ctypes.data), C.c_size_t(pitch)))
+    if dst is not None:
+        return dst
+    out = out.reshape(b, h, w, 3)
+    return out[0] if single else out
 
 
 def clahe(frames, clip_limit=40.0, tiles=(8, 8)):
@@ -963,6 +1023,17 @@ class SlidingWindowEstimator:
         mask = np.ascontiguousarray(mask, np.uint8)
         _chk(lib().gf_estimator_set_roi(self.h, _p(mask, C.c_uint8), mask.shape[1]))
 
+    def set_show_track(self, on=True):
+        """gf_estimator_set_show_track: SHOW_TRACK of the estimator's own tracker"""
+        _chk(lib().gf_estimator_set_show_track(self.h, int(bool(on))))
+
+    def track_image(self):
+        """gf_estimator_get_track_image: getTrackImage() of the last inputImage, [height, width, 3] u8"""
+        t = self.cfg.tracker
+        out = np.empty((t.height, t.width, 3), np.uint8)
+        _chk(lib().gf_estimator_get_track_image(self.h, _p(out, C.c_uint8), 3 * t.width))
+        return out
+
     def inputImage(self, t, img, depth=None):
         img = np.ascontiguousarray(img, np.uint8)
         cap = self.cfg.tracker.max_cnt + 8
@@ -1042,6 +1113,13 @@ def estimator_cfg_from_yaml(config_file):
     c = EstimatorCfg()
     _chk(lib().gf_estimator_cfg_from_yaml(os.fsencode(config_file), C.byref(c)))
     return c
+
+
+def show_track_from_yaml(config_file):
+    """gf_show_track_from_yaml: `show_track` (SHOW_TRACK, parameters.cpp:202) of a config file, 0 when the key is missing"""
+    v = C.c_int(0)
+    _chk(lib().gf_show_track_from_yaml(os.fsencode(config_file), C.byref(v)))
+    return v.value
 
 
 def tum_append(path, t, P, R):

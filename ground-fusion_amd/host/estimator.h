@@ -144,6 +144,24 @@ class Estimator {
     // the region of interest of the estimator's own tracker (FeatureTracker::setRegionOfInterest, gf_estimator_set_roi): rows x cols bytes of cfg.tracker's frame
     // size, non-zero = allowed, nullptr clears; from the next inputImage on
     void setRegionOfInterest(const uint8_t* mask, int stride) { need(); check(gf_estimator_set_roi(h_, mask, stride)); }
+    // SHOW_TRACK and getTrackImage of the estimator's own tracker (FeatureTracker::setShowTrack / getTrackImage; gf_estimator_set_show_track,
+    // gf_estimator_get_track_image): the picture of the last inputImage, rows x cols x 3 bytes (bgr8)
+    void setShowTrack(bool on) { need(); check(gf_estimator_set_show_track(h_, on ? 1 : 0)); }
+    void getTrackImage(std::vector<uint8_t>& store, ImageView<uint8_t>& view) {
+        need();
+        const int W = cfg.tracker.width, H = cfg.tracker.height;
+        store.resize((size_t)W * H * 3);
+        check(gf_estimator_get_track_image(h_, store.data(), 3 * W));
+        view.data = store.data(); view.rows = H; view.cols = W; view.stride = 3 * W; view.pixel_format = GF_PIX_BGR8;
+    }
+#ifdef GF_WITH_OPENCV
+    cv::Mat getTrackImage() {
+        need();
+        cv::Mat m(cfg.tracker.height, cfg.tracker.width, CV_8UC3);
+        check(gf_estimator_get_track_image(h_, m.ptr<uint8_t>(), (int)m.step));
+        return m;
+    }
+#endif
 #ifdef GF_WITH_OPENCV
     void setRegionOfInterest(const cv::Mat& mask) {
         if (mask.empty()) { setRegionOfInterest(nullptr, 0); return; }

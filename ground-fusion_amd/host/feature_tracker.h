@@ -117,6 +117,31 @@ class FeatureTracker {
     }
 #endif
 
+    // SHOW_TRACK (parameters.cpp:202; feature_tracker.cpp:304-305): on, every trackImage leaves the picture getTrackImage returns (gf_tracker_set_show_track).
+    // Any time; the first frame after it went on already gives a complete picture.
+    void setShowTrack(bool on) {
+        show_track_ = on;
+        const int seq = 0;
+        if (h_) check(gf_tracker_set_show_track(h_, 1, &seq, on ? 1 : 0));
+    }
+    // getTrackImage (feature_tracker.cpp:1047; drawTrack :849-905): the frame of the last trackImage with a dot per feature, coloured from blue to red by track
+    // length, and a green arrow back to where the feature was one frame earlier -- rows x cols x 3 bytes in the reference's channel order (bgr8), rendered on
+    // the device (gf_tracker_track_image).  Without OpenCV: into `store`, with `view` describing it (stride 3 x cols bytes, GF_PIX_BGR8).
+    void getTrackImage(std::vector<uint8_t>& store, ImageView<uint8_t>& view) {
+        if (!h_) throw std::runtime_error("getTrackImage: no frame yet");
+        store.resize((size_t)row * col * 3);
+        check(gf_tracker_track_image(h_, 0, store.data(), 3 * col));
+        view.data = store.data(); view.rows = row; view.cols = col; view.stride = 3 * col; view.pixel_format = GF_PIX_BGR8;
+    }
+#ifdef GF_WITH_OPENCV
+    cv::Mat getTrackImage() {
+        if (!h_) throw std::runtime_error("getTrackImage: no frame yet");
+        cv::Mat m(row, col, CV_8UC3);
+        check(gf_tracker_track_image(h_, 0, m.ptr<uint8_t>(), (int)m.step));
+        return m;
+    }
+#endif
+
     FeatureFrame trackImage(double _cur_time, const GrayImage& _img, const DepthImage& _img1 = DepthImage()) {
         if (!h_) { pixel_format_ = _img.pixel_format; create(_img.cols, _img.rows); }
         // one handle has one format (a camera does not change its encoding): the first frame decides, as it decides the size
@@ -183,7 +208,7 @@ class FeatureTracker {
   private:
     gf_tracker* h_ = nullptr;
     double fx_ = 1, fy_ = 1, cx_ = 0, cy_ = 0, k1_ = 0, k2_ = 0, p1_ = 0, p2_ = 0;
-    bool equalize_ = false;
+    bool equalize_ = false, show_track_ = false;
     int pixel_format_ = GF_PIX_MONO8;
     std::vector<uint8_t> roi_;   // a region of interest set before the handle exists (tight rows)
     static void check(int rc) { if (rc != GF_OK) throw std::runtime_error(std::string("groundfusion_hip: ") + gf_last_error()); }
@@ -196,6 +221,7 @@ class FeatureTracker {
         row = c.height; col = c.width;
         check(gf_tracker_create(&c, &h_));
         if (!roi_.empty()) { check(gf_tracker_set_roi(h_, 0, roi_.data(), col)); roi_.clear(); }
+        if (show_track_) setShowTrack(true);
     }
     void refresh() {
         const int cap = (MAX_CNT + 3) & ~3;

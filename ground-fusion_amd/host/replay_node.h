@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <deque>
 #include <fstream>
+#include <functional>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -46,6 +47,9 @@ template <class Est> class ReplayNode {
     // the tracker converts them to MONO8 on the device, where getImageFromMsg's cv_bridge::toCvCopy(msg, MONO8) (rosNodeTest.cpp:238-254) runs on the host.  The
     // estimator's tracker must have been created for the topic's encoding (bag_image_format below tells it).  Same pixels, so the same trajectory.
     bool device_gray = false;
+    // called after every inputImage with the frame's index (0, 1, ..) and its time: where pubTrackImage sits in the node (rosNodeTest.cpp sync_process ->
+    // estimator.inputImage -> visualization.cpp:155-162).  gf_replay --track-images writes the estimator's getTrackImage from it.
+    std::function<void(long, double)> after_image;
 
     explicit ReplayNode(Est& e) : estimator(e) {}
 
@@ -99,6 +103,7 @@ template <class Est> class ReplayNode {
             GrayImage g; g.data = gray_.data(); g.rows = gh_; g.cols = gw_; g.stride = gstep_; g.pixel_format = gfmt_;
             DepthImage d; d.data = (const uint16_t*)depth_.data(); d.rows = dh_; d.cols = dw_; d.stride = dw_;
             estimator.inputImage(time, g, d);
+            if (after_image) after_image(n_pairs, time);
             n_pairs++;
         }
     }

@@ -235,6 +235,38 @@ int gf_tracker_get_seq_cfg(gf_tracker* h, int seq, gf_tracker_seq_cfg* out);
  * unit takes over.  Keeps the sequence's parameters and its region of interest (they are settings), allows gf_tracker_set_seq_cfg again, touches no other
  * sequence. */
 int gf_tracker_reset_seq(gf_tracker* h, int seq);
+/* The track image: SHOW_TRACK and FeatureTracker::getTrackImage() (feature_tracker.cpp:849-905 drawTrack, :1047; what the node publishes as image_track) -- the
+ * MONO8 frame trackImage tracked on (after the handle's colour / raw conversion and equalisation) as height x width x 3 bytes in the reference's channel order
+ * (labelled bgr8 there), a dot per feature coloured (255 (1 - len), 0, 255 len) by len = min(1, track_cnt / 20), and a green arrow from each feature that LK
+ * carried into the frame back to the point it was tracked from; a newly detected corner has none.  Geometry, colours, order (all dots in list order, then all
+ * arrows) and rounding are the reference's; the outlines of OpenCV's thick circles and lines are replaced by exact integer distance tests, so boundary pixels of
+ * a dot or stroke can differ from an OpenCV build and nothing else can ("Track image"; csrc/gf_track_draw.hpp).
+ * gf_tracker_set_show_track: SHOW_TRACK of the `count` listed sequences (feature_tracker.cpp:304-305).  Off by default; a handle that never turns it on
+ * allocates, copies, records and launches exactly what it did without these calls.  On: each frame the sequence takes leaves its list of primitives in host
+ * memory, and the frame after the switch went on is already complete (the arrows need nothing from earlier frames).  The switch is a setting like the region
+ * of interest: gf_tracker_reset_seq keeps it and drops the recorded picture; turning it off drops the picture too.  Refused as the lists of the track calls. */
+int gf_tracker_set_show_track(gf_tracker* h, int count, const int* seq, int on);
+/* getTrackImage (feature_tracker.cpp:1047; drawTrack :849-905) of each listed sequence into device memory.  `dst` IS WRITTEN, unlike every other gf_frame_ref
+ * of this interface: dst[i] = the device pointer of the first byte of row 0 and the bytes from row to row (>= 3 x width, any alignment of both) of the image of
+ * seq[i], e.g. an encoder's or a publisher's buffer, filled in place; exactly 3 x width bytes of each of the height rows are written.  The picture is that of
+ * the moment the sequence's last track call returned, as in the reference: gf_tracker_set_prediction / gf_tracker_remove_outliers do not change it, and a
+ * sequence that sat out the last calls gives its own last frame.  The background is read from the handle's own pyramid, never from the caller's frame.  One
+ * launch for the list, ordered on the handle's stream; returns when the images are complete.  Refused with GF_ERR_INVALID, the message naming the list position,
+ * and nothing written: a null handle or table, count < 0 or > batch, a sequence out of range or named twice, a sequence whose switch is off or that has no
+ * frame recorded since the switch went on / gf_tracker_create / gf_tracker_reset_seq, a null data pointer, a pitch shorter than 3 x width. */
+int gf_tracker_track_image_some_device(gf_tracker* h, int count, const int* seq, const gf_frame_ref* dst);
+/* getTrackImage (feature_tracker.cpp:1047; drawTrack :849-905) of one sequence into host memory, rows `stride` bytes apart (>= 3 x width): the call above
+ * through a staging image of the handle, obtained by the first call.  Refused as above. */
+int gf_tracker_track_image(gf_tracker* h, int seq, uint8_t* dst, int stride);
+/* drawTrack (feature_tracker.cpp:849-905) as a building block on host buffers (copies in, renders with the tracker's kernel, copies out; synchronous): `batch`
+ * MONO8 frames of height rows, gray_pitch bytes apart (frame b at gray + b x height x gray_pitch), and for frame b n[b] <= cap features in row b of the
+ * [batch][cap] tables cur_xy (x, y pairs), track_cnt, prev_xy and has_prev (feature i has an arrow back to prev_xy[i]; both may be NULL: no arrows) -> frame b at
+ * dst + b x height x dst_pitch, dst_pitch >= 3 x width.  Any sizes and any alignment: the device copies take the host pointers' phase (address & 15).  `gray`
+ * is read and `dst` read and written from the first byte to the last pixel of the last row -- (batch x height - 1) x pitch + one row of pixels, nothing behind
+ * it -- so either may be a crop of a wider image; the bytes of `dst` in that span that are no pixel come back as they went.  Refused (GF_ERR_INVALID): track_cnt < 0, a point that is not finite or beyond
+ * 2^20 in magnitude, short pitches, n[b] > cap.  GF_ERR_HIP if a byte next to the device copy of dst was written. */
+int gf_draw_track_batch(const uint8_t* gray, size_t gray_pitch, int batch, int width, int height, const int* n, const float* cur_xy, const int* track_cnt,
+                        const float* prev_xy, const uint8_t* has_prev, int cap, uint8_t* dst, size_t dst_pitch);
 /* FeatureTracker::removeOutliers (feature_tracker.cpp:1029-1045) */
 int gf_tracker_remove_outliers(gf_tracker* h, int seq, const int* ids, int n);
 /* public members ids / track_cnt / prev_pts (feature_tracker.h:85-88) */
@@ -603,6 +635,11 @@ int gf_estimator_get_state(gf_estimator* h, double* Ps, double* Rs, double* Vs, 
  * bytes of the tracker's frame size, rows `stride` bytes apart, non-zero = allowed, NULL clears; it holds from the next gf_estimator_input_image on.
  * GF_ERR_INVALID without a tracker, and as gf_tracker_set_roi refuses. */
 int gf_estimator_set_roi(gf_estimator* h, const uint8_t* mask, int stride);
+/* SHOW_TRACK and getTrackImage (feature_tracker.cpp:849-905, :1047) of an estimator that owns its tracker: gf_tracker_set_show_track / gf_tracker_track_image
+ * on that tracker's one sequence -- the picture of the last gf_estimator_input_image, height x width x 3 bytes, rows `stride` bytes apart.  GF_ERR_INVALID
+ * without a tracker, and as those calls refuse. */
+int gf_estimator_set_show_track(gf_estimator* h, int on);
+int gf_estimator_get_track_image(gf_estimator* h, uint8_t* dst, int stride);
 int gf_estimator_set_state(gf_estimator* h, int frame_count, int solver_flag, const double* Ps, const double* Rs, const double* Vs,
                            const double* Bas, const double* Bgs);
 int gf_estimator_get_features(gf_estimator* h, int cap, int* id, int* start_frame, int* n_obs, double* estimated_depth, int* estimate_flag,
@@ -664,6 +701,9 @@ int gf_estimator_group_stats(gf_estimator_group* g, long long* batches, long lon
  * (EQUALIZE, parameters.cpp:169; any non-zero value switches it on) sets cfg->tracker.equalize to 1.  Options outside the built path (use_line, use_yolo, plane, use_motion, num_of_cam 2, estimate_extrinsic 2,
  * gnss_local_online_sync) return GF_ERR_INVALID instead of being ignored. */
 int gf_estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* cfg);
+/* show_track (SHOW_TRACK, parameters.cpp:202; what makes the node publish getTrackImage, feature_tracker.cpp:849-905 / :1047) of the same file with the same
+ * reader; a missing key reads as 0.  gf_estimator_cfg does not carry it: a caller that wants the pictures turns them on (gf_estimator_set_show_track). */
+int gf_show_track_from_yaml(const char* config_file, int* show_track);
 /* the line pubOdometry appends to VINS_RESULT_PATH (utility/visualization.cpp:346-357): "t x y z qx qy qz qw", fixed, 9 decimals;
  * P = Ps[WINDOW_SIZE], R = Rs[WINDOW_SIZE] (row-major), quaternion as Eigen::Quaterniond(R) */
 int gf_tum_append(const char* path, double t, const double* P, const double* R);

@@ -9,10 +9,15 @@
 //                                                                   encoding: colour, Bayer, yuv422, mono16) and cv_bridge::toCvCopy(msg, MONO8) (rosNodeTest.cpp:238-254) runs on the device; same vio.txt
 //   --roi <mask.pgm>                                                with any single-process form: a region of interest for the tracker (8-bit PGM of the configured
 //                                                                   frame size, non-zero = allowed; gf_estimator_set_roi).  No YAML key: the reference has none
+//   --track-images <dir>                                            with any single-process form: SHOW_TRACK on, and FeatureTracker::getTrackImage() of every
+//                                                                   camera frame -- what the node publishes as image_track (feature_tracker.cpp:849-905, :1047) -- as
+//                                                                   <dir>/<frame index, six digits>.ppm (binary PPM, so R, G, B: the picture's bgr8 bytes reversed).
+//                                                                   Without it a `show_track: 1` of the config does nothing: the reference's imshow has no counterpart
 // reads the reference's own YAML configuration (parameters.cpp key names), replays the recorded IMU / wheel / RGB / depth messages of
 // <dataset dir> (layout in host/replay_node.h) through FeatureTracker::trackImage and Estimator::processImage on the GPU, and writes the
 // trajectory file the reference writes (output_path/vio.txt, TUM format) — to <vio.txt> when given, else to `output_path` of the config.
 #include <poll.h>
+#include <sys/stat.h>
 #include <sys/wait.h>
 #include <unistd.h>
 
@@ -52,8 +57,24 @@ static void set_roi_from_pgm(gf::Estimator& estimator, const std::string& path) 
     estimator.setRegionOfInterest(mask.data(), w);
 }
 
+// --track-images: one frame's picture as a binary PPM
+static void write_track_ppm(gf::Estimator& estimator, const std::string& dir, long frame) {
+    static std::vector<uint8_t> store, rgb;
+    gf::ImageView<uint8_t> v;
+    estimator.getTrackImage(store, v);
+    rgb.resize(store.size());
+    for (size_t i = 0; i + 2 < store.size(); i += 3) { rgb[i] = store[i + 2]; rgb[i + 1] = store[i + 1]; rgb[i + 2] = store[i]; }
+    char name[32];
+    snprintf(name, sizeof name, "/%06ld.ppm", frame);
+    FILE* f = fopen((dir + name).c_str(), "wb");
+    if (!f) throw std::runtime_error("--track-images: cannot write " + dir + name);
+    fprintf(f, "P6\n%d %d\n255\n", v.cols, v.rows);
+    const bool ok = fwrite(rgb.data(), 1, rgb.size(), f) == rgb.size();
+    if (fclose(f) != 0 || !ok) throw std::runtime_error("--track-images: cannot write " + dir + name);
+}
+
 static void replay_one(const char* config, const std::string& source, bool from_bag, const std::string& out, gf::Estimator& estimator, bool quiet, bool device_gray = false,
-                       const std::string& roi = std::string()) {
+                       const std::string& roi = std::string(), const std::string& track_images = std::string()) {
     estimator.readParameters(config);
     if (device_gray) {   // the tracker is created for the encoding of the colour topic: one handle has one format
         const int fmt = gf::ReplayNode<gf::Estimator>::bag_image_format(source, yaml_string(config, "image0_topic"));
@@ -70,6 +91,12 @@ static void replay_one(const char* config, const std::string& source, bool from_
     node.w_replace = wr.empty() ? 0 : atoi(wr.c_str());
     node.gnss_local_time_diff = estimator.cfg.gnss_enable ? estimator.cfg.gnss_local_time_diff : 0.0;   // rosNodeTest.cpp:703-708
     node.device_gray = device_gray;
+    if (!track_images.empty()) {
+        struct stat st;
+        if (stat(track_images.c_str(), &st) != 0 && mkdir(track_images.c_str(), 0777) != 0) throw std::runtime_error("--track-images: cannot create " + track_images);
+        estimator.setShowTrack(true);
+        node.after_image = [&estimator, track_images](long frame, double) { write_track_ppm(estimator, track_images, frame); };
+    }
     if (from_bag) node.run_bag(source, yaml_string(config, "imu_topic"), yaml_string(config, "wheel_topic"), yaml_string(config, "image0_topic"), yaml_string(config, "image1_topic"));
     else node.run(source);
     if (!quiet)
@@ -180,6 +207,15 @@ int main(int argc, char** argv) {
             for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
             argc -= 2; i--;
         }
+    std::string track_images;   // --track-images <dir>, anywhere on the line
+    for (int i = 1; i < argc; i++)
+        if (std::string(argv[i]) == "--track-images") {
+            if (i + 1 >= argc) { fprintf(stderr, "gf_replay: --track-images needs a directory\n"); return 2; }
+            track_images = argv[i + 1];
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2; i--;
+        }
+    if (!track_images.empty() && argc >= 2 && std::string(argv[1]) == "--ranks") { fprintf(stderr, "gf_replay: --track-images goes with the single-process forms (one directory, one camera)\n"); return 2; }
     if (!roi.empty() && argc >= 2 && std::string(argv[1]) == "--ranks") { fprintf(stderr, "gf_replay: --roi goes with the single-process forms (one mask, one camera)\n"); return 2; }
     if (argc >= 5 && std::string(argv[1]) == "--ranks") {
         const int world = atoi(argv[2]);
@@ -217,13 +253,13 @@ int main(int argc, char** argv) {
         return rc;
     }
     const bool from_bag = argc >= 4 && std::string(argv[2]) == "--bag";
-    if (argc < 3 || (from_bag && argc < 4)) { fprintf(stderr, "usage: %s [--roi <mask.pgm>] <config.yaml> <dataset dir> [<vio.txt>]\n       %s [--device-gray] [--roi <mask.pgm>] <config.yaml> --bag <recording.bag> [<vio.txt>]\n       %s --ranks N <config.yaml> <dataset dir> ...\n", argv[0], argv[0], argv[0]); return 2; }
+    if (argc < 3 || (from_bag && argc < 4)) { fprintf(stderr, "usage: %s [--roi <mask.pgm>] [--track-images <dir>] <config.yaml> <dataset dir> [<vio.txt>]\n       %s [--device-gray] [--roi <mask.pgm>] [--track-images <dir>] <config.yaml> --bag <recording.bag> [<vio.txt>]\n       %s --ranks N <config.yaml> <dataset dir> ...\n", argv[0], argv[0], argv[0]); return 2; }
     if (device_gray && !from_bag) { fprintf(stderr, "gf_replay: --device-gray goes with --bag (PGM frames are MONO8 already)\n"); return 2; }
     const int out_arg = from_bag ? 4 : 3;
     try {
         gf::Estimator estimator;
         const std::string out = argc > out_arg ? argv[out_arg] : yaml_string(argv[1], "output_path") + "/vio.txt";
-        replay_one(argv[1], from_bag ? argv[3] : argv[2], from_bag, out, estimator, false, device_gray, roi);
+        replay_one(argv[1], from_bag ? argv[3] : argv[2], from_bag, out, estimator, false, device_gray, roi, track_images);
         if (estimator.cfg.gnss_enable) {   // gnss_result.txt of the reference carries the ECEF / ENU position; here as one closing line
             int gi[8]; double yaw, anc[3], ecef[3], enu[3];
             if (gf_estimator_get_gnss_state(estimator.handle(), gi, nullptr, nullptr, &yaw, anc, ecef, enu) == GF_OK) {
