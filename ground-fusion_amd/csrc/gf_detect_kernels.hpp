@@ -293,6 +293,85 @@ __global__ void __launch_bounds__(256) roi_pack_refs_kernel(const gf_frame_ref* 
     gfroi::pack_thread(f.data, f.pitch, w, h, blockIdx.y, blockIdx.x * 256 + threadIdx.x, table + (size_t)list_entry(seq_of, blockIdx.z) * seq_words);
 }
 
+// The box setter of the region of interest (gf_tracker_set_boxes_some, gf_roi_boxes_batch): for every job (one listed sequence and its list boxes[first .. first + n))
+// the words of R_eff = R_base AND NOT union(boxes) into `table`, the table the detector reads, in ONE launch.  Block (bx, band, job) owns the kRoiBoxSpan columns
+// from bx * kRoiBoxSpan of one band of one sequence:
+//   - the list goes through LDS in pieces of kRoiBoxPiece boxes, as many pieces as the list has (it is never cut): thread t of a piece clips box t to the frame's
+//     columns and to this band's rows (gfroi::box_cols / box_rows, the host's functions), so a box's row mask for the band is computed once per block, not per
+//     word, and what lies in LDS is 12 bytes a box: the row mask and the column range;
+//   - every lane then walks the piece (the same LDS address in all lanes: a broadcast; a box that misses the band is skipped by the whole wavefront at once)
+//     and ORs the row mask into those of its kRoiBoxWords neighbouring words whose column lies in the range;
+//   - it reads its base words and writes its composed words in the widest pieces their word index allows: 16 bytes where the lane's first word index is a
+//     multiple of four (always, at a width that is one, which every tracker handle's is), else 8-byte pieces on even indices and single words at the ends.
+// base == nullptr: no base region, every base word is all ones.  base and table are [*][seq_words] from 16-byte aligned starts, indexed by job.seq.
+// Bounds: a lane with x >= w writes nothing; the others touch words x .. min(x + 4, w) - 1 of row `band` < bands(h) of sequence job.seq (the host checks it);
+// box (first + i), i < n, is inside the list's range by the host's check of `first`.
+constexpr int kRoiBoxPiece = 256, kRoiBoxWords = 4, kRoiBoxSpan = kRoiBoxPiece * kRoiBoxWords;
+struct RoiBoxJob { int seq, first, n, pad; };
+static_assert(sizeof(RoiBoxJob) == 16 && sizeof(gf_box) == 16, "jobs and boxes travel in one staging block, as they lie");
+
+// words [0, n) of v <-> p[0 .. n), p's word index being g: one 16-byte piece, or 8-byte pieces on even indices and single words
+template <bool STORE> __device__ __forceinline__ void roi_words_io(uint32_t* p, size_t g, int n, uint32_t (&v)[kRoiBoxWords]) {
+    if (n == 4 && !(g & 3)) {
+        uint4* q = reinterpret_cast<uint4*>(p);
+        if (STORE) *q = make_uint4(v[0], v[1], v[2], v[3]);
+        else { const uint4 t = *q; v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
+        return;
+    }
+    int done = 0;
+#pragma unroll
+    for (int k = 0; k < kRoiBoxWords; k++) {
+        if (k < done || k >= n) continue;
+        constexpr int last = kRoiBoxWords - 1;
+        if (k + 2 <= n && !((g + k) & 1)) {
+            uint2* q = reinterpret_cast<uint2*>(p + k);
+            if (STORE) *q = make_uint2(v[k], v[k < last ? k + 1 : last]);
+            else { const uint2 t = *q; v[k] = t.x; v[k < last ? k + 1 : last] = t.y; }
+            done = k + 2;
+        } else {
+            if (STORE) p[k] = v[k]; else v[k] = p[k];
+            done = k + 1;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kRoiBoxPiece) roi_boxes_kernel(const RoiBoxJob* __restrict__ jobs, const gf_box* __restrict__ boxes, int w, int h,
+                                                                 const uint32_t* __restrict__ base, uint32_t* __restrict__ table, size_t seq_words) {
+    __shared__ uint32_t s_rows[kRoiBoxPiece];
+    __shared__ int s_x0[kRoiBoxPiece], s_x1[kRoiBoxPiece];
+    const RoiBoxJob job = jobs[blockIdx.z];
+    const int band = blockIdx.y, t = threadIdx.x;
+    const int x = (blockIdx.x * kRoiBoxPiece + t) * kRoiBoxWords;
+    uint32_t cov[kRoiBoxWords] = {0, 0, 0, 0};
+    for (int at = 0; at < job.n; at += kRoiBoxPiece) {   // job.n is the block's: every thread takes every barrier
+        const int m = min(kRoiBoxPiece, job.n - at);
+        if (at) __syncthreads();   // the piece before this one has been read
+        if (t < m) {
+            const gf_box b = boxes[(size_t)job.first + at + t];
+            int x0, x1;
+            const bool cols = gfroi::box_cols(b, w, x0, x1);
+            s_rows[t] = cols ? gfroi::box_rows(b, h, band) : 0u;
+            s_x0[t] = x0; s_x1[t] = x1;
+        }
+        __syncthreads();
+        for (int i = 0; i < m; i++) {
+            const uint32_t rows = s_rows[i];
+            if (!rows) continue;
+            const int x0 = s_x0[i], x1 = s_x1[i];
+#pragma unroll
+            for (int k = 0; k < kRoiBoxWords; k++) if (x + k >= x0 && x + k <= x1) cov[k] |= rows;
+        }
+    }
+    if (x >= w) return;
+    const int n = min(kRoiBoxWords, w - x);
+    const size_t g = (size_t)job.seq * seq_words + gfroi::word_at(w, band, x);
+    uint32_t v[kRoiBoxWords] = {~0u, ~0u, ~0u, ~0u};
+    if (base) roi_words_io<false>(const_cast<uint32_t*>(base) + g, g, n, v);
+#pragma unroll
+    for (int k = 0; k < kRoiBoxWords; k++) v[k] = gfroi::compose_word(v[k], cov[k]);
+    roi_words_io<true>(table + g, g, n, v);
+}
+
 // Both selection kernels run one block per list position and touch only tables of the call ([count], by position): the candidates, want, the output and the
 // call's depth frames.  Nothing here is kept per sequence, so the same list reaches both by construction.
 struct SelectArgs {

@@ -1958,6 +1958,13 @@ int gf_estimator_set_roi(gf_estimator* e, const uint8_t* mask, int stride) {
     if (!e || !e->tracker) return gf::set_err(GF_ERR_INVALID, "estimator was created without a tracker (cfg.with_tracker)");
     return gf_tracker_set_roi(e->tracker, 0, mask, stride);
 }
+// the exclusion boxes of the estimator's own tracker (gf_tracker_set_boxes_some on its one sequence): from the next gf_estimator_input_image on; n == 0 clears
+int gf_estimator_set_boxes(gf_estimator* e, const gf_box* boxes, int n) {
+    if (!e || !e->tracker) return gf::set_err(GF_ERR_INVALID, "estimator was created without a tracker (cfg.with_tracker)");
+    if (n < 0) return gf::set_err(GF_ERR_INVALID, "%d boxes", n);
+    const int seq = 0, first[2] = {0, n};
+    return gf_tracker_set_boxes_some(e->tracker, 1, &seq, first, boxes);
+}
 // SHOW_TRACK and getTrackImage (feature_tracker.cpp:849-905, :1047) of the estimator's own tracker, on its one sequence
 int gf_estimator_set_show_track(gf_estimator* e, int on) {
     if (!e || !e->tracker) return gf::set_err(GF_ERR_INVALID, "estimator was created without a tracker (cfg.with_tracker)");

@@ -24,6 +24,9 @@ int draw_track_launch(const gfdraw::DrawJob* d_jobs, int count, int w, int h, hi
 
 }  // namespace gf
 
+static int draw_track_host_buffers(const uint8_t* gray, size_t gray_pitch, int batch, int width, int height, const int* n, const float* cur_xy, const int* track_cnt,
+                                   const float* prev_xy, const uint8_t* has_prev, int cap, uint8_t* dst, size_t dst_pitch, const int* n_boxes, const gf_box* boxes, int box_cap);
+
 extern "C" {
 
 // Copies in, renders with the tracker's kernel, copies out; synchronous.  The device copies of `gray` and `dst` take the host pointers' alignment (address & 15),
@@ -32,11 +35,25 @@ extern "C" {
 // it that are no pixel come back as they were.
 int gf_draw_track_batch(const uint8_t* gray, size_t gray_pitch, int batch, int width, int height, const int* n, const float* cur_xy, const int* track_cnt,
                         const float* prev_xy, const uint8_t* has_prev, int cap, uint8_t* dst, size_t dst_pitch) {
+    return draw_track_host_buffers(gray, gray_pitch, batch, width, height, n, cur_xy, track_cnt, prev_xy, has_prev, cap, dst, dst_pitch, nullptr, nullptr, 0);
+}
+// The same with the frames of frame b's n_boxes[b] <= box_cap boxes, row b of the [batch][box_cap] table, behind its dots and strokes (drawTrackbox, :960-975)
+int gf_draw_track_boxes_batch(const uint8_t* gray, size_t gray_pitch, int batch, int width, int height, const int* n, const float* cur_xy, const int* track_cnt,
+                              const float* prev_xy, const uint8_t* has_prev, int cap, uint8_t* dst, size_t dst_pitch, const int* n_boxes, const gf_box* boxes, int box_cap) {
+    if (!n_boxes || box_cap < 0) return gf::set_err(GF_ERR_INVALID, "track image: null table of box counts or a box capacity of %d", box_cap);
+    return draw_track_host_buffers(gray, gray_pitch, batch, width, height, n, cur_xy, track_cnt, prev_xy, has_prev, cap, dst, dst_pitch, n_boxes, boxes, box_cap);
+}
+
+}  // extern "C"
+
+static int draw_track_host_buffers(const uint8_t* gray, size_t gray_pitch, int batch, int width, int height, const int* n, const float* cur_xy, const int* track_cnt,
+                                   const float* prev_xy, const uint8_t* has_prev, int cap, uint8_t* dst, size_t dst_pitch, const int* n_boxes, const gf_box* boxes, int box_cap) {
     using namespace gfdraw;
     if (!gray || !dst || !n) return gf::set_err(GF_ERR_INVALID, "null argument");
     if (batch < 1 || width < 1 || height < 1 || cap < 0) return gf::set_err(GF_ERR_INVALID, "track image: batch %d of %dx%d frames, capacity %d", batch, width, height, cap);
     if (gray_pitch < (size_t)width || dst_pitch < 3 * (size_t)width) return gf::set_err(GF_ERR_INVALID, "track image: a pitch is shorter than a row of %d pixels", width);
-    std::vector<Prim> lists(list_capacity((size_t)batch * cap));
+    const size_t room = list_capacity((size_t)cap) + (size_t)box_cap;   // primitives of one frame
+    std::vector<Prim> lists((size_t)batch * room);
     std::vector<int> count(batch);
     for (int b = 0; b < batch; b++) {
         if (n[b] < 0 || n[b] > cap) return gf::set_err(GF_ERR_INVALID, "track image: frame %d lists %d features, capacity %d", b, n[b], cap);
@@ -44,8 +61,12 @@ int gf_draw_track_batch(const uint8_t* gray, size_t gray_pitch, int batch, int w
         char msg[160];
         const size_t at = (size_t)b * cap;
         count[b] = build_list(n[b], cur_xy + 2 * at, track_cnt + at, prev_xy ? prev_xy + 2 * at : nullptr, has_prev ? has_prev + at : nullptr,
-                              lists.data() + list_capacity(at), msg, sizeof msg);
+                              lists.data() + (size_t)b * room, msg, sizeof msg);
         if (count[b] < 0) return gf::set_err(GF_ERR_INVALID, "track image: frame %d: %s", b, msg);
+        if (n_boxes) {
+            if (n_boxes[b] < 0 || n_boxes[b] > box_cap || (n_boxes[b] > 0 && !boxes)) return gf::set_err(GF_ERR_INVALID, "track image: frame %d lists %d boxes, capacity %d", b, n_boxes[b], box_cap);
+            count[b] += append_frames(boxes ? boxes + (size_t)b * box_cap : nullptr, n_boxes[b], lists.data() + (size_t)b * room + count[b]);
+        }
     }
     if (int rc = gf::require_device()) return rc;
     constexpr size_t kGuard = 64;   // bytes on either side of the destination that must come back as they were put
@@ -64,7 +85,7 @@ int gf_draw_track_batch(const uint8_t* gray, size_t gray_pitch, int batch, int w
     if (!lists.empty()) HIPCHK(hipMemcpy(d_lists.p, lists.data(), lists.size() * sizeof(Prim), hipMemcpyHostToDevice));
     std::vector<DrawJob> jobs(batch);
     for (int b = 0; b < batch; b++)
-        jobs[b] = DrawJob{g0 + (size_t)b * height * gray_pitch, gray_pitch, o0 + (size_t)b * height * dst_pitch, dst_pitch, d_lists.p + list_capacity((size_t)b * cap), count[b], 0};
+        jobs[b] = DrawJob{g0 + (size_t)b * height * gray_pitch, gray_pitch, o0 + (size_t)b * height * dst_pitch, dst_pitch, d_lists.p + (size_t)b * room, count[b], 0};
     HIPCHK(hipMemcpy(d_jobs.p, jobs.data(), jobs.size() * sizeof(DrawJob), hipMemcpyHostToDevice));
     if (int rc = gf::draw_track_launch(d_jobs.p, batch, width, height, nullptr)) return rc;
     HIPCHK(hipDeviceSynchronize());
@@ -75,5 +96,3 @@ int gf_draw_track_batch(const uint8_t* gray, size_t gray_pitch, int batch, int w
     HIPCHK(hipMemcpy(dst, o0, dst_bytes, hipMemcpyDeviceToHost));
     return GF_OK;
 }
-
-}  // extern "C"

@@ -6,12 +6,15 @@
 // The geometry, colours, order and rounding are the reference's; OpenCV's thick-circle and thick-line outlines are replaced by distance tests:
 //   dot     (cv::circle, radius 2, thickness 6)      pixels with dx^2 + dy^2 <= 25 around the rounded centre
 //   stroke  (one line of cv::arrowedLine, thickness 3) pixels whose squared distance to the segment is <= 9/4
-// Green where any stroke covers, else the colour of the covering dot with the largest list index, else (g, g, g).
+//   frame   (drawTrackbox's cv::rectangle of a box, thickness 5, feature_tracker.cpp:960-975)  the pixels within 2 of the rectangle's outline, three inequalities
+// (0, 128, 255) where any box's frame covers, else green where any stroke covers, else the colour of the covering dot with the largest list index, else (g, g, g).
 #pragma once
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
+
+#include "../../include/groundfusion_hip.h"   // gf_box
 
 #if defined(__HIPCC__) || defined(__HIP__)
 #include <hip/hip_runtime.h>
@@ -39,8 +42,11 @@ GF_DRAW_HD uint8_t color2(int k) {
     return t[k];
 }
 
-// One primitive.  A dot: centre (ux, uy), colour bytes (c0, 0, c2); vx, vy unused (0).  A stroke: the segment (ux, uy) - (vx, vy), always (0, 255, 0).
+// One primitive.  A dot: centre (ux, uy), colour bytes (c0, 0, c2); vx, vy unused (0).  A stroke (stroke == 1): the segment (ux, uy) - (vx, vy), always (0, 255, 0).
+// A frame (stroke == kFrame): the rectangle of pixels X0 = ux .. X1 = vx, Y0 = uy .. Y1 = vy whose outline is drawn 5 wide, always (0, 128, 255).
 struct Prim { int32_t ux, uy, vx, vy; uint8_t stroke, c0, c2, pad; };
+constexpr uint8_t kFrame = 2;
+constexpr int kFrameReach = 2;         // a frame reaches 2 pixels outside and inside its rectangle's outline
 static_assert(sizeof(Prim) == 20, "Prim is copied to the device as it lies");
 
 GF_DRAW_HD Prim make_dot(int x, int y, int track_cnt) {
@@ -48,6 +54,15 @@ GF_DRAW_HD Prim make_dot(int x, int y, int track_cnt) {
     return Prim{x, y, 0, 0, 0, color0(k), color2(k), 0};
 }
 GF_DRAW_HD Prim make_stroke(int ux, int uy, int vx, int vy) { return Prim{ux, uy, vx, vy, 1, 0, 255, 0}; }
+// The frame of a box: cv::rectangle(img, Rect(xmin, ymin, xmax - xmin, ymax - ymin), Scalar(0, 128, 255), 5).  False, and nothing is drawn, unless xmax > xmin &&
+// ymax > ymin (an empty cv::Rect).  X1 = xmax - 1 and Y1 = ymax - 1 in 64 bits, then every coordinate clamped to +-kMaxCoord: a frame's pixels inside an image
+// (coordinates 0 .. < 2^20 - 2) are the same with the clamped corners as with the box's own.
+GF_DRAW_HD int32_t clamp_coord(int64_t v) { return (int32_t)(v < -kMaxCoord ? -kMaxCoord : v > kMaxCoord ? kMaxCoord : v); }
+GF_DRAW_HD bool make_frame(const gf_box& b, Prim& out) {
+    if (!(b.xmax > b.xmin && b.ymax > b.ymin)) return false;
+    out = Prim{clamp_coord(b.xmin), clamp_coord(b.ymin), clamp_coord((int64_t)b.xmax - 1), clamp_coord((int64_t)b.ymax - 1), kFrame, 0, 255, 0};
+    return true;
+}
 
 // ---- coverage, in exact integers.  A dot's centre and a stroke's ends lie within 2^21 of the origin (build_list: points within 2^20, tips within 0.2 * the
 // arrow's length of one), pixels inside an image: every difference is below 2^23, every dot product and L below 2^47.
@@ -66,13 +81,21 @@ GF_DRAW_HD bool stroke_covers(const Prim& s, int x, int y) {
     if (cr >= ((int64_t)1 << 25)) return false;
     return 4 * cr * cr <= 9 * L;
 }
-GF_DRAW_HD bool covers(const Prim& p, int x, int y) { return p.stroke ? stroke_covers(p, x, y) : dot_covers(p, x, y); }
+// the frame of X0 = ux .. X1 = vx, Y0 = uy .. Y1 = vy (|coordinates| <= 2^20: the sums below stay far inside 32 bits)
+GF_DRAW_HD bool frame_covers(const Prim& f, int x, int y) {
+    if (x < f.ux - kFrameReach || x > f.vx + kFrameReach || y < f.uy - kFrameReach || y > f.vy + kFrameReach) return false;
+    return !(x > f.ux + kFrameReach && x < f.vx - kFrameReach && y > f.uy + kFrameReach && y < f.vy - kFrameReach);
+}
+GF_DRAW_HD bool covers(const Prim& p, int x, int y) { return p.stroke == kFrame ? frame_covers(p, x, y) : p.stroke ? stroke_covers(p, x, y) : dot_covers(p, x, y); }
 
 // ---- binning: whether a primitive can cover a pixel of the rectangle x0 .. x1, y0 .. y1 (inclusive), by its bounding box.  Never false for a primitive that
 // covers one (tests/native/track_draw_host.cpp holds it to brute force); what it lets through in vain costs the kernel time only.
 GF_DRAW_HD bool touches(const Prim& p, int x0, int y0, int x1, int y1) {
     int lx, hx, ly, hy;
-    if (p.stroke) {
+    if (p.stroke == kFrame) {   // also not a tile that lies wholly in the frame's open inside
+        if (x0 > p.ux + kFrameReach && x1 < p.vx - kFrameReach && y0 > p.uy + kFrameReach && y1 < p.vy - kFrameReach) return false;
+        lx = p.ux - kFrameReach; hx = p.vx + kFrameReach; ly = p.uy - kFrameReach; hy = p.vy + kFrameReach;
+    } else if (p.stroke) {
         lx = (p.ux < p.vx ? p.ux : p.vx) - kStrokeReach; hx = (p.ux < p.vx ? p.vx : p.ux) + kStrokeReach;
         ly = (p.uy < p.vy ? p.uy : p.vy) - kStrokeReach; hy = (p.uy < p.vy ? p.vy : p.uy) + kStrokeReach;
     } else { lx = p.ux - kDotReach; hx = p.ux + kDotReach; ly = p.uy - kDotReach; hy = p.uy + kDotReach; }
@@ -80,15 +103,18 @@ GF_DRAW_HD bool touches(const Prim& p, int x0, int y0, int x1, int y1) {
 }
 
 // ---- the per-pixel resolve.  A pixel walks the primitives that may cover it, in any order and in any number of pieces, and keeps: whether a stroke covered it,
-// and the covering dot of the largest list index.  The result is a function of the list alone.
-struct Acc { int32_t dot; uint8_t green, c0, c2; };   // dot: list index of the dot kept so far, -1: none
-GF_DRAW_HD Acc acc_empty() { return Acc{-1, 0, 0, 0}; }
+// whether a frame did (frames cover strokes and dots, and all frames have one colour, so a later one covering an earlier one changes no byte), and the covering
+// dot of the largest list index.  The result is a function of the list alone.
+struct Acc { int32_t dot; uint8_t green, c0, c2, frame; };   // dot: list index of the dot kept so far, -1: none
+GF_DRAW_HD Acc acc_empty() { return Acc{-1, 0, 0, 0, 0}; }
 GF_DRAW_HD void accumulate(Acc& a, const Prim& p, int index, int x, int y) {
-    if (p.stroke) { if (!a.green && stroke_covers(p, x, y)) a.green = 1; }
+    if (p.stroke == kFrame) { if (!a.frame && frame_covers(p, x, y)) a.frame = 1; }
+    else if (p.stroke) { if (!a.green && stroke_covers(p, x, y)) a.green = 1; }
     else if (index > a.dot && dot_covers(p, x, y)) { a.dot = index; a.c0 = p.c0; a.c2 = p.c2; }
 }
 // the pixel's three bytes in memory order, as c0 | c1 << 8 | c2 << 16
 GF_DRAW_HD uint32_t finish(const Acc& a, uint8_t g) {
+    if (a.frame) return (128u << 8) | (255u << 16);   // Scalar(0, 128, 255)
     if (a.green) return 255u << 8;
     if (a.dot >= 0) return (uint32_t)a.c0 | ((uint32_t)a.c2 << 16);
     return (uint32_t)g * 0x010101u;
@@ -104,6 +130,12 @@ GF_DRAW_HD uint32_t resolve(const Prim* list, int n, int x, int y, uint8_t g) {
 // null: no arrows).  out: room for list_capacity(n) primitives -- all dots in list order, then the arrows' strokes.  Returns the number written, or -1 with the
 // reason in msg: a track_cnt < 0, a point that is not finite or beyond 2^20 in magnitude.
 inline size_t list_capacity(size_t n) { return 4 * n; }
+// the frames of the boxes in force, appended behind a frame's dots and strokes (drawTrackbox draws them last, :960-975); returns how many were written (<= n)
+inline int append_frames(const gf_box* boxes, int n, Prim* out) {
+    int m = 0;
+    for (int i = 0; i < n; i++) if (make_frame(boxes[i], out[m])) m++;
+    return m;
+}
 inline bool point_ok(float x, float y) { return isfinite(x) && isfinite(y) && fabsf(x) <= (float)kMaxCoord && fabsf(y) <= (float)kMaxCoord; }
 inline int build_list(int n, const float* cur_xy, const int* track_cnt, const float* prev_xy, const uint8_t* has_prev, Prim* out, char* msg, size_t msg_len) {
     for (int i = 0; i < n; i++) {

@@ -81,8 +81,11 @@ template <class V> inline void reduce_vector(std::vector<V>& v, const uint8_t* s
 // the reference) and greedy keep of points not covered by an earlier kept point's filled circle.
 // roi: the sequence's region of interest (gf_roi.hpp) or null.  With one, the walk starts from `mask = R` instead of an all-255 image: a point whose rounded pixel
 // is excluded fails `mask.at(pt) == 255` like a covered one -- not kept, no circle, gone from ids / track_cnt / cur_pts.
+// boxes, n_boxes: the sequence's exclusion boxes (gf_box); the walk then starts from R_eff = R AND NOT union(boxes), tested per point against the base table and
+// the list (gfroi::allowed): no table is composed on the host.
 // T: the circle of the sequence's min_dist.  width, height: the frame's.
-inline void set_mask_host(int width, int height, SeqState& s, const DiskTable& T, const uint32_t* roi, P2i* centers, int& n_centers) {
+inline void set_mask_host(int width, int height, SeqState& s, const DiskTable& T, const uint32_t* roi, P2i* centers, int& n_centers, const gf_box* boxes = nullptr,
+                          int n_boxes = 0) {
     struct E { int cnt; P2f pt; int id; uint16_t depth; };
     static thread_local std::vector<E> v;
     v.clear();
@@ -98,7 +101,7 @@ inline void set_mask_host(int width, int height, SeqState& s, const DiskTable& T
     s.grid_next.clear();
     for (auto& it : v) {
         const int x = cvRoundf(it.pt.x), y = cvRoundf(it.pt.y);
-        if (roi && !gfroi::allowed(roi, width, x, y)) continue;   // tracked points are inside the image (inBorder, feature_tracker.cpp:14-20)
+        if ((roi || n_boxes > 0) && !gfroi::allowed(roi, boxes, n_boxes, width, x, y)) continue;   // tracked points are inside the image (inBorder, feature_tracker.cpp:14-20)
         const int cx = x / cell, cy = y / cell;
         bool covered = false;
         for (int yy = std::max(cy - 1, 0); yy <= std::min(cy + 1, gh - 1) && !covered; yy++)
@@ -198,9 +201,10 @@ struct LkRows {
 struct LkTally { long long level_passes = 0, iterations = 0, points = 0, tracked = 0; };   // what the sequence adds to gf_tracker_stats
 
 // After LK (feature_tracker.cpp:170-186): the reduction by status, track_cnt++, setMask and the number of corners the sequence wants.
-// T: the circle of par.min_dist; roi: the sequence's region of interest or null; centers_row / *n_centers: setMask's kept points for the detector.
+// T: the circle of par.min_dist; roi: the sequence's region of interest or null; centers_row / *n_centers: setMask's kept points for the detector;
+// boxes, n_boxes: the sequence's exclusion boxes, as set_mask_host takes them.
 inline LkTally after_lk(SeqState& s, const gf_tracker_seq_cfg& par, int width, int height, const DiskTable& T, const uint32_t* roi, const LkRows& r,
-                        P2i* centers_row, int* n_centers, int* want) {
+                        P2i* centers_row, int* n_centers, int* want, const gf_box* boxes = nullptr, int n_boxes = 0) {
     LkTally tally;
     const int n = (int)s.prev_pts.size();
     if (n > 0) {
@@ -227,7 +231,7 @@ inline LkTally after_lk(SeqState& s, const gf_tracker_seq_cfg& par, int width, i
     }
     for (auto& c : s.track_cnt) c++;
     int nc = 0;   // counted here and stored once: the tables are page-locked memory that neighbouring sequences' threads write too
-    set_mask_host(width, height, s, T, roi, centers_row, nc);
+    set_mask_host(width, height, s, T, roi, centers_row, nc, boxes, n_boxes);
     *n_centers = nc;
     *want = par.max_cnt - (int)s.cur_pts.size();
     return tally;
@@ -272,7 +276,9 @@ inline Packed after_detect(SeqState& s, const gf_tracker_seq_cfg& par, const Det
 // After after_detect, for a sequence whose show_track is on (drawTrack, feature_tracker.cpp:849-905): the frame's primitive list from what the frame left -- a dot
 // per feature at its current point, coloured by track_cnt, and an arrow for every feature whose id was in the previous frame, back to the point LK tracked it from
 // (draw_from; a newly detected corner has none).  False if the builder refuses a point; the sequence then has no picture and keeps the reason in draw_why.
-inline bool record_track(SeqState& s) {
+// boxes, n_boxes: the exclusion boxes in force for the frame; their frames follow all dots and strokes (drawTrackbox, feature_tracker.cpp:960-975).  Its yellow
+// dots for the features inside a box (:982-987) have no counterpart: no kept feature lies inside a box.
+inline bool record_track(SeqState& s, const gf_box* boxes = nullptr, int n_boxes = 0) {
     const size_t n = s.ids.size();
     static thread_local std::vector<float> cur, prev;
     static thread_local std::vector<uint8_t> has;
@@ -282,9 +288,10 @@ inline bool record_track(SeqState& s) {
         auto it = std::lower_bound(s.draw_from.begin(), s.draw_from.end(), s.ids[i], [](const std::pair<int, P2f>& a, int v) { return a.first < v; });
         if (it != s.draw_from.end() && it->first == s.ids[i]) { has[i] = 1; prev[2 * i] = it->second.x; prev[2 * i + 1] = it->second.y; }
     }
-    s.draw_list.resize(gfdraw::list_capacity(n));
+    s.draw_list.resize(gfdraw::list_capacity(n) + (size_t)n_boxes);
     char msg[160] = "";
-    const int m = gfdraw::build_list((int)n, cur.data(), s.track_cnt.data(), prev.data(), has.data(), s.draw_list.data(), msg, sizeof msg);
+    int m = gfdraw::build_list((int)n, cur.data(), s.track_cnt.data(), prev.data(), has.data(), s.draw_list.data(), msg, sizeof msg);
+    if (m >= 0 && n_boxes > 0) m += gfdraw::append_frames(boxes, n_boxes, s.draw_list.data() + m);
     s.draw_sent = false;
     s.draw_have = m >= 0;
     s.draw_list.resize(m >= 0 ? (size_t)m : 0);

@@ -189,6 +189,16 @@ struct gf_tracker {
     DevBuf<uint32_t> d_roi; DevBuf<int> d_roi_seq;
     std::vector<uint32_t> roi_bits; std::vector<uint8_t> roi_has;
     size_t roi_words = 0;
+    // The sequences' exclusion boxes (gf_roi.hpp; gf_tracker_set_boxes_some), obtained by the first box setter of the handle.  From then on d_roi holds the words of
+    // R_eff = R_base AND NOT union(boxes), written by roi_boxes_kernel, and d_roi_base the base words the setters of R pack (the table they wrote into d_roi before):
+    // next frame's boxes compose with the same base.  roi_bits stays the host's copy of the BASE words; setMask's walk and gf_tracker_get_roi test a pixel against
+    // it and boxes[seq] (gfroi::allowed with a list), so no table is rebuilt on or copied to the host for a list of boxes.  h_box_stage / d_box_stage: the jobs of one
+    // setter and their boxes, [B] RoiBoxJob then [B x GF_MAX_BOXES_PER_SEQ] gf_box; ev_boxes: behind the kernel that read them last, so that a second setter
+    // between two track calls does not write under it (box_pending: one left since the stream was last drained).
+    std::vector<std::vector<gf_box>> boxes;
+    DevBuf<uint32_t> d_roi_base;
+    DevBuf<uint8_t> d_box_stage; PinBuf<uint8_t> h_box_stage;
+    Event ev_boxes; bool box_pending = false;
     // The sequences' own parameters (gf_seq_cfg.hpp; gf_tracker_set_seq_cfg), the fourth thing addressed by SEQUENCE.  par[seq] is what is in force, the handle's cfg
     // until a setter says otherwise (host memory only).  The rest is obtained by the first setter of the handle, as the region of interest's tables are: the circle
     // tables of the sequences' min_dist -- seq_disk on the host for setMask's walk, d_seq_disk for the detector -- and the two lists that carry min_dist and
@@ -340,19 +350,91 @@ static void roi_clear_host(gf_tracker* h, int seq) {
     std::fill_n(h->roi_bits.begin() + (size_t)seq * h->roi_words, h->roi_words, ~0u);
     h->roi_has[seq] = 0;
 }
+// the table the setters of R write: the detector's own until the handle has boxes, the base table from then on
+static uint32_t* roi_base_table(gf_tracker* h) { return h->d_roi_base.p ? h->d_roi_base.p : h->d_roi.p; }
+static int boxes_compose(gf_tracker* h, int count, const int* seq);
 static int roi_packed(gf_tracker* h, int count, const int* seq) {   // behind a packing kernel: the words come back (setMask's walk reads them on the host) and the sequences have a region
     for (int i = 0; i < count; i++) {
         const size_t off = (size_t)seq[i] * h->roi_words;
-        HIPCHK(hipMemcpyAsync(h->roi_bits.data() + off, h->d_roi.p + off, h->roi_words * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(h->roi_bits.data() + off, roi_base_table(h) + off, h->roi_words * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     for (int i = 0; i < count; i++) h->roi_has[seq[i]] = 1;
-    return GF_OK;
+    return h->d_roi_base.p ? boxes_compose(h, count, seq) : GF_OK;   // a new base under the boxes in force
 }
 static int roi_upload(gf_tracker* h, int seq) {   // the host copy of one sequence's words -> the table
     const size_t off = (size_t)seq * h->roi_words;
-    HIPCHK(hipMemcpyAsync(h->d_roi.p + off, h->roi_bits.data() + off, h->roi_words * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(roi_base_table(h) + off, h->roi_bits.data() + off, h->roi_words * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));   // roi_bits is pageable
+    return h->d_roi_base.p ? boxes_compose(h, 1, &seq) : GF_OK;
+}
+
+// ---- exclusion boxes (gf_roi.hpp).  The first box setter of a handle: the base table, a copy of what the detector's table holds (no sequence has boxes yet), the
+// staging of a setter's jobs and boxes, and the lists themselves.
+static int boxes_ready(gf_tracker* h) {
+    if (h->d_roi_base.p) return GF_OK;
+    if (int rc = roi_ready(h)) return rc;
+    const size_t all = (size_t)h->B * h->roi_words, stage = (size_t)h->B * (sizeof(RoiBoxJob) + (size_t)GF_MAX_BOXES_PER_SEQ * sizeof(gf_box));
+    DevBuf<uint32_t> base; DevBuf<uint8_t> dst; PinBuf<uint8_t> hst;
+    HIPCHK(base.fit(all)); HIPCHK(dst.alloc(stage)); HIPCHK(hst.alloc(stage));
+    if (!h->ev_boxes.e) HIPCHK(hipEventCreateWithFlags(&h->ev_boxes.e, hipEventDisableTiming));
+    HIPCHK(hipMemcpyAsync(base.p, h->d_roi.p, all * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->d_draw_prims.p) {   // a handle that shows tracks already: its rows of primitives gain room for the boxes' frames, and every list goes down again
+        const size_t row = gfdraw::list_capacity(h->cap) + (size_t)GF_MAX_BOXES_PER_SEQ;
+        DevBuf<gfdraw::Prim> dp; PinBuf<gfdraw::Prim> hp;
+        HIPCHK(dp.alloc((size_t)h->B * row)); HIPCHK(hp.alloc((size_t)h->B * row));
+        h->d_draw_prims = std::move(dp); h->h_draw_prims = std::move(hp);
+        for (auto& q : h->seq) q.draw_sent = false;
+    }
+    h->boxes.assign(h->B, std::vector<gf_box>());
+    h->d_roi_base = std::move(base); h->d_box_stage = std::move(dst); h->h_box_stage = std::move(hst);
+    return GF_OK;
+}
+// The words of R_eff of the `count` listed sequences (checked by the caller) from their base words and the lists in h->boxes: the jobs and boxes into the page-locked
+// staging, one copy and one launch on the handle's stream, no wait for either.  Only a call that finds the staging of an earlier one still unread waits for that.
+static int boxes_compose(gf_tracker* h, int count, const int* seq) {
+    if (count == 0) return GF_OK;
+    if (h->box_pending) HIPCHK(hipEventSynchronize(h->ev_boxes));
+    RoiBoxJob* jobs = reinterpret_cast<RoiBoxJob*>(h->h_box_stage.p);
+    gf_box* list = reinterpret_cast<gf_box*>(jobs + count);   // right behind the jobs of THIS call: one copy carries both
+    int total = 0;
+    for (int i = 0; i < count; i++) {
+        const std::vector<gf_box>& b = h->boxes[seq[i]];
+        jobs[i] = RoiBoxJob{seq[i], total, (int)b.size(), 0};
+        if (!b.empty()) memcpy(list + total, b.data(), b.size() * sizeof(gf_box));
+        total += (int)b.size();
+    }
+    const size_t bytes = (size_t)count * sizeof(RoiBoxJob) + (size_t)total * sizeof(gf_box);
+    HIPCHK(hipMemcpyAsync(h->d_box_stage.p, h->h_box_stage.p, bytes, hipMemcpyHostToDevice, h->stream));
+    const RoiBoxJob* d_jobs = reinterpret_cast<const RoiBoxJob*>(h->d_box_stage.p);
+    const int W = h->cfg.width, H = h->cfg.height;
+    roi_boxes_kernel<<<dim3((W + kRoiBoxSpan - 1) / kRoiBoxSpan, gfroi::bands(H), count), kRoiBoxPiece, 0, h->stream>>>(
+        d_jobs, reinterpret_cast<const gf_box*>(d_jobs + count), W, H, h->d_roi_base.p, h->d_roi.p, h->roi_words);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev_boxes, h->stream));
+    h->box_pending = true;
+    return GF_OK;
+}
+// The lists of a box setter, before anything is copied, launched or changed; the message names the list position.
+static int check_box_lists(gf_tracker* h, int count, const int* seq, const int* first, const gf_box* boxes) {
+    if (count < 0 || count > h->B) return set_err(GF_ERR_INVALID, "%d sequences listed for a handle of %d", count, h->B);
+    if (count > 0 && !seq) return set_err(GF_ERR_INVALID, "null sequence list");
+    h->listed.assign(h->B, 0);
+    for (int i = 0; i < count; i++) {
+        if (seq[i] < 0 || seq[i] >= h->B) return set_err(GF_ERR_INVALID, "list position %d names sequence %d of a handle of %d", i, seq[i], h->B);
+        if (h->listed[seq[i]]) return set_err(GF_ERR_INVALID, "list position %d names sequence %d a second time", i, seq[i]);
+        h->listed[seq[i]] = 1;
+    }
+    if (count == 0 || (!first && !boxes)) return GF_OK;
+    if (!first) return set_err(GF_ERR_INVALID, "boxes without the table of offsets `first` (list position 0)");
+    if (first[0] != 0) return set_err(GF_ERR_INVALID, "list position 0: first[0] is %d, not 0", first[0]);
+    for (int i = 0; i < count; i++) {
+        if (first[i + 1] < first[i]) return set_err(GF_ERR_INVALID, "list position %d (sequence %d): first decreases from %d to %d", i, seq[i], first[i], first[i + 1]);
+        if (first[i + 1] - first[i] > GF_MAX_BOXES_PER_SEQ)
+            return set_err(GF_ERR_INVALID, "list position %d (sequence %d): %d boxes > GF_MAX_BOXES_PER_SEQ = %d", i, seq[i], first[i + 1] - first[i], GF_MAX_BOXES_PER_SEQ);
+        if (!boxes && first[i + 1] > first[i]) return set_err(GF_ERR_INVALID, "list position %d (sequence %d): %d boxes listed but `boxes` is null", i, seq[i], first[i + 1] - first[i]);
+    }
     return GF_OK;
 }
 
@@ -629,7 +711,9 @@ static void book_after_lk(Call& c) {
         const LkRows r{row(h->h_cur_pts, b, cap), h->h_status.p + at, c.in.kernel_samples(h->h_depth_out, b, cap), h->h_counters.p + 2 * at, c.in.host_image(b, par), c.in.host_dstride};
         const uint32_t* roi = !h->roi_has.empty() && h->roi_has[q] ? h->roi_bits.data() + (size_t)q * h->roi_words : nullptr;
         int want = 0;
-        const LkTally n = after_lk(h->seq[q], par, h->cfg.width, h->cfg.height, h->seq_disk.empty() ? h->disk : h->seq_disk[q], roi, r, row(h->h_centers, b, cap), h->h_ncenters.p + b, &want);
+        const gf_box* boxes = h->boxes.empty() ? nullptr : h->boxes[q].data();
+        const LkTally n = after_lk(h->seq[q], par, h->cfg.width, h->cfg.height, h->seq_disk.empty() ? h->disk : h->seq_disk[q], roi, r, row(h->h_centers, b, cap), h->h_ncenters.p + b, &want,
+                                   boxes, boxes ? (int)h->boxes[q].size() : 0);
         a_levels += n.level_passes; a_iters += n.iterations; a_points += n.points; a_tracked += n.tracked;
         h->h_want.p[b] = want;
         if (h->h_seq_md.p) h->h_seq_md.p[b] = par.min_dist;
@@ -723,7 +807,7 @@ static int book_after_detect(Call& c, gf_feature_obs* out, int cap_out, int* n_o
         const int q = c.seq[b];
         const DetectRows r{row(h->h_out_pts, b, cap), c.in.kernel_samples(h->h_out_depth, b, cap), h->h_want.p[b] > 0 ? h->h_out_n.p[b] : 0, c.in.host_image(b, h->par[q]), c.in.host_dstride};
         const Packed p = after_detect(h->seq[q], h->par[q], r, have_depth, out + (size_t)b * cap_out, cap_out);
-        if (h->seq[q].show_track) (void)record_track(h->seq[q]);   // a refused list: the sequence has no picture of this frame, and keeps the reason (draw_why)
+        if (h->seq[q].show_track) (void)record_track(h->seq[q], h->boxes.empty() ? nullptr : h->boxes[q].data(), h->boxes.empty() ? 0 : (int)h->boxes[q].size());   // a refused list: the sequence has no picture of this frame, and keeps the reason (draw_why)
         if (p.overflow >= 0) a_overflow = p.overflow;
         n_out[b] = p.written;
         a_out += p.written;
@@ -746,6 +830,7 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
     if (int rc = redo_fallback(c)) return rc;
     book_after_lk(c);
     if (int rc = run_detect(c)) return rc;
+    h->box_pending = false;   // the stream is drained: a box setter's staging has been read
     if (h->profiling) if (int rc = read_profile(c)) return rc;
     if (c.any_want) if (int rc = check_candidates(c)) return rc;
     if (int rc = book_after_detect(c, out, cap_out, n_out)) return rc;
@@ -1025,7 +1110,7 @@ int gf_tracker_set_roi_some_device(gf_tracker* h, int count, const int* seq, con
     }
     const int W = h->cfg.width, H = h->cfg.height;
     HIPCHK(hipMemcpyAsync(h->d_roi_seq.p, seq, (size_t)count * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    gf::roi_pack_kernel<<<dim3((W + 255) / 256, gfroi::bands(H), count), 256, 0, h->stream>>>((const uint8_t*)d_masks, h->d_roi_seq.p, W, H, h->d_roi.p, h->roi_words);
+    gf::roi_pack_kernel<<<dim3((W + 255) / 256, gfroi::bands(H), count), 256, 0, h->stream>>>((const uint8_t*)d_masks, h->d_roi_seq.p, W, H, gf::roi_base_table(h), h->roi_words);
     HIPCHK(hipGetLastError());
     return gf::roi_packed(h, count, seq);
 }
@@ -1042,7 +1127,7 @@ int gf_tracker_set_roi_some_device_refs(gf_tracker* h, int count, const int* seq
     for (int i = 0; i < count; i++) h->h_refs.p[i] = masks[i];
     HIPCHK(hipMemcpyAsync(h->d_refs.p, h->h_refs.p, (size_t)count * sizeof(gf_frame_ref), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_roi_seq.p, seq, (size_t)count * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    gf::roi_pack_refs_kernel<<<dim3((W + 255) / 256, gfroi::bands(H), count), 256, 0, h->stream>>>(h->d_refs.p, h->d_roi_seq.p, W, H, h->d_roi.p, h->roi_words);
+    gf::roi_pack_refs_kernel<<<dim3((W + 255) / 256, gfroi::bands(H), count), 256, 0, h->stream>>>(h->d_refs.p, h->d_roi_seq.p, W, H, gf::roi_base_table(h), h->roi_words);
     HIPCHK(hipGetLastError());
     return gf::roi_packed(h, count, seq);
 }
@@ -1052,11 +1137,78 @@ int gf_tracker_get_roi(gf_tracker* h, int seq, uint8_t* mask, int stride, int* h
     if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
     const int W = h->cfg.width, H = h->cfg.height;
     if (mask && stride < W) return gf::set_err(GF_ERR_INVALID, "a mask stride of %d bytes is shorter than a row of %d pixels", stride, W);
-    *has = !h->roi_has.empty() && h->roi_has[seq] ? 1 : 0;
+    const bool base = !h->roi_has.empty() && h->roi_has[seq];
+    const int nb = h->boxes.empty() ? 0 : (int)h->boxes[seq].size();
+    *has = base || nb > 0 ? 1 : 0;
     if (!*has || !mask) return GF_OK;
-    const uint32_t* t = h->roi_bits.data() + (size_t)seq * h->roi_words;
+    const uint32_t* t = base ? h->roi_bits.data() + (size_t)seq * h->roi_words : nullptr;
+    const gf_box* bx = nb ? h->boxes[seq].data() : nullptr;
     for (int y = 0; y < H; y++)
-        for (int x = 0; x < W; x++) mask[(size_t)y * stride + x] = gfroi::allowed(t, W, x, y) ? 255 : 0;
+        for (int x = 0; x < W; x++) mask[(size_t)y * stride + x] = gfroi::allowed(t, bx, nb, W, x, y) ? 255 : 0;
+    return GF_OK;
+}
+
+// ---- exclusion boxes (gf_roi.hpp): trackImagebox's boxes (feature_tracker.cpp:374, :565-599) as part of the region in force
+int gf_tracker_set_boxes_some(gf_tracker* h, int count, const int* seq, const int* first, const gf_box* boxes) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (int rc = gf::check_box_lists(h, count, seq, first, boxes)) return rc;
+    if (count == 0) return GF_OK;
+    if (!h->d_roi_base.p && (!first || first[count] == 0)) return GF_OK;   // nothing to clear: the handle stays one that never had boxes
+    if (int rc = gf::boxes_ready(h)) return rc;
+    for (int i = 0; i < count; i++) {
+        if (first) h->boxes[seq[i]].assign(boxes + first[i], boxes + first[i + 1]);
+        else h->boxes[seq[i]].clear();
+    }
+    return gf::boxes_compose(h, count, seq);
+}
+
+int gf_tracker_get_boxes(gf_tracker* h, int seq, gf_box* boxes, int cap, int* n) {
+    if (!h || !n) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    if (cap < 0 || (cap > 0 && !boxes)) return gf::set_err(GF_ERR_INVALID, "room for %d boxes at a null pointer", cap);
+    *n = h->boxes.empty() ? 0 : (int)h->boxes[seq].size();
+    for (int i = 0; i < *n && i < cap; i++) boxes[i] = h->boxes[seq][i];
+    return GF_OK;
+}
+
+int gf_roi_boxes_batch(int batch, int width, int height, const int* first, const gf_box* boxes, const uint8_t* base_masks, uint8_t* out_masks) {
+    if (batch < 1 || batch > 65535 || width < 1 || height < 1 || !first || !out_masks) return gf::set_err(GF_ERR_INVALID, "bad argument");
+    if (first[0] != 0) return gf::set_err(GF_ERR_INVALID, "first[0] is %d, not 0", first[0]);
+    for (int b = 0; b < batch; b++) {
+        if (first[b + 1] < first[b]) return gf::set_err(GF_ERR_INVALID, "frame %d: first decreases from %d to %d", b, first[b], first[b + 1]);
+        if (first[b + 1] - first[b] > GF_MAX_BOXES_PER_SEQ) return gf::set_err(GF_ERR_INVALID, "frame %d: %d boxes > GF_MAX_BOXES_PER_SEQ = %d", b, first[b + 1] - first[b], GF_MAX_BOXES_PER_SEQ);
+    }
+    const int total = first[batch];
+    if (total > 0 && !boxes) return gf::set_err(GF_ERR_INVALID, "%d boxes listed but `boxes` is null", total);
+    if (int rc = gf::require_device()) return rc;
+    const size_t words = gfroi::words(width, height), px = (size_t)width * height;
+    gf::DevBuf<uint32_t> d_base, d_out; gf::DevBuf<uint8_t> d_masks, d_stage; gf::DevBuf<int> d_ident;
+    HIPCHK(d_out.fit((size_t)batch * words));
+    std::vector<gf::RoiBoxJob> jobs(batch);
+    for (int b = 0; b < batch; b++) jobs[b] = gf::RoiBoxJob{b, first[b], first[b + 1] - first[b], 0};
+    const size_t job_bytes = (size_t)batch * sizeof(gf::RoiBoxJob);
+    HIPCHK(d_stage.fit(job_bytes + (size_t)std::max(total, 1) * sizeof(gf_box)));
+    HIPCHK(hipMemcpy(d_stage.p, jobs.data(), job_bytes, hipMemcpyHostToDevice));
+    if (total > 0) HIPCHK(hipMemcpy(d_stage.p + job_bytes, boxes, (size_t)total * sizeof(gf_box), hipMemcpyHostToDevice));
+    if (base_masks) {   // the base words by the tracker's packing kernel
+        std::vector<int> ident(batch);
+        for (int b = 0; b < batch; b++) ident[b] = b;
+        HIPCHK(d_base.fit((size_t)batch * words)); HIPCHK(d_masks.fit((size_t)batch * px)); HIPCHK(d_ident.fit(batch));
+        HIPCHK(hipMemcpy(d_masks.p, base_masks, (size_t)batch * px, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_ident.p, ident.data(), (size_t)batch * sizeof(int), hipMemcpyHostToDevice));
+        gf::roi_pack_kernel<<<dim3((width + 255) / 256, gfroi::bands(height), batch), 256>>>(d_masks.p, d_ident.p, width, height, d_base.p, words);
+        HIPCHK(hipGetLastError());
+    }
+    const gf::RoiBoxJob* d_jobs = reinterpret_cast<const gf::RoiBoxJob*>(d_stage.p);
+    gf::roi_boxes_kernel<<<dim3((width + gf::kRoiBoxSpan - 1) / gf::kRoiBoxSpan, gfroi::bands(height), batch), gf::kRoiBoxPiece>>>(
+        d_jobs, reinterpret_cast<const gf_box*>(d_jobs + batch), width, height, d_base.p, d_out.p, words);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<uint32_t> table((size_t)batch * words);
+    HIPCHK(hipMemcpy(table.data(), d_out.p, table.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int b = 0; b < batch; b++)
+        for (int y = 0; y < height; y++)
+            for (int x = 0; x < width; x++) out_masks[(size_t)b * px + (size_t)y * width + x] = gfroi::allowed(table.data() + (size_t)b * words, width, x, y) ? 255 : 0;
     return GF_OK;
 }
 
@@ -1122,7 +1274,7 @@ int gf_tracker_set_show_track(gf_tracker* h, int count, const int* seq, int on) 
     if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
     if (int rc = gf::check_list(h, count, seq)) return rc;
     if (on && count > 0 && !h->d_draw_prims.p) {   // the first switch of the handle that goes on
-        const size_t row = gfdraw::list_capacity(h->cap);
+        const size_t row = gfdraw::list_capacity(h->cap) + (h->d_roi_base.p ? (size_t)GF_MAX_BOXES_PER_SEQ : 0);   // draw_room(), defined below
         gf::DevBuf<gfdraw::Prim> dp; gf::PinBuf<gfdraw::Prim> hp; gf::DevBuf<gfdraw::DrawJob> dj; gf::PinBuf<gfdraw::DrawJob> hj;
         HIPCHK(dp.alloc((size_t)h->B * row)); HIPCHK(hp.alloc((size_t)h->B * row)); HIPCHK(dj.alloc(h->B)); HIPCHK(hj.alloc(h->B));
         h->d_draw_prims = std::move(dp); h->h_draw_prims = std::move(hp); h->d_draw_jobs = std::move(dj); h->h_draw_jobs = std::move(hj);
@@ -1136,11 +1288,13 @@ int gf_tracker_set_show_track(gf_tracker* h, int count, const int* seq, int on) 
 }
 
 namespace gf {
+// the primitives a sequence's row of d_draw_prims holds: a frame's dots and strokes, and on a handle that has boxes their frames
+static size_t draw_room(const gf_tracker* h) { return gfdraw::list_capacity(h->cap) + (h->d_roi_base.p ? (size_t)GF_MAX_BOXES_PER_SEQ : 0); }
 // everything a picture call refuses, before anything is copied or launched.  dst[i].data is only asked whether it is null.
 static int draw_check(gf_tracker* h, int count, const int* seq, const gf_frame_ref* dst) {
     if (int rc = check_list(h, count, seq)) return rc;
     if (count > 0 && !dst) return set_err(GF_ERR_INVALID, "null table of destinations");
-    const size_t row_bytes = 3 * (size_t)h->cfg.width, room = gfdraw::list_capacity(h->cap);
+    const size_t row_bytes = 3 * (size_t)h->cfg.width, room = draw_room(h);
     for (int i = 0; i < count; i++) {
         const SeqState& s = h->seq[seq[i]];
         if (!s.show_track) return set_err(GF_ERR_INVALID, "list position %d (sequence %d): show_track is off (gf_tracker_set_show_track)", i, seq[i]);
@@ -1155,7 +1309,7 @@ static int draw_check(gf_tracker* h, int count, const int* seq, const gf_frame_r
 }
 // the checked call: lists that are new since the sequence's last picture go down, then the jobs, one launch, and the host waits
 static int draw_run(gf_tracker* h, int count, const int* seq, const gf_frame_ref* dst) {
-    const size_t room = gfdraw::list_capacity(h->cap);
+    const size_t room = draw_room(h);
     const LevelGeom g0 = h->G.lv[0];
     for (int i = 0; i < count; i++) {
         const int q = seq[i];

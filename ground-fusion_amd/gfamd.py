@@ -85,6 +85,46 @@ class TrackerStats(C.Structure):
                 ("sequence_frames", C.c_longlong)]
 
 
+class Box(C.Structure):
+    """gf_box: the four integers of a darknet_ros_msgs/BoundingBox"""
+    _fields_ = [("xmin", C.c_int32), ("ymin", C.c_int32), ("xmax", C.c_int32), ("ymax", C.c_int32)]
+
+
+MAX_BOXES_PER_SEQ = 256   # GF_MAX_BOXES_PER_SEQ
+assert C.sizeof(Box) == 16
+
+
+def _boxes(boxes):
+    """[n, 4] int32 rows of xmin, ymin, xmax, ymax from anything array-like (an empty list: no boxes)"""
+    a = np.ascontiguousarray(boxes if boxes is not None else [], np.int64).reshape(-1, 4)
+    if a.size and (a.min() < -2 ** 31 or a.max() > 2 ** 31 - 1):
+        raise ValueError("a box coordinate is no int32")
+    return np.ascontiguousarray(a, np.int32)
+
+
+def _box_lists(lists):
+    """(first [len + 1] int32, boxes [total, 4] int32) of a list of box lists"""
+    rows = [_boxes(l) for l in lists]
+    first = np.zeros(len(rows) + 1, np.int32)
+    first[1:] = np.cumsum([len(r) for r in rows])
+    return first, np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 4)), np.int32).reshape(-1, 4)
+
+
+def roi_boxes_batch(lists, width, height, base_masks=None):
+    """gf_roi_boxes_batch: the region the box lists leave, by the tracker's kernels -- lists[b] = boxes (xmin, ymin, xmax, ymax) of frame b, base_masks None or
+    [batch, height, width] u8 (non-zero = allowed) -> [batch, height, width] u8 of 0 / 255"""
+    first, flat = _box_lists(lists)
+    b = len(lists)
+    if base_masks is not None:
+        base_masks = np.ascontiguousarray(base_masks, np.uint8)
+        if base_masks.shape != (b, height, width):
+            raise ValueError("roi_boxes_batch: base_masks must be [batch, height, width]")
+    out = np.zeros((b, height, width), np.uint8)
+    _chk(lib().gf_roi_boxes_batch(b, width, height, _p(first, C.c_int), flat.ctypes.data_as(C.POINTER(Box)) if len(flat) else None,
+                                  None if base_masks is None else _p(base_masks, C.c_uint8), _p(out, C.c_uint8)))
+    return out
+
+
 OBS_DTYPE = np.dtype([("id", np.int32), ("camera_id", np.int32), ("v", np.float64, (8,))])
 assert OBS_DTYPE.itemsize == C.sizeof(FeatureObs)
 
@@ -96,7 +136,8 @@ EXPORTS = ["gf_last_error", "gf_device_count", "gf_set_device", "gf_tracker_crea
            "gf_tracker_get_state", "gf_tracker_set_profiling", "gf_tracker_get_stats", "gf_tracker_reset_stats", "gf_lk_track",
            "gf_good_features", "gf_min_eigen_val", "gf_pyramid_level", "gf_clahe_batch", "gf_clahe_batch_device", "gf_cvt_gray_batch", "gf_cvt_gray_batch_device",
            "gf_tracker_set_show_track", "gf_tracker_track_image_some_device", "gf_tracker_track_image", "gf_draw_track_batch",
-           "gf_estimator_set_show_track", "gf_estimator_get_track_image", "gf_show_track_from_yaml"]
+           "gf_estimator_set_show_track", "gf_estimator_get_track_image", "gf_show_track_from_yaml",
+           "gf_tracker_set_boxes_some", "gf_tracker_get_boxes", "gf_roi_boxes_batch", "gf_estimator_set_boxes", "gf_draw_track_boxes_batch"]
 
 
 def lib():
@@ -368,6 +409,28 @@ class FeatureTracker:
         _chk(lib().gf_tracker_get_roi(self.h, seq, _p(mask, C.c_uint8), self.cfg.width, C.byref(has)))
         return mask if has.value else None
 
+    def set_boxes(self, boxes, seq=0):
+        """gf_tracker_set_boxes_some for one sequence: its exclusion boxes (rows of xmin, ymin, xmax, ymax) from its next frame on; None or an empty list clears"""
+        self.set_boxes_some([seq], [boxes])
+
+    def set_boxes_some(self, seqs, lists):
+        """gf_tracker_set_boxes_some: lists[i] = the boxes of sequence seqs[i] (an empty one clears it); lists=None clears every listed sequence.  The region in
+        force is the region of set_roi minus the boxes; no synchronisation, the composition runs on the handle's stream ahead of the next frame."""
+        seqs, N = self._seqs(seqs)
+        if lists is None:
+            _chk(lib().gf_tracker_set_boxes_some(self.h, N, _p(seqs, C.c_int), None, None))
+            return
+        assert len(lists) == N
+        first, flat = _box_lists(lists)
+        _chk(lib().gf_tracker_set_boxes_some(self.h, N, _p(seqs, C.c_int), _p(first, C.c_int), flat.ctypes.data_as(C.POINTER(Box)) if len(flat) else None))
+
+    def get_boxes(self, seq=0):
+        """gf_tracker_get_boxes: the boxes in force for sequence `seq`, [n, 4] int32"""
+        out = np.zeros((MAX_BOXES_PER_SEQ, 4), np.int32)
+        n = C.c_int(0)
+        _chk(lib().gf_tracker_get_boxes(self.h, seq, out.ctypes.data_as(C.POINTER(Box)), MAX_BOXES_PER_SEQ, C.byref(n)))
+        return out[:n.value].copy()
+
     def set_seq_cfg(self, seq, **fields):
         """gf_tracker_set_seq_cfg: sequence `seq` gets parameters of its own -- any of max_cnt, min_dist, flow_back, depth_cam, fx, fy, cx, cy, k1, k2, p1, p2; the
         fields that are not named keep the value in force.  Without fields: back to the handle's cfg.  Refused (GfError) once the sequence has taken a frame,
@@ -434,12 +497,13 @@ class FeatureTracker:
         _chk(lib().gf_tracker_reset_stats(self.h))
 
 
-def draw_track(gray, lists, dst=None):
+def draw_track(gray, lists, dst=None, boxes=None):
     """gf_draw_track_batch: drawTrack (feature_tracker.cpp:849-905) on host frames with the tracker's kernel.  gray: [h, w] or [batch, h, w] u8 (rows may be
     padded: a view of a wider array whose frames lie h rows apart).  lists: per frame (cur [n, 2], track_cnt [n], prev [n, 2] or None, has_prev [n] or None).
     dst: None -> returns new [batch, h, w, 3] pictures ([h, w, 3] for one frame without a batch axis); or a u8 [batch, h, >= 3 w] array whose rows lie one
     pitch >= 3 w apart and whose frames lie h rows apart, starting at any address (a view into a larger buffer, a crop of a wider image), which is written in
-    place -- 3 w bytes per row -- and returned.  Neither array is touched behind the last pixel of its last row."""
+    place -- 3 w bytes per row -- and returned.  Neither array is touched behind the last pixel of its last row.
+    boxes: None, or per frame a list of boxes whose frames are drawn over the dots and strokes (gf_draw_track_boxes_batch; drawTrackbox, :960-975)."""
     a = np.asarray(gray)
     single = a.ndim == 2
     if single:
@@ -465,8 +529,19 @@ def draw_track(gray, lists, dst=None):
     pitch = out.strides[1] if out.ndim == 3 else 0
     if out.dtype != np.uint8 or out.ndim != 3 or out.shape[:2] != (b, h) or out.shape[2] < 3 * w or out.strides[2] != 1 or pitch < 3 * w or (b > 1 and out.strides[0] != h * pitch):
         raise ValueError("draw_track: dst must be u8 [batch, h, >= 3 w] with rows of one pitch >= 3 w and frames h rows apart")
-    _chk(lib().gf_draw_track_batch(C.c_void_p(a.ctypes.data), C.c_size_t(a.strides[1]), b, w, h, _p(n, C.c_int), _p(cur, C.c_float), _p(cnt, C.c_int),
-                                   _p(prev, C.c_float), _p(has, C.c_uint8), cap, C.c_void_p(out.ctypes.data), C.c_size_t(pitch)))
+    args = (C.c_void_p(a.ctypes.data), C.c_size_t(a.strides[1]), b, w, h, _p(n, C.c_int), _p(cur, C.c_float), _p(cnt, C.c_int),
+            _p(prev, C.c_float), _p(has, C.c_uint8), cap, C.c_void_p(out.ctypes.data), C.c_size_t(pitch))
+    if boxes is None:
+        _chk(lib().gf_draw_track_batch(*args))
+    else:   # gf_draw_track_boxes_batch: the frames of boxes[k] (rows of xmin, ymin, xmax, ymax) over frame k's dots and strokes
+        rows = [_boxes(l) for l in ([boxes] if single else boxes)]
+        assert len(rows) == b
+        box_cap = max([len(r) for r in rows] + [1])
+        nb = np.array([len(r) for r in rows], np.int32)
+        table = np.zeros((b, box_cap, 4), np.int32)
+        for k, r in enumerate(rows):
+            table[k, :len(r)] = r
+        _chk(lib().gf_draw_track_boxes_batch(*args, _p(nb, C.c_int), table.ctypes.data_as(C.POINTER(Box)), box_cap))
     if dst is not None:
         return dst
     out = out.reshape(b, h, w, 3)
@@ -1022,6 +1097,11 @@ class SlidingWindowEstimator:
             return
         mask = np.ascontiguousarray(mask, np.uint8)
         _chk(lib().gf_estimator_set_roi(self.h, _p(mask, C.c_uint8), mask.shape[1]))
+
+    def set_boxes(self, boxes):
+        """gf_estimator_set_boxes: the exclusion boxes of the estimator's own tracker (rows of xmin, ymin, xmax, ymax; None or an empty list clears)"""
+        b = _boxes(boxes)
+        _chk(lib().gf_estimator_set_boxes(self.h, b.ctypes.data_as(C.POINTER(Box)) if len(b) else None, len(b)))
 
     def set_show_track(self, on=True):
         """gf_estimator_set_show_track: SHOW_TRACK of the estimator's own tracker"""

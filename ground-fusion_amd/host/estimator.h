@@ -144,6 +144,8 @@ class Estimator {
     // the region of interest of the estimator's own tracker (FeatureTracker::setRegionOfInterest, gf_estimator_set_roi): rows x cols bytes of cfg.tracker's frame
     // size, non-zero = allowed, nullptr clears; from the next inputImage on
     void setRegionOfInterest(const uint8_t* mask, int stride) { need(); check(gf_estimator_set_roi(h_, mask, stride)); }
+    // the exclusion boxes of the estimator's own tracker for the next frames (FeatureTracker::setBoxes, gf_estimator_set_boxes); n == 0 clears
+    void setBoxes(const gf_box* boxes, int n) { need(); check(gf_estimator_set_boxes(h_, boxes, n)); }
     // SHOW_TRACK and getTrackImage of the estimator's own tracker (FeatureTracker::setShowTrack / getTrackImage; gf_estimator_set_show_track,
     // gf_estimator_get_track_image): the picture of the last inputImage, rows x cols x 3 bytes (bgr8)
     void setShowTrack(bool on) { need(); check(gf_estimator_set_show_track(h_, on ? 1 : 0)); }

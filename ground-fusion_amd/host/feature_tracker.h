@@ -108,6 +108,15 @@ class FeatureTracker {
         }
         check(gf_tracker_set_roi(h_, 0, mask, stride));
     }
+    // The exclusion boxes of the next frames: what trackImagebox (feature_tracker.cpp:374) takes as darknet's BoundingBoxes, here part of the region setMask()
+    // starts from (gf_tracker_set_boxes_some): tracks that end up inside a box are dropped, corners are sought outside.  They hold until replaced; n == 0
+    // clears.  Any time; before the first frame they are kept until the handle exists.
+    void setBoxes(const gf_box* boxes, int n) {
+        if (n < 0 || n > GF_MAX_BOXES_PER_SEQ || (n > 0 && !boxes)) throw std::runtime_error("setBoxes: 0 .. GF_MAX_BOXES_PER_SEQ boxes");
+        if (!h_) { boxes_.assign(boxes, boxes + n); return; }
+        const int seq = 0, first[2] = {0, n};
+        check(gf_tracker_set_boxes_some(h_, 1, &seq, first, boxes));
+    }
 #ifdef GF_WITH_OPENCV
     void setRegionOfInterest(const cv::Mat& mask) {   // CV_8UC1 of the frame size; an empty Mat clears
         if (mask.empty()) { setRegionOfInterest(nullptr, 0); return; }
@@ -211,6 +220,7 @@ class FeatureTracker {
     bool equalize_ = false, show_track_ = false;
     int pixel_format_ = GF_PIX_MONO8;
     std::vector<uint8_t> roi_;   // a region of interest set before the handle exists (tight rows)
+    std::vector<gf_box> boxes_;  // exclusion boxes set before the handle exists
     static void check(int rc) { if (rc != GF_OK) throw std::runtime_error(std::string("groundfusion_hip: ") + gf_last_error()); }
     void create(int w, int h) {
         gf_tracker_cfg c{};
@@ -221,6 +231,7 @@ class FeatureTracker {
         row = c.height; col = c.width;
         check(gf_tracker_create(&c, &h_));
         if (!roi_.empty()) { check(gf_tracker_set_roi(h_, 0, roi_.data(), col)); roi_.clear(); }
+        if (!boxes_.empty()) { const std::vector<gf_box> b = std::move(boxes_); boxes_.clear(); setBoxes(b.data(), (int)b.size()); }
         if (show_track_) setShowTrack(true);
     }
     void refresh() {

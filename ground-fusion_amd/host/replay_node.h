@@ -50,6 +50,8 @@ template <class Est> class ReplayNode {
     // called after every inputImage with the frame's index (0, 1, ..) and its time: where pubTrackImage sits in the node (rosNodeTest.cpp sync_process ->
     // estimator.inputImage -> visualization.cpp:155-162).  gf_replay --track-images writes the estimator's getTrackImage from it.
     std::function<void(long, double)> after_image;
+    // called before every inputImage, with the same two: where the node would hand trackImagebox the detector's boxes for the frame (gf_replay --boxes)
+    std::function<void(long, double)> before_image;
 
     explicit ReplayNode(Est& e) : estimator(e) {}
 
@@ -102,6 +104,7 @@ template <class Est> class ReplayNode {
             if (gw_ != dw_ || gh_ != dh_) throw std::runtime_error("replay: gray and depth frames differ in size");
             GrayImage g; g.data = gray_.data(); g.rows = gh_; g.cols = gw_; g.stride = gstep_; g.pixel_format = gfmt_;
             DepthImage d; d.data = (const uint16_t*)depth_.data(); d.rows = dh_; d.cols = dw_; d.stride = dw_;
+            if (before_image) before_image(n_pairs, time);
             estimator.inputImage(time, g, d);
             if (after_image) after_image(n_pairs, time);
             n_pairs++;

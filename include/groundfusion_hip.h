@@ -205,8 +205,40 @@ int gf_tracker_set_roi_some_device(gf_tracker* h, int count, const int* seq, con
  * masks == NULL clears the listed sequences.  Refusals as above plus a null data pointer or a pitch shorter than a row (the message names the list position);
  * leaves the bits of the tight setter. */
 int gf_tracker_set_roi_some_device_refs(gf_tracker* h, int count, const int* seq, const gf_frame_ref* masks);
-/* *has = whether the sequence has a region; if so and mask != NULL, the stored region as 0 / 255 bytes, rows `stride` bytes apart (>= width) */
+/* *has = whether the sequence has a region in force -- a base region R or a non-empty list of exclusion boxes (below); if so and mask != NULL, that region
+ * (R_eff) as 0 / 255 bytes, rows `stride` bytes apart (>= width).  For a sequence without boxes: the stored R, as ever. */
 int gf_tracker_get_roi(gf_tracker* h, int seq, uint8_t* mask, int stride, int* has);
+/* Exclusion boxes: dynamic objects per sequence and frame, from a detector that runs beside the tracker.  The reference takes darknet_ros_msgs/BoundingBoxes in
+ * trackImagebox (feature_tracker.cpp:374), withholds the features strictly inside a rectangle (:565-599, pointPolygonTest(...) > 0) and draws the rectangles
+ * (drawTrackbox, :960-975).  Here a box feeds the region of interest: the region in force of a sequence is
+ *     R_eff = R_base AND NOT union(boxes),
+ * R_base the region of gf_tracker_set_roi* (all allowed if none is set), a box excluding the pixels xmin <= x <= xmax && ymin <= y <= ymax of the frame.  Every
+ * float position strictly inside the rectangle rounds to a pixel of that closed box, so every feature the reference would withhold is excluded -- in setMask's
+ * walk, on its rounded pixel, as with any region (points 1-3 above with R = R_eff).  Any int32_t is accepted, INT32_MIN and INT32_MAX included; a box is clipped
+ * to the frame before any arithmetic; one with xmin > xmax or ymin > ymax excludes nothing.  The boxes belong to the SEQUENCE like R: they hold from the next
+ * frame the sequence is given until they are replaced or cleared, through every entry point; gf_tracker_reset_seq keeps them; a base setter leaves them in force
+ * over the new base, clearing them restores the base bits.  A handle that never sets boxes allocates, copies and launches exactly what it did without them; the
+ * first box setter of a handle allocates a second table (the base words, apart from the words the detector reads) and page-locked staging. */
+typedef struct gf_box { int32_t xmin, ymin, xmax, ymax; } gf_box;   /* the four integers of a darknet_ros_msgs/BoundingBox */
+typedef char gf_box_is_16_bytes[sizeof(gf_box) == 16 ? 1 : -1];      /* tables of boxes cross the boundary as they lie */
+#define GF_MAX_BOXES_PER_SEQ 256   /* a longer list of one sequence is refused */
+/* The boxes of the `count` listed sequences for their next frames (trackImagebox's `boxes`, feature_tracker.cpp:374; the filter of :565-599 as a region; what
+ * drawTrackbox, :960-975, would draw): those of seq[i] are boxes[first[i] .. first[i + 1]), first = count + 1 offsets.  An empty range clears that sequence;
+ * boxes == NULL with first == NULL clears all listed sequences; sequences that are not listed keep what they had.  The boxes are copied into page-locked staging
+ * of the handle, and the copy and ONE kernel launch for the whole list (each listed sequence's words of R_eff into the table the detector reads) are ordered on
+ * the handle's stream ahead of the next track call: no stream synchronisation, no device-to-host copy.  (A second box or base setter before the next track call
+ * waits for the first one's kernel, whose staging it reuses.)  Refused with GF_ERR_INVALID, the message naming the list position, and nothing changed: a null
+ * handle, count < 0 or > batch, a sequence out of range or named twice, first[0] != 0 or a decreasing first, a range longer than GF_MAX_BOXES_PER_SEQ,
+ * boxes == NULL with a non-empty range, exactly one of first and boxes NULL with count > 0. */
+int gf_tracker_set_boxes_some(gf_tracker* h, int count, const int* seq, const int* first, const gf_box* boxes);
+/* the boxes in force for seq (trackImagebox's list, feature_tracker.cpp:374, :565-599, :960-975): *n of them, the first min(*n, cap) into boxes (may be NULL
+ * with cap == 0) */
+int gf_tracker_get_boxes(gf_tracker* h, int seq, gf_box* boxes, int cap, int* n);
+/* The composition as a building block on host buffers (copies in, runs the tracker's packing and composing kernels, copies out; synchronous) -- the region
+ * trackImagebox's filter (feature_tracker.cpp:374, :565-599; the rectangles of :960-975) leaves, for `batch` frames of height x width, any width >= 1 and
+ * height >= 1: the boxes of frame b are boxes[first[b] .. first[b + 1]), each list at most GF_MAX_BOXES_PER_SEQ long; base_masks is NULL (all allowed) or `batch`
+ * tight height x width byte images back to back (non-zero = allowed); out_masks: `batch` tight images of 0 / 255. */
+int gf_roi_boxes_batch(int batch, int width, int height, const int* first, const gf_box* boxes, const uint8_t* base_masks, uint8_t* out_masks);
 /* Parameters per sequence: what the reference keeps per FeatureTracker object (MAX_CNT, MIN_DIST, FLOW_BACK, depth_cam, m_camera; feature_tracker.h:76-98).
  * A sequence that was never set runs with the handle's gf_tracker_cfg, every result as without these calls, bit for bit.  With its parameters set, a tracker
  * call for that sequence is FeatureTracker::trackImage of an object constructed with them: setMask's circles and goodFeaturesToTrack's minimum distance use its
@@ -267,6 +299,18 @@ int gf_tracker_track_image(gf_tracker* h, int seq, uint8_t* dst, int stride);
  * 2^20 in magnitude, short pitches, n[b] > cap.  GF_ERR_HIP if a byte next to the device copy of dst was written. */
 int gf_draw_track_batch(const uint8_t* gray, size_t gray_pitch, int batch, int width, int height, const int* n, const float* cur_xy, const int* track_cnt,
                         const float* prev_xy, const uint8_t* has_prev, int cap, uint8_t* dst, size_t dst_pitch);
+/* drawTrackbox's rectangles (feature_tracker.cpp:960-975; the boxes of trackImagebox, :374, whose filter is :565-599) over drawTrack's picture:
+ * `cv::rectangle(imTrack, Rect(xmin, ymin, xmax - xmin, ymax - ymin), Scalar(0, 128, 255), 5)` after the arrows, as one frame primitive per box behind all dots
+ * and strokes of the list.  In exact integers: nothing is drawn unless xmax > xmin && ymax > ymin; with X0 = xmin, X1 = xmax - 1, Y0 = ymin, Y1 = ymax - 1 a
+ * pixel belongs to the frame iff X0 - 2 <= x <= X1 + 2 and Y0 - 2 <= y <= Y1 + 2 and not (X0 + 2 < x < X1 - 2 and Y0 + 2 < y < Y1 - 2); its bytes are
+ * (0, 128, 255) whatever dots and strokes lie under it.  Only the rounded outer corners of OpenCV's thick rectangle can differ.  A tracker sequence with
+ * show_track on and boxes in force records them with each frame, so gf_tracker_track_image* shows the boxes that frame was tracked under; drawTrackbox's yellow
+ * dots for features inside a box (:982-987) have no counterpart, since no kept feature lies inside one.
+ * gf_draw_track_boxes_batch: gf_draw_track_batch with, for frame b, the n_boxes[b] <= box_cap boxes of row b of the [batch][box_cap] table `boxes` (any int32_t
+ * coordinates; clamped to +-2^20, which moves no pixel of an image). */
+int gf_draw_track_boxes_batch(const uint8_t* gray, size_t gray_pitch, int batch, int width, int height, const int* n, const float* cur_xy, const int* track_cnt,
+                              const float* prev_xy, const uint8_t* has_prev, int cap, uint8_t* dst, size_t dst_pitch, const int* n_boxes, const gf_box* boxes,
+                              int box_cap);
 /* FeatureTracker::removeOutliers (feature_tracker.cpp:1029-1045) */
 int gf_tracker_remove_outliers(gf_tracker* h, int seq, const int* ids, int n);
 /* public members ids / track_cnt / prev_pts (feature_tracker.h:85-88) */
@@ -635,6 +679,10 @@ int gf_estimator_get_state(gf_estimator* h, double* Ps, double* Rs, double* Vs, 
  * bytes of the tracker's frame size, rows `stride` bytes apart, non-zero = allowed, NULL clears; it holds from the next gf_estimator_input_image on.
  * GF_ERR_INVALID without a tracker, and as gf_tracker_set_roi refuses. */
 int gf_estimator_set_roi(gf_estimator* h, const uint8_t* mask, int stride);
+/* The exclusion boxes of an estimator that owns its tracker: gf_tracker_set_boxes_some on that tracker's one sequence (trackImagebox's boxes,
+ * feature_tracker.cpp:374, :565-599, :960-975), in force from the next gf_estimator_input_image until replaced; n == 0 clears.  GF_ERR_INVALID without a
+ * tracker, and as gf_tracker_set_boxes_some refuses. */
+int gf_estimator_set_boxes(gf_estimator* h, const gf_box* boxes, int n);
 /* SHOW_TRACK and getTrackImage (feature_tracker.cpp:849-905, :1047) of an estimator that owns its tracker: gf_tracker_set_show_track / gf_tracker_track_image
  * on that tracker's one sequence -- the picture of the last gf_estimator_input_image, height x width x 3 bytes, rows `stride` bytes apart.  GF_ERR_INVALID
  * without a tracker, and as those calls refuse. */

@@ -9,6 +9,10 @@
 //                                                                   encoding: colour, Bayer, yuv422, mono16) and cv_bridge::toCvCopy(msg, MONO8) (rosNodeTest.cpp:238-254) runs on the device; same vio.txt
 //   --roi <mask.pgm>                                                with any single-process form: a region of interest for the tracker (8-bit PGM of the configured
 //                                                                   frame size, non-zero = allowed; gf_estimator_set_roi).  No YAML key: the reference has none
+//   --boxes <file>                                                  with any single-process form: exclusion boxes per camera frame, what a detector beside the
+//                                                                   tracker would hand over (trackImagebox, feature_tracker.cpp:374; gf_estimator_set_boxes).  Text
+//                                                                   lines `<t> <xmin> <ymin> <xmax> <ymax>`, sorted by time; the boxes in force for the camera frame
+//                                                                   stamped t are the lines with exactly that time, a frame without lines has none
 //   --track-images <dir>                                            with any single-process form: SHOW_TRACK on, and FeatureTracker::getTrackImage() of every
 //                                                                   camera frame -- what the node publishes as image_track (feature_tracker.cpp:849-905, :1047) -- as
 //                                                                   <dir>/<frame index, six digits>.ppm (binary PPM, so R, G, B: the picture's bgr8 bytes reversed).
@@ -57,6 +61,39 @@ static void set_roi_from_pgm(gf::Estimator& estimator, const std::string& path) 
     estimator.setRegionOfInterest(mask.data(), w);
 }
 
+// --boxes: the file's lines, in order.  Refused with the line number: a line that is not a time and four int32, and a time smaller than the line's before.
+struct TimedBox { double t; gf_box box; };
+static std::vector<TimedBox> read_boxes_file(const std::string& path) {
+    std::ifstream in(path);
+    if (!in) throw std::runtime_error("--boxes: cannot read " + path);
+    std::vector<TimedBox> out;
+    std::string line;
+    for (long no = 1; std::getline(in, line); no++) {
+        if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+        const auto bad = [&](const char* why) { return std::runtime_error("--boxes: " + path + " line " + std::to_string(no) + ": " + why + " (a line is <t> <xmin> <ymin> <xmax> <ymax>)"); };
+        const char* p = line.c_str();
+        char* end = nullptr;
+        TimedBox b{};
+        b.t = strtod(p, &end);
+        if (end == p || !std::isfinite(b.t)) throw bad("no time stamp");
+        int32_t* v[4] = {&b.box.xmin, &b.box.ymin, &b.box.xmax, &b.box.ymax};
+        for (int k = 0; k < 4; k++) {
+            p = end;
+            const long long c = strtoll(p, &end, 10);
+            if (end == p) throw bad("fewer than four coordinates");
+            if (c < INT32_MIN || c > INT32_MAX) throw bad("a coordinate is no int32");
+            *v[k] = (int32_t)c;
+        }
+        if (std::string(end).find_first_not_of(" \t\r") != std::string::npos) throw bad("something follows the fourth coordinate");
+        if (!out.empty() && b.t < out.back().t) throw bad("its time is smaller than the line's before: the file is sorted by time");
+        size_t same = 1;
+        for (size_t i = out.size(); i > 0 && out[i - 1].t == b.t; i--) same++;
+        if (same > (size_t)GF_MAX_BOXES_PER_SEQ) throw bad("more than GF_MAX_BOXES_PER_SEQ boxes for one time stamp");
+        out.push_back(b);
+    }
+    return out;
+}
+
 // --track-images: one frame's picture as a binary PPM
 static void write_track_ppm(gf::Estimator& estimator, const std::string& dir, long frame) {
     static std::vector<uint8_t> store, rgb;
@@ -74,7 +111,7 @@ static void write_track_ppm(gf::Estimator& estimator, const std::string& dir, lo
 }
 
 static void replay_one(const char* config, const std::string& source, bool from_bag, const std::string& out, gf::Estimator& estimator, bool quiet, bool device_gray = false,
-                       const std::string& roi = std::string(), const std::string& track_images = std::string()) {
+                       const std::string& roi = std::string(), const std::string& track_images = std::string(), const std::vector<TimedBox>* boxes = nullptr) {
     estimator.readParameters(config);
     if (device_gray) {   // the tracker is created for the encoding of the colour topic: one handle has one format
         const int fmt = gf::ReplayNode<gf::Estimator>::bag_image_format(source, yaml_string(config, "image0_topic"));
@@ -91,6 +128,14 @@ static void replay_one(const char* config, const std::string& source, bool from_
     node.w_replace = wr.empty() ? 0 : atoi(wr.c_str());
     node.gnss_local_time_diff = estimator.cfg.gnss_enable ? estimator.cfg.gnss_local_time_diff : 0.0;   // rosNodeTest.cpp:703-708
     node.device_gray = device_gray;
+    size_t box_at = 0;   // the file is sorted and camera frames come in time order: one walk
+    if (boxes)
+        node.before_image = [&estimator, boxes, &box_at](long, double t) {
+            while (box_at < boxes->size() && (*boxes)[box_at].t < t) box_at++;
+            std::vector<gf_box> now;
+            for (size_t i = box_at; i < boxes->size() && (*boxes)[i].t == t; i++) now.push_back((*boxes)[i].box);
+            estimator.setBoxes(now.data(), (int)now.size());
+        };
     if (!track_images.empty()) {
         struct stat st;
         if (stat(track_images.c_str(), &st) != 0 && mkdir(track_images.c_str(), 0777) != 0) throw std::runtime_error("--track-images: cannot create " + track_images);
@@ -207,6 +252,14 @@ int main(int argc, char** argv) {
             for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
             argc -= 2; i--;
         }
+    std::string boxes_file;   // --boxes <file>, anywhere on the line
+    for (int i = 1; i < argc; i++)
+        if (std::string(argv[i]) == "--boxes") {
+            if (i + 1 >= argc) { fprintf(stderr, "gf_replay: --boxes needs a file\n"); return 2; }
+            boxes_file = argv[i + 1];
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2; i--;
+        }
     std::string track_images;   // --track-images <dir>, anywhere on the line
     for (int i = 1; i < argc; i++)
         if (std::string(argv[i]) == "--track-images") {
@@ -216,6 +269,11 @@ int main(int argc, char** argv) {
             argc -= 2; i--;
         }
     if (!track_images.empty() && argc >= 2 && std::string(argv[1]) == "--ranks") { fprintf(stderr, "gf_replay: --track-images goes with the single-process forms (one directory, one camera)\n"); return 2; }
+    if (!boxes_file.empty() && argc >= 2 && std::string(argv[1]) == "--ranks") { fprintf(stderr, "gf_replay: --boxes goes with the single-process forms (one file, one camera)\n"); return 2; }
+    std::vector<TimedBox> boxes;
+    if (!boxes_file.empty()) {
+        try { boxes = read_boxes_file(boxes_file); } catch (const std::exception& e) { fprintf(stderr, "gf_replay: %s\n", e.what()); return 2; }
+    }
     if (!roi.empty() && argc >= 2 && std::string(argv[1]) == "--ranks") { fprintf(stderr, "gf_replay: --roi goes with the single-process forms (one mask, one camera)\n"); return 2; }
     if (argc >= 5 && std::string(argv[1]) == "--ranks") {
         const int world = atoi(argv[2]);
@@ -253,13 +311,13 @@ int main(int argc, char** argv) {
         return rc;
     }
     const bool from_bag = argc >= 4 && std::string(argv[2]) == "--bag";
-    if (argc < 3 || (from_bag && argc < 4)) { fprintf(stderr, "usage: %s [--roi <mask.pgm>] [--track-images <dir>] <config.yaml> <dataset dir> [<vio.txt>]\n       %s [--device-gray] [--roi <mask.pgm>] [--track-images <dir>] <config.yaml> --bag <recording.bag> [<vio.txt>]\n       %s --ranks N <config.yaml> <dataset dir> ...\n", argv[0], argv[0], argv[0]); return 2; }
+    if (argc < 3 || (from_bag && argc < 4)) { fprintf(stderr, "usage: %s [--roi <mask.pgm>] [--boxes <file>] [--track-images <dir>] <config.yaml> <dataset dir> [<vio.txt>]\n       %s [--device-gray] [--roi <mask.pgm>] [--boxes <file>] [--track-images <dir>] <config.yaml> --bag <recording.bag> [<vio.txt>]\n       %s --ranks N <config.yaml> <dataset dir> ...\n", argv[0], argv[0], argv[0]); return 2; }
     if (device_gray && !from_bag) { fprintf(stderr, "gf_replay: --device-gray goes with --bag (PGM frames are MONO8 already)\n"); return 2; }
     const int out_arg = from_bag ? 4 : 3;
     try {
         gf::Estimator estimator;
         const std::string out = argc > out_arg ? argv[out_arg] : yaml_string(argv[1], "output_path") + "/vio.txt";
-        replay_one(argv[1], from_bag ? argv[3] : argv[2], from_bag, out, estimator, false, device_gray, roi, track_images);
+        replay_one(argv[1], from_bag ? argv[3] : argv[2], from_bag, out, estimator, false, device_gray, roi, track_images, boxes_file.empty() ? nullptr : &boxes);
         if (estimator.cfg.gnss_enable) {   // gnss_result.txt of the reference carries the ECEF / ENU position; here as one closing line
             int gi[8]; double yaw, anc[3], ecef[3], enu[3];
             if (gf_estimator_get_gnss_state(estimator.handle(), gi, nullptr, nullptr, &yaw, anc, ecef, enu) == GF_OK) {
