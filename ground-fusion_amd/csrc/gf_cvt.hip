@@ -3,6 +3,8 @@
 // tracker (gf_tracker_cfg.pixel_format) and exported as its own C-ABI.
 #include <hip/hip_runtime.h>
 #include <climits>
+#include <string>
+#include <vector>
 #include <type_traits>
 
 #include "../../include/groundfusion_hip.h"
@@ -107,6 +109,36 @@ int cvt_launch_refs(const gf_frame_ref* d_refs, const gf_frame_ref* h_refs, int 
     return GF_OK;
 }
 
+// One format per frame (gf_cvt_kernels.hpp, cvt_mixed_kernel): frame b lies at d_refs[b] in d_formats[b] and goes to the tight frame b of d_dst; an entry that is
+// no GF_PIX_* is skipped.  h_refs / h_formats: the same tables as the host reads them (the tracker's page-locked ones), or null where the host cannot read them
+// (gf_cvt_gray_mixed_device).  With them the grid is the largest any listed frame needs, a call without a frame to convert launches nothing and the Bayer part
+// is launched only where a Bayer frame is listed; without them the grid is that of the widest form of the size (narrower frames take several turns) and both
+// parts are launched.  Two launches at the most, whatever the formats and however long the list: the streaming formats keep the registers and the occupancy of
+// their homogeneous kernels, which the Bayer stencil would cost them ("Formats per sequence").
+int cvt_launch_mixed(const gf_frame_ref* d_refs, const int* d_formats, const gf_frame_ref* h_refs, const int* h_formats, uint8_t* d_dst, int batch, int w, int h, hipStream_t stream) {
+    using namespace gfcvt;
+    if (batch < 1 || w < 1 || h < 1) return set_err(GF_ERR_INVALID, "cvt_gray_mixed: %d frames of %dx%d (all must be >= 1)", batch, w, h);
+    if ((long long)w * h > INT_MAX) return set_err(GF_ERR_INVALID, "cvt_gray_mixed: %dx%d frames have more than 2^31 - 1 pixels", w, h);
+    const int dst_dwords = !((reinterpret_cast<uintptr_t>(d_dst) | (size_t)w) & 3) ? 1 : 0;
+    unsigned gx_stream = 0, gx_bayer = 0;
+    if (h_refs && h_formats) {
+        for (int b = 0; b < batch; b++) {
+            const int f = h_formats[b];
+            if (!gfpix::valid(f)) continue;
+            const unsigned need = mixed_blocks(f, mixed_form(f, h_refs[b].data, h_refs[b].pitch, dst_dwords, w), w, h);
+            if (gfpix::is_bayer(f)) gx_bayer = std::max(gx_bayer, need); else gx_stream = std::max(gx_stream, need);
+        }
+    } else {
+        gx_stream = mixed_blocks(GF_PIX_MONO8, dst_dwords ? ((w & 15) ? 4 : 16) : 1, w, h);
+        if (w >= 3 && h >= 3) gx_bayer = mixed_blocks(GF_PIX_BAYER_RGGB8, dst_dwords && w >= 8 ? 4 : 1, w, h);
+    }
+    const unsigned gy = (unsigned)std::min(batch, 65535);
+    if (gx_stream) cvt_mixed_kernel<1><<<dim3(gx_stream, gy), kThreads, 0, stream>>>(d_refs, d_formats, d_dst, batch, w, h, dst_dwords);
+    if (gx_bayer) cvt_mixed_kernel<2><<<dim3(gx_bayer, gy), kThreads, 0, stream>>>(d_refs, d_formats, d_dst, batch, w, h, dst_dwords);
+    HIPCHK(hipGetLastError());
+    return GF_OK;
+}
+
 }  // namespace gf
 
 extern "C" {
@@ -133,6 +165,46 @@ int gf_cvt_gray_batch(const uint8_t* src, size_t src_pitch, int format, uint8_t*
     HIPCHK(d_in.fit(in)); HIPCHK(d_out.fit(out));
     HIPCHK(hipMemcpy(d_in.p, src, in, hipMemcpyHostToDevice));
     if (int rc = gf_cvt_gray_batch_device(d_in.p, src_pitch, format, d_out.p, batch, width, height, nullptr)) return rc;
+    HIPCHK(hipMemcpy(dst, d_out.p, out, hipMemcpyDeviceToHost));
+    return GF_OK;
+}
+
+int gf_cvt_gray_mixed_device(const gf_frame_ref* d_refs, const int* d_formats, void* d_dst, int batch, int width, int height, void* stream) {
+    if (!d_refs || !d_formats || !d_dst) return gf::set_err(GF_ERR_INVALID, "cvt_gray_mixed: null argument");
+    return gf::cvt_launch_mixed(d_refs, d_formats, nullptr, nullptr, static_cast<uint8_t*>(d_dst), batch, width, height, static_cast<hipStream_t>(stream));
+}
+
+int gf_cvt_gray_mixed(const uint8_t* const* src, const size_t* pitch, const int* format, uint8_t* dst, int batch, int width, int height) {
+    if (!src || !pitch || !format || !dst) return gf::set_err(GF_ERR_INVALID, "cvt_gray_mixed: null argument");
+    if (batch < 1 || width < 1 || height < 1) return gf::set_err(GF_ERR_INVALID, "cvt_gray_mixed: %d frames of %dx%d (all must be >= 1)", batch, width, height);
+    const size_t px = (size_t)width * height, out = (size_t)batch * px;
+    const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst);
+    std::vector<size_t> at(batch), bytes(batch);
+    size_t in = 0;
+    for (int b = 0; b < batch; b++) {   // everything gf_cvt_gray_batch refuses, per frame
+        if (!src[b]) return gf::set_err(GF_ERR_INVALID, "cvt_gray_mixed: frame %d: null source", b);
+        if (gf::cvt_check(pitch[b], format[b], 1, width, height)) return gf::set_err(GF_ERR_INVALID, "cvt_gray_mixed: frame %d: %s", b, std::string(gf_last_error()).c_str());
+        bytes[b] = gf::cvt_src_bytes(pitch[b], format[b], 1, width, height);
+        const uintptr_t s0 = reinterpret_cast<uintptr_t>(src[b]);
+        if (s0 < d0 + out && d0 < s0 + bytes[b]) return gf::set_err(GF_ERR_INVALID, "cvt_gray_mixed: frame %d: source and destination overlap", b);
+        at[b] = ((in + 15) & ~(size_t)15) + (s0 & 15);   // the device copy keeps the host pointer's phase: the frame takes the form it would take where it lies
+        in = at[b] + bytes[b];
+    }
+    if (int rc = gf::require_device()) return rc;
+    gf::DevBuf<uint8_t> d_in, d_out, d_tab;
+    const size_t tab = (size_t)batch * (sizeof(gf_frame_ref) + sizeof(int));
+    HIPCHK(d_in.fit(in)); HIPCHK(d_out.fit(out)); HIPCHK(d_tab.fit(tab));
+    std::vector<uint8_t> h_tab(tab);
+    gf_frame_ref* refs = reinterpret_cast<gf_frame_ref*>(h_tab.data());
+    int* fmts = reinterpret_cast<int*>(refs + batch);
+    for (int b = 0; b < batch; b++) {
+        HIPCHK(hipMemcpy(d_in.p + at[b], src[b], bytes[b], hipMemcpyHostToDevice));
+        refs[b] = gf_frame_ref{d_in.p + at[b], pitch[b]};
+        fmts[b] = format[b];
+    }
+    HIPCHK(hipMemcpy(d_tab.p, h_tab.data(), tab, hipMemcpyHostToDevice));
+    const gf_frame_ref* d_refs = reinterpret_cast<const gf_frame_ref*>(d_tab.p);
+    if (int rc = gf::cvt_launch_mixed(d_refs, reinterpret_cast<const int*>(d_refs + batch), refs, fmts, d_out.p, batch, width, height, nullptr)) return rc;
     HIPCHK(hipMemcpy(dst, d_out.p, out, hipMemcpyDeviceToHost));
     return GF_OK;
 }

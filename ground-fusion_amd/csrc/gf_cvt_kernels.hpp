@@ -26,10 +26,10 @@ constexpr int kThreads = 256;
 template <int N> struct __attribute__((packed, aligned(4))) Dwords { uint32_t v[N]; };   // N dwords on a 4-byte boundary: one load / store instruction of that width
 
 // pixel j (0 .. NPX-1) of a piece held as little-endian dwords: byte k of the piece is (v[k >> 2] >> 8 (k & 3)) & 255; all indices are compile-time after unrolling
-template <int CH, int NPX> __device__ __forceinline__ unsigned byte_of(const Dwords<NPX * CH / 4>& s, int k) { return (s.v[k >> 2] >> (8 * (k & 3))) & 255u; }
+template <int CH, int NPX> GF_PIX_HD unsigned byte_of(const Dwords<NPX * CH / 4>& s, int k) { return (s.v[k >> 2] >> (8 * (k & 3))) & 255u; }
 
 template <int CH, int NPX>
-__device__ __forceinline__ void cvt_gray_vec_thread(unsigned bx, unsigned tx, unsigned by, unsigned gy, const uint8_t* __restrict__ src, size_t src_pitch, uint8_t* __restrict__ dst, int batch, int w, int h, int red_at) {
+GF_PIX_HD void cvt_gray_vec_thread(unsigned bx, unsigned tx, unsigned by, unsigned gy, const uint8_t* __restrict__ src, size_t src_pitch, uint8_t* __restrict__ dst, int batch, int w, int h, int red_at) {
     const int per_row = w / NPX;
     const unsigned p = bx * kThreads + tx;   // piece of the frame; the host keeps per_row * h below 2^31
     if (p >= (unsigned)per_row * (unsigned)h) return;
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(kThreads) void cvt_gray_vec_kernel(const uint8_t* _
 }
 
 template <int CH>
-__device__ __forceinline__ void cvt_gray_byte_thread(unsigned bx, unsigned tx, unsigned by, unsigned gy, const uint8_t* __restrict__ src, size_t src_pitch, uint8_t* __restrict__ dst, int batch, int w, int h, int red_at) {
+GF_PIX_HD void cvt_gray_byte_thread(unsigned bx, unsigned tx, unsigned by, unsigned gy, const uint8_t* __restrict__ src, size_t src_pitch, uint8_t* __restrict__ dst, int batch, int w, int h, int red_at) {
     const unsigned p = bx * kThreads + tx;   // pixel of the frame; the host keeps w * h below 2^31
     if (p >= (unsigned)w * (unsigned)h) return;
     const int y = p / w, x = p - y * w;
@@ -270,5 +270,78 @@ __global__ __launch_bounds__(kThreads) void cvt_bayer_byte_refs_kernel(const gf_
     GF_CVT_REFS_LOOP((cvt_bayer_byte_thread(blockIdx.x, threadIdx.x, 0, 1, f.data, f.pitch, d, 1, w, h, green_first, blue_row0)))
 }
 #undef GF_CVT_REFS_LOOP
+
+// ---------------------------------------------------------------------------------------------------------------- one format per frame
+// cvt_mixed_kernel: frame b is refs[b] in formats[b] (gf_tracker_set_seq_format: a fleet of cameras with different encodings on one handle; the same
+// rosNodeTest.cpp:238-254 per camera).  A block reads its entry with wave-uniform loads, takes the form the frame's own pointer and pitch allow, as the _refs
+// kernels do, and branches ONCE to the thread function the homogeneous kernel of that format and form runs, on the arguments of a batch of one: same loads, same
+// arithmetic, same bytes.  The branch is on scalars, so no wavefront diverges on the format.  An entry whose format is no GF_PIX_* (the tracker writes -1 for a
+// frame that needs no conversion) is skipped: nothing is read, nothing is written for it.
+// blockIdx.x walks the pieces of a frame with a stride of gridDim.x: the host sizes the grid for the largest need of the frames it knows (cvt_launch_mixed with
+// a host copy of the tables), or for the widest form of the size when it cannot read the tables; a frame that needs more blocks than the grid has takes several
+// turns, a block beyond its frame's need leaves before it touches memory.
+GF_PIX_HD int mixed_form(int format, const void* data, size_t pitch, int dst_dwords, int w) {   // pixels a lane takes per row: 16, 4 or 1
+    const bool dwords = dst_dwords && gfref::form(reinterpret_cast<uintptr_t>(data), pitch) >= 4;
+    if (gfpix::is_bayer(format)) return dwords && w >= 8 ? 4 : 1;
+    return !dwords ? 1 : !(w & 15) ? 16 : 4;
+}
+GF_PIX_HD unsigned mixed_blocks(int format, int form, int w, int h) {   // blocks of kThreads lanes a frame of that format and form needs
+    const size_t rows = gfpix::is_bayer(format) && form == 4 ? ((size_t)h + kBayerBand - 1) / kBayerBand : (size_t)h;
+    return (unsigned)(((size_t)(w / form) * rows + kThreads - 1) / kThreads);
+}
+// PART: 0 every format, 1 all but Bayer, 2 Bayer alone (a launch of a part skips the other part's frames)
+template <int PART> GF_PIX_HD bool mixed_serves(int format) { return gfpix::valid(format) && (PART == 0 || (PART == 2) == gfpix::is_bayer(format)); }
+
+// lane tx of (virtual) block bx of a frame
+GF_PIX_HD void cvt_mixed_thread(unsigned bx, unsigned tx, const uint8_t* src, size_t pitch, int format, int form, uint8_t* d, int w, int h) {
+    const int ch = gfpix::channels(format), red_at = gfpix::red_at(format);
+    if (gfpix::is_bayer(format)) {
+        const int gf = gfpix::bayer_green_first(format), br = gfpix::bayer_blue_row0(format);
+        if (form == 4) cvt_bayer_vec_thread(bx, tx, 0, 1, src, pitch, d, 1, w, h, gf, br);
+        else cvt_bayer_byte_thread(bx, tx, 0, 1, src, pitch, d, 1, w, h, gf, br);
+    } else if (format == GF_PIX_MONO16) {
+        if (form == 16) cvt_pair_vec_thread<true, 16>(bx, tx, 0, 1, src, pitch, d, 1, w, h, 0);
+        else if (form == 4) cvt_pair_vec_thread<true, 4>(bx, tx, 0, 1, src, pitch, d, 1, w, h, 0);
+        else cvt_pair_byte_thread<true>(bx, tx, 0, 1, src, pitch, d, 1, w, h, 0);
+    } else if (ch == 2) {
+        const int la = gfpix::luma_at(format);
+        if (form == 16) cvt_pair_vec_thread<false, 16>(bx, tx, 0, 1, src, pitch, d, 1, w, h, la);
+        else if (form == 4) cvt_pair_vec_thread<false, 4>(bx, tx, 0, 1, src, pitch, d, 1, w, h, la);
+        else cvt_pair_byte_thread<false>(bx, tx, 0, 1, src, pitch, d, 1, w, h, la);
+    } else if (ch == 1) {
+        if (form == 16) cvt_gray_vec_thread<1, 16>(bx, tx, 0, 1, src, pitch, d, 1, w, h, red_at);
+        else if (form == 4) cvt_gray_vec_thread<1, 4>(bx, tx, 0, 1, src, pitch, d, 1, w, h, red_at);
+        else cvt_gray_byte_thread<1>(bx, tx, 0, 1, src, pitch, d, 1, w, h, red_at);
+    } else if (ch == 3) {
+        if (form == 16) cvt_gray_vec_thread<3, 16>(bx, tx, 0, 1, src, pitch, d, 1, w, h, red_at);
+        else if (form == 4) cvt_gray_vec_thread<3, 4>(bx, tx, 0, 1, src, pitch, d, 1, w, h, red_at);
+        else cvt_gray_byte_thread<3>(bx, tx, 0, 1, src, pitch, d, 1, w, h, red_at);
+    } else {
+        if (form == 16) cvt_gray_vec_thread<4, 16>(bx, tx, 0, 1, src, pitch, d, 1, w, h, red_at);
+        else if (form == 4) cvt_gray_vec_thread<4, 4>(bx, tx, 0, 1, src, pitch, d, 1, w, h, red_at);
+        else cvt_gray_byte_thread<4>(bx, tx, 0, 1, src, pitch, d, 1, w, h, red_at);
+    }
+}
+
+// what block (bx, by) of a grid (gx, gy) does for lane tx, given the entries as the block has read them: the walk a host program repeats
+template <int PART, class ENTRY>
+GF_PIX_HD void cvt_mixed_block(unsigned bx, unsigned gx, unsigned by, unsigned gy, unsigned tx, ENTRY entry, uint8_t* dst, int batch, int w, int h, int dst_dwords) {
+    for (int b = by; b < batch; b += gy) {
+        const uint8_t* data; size_t pitch; int format;
+        entry(b, data, pitch, format);
+        if (!mixed_serves<PART>(format)) continue;
+        const int form = mixed_form(format, data, pitch, dst_dwords, w);
+        const unsigned need = mixed_blocks(format, form, w, h);
+        for (unsigned v = bx; v < need; v += gx) cvt_mixed_thread(v, tx, data, pitch, format, form, dst + (size_t)b * h * w, w, h);
+    }
+}
+
+template <int PART>
+__global__ __launch_bounds__(kThreads) void cvt_mixed_kernel(const gf_frame_ref* __restrict__ refs, const int* __restrict__ formats, uint8_t* __restrict__ dst, int batch, int w, int h, int dst_dwords) {
+    cvt_mixed_block<PART>(blockIdx.x, gridDim.x, blockIdx.y, gridDim.y, threadIdx.x, [&](int b, const uint8_t*& data, size_t& pitch, int& format) {
+        const gfref::Frame f = gfref::entry(refs, b);
+        data = f.data; pitch = f.pitch; format = __builtin_amdgcn_readfirstlane(formats[b]);
+    }, dst, batch, w, h, dst_dwords);
+}
 
 }  // namespace gfcvt

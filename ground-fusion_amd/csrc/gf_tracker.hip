@@ -41,6 +41,7 @@
 #include "gf_pixfmt.hpp"
 #include "gf_roi.hpp"
 #include "gf_seq_cfg.hpp"
+#include "gf_seq_format.hpp"
 #include "gf_track_draw.hpp"
 #include "gf_track_host.hpp"
 
@@ -54,6 +55,8 @@ int cvt_launch(const uint8_t* d_src, size_t src_pitch, int format, uint8_t* d_ds
 // the table forms of the two (gf_frame_ref.hpp): frame b of the source lies at refs[b]
 int clahe_launch_refs(const gf_frame_ref* d_refs, uint8_t* d_dst, uint8_t* d_lut, int batch, int w, int h, double clip_limit, int tiles_x, int tiles_y, hipStream_t stream);
 int cvt_launch_refs(const gf_frame_ref* d_refs, const gf_frame_ref* h_refs, int format, uint8_t* d_dst, int batch, int w, int h, hipStream_t stream, int* n_bytes);
+// one format per frame (gf_tracker_set_seq_format): entry b at d_refs[b] in d_formats[b], -1 = skip; h_*: the same tables as the host reads them
+int cvt_launch_mixed(const gf_frame_ref* d_refs, const int* d_formats, const gf_frame_ref* h_refs, const int* h_formats, uint8_t* d_dst, int batch, int w, int h, hipStream_t stream);
 // gf_track_draw.hip: the track image of `count` frames, one per entry of d_jobs (gf_track_draw.hpp), in one launch
 int draw_track_launch(const gfdraw::DrawJob* d_jobs, int count, int w, int h, hipStream_t stream);
 constexpr double kClaheClip = 40.0;   // cv::createCLAHE() defaults (rosNodeTest.cpp:258)
@@ -217,6 +220,17 @@ struct gf_tracker {
     DevBuf<gfdraw::Prim> d_draw_prims; PinBuf<gfdraw::Prim> h_draw_prims;
     DevBuf<gfdraw::DrawJob> d_draw_jobs; PinBuf<gfdraw::DrawJob> h_draw_jobs;
     DevBuf<uint8_t> d_draw_host;
+    // A pixel format and an equalise switch per sequence (gf_seq_format.hpp; gf_tracker_set_seq_format), the fifth thing addressed by SEQUENCE.  fmt[seq] is what
+    // is in force, the handle's cfg until a setter says otherwise (host memory only); fmt_any: a setter has given a sequence values of its own.  Everything else is
+    // obtained by the setters, as the tables above are: d_cvt / d_eq / d_eq_lut where gf_tracker_create did not need them, d_raw (and d_raw2) grown to raw_ch bytes
+    // per pixel, the widest format in force, and the table of a mixed call: [B] conversion sources, [B] equalisation sources (dense), [B] pyramid sources, then
+    // [B] formats as the conversion kernel reads them.  It travels like the list and the frame table: page-locked, read over the bus by the three stages.
+    std::vector<gf_tracker_seq_format> fmt;
+    bool fmt_any = false;
+    int raw_ch = 1;
+    gfseqfmt::Plan plan;                     // of the call in progress (plan_call)
+    std::vector<gf_frame_ref> plan_frames;   // scratch: where the caller's frames of that call lie
+    DevBuf<uint8_t> d_mix; PinBuf<uint8_t> h_mix;
 
     std::unique_ptr<HostPool> pool;
 };
@@ -439,6 +453,33 @@ static int check_box_lists(gf_tracker* h, int count, const int* seq, const int* 
 }
 
 // The row step of host frames on a handle that takes colour or raw frames: refused before anything is copied.  (A MONO8 handle hands its stride to the copy as it always did.)
+// ---- formats per sequence (gf_seq_format.hpp).  The plan of the list of a call on a handle that has any: formats, sizes, offsets and slots by list position.
+static void plan_call(gf_tracker* h, int count, const int* seq) {
+    gfseqfmt::plan_list(h->plan, h->fmt.data(), gfseqfmt::of_handle(h->cfg), count, seq, h->cfg.width, h->cfg.height);
+}
+// The row steps of the host frames of a list on such a handle: each sequence's own (host_stride) or the call's, against a row of its own format.
+static int check_strides_listed(gf_tracker* h, int count, const int* seq, int stride) {
+    for (int i = 0; i < count; i++) {
+        const gf_tracker_seq_format& f = h->fmt[seq[i]];
+        const long long eff = gfseqfmt::host_stride(f, stride);
+        const size_t row = gfseqfmt::row_bytes(h->cfg.width, f.pixel_format);
+        if (eff < 0 || (size_t)eff < row)
+            return set_err(GF_ERR_INVALID, "gray frame at list position %d (sequence %d): a stride of %lld bytes is shorter than a row of %d pixels of %d bytes (pixel format %d)", i, seq[i], eff, h->cfg.width,
+                           gfpix::channels(f.pixel_format), f.pixel_format);
+    }
+    return GF_OK;
+}
+// The host frames of the list into `raw` (d_raw or d_raw2) on `stream`: each as it lies, with its own row bytes, to the sum of the frames before it.
+static int copy_host_frames(gf_tracker* h, int count, const int* seq, const uint8_t* const* gray, int stride, uint8_t* raw, hipStream_t stream) {
+    plan_call(h, count, seq);
+    const int W = h->cfg.width, H = h->cfg.height;
+    for (int i = 0; i < count; i++) {
+        const size_t row = gfseqfmt::row_bytes(W, h->plan.format[i]);
+        HIPCHK(hipMemcpy2DAsync(raw + h->plan.offset[i], row, gray[i], (size_t)gfseqfmt::host_stride(h->fmt[seq[i]], stride), row, H, hipMemcpyHostToDevice, stream));
+    }
+    return GF_OK;
+}
+
 static int check_stride(gf_tracker* h, int stride) {
     if (h->cfg.pixel_format && (stride < 0 || (size_t)stride < (size_t)h->cfg.width * h->ch))
         return set_err(GF_ERR_INVALID, "a stride of %d bytes is shorter than a row of %d pixels of %d bytes (gf_tracker_cfg.pixel_format %d)", stride, h->cfg.width, h->ch, h->cfg.pixel_format);
@@ -447,7 +488,7 @@ static int check_stride(gf_tracker* h, int stride) {
 // The host frames of the `count` listed sequences (gf_tracker_track_some, gf_tracker_prefetch_some), refused before anything is copied.
 // *have_depth: the call has depth images, one for every listed sequence with a depth camera.
 static int check_host_frames(gf_tracker* h, int count, const int* seq, const uint8_t* const* gray, int stride, const uint16_t* const* depth, bool* have_depth) {
-    if (int rc = check_stride(h, stride)) return rc;
+    if (int rc = h->fmt_any ? check_strides_listed(h, count, seq, stride) : check_stride(h, stride)) return rc;
     *have_depth = depth != nullptr;
     for (int i = 0; i < count; i++) {
         if (!gray[i]) return set_err(GF_ERR_INVALID, "null image for sequence %d", seq[i]);
@@ -556,6 +597,9 @@ struct Call {
     bool refs_down = false;               // its depth half is still wanted on the device: with the first copy list that leaves
     const uint16_t* kdepth = nullptr;     // what LK and the selection sample: tight device depth frames, the device table's depth half (depth_by_refs) or null
     bool any_prev = false, any_pred = false, any_plain = false, any_want = false;
+    bool mixed = false;                   // a listed sequence runs with a format or switch that is not the handle's own: the front goes through h->plan
+    const uint8_t* mix = nullptr;         // the table of a mixed call where the front's kernels read it (h_mix over the bus, or d_mix)
+    bool did_cvt = false, did_eq = false; // the call converted / equalised at least one listed sequence (read_profile)
     void lap(double& acc) { const auto n = std::chrono::steady_clock::now(); acc += std::chrono::duration<double, std::milli>(n - tp).count(); tp = n; }
     void add_refs() { if (refs_down) { ho.down(h->d_refs, h->h_refs, (size_t)2 * h->B); refs_down = false; } }
 };
@@ -580,6 +624,21 @@ static int publish(Call& c) {
     if (in.gray_refs && !refs_bus) HIPCHK(hipMemcpyAsync(h->d_refs.p, h->h_refs.p, (size_t)2 * h->B * sizeof(gf_frame_ref), hipMemcpyHostToDevice, h->stream));
     c.refs = !in.gray_refs ? nullptr : refs_bus ? h->h_refs.hd : h->d_refs.p;
     c.refs_down = refs_bus && in.depth_refs;
+    if (c.mixed) {   // the plan's three tables of sources and the formats, the same way
+        gfseqfmt::Plan& p = h->plan;
+        const int W = h->cfg.width, H = h->cfg.height;
+        h->plan_frames.resize(c.N);
+        if (in.gray_refs) std::copy(in.gray_refs, in.gray_refs + c.N, h->plan_frames.begin());
+        else gfseqfmt::tight_frames(p, in.gray, W, h->plan_frames.data());   // base + the sum of the frames before it, rows tight
+        gfseqfmt::plan_sources(p, h->plan_frames.data(), h->d_cvt.p, h->d_eq.p, W, H);
+        gf_frame_ref* t = reinterpret_cast<gf_frame_ref*>(h->h_mix.p);
+        int* f = reinterpret_cast<int*>(t + 3 * (size_t)h->B);
+        for (int i = 0; i < c.N; i++) { t[i] = p.cvt_src[i]; t[2 * (size_t)h->B + i] = p.pyr_src[i]; f[i] = p.cvt_format[i]; }
+        for (int j = 0; j < p.n_eq; j++) t[h->B + j] = p.eq_src[j];
+        const bool mix_bus = over_bus && h->h_mix.hd;
+        if (!mix_bus) HIPCHK(hipMemcpyAsync(h->d_mix.p, h->h_mix.p, h->h_mix.n, hipMemcpyHostToDevice, h->stream));
+        c.mix = mix_bus ? h->h_mix.hd : h->d_mix.p;
+    }
     return GF_OK;
 }
 
@@ -592,6 +651,32 @@ static int launch_front(Call& c) {
     const gf_frame_ref* refs = c.refs;
     int refs_widest = 16, refs_narrow = -1;   // the widest piece of the first reader of the caller's frames; frames it counted itself
     if (prof) HIPCHK(hipEventRecord(h->ev[0], h->stream));
+    if (c.mixed) {   // formats per sequence (gf_seq_format.hpp): the same three stages through the plan's tables, each over the positions that need it
+        const gfseqfmt::Plan& p = h->plan;
+        const gf_frame_ref* t = reinterpret_cast<const gf_frame_ref*>(c.mix);
+        const gf_frame_ref* ht = reinterpret_cast<const gf_frame_ref*>(h->h_mix.p);
+        const size_t B = (size_t)h->B;
+        if (p.n_cvt) {
+            if (int rc = cvt_launch_mixed(t, reinterpret_cast<const int*>(t + 3 * B), ht, reinterpret_cast<const int*>(ht + 3 * B), h->d_cvt.p, N, W, H, h->stream)) return rc;
+            c.did_cvt = true;
+            if (prof) HIPCHK(hipEventRecord(h->ev[8], h->stream));
+        }
+        if (p.n_eq) {
+            if (int rc = clahe_launch_refs(t + B, h->d_eq.p, h->d_eq_lut.p, p.n_eq, W, H, kClaheClip, kClaheTiles, kClaheTiles, h->stream)) return rc;
+            c.did_eq = true;
+            if (prof) HIPCHK(hipEventRecord(h->ev[7], h->stream));
+        }
+        if (int rc = launch_pyramid(h, nullptr, N, c.cur_of, t + 2 * B, &refs_widest)) return rc;
+        if (prof) HIPCHK(hipEventRecord(h->ev[1], h->stream));
+        if (c.in.gray_refs) {   // each frame against the widest piece of ITS first reader: the conversion's dwords, CLAHE's or the pyramid's 16 bytes
+            for (int i = 0; i < N; i++) {
+                const int widest = p.cvt_format[i] >= 0 ? 4 : p.eq_index[i] >= 0 ? ((W & 15) ? 4 : 16) : refs_widest;
+                h->stats.frames_unaligned += gfref::unaligned(reinterpret_cast<uintptr_t>(c.in.gray_refs[i].data), c.in.gray_refs[i].pitch, widest) ? 1 : 0;
+            }
+        }
+        return GF_OK;
+    }
+    c.did_cvt = h->cfg.pixel_format != 0; c.did_eq = h->cfg.equalize != 0;
     if (h->cfg.pixel_format) {   // rosNodeTest.cpp:238-254: toCvCopy(msg, MONO8) ahead of CLAHE and trackImage
         if (int rc = refs ? cvt_launch_refs(refs, h->h_refs.p, h->cfg.pixel_format, h->d_cvt.p, N, W, H, h->stream, &refs_narrow)
                           : cvt_launch(gray, (size_t)W * h->ch, h->cfg.pixel_format, h->d_cvt.p, N, W, H, h->stream)) return rc;
@@ -769,8 +854,8 @@ static int read_profile(Call& c) {   // gf_tracker_set_profiling: the stages' ti
     gf_tracker* h = c.h;
     float ms = 0;
     hipEvent_t from = h->ev[0];   // the stages ahead of the pyramid, each from where the one before it ended
-    if (h->cfg.pixel_format) { HIPCHK(hipEventElapsedTime(&ms, from, h->ev[8])); h->stats.ms_convert += ms; from = h->ev[8]; }
-    if (h->cfg.equalize) { HIPCHK(hipEventElapsedTime(&ms, from, h->ev[7])); h->stats.ms_equalize += ms; from = h->ev[7]; }
+    if (c.did_cvt) { HIPCHK(hipEventElapsedTime(&ms, from, h->ev[8])); h->stats.ms_convert += ms; from = h->ev[8]; }
+    if (c.did_eq) { HIPCHK(hipEventElapsedTime(&ms, from, h->ev[7])); h->stats.ms_equalize += ms; from = h->ev[7]; }
     HIPCHK(hipEventElapsedTime(&ms, from, h->ev[1])); h->stats.ms_pyramid += ms;
     if (c.any_prev) { HIPCHK(hipEventElapsedTime(&ms, h->ev[2], h->ev[3])); h->stats.ms_lk += ms; }
     HIPCHK(hipEventElapsedTime(&ms, h->ev[4], h->ev[5])); h->stats.ms_detect += ms;
@@ -823,6 +908,7 @@ static int book_after_detect(Call& c, gf_feature_obs* out, int cap_out, int* n_o
 static int track_core(gf_tracker* h, int count, const int* seq, const double* t, const FrameInput& in, gf_feature_obs* out, int cap_out, int* n_out) {
     if (count == 0) return GF_OK;
     Call c{h, count, seq, in, HandOver(h->copy_lists, h->stream)};
+    if (h->fmt_any) { plan_call(h, count, seq); c.mixed = !h->plan.homogeneous; }
     for (int i = 0; i < count; i++) h->h_cur.p[i] = 2 * seq[i] + begin_frame(h->seq[seq[i]], t[i]);   // the new frame goes to the sequence's other pyramid
     if (int rc = publish(c)) return rc;
     if (int rc = launch_front(c)) return rc;
@@ -873,6 +959,8 @@ int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out) {
     gf::make_disk_table(cfg->min_dist, h->disk);
     h->seq.resize(h->B);
     h->par.assign(h->B, gfseq::of_handle(*cfg));
+    h->fmt.assign(h->B, gfseqfmt::of_handle(*cfg));
+    h->raw_ch = h->ch;
     h->ident.resize(h->B);
     for (int b = 0; b < h->B; b++) h->ident[b] = b;
     {
@@ -954,7 +1042,9 @@ static int refs_ready(gf_tracker* h) {   // the first _refs call of a handle: th
 }
 // every entry of a table of `count`, or GF_ERR_INVALID naming the list position; what: "gray", "depth" or "mask"
 static int check_refs(const gf_tracker* h, int count, const int* seq, const gf_frame_ref* refs, size_t row_bytes, bool u16, const char* what) {
+    const bool own_rows = row_bytes == 0;   // gray frames: a row of each sequence's own format (gf_tracker_set_seq_format)
     for (int i = 0; i < count; i++) {
+        if (own_rows) row_bytes = gfseqfmt::row_bytes(h->cfg.width, h->fmt[seq[i]].pixel_format);
         const gfref::Verdict v = gfref::check(refs[i], row_bytes, u16, u16 && !h->par[seq[i]].depth_cam);
         if (v != gfref::kOk)
             return set_err(GF_ERR_INVALID, "%s frame at list position %d (sequence %d): %s (data %p, pitch %zu bytes, a row is %zu bytes)", what, i, seq[i], gfref::verdict_text(v), refs[i].data, refs[i].pitch, row_bytes);
@@ -970,7 +1060,7 @@ int gf_tracker_track_some_device_refs(gf_tracker* h, int count, const int* seq, 
     if (count == 0) return GF_OK;
     if (!gray) return gf::set_err(GF_ERR_INVALID, "null table of gray frames");
     if (!t || !out || !n_out) return gf::set_err(GF_ERR_INVALID, "null argument");
-    if (int rc = gf::check_refs(h, count, seq, gray, (size_t)h->cfg.width * h->ch, false, "gray")) return rc;
+    if (int rc = gf::check_refs(h, count, seq, gray, 0, false, "gray")) return rc;
     if (depth) if (int rc = gf::check_refs(h, count, seq, depth, (size_t)h->cfg.width * 2, true, "depth")) return rc;
     if (int rc = gf::refs_ready(h)) return rc;
     return gf::track_core(h, count, seq, t, gf::FrameInput::by_refs(gray, depth), out, cap, n_out);
@@ -991,7 +1081,8 @@ int gf_tracker_track_some(gf_tracker* h, int count, const int* seq, const double
     if (int rc = gf::check_host_frames(h, count, seq, gray, stride, depth, &have_depth)) return rc;   // refuse before the first copy
     const size_t row = (size_t)h->cfg.width * h->ch;   // bytes of a row of the handle's pixel format
     const int H = h->cfg.height;
-    for (int i = 0; i < count; i++) HIPCHK(hipMemcpy2DAsync(h->d_raw.p + (size_t)i * row * H, row, gray[i], stride, row, H, hipMemcpyHostToDevice, h->stream));
+    if (h->fmt_any) { if (int rc = gf::copy_host_frames(h, count, seq, gray, stride, h->d_raw.p, h->stream)) return rc; }
+    else for (int i = 0; i < count; i++) HIPCHK(hipMemcpy2DAsync(h->d_raw.p + (size_t)i * row * H, row, gray[i], stride, row, H, hipMemcpyHostToDevice, h->stream));
     // the depth image stays where it is: its <= max_cnt samples are taken on the host (after_lk, after_detect)
     return gf::track_core(h, count, seq, t, gf::FrameInput::with_host_depth(h->d_raw.p, have_depth ? depth : nullptr, dstride), out, cap, n_out);
 }
@@ -1012,14 +1103,15 @@ int gf_tracker_prefetch_some(gf_tracker* h, int count, const int* seq, const uin
     if (!h->copy_stream) {
         HIPCHK(hipStreamCreateWithFlags(&h->copy_stream.s, hipStreamNonBlocking));
         for (auto& e : h->ev_copy) HIPCHK(hipEventCreateWithFlags(&e.e, hipEventDisableTiming));
-        HIPCHK(h->d_raw2.alloc((size_t)h->B * row * H));
+        HIPCHK(h->d_raw2.alloc((size_t)h->B * h->cfg.width * H * h->raw_ch));   // the pair of d_raw: room for the widest format in force
     }
     const int slot = (h->pf_head + h->pf_count) & 1;      // a pair no frame in flight uses: track calls return when their frame is done
     uint8_t* raw = slot ? h->d_raw2.p : h->d_raw.p;
     // images that sit back to back in one allocation (a pinned ring of frames) go as ONE copy per plane: 256 separate 2-D copies cost more host time than the bus needs
-    bool contig = (size_t)stride == row;
+    bool contig = (size_t)stride == row && !h->fmt_any;
     for (int i = 1; i < count && contig; i++) contig = gray[i] == gray[0] + (size_t)i * row * H;
-    if (contig && count > 0) HIPCHK(hipMemcpyAsync(raw, gray[0], (size_t)count * row * H, hipMemcpyHostToDevice, h->copy_stream));
+    if (h->fmt_any) { if (int rc = gf::copy_host_frames(h, count, seq, gray, stride, raw, h->copy_stream)) return rc; }
+    else if (contig && count > 0) HIPCHK(hipMemcpyAsync(raw, gray[0], (size_t)count * row * H, hipMemcpyHostToDevice, h->copy_stream));
     else for (int i = 0; i < count; i++) HIPCHK(hipMemcpy2DAsync(raw + (size_t)i * row * H, row, gray[i], stride, row, H, hipMemcpyHostToDevice, h->copy_stream));
     HIPCHK(hipEventRecord(h->ev_copy[slot], h->copy_stream));
     // the depth images do not travel: gf_tracker_track_prefetched samples them on the host (they must stay valid until it returns, like the gray images until the copy is done)
@@ -1256,6 +1348,43 @@ int gf_tracker_get_seq_cfg(gf_tracker* h, int seq, gf_tracker_seq_cfg* out) {
     if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
     if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
     *out = h->par[seq];
+    return GF_OK;
+}
+
+// ---- a pixel format and an equalise switch per sequence (gf_seq_format.hpp; rosNodeTest.cpp:238-261 per camera).  Between frames, with the stream drained.
+int gf_tracker_set_seq_format(gf_tracker* h, int seq, const gf_tracker_seq_format* f) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    if (h->seq[seq].started) return gf::set_err(GF_ERR_INVALID, "sequence %d has taken a frame: its format is fixed until gf_tracker_reset_seq", seq);
+    if (h->pf_count) return gf::set_err(GF_ERR_INVALID, "sequence %d: a frame staged by gf_tracker_prefetch_* is waiting (the staging buffers may have to grow): gf_tracker_track_prefetched has to consume it first", seq);
+    const gf_tracker_seq_format own = gfseqfmt::of_handle(h->cfg), want = f ? *f : own;
+    const int W = h->cfg.width, H = h->cfg.height, B = h->B;
+    char msg[256];
+    if (f && !gfseqfmt::fits(W, H, want, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "sequence %d: %s", seq, msg);
+    if (!f && !h->fmt_any) return GF_OK;   // nothing to take back: the handle stays one that never set any
+    // what a handle created with that format would have, into locals first: a failed allocation changes nothing
+    const size_t px = (size_t)W * H;
+    const int ch = std::max(h->raw_ch, gfpix::channels(want.pixel_format));
+    gf::DevBuf<uint8_t> cvt, eq, lut, raw, raw2, dmix; gf::PinBuf<uint8_t> hmix;
+    const bool need_cvt = want.pixel_format != GF_PIX_MONO8 && !h->d_cvt.p, need_eq = want.equalize && !h->d_eq.p, need_raw = ch > h->raw_ch, need_mix = !h->h_mix.p;
+    const size_t mix_bytes = (size_t)B * (3 * sizeof(gf_frame_ref) + sizeof(int));
+    if (need_cvt) HIPCHK(cvt.alloc((size_t)B * px));
+    if (need_eq) { HIPCHK(eq.alloc((size_t)B * px)); HIPCHK(lut.alloc(gf::clahe_lut_bytes(B, gf::kClaheTiles, gf::kClaheTiles))); }
+    if (need_raw) { HIPCHK(raw.alloc((size_t)B * px * ch)); if (h->d_raw2.p) HIPCHK(raw2.alloc((size_t)B * px * ch)); }
+    if (need_mix) { HIPCHK(dmix.alloc(mix_bytes)); HIPCHK(hmix.alloc(mix_bytes)); }
+    if (need_cvt) h->d_cvt = std::move(cvt);
+    if (need_eq) { h->d_eq = std::move(eq); h->d_eq_lut = std::move(lut); }
+    if (need_raw) { h->d_raw = std::move(raw); if (h->d_raw2.p) h->d_raw2 = std::move(raw2); h->raw_ch = ch; }   // nothing is staged and the stream is drained: no frame is lost
+    if (need_mix) { h->d_mix = std::move(dmix); h->h_mix = std::move(hmix); }
+    h->fmt[seq] = want;
+    h->fmt_any = true;
+    return GF_OK;
+}
+
+int gf_tracker_get_seq_format(gf_tracker* h, int seq, gf_tracker_seq_format* out) {
+    if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    *out = h->fmt[seq];
     return GF_OK;
 }
 

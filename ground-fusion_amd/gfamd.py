@@ -28,6 +28,11 @@ class TrackerSeqCfg(C.Structure):
                 ("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double)]
 
 
+class TrackerSeqFormat(C.Structure):
+    """gf_tracker_seq_format: the pixel format, equalise switch and host row step a sequence of a tracker handle may have of its own (rosNodeTest.cpp:238-261)"""
+    _fields_ = [("pixel_format", C.c_int), ("equalize", C.c_int), ("host_stride", C.c_int)]
+
+
 # GF_PIX_*: the formats of the frames a tracker handle takes and of cvt_gray (rosNodeTest.cpp:238-254), and their bytes per pixel
 PIX_MONO8, PIX_RGB8, PIX_BGR8, PIX_RGBA8, PIX_BGRA8 = range(5)
 PIX_CHANNELS = (1, 3, 3, 4, 4)
@@ -137,7 +142,8 @@ EXPORTS = ["gf_last_error", "gf_device_count", "gf_set_device", "gf_tracker_crea
            "gf_good_features", "gf_min_eigen_val", "gf_pyramid_level", "gf_clahe_batch", "gf_clahe_batch_device", "gf_cvt_gray_batch", "gf_cvt_gray_batch_device",
            "gf_tracker_set_show_track", "gf_tracker_track_image_some_device", "gf_tracker_track_image", "gf_draw_track_batch",
            "gf_estimator_set_show_track", "gf_estimator_get_track_image", "gf_show_track_from_yaml",
-           "gf_tracker_set_boxes_some", "gf_tracker_get_boxes", "gf_roi_boxes_batch", "gf_estimator_set_boxes", "gf_draw_track_boxes_batch"]
+           "gf_tracker_set_boxes_some", "gf_tracker_get_boxes", "gf_roi_boxes_batch", "gf_estimator_set_boxes", "gf_draw_track_boxes_batch",
+           "gf_tracker_set_seq_format", "gf_tracker_get_seq_format", "gf_cvt_gray_mixed", "gf_cvt_gray_mixed_device"]
 
 
 def lib():
@@ -188,6 +194,7 @@ class FeatureTracker:
         self.cap = 4 * ((self.cfg.max_cnt + 3) // 4)
         self.channels = pix_bytes(self.cfg.pixel_format)   # a handle of a format with more than one byte per pixel takes [height, width, bytes] u8 frames wherever a MONO8 handle takes [height, width]
         self.row_bytes = self.cfg.width * self.channels
+        self._fmt = {}   # set_seq_format: the sequences that have a format of their own, seq -> (pixel_format, equalize, host_stride)
 
     def close(self):
         if getattr(self, "h", None):
@@ -221,7 +228,10 @@ class FeatureTracker:
         seqs, N = self._seqs(seqs)
         ts = np.ascontiguousarray(ts, np.float64)
         assert len(ts) == N and len(imgs) == N and (depths is None or len(depths) == N)
-        imgs = [None if i is None else np.ascontiguousarray(i, np.uint8) if stride is None else self._pitched(i, np.uint8, stride) for i in imgs]
+        if self._fmt:   # formats per sequence (set_seq_format): each frame in its sequence's own shape and row step
+            imgs, stride = self._host_frames(seqs, imgs, stride)
+        else:
+            imgs = [None if i is None else np.ascontiguousarray(i, np.uint8) if stride is None else self._pitched(i, np.uint8, stride) for i in imgs]
         gp = (C.POINTER(C.c_uint8) * max(N, 1))(*[None if i is None else _p(i, C.c_uint8) for i in imgs])
         if depths is not None:
             # (an entry may be None for a sequence whose own depth_cam is 0, set_seq_cfg: its image is not read)
@@ -300,6 +310,8 @@ class FeatureTracker:
     def trackImageBatch(self, ts, imgs, depths=None, stride=None, dstride=None):
         """stride / dstride: row pitch of the gray (bytes) / depth (u16 elements) images, for frames with padded rows (cv::Mat::step); default: contiguous rows"""
         B = self.cfg.batch
+        if self._fmt:   # formats per sequence: the list form with every sequence listed takes each frame in its own shape
+            return self.trackImageSome(range(B), ts, imgs, depths, stride, dstride)
         ts = np.ascontiguousarray(ts, np.float64)
         imgs = [np.ascontiguousarray(i, np.uint8) for i in imgs] if stride is None else [self._pitched(i, np.uint8, stride) for i in imgs]
         gp = (C.POINTER(C.c_uint8) * B)(*[_p(i, C.c_uint8) for i in imgs])
@@ -447,6 +459,52 @@ class FeatureTracker:
         for k, v in fields.items():
             setattr(c, k, v)
         _chk(lib().gf_tracker_set_seq_cfg(self.h, seq, C.byref(c)))
+
+    def set_seq_format(self, seq, pixel_format=None, equalize=None, host_stride=0):
+        """gf_tracker_set_seq_format: sequence `seq` takes frames of `pixel_format` (PIX_*) and is equalised or not, whatever the handle's cfg says; a field left
+        None keeps the value in force, host_stride = bytes per row of its host frames (0: the call's stride).  Without pixel_format and equalize: back to the
+        handle's cfg.  From then on the frame-taking methods take, for that sequence, an array of its format's shape: [h, w], [h, w, bytes], u16 [h, w] for MONO16.
+        Refused (GfError) once the sequence has taken a frame, until reset_seq, and while a prefetched frame is waiting."""
+        if pixel_format is None and equalize is None and not host_stride:
+            _chk(lib().gf_tracker_set_seq_format(self.h, seq, None))
+            self._fmt.pop(int(seq), None)
+            return
+        f = TrackerSeqFormat()
+        _chk(lib().gf_tracker_get_seq_format(self.h, seq, C.byref(f)))
+        if pixel_format is not None:
+            f.pixel_format = int(pixel_format)
+        if equalize is not None:
+            f.equalize = int(equalize)
+        f.host_stride = int(host_stride)
+        _chk(lib().gf_tracker_set_seq_format(self.h, seq, C.byref(f)))
+        self._fmt[int(seq)] = (f.pixel_format, f.equalize, f.host_stride)
+
+    def get_seq_format(self, seq):
+        """gf_tracker_get_seq_format: what is in force for sequence `seq`, as a dict of pixel_format, equalize, host_stride"""
+        f = TrackerSeqFormat()
+        _chk(lib().gf_tracker_get_seq_format(self.h, seq, C.byref(f)))
+        return {k: getattr(f, k) for k, _ in TrackerSeqFormat._fields_}
+
+    def seq_pixel_format(self, seq):
+        """the pixel format in force for sequence `seq` (the handle's own unless set_seq_format gave it one)"""
+        return self._fmt.get(int(seq), (self.cfg.pixel_format,))[0]
+
+    def device_frame_offsets(self, seqs=None):
+        """the layout of the tight device entry points on a handle with formats per sequence: (byte offset of the frame of each listed sequence, total bytes) --
+        frame i has height x width x bytes per pixel of seqs[i] bytes and starts where the frames listed before it end"""
+        seqs = range(self.cfg.batch) if seqs is None else seqs
+        sizes = [self.cfg.height * self.cfg.width * pix_bytes(self.seq_pixel_format(q)) for q in seqs]
+        offs = [int(o) for o in np.concatenate([[0], np.cumsum(sizes)])]
+        return offs[:-1], offs[-1]
+
+    def _host_frames(self, seqs, imgs, stride):
+        """the host frames of a list on a handle with formats per sequence: each as u8 rows that lie its sequence's host_stride apart, or the call's stride
+        (default: the widest listed row) where it has none; a frame whose rows lie otherwise is copied into one that fits"""
+        rows = [None if i is None else _frame_rows(i, self.seq_pixel_format(q), self.cfg.width, self.cfg.height) for q, i in zip(seqs, imgs)]
+        own = [self._fmt.get(int(q), (0, 0, 0))[2] for q in seqs]
+        if stride is None:
+            stride = max([r.shape[1] for r, o in zip(rows, own) if r is not None and not o] + [self.cfg.width])
+        return [None if r is None else _with_pitch(r, o or stride) for r, o in zip(rows, own)], stride
 
     def get_seq_cfg(self, seq):
         """gf_tracker_get_seq_cfg: the parameters in force for sequence `seq`, as a dict of the twelve fields"""
@@ -596,6 +654,53 @@ def cvt_gray(frames, pixel_format):
     out = np.empty((b, h, w), np.uint8)
     _chk(lib().gf_cvt_gray_batch(C.c_void_p(a.ctypes.data), C.c_size_t(pitch), int(pixel_format), _p(out, C.c_uint8), b, w, h))
     return out[0] if single else out
+
+
+def _frame_rows(img, pixel_format, width=None, height=None):
+    """a frame of format PIX_* -- [h, w], [h, w, bytes] u8, or u16 [h, w] for PIX_MONO16 -- as a u8 [h, w x bytes] array of its rows (a view where the rows allow it)"""
+    ch = pix_bytes(pixel_format)
+    a = np.asarray(img)
+    if pixel_format == PIX_MONO16 and a.dtype == np.uint16:
+        a = np.ascontiguousarray(a, "<u2").view(np.uint8).reshape(a.shape + (2,))
+    if a.dtype != np.uint8 or a.ndim != (2 if ch == 1 else 3) or (ch > 1 and a.shape[2] != ch):
+        raise ValueError("a frame of pixel format %d must be u8 [h, w%s]%s, got %s %s" % (pixel_format, ", %d" % ch if ch > 1 else "", " or u16 [h, w]" if pixel_format == PIX_MONO16 else "", a.dtype, a.shape))
+    if width is not None and a.shape[:2] != (height, width):
+        raise ValueError("a frame of %dx%d where the handle takes %dx%d" % (a.shape[1], a.shape[0], width, height))
+    h, w = a.shape[:2]
+    if a.strides[1:] != ((ch, 1) if ch > 1 else (1,)) or a.strides[0] < w * ch:
+        a = np.ascontiguousarray(a)
+    return np.lib.stride_tricks.as_strided(a, (h, w * ch), (a.strides[0], 1), writeable=False)
+
+
+def _with_pitch(rows, pitch):
+    """u8 [h, n] rows -> the same rows `pitch` bytes apart (copied unless they lie so already; a pitch below n is left for the library to refuse)"""
+    if rows.strides[0] == pitch or pitch < rows.shape[1]:
+        return rows
+    buf = np.zeros((rows.shape[0], pitch), np.uint8)
+    buf[:, :rows.shape[1]] = rows
+    return buf[:, :rows.shape[1]]
+
+
+def cvt_gray_mixed(frames, formats):
+    """gf_cvt_gray_mixed: cv_bridge::toCvCopy(msg, MONO8) (rosNodeTest.cpp:238-254) on host frames that each have a format of their own, in two launches at the
+    most: frames[b] of formats[b] (PIX_*) in that format's shape; rows may be padded and the array may start at any address.  Returns tight [batch, h, w] frames."""
+    b = len(frames)
+    assert len(formats) == b and b > 0
+    fm = np.ascontiguousarray(formats, np.int32)
+    # (a value that is no format is the library's to refuse: its frame goes as the bytes it has)
+    rows = [_frame_rows(f, int(q)) if pix_bytes(int(q)) else _frame_rows(np.asarray(f, np.uint8).reshape(len(f), -1), PIX_MONO8) for f, q in zip(frames, fm)]
+    h, w = rows[0].shape[0], rows[0].shape[1] // (pix_bytes(int(fm[0])) or 1)
+    src = (C.c_void_p * b)(*[r.ctypes.data for r in rows])
+    pitch = (C.c_size_t * b)(*[r.strides[0] for r in rows])
+    out = np.empty((b, h, w), np.uint8)
+    _chk(lib().gf_cvt_gray_mixed(src, pitch, _p(fm, C.c_int), _p(out, C.c_uint8), b, w, h))
+    return out
+
+
+def cvt_gray_mixed_device(d_refs, d_formats, d_dst, batch, width, height, stream=0):
+    """gf_cvt_gray_mixed_device on integer device addresses: d_refs = a device-readable table of `batch` gf_frame_ref (16 bytes each: address of row 0, bytes from
+    row to row), d_formats = `batch` int32 PIX_* values (an entry that is no format is skipped); asynchronous on `stream`"""
+    _chk(lib().gf_cvt_gray_mixed_device(C.c_void_p(d_refs), C.c_void_p(d_formats), C.c_void_p(d_dst), batch, width, height, C.c_void_p(stream) if stream else None))
 
 
 def cvt_gray_device(d_src, src_pitch, pixel_format, d_dst, batch, width, height, stream=0):

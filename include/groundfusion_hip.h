@@ -63,8 +63,8 @@ typedef struct gf_tracker_cfg {
      * little-endian pixels.  The caller's frames are never written.  Host entry points: `stride` is bytes per row and must be >= width x bytes per pixel;
      * the staged path copies the frame as it is under the previous frame's kernels and converts on the tracking stream once the copy has landed.  Device entry
      * points: the frames are tight height x width x bytes per pixel, back to back in list order, or -- the _refs forms -- one pointer and row pitch per listed
-     * sequence (gf_frame_ref).  One handle has one format: a fleet of cameras with mixed
-     * encodings uses one handle per encoding.  Anything outside GF_PIX_MONO8 .. GF_PIX_BGRA8 and GF_PIX_BAYER_RGGB8 .. GF_PIX_MONO16 is refused by gf_tracker_create. */
+     * sequence (gf_frame_ref).  This is the format of every sequence that has none of its own: a fleet of cameras with mixed
+     * encodings sets them per sequence (gf_tracker_set_seq_format).  Anything outside GF_PIX_MONO8 .. GF_PIX_BGRA8 and GF_PIX_BAYER_RGGB8 .. GF_PIX_MONO16 is refused by gf_tracker_create. */
     int pixel_format;
 } gf_tracker_cfg;
 
@@ -103,7 +103,7 @@ typedef struct gf_tracker_stats {
      * the _refs calls: pointer or pitch no multiple of 16 where the pyramid or CLAHE reads the caller's frame, no multiple of 4 where a conversion kernel does;
      * 0 on a handle that only uses the other entry points */
     long long frames_unaligned;
-    double ms_convert;           /* the colour / raw -> MONO8 kernel of gf_tracker_cfg.pixel_format (hipEvents, like ms_equalize; part of ms_total_gpu); 0 on a MONO8 handle */
+    double ms_convert;           /* the colour / raw -> MONO8 kernels of pixel_format (hipEvents, like ms_equalize; part of ms_total_gpu); grows on the calls that convert a listed sequence */
     long long sequence_frames;   /* listed sequences summed over the calls (`frames` counts the calls): frames x batch for the lock-step entry points; stays the last member */
 } gf_tracker_stats;
 
@@ -153,11 +153,11 @@ int gf_tracker_track_some(gf_tracker* h, int count, const int* seq, const double
 int gf_tracker_track_some_device(gf_tracker* h, int count, const int* seq, const double* t, const void* d_gray, const void* d_depth,
                                  gf_feature_obs* out, int cap, int* n_out);
 /* A frame that already lives on the device, where its producer keeps it: the device pointer (current device) of the first byte of row 0 and the bytes from one
- * row to the next.  Any byte alignment of both; pitch >= width x bytes per pixel of the handle's pixel_format.  Frames of one call may lie in different
+ * row to the next.  Any byte alignment of both; pitch >= width x bytes per pixel of the sequence's pixel format (the handle's, or its own: gf_tracker_set_seq_format).  Frames of one call may lie in different
  * allocations, be views into larger surfaces (the luma plane of an NV12 / I420 surface, a crop of a wider image) and may alias each other.  Nothing behind a
  * gf_frame_ref is ever written. */
 typedef struct gf_frame_ref { const void* data; size_t pitch; } gf_frame_ref;
-/* trackImage (feature_tracker.h:47) on device images that are handed over by reference: gray[i] is the frame of seq[i] in the handle's pixel_format (height rows
+/* trackImage (feature_tracker.h:47) on device images that are handed over by reference: gray[i] is the frame of seq[i] in that sequence's pixel format (height rows
  * of width x bytes per pixel), depth is NULL or one entry per listed sequence of u16 millimetres (data and pitch even; an entry with data == NULL is allowed
  * exactly for a sequence whose depth_cam is 0).  Every other property of the call -- list semantics, count == 0, sequences that sit out, setPrediction /
  * removeOutliers, parameters per sequence, region of interest, equalize, statistics, synchronisation -- is that of gf_tracker_track_some_device, which is the
@@ -267,6 +267,32 @@ int gf_tracker_get_seq_cfg(gf_tracker* h, int seq, gf_tracker_seq_cfg* out);
  * unit takes over.  Keeps the sequence's parameters and its region of interest (they are settings), allows gf_tracker_set_seq_cfg again, touches no other
  * sequence. */
 int gf_tracker_reset_seq(gf_tracker* h, int seq);
+/* A pixel format and an equalise switch per sequence: what the reference's node does per camera ahead of trackImage, cv_bridge::toCvCopy(msg, MONO8) and the
+ * CLAHE of getImageFromMsg (rosNodeTest.cpp:238-261).  A sequence that was never set runs with the handle's gf_tracker_cfg.pixel_format / equalize, and a
+ * handle on which the setter is never called allocates, copies, records and launches exactly what it did without it.  With a format of its own, a tracker call
+ * for that sequence gives the bits of a handle created with cfg.pixel_format = pixel_format, cfg.equalize = equalize for the same frames -- observations, ids,
+ * gf_tracker_get_state, the track image -- through every entry point that takes frames, in the launches it shares with its neighbours: one conversion (two
+ * launches at the most, whatever the formats), one CLAHE launch over the equalised sequences, one pyramid.  A MONO8 sequence without equalisation is read by
+ * the pyramid where the caller's frame lies; it is not copied.
+ * Layouts.  Host list entry points: the row step of listed sequence i is host_stride if non-zero, otherwise the call's `stride`, and must be >= width x bytes
+ * per pixel of THAT sequence's format.  Tight device entry points: the frames lie back to back in list order, frame i has height x width x bytes per pixel of
+ * seq[i] bytes, so its offset is the sum of the frames listed before it.  _refs entry points: pitch >= width x bytes per pixel of that sequence's format.
+ * Depth frames are untouched.  A call with a too-short stride or pitch is refused naming the list position, and changes nothing.
+ * A setting, like gf_tracker_seq_cfg: fixed while the sequence holds tracking state (refused once it has taken a frame, until gf_tracker_reset_seq, which
+ * keeps it), refused while any frame staged by gf_tracker_prefetch_* is waiting (the staging buffers may have to grow).  The first setter that needs them
+ * allocates the conversion and equalisation buffers and LUTs for the batch and grows the staging buffers to the widest format set so far; GF_ERR_HIP and nothing
+ * changed if that fails.  Refused with GF_ERR_INVALID, a message that names the field, and nothing changed: a null handle, seq out of range, a pixel_format
+ * gf_tracker_create refuses, equalize not 0 / 1, host_stride < 0 or non-zero and below a row of the format.
+ * gf_tracker_stats.ms_convert / ms_equalize grow on the calls that convert / equalise at least one listed sequence, and only on those. */
+typedef struct gf_tracker_seq_format {
+    int pixel_format;  /* GF_PIX_*: the format of every frame this sequence is given */
+    int equalize;      /* 0 / 1: CLAHE (clip 40, 8 x 8) on this sequence's MONO8 frame before the pyramid */
+    int host_stride;   /* bytes per row of this sequence's HOST frames on the list entry points; 0 = the call's `stride` */
+} gf_tracker_seq_format;
+/* rosNodeTest.cpp:238-261 per sequence.  f == NULL: back to the handle's gf_tracker_cfg.pixel_format / equalize, host_stride 0 */
+int gf_tracker_set_seq_format(gf_tracker* h, int seq, const gf_tracker_seq_format* f);
+/* rosNodeTest.cpp:238-261 per sequence: what is in force for seq (the handle's values for a sequence that was never set) */
+int gf_tracker_get_seq_format(gf_tracker* h, int seq, gf_tracker_seq_format* out);
 /* The track image: SHOW_TRACK and FeatureTracker::getTrackImage() (feature_tracker.cpp:849-905 drawTrack, :1047; what the node publishes as image_track) -- the
  * MONO8 frame trackImage tracked on (after the handle's colour / raw conversion and equalisation) as height x width x 3 bytes in the reference's channel order
  * (labelled bgr8 there), a dot per feature coloured (255 (1 - len), 0, 255 len) by len = min(1, track_cnt / 20), and a green arrow from each feature that LK
@@ -337,6 +363,17 @@ int gf_clahe_batch(const uint8_t* src, uint8_t* dst, int batch, int width, int h
 int gf_cvt_gray_batch_device(const void* d_src, size_t src_pitch, int format, void* d_dst, int batch, int width, int height, void* stream);
 /* The same conversion (rosNodeTest.cpp:238-254) on host frames (copies in, converts, copies out; synchronous): the building block the parity tests call. */
 int gf_cvt_gray_batch(const uint8_t* src, size_t src_pitch, int format, uint8_t* dst, int batch, int width, int height);
+/* The same conversion (rosNodeTest.cpp:238-254) with a format of its own per frame, the building block of gf_tracker_set_seq_format: frame b lies at d_refs[b]
+ * (device pointer of row 0, bytes from row to row >= width x bytes per pixel of its format) in d_formats[b] -> tight height x width u8 frame b at d_dst.  Both
+ * tables are device-readable, [batch].  Each frame takes the load form its own pointer and pitch allow (any alignment) and gives the bytes
+ * gf_cvt_gray_batch_device gives for it; nothing behind a ref is written.  Two launches at the most whatever the formats and the batch.  Asynchronous on
+ * `stream`.  The host cannot read the tables: it refuses null pointers and sizes < 1 or beyond 2^31 - 1 pixels; an entry whose format is no GF_PIX_* writes
+ * nothing for that frame and reads nothing, and an entry with a short pitch or a Bayer frame under 3 x 3 is the caller's error. */
+int gf_cvt_gray_mixed_device(const gf_frame_ref* d_refs, const int* d_formats, void* d_dst, int batch, int width, int height, void* stream);
+/* The same (rosNodeTest.cpp:238-254) on host buffers (copies in, converts, copies out; synchronous): src[b], pitch[b], format[b] per frame; the device copy
+ * of a frame keeps its host pointer's phase (address & 15), so it takes the form it would take where it lies.  Refuses per frame, naming the frame, what
+ * gf_cvt_gray_batch refuses: an unknown format, a pitch below a row, a Bayer frame under 3 x 3, a source that overlaps the destination. */
+int gf_cvt_gray_mixed(const uint8_t* const* src, const size_t* pitch, const int* format, uint8_t* dst, int batch, int width, int height);
 int gf_tracker_get_stats(gf_tracker* h, gf_tracker_stats* out);
 int gf_tracker_reset_stats(gf_tracker* h);
 
