@@ -1958,6 +1958,11 @@ int gf_estimator_set_roi(gf_estimator* e, const uint8_t* mask, int stride) {
     if (!e || !e->tracker) return gf::set_err(GF_ERR_INVALID, "estimator was created without a tracker (cfg.with_tracker)");
     return gf_tracker_set_roi(e->tracker, 0, mask, stride);
 }
+// readIntrinsicParameter (feature_tracker.cpp:745-759) of the estimator's own tracker: the camera of its one sequence, before the first gf_estimator_input_image
+int gf_estimator_set_camera(gf_estimator* e, const gf_camera_model* camera) {
+    if (!e || !e->tracker) return gf::set_err(GF_ERR_INVALID, "estimator was created without a tracker (cfg.with_tracker)");
+    return gf_tracker_set_seq_camera(e->tracker, 0, camera);
+}
 // the exclusion boxes of the estimator's own tracker (gf_tracker_set_boxes_some on its one sequence): from the next gf_estimator_input_image on; n == 0 clears
 int gf_estimator_set_boxes(gf_estimator* e, const gf_box* boxes, int n) {
     if (!e || !e->tracker) return gf::set_err(GF_ERR_INVALID, "estimator was created without a tracker (cfg.with_tracker)");

@@ -21,6 +21,7 @@
 
 #include "../../include/groundfusion_hip.h"
 #include "../host/rosbag_reader.h"
+#include "gf_camera_models.hpp"
 #include "gf_dmath.hpp"
 
 namespace gf { int set_err(int code, const char* fmt, ...); }
@@ -155,8 +156,45 @@ int gf_show_track_from_yaml(const char* config_file, int* show_track) {
     return GF_OK;
 }
 
-int gf_estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* c) {
-    if (!config_file || !c) return gf::set_err(GF_ERR_INVALID, "null argument");
+// A camodocal calibration file already parsed (`path` names it in messages): model_type and the keys of the model's readFromYamlFile
+// (PinholeCamera.cc:145-183, CataCamera.cc:160-202, EquidistantCamera.cc:146-182); checked as every setter checks a model (gfcam::prepare).
+static int camera_from_doc(const YamlDoc& k, const char* path, gf_camera_model* out) {
+    const std::string type = k.has("model_type") ? k.str("model_type") : std::string("PINHOLE");   // CameraFactory.cc: a file without the key is a pinhole
+    gf_camera_model m;
+    memset(&m, 0, sizeof m);
+    const char* proj[4]; const char* dist[4]; const char* dist_node = "distortion_parameters";
+    if (type == "PINHOLE") { m.model = GF_CAMERA_PINHOLE; const char* p[4] = {"fx", "fy", "cx", "cy"}; const char* d[4] = {"k1", "k2", "p1", "p2"}; memcpy(proj, p, sizeof p); memcpy(dist, d, sizeof d); }
+    else if (type == "MEI") { m.model = GF_CAMERA_MEI; const char* p[4] = {"gamma1", "gamma2", "u0", "v0"}; const char* d[4] = {"k1", "k2", "p1", "p2"}; memcpy(proj, p, sizeof p); memcpy(dist, d, sizeof d); }
+    else if (type == "KANNALA_BRANDT") {   // EquidistantCamera keeps its polynomial among the projection parameters
+        m.model = GF_CAMERA_KANNALA_BRANDT; dist_node = "projection_parameters";
+        const char* p[4] = {"mu", "mv", "u0", "v0"}; const char* d[4] = {"k2", "k3", "k4", "k5"}; memcpy(proj, p, sizeof p); memcpy(dist, d, sizeof d);
+    }
+    else if (type == "PINHOLE_FULL" || type == "SCARAMUZZA") return gf::set_err(GF_ERR_INVALID, "%s: model_type '%s' is not built (PINHOLE, MEI and KANNALA_BRANDT are)", path, type.c_str());
+    else return gf::set_err(GF_ERR_INVALID, "%s: unknown model_type '%s' (PINHOLE, MEI and KANNALA_BRANDT are built)", path, type.c_str());
+    for (int i = 0; i < 4; i++) {
+        m.proj[i] = k.real(std::string("projection_parameters.") + proj[i]);
+        m.dist[i] = k.real(std::string(dist_node) + "." + dist[i]);
+    }
+    for (int i = 0; i < 2; i++)
+        if (!k.has(std::string("projection_parameters.") + proj[i])) return gf::set_err(GF_ERR_INVALID, "%s: projection_parameters.%s is missing", path, proj[i]);
+    if (m.model == GF_CAMERA_MEI) m.xi = k.real("mirror_parameters.xi");
+    gfcam::Camera checked;
+    char msg[320];
+    if (!gfcam::prepare(m, checked, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "%s: %s", path, msg);
+    *out = m;
+    return GF_OK;
+}
+
+int gf_camera_from_yaml(const char* calib_file, gf_camera_model* out) {
+    if (!calib_file || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    YamlDoc k;
+    std::string err;
+    if (!parse_yaml(calib_file, k, err)) return gf::set_err(GF_ERR_INVALID, "%s: %s", calib_file, err.c_str());
+    return camera_from_doc(k, calib_file, out);
+}
+
+// camera == null: gf_estimator_cfg_from_yaml, which takes a PINHOLE file alone
+static int estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* c, gf_camera_model* camera) {
     YamlDoc y;
     std::string err;
     if (!parse_yaml(config_file, y, err)) return gf::set_err(GF_ERR_INVALID, "%s: %s", config_file, err.c_str());
@@ -229,6 +267,14 @@ int gf_estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* c) {
     const std::string cam = (pn == std::string::npos ? std::string(".") : cf.substr(0, pn)) + "/" + y.str("cam0_calib");
     YamlDoc k;
     if (!parse_yaml(cam.c_str(), k, err)) return gf::set_err(GF_ERR_INVALID, "cam0_calib: %s", err.c_str());
+    if (camera) {
+        if (int rc = camera_from_doc(k, cam.c_str(), camera)) return rc;
+        if (camera->model != GF_CAMERA_PINHOLE) {   // valid placeholders: nothing reads them once gf_estimator_set_camera has the model
+            t.fx = camera->proj[0]; t.fy = camera->proj[1]; t.cx = camera->proj[2]; t.cy = camera->proj[3];
+            t.k1 = t.k2 = t.p1 = t.p2 = 0.0;
+            return GF_OK;
+        }
+    }
     if (k.has("model_type") && k.str("model_type") != "PINHOLE") return gf::set_err(GF_ERR_INVALID, "%s: model_type '%s': only PINHOLE is built", cam.c_str(), k.str("model_type").c_str());
     t.k1 = k.real("distortion_parameters.k1"); t.k2 = k.real("distortion_parameters.k2");
     t.p1 = k.real("distortion_parameters.p1"); t.p2 = k.real("distortion_parameters.p2");
@@ -236,6 +282,16 @@ int gf_estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* c) {
     t.cx = k.real("projection_parameters.cx"); t.cy = k.real("projection_parameters.cy");
     if (!(t.fx > 0) || !(t.fy > 0)) return gf::set_err(GF_ERR_INVALID, "%s: projection_parameters.fx / fy missing", cam.c_str());
     return GF_OK;
+}
+
+int gf_estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* c) {
+    if (!config_file || !c) return gf::set_err(GF_ERR_INVALID, "null argument");
+    return estimator_cfg_from_yaml(config_file, c, nullptr);
+}
+
+int gf_estimator_cfg_from_yaml_camera(const char* config_file, gf_estimator_cfg* c, gf_camera_model* camera) {
+    if (!config_file || !c || !camera) return gf::set_err(GF_ERR_INVALID, "null argument");
+    return estimator_cfg_from_yaml(config_file, c, camera);
 }
 
 int gf_tum_append(const char* path, double t, const double* P, const double* R) {

@@ -15,6 +15,7 @@
 #include <utility>
 #include <vector>
 
+#include "gf_camera_models.hpp"
 #include "gf_roi.hpp"
 #include "gf_seq_cfg.hpp"
 #include "gf_track_draw.hpp"
@@ -28,6 +29,9 @@ struct SeqState {  // per-sequence FeatureTracker members (feature_tracker.h:76-
     std::vector<P2f> prev_pts, cur_pts, predict_pts, prev_un_pts, cur_un_pts, pts_velocity;
     std::vector<int> ids, track_cnt;
     std::vector<uint16_t> cur_depth;
+    // the row of LK's tables each point of cur_pts came from, through the reduction by status and setMask's sort: where a lift that ran on the device left the
+    // point's pair (after_detect).  Kept for the sequences that need it (after_lk's keep_rows), empty otherwise
+    std::vector<int> lk_row;
     // cur_un_pts_map / prev_un_pts_map (feature_tracker.h:89): id -> point, kept as id-sorted vectors (ids are unique)
     std::vector<std::pair<int, P2f>> cur_un_pts_map, prev_un_pts_map;
     std::vector<int> grid_head, grid_next;  // scratch of set_mask_host
@@ -48,27 +52,13 @@ struct SeqState {  // per-sequence FeatureTracker members (feature_tracker.h:76-
 
 static inline int cvRoundf(float v) { return (int)lrintf(v); }
 
-// camodocal PinholeCamera (camera_models/src/camera_models/PinholeCamera.cc:450-510, :520-542, :646-662)
-inline void distortion(const gf_tracker_seq_cfg& c, double x, double y, double& dx, double& dy) {
-    double mx2 = x * x, my2 = y * y, mxy = x * y, rho2 = mx2 + my2, rad = c.k1 * rho2 + c.k2 * rho2 * rho2;
-    dx = x * rad + 2.0 * c.p1 * mxy + c.p2 * (rho2 + 2.0 * mx2);
-    dy = y * rad + 2.0 * c.p2 * mxy + c.p1 * (rho2 + 2.0 * my2);
-}
-inline bool no_distortion(const gf_tracker_seq_cfg& c) { return c.k1 == 0.0 && c.k2 == 0.0 && c.p1 == 0.0 && c.p2 == 0.0; }
-inline void lift_projective(const gf_tracker_seq_cfg& c, double u, double v, double& X, double& Y) {
-    const double i11 = 1.0 / c.fx, i13 = -c.cx / c.fx, i22 = 1.0 / c.fy, i23 = -c.cy / c.fy;
-    const double mx_d = i11 * u + i13, my_d = i22 * v + i23;
-    if (no_distortion(c)) { X = mx_d; Y = my_d; return; }
-    double dux, duy;
-    distortion(c, mx_d, my_d, dux, duy);
-    double mx_u = mx_d - dux, my_u = my_d - duy;
-    for (int i = 1; i < 8; ++i) { distortion(c, mx_u, my_u, dux, duy); mx_u = mx_d - dux; my_u = my_d - duy; }
-    X = mx_u; Y = my_u;
-}
+// camodocal PinholeCamera (camera_models/src/camera_models/PinholeCamera.cc:450-510, :520-542, :646-662) on the camera fields of a sequence's parameters: the
+// formulas are gf_camera_models.hpp, shared with the other models and with the device
+inline void distortion(const gf_tracker_seq_cfg& c, double x, double y, double& dx, double& dy) { gfcam::distortion(c.k1, c.k2, c.p1, c.p2, x, y, dx, dy); }
+inline bool no_distortion(const gf_tracker_seq_cfg& c) { return gfcam::no_distortion(c.k1, c.k2, c.p1, c.p2); }
+inline void lift_projective(const gf_tracker_seq_cfg& c, double u, double v, double& X, double& Y) { gfcam::undistort(c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2, u, v, X, Y); }
 inline void space_to_plane(const gf_tracker_seq_cfg& c, const double* P, double& u, double& v) {
-    double xu = P[0] / P[2], yu = P[1] / P[2], xd = xu, yd = yu;
-    if (!no_distortion(c)) { double dx, dy; distortion(c, xu, yu, dx, dy); xd = xu + dx; yd = yu + dy; }
-    u = c.fx * xd + c.cx; v = c.fy * yd + c.cy;
+    gfcam::distort_to_plane(c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2, P[0] / P[2], P[1] / P[2], u, v);
 }
 
 template <class V> inline void reduce_vector(std::vector<V>& v, const uint8_t* st) {  // feature_tracker.cpp:30-46
@@ -86,12 +76,13 @@ template <class V> inline void reduce_vector(std::vector<V>& v, const uint8_t* s
 // T: the circle of the sequence's min_dist.  width, height: the frame's.
 inline void set_mask_host(int width, int height, SeqState& s, const DiskTable& T, const uint32_t* roi, P2i* centers, int& n_centers, const gf_box* boxes = nullptr,
                           int n_boxes = 0) {
-    struct E { int cnt; P2f pt; int id; uint16_t depth; };
+    struct E { int cnt; P2f pt; int id; uint16_t depth; int row; };
     static thread_local std::vector<E> v;
     v.clear();
-    for (size_t i = 0; i < s.cur_pts.size(); i++) v.push_back({s.track_cnt[i], s.cur_pts[i], s.ids[i], s.cur_depth[i]});
+    const bool rows = s.lk_row.size() == s.cur_pts.size();   // a sequence that keeps no rows (after_lk) gets none back
+    for (size_t i = 0; i < s.cur_pts.size(); i++) v.push_back({s.track_cnt[i], s.cur_pts[i], s.ids[i], s.cur_depth[i], rows ? s.lk_row[i] : -1});
     std::sort(v.begin(), v.end(), [](const E& a, const E& b) { return a.cnt > b.cnt; });
-    s.cur_pts.clear(); s.ids.clear(); s.track_cnt.clear(); s.cur_depth.clear();
+    s.cur_pts.clear(); s.ids.clear(); s.track_cnt.clear(); s.cur_depth.clear(); s.lk_row.clear();
     n_centers = 0;
     // `mask.at(pt) == 255` <=> pt is inside no earlier kept point's filled circle; circles reach at most `radius`
     // pixels, so only centres in the 3x3 neighbourhood of radius-sized cells can cover pt.
@@ -112,6 +103,7 @@ inline void set_mask_host(int width, int height, SeqState& s, const DiskTable& T
                 }
         if (!covered) {
             s.cur_pts.push_back(it.pt); s.ids.push_back(it.id); s.track_cnt.push_back(it.cnt); s.cur_depth.push_back(it.depth);
+            if (rows) s.lk_row.push_back(it.row);
             centers[n_centers] = P2i{x, y};
             s.grid_next.push_back(s.grid_head[(size_t)cy * gw + cx]);
             s.grid_head[(size_t)cy * gw + cx] = n_centers++;
@@ -138,14 +130,19 @@ inline void pts_velocity(SeqState& s) {  // feature_tracker.cpp:810-847
     } else for (size_t i = 0; i < n; i++) s.pts_velocity[i] = {0.f, 0.f};
 }
 
-inline void set_prediction(SeqState& s, const gf_tracker_seq_cfg& par, const int* ids, const double* xyz, int n) {  // feature_tracker.cpp:1006-1027
+// cam: the sequence's camera where it is no pinhole (gf_tracker_set_seq_camera); null: the pinhole of par
+inline void set_prediction(SeqState& s, const gf_tracker_seq_cfg& par, const int* ids, const double* xyz, int n, const gfcam::Camera* cam = nullptr) {  // feature_tracker.cpp:1006-1027
     s.hasPrediction = true;
     s.predict_pts.clear();
     std::map<int, const double*> m;
     for (int i = 0; i < n; i++) m[ids[i]] = xyz + 3 * i;
     for (size_t i = 0; i < s.ids.size(); i++) {
         auto it = m.find(s.ids[i]);
-        if (it != m.end()) { double u, v; space_to_plane(par, it->second, u, v); s.predict_pts.push_back({(float)u, (float)v}); }
+        if (it != m.end()) {
+            double u, v;
+            if (cam) gfcam::space_to_plane(*cam, it->second, u, v); else space_to_plane(par, it->second, u, v);
+            s.predict_pts.push_back({(float)u, (float)v});
+        }
         else s.predict_pts.push_back(s.prev_pts[i]);
     }
 }
@@ -161,7 +158,7 @@ inline void remove_outliers(SeqState& s, const int* ids, int n) {  // feature_tr
 
 // The sequence takes a frame stamped t.  Returns the pyramid slot (0 or 1) the frame goes to; s.slot itself moves when the frame is done (after_detect).
 inline int begin_frame(SeqState& s, double t) {
-    s.cur_time = t; s.cur_pts.clear(); s.cur_depth.clear();
+    s.cur_time = t; s.cur_pts.clear(); s.cur_depth.clear(); s.lk_row.clear();
     s.started = true;
     return s.slot ^ 1;
 }
@@ -202,14 +199,16 @@ struct LkTally { long long level_passes = 0, iterations = 0, points = 0, tracked
 
 // After LK (feature_tracker.cpp:170-186): the reduction by status, track_cnt++, setMask and the number of corners the sequence wants.
 // T: the circle of par.min_dist; roi: the sequence's region of interest or null; centers_row / *n_centers: setMask's kept points for the detector;
-// boxes, n_boxes: the sequence's exclusion boxes, as set_mask_host takes them.
+// boxes, n_boxes: the sequence's exclusion boxes, as set_mask_host takes them.  keep_rows: the sequence's pairs come from a lift on the device (after_detect's
+// un_lk): every kept point carries the row of LK's table it came from (SeqState::lk_row).
 inline LkTally after_lk(SeqState& s, const gf_tracker_seq_cfg& par, int width, int height, const DiskTable& T, const uint32_t* roi, const LkRows& r,
-                        P2i* centers_row, int* n_centers, int* want, const gf_box* boxes = nullptr, int n_boxes = 0) {
+                        P2i* centers_row, int* n_centers, int* want, const gf_box* boxes = nullptr, int n_boxes = 0, bool keep_rows = false) {
     LkTally tally;
     const int n = (int)s.prev_pts.size();
     if (n > 0) {
         const uint8_t* st = r.status;
         s.cur_pts.resize(n); s.cur_depth.resize(n);
+        if (keep_rows) { s.lk_row.resize(n); for (int i = 0; i < n; i++) s.lk_row[i] = i; }
         for (int i = 0; i < n; i++) {
             const P2f c = r.cur_pts[i];
             s.cur_pts[i] = c;
@@ -222,6 +221,7 @@ inline LkTally after_lk(SeqState& s, const gf_tracker_seq_cfg& par, int width, i
         tally.points = n;
         reduce_vector(s.prev_pts, st); reduce_vector(s.cur_pts, st); reduce_vector(s.ids, st); reduce_vector(s.track_cnt, st);
         reduce_vector(s.cur_depth, st);
+        if (keep_rows) reduce_vector(s.lk_row, st);
         tally.tracked = (long long)s.cur_pts.size();
     }
     if (s.show_track) {   // the arrows' far ends, while prev_pts and ids still go by the same index
@@ -246,14 +246,21 @@ struct Packed { int written; int overflow; };   // observations written; or over
 
 // After the detection (feature_tracker.cpp:85-93, 210-211, 322-368): addPoints, undistortedPts, ptsVelocity, the roll-over of prev_* and of the pyramid slot,
 // and the featureFrame into out[0 .. cap_out).  have_depth: the call came with depth images.
-inline Packed after_detect(SeqState& s, const gf_tracker_seq_cfg& par, const DetectRows& r, bool have_depth, gf_feature_obs* out, int cap_out) {
+// cam: the sequence's camera where it is no pinhole (gf_tracker_set_seq_camera); null: the pinhole of par, lifted here as ever.  un_lk / un_out: the pairs a
+// lift on the device left for the rows of LK's table and of the detection's (a tracked point picks its own by the row it came from, a new corner by position);
+// both null: the model's lift runs here, per point.
+inline Packed after_detect(SeqState& s, const gf_tracker_seq_cfg& par, const DetectRows& r, bool have_depth, gf_feature_obs* out, int cap_out,
+                           const gfcam::Camera* cam = nullptr, const P2f* un_lk = nullptr, const P2f* un_out = nullptr) {
+    const size_t n_tracked = s.cur_pts.size();
     for (int i = 0; i < r.out_n; i++) {
         const P2f p = r.out_pts[i];
         s.cur_pts.push_back(p); s.ids.push_back(s.n_id++); s.track_cnt.push_back(1);
         s.cur_depth.push_back(r.host_depth ? r.host_depth[(size_t)(int)p.y * r.host_dstride + (int)p.x] : !r.out_depth ? (uint16_t)0 : r.out_depth[i]);   // corners sit on pixel centres
     }
     s.cur_un_pts.clear();
-    for (auto& p : s.cur_pts) { double X, Y; lift_projective(par, (double)p.x, (double)p.y, X, Y); s.cur_un_pts.push_back({(float)(X / 1.0), (float)(Y / 1.0)}); }
+    if (!cam) for (auto& p : s.cur_pts) { double X, Y; lift_projective(par, (double)p.x, (double)p.y, X, Y); s.cur_un_pts.push_back({(float)(X / 1.0), (float)(Y / 1.0)}); }
+    else if (un_lk && un_out) for (size_t i = 0; i < s.cur_pts.size(); i++) s.cur_un_pts.push_back(i < n_tracked ? un_lk[s.lk_row[i]] : un_out[i - n_tracked]);
+    else for (auto& p : s.cur_pts) { double P[3]; P2f o; gfcam::lift_pair(*cam, (double)p.x, (double)p.y, P, o.x, o.y); s.cur_un_pts.push_back(o); }
     pts_velocity(s);
     s.prev_pts = s.cur_pts; s.prev_un_pts = s.cur_un_pts; s.prev_un_pts_map.swap(s.cur_un_pts_map); s.prev_time = s.cur_time;
     s.hasPrediction = false;

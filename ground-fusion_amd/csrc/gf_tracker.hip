@@ -10,7 +10,7 @@
 //   run_lk         stage_points per sequence, tables down, one or two LK launches, tables up; the host waits
 //   redo_fallback  LK from scratch for the predicted sequences with fewer than 10 forward successes
 //   book_after_lk  per sequence on the pool (after_lk): reduction by status, setMask, the corners wanted
-//   run_detect     tables down, detector, selection, tables up; the host waits
+//   run_detect     tables down, detector, selection, the lift of the sequences whose camera is no pinhole (launch_lift), tables up; the host waits
 //   read_profile, check_candidates   event times; the candidate capacity and the selection-branch counters
 //   book_after_detect  per sequence on the pool (after_detect): addPoints, lift, velocities, roll-over, packing; then the stats
 // There is no CPU fallback: without a HIP device every entry point fails with GF_ERR_NO_DEVICE.
@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/groundfusion_hip.h"
+#include "gf_camera_models.hpp"
 #include "gf_comm.hpp"
 #include "gf_detect_kernels.hpp"
 #include "gf_lk_kernels.hpp"
@@ -59,6 +60,8 @@ int cvt_launch_refs(const gf_frame_ref* d_refs, const gf_frame_ref* h_refs, int 
 int cvt_launch_mixed(const gf_frame_ref* d_refs, const int* d_formats, const gf_frame_ref* h_refs, const int* h_formats, uint8_t* d_dst, int batch, int w, int h, hipStream_t stream);
 // gf_track_draw.hip: the track image of `count` frames, one per entry of d_jobs (gf_track_draw.hpp), in one launch
 int draw_track_launch(const gfdraw::DrawJob* d_jobs, int count, int w, int h, hipStream_t stream);
+// gf_camera.hip: liftProjective of the listed entries' cameras (gf_tracker_set_seq_camera), one launch
+int camera_lift_launch(const gfcam::LiftArgs& A, int max_n, hipStream_t stream);
 constexpr double kClaheClip = 40.0;   // cv::createCLAHE() defaults (rosNodeTest.cpp:258)
 constexpr int kClaheTiles = 8;
 
@@ -231,6 +234,17 @@ struct gf_tracker {
     gfseqfmt::Plan plan;                     // of the call in progress (plan_call)
     std::vector<gf_frame_ref> plan_frames;   // scratch: where the caller's frames of that call lie
     DevBuf<uint8_t> d_mix; PinBuf<uint8_t> h_mix;
+    // A camera model per sequence (gf_camera_models.hpp; gf_tracker_set_seq_camera), the sixth thing addressed by SEQUENCE.  Everything here is obtained by the
+    // first setter that gives a sequence a model other than PINHOLE; a pinhole stays the eight fields of par[seq] and is lifted on the host as ever.  cam_on[seq]:
+    // the sequence has such a model, cam_model / cam[seq] as it was set / as the formulas read it, d_cams the same table on the device (a row written by the
+    // setter).  Per call, by list position: cam_of (the sequence, or -1 for a pinhole one, which the kernel skips) and the two tables of lifted pairs, for the rows
+    // of LK's points and of the new corners, which come up with the call's last copies.  lift_host (GF_CAMERA_LIFT_HOST=1): none of the per-call tables is used,
+    // after_detect lifts with the same header.
+    bool lift_host = false;
+    std::vector<uint8_t> cam_on; std::vector<gf_camera_model> cam_model; std::vector<gfcam::Camera> cam;
+    DevBuf<gfcam::Camera> d_cams;
+    DevBuf<int> d_cam_of; PinBuf<int> h_cam_of;
+    DevBuf<float2> d_un_lk, d_un_out; PinBuf<float2> h_un_lk, h_un_out;
 
     std::unique_ptr<HostPool> pool;
 };
@@ -597,6 +611,7 @@ struct Call {
     bool refs_down = false;               // its depth half is still wanted on the device: with the first copy list that leaves
     const uint16_t* kdepth = nullptr;     // what LK and the selection sample: tight device depth frames, the device table's depth half (depth_by_refs) or null
     bool any_prev = false, any_pred = false, any_plain = false, any_want = false;
+    bool lift = false;                    // a listed sequence has a camera that is lifted on the device (run_detect, book_after_detect)
     bool mixed = false;                   // a listed sequence runs with a format or switch that is not the handle's own: the front goes through h->plan
     const uint8_t* mix = nullptr;         // the table of a mixed call where the front's kernels read it (h_mix over the bus, or d_mix)
     bool did_cvt = false, did_eq = false; // the call converted / equalised at least one listed sequence (read_profile)
@@ -798,7 +813,7 @@ static void book_after_lk(Call& c) {
         int want = 0;
         const gf_box* boxes = h->boxes.empty() ? nullptr : h->boxes[q].data();
         const LkTally n = after_lk(h->seq[q], par, h->cfg.width, h->cfg.height, h->seq_disk.empty() ? h->disk : h->seq_disk[q], roi, r, row(h->h_centers, b, cap), h->h_ncenters.p + b, &want,
-                                   boxes, boxes ? (int)h->boxes[q].size() : 0);
+                                   boxes, boxes ? (int)h->boxes[q].size() : 0, h->d_cams.p && !h->lift_host && h->cam_on[q]);
         a_levels += n.level_passes; a_iters += n.iterations; a_points += n.points; a_tracked += n.tracked;
         h->h_want.p[b] = want;
         if (h->h_seq_md.p) h->h_seq_md.p[b] = par.min_dist;
@@ -807,7 +822,24 @@ static void book_after_lk(Call& c) {
         h->h_out_n.p[b] = 0;
     });
     c.any_want = a_want.load() != 0;
+    if (h->d_cams.p && !h->lift_host)
+        for (int b = 0; b < c.N; b++) { const int q = c.seq[b]; h->h_cam_of.p[b] = h->cam_on[q] ? q : -1; c.lift |= h->cam_on[q] != 0; }
     h->stats.lk_level_passes += a_levels; h->stats.lk_iterations += a_iters; h->stats.lk_points += a_points; h->stats.tracked_features += a_tracked;
+}
+
+// undistortedPts (feature_tracker.cpp:797-808) for the listed sequences whose camera is no pinhole, in one launch behind the selection: every row of LK's points
+// (tracked or not: the host picks by row) and the new corners, where they lie on the device.  d_npts is this call's only if LK ran, d_out_n only if the
+// detection did; a table without counts is not lifted.
+static_assert(sizeof(float2) == sizeof(gfcam::Pair) && alignof(float2) == alignof(gfcam::Pair), "float2 tables are passed as tables of gfcam::Pair");
+static gfcam::Pair* pairs(float2* p) { return reinterpret_cast<gfcam::Pair*>(p); }
+static int launch_lift(Call& c) {
+    gf_tracker* h = c.h;
+    gfcam::LiftArgs A{};
+    A.cams = h->d_cams.p; A.cam_of = h->d_cam_of.p; A.first = nullptr; A.cap = h->cap; A.batch = c.N; A.n_sets = 2;
+    A.set[0] = gfcam::LiftSet{pairs(h->d_cur_pts.p), c.any_prev ? h->d_npts.p : nullptr, pairs(h->d_un_lk.p), nullptr};
+    A.set[1] = gfcam::LiftSet{pairs(h->d_out_pts.p), c.any_want ? h->d_out_n.p : nullptr, pairs(h->d_un_out.p), nullptr};
+    if (!c.any_prev && !c.any_want) return GF_OK;
+    return camera_lift_launch(A, h->cap, h->stream);
 }
 
 // Shi-Tomasi top-up (feature_tracker.cpp:190-206) for the sequences that want corners.  Returns with the stream drained.
@@ -824,6 +856,7 @@ static int run_detect(Call& c) {
         ho.down(h->d_want, h->h_want, N);
         if (h->d_seq_md.p) ho.down(h->d_seq_md, h->h_seq_md, N);
         ho.down(h->d_out_n, h->h_out_n, N);   // zeros (book_after_lk): a sequence that neither selection kernel serves reads 0, not an earlier call's count
+        if (c.lift) ho.down(h->d_cam_of, h->h_cam_of, N);
         if (int rc = ho.flush()) return rc;
         HIPCHK(hipMemsetAsync(h->d_maxkey.p, 0, N * sizeof(unsigned), h->stream));
         HIPCHK(hipMemsetAsync(h->d_cand_count.p, 0, N * sizeof(int), h->stream));
@@ -836,13 +869,22 @@ static int run_detect(Call& c) {
         const SelectArgs S = select_args(h, c.kdepth, topk ? 1 : 0);
         if (c.in.depth_by_refs()) launch_select<true>(h, N, S, topk, sort); else launch_select<false>(h, N, S, topk, sort);
         HIPCHK(hipGetLastError());
+        if (c.lift) if (int rc = launch_lift(c)) return rc;
         ho.up(h->h_out_n, h->d_out_n, N);
         ho.up(h->h_out_pts, h->d_out_pts, (size_t)N * cap);
         ho.up(h->h_out_depth, h->d_out_depth, (size_t)N * cap);
         ho.up(h->h_cand_count, h->d_cand_count, N);
+        if (c.lift) { ho.up(h->h_un_lk, h->d_un_lk, (size_t)N * cap); ho.up(h->h_un_out, h->d_un_out, (size_t)N * cap); }
         if (int rc = ho.flush()) return rc;
     }
     if (prof && !c.any_want) HIPCHK(hipEventRecord(h->ev[4], h->stream));
+    if (c.lift && !c.any_want) {   // no sequence wants corners: the tracked points alone
+        ho.down(h->d_cam_of, h->h_cam_of, N);
+        if (int rc = ho.flush()) return rc;
+        if (int rc = launch_lift(c)) return rc;
+        ho.up(h->h_un_lk, h->d_un_lk, (size_t)N * cap);
+        if (int rc = ho.flush()) return rc;
+    }
     if (prof) HIPCHK(hipEventRecord(h->ev[5], h->stream));
     c.lap(h->stats.ms_host_mid);
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -891,7 +933,9 @@ static int book_after_detect(Call& c, gf_feature_obs* out, int cap_out, int* n_o
     h->pool->parallel_for(c.N, [&](int b) {   // b: list position
         const int q = c.seq[b];
         const DetectRows r{row(h->h_out_pts, b, cap), c.in.kernel_samples(h->h_out_depth, b, cap), h->h_want.p[b] > 0 ? h->h_out_n.p[b] : 0, c.in.host_image(b, h->par[q]), c.in.host_dstride};
-        const Packed p = after_detect(h->seq[q], h->par[q], r, have_depth, out + (size_t)b * cap_out, cap_out);
+        const bool own = !h->cam_on.empty() && h->cam_on[q];
+        const Packed p = after_detect(h->seq[q], h->par[q], r, have_depth, out + (size_t)b * cap_out, cap_out, own ? &h->cam[q] : nullptr,
+                                      own && c.lift ? row(h->h_un_lk, b, cap) : nullptr, own && c.lift ? row(h->h_un_out, b, cap) : nullptr);
         if (h->seq[q].show_track) (void)record_track(h->seq[q], h->boxes.empty() ? nullptr : h->boxes[q].data(), h->boxes.empty() ? 0 : (int)h->boxes[q].size());   // a refused list: the sequence has no picture of this frame, and keeps the reason (draw_why)
         if (p.overflow >= 0) a_overflow = p.overflow;
         n_out[b] = p.written;
@@ -975,6 +1019,7 @@ int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out) {
         h->copy_lists = !(getenv("GF_TRACKER_COPIES") && atoi(getenv("GF_TRACKER_COPIES")) != 0);
         h->pyr_head = !(getenv("GF_PYR_HEAD") && atoi(getenv("GF_PYR_HEAD")) == 0);
         h->select_topk = !(getenv("GF_SELECT_TOPK") && atoi(getenv("GF_SELECT_TOPK")) == 0);
+        if (const char* e = getenv("GF_CAMERA_LIFT_HOST")) h->lift_host = atoi(e) != 0;
         if (const char* e = getenv("GF_LK_POINTS")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) h->lk_points = v; }
     }
     const int W = cfg->width, H = cfg->height, B = h->B, cap = h->cap;
@@ -1170,7 +1215,7 @@ int gf_tracker_track(gf_tracker* h, int seq, double t, const uint8_t* gray, int 
 
 int gf_tracker_set_prediction(gf_tracker* h, int seq, const int* ids, const double* xyz, int n) {
     if (!h || seq < 0 || seq >= h->B || (n > 0 && (!ids || !xyz))) return gf::set_err(GF_ERR_INVALID, "bad argument");
-    gf::set_prediction(h->seq[seq], h->par[seq], ids, xyz, n);
+    gf::set_prediction(h->seq[seq], h->par[seq], ids, xyz, n, !h->cam_on.empty() && h->cam_on[seq] ? &h->cam[seq] : nullptr);
     return GF_OK;
 }
 
@@ -1348,6 +1393,50 @@ int gf_tracker_get_seq_cfg(gf_tracker* h, int seq, gf_tracker_seq_cfg* out) {
     if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
     if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
     *out = h->par[seq];
+    return GF_OK;
+}
+
+// ---- a camera model per sequence (gf_camera_models.hpp; readIntrinsicParameter, feature_tracker.cpp:745-759).  Between frames, with the stream drained.
+namespace gf {
+static int seq_camera_ready(gf_tracker* h) {   // the first setter of a model other than PINHOLE: the cameras by sequence, the list and the two tables of pairs by list position
+    if (h->d_cams.p) return GF_OK;
+    const size_t B = (size_t)h->B, cap = (size_t)h->cap;
+    DevBuf<gfcam::Camera> cams; DevBuf<int> of; PinBuf<int> hof; DevBuf<float2> lk, out; PinBuf<float2> hlk, hout;
+    HIPCHK(cams.alloc(B)); HIPCHK(of.alloc(B)); HIPCHK(hof.alloc(B));
+    HIPCHK(lk.alloc(B * cap)); HIPCHK(out.alloc(B * cap)); HIPCHK(hlk.alloc(B * cap)); HIPCHK(hout.alloc(B * cap));
+    h->cam_on.assign(B, 0); h->cam_model.assign(B, gf_camera_model{}); h->cam.assign(B, gfcam::Camera{});
+    h->d_cams = std::move(cams); h->d_cam_of = std::move(of); h->h_cam_of = std::move(hof);
+    h->d_un_lk = std::move(lk); h->d_un_out = std::move(out); h->h_un_lk = std::move(hlk); h->h_un_out = std::move(hout);
+    return GF_OK;
+}
+}  // namespace gf
+
+int gf_tracker_set_seq_camera(gf_tracker* h, int seq, const gf_camera_model* m) {
+    if (!h || !m) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    if (h->seq[seq].started) return gf::set_err(GF_ERR_INVALID, "sequence %d has taken a frame: its camera is fixed until gf_tracker_reset_seq", seq);
+    if (gf::seq_is_staged(h, seq)) return gf::set_err(GF_ERR_INVALID, "sequence %d is listed by a staged frame: gf_tracker_track_prefetched has to consume it first", seq);
+    gfcam::Camera checked;
+    char msg[320];
+    if (!gfcam::prepare(*m, checked, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "sequence %d: %s", seq, msg);
+    if (m->model == GF_CAMERA_PINHOLE) {   // the eight camera fields of the sequence's parameters, through their own setter
+        gf_tracker_seq_cfg want = h->par[seq];
+        want.fx = m->proj[0]; want.fy = m->proj[1]; want.cx = m->proj[2]; want.cy = m->proj[3];
+        want.k1 = m->dist[0]; want.k2 = m->dist[1]; want.p1 = m->dist[2]; want.p2 = m->dist[3];
+        if (int rc = gf_tracker_set_seq_cfg(h, seq, &want)) return rc;
+        if (!h->cam_on.empty()) h->cam_on[seq] = 0;
+        return GF_OK;
+    }
+    if (int rc = gf::seq_camera_ready(h)) return rc;
+    HIPCHK(hipMemcpy(h->d_cams.p + seq, &checked, sizeof checked, hipMemcpyHostToDevice));
+    h->cam[seq] = checked; h->cam_model[seq] = *m; h->cam_on[seq] = 1;
+    return GF_OK;
+}
+
+int gf_tracker_get_seq_camera(gf_tracker* h, int seq, gf_camera_model* out) {
+    if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    *out = !h->cam_on.empty() && h->cam_on[seq] ? h->cam_model[seq] : gfcam::pinhole_of(h->par[seq]);
     return GF_OK;
 }
 

@@ -130,6 +130,77 @@ def roi_boxes_batch(lists, width, height, base_masks=None):
     return out
 
 
+CAMERA_PINHOLE, CAMERA_MEI, CAMERA_KANNALA_BRANDT = 0, 1, 2   # GF_CAMERA_*
+CAMERA_NAMES = {"PINHOLE": CAMERA_PINHOLE, "MEI": CAMERA_MEI, "KANNALA_BRANDT": CAMERA_KANNALA_BRANDT}
+
+
+class CameraModel(C.Structure):
+    """gf_camera_model: a camodocal camera -- proj = fx fy cx cy | gamma1 gamma2 u0 v0 | mu mv u0 v0, dist = k1 k2 p1 p2 | k1 k2 p1 p2 | k2 k3 k4 k5, xi (MEI)"""
+    _fields_ = [("model", C.c_int32), ("reserved", C.c_int32), ("proj", C.c_double * 4), ("dist", C.c_double * 4), ("xi", C.c_double)]
+
+    @classmethod
+    def make(cls, model, proj, dist=(0.0, 0.0, 0.0, 0.0), xi=0.0):
+        """model: CAMERA_* or its camodocal name"""
+        m = cls()
+        m.model = CAMERA_NAMES[model] if isinstance(model, str) else int(model)
+        m.proj[:] = [float(v) for v in proj]
+        m.dist[:] = [float(v) for v in dist]
+        m.xi = float(xi)
+        return m
+
+    def as_dict(self):
+        return {"model": self.model, "proj": list(self.proj), "dist": list(self.dist), "xi": self.xi}
+
+
+assert C.sizeof(CameraModel) == 80
+
+
+def _camera_batch(cams, counts):
+    """(gf_camera_model[batch], first [batch + 1] int32) of a list of CameraModel and the sequences' point counts"""
+    arr = (CameraModel * len(cams))(*cams)
+    first = np.zeros(len(cams) + 1, np.int32)
+    first[1:] = np.cumsum(counts)
+    return arr, first
+
+
+def camera_lift(cams, points, rays=True):
+    """gf_camera_lift_batch: liftProjective of cams[b] on points[b] ([n_b, 2] float pixels) through the tracker's kernel -> (un, rays): lists of [n_b, 2] float32
+    pairs (float)(P.x / P.z), (float)(P.y / P.z) and of [n_b, 3] float64 rays P (rays=False: None, the kernel writes none)"""
+    pts = [np.ascontiguousarray(p, np.float32).reshape(-1, 2) for p in points]
+    arr, first = _camera_batch(cams, [len(p) for p in pts])
+    uv = np.ascontiguousarray(np.concatenate(pts) if pts else np.zeros((0, 2)), np.float32)
+    n = len(uv)
+    un = np.zeros((n, 2), np.float32)
+    ray = np.zeros((n, 3), np.float64) if rays else None
+    _chk(lib().gf_camera_lift_batch(arr, len(cams), _p(first, C.c_int), _p(uv, C.c_float), _p(ray, C.c_double) if rays else None, _p(un, C.c_float)))
+    cut = lambda a: [a[first[b]:first[b + 1]] for b in range(len(cams))]
+    return cut(un), (cut(ray) if rays else None)
+
+
+def camera_lift_device(cams, counts, d_uv, d_rays, d_un, stream=0):
+    """gf_camera_lift_batch_device: the same on device arrays (integer addresses; d_rays 0 / None: no rays); cams and the sequences' point counts stay on the host"""
+    arr, first = _camera_batch(cams, counts)
+    _chk(lib().gf_camera_lift_batch_device(arr, len(cams), _p(first, C.c_int), C.c_void_p(d_uv), C.c_void_p(d_rays) if d_rays else None, C.c_void_p(d_un),
+                                           C.c_void_p(stream) if stream else None))
+
+
+def camera_project(cams, xyz):
+    """gf_camera_project_batch: spaceToPlane of cams[b] on xyz[b] ([n_b, 3]) on the host -> list of [n_b, 2] float64 pixels"""
+    pts = [np.ascontiguousarray(p, np.float64).reshape(-1, 3) for p in xyz]
+    arr, first = _camera_batch(cams, [len(p) for p in pts])
+    flat = np.ascontiguousarray(np.concatenate(pts) if pts else np.zeros((0, 3)), np.float64)
+    uv = np.zeros((len(flat), 2), np.float64)
+    _chk(lib().gf_camera_project_batch(arr, len(cams), _p(first, C.c_int), _p(flat, C.c_double), _p(uv, C.c_double)))
+    return [uv[first[b]:first[b + 1]] for b in range(len(cams))]
+
+
+def camera_from_yaml(calib_file):
+    """gf_camera_from_yaml: a camodocal calibration file (PINHOLE, MEI, KANNALA_BRANDT) -> CameraModel"""
+    m = CameraModel()
+    _chk(lib().gf_camera_from_yaml(os.fsencode(calib_file), C.byref(m)))
+    return m
+
+
 OBS_DTYPE = np.dtype([("id", np.int32), ("camera_id", np.int32), ("v", np.float64, (8,))])
 assert OBS_DTYPE.itemsize == C.sizeof(FeatureObs)
 
@@ -143,7 +214,9 @@ EXPORTS = ["gf_last_error", "gf_device_count", "gf_set_device", "gf_tracker_crea
            "gf_tracker_set_show_track", "gf_tracker_track_image_some_device", "gf_tracker_track_image", "gf_draw_track_batch",
            "gf_estimator_set_show_track", "gf_estimator_get_track_image", "gf_show_track_from_yaml",
            "gf_tracker_set_boxes_some", "gf_tracker_get_boxes", "gf_roi_boxes_batch", "gf_estimator_set_boxes", "gf_draw_track_boxes_batch",
-           "gf_tracker_set_seq_format", "gf_tracker_get_seq_format", "gf_cvt_gray_mixed", "gf_cvt_gray_mixed_device"]
+           "gf_tracker_set_seq_format", "gf_tracker_get_seq_format", "gf_cvt_gray_mixed", "gf_cvt_gray_mixed_device",
+           "gf_tracker_set_seq_camera", "gf_tracker_get_seq_camera", "gf_camera_lift_batch", "gf_camera_lift_batch_device", "gf_camera_project_batch",
+           "gf_camera_from_yaml", "gf_estimator_cfg_from_yaml_camera", "gf_estimator_set_camera"]
 
 
 def lib():
@@ -459,6 +532,17 @@ class FeatureTracker:
         for k, v in fields.items():
             setattr(c, k, v)
         _chk(lib().gf_tracker_set_seq_cfg(self.h, seq, C.byref(c)))
+
+    def set_seq_camera(self, seq, camera):
+        """gf_tracker_set_seq_camera: sequence `seq` gets the camera `camera` (CameraModel): its lift and its projection are that model's.  Refused (GfError) once
+        the sequence has taken a frame, until reset_seq, and while a prefetched frame lists it."""
+        _chk(lib().gf_tracker_set_seq_camera(self.h, seq, C.byref(camera)))
+
+    def get_seq_camera(self, seq):
+        """gf_tracker_get_seq_camera: the camera in force for sequence `seq` (the pinhole of its parameters ahead of any setter)"""
+        m = CameraModel()
+        _chk(lib().gf_tracker_get_seq_camera(self.h, seq, C.byref(m)))
+        return m
 
     def set_seq_format(self, seq, pixel_format=None, equalize=None, host_stride=0):
         """gf_tracker_set_seq_format: sequence `seq` takes frames of `pixel_format` (PIX_*) and is equalised or not, whatever the handle's cfg says; a field left
@@ -1208,6 +1292,10 @@ class SlidingWindowEstimator:
         b = _boxes(boxes)
         _chk(lib().gf_estimator_set_boxes(self.h, b.ctypes.data_as(C.POINTER(Box)) if len(b) else None, len(b)))
 
+    def set_camera(self, camera):
+        """gf_estimator_set_camera: the camera (CameraModel) of the estimator's own tracker, before its first image"""
+        _chk(lib().gf_estimator_set_camera(self.h, C.byref(camera)))
+
     def set_show_track(self, on=True):
         """gf_estimator_set_show_track: SHOW_TRACK of the estimator's own tracker"""
         _chk(lib().gf_estimator_set_show_track(self.h, int(bool(on))))
@@ -1298,6 +1386,13 @@ def estimator_cfg_from_yaml(config_file):
     c = EstimatorCfg()
     _chk(lib().gf_estimator_cfg_from_yaml(os.fsencode(config_file), C.byref(c)))
     return c
+
+
+def estimator_cfg_from_yaml_camera(config_file):
+    """gf_estimator_cfg_from_yaml_camera: the same with a PINHOLE, MEI or KANNALA_BRANDT cam0_calib file -> (EstimatorCfg, CameraModel for set_camera)"""
+    c, m = EstimatorCfg(), CameraModel()
+    _chk(lib().gf_estimator_cfg_from_yaml_camera(os.fsencode(config_file), C.byref(c), C.byref(m)))
+    return c, m
 
 
 def show_track_from_yaml(config_file):

@@ -293,6 +293,50 @@ typedef struct gf_tracker_seq_format {
 int gf_tracker_set_seq_format(gf_tracker* h, int seq, const gf_tracker_seq_format* f);
 /* rosNodeTest.cpp:238-261 per sequence: what is in force for seq (the handle's values for a sequence that was never set) */
 int gf_tracker_get_seq_format(gf_tracker* h, int seq, gf_tracker_seq_format* out);
+/* A camera model per sequence: what FeatureTracker::readIntrinsicParameter (feature_tracker.cpp:745-759) gets from CameraFactory::generateCameraFromYamlFile --
+ * camodocal's PINHOLE (PinholeCamera), MEI (CataCamera) or KANNALA_BRANDT (EquidistantCamera); PINHOLE_FULL and SCARAMUZZA are not built.  liftProjective
+ * (undistortedPts, feature_tracker.cpp:797-808) and spaceToPlane (setPrediction, :1006-1027) of the sequence then are that model's: PinholeCamera.cc:450-542,
+ * CataCamera.cc:556-659, EquidistantCamera.cc:428-461 with backprojectSymmetric (:716-818), in double precision (csrc/gf_camera_models.hpp; DESIGN.md
+ * section 4, "Camera models").  Pixel coordinates, ids, track counts and depths do not depend on the model.
+ *   proj   PINHOLE fx fy cx cy | MEI gamma1 gamma2 u0 v0 | KANNALA_BRANDT mu mv u0 v0
+ *   dist   PINHOLE k1 k2 p1 p2 | MEI k1 k2 p1 p2        | KANNALA_BRANDT k2 k3 k4 k5
+ * Refused wherever a model is taken (GF_ERR_INVALID, the message naming the field): a model that is none of the three, reserved != 0, a value that is not
+ * finite, proj[0] or proj[1] <= 0, xi < 0 (MEI), and a KANNALA_BRANDT set in which a zero coefficient precedes a non-zero one (k3 = 0 with k5 != 0, say): the
+ * reference divides by zero for such a set. */
+enum { GF_CAMERA_PINHOLE = 0, GF_CAMERA_MEI = 1, GF_CAMERA_KANNALA_BRANDT = 2 };
+typedef struct gf_camera_model {
+    int32_t model;      /* GF_CAMERA_PINHOLE 0, GF_CAMERA_MEI 1, GF_CAMERA_KANNALA_BRANDT 2 */
+    int32_t reserved;   /* 0 */
+    double proj[4];     /* fx fy cx cy | gamma1 gamma2 u0 v0 | mu mv u0 v0 */
+    double dist[4];     /* k1 k2 p1 p2 | k1 k2 p1 p2        | k2 k3 k4 k5 */
+    double xi;          /* MEI only */
+} gf_camera_model;
+typedef char gf_camera_model_is_80_bytes[sizeof(gf_camera_model) == 80 ? 1 : -1];
+/* The camera of seq (feature_tracker.cpp:745-759).  A setting like gf_tracker_seq_cfg: refused once the sequence has taken a frame (until gf_tracker_reset_seq,
+ * which keeps it) and while a frame staged by gf_tracker_prefetch_* lists it.  With GF_CAMERA_PINHOLE the call is gf_tracker_set_seq_cfg with the eight camera
+ * fields replaced.  With another model the camera fields of the sequence's gf_tracker_seq_cfg stay stored, unused until a pinhole is set again; the sequence's
+ * points are lifted by ONE kernel launch per tracker call behind the corner selection, for all listed sequences with such a model (environment
+ * GF_CAMERA_LIFT_HOST=1, read by gf_tracker_create: on the host instead, with the same formulas), and the lifted pairs come back with the call's last copies:
+ * no further synchronisation.  Pinhole sequences keep their host lift bit for bit, and a handle on which no such model is set allocates, copies and launches
+ * what it did without these calls. */
+int gf_tracker_set_seq_camera(gf_tracker* h, int seq, const gf_camera_model* cam);
+/* feature_tracker.cpp:745-759: the camera in force for seq; ahead of any setter the pinhole of the sequence's gf_tracker_seq_cfg */
+int gf_tracker_get_seq_camera(gf_tracker* h, int seq, gf_camera_model* out);
+/* liftProjective (PinholeCamera.cc:450-510, CataCamera.cc:556-626, EquidistantCamera.cc:428-442) as a building block, through the tracker's kernel: sequence b
+ * of `batch` has camera cams[b] and the points uv[first[b] .. first[b + 1]) (float pixel pairs; first: batch + 1 offsets from 0, not decreasing).  rays: 3
+ * doubles per point, the ray P (may be NULL); un: the float pair (float)(P.x / P.z), (float)(P.y / P.z) of feature_tracker.cpp:803-805.  Every point takes a
+ * bounded number of steps whatever its coordinates.  Host arrays (copies in, one launch, copies out; synchronous). */
+int gf_camera_lift_batch(const gf_camera_model* cams, int batch, const int* first, const float* uv, double* rays, float* un);
+/* The same lift (feature_tracker.cpp:797-808) on device arrays: uv, rays (may be NULL) and un are device pointers of the current device; cams and first stay
+ * host tables.  One launch on `stream` (a hipStream_t, NULL = the null stream); returns when it has run (the checked cameras travel in staging of the call). */
+int gf_camera_lift_batch_device(const gf_camera_model* cams, int batch, const int* first, const float* d_uv, double* d_rays, float* d_un, void* stream);
+/* spaceToPlane (PinholeCamera.cc:520-542, CataCamera.cc:636-659, EquidistantCamera.cc:451-461) on the host, what setPrediction uses: xyz 3 doubles per
+ * point, uv 2 doubles per point, sequences and offsets as above. */
+int gf_camera_project_batch(const gf_camera_model* cams, int batch, const int* first, const double* xyz, double* uv);
+/* A camodocal calibration file (CameraFactory::generateCameraFromYamlFile, CameraFactory.cc; keys as PinholeCamera.cc:145-183, CataCamera.cc:160-202,
+ * EquidistantCamera.cc:146-182): model_type (missing: PINHOLE), projection_parameters, distortion_parameters, mirror_parameters.xi.  A missing numeric key reads
+ * as 0 like every cv::FileNode, so a missing focal parameter is refused by name; PINHOLE_FULL and SCARAMUZZA are refused by name. */
+int gf_camera_from_yaml(const char* calib_file, gf_camera_model* out);
 /* The track image: SHOW_TRACK and FeatureTracker::getTrackImage() (feature_tracker.cpp:849-905 drawTrack, :1047; what the node publishes as image_track) -- the
  * MONO8 frame trackImage tracked on (after the handle's colour / raw conversion and equalisation) as height x width x 3 bytes in the reference's channel order
  * (labelled bgr8 there), a dot per feature coloured (255 (1 - len), 0, 255 len) by len = min(1, track_cnt / 20), and a green arrow from each feature that LK
@@ -786,6 +830,13 @@ int gf_estimator_group_stats(gf_estimator_group* g, long long* batches, long lon
  * (EQUALIZE, parameters.cpp:169; any non-zero value switches it on) sets cfg->tracker.equalize to 1.  Options outside the built path (use_line, use_yolo, plane, use_motion, num_of_cam 2, estimate_extrinsic 2,
  * gnss_local_online_sync) return GF_ERR_INVALID instead of being ignored. */
 int gf_estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* cfg);
+/* readParameters (parameters.cpp:138-558) as above with the cam0_calib file read by gf_camera_from_yaml: PINHOLE, MEI and KANNALA_BRANDT files are accepted and
+ * the model is handed back in *camera, for gf_estimator_set_camera.  For a model other than PINHOLE cfg->tracker gets the projection parameters as fx fy cx cy
+ * and zero distortion, valid placeholders that nothing reads once the camera is set. */
+int gf_estimator_cfg_from_yaml_camera(const char* config_file, gf_estimator_cfg* cfg, gf_camera_model* camera);
+/* readIntrinsicParameter (feature_tracker.cpp:745-759) of an estimator that owns its tracker: gf_tracker_set_seq_camera on that tracker's one sequence, before
+ * the first gf_estimator_input_image.  GF_ERR_INVALID without a tracker, and as that call refuses. */
+int gf_estimator_set_camera(gf_estimator* h, const gf_camera_model* camera);
 /* show_track (SHOW_TRACK, parameters.cpp:202; what makes the node publish getTrackImage, feature_tracker.cpp:849-905 / :1047) of the same file with the same
  * reader; a missing key reads as 0.  gf_estimator_cfg does not carry it: a caller that wants the pictures turns them on (gf_estimator_set_show_track). */
 int gf_show_track_from_yaml(const char* config_file, int* show_track);
