@@ -857,7 +857,7 @@ int gf_ba_create(const gf_ba_cfg* cfg, gf_ba** out) {
     const int Rmax = 15 * d.NP + 17 + (gnss ? 5 * d.NP + 3 : 0);
     d.RP = (Rmax + 1 + 15) & ~15; /* one spare column: the Schur GEMM carries the right-hand side in column R */ d.GO = gnss ? ((16 * d.NP + 20 + d.F + 3) & ~3) : 0; d.XS = gnss ? ((d.GO + 5 * d.NP + 4 + 3) & ~3) : ((16 * d.NP + 20 + d.F + 3) & ~3); d.NFB = 2 * d.NP + 7 + (gnss ? 5 * d.NP + 2 : 0); d.FP = (d.F + 3) & ~3; d.NPRI = d.RP; d.ECW = (6 * d.NP + 8 + 15) & ~15; d.NC = 6 * d.NP + 8; d.NVC = (d.NC * (d.NC + 1) / 2 + 3) & ~3;
     h->step_lds = (size_t)(Rmax + 1) * (Rmax + 2) / 2 * sizeof(double);  // packed lower S plus the right-hand-side row
-    h->big_step = h->step_lds + 27 * 1024 > 160 * 1024 || getenv("GF_BA_FORCE_GLOBAL") != nullptr;   // reduced system too large for LDS: ba_step<true> keeps it in global memory
+    h->big_step = h->step_lds + kStepStaticLds > 160 * 1024 || getenv("GF_BA_FORCE_GLOBAL") != nullptr;   // reduced system too large for LDS: ba_step<true> keeps it in global memory
     if (Rmax + 1 > 512) return gf::set_err(GF_ERR_INVALID, "window_size %d: reduced system (%d) exceeds 511 columns", d.W, Rmax);
     if (d.NV > 65535) return gf::set_err(GF_ERR_INVALID, "max_visual %d exceeds 65535", d.NV);
     if (misc_win_lds_doubles(d.W) * sizeof(double) > 160 * 1024) /* the sweep has no static LDS */ return gf::set_err(GF_ERR_INVALID, "window_size %d: the IMU / wheel block rows exceed LDS (window_size <= 20 in this build)", d.W);
@@ -928,7 +928,7 @@ int gf_ba_create(const gf_ba_cfg* cfg, gf_ba** out) {
     if (!h->vis_fixed.lds || !h->vis_free.lds) { h->vtile_stride = (vwin_slot_doubles(d.NP, true) + 3) & ~(size_t)3; TRACED(h->vtile.alloc(B * h->vtile_stride, false)); }
     h->mwin_lds = misc_win_lds_doubles(d.W) * sizeof(double);
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_linearize_misc_win), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->mwin_lds));
-    h->can_fuse_misc = !h->big_step && std::max(h->step_lds, h->mwin_lds) + 27 * 1024 <= 160 * 1024;
+    h->can_fuse_misc = !h->big_step && std::max(h->step_lds, h->mwin_lds) + kStepStaticLds <= 160 * 1024;
     if (h->can_fuse_misc) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_misc_step), hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(h->step_lds, h->mwin_lds)));
     if (!h->big_marg) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_marg_finish<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->marg_lds));
     HIPCHK(hipStreamSynchronize(h->stream));

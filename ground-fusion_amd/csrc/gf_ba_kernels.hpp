@@ -130,7 +130,6 @@ template <bool EX> __host__ __device__ constexpr int ef_stride() { return EX ? 1
 #define GF_WSTAMP_T(t, i) do { } while (0)
 #endif
 __device__ __forceinline__ double* cost_part(const Win& w, int part, int which, int b) { return w.cost + ((size_t)(part * 2 + which) * w.d.B + b); }
-__device__ __forceinline__ double cost_total(const Win& w, int which, int b) { return (*cost_part(w, 0, which, b) + *cost_part(w, 1, which, b)) + *cost_part(w, 2, which, b); }
 
 __device__ __forceinline__ Q4 q_of(const double* p) { return Q4{p[6], p[3], p[4], p[5]}; }
 __device__ __forceinline__ V3 p_of(const double* p) { return V3{p[0], p[1], p[2]}; }
@@ -724,6 +723,12 @@ namespace gfb {
 #else
 #define GF_STAMP(i) do { } while (0)
 #endif
+
+// ba_step's LDS: the packed reduced system (dynamic) next to the kernel's static tables.  The host keeps S in LDS while step_lds + kStepStaticLds fits the CU's
+// 160 KB (gf_ba_create); such a system has at most kStepLdsCols rows (183 at that limit), which is what the per-reduced-column tables of the LDS forms hold.
+constexpr size_t kStepStaticLds = 27 * 1024;
+constexpr int kStepLdsCols = 256;
+static_assert((size_t)kStepLdsCols * (kStepLdsCols + 1) / 2 * sizeof(double) + kStepStaticLds > 160 * 1024, "a system that fits LDS must fit the per-column tables");
 
 struct StepBufs {  // per-window global scratch of ba_step
     double* scale;  // [B][VS] Jacobi column scaling 1/(1+|J_c|)        (VS = RP + FP: reduced columns, then eliminated columns)
@@ -1585,7 +1590,7 @@ template <bool GS, int NW = 8, bool CH = false>
 __device__ __forceinline__ void ba_step_body(Win w, StepBufs sb, int first, int max_iters, int finalize_only) {
     static_assert(!(CH && GS), "the chain form keeps its dense part in LDS");
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    constexpr int NRC = CH ? 256 : 512;   // capacity of the per-reduced-column tables (chain form: R <= 15 NP + 17 <= 195 by the host's choice)
+    constexpr int NRC = GS ? 512 : kStepLdsCols;   // capacity of the per-reduced-column tables: R <= 511 with S in global memory; a system whose packed triangle fits LDS has R + 1 <= kStepLdsCols (gf_ba_create)
     constexpr int NCC = CH ? 96 : 256;    // capacity of the per-compact-column tables (chain form: ECW = 80)
     __shared__ double sred[512];
     __shared__ double s_inv[16 * 17];
@@ -1594,18 +1599,41 @@ __device__ __forceinline__ void ba_step_body(Win w, StepBufs sb, int first, int 
     __shared__ int s_cmap[NCC];      // compact column -> reduced column (or -1), right-hand-side slot -> R
     __shared__ double s_uc[NCC];     // a vector gathered to the compact layout (the Gauss-Newton solution during the back-substitution)
     __shared__ double s_ucc[NCC];    // the Cauchy direction in the compact layout (kept for the quadratic form u^T H u)
-    __shared__ double s_rd[NRC];     // scratch: the Cauchy direction during the Schur pass, the solution during the backward substitution
+    __shared__ double s_rd[NRC];     // scratch: the Cauchy direction during the Schur pass, the solution during the backward substitution, the step u for the candidate
     __shared__ int s_rc[NRC];        // reduced column -> compact column of the visual system Vc (or -1)
     __shared__ double s_hd[NRC];     // diagonal of H + Vc
     __shared__ double s_gt[NRC];     // g + Vc's right-hand-side row
     __shared__ double s_yd[CH ? 96 : 1];   // chain form: the solution of the dense part
+    __shared__ SolverState s_st;     // the window's solver state for the life of the launch: read from global memory once, written back once (store_state)
+    __shared__ double s_cst[6];      // the cost parts of both buffer sets ([set][part]), read next to the state
+    constexpr int STW = sizeof(SolverState) / sizeof(int);
+    static_assert(sizeof(SolverState) % sizeof(int) == 0 && STW + 6 <= 64, "the state and the cost parts are copied by the first wavefront, one word / one value per lane");
+    // the static tables must stay inside what the host leaves next to the packed system (gf_ba_create: step_lds + kStepStaticLds <= 160 KB keeps S in LDS).
+    // The sum below is kept by hand from the declarations above: a __shared__ added elsewhere in the body or in a callee (the profiling build adds none) is not in
+    // it.  The compiler's own total is the check that counts: `LDS Size` of -Rpass-analysis=kernel-resource-usage, 19 040 bytes for ba_step<false, 8>.
+    static_assert(sizeof(double) * (512 + 16 * 17 + 32 + 2 * NCC + 3 * NRC + (CH ? 96 : 1) + 6) + sizeof(int) * (4 + NCC + NRC) + sizeof(SolverState) <= kStepStaticLds, "ba_step: static LDS over its budget");
     constexpr int NT = 64 * NW;
     const Dims d = w.d;
     const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    SolverState& st = w.st[b];
-    if (uni(st.done)) return;
-    if ((uni(st.chain) != 0) != CH) return;   // a batch may hold windows of both kinds: each form of the kernel takes its own (the host launches a form only when the batch has such windows)
-    const int R = uni(st.R), NE = uni(st.NE), RP = d.RP, VS = sb.VS, ECW = d.ECW;
+    SolverState& gst = w.st[b];
+    if (uni(gst.done)) return;
+    if ((uni(gst.chain) != 0) != CH) return;   // a batch may hold windows of both kinds: each form of the kernel takes its own (the host launches a form only when the batch has such windows)
+    // Everything the phases below read or write of the state goes to the LDS copy: the decisions of thread 0 reach the block through LDS behind a barrier, never
+    // through a global store followed by a global load.  The copy and the six cost parts are in flight together with the column map's loads; the barrier behind the
+    // map is their one wait.
+    // (The copy moves the struct as words, its fields are read through their own types: no thread touches s_st between this copy and the barrier behind the
+    // column map below, nor between the last field store and the barrier inside store_state -- those barriers are what orders the two kinds of access.)
+    if (tid < STW) reinterpret_cast<int*>(&s_st)[tid] = reinterpret_cast<const int*>(&gst)[tid];
+    else if (tid < STW + 6) { const int q = tid - STW; s_cst[q] = *cost_part(w, q % 3, q / 3, b); }
+    SolverState& st = s_st;
+    // store_state writes the WHOLE struct back, the fields this kernel never changes included (R, NE, chain, h_prior): whoever else writes a SolverState field must
+    // have done so before this launch's copy was taken.  In ba_misc_step the sweep in front (which sets h_prior) is separated from the copy by that kernel's barrier.
+    auto store_state = [&]() {   // every exit behind this point: the block's last barrier, then the state back to global memory with plain stores
+        __syncthreads();
+        if (tid < STW) reinterpret_cast<int*>(&gst)[tid] = reinterpret_cast<const int*>(&s_st)[tid];
+    };
+    auto cost_of = [&](int which) { return (s_cst[3 * which] + s_cst[3 * which + 1]) + s_cst[3 * which + 2]; };   // a buffer set's cost: prior + IMU + wheel, then visual, then GNSS, from the parts read at the head
+    const int R = uni(gst.R), NE = uni(gst.NE), RP = d.RP, VS = sb.VS, ECW = d.ECW;
     double* S = GS ? sb.Sg + (size_t)blockIdx.x * sb.SgStride : smem;  // packed lower (R+1)(R+2)/2: row R carries the right-hand side
     // chain form: S is the packed triangle of the DENSE part only (poses + trailing blocks, ND columns, row ND = right-hand side); RC = dimension of what the blocked
     // Cholesky below factors; DMAP: reduced column (or the right-hand-side slot R) -> row / column of S
@@ -1625,11 +1653,11 @@ __device__ __forceinline__ void ba_step_body(Win w, StepBufs sb, int first, int 
     if (tid == 0) {
         s_flag[0] = 0;
         if (first) {
-            st.x_cost = cost_total(w, st.cur, b);
+            st.x_cost = cost_of(st.cur);
             st.initial_cost = st.x_cost;
             st.last_successful = 1;
         } else if (st.cand_valid) {
-            const double cand_cost = cost_total(w, 1 - st.cur, b);
+            const double cand_cost = cost_of(1 - st.cur);
             st.cand_cost = cand_cost;
             if (st.step_norm <= 1e-8 * (st.x_norm + 1e-8)) { st.done = 1; st.termination = 2; }
             else if (fabs(st.x_cost - cand_cost) <= 1e-6 * st.x_cost) { st.done = 1; st.termination = 1; }
@@ -1646,8 +1674,9 @@ __device__ __forceinline__ void ba_step_body(Win w, StepBufs sb, int first, int 
         }
     }
     __syncthreads();
-    if (uni(st.done)) return;
+    if (uni(st.done)) { store_state(); return; }
     const int cur = uni(st.cur);
+    const bool reuse = uni(st.reuse) != 0, have_scale = uni(st.have_scale) != 0;   // as the accept / reject step left them; both change again only behind their last use below
     double* H = w.H + ((size_t)cur * d.B + b) * RP * RP;
     double* g = w.g + ((size_t)cur * d.B + b) * RP;
     const double* xs = w.xs + ((size_t)cur * d.B + b) * d.XS;
@@ -1658,6 +1687,14 @@ __device__ __forceinline__ void ba_step_body(Win w, StepBufs sb, int first, int 
     // the sum, once per call
     const double* Vc = w.Vc + ((size_t)cur * d.B + b) * d.NVC;
     const int RHSK = 6 * d.NP + 7;
+    // This thread's first reduced column (tid) and first eliminated column (tid): what the vector phases below need of them is loaded here, next to the head's own
+    // loads -- one wait for all -- and stays in registers until the Cauchy direction is formed.  Further columns of a thread (R or NE above the block size) are
+    // read where they are used, as before.
+    double p_sc = 0.0, p_sce = 0.0, p_ete = 0.0, p_etb = 0.0;
+    if (!reuse) {
+        if (tid < R && have_scale) p_sc = scale[tid];
+        if (tid < NE) { p_ete = ete[tid]; p_etb = etb[tid]; if (have_scale) p_sce = scale[RP + tid]; }
+    }
     for (int c = tid; c < R; c += NT) {
         const int k = s_rc[c];
         s_hd[c] = H[(size_t)c * RP + c] + (k >= 0 ? Vc[pk(k, k)] : 0.0);
@@ -1665,18 +1702,18 @@ __device__ __forceinline__ void ba_step_body(Win w, StepBufs sb, int first, int 
     }
     __syncthreads();
     GF_STAMP(1);
-    if (!uni(st.reuse)) {
+    if (!reuse) {
         // ---------------- Jacobi scaling from the initial Jacobian (trust_region_minimizer.cc: jacobian_scaling_)
-        if (!st.have_scale) {
-            for (int c = tid; c < R; c += NT) scale[c] = 1.0 / (1.0 + sqrt(s_hd[c]));
-            for (int e = tid; e < NE; e += NT) scale[RP + e] = 1.0 / (1.0 + sqrt(ete[e]));
+        if (!have_scale) {
+            for (int c = tid; c < R; c += NT) { const double v = 1.0 / (1.0 + sqrt(s_hd[c])); scale[c] = v; if (c == tid) p_sc = v; }
+            for (int e = tid; e < NE; e += NT) { const double v = 1.0 / (1.0 + sqrt(e == tid ? p_ete : ete[e])); scale[RP + e] = v; if (e == tid) p_sce = v; }
             __syncthreads();
             if (tid == 0) st.have_scale = 1;
         }
         // unscaled gradient max norm (gradient tolerance)
         double gm = 0;
         for (int c = tid; c < R; c += NT) gm = fmax(gm, fabs(s_gt[c]));
-        for (int e = tid; e < NE; e += NT) gm = fmax(gm, fabs(etb[e]));
+        for (int e = tid; e < NE; e += NT) gm = fmax(gm, fabs(e == tid ? p_etb : etb[e]));
         gm = block_max<NW>(gm, sred, tid, NT);
         if (tid == 0) st.gmax = gm;
     }
@@ -1690,29 +1727,33 @@ __device__ __forceinline__ void ba_step_body(Win w, StepBufs sb, int first, int 
     }
     __syncthreads();
     GF_STAMP(3);
-    if (uni(st.done) || finalize_only) return;
+    if (uni(st.done) || finalize_only) { store_state(); return; }
 
-    if (!uni(st.reuse)) {
+    if (!reuse) {
         GF_STAMP(4);
-        // ---------------- dogleg diagonal, scaled gradient, Cauchy point
+        // ---------------- dogleg diagonal, scaled gradient, Cauchy point.  A column's diagonal, gradient and Cauchy entry are formed by one thread from its own
+        // operands and go to global memory for the later launches; what this launch reads of them again it takes from the registers they were formed in, and
+        // from the LDS copies the passes below read once per matrix entry: the column scaling in s_hd, the Cauchy direction in s_rd (s_hd's diagonal of H + Vc
+        // is used up here; s_rd is free until the Cholesky).
+        double gsq = 0;
         for (int c = tid; c < R; c += NT) {
-            const double dd = sqrt(fmin(fmax(scale[c] * scale[c] * s_hd[c], 1e-6), 1e32));
-            diag[c] = dd; grad[c] = scale[c] * s_gt[c] / dd; u[c] = scale[c] * (grad[c] / dd);
+            const double sc = c == tid ? p_sc : scale[c];
+            const double dd = sqrt(fmin(fmax(sc * sc * s_hd[c], 1e-6), 1e32));
+            const double gr = sc * s_gt[c] / dd, uu = sc * (gr / dd);
+            diag[c] = dd; grad[c] = gr; u[c] = uu;
+            s_hd[c] = sc; s_rd[c] = uu;
+            gsq += gr * gr;
         }
         for (int e = tid; e < NE; e += NT) {
-            const double sc = scale[RP + e];
-            const double dd = sqrt(fmin(fmax(sc * sc * ete[e], 1e-6), 1e32));
-            diag[RP + e] = dd; grad[RP + e] = sc * etb[e] / dd; u[RP + e] = sc * (grad[RP + e] / dd);
-            gn[RP + e] = u[RP + e];   // the Cauchy direction's eliminated part survives in gn's tail until the back-substitution rewrites it
+            const double sc = e == tid ? p_sce : scale[RP + e], ee = e == tid ? p_ete : ete[e], eb = e == tid ? p_etb : etb[e];
+            const double dd = sqrt(fmin(fmax(sc * sc * ee, 1e-6), 1e32));
+            const double gr = sc * eb / dd, uu = sc * (gr / dd);
+            diag[RP + e] = dd; grad[RP + e] = gr; u[RP + e] = uu;
+            gn[RP + e] = uu;   // the Cauchy direction's eliminated part survives in gn's tail until the back-substitution rewrites it
+            gsq += gr * gr;
         }
         __syncthreads();
-        if (tid < ECW) { const int c = s_cmap[tid]; s_ucc[tid] = (c >= 0 && c < R) ? u[c] : 0.0; }
-        // the passes below read the column scaling and the Cauchy direction once per matrix entry: LDS copies (s_hd and s_rd are free until the
-        // next call / the Cholesky)
-        for (int c = tid; c < R; c += NT) { s_hd[c] = scale[c]; s_rd[c] = u[c]; }
-        double gsq = 0;
-        for (int c = tid; c < R; c += NT) gsq += grad[c] * grad[c];
-        for (int e = tid; e < NE; e += NT) gsq += grad[RP + e] * grad[RP + e];
+        if (tid < ECW) { const int c = s_cmap[tid]; s_ucc[tid] = (c >= 0 && c < R) ? s_rd[c] : 0.0; }
         gsq = block_sum<NW>(gsq, sred, tid, NT);
         // alpha = |g~|^2 / (u^T H u) of the Cauchy point: the quadratic form is accumulated below, inside the passes that stream Et (Es build) and
         // H (load of the reduced system) anyway, instead of a separate sweep over both
@@ -1722,7 +1763,7 @@ __device__ __forceinline__ void ba_step_body(Win w, StepBufs sb, int first, int 
         constexpr int QN = GS ? 8 : 3;
         double uk[QN];
 #pragma unroll
-        for (int q = 0; q < QN; q++) uk[q] = (lane + 64 * q) < R ? u[lane + 64 * q] : 0.0;
+        for (int q = 0; q < QN; q++) uk[q] = (lane + 64 * q) < R ? s_rd[lane + 64 * q] : 0.0;
         // ---------------- Gauss-Newton step: (J^T J + mu D^2) y = J^T r through the Schur complement, retry with larger mu on failure
         bool ok = false;
         while (!ok) {
@@ -2399,11 +2440,46 @@ __device__ __forceinline__ void ba_step_body(Win w, StepBufs sb, int first, int 
     __syncthreads();
     bool valid = s_flag[2] != 0;
     GF_STAMP(11);
+    // ---------------- the loads of the closing phases, issued together: the dogleg's operands of this thread's first reduced and first eliminated column, the
+    // state and the column of the parameter block this thread moves, and the copy of the state into the candidate's buffer (the blocks the step touches are
+    // overwritten behind the barrier in front of stamp 13).  Nothing below waits for global memory a second time: the step u reaches the candidate through LDS
+    // (reduced part in s_rd, which is free behind the back-substitution; eliminated part in sred behind the reductions' slots, when it fits).
+    double* xc = w.xs + ((size_t)(1 - cur) * d.B + b) * d.XS;
+    const int NBLK = d.NFB + d.F, nfeat_b = w.nfeat[b];
+    const bool ue_lds = NE <= 512 - 32;
+    auto blk_desc = [&](int blk, int& c0, int& off, int& kind) {   // parameter block -> its first column (-1: constant or absent), offset in the state, kind
+        if (blk < d.NFB) {
+            c0 = colf[blk];
+            if (blk < 2 * d.NP) { kind = (blk & 1) ? 1 : 0; off = (blk & 1) ? off_sb(blk >> 1) : off_pose(blk >> 1); }
+            else if (blk < 2 * d.NP + 7) { const int q = blk - 2 * d.NP; kind = q == 0 ? 2 : q == 1 ? 3 : q <= 4 ? 4 : q == 5 ? 7 : 8; off = q == 0 ? off_ex(d.NP) : q == 1 ? off_exw(d.NP) : q <= 4 ? off_ix(d.NP) + (q - 2) : q == 5 ? off_td(d.NP) : off_tdw(d.NP); }
+            else { const int q = blk - (2 * d.NP + 7); kind = q < 5 * d.NP + 1 ? 10 : 13; off = d.GO + q; }   // rcv_dt, rcv_ddt, yaw: scalars in state order; then anc_ecef (3)
+        } else {
+            const int f = blk - d.NFB;
+            kind = 9; off = off_feat(d.NP) + f; c0 = -1;
+            if (f < nfeat_b) { const int e = cole[f]; c0 = e >= 0 ? RP + e : -1; }
+        }
+    };
+    auto blk_state = [&](int off, int kind, double (&xv)[9]) {
+        const int gs = gsize_kind(kind);
+#pragma unroll
+        for (int q = 0; q < 9; q++) xv[q] = q < gs ? xs[off + q] : 0.0;
+    };
+    int b_c0 = -1, b_off = 0, b_kind = 9;
+    double b_x[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double q_g = 0, q_n = 0, q_d = 1, q_s = 0, r_g = 0, r_n = 0, r_d = 1, r_s = 0;
+    double msk_ex = 0, msk_exw = 0;   // PoseSubsetParameterization masks of the camera / wheel extrinsic
+    if (valid) {
+        if (tid < R) { q_g = grad[tid]; q_n = gn[tid]; q_d = diag[tid]; q_s = scale[tid]; }
+        if (tid < NE) { r_g = grad[RP + tid]; r_n = gn[RP + tid]; r_d = diag[RP + tid]; r_s = scale[RP + tid]; }
+        if (tid < NBLK) { blk_desc(tid, b_c0, b_off, b_kind); blk_state(b_off, b_kind, b_x); }
+        msk_ex = w.wpar[WPAR * b + 4]; msk_exw = w.wpar[WPAR * b + 5];
+    }
+    for (int i = tid; i < d.XS; i += NT) xc[i] = xs[i];
     // ---------------- traditional dogleg interpolation (dogleg_strategy.cc ComputeTraditionalDoglegStep)
     if (valid) {
         double a = 0, c2 = 0, dt = 0;
-        for (int c = tid; c < R; c += NT) { a += grad[c] * grad[c]; c2 += gn[c] * gn[c]; dt += grad[c] * gn[c]; }
-        for (int e = tid; e < NE; e += NT) { a += grad[RP + e] * grad[RP + e]; c2 += gn[RP + e] * gn[RP + e]; dt += grad[RP + e] * gn[RP + e]; }
+        for (int c = tid; c < R; c += NT) { const bool f = c == tid; const double gr = f ? q_g : grad[c], gv = f ? q_n : gn[c]; a += gr * gr; c2 += gv * gv; dt += gr * gv; }
+        for (int e = tid; e < NE; e += NT) { const bool f = e == tid; const double gr = f ? r_g : grad[RP + e], gv = f ? r_n : gn[RP + e]; a += gr * gr; c2 += gv * gv; dt += gr * gv; }
         double v3[3] = {a, c2, dt};
         block_sum_n<3, NW>(v3, sred, tid);
         const double gnorm = sqrt(v3[0]), gnn = sqrt(v3[1]), gdot = v3[2];
@@ -2418,8 +2494,21 @@ __device__ __forceinline__ void ba_step_body(Win w, StepBufs sb, int first, int 
             ca = -alpha * (1.0 - beta); cb = beta; dsn = -1;
         }
         double nn = 0;
-        for (int c = tid; c < R; c += NT) { const double sv = ca * grad[c] + cb * gn[c]; nn += sv * sv; stepv[c] = sv / diag[c]; u[c] = scale[c] * stepv[c]; }
-        for (int e = tid; e < NE; e += NT) { const double sv = ca * grad[RP + e] + cb * gn[RP + e]; nn += sv * sv; stepv[RP + e] = sv / diag[RP + e]; u[RP + e] = scale[RP + e] * stepv[RP + e]; }
+        for (int c = tid; c < R; c += NT) {
+            const bool f = c == tid;
+            const double sv = ca * (f ? q_g : grad[c]) + cb * (f ? q_n : gn[c]);
+            nn += sv * sv;
+            const double sd = sv / (f ? q_d : diag[c]), uu = (f ? q_s : scale[c]) * sd;
+            stepv[c] = sd; u[c] = uu; s_rd[c] = uu;
+        }
+        for (int e = tid; e < NE; e += NT) {
+            const bool f = e == tid;
+            const double sv = ca * (f ? r_g : grad[RP + e]) + cb * (f ? r_n : gn[RP + e]);
+            nn += sv * sv;
+            const double sd = sv / (f ? r_d : diag[RP + e]), uu = (f ? r_s : scale[RP + e]) * sd;
+            stepv[RP + e] = sd; u[RP + e] = uu;
+            if (ue_lds) sred[32 + e] = uu;   // the reductions below use sred[0 .. 23]
+        }
         nn = block_sum<NW>(nn, sred, tid, NT);
         if (dsn < 0) dsn = sqrt(nn);
         if (tid == 0) st.dogleg_step_norm = dsn;
@@ -2438,39 +2527,38 @@ __device__ __forceinline__ void ba_step_body(Win w, StepBufs sb, int first, int 
     }
     __syncthreads();
     GF_STAMP(13);
-    // ---------------- candidate point x (+) delta, delta = step .* scale = u  (its normal equations are written, not accumulated, by the next sweeps)
-    double* xc = w.xs + ((size_t)(1 - cur) * d.B + b) * d.XS;
-    for (int i = tid; i < d.XS; i += NT) xc[i] = xs[i];
-    __syncthreads();
+    // ---------------- candidate point x (+) delta, delta = step .* scale = u  (its normal equations are written, not accumulated, by the next sweeps).
+    // A block's state is in registers already; its new value is written once and the two norms are formed from the registers, entry by entry as before.
     double sn = 0, xn = 0;
     if (valid) {
-        for (int blk = tid; blk < d.NFB + d.F; blk += NT) {
-            int c0, off, kind;
-            if (blk < d.NFB) {
-                c0 = colf[blk];
-                if (blk < 2 * d.NP) { kind = (blk & 1) ? 1 : 0; off = (blk & 1) ? off_sb(blk >> 1) : off_pose(blk >> 1); }
-                else if (blk < 2 * d.NP + 7) { const int q = blk - 2 * d.NP; kind = q == 0 ? 2 : q == 1 ? 3 : q <= 4 ? 4 : q == 5 ? 7 : 8; off = q == 0 ? off_ex(d.NP) : q == 1 ? off_exw(d.NP) : q <= 4 ? off_ix(d.NP) + (q - 2) : q == 5 ? off_td(d.NP) : off_tdw(d.NP); }
-                else { const int q = blk - (2 * d.NP + 7); kind = q < 5 * d.NP + 1 ? 10 : 13; off = d.GO + q; }   // rcv_dt, rcv_ddt, yaw: scalars in state order; then anc_ecef (3)
-            } else {
-                const int f = blk - d.NFB;
-                if (f >= w.nfeat[b]) continue;
-                const int e = cole[f];
-                c0 = e >= 0 ? RP + e : -1; kind = 9; off = off_feat(d.NP) + f;
-            }
+        auto u_at = [&](int c) { return c < RP ? s_rd[c] : (ue_lds ? sred[32 + c - RP] : u[c]); };
+        for (int blk = tid; blk < NBLK; blk += NT) {
+            int c0 = b_c0, off = b_off, kind = b_kind;
+            double xv[9], dl[9], ov[9];
+#pragma unroll
+            for (int q = 0; q < 9; q++) xv[q] = b_x[q];
+            if (blk != tid) { blk_desc(blk, c0, off, kind); blk_state(off, kind, xv); }
             if (c0 < 0) continue;
-            const int gs = gsize_kind(kind);
+            const int gs = gsize_kind(kind), nt = gs == 7 ? 6 : gs;   // a pose block has six tangent components
+#pragma unroll
+            for (int q = 0; q < 9; q++) dl[q] = q < nt ? u_at(c0 + q) : 0.0;
             if (gs == 7) {
                 if (kind == 2 || kind == 3) {   // PoseSubsetParameterization::Plus (pose_subset_parameterization.cpp:27-56): masked components of the increment are dropped -- here only;
                                                 // the columns, the step and the model cost change are those of the full block (its ComputeJacobian is the identity whatever the mask)
-                    const int mask = (int)w.wpar[WPAR * b + (kind == 2 ? 4 : 5)];
-                    double dm[6];
+                    const int mask = (int)(kind == 2 ? msk_ex : msk_exw);
 #pragma unroll
-                    for (int q = 0; q < 6; q++) dm[q] = ((mask >> q) & 1) ? 0.0 : u[c0 + q];
-                    pose_plus(xs + off, dm, xc + off);
-                } else pose_plus(xs + off, u + c0, xc + off);
+                    for (int q = 0; q < 6; q++) dl[q] = ((mask >> q) & 1) ? 0.0 : dl[q];
+                }
+                pose_plus(xv, dl, ov);
+                ov[7] = 0.0; ov[8] = 0.0;
+            } else {
+#pragma unroll
+                for (int q = 0; q < 9; q++) ov[q] = xv[q] + dl[q];
             }
-            else for (int q = 0; q < gs; q++) xc[off + q] = xs[off + q] + u[c0 + q];
-            for (int q = 0; q < gs; q++) { const double dv = xs[off + q] - xc[off + q]; sn += dv * dv; xn += xs[off + q] * xs[off + q]; }
+#pragma unroll
+            for (int q = 0; q < 9; q++) {
+                if (q < gs) { xc[off + q] = ov[q]; const double dv = xv[q] - ov[q]; sn += dv * dv; xn += xv[q] * xv[q]; }
+            }
         }
     }
     { double v2[2] = {sn, xn}; block_sum_n<2, NW>(v2, sred, tid); sn = v2[0]; xn = v2[1]; }
@@ -2485,6 +2573,7 @@ __device__ __forceinline__ void ba_step_body(Win w, StepBufs sb, int first, int 
             st.mu *= 10.0; st.reuse = 0;
         }
     }
+    store_state();
 }
 template <bool GS, int NW = 8>
 __global__ void __launch_bounds__(64 * NW) ba_step(Win w, StepBufs sb, int first, int max_iters, int finalize_only) { ba_step_body<GS, NW>(w, sb, first, max_iters, finalize_only); }
