@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "gf_lk_kernels.hpp"
 #include "gf_roi.hpp"
 #include "gf_seq_cfg.hpp"   // kMaxRadius, DiskTable
@@ -115,17 +116,15 @@ __device__ __noinline__ void strip_flush(unsigned long long* cand, int* count, i
         if (base + k < cap) cand[base + k] = ckeys[k];
 }
 
+// g: level 0 of the strip's frame, A.g on a handle without sizes; cur: the strip's entry of A.frame_of, >= 0
 template <int R>
-__global__ void __launch_bounds__(64) detect_strip_kernel(DetectArgs A, DiskTable T) {
+__device__ __forceinline__ void detect_strip_body(const DetectArgs& A, const DiskTable& T, const LevelGeom g, const int cur) {
     static_assert(R >= 1 && R <= 32, "one allow bit per strip row");
     constexpr int NS = R + 6;   // raw rows Y0 - 3 .. Y0 + R + 2
     constexpr int kCap = 320;   // candidates staged per strip (3 x 3 maxima exclude their neighbours: <= 60 R / 4 without plateaus); flushed early when a row might not fit
     __shared__ unsigned long long ckeys[kCap];
     __shared__ short s_hw[kMaxRadius + 1];
     const int b = blockIdx.z;
-    const int cur = list_entry(A.frame_of, b);
-    if (cur < 0) return;
-    const LevelGeom g = A.g;
     const int lane = threadIdx.x;
     const int X0 = blockIdx.x * kDS_W, Y0 = blockIdx.y * R;
     const int x = X0 - 2 + lane;
@@ -277,6 +276,27 @@ __global__ void __launch_bounds__(64) detect_strip_kernel(DetectArgs A, DiskTabl
     if (lane == 0 && best) atomicMax(A.maxkey + b, best);
     if (n_cand) strip_flush(cand_b, count_b, A.cand_cap, ckeys, n_cand, lane);
 }
+template <int R>
+__global__ void __launch_bounds__(64) detect_strip_kernel(DetectArgs A, DiskTable T) {
+    const int cur = list_entry(A.frame_of, blockIdx.z);
+    if (cur < 0) return;
+    detect_strip_body<R>(A, T, A.g, cur);
+}
+// A frame size per sequence (gf_seq_size.hpp): the grid is that of the largest listed frame, level 0 of a strip's own frame comes from its row of the handle's
+// table of sizes (block-uniform loads), and a strip that lies outside its own frame leaves before it loads anything of the image or the tables.  A.g is not read;
+// A.pyr_bytes is the distance between two slots as ever.  Strips and bands are counted from the frame's own origin, so the last strip and the last band of a
+// smaller frame are partial where they are in a handle of that size.
+template <int R>
+__global__ void __launch_bounds__(64) detect_strip_sized_kernel(DetectArgs A, DiskTable T, const SizeRow* __restrict__ rows, const uint8_t* __restrict__ size_of) {
+    const int cur = list_entry(A.frame_of, blockIdx.z);
+    if (cur < 0) return;
+    const LevelGeom& t = size_row(rows, size_of, blockIdx.z).G.lv[0];
+    LevelGeom g;
+    g.w = __builtin_amdgcn_readfirstlane(t.w); g.h = __builtin_amdgcn_readfirstlane(t.h);
+    g.stride = __builtin_amdgcn_readfirstlane(t.stride); g.img_off = __builtin_amdgcn_readfirstlane(t.img_off);
+    if ((int)(blockIdx.x * kDS_W) >= g.w || (int)(blockIdx.y * R) >= g.h) return;
+    detect_strip_body<R>(A, T, g, cur);
+}
 
 // The device setter of the region of interest (gf_tracker_set_roi_some_device): `count` tight h x w byte masks, back to back in list order -> the tables of the
 // sequences seq_of[i].  One thread per word: thread x of band blockIdx.y of mask blockIdx.z walks its column down the band (gfroi::pack_thread, the function the
@@ -289,6 +309,17 @@ __global__ void __launch_bounds__(256) roi_pack_kernel(const uint8_t* __restrict
 // The same from masks that lie where the caller keeps them (gf_tracker_set_roi_some_device_refs): mask i is refs[i], any pointer, any pitch >= w (byte loads).
 __global__ void __launch_bounds__(256) roi_pack_refs_kernel(const gf_frame_ref* __restrict__ refs, const int* __restrict__ seq_of, int w, int h, uint32_t* __restrict__ table,
                                                             size_t seq_words) {
+    const gfref::Frame f = gfref::entry(refs, blockIdx.z);
+    gfroi::pack_thread(f.data, f.pitch, w, h, blockIdx.y, blockIdx.x * 256 + threadIdx.x, table + (size_t)list_entry(seq_of, blockIdx.z) * seq_words);
+}
+// A frame size per sequence (gf_seq_size.hpp): mask i is refs[i] (the caller's entries, or the tight block's masks at the sum of those before them) and has the
+// size of its sequence's row of the handle's table; the grid is that of the largest listed mask and a block outside its own mask leaves before it reads any of it.
+// The words go into the sequence's table in the geometry of its own width, which the detector's sized form reads them in.
+__global__ void __launch_bounds__(256) roi_pack_sized_kernel(const gf_frame_ref* __restrict__ refs, const int* __restrict__ seq_of, const SizeRow* __restrict__ rows,
+                                                             const uint8_t* __restrict__ size_of, uint32_t* __restrict__ table, size_t seq_words) {
+    const SizeRow& r = size_row(rows, size_of, blockIdx.z);
+    const int w = __builtin_amdgcn_readfirstlane(r.w), h = __builtin_amdgcn_readfirstlane(r.h);
+    if ((int)(blockIdx.x * 256) >= w || (int)blockIdx.y >= gfroi::bands(h)) return;
     const gfref::Frame f = gfref::entry(refs, blockIdx.z);
     gfroi::pack_thread(f.data, f.pitch, w, h, blockIdx.y, blockIdx.x * 256 + threadIdx.x, table + (size_t)list_entry(seq_of, blockIdx.z) * seq_words);
 }
@@ -318,28 +349,30 @@ template <bool STORE> __device__ __forceinline__ void roi_words_io(uint32_t* p, 
         else { const uint4 t = *q; v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
         return;
     }
-    int done = 0;
-#pragma unroll
-    for (int k = 0; k < kRoiBoxWords; k++) {
-        if (k < done || k >= n) continue;
-        constexpr int last = kRoiBoxWords - 1;
-        if (k + 2 <= n && !((g + k) & 1)) {
-            uint2* q = reinterpret_cast<uint2*>(p + k);
-            if (STORE) *q = make_uint2(v[k], v[k < last ? k + 1 : last]);
-            else { const uint2 t = *q; v[k] = t.x; v[k < last ? k + 1 : last] = t.y; }
-            done = k + 2;
-        } else {
-            if (STORE) p[k] = v[k]; else v[k] = p[k];
-            done = k + 1;
-        }
+    // 8-byte pieces on even word indices, single words at the ends; every index below is a constant, so v stays in registers
+    static_assert(kRoiBoxWords == 4, "the cases below are written out for four words");
+    auto one = [&](auto K) { constexpr int k = decltype(K)::value; if (STORE) p[k] = v[k]; else v[k] = p[k]; };
+    auto two = [&](auto K) {
+        constexpr int k = decltype(K)::value;
+        uint2* q = reinterpret_cast<uint2*>(p + k);
+        if (STORE) *q = make_uint2(v[k], v[k + 1]);
+        else { const uint2 t = *q; v[k] = t.x; v[k + 1] = t.y; }
+    };
+    using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
+    if (g & 1) {
+        if (n >= 1) one(I0{});
+        if (n >= 3) two(I1{}); else if (n >= 2) one(I1{});
+        if (n >= 4) one(I3{});
+    } else {
+        if (n >= 2) two(I0{}); else if (n >= 1) one(I0{});
+        if (n >= 4) two(I2{}); else if (n >= 3) one(I2{});
     }
 }
 
-__global__ void __launch_bounds__(kRoiBoxPiece) roi_boxes_kernel(const RoiBoxJob* __restrict__ jobs, const gf_box* __restrict__ boxes, int w, int h,
-                                                                 const uint32_t* __restrict__ base, uint32_t* __restrict__ table, size_t seq_words) {
+__device__ __forceinline__ void roi_boxes_body(const RoiBoxJob job, const gf_box* __restrict__ boxes, const int w, const int h,
+                                               const uint32_t* __restrict__ base, uint32_t* __restrict__ table, size_t seq_words) {
     __shared__ uint32_t s_rows[kRoiBoxPiece];
     __shared__ int s_x0[kRoiBoxPiece], s_x1[kRoiBoxPiece];
-    const RoiBoxJob job = jobs[blockIdx.z];
     const int band = blockIdx.y, t = threadIdx.x;
     const int x = (blockIdx.x * kRoiBoxPiece + t) * kRoiBoxWords;
     uint32_t cov[kRoiBoxWords] = {0, 0, 0, 0};
@@ -370,6 +403,20 @@ __global__ void __launch_bounds__(kRoiBoxPiece) roi_boxes_kernel(const RoiBoxJob
 #pragma unroll
     for (int k = 0; k < kRoiBoxWords; k++) v[k] = gfroi::compose_word(v[k], cov[k]);
     roi_words_io<true>(table + g, g, n, v);
+}
+__global__ void __launch_bounds__(kRoiBoxPiece) roi_boxes_kernel(const RoiBoxJob* __restrict__ jobs, const gf_box* __restrict__ boxes, int w, int h,
+                                                                 const uint32_t* __restrict__ base, uint32_t* __restrict__ table, size_t seq_words) {
+    roi_boxes_body(jobs[blockIdx.z], boxes, w, h, base, table, seq_words);
+}
+// A frame size per sequence: job.pad names the row of the handle's table of sizes that the job's sequence has; the boxes are clipped to that frame and the words
+// composed in its geometry.  Gridded for the largest listed frame: a block outside its own frame leaves as a whole, before the first barrier.
+__global__ void __launch_bounds__(kRoiBoxPiece) roi_boxes_sized_kernel(const RoiBoxJob* __restrict__ jobs, const gf_box* __restrict__ boxes, const SizeRow* __restrict__ rows,
+                                                                       const uint32_t* __restrict__ base, uint32_t* __restrict__ table, size_t seq_words) {
+    const RoiBoxJob job = jobs[blockIdx.z];
+    const SizeRow& r = rows[__builtin_amdgcn_readfirstlane(job.pad)];
+    const int w = __builtin_amdgcn_readfirstlane(r.w), h = __builtin_amdgcn_readfirstlane(r.h);
+    if ((int)(blockIdx.x * kRoiBoxSpan) >= w || (int)blockIdx.y >= gfroi::bands(h)) return;
+    roi_boxes_body(job, boxes, w, h, base, table, seq_words);
 }
 
 // Both selection kernels run one block per list position and touch only tables of the call ([count], by position): the candidates, want, the output and the
@@ -417,7 +464,7 @@ constexpr int kTopKMax = 16;
 constexpr int kTopKQ = 4;   // candidates per thread held in registers (4 096 per sequence; more are streamed from global memory every round)
 // REFS (here and in select_corners_body): A.depth is the call's table of gf_frame_ref instead of tight frames (gfref::depth_at).
 template <bool REFS>
-__device__ __forceinline__ void select_topk_body(const SelectArgs& A, unsigned long long* s_best) {
+__device__ __forceinline__ void select_topk_body(const SelectArgs& A, const int w, unsigned long long* s_best) {
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int want = A.want[b];
     if (want <= 0) { if (tid == 0) A.out_n[b] = 0; return; }
@@ -441,7 +488,7 @@ __device__ __forceinline__ void select_topk_body(const SelectArgs& A, unsigned l
         unsigned long long k = i < n ? gk[i] : 0ull;
         if (!(f32_from_orderable((unsigned)(k >> 32)) > thresh)) k = 0ull;
         const unsigned off = (unsigned)(k & 0xffffffffu);
-        ky[q] = (int)(off / (unsigned)A.w); kx[q] = (int)(off - (unsigned)ky[q] * A.w);
+        ky[q] = (int)(off / (unsigned)w); kx[q] = (int)(off - (unsigned)ky[q] * w);
         kq[q] = k;
     }
     const bool streamed = n > 1024 * kTopKQ;   // the rest of a very long list is read again every round and tested against every accepted corner
@@ -460,7 +507,7 @@ __device__ __forceinline__ void select_topk_body(const SelectArgs& A, unsigned l
                 const unsigned long long k = gk[i];
                 if (k >= last || !(f32_from_orderable((unsigned)(k >> 32)) > thresh)) continue;
                 const unsigned off = (unsigned)(k & 0xffffffffu);
-                const int y = (int)(off / (unsigned)A.w), x = (int)(off - (unsigned)y * A.w);
+                const int y = (int)(off / (unsigned)w), x = (int)(off - (unsigned)y * w);
                 bool ok = true;
 #pragma unroll
                 for (int a = 0; a < kTopKMax; a++) {
@@ -481,7 +528,7 @@ __device__ __forceinline__ void select_topk_body(const SelectArgs& A, unsigned l
         best = s_best[r % 3];
         if (best == 0) break;   // the same word in every thread
         const unsigned off = (unsigned)(best & 0xffffffffu);
-        const int y = (int)(off / (unsigned)A.w), x = (int)(off - (unsigned)y * A.w);
+        const int y = (int)(off / (unsigned)w), x = (int)(off - (unsigned)y * w);
 #pragma unroll
         for (int a = 0; a < kTopKMax; a++) if (a == nacc) { ax[a] = x; ay[a] = y; }
 #pragma unroll
@@ -500,17 +547,22 @@ __device__ __forceinline__ void select_topk_body(const SelectArgs& A, unsigned l
 }
 __global__ void __launch_bounds__(1024) select_topk_kernel(SelectArgs A) {
     __shared__ unsigned long long s_best[3];
-    select_topk_body<false>(A, s_best);
+    select_topk_body<false>(A, A.w, s_best);
 }
 __global__ void __launch_bounds__(1024) select_topk_refs_kernel(SelectArgs A) {
     __shared__ unsigned long long s_best[3];
-    select_topk_body<true>(A, s_best);
+    select_topk_body<true>(A, A.w, s_best);
+}
+// A frame size per sequence: the width the candidates' offsets were packed with is the list position's own (detect_strip_sized_kernel); depth through the table
+__global__ void __launch_bounds__(1024) select_topk_sized_kernel(SelectArgs A, const SizeRow* __restrict__ rows, const uint8_t* __restrict__ size_of) {
+    __shared__ unsigned long long s_best[3];
+    select_topk_body<true>(A, __builtin_amdgcn_readfirstlane(size_row(rows, size_of, blockIdx.x).w), s_best);
 }
 
 // One 1024-thread block per sequence: sort candidates (value desc, address desc), then wavefront 0 runs the
 // greedy minimum-distance selection 64 candidates at a time against a cell grid of accepted corners.
 template <bool REFS>
-__device__ __forceinline__ void select_corners_body(const SelectArgs& A) {
+__device__ __forceinline__ void select_corners_body(const SelectArgs& A, const int w, const int h) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int want = A.want[b];
@@ -565,7 +617,7 @@ __device__ __forceinline__ void select_corners_body(const SelectArgs& A) {
     // the sequence's own spacing: a larger cell than the one the handle's min_dist sized the area for needs less of it
     const int min_dist = A.min_dist_of ? A.min_dist_of[b] : A.min_dist;
     const int cell = min_dist >= 1 ? min_dist : 1;
-    const int gw = (A.w + cell - 1) / cell, gh = (A.h + cell - 1) / cell;
+    const int gw = (w + cell - 1) / cell, gh = (h + cell - 1) / cell;
     // accepted corners live after the key area: head[gw*gh] (int16 index or -1), then (x,y,next) records
     short* head = reinterpret_cast<short*>(smem + (size_t)A.sort_cap * 8);
     short* rec = head + ((gw * gh + 3) & ~3);  // rec[3*i] = x, y, next
@@ -580,7 +632,7 @@ __device__ __forceinline__ void select_corners_body(const SelectArgs& A) {
         const bool valid = key != 0ull;
         if (!__any(valid)) break;  // zero keys (below threshold / padding) sort last
         const unsigned off = (unsigned)(key & 0xffffffffu);
-        const int y = (int)(off / (unsigned)A.w), x = (int)(off - (unsigned)y * A.w);
+        const int y = (int)(off / (unsigned)w), x = (int)(off - (unsigned)y * w);
         const int xc = x / cell, yc = y / cell;
         bool good = valid;
         if (good && min_dist >= 1) {
@@ -616,7 +668,12 @@ __device__ __forceinline__ void select_corners_body(const SelectArgs& A) {
     }
     if (lane == 0) A.out_n[b] = naccept;
 }
-__global__ void __launch_bounds__(1024) select_corners_kernel(SelectArgs A) { select_corners_body<false>(A); }
-__global__ void __launch_bounds__(1024) select_corners_refs_kernel(SelectArgs A) { select_corners_body<true>(A); }
+__global__ void __launch_bounds__(1024) select_corners_kernel(SelectArgs A) { select_corners_body<false>(A, A.w, A.h); }
+__global__ void __launch_bounds__(1024) select_corners_refs_kernel(SelectArgs A) { select_corners_body<true>(A, A.w, A.h); }
+// A frame size per sequence: the selection grid is that of the list position's own frame, which fits the area sized for the handle's
+__global__ void __launch_bounds__(1024) select_corners_sized_kernel(SelectArgs A, const SizeRow* __restrict__ rows, const uint8_t* __restrict__ size_of) {
+    const SizeRow& r = size_row(rows, size_of, blockIdx.x);
+    select_corners_body<true>(A, __builtin_amdgcn_readfirstlane(r.w), __builtin_amdgcn_readfirstlane(r.h));
+}
 
 }  // namespace gf

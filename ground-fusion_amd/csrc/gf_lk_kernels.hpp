@@ -690,7 +690,7 @@ struct LkBatchArgs {
 // row/column indexing (:155-168).
 // REFS (here and in lk_track_mp_body): A.depth is the call's table of gf_frame_ref instead of tight frames (gfref::depth_at).
 template <bool REFS>
-__device__ __forceinline__ void lk_track_body(const PyrGeom& G, const LkBatchArgs& A, uint8_t* tiles) {
+__device__ __forceinline__ void lk_track_body(const PyrGeom& G, const size_t slot_bytes, const LkBatchArgs& A, uint8_t* tiles) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int b = blockIdx.y;
     const int i = blockIdx.x * 4 + wave;
@@ -703,8 +703,8 @@ __device__ __forceinline__ void lk_track_body(const PyrGeom& G, const LkBatchArg
     float2 pp = A.prev_pts[pi];
     pp.x = unif(pp.x); pp.y = unif(pp.y);
     const int cur = list_entry(A.cur_of, b);
-    const uint8_t* prevI = A.img + (size_t)(cur ^ 1) * G.img_bytes;
-    const uint8_t* curI = A.img + (size_t)cur * G.img_bytes;
+    const uint8_t* prevI = A.img + (size_t)(cur ^ 1) * slot_bytes;
+    const uint8_t* curI = A.img + (size_t)cur * slot_bytes;
     unsigned n_levels = 0, n_iters = 0;
     float cx, cy;
     int st;
@@ -748,11 +748,23 @@ __device__ __forceinline__ void lk_track_body(const PyrGeom& G, const LkBatchArg
 }
 __global__ void __launch_bounds__(256, 7) lk_track_kernel(PyrGeom G, LkBatchArgs A) {
     __shared__ __attribute__((aligned(16))) uint8_t tiles[4 * kTileBytes];
-    lk_track_body<false>(G, A, tiles);
+    lk_track_body<false>(G, G.img_bytes, A, tiles);
 }
 __global__ void __launch_bounds__(256, 7) lk_track_refs_kernel(PyrGeom G, LkBatchArgs A) {
     __shared__ __attribute__((aligned(16))) uint8_t tiles[4 * kTileBytes];
-    lk_track_body<true>(G, A, tiles);
+    lk_track_body<true>(G, G.img_bytes, A, tiles);
+}
+// A frame size per sequence (gf_seq_size.hpp): the geometry of a block's list position is a row of the handle's table of sizes, named by one byte per list
+// position that travels with cur_of.  The index is the block's, so the row is read with block-uniform loads where the by-value argument of the forms above
+// lies; the distance between two pyramid slots is the handle's, not the row's.  Depth samples go through the call's table of gf_frame_ref (the _refs form),
+// which the host builds from the frames' own sizes.  The arithmetic of a point is lk_track_body's.
+struct SizeRow { PyrGeom G; int w, h, pad[2]; };
+__device__ __forceinline__ const SizeRow& size_row(const SizeRow* __restrict__ rows, const uint8_t* __restrict__ size_of, unsigned i) {
+    return rows[__builtin_amdgcn_readfirstlane((int)size_of[i])];
+}
+__global__ void __launch_bounds__(256, 7) lk_track_sized_kernel(const SizeRow* __restrict__ rows, const uint8_t* __restrict__ size_of, size_t slot_bytes, LkBatchArgs A) {
+    __shared__ __attribute__((aligned(16))) uint8_t tiles[4 * kTileBytes];
+    lk_track_body<true>(size_row(rows, size_of, blockIdx.y).G, slot_bytes, A, tiles);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -987,7 +999,7 @@ __device__ __forceinline__ int lk_solve_mp(const PyrGeom& G, const uint8_t* imI,
 
 // P points per wavefront, four wavefronts per block: grid.x = ceil(cap / (4 P)), grid.y = list position.  Same outputs as lk_track_kernel, bit for bit.
 template <int P, bool REFS>
-__device__ __forceinline__ void lk_track_mp_body(const PyrGeom& G, const LkBatchArgs& A, uint8_t* tiles) {
+__device__ __forceinline__ void lk_track_mp_body(const PyrGeom& G, const size_t slot_bytes, const LkBatchArgs& A, uint8_t* tiles) {
     constexpr int SH = LkGroup<P>::SH;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int b = blockIdx.y;
@@ -1003,8 +1015,8 @@ __device__ __forceinline__ void lk_track_mp_body(const PyrGeom& G, const LkBatch
     const size_t pi = (size_t)b * A.cap + min(i, n - 1);
     const float2 pp = A.prev_pts[pi];
     const int cur = list_entry(A.cur_of, b);
-    const uint8_t* prevI = A.img + (size_t)(cur ^ 1) * G.img_bytes;
-    const uint8_t* curI = A.img + (size_t)cur * G.img_bytes;
+    const uint8_t* prevI = A.img + (size_t)(cur ^ 1) * slot_bytes;
+    const uint8_t* curI = A.img + (size_t)cur * slot_bytes;
     unsigned n_levels = 0, n_iters = 0;
     float cx, cy;
     if (A.fwd_use_init) { const float2 ip = A.init_pts[pi]; cx = ip.x; cy = ip.y; } else { cx = 0.f; cy = 0.f; }
@@ -1050,12 +1062,17 @@ __device__ __forceinline__ void lk_track_mp_body(const PyrGeom& G, const LkBatch
 template <int P>
 __global__ void __launch_bounds__(256, P == 4 ? 2 : 3) lk_track_mp_kernel(PyrGeom G, LkBatchArgs A) {
     __shared__ __attribute__((aligned(16))) uint8_t tiles[4 * P * kTileBytes];
-    lk_track_mp_body<P, false>(G, A, tiles);
+    lk_track_mp_body<P, false>(G, G.img_bytes, A, tiles);
 }
 template <int P>
 __global__ void __launch_bounds__(256, P == 4 ? 2 : 3) lk_track_mp_refs_kernel(PyrGeom G, LkBatchArgs A) {
     __shared__ __attribute__((aligned(16))) uint8_t tiles[4 * P * kTileBytes];
-    lk_track_mp_body<P, true>(G, A, tiles);
+    lk_track_mp_body<P, true>(G, G.img_bytes, A, tiles);
+}
+template <int P>
+__global__ void __launch_bounds__(256, P == 4 ? 2 : 3) lk_track_mp_sized_kernel(const SizeRow* __restrict__ rows, const uint8_t* __restrict__ size_of, size_t slot_bytes, LkBatchArgs A) {
+    __shared__ __attribute__((aligned(16))) uint8_t tiles[4 * P * kTileBytes];
+    lk_track_mp_body<P, true>(size_row(rows, size_of, blockIdx.y).G, slot_bytes, A, tiles);
 }
 
 // The derivative image of one level as lk_solve evaluates it (same device functions), for gf_pyramid_level's parity check against calcSharrDeriv:

@@ -43,6 +43,7 @@
 #include "gf_roi.hpp"
 #include "gf_seq_cfg.hpp"
 #include "gf_seq_format.hpp"
+#include "gf_seq_size.hpp"
 #include "gf_track_draw.hpp"
 #include "gf_track_host.hpp"
 
@@ -246,8 +247,29 @@ struct gf_tracker {
     DevBuf<int> d_cam_of; PinBuf<int> h_cam_of;
     DevBuf<float2> d_un_lk, d_un_out; PinBuf<float2> h_un_lk, h_un_out;
 
+    // A frame size per sequence (gf_seq_size.hpp; gf_tracker_set_seq_size), the seventh thing addressed by SEQUENCE.  sizes: the sizes in force (row 0: the handle's
+    // own) and each sequence's row, host memory only until a setter gives a sequence a size of its own.  Everything else is obtained by that first setter: d_size_rows,
+    // the table as the kernels read it (a row written by the setter that takes it), and per call, by list position: the byte that names each position's row
+    // (h_size_of: page-locked, carried to d_size_of by the copy list in front of LK and of the detection) and the compact per-size tables of the front's launches
+    // (SizeSub below), which those launches read over the bus as they read the list.  size_plan: of the call in progress, or of a setter.
+    gfsize::Table sizes;
+    bool size_any = false;
+    gfsize::Plan size_plan;
+    std::vector<int> size_bpp;            // scratch of plan_sizes: bytes per pixel of each listed sequence's format
+    // of a call with sizes, per distinct size g of the plan: how many of its members are converted / equalised, and where its slots of d_cvt / d_eq begin (bytes)
+    // and its entries of the dense table of equalisation sources and sets of LUTs (entries)
+    int size_ncvt[GF_MAX_SEQ_SIZES] = {}, size_neq[GF_MAX_SEQ_SIZES] = {}, size_eq_first[GF_MAX_SEQ_SIZES] = {};
+    size_t size_cvt_at[GF_MAX_SEQ_SIZES] = {}, size_eq_at[GF_MAX_SEQ_SIZES] = {};
+    PyrGeom size_geom[GF_MAX_SEQ_SIZES];
+    DevBuf<SizeRow> d_size_rows;
+    DevBuf<uint8_t> d_size_of; PinBuf<uint8_t> h_size_of;
+    DevBuf<uint8_t> d_size_sub; PinBuf<uint8_t> h_size_sub;
+
     std::unique_ptr<HostPool> pool;
 };
+static_assert(gfsize::kPad == gf::kPad && gfsize::kWin == gf::kWin && gfsize::kMaxLevels == gf::kMaxLevels, "gf_seq_size.hpp restates the pyramid's constants");
+static_assert(sizeof(gfsize::Geom) == sizeof(gf::PyrGeom) && offsetof(gfsize::Geom, nlevels) == offsetof(gf::PyrGeom, nlevels) && offsetof(gfsize::Geom, img_bytes) == offsetof(gf::PyrGeom, img_bytes) &&
+              sizeof(gfsize::Level) == sizeof(gf::LevelGeom) && offsetof(gfsize::Level, img_off) == offsetof(gf::LevelGeom, img_off), "gfsize::Geom is PyrGeom field for field");
 
 namespace gf {
 
@@ -256,9 +278,10 @@ namespace gf {
 // d_raw_frames: `count` frames back to back, frame i for the sequence at list position i; cur_of[i]: the pyramid it is written to (device-readable, [count]).
 // refs (the _refs entry points, MONO8 without equalisation): the frames lie at refs[i] instead (device-readable table; d_raw_frames is not read).  The kernel
 // follows the sizes as before and each block takes the load form its own frame's pointer and pitch allow.  *widest: the widest piece of the launched first reader.
-static int launch_pyramid(gf_tracker* h, const uint8_t* d_raw_frames, int count, const int* cur_of, const gf_frame_ref* refs = nullptr, int* widest = nullptr) {
-    const PyrGeom& G = h->G;
-    const size_t seq_img = G.img_bytes;   // distance between two pyramids, whichever sequence and slot they belong to
+// geom (a frame size per sequence, gf_seq_size.hpp): the geometry of the `count` frames where it is not the handle's; the pyramids still lie the handle's slots apart.
+static int launch_pyramid(gf_tracker* h, const uint8_t* d_raw_frames, int count, const int* cur_of, const gf_frame_ref* refs = nullptr, int* widest = nullptr, const PyrGeom* geom = nullptr) {
+    const PyrGeom& G = geom ? *geom : h->G;
+    const size_t seq_img = h->G.img_bytes;   // distance between two pyramids, whichever sequence and slot they belong to
     uint8_t* img = h->d_img.p;
     const LevelGeom g0 = G.lv[0];
     const bool v16 = !((g0.w | g0.stride | (int)(((size_t)g0.w * g0.h) & 15) | (int)(seq_img & 15) | (int)((g0.img_off - kPad * g0.stride - kPad) & 15)) & 15) &&
@@ -330,8 +353,16 @@ template <bool REFS> static void launch_lk_form(gf_tracker* h, int batch, const 
     else if (h->lk_points == 2) (REFS ? lk_track_mp_refs_kernel<2> : lk_track_mp_kernel<2>)<<<dim3((cap + 7) / 8, batch), 256, 0, h->stream>>>(h->G, A);
     else (REFS ? lk_track_refs_kernel : lk_track_kernel)<<<dim3((cap + 3) / 4, batch), 256, 0, h->stream>>>(h->G, A);
 }
-static void launch_lk(gf_tracker* h, int batch, const LkBatchArgs& A, bool depth_refs = false) {
-    if (depth_refs) launch_lk_form<true>(h, batch, A); else launch_lk_form<false>(h, batch, A);
+// sized (a frame size per sequence): the forms that read each list position's geometry from the handle's table of sizes; A.depth is the call's table then
+static void launch_lk_sized(gf_tracker* h, int batch, const LkBatchArgs& A) {
+    const int cap = h->cap;
+    const SizeRow* rows = h->d_size_rows.p; const uint8_t* of = h->d_size_of.p; const size_t slot = h->G.img_bytes;
+    if (h->lk_points == 4) lk_track_mp_sized_kernel<4><<<dim3((cap + 15) / 16, batch), 256, 0, h->stream>>>(rows, of, slot, A);
+    else if (h->lk_points == 2) lk_track_mp_sized_kernel<2><<<dim3((cap + 7) / 8, batch), 256, 0, h->stream>>>(rows, of, slot, A);
+    else lk_track_sized_kernel<<<dim3((cap + 3) / 4, batch), 256, 0, h->stream>>>(rows, of, slot, A);
+}
+static void launch_lk(gf_tracker* h, int batch, const LkBatchArgs& A, bool depth_refs = false, bool sized = false) {
+    if (sized) launch_lk_sized(h, batch, A); else if (depth_refs) launch_lk_form<true>(h, batch, A); else launch_lk_form<false>(h, batch, A);
 }
 
 static LkBatchArgs lk_args(gf_tracker* h, int fwd_max_level, int use_init, int flow_back, int post_checks, const uint8_t* seqmask,
@@ -359,6 +390,12 @@ static int check_list(gf_tracker* h, int count, const int* seq) {
     }
     return GF_OK;
 }
+
+// A frame size per sequence (gf_seq_size.hpp): whether the sequence has one of its own, and the frame everything of the sequence that is an image has.
+static bool seq_has_size(const gf_tracker* h, int seq) { return h->size_any && h->sizes.row_of[seq] != 0; }
+static int seq_width(const gf_tracker* h, int seq) { return h->sizes.w[h->sizes.row_of[seq]]; }     // the sequence's own frame, the handle's unless a setter said otherwise
+static int seq_height(const gf_tracker* h, int seq) { return h->sizes.h[h->sizes.row_of[seq]]; }
+static bool any_has_size(const gf_tracker* h, int count, const int* seq) { for (int i = 0; i < count; i++) if (seq_has_size(h, seq[i])) return true; return false; }
 
 // ---- region of interest (gf_roi.hpp).  The setters run between frames: every track call returns with the handle's stream drained, so the table is never written
 // under a detector that reads it; they leave on the same stream, in front of the next frame's kernels.
@@ -389,6 +426,23 @@ static int roi_packed(gf_tracker* h, int count, const int* seq) {   // behind a 
     HIPCHK(hipStreamSynchronize(h->stream));
     for (int i = 0; i < count; i++) h->roi_has[seq[i]] = 1;
     return h->d_roi_base.p ? boxes_compose(h, count, seq) : GF_OK;   // a new base under the boxes in force
+}
+// The device setters on a list with sizes (h->size_plan is its plan, h_refs[0 .. count) its masks): one launch, every mask packed in its own geometry
+static int roi_pack_sized(gf_tracker* h, int count, const int* seq) {
+    const gfsize::Plan& p = h->size_plan;
+    for (int i = 0; i < count; i++) {
+        h->h_size_of.p[i] = p.row[i];
+        if (p.row[i] != 0) {   // the words its own geometry does not reach stay all ones
+            const size_t off = (size_t)seq[i] * h->roi_words;
+            HIPCHK(hipMemsetAsync(roi_base_table(h) + off, 0xff, h->roi_words * sizeof(uint32_t), h->stream));
+        }
+    }
+    HIPCHK(hipMemcpyAsync(h->d_refs.p, h->h_refs.p, (size_t)count * sizeof(gf_frame_ref), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_size_of.p, h->h_size_of.p, (size_t)count, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_roi_seq.p, seq, (size_t)count * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    roi_pack_sized_kernel<<<dim3((p.max_w + 255) / 256, gfroi::bands(p.max_h), count), 256, 0, h->stream>>>(h->d_refs.p, h->d_roi_seq.p, h->d_size_rows.p, h->d_size_of.p, roi_base_table(h), h->roi_words);
+    HIPCHK(hipGetLastError());
+    return roi_packed(h, count, seq);
 }
 static int roi_upload(gf_tracker* h, int seq) {   // the host copy of one sequence's words -> the table
     const size_t off = (size_t)seq * h->roi_words;
@@ -429,7 +483,7 @@ static int boxes_compose(gf_tracker* h, int count, const int* seq) {
     int total = 0;
     for (int i = 0; i < count; i++) {
         const std::vector<gf_box>& b = h->boxes[seq[i]];
-        jobs[i] = RoiBoxJob{seq[i], total, (int)b.size(), 0};
+        jobs[i] = RoiBoxJob{seq[i], total, (int)b.size(), h->sizes.row_of[seq[i]]};   // .pad: the row of the sequence's size, read by the sized form alone
         if (!b.empty()) memcpy(list + total, b.data(), b.size() * sizeof(gf_box));
         total += (int)b.size();
     }
@@ -437,8 +491,12 @@ static int boxes_compose(gf_tracker* h, int count, const int* seq) {
     HIPCHK(hipMemcpyAsync(h->d_box_stage.p, h->h_box_stage.p, bytes, hipMemcpyHostToDevice, h->stream));
     const RoiBoxJob* d_jobs = reinterpret_cast<const RoiBoxJob*>(h->d_box_stage.p);
     const int W = h->cfg.width, H = h->cfg.height;
-    roi_boxes_kernel<<<dim3((W + kRoiBoxSpan - 1) / kRoiBoxSpan, gfroi::bands(H), count), kRoiBoxPiece, 0, h->stream>>>(
-        d_jobs, reinterpret_cast<const gf_box*>(d_jobs + count), W, H, h->d_roi_base.p, h->d_roi.p, h->roi_words);
+    if (any_has_size(h, count, seq))   // a frame size per sequence: each job clipped to and composed in its own frame (every size is inside the grid of the handle's)
+        roi_boxes_sized_kernel<<<dim3((W + kRoiBoxSpan - 1) / kRoiBoxSpan, gfroi::bands(H), count), kRoiBoxPiece, 0, h->stream>>>(
+            d_jobs, reinterpret_cast<const gf_box*>(d_jobs + count), h->d_size_rows.p, h->d_roi_base.p, h->d_roi.p, h->roi_words);
+    else
+        roi_boxes_kernel<<<dim3((W + kRoiBoxSpan - 1) / kRoiBoxSpan, gfroi::bands(H), count), kRoiBoxPiece, 0, h->stream>>>(
+            d_jobs, reinterpret_cast<const gf_box*>(d_jobs + count), W, H, h->d_roi_base.p, h->d_roi.p, h->roi_words);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev_boxes, h->stream));
     h->box_pending = true;
@@ -471,6 +529,19 @@ static int check_box_lists(gf_tracker* h, int count, const int* seq, const int* 
 static void plan_call(gf_tracker* h, int count, const int* seq) {
     gfseqfmt::plan_list(h->plan, h->fmt.data(), gfseqfmt::of_handle(h->cfg), count, seq, h->cfg.width, h->cfg.height);
 }
+// ---- a frame size per sequence (gf_seq_size.hpp).  The plan of the list of a call on a handle that has any: each frame with its own size and its own format's bytes.
+static void plan_sizes(gf_tracker* h, int count, const int* seq) {
+    h->size_bpp.resize(count);
+    for (int i = 0; i < count; i++) h->size_bpp[i] = gfpix::channels(h->fmt[seq[i]].pixel_format);
+    gfsize::plan_list(h->size_plan, h->sizes, count, seq, h->size_bpp.data());
+}
+// The compact tables of such a call in the page-locked block h_size_sub / d_size_sub, each [B], entry k for list position size_plan.member[k]: what the pyramid
+// reads, what the conversion reads (data null: skipped) and in which format (-1: skipped), the dense table of what the equalisation reads, and the entries of cur_of.
+struct SizeSub {
+    gf_frame_ref* pyr; gf_frame_ref* cvt; gf_frame_ref* eq; int* cur; int* fmt;
+    SizeSub(uint8_t* base, size_t B) : pyr(reinterpret_cast<gf_frame_ref*>(base)), cvt(pyr + B), eq(cvt + B), cur(reinterpret_cast<int*>(eq + B)), fmt(cur + B) {}
+    static size_t bytes(size_t B) { return B * (3 * sizeof(gf_frame_ref) + 2 * sizeof(int)); }
+};
 // The row steps of the host frames of a list on such a handle: each sequence's own (host_stride) or the call's, against a row of its own format.
 static int check_strides_listed(gf_tracker* h, int count, const int* seq, int stride) {
     for (int i = 0; i < count; i++) {
@@ -501,12 +572,40 @@ static int check_stride(gf_tracker* h, int stride) {
 }
 // The host frames of the `count` listed sequences (gf_tracker_track_some, gf_tracker_prefetch_some), refused before anything is copied.
 // *have_depth: the call has depth images, one for every listed sequence with a depth camera.
-static int check_host_frames(gf_tracker* h, int count, const int* seq, const uint8_t* const* gray, int stride, const uint16_t* const* depth, bool* have_depth) {
-    if (int rc = h->fmt_any ? check_strides_listed(h, count, seq, stride) : check_stride(h, stride)) return rc;
+// *sized: a listed sequence has a frame size of its own; h->size_plan is the plan of the list then, and the rows are checked against each sequence's own width
+static int check_host_frames(gf_tracker* h, int count, const int* seq, const uint8_t* const* gray, int stride, const uint16_t* const* depth, int dstride, bool* have_depth, bool* sized) {
+    *sized = false;
+    if (h->size_any) { plan_sizes(h, count, seq); *sized = h->size_plan.sized; }
+    if (!*sized) {
+        if (int rc = h->fmt_any ? check_strides_listed(h, count, seq, stride) : check_stride(h, stride)) return rc;
+    } else {
+        for (int i = 0; i < count; i++) {   // each sequence's own row step (host_stride) or the call's, against a row of its own width and format
+            const gf_tracker_seq_format& f = h->fmt[seq[i]];
+            const long long eff = gfseqfmt::host_stride(f, stride);
+            const int w = h->size_plan.w[i];
+            if (eff < 0 || (size_t)eff < gfseqfmt::row_bytes(w, f.pixel_format))
+                return set_err(GF_ERR_INVALID, "gray frame at list position %d (sequence %d): a stride of %lld bytes is shorter than a row of its %d pixels of %d bytes (pixel format %d)", i, seq[i], eff, w,
+                               gfpix::channels(f.pixel_format), f.pixel_format);
+        }
+    }
     *have_depth = depth != nullptr;
     for (int i = 0; i < count; i++) {
         if (!gray[i]) return set_err(GF_ERR_INVALID, "null image for sequence %d", seq[i]);
         if (*have_depth && !depth[i] && h->par[seq[i]].depth_cam) *have_depth = false;
+    }
+    if (*sized && *have_depth)
+        for (int i = 0; i < count; i++)
+            if (depth[i] && dstride < h->size_plan.w[i])
+                return set_err(GF_ERR_INVALID, "depth frame at list position %d (sequence %d): a stride of %d pixels is shorter than a row of its %d pixels", i, seq[i], dstride, h->size_plan.w[i]);
+    return GF_OK;
+}
+// The host frames of a list with sizes into `raw` on `stream`: each with its own rows, tight, at the sum of the frames before it (h->size_plan)
+static int copy_host_frames_sized(gf_tracker* h, int count, const int* seq, const uint8_t* const* gray, int stride, uint8_t* raw, hipStream_t stream) {
+    const gfsize::Plan& p = h->size_plan;
+    for (int i = 0; i < count; i++) {
+        const gf_tracker_seq_format& f = h->fmt[seq[i]];
+        const size_t row = gfseqfmt::row_bytes(p.w[i], f.pixel_format);
+        HIPCHK(hipMemcpy2DAsync(raw + p.gray_off[i], row, gray[i], (size_t)gfseqfmt::host_stride(f, stride), row, (size_t)p.h[i], hipMemcpyHostToDevice, stream));
     }
     return GF_OK;
 }
@@ -526,6 +625,10 @@ static void launch_detect(gf_tracker* h, int count, const DetectArgs& D) {
     const int W = h->cfg.width, H = h->cfg.height;
     detect_strip_kernel<kDS_R><<<dim3((W + kDS_W - 1) / kDS_W, (H + kDS_R - 1) / kDS_R, count), 64, 0, h->stream>>>(D, h->disk);
 }
+// a frame size per sequence: one launch gridded for the largest listed frame (W x H), every strip with its own frame's geometry
+static void launch_detect_sized(gf_tracker* h, int count, const DetectArgs& D, int W, int H) {
+    detect_strip_sized_kernel<kDS_R><<<dim3((W + kDS_W - 1) / kDS_W, (H + kDS_R - 1) / kDS_R, count), 64, 0, h->stream>>>(D, h->disk, h->d_size_rows.p, h->d_size_of.p);
+}
 static SelectArgs select_args(gf_tracker* h, const uint16_t* depth, int skip_small) {   // depth: tight device frames, the call's table of gf_frame_ref (launch_select<true>) or null
     const int W = h->cfg.width, H = h->cfg.height;
     SelectArgs S{};
@@ -538,6 +641,10 @@ static SelectArgs select_args(gf_tracker* h, const uint16_t* depth, int skip_sma
 template <bool REFS> static void launch_select(gf_tracker* h, int count, const SelectArgs& S, bool topk, bool sort) {
     if (topk) (REFS ? select_topk_refs_kernel : select_topk_kernel)<<<dim3(count), 1024, 0, h->stream>>>(S);
     if (sort) (REFS ? select_corners_refs_kernel : select_corners_kernel)<<<dim3(count), 1024, h->select_lds, h->stream>>>(S);
+}
+static void launch_select_sized(gf_tracker* h, int count, const SelectArgs& S, bool topk, bool sort) {
+    if (topk) select_topk_sized_kernel<<<dim3(count), 1024, 0, h->stream>>>(S, h->d_size_rows.p, h->d_size_of.p);
+    if (sort) select_corners_sized_kernel<<<dim3(count), 1024, h->select_lds, h->stream>>>(S, h->d_size_rows.p, h->d_size_of.p);
 }
 
 // Where the frames of a call lie, one per list position, in one of three forms: tight device frames with or without tight device depth frames (device());
@@ -615,8 +722,14 @@ struct Call {
     bool mixed = false;                   // a listed sequence runs with a format or switch that is not the handle's own: the front goes through h->plan
     const uint8_t* mix = nullptr;         // the table of a mixed call where the front's kernels read it (h_mix over the bus, or d_mix)
     bool did_cvt = false, did_eq = false; // the call converted / equalised at least one listed sequence (read_profile)
+    bool sized = false;                   // a listed sequence has a frame size that is not the handle's: the call goes through h->size_plan and the sized forms
+    bool size_of_down = false;            // the bytes that name each position's size are still wanted on the device: with the first copy list that leaves
+    const uint8_t* sub = nullptr;         // the compact per-size tables (SizeSub) where the front's launches read them: h_size_sub over the bus, or d_size_sub
     void lap(double& acc) { const auto n = std::chrono::steady_clock::now(); acc += std::chrono::duration<double, std::milli>(n - tp).count(); tp = n; }
-    void add_refs() { if (refs_down) { ho.down(h->d_refs, h->h_refs, (size_t)2 * h->B); refs_down = false; } }
+    void add_refs() {
+        if (refs_down) { ho.down(h->d_refs, h->h_refs, (size_t)2 * h->B); refs_down = false; }
+        if (size_of_down) { ho.down(h->d_size_of, h->h_size_of, (size_t)N); size_of_down = false; }
+    }
 };
 
 // The list has to be readable on the device before the pyramid, which is launched before the first copy list so that it runs under the host's table filling.
@@ -654,6 +767,54 @@ static int publish(Call& c) {
         if (!mix_bus) HIPCHK(hipMemcpyAsync(h->d_mix.p, h->h_mix.p, h->h_mix.n, hipMemcpyHostToDevice, h->stream));
         c.mix = mix_bus ? h->h_mix.hd : h->d_mix.p;
     }
+    if (c.sized) {   // a frame size per sequence (gf_seq_size.hpp): every frame by pointer and pitch, whichever way the caller handed it in
+        const gfsize::Plan& p = h->size_plan;
+        const size_t B = (size_t)h->B;
+        // the depth half of the frame table, which the sized forms of LK and the selection sample through: the caller's entries, or tight frames at the sum of those before
+        const bool kd = in.depth || in.depth_refs;
+        if (!in.gray_refs)
+            for (int i = 0; i < c.N; i++)
+                h->h_refs.p[B + i] = in.depth ? gf_frame_ref{reinterpret_cast<const uint8_t*>(in.depth) + p.depth_off[i], (size_t)p.w[i] * 2} : gf_frame_ref{nullptr, 0};
+        c.kdepth = kd ? reinterpret_cast<const uint16_t*>(h->d_refs.p + B) : nullptr;
+        // the compact tables: entry k belongs to list position member[k].  Per distinct size the members that are converted take the slots of d_cvt from that
+        // size's first on, in list order, and those that are equalised the slots of d_eq and the sets of LUTs likewise; each stage reads what the one before it left.
+        SizeSub t(h->h_size_sub.p, B);
+        size_t cvt_at = 0, eq_at = 0;
+        int eq_first = 0;
+        for (int g = 0; g < p.n_groups; g++) {
+            const size_t px = (size_t)h->sizes.w[p.group_row[g]] * h->sizes.h[p.group_row[g]];
+            const size_t pitch = (size_t)h->sizes.w[p.group_row[g]];
+            h->size_cvt_at[g] = cvt_at; h->size_eq_at[g] = eq_at; h->size_eq_first[g] = eq_first;
+            int n_cvt = 0, n_eq = 0;
+            for (int k = p.group_first[g]; k < p.group_first[g] + p.group_n[g]; k++) {
+                const int i = p.member[k];
+                const gf_tracker_seq_format& f = h->fmt[c.seq[i]];
+                gf_frame_ref cur = in.gray_refs ? in.gray_refs[i] : gf_frame_ref{in.gray + p.gray_off[i], gfseqfmt::row_bytes(p.w[i], f.pixel_format)};
+                t.cur[k] = h->h_cur.p[i];
+                const bool conv = f.pixel_format != GF_PIX_MONO8;
+                t.fmt[k] = conv ? f.pixel_format : -1;
+                t.cvt[k] = conv ? cur : gf_frame_ref{nullptr, 0};
+                if (conv) { cur = gf_frame_ref{h->d_cvt.p + cvt_at + (size_t)(k - p.group_first[g]) * px, pitch}; n_cvt++; }   // the slot is the entry's index in its size's launch
+                if (f.equalize) { t.eq[eq_first + n_eq] = cur; cur = gf_frame_ref{h->d_eq.p + eq_at + (size_t)n_eq * px, pitch}; n_eq++; }
+                t.pyr[k] = cur;
+            }
+            h->size_ncvt[g] = n_cvt; h->size_neq[g] = n_eq;
+            if (n_cvt) cvt_at += (size_t)p.group_n[g] * px;
+            eq_at += (size_t)n_eq * px; eq_first += n_eq;
+        }
+        for (int i = 0; i < c.N; i++) h->h_size_of.p[i] = p.row[i];
+        const bool sub_bus = over_bus && h->h_size_sub.hd;
+        if (!sub_bus) HIPCHK(hipMemcpyAsync(h->d_size_sub.p, h->h_size_sub.p, h->h_size_sub.n, hipMemcpyHostToDevice, h->stream));
+        c.sub = sub_bus ? h->h_size_sub.hd : h->d_size_sub.p;
+        // the bytes and the depth half go down with the list: by the copy list in front of LK / the detection, or by plain copies here
+        const bool tables_bus = over_bus && h->h_size_of.hd && h->h_refs.hd;
+        if (tables_bus) { c.size_of_down = true; c.refs_down = kd; }
+        else {
+            HIPCHK(hipMemcpyAsync(h->d_size_of.p, h->h_size_of.p, (size_t)c.N, hipMemcpyHostToDevice, h->stream));
+            if (kd) HIPCHK(hipMemcpyAsync(h->d_refs.p, h->h_refs.p, 2 * B * sizeof(gf_frame_ref), hipMemcpyHostToDevice, h->stream));
+            c.refs_down = false;
+        }
+    }
     return GF_OK;
 }
 
@@ -666,6 +827,39 @@ static int launch_front(Call& c) {
     const gf_frame_ref* refs = c.refs;
     int refs_widest = 16, refs_narrow = -1;   // the widest piece of the first reader of the caller's frames; frames it counted itself
     if (prof) HIPCHK(hipEventRecord(h->ev[0], h->stream));
+    if (c.sized) {   // a frame size per sequence: each stage once per distinct size of the call that needs it, over that size's members -- conversion, CLAHE, and
+        // one pass of launch_pyramid with the route a handle of that size takes
+        const gfsize::Plan& p = h->size_plan;
+        const SizeSub t(const_cast<uint8_t*>(c.sub), (size_t)h->B), ht(h->h_size_sub.p, (size_t)h->B);
+        for (int g = 0; g < p.n_groups; g++) {
+            if (!h->size_ncvt[g]) continue;
+            const int first = p.group_first[g], fw = h->sizes.w[p.group_row[g]], fh = h->sizes.h[p.group_row[g]];
+            if (int rc = cvt_launch_mixed(t.cvt + first, t.fmt + first, ht.cvt + first, ht.fmt + first, h->d_cvt.p + h->size_cvt_at[g], p.group_n[g], fw, fh, h->stream)) return rc;
+            c.did_cvt = true;
+        }
+        if (c.did_cvt && prof) HIPCHK(hipEventRecord(h->ev[8], h->stream));
+        for (int g = 0; g < p.n_groups; g++) {
+            if (!h->size_neq[g]) continue;
+            const int fw = h->sizes.w[p.group_row[g]], fh = h->sizes.h[p.group_row[g]];
+            if (int rc = clahe_launch_refs(t.eq + h->size_eq_first[g], h->d_eq.p + h->size_eq_at[g], h->d_eq_lut.p + clahe_lut_bytes(h->size_eq_first[g], kClaheTiles, kClaheTiles), h->size_neq[g], fw, fh,
+                                           kClaheClip, kClaheTiles, kClaheTiles, h->stream)) return rc;
+            c.did_eq = true;
+        }
+        if (c.did_eq && prof) HIPCHK(hipEventRecord(h->ev[7], h->stream));
+        for (int g = 0; g < p.n_groups; g++) {
+            int widest = 16;
+            if (int rc = launch_pyramid(h, nullptr, p.group_n[g], t.cur + p.group_first[g], t.pyr + p.group_first[g], &widest, &h->size_geom[p.group_row[g]])) return rc;
+            if (c.in.gray_refs)   // each frame against the widest piece of ITS first reader: the conversion's dwords, CLAHE's or the pyramid's 16 bytes
+                for (int k = p.group_first[g]; k < p.group_first[g] + p.group_n[g]; k++) {
+                    const int i = p.member[k];
+                    const gf_tracker_seq_format& f = h->fmt[c.seq[i]];
+                    const int first_reader = f.pixel_format != GF_PIX_MONO8 ? 4 : f.equalize ? ((p.w[i] & 15) ? 4 : 16) : widest;
+                    h->stats.frames_unaligned += gfref::unaligned(reinterpret_cast<uintptr_t>(c.in.gray_refs[i].data), c.in.gray_refs[i].pitch, first_reader) ? 1 : 0;
+                }
+        }
+        if (prof) HIPCHK(hipEventRecord(h->ev[1], h->stream));
+        return GF_OK;
+    }
     if (c.mixed) {   // formats per sequence (gf_seq_format.hpp): the same three stages through the plan's tables, each over the positions that need it
         const gfseqfmt::Plan& p = h->plan;
         const gf_frame_ref* t = reinterpret_cast<const gf_frame_ref*>(c.mix);
@@ -742,8 +936,8 @@ static int run_lk(Call& c) {
         }
         if (int rc = ho.flush()) return rc;
         if (h->profiling) HIPCHK(hipEventRecord(h->ev[2], h->stream));
-        if (c.any_plain) { launch_lk(h, N, lk_args(h, 3, 0, h->cfg.flow_back, 1, mask_plain, c.kdepth), c.in.depth_by_refs()); h->stats.lk_launches++; }
-        if (c.any_pred) { launch_lk(h, N, lk_args(h, 1, 1, h->cfg.flow_back, 1, mask_pred, c.kdepth), c.in.depth_by_refs()); h->stats.lk_launches++; }
+        if (c.any_plain) { launch_lk(h, N, lk_args(h, 3, 0, h->cfg.flow_back, 1, mask_plain, c.kdepth), c.in.depth_by_refs(), c.sized); h->stats.lk_launches++; }
+        if (c.any_pred) { launch_lk(h, N, lk_args(h, 1, 1, h->cfg.flow_back, 1, mask_pred, c.kdepth), c.in.depth_by_refs(), c.sized); h->stats.lk_launches++; }
         HIPCHK(hipGetLastError());
         if (h->profiling) HIPCHK(hipEventRecord(h->ev[3], h->stream));
         ho.up(h->h_cur_pts, h->d_cur_pts, (size_t)N * cap);
@@ -777,7 +971,7 @@ static int redo_fallback(Call& c) {
     std::vector<uint16_t> keep_depth(h->h_depth_out.p, h->h_depth_out.p + (size_t)N * cap);
     std::vector<unsigned> keep_cnt(h->h_counters.p, h->h_counters.p + (size_t)N * cap * 2);
     HIPCHK(hipMemcpyAsync(h->d_seqmask.p, h->h_seqmask.p, N, hipMemcpyHostToDevice, h->stream));
-    launch_lk(h, N, lk_args(h, 3, 0, h->cfg.flow_back, 1, h->d_seqmask.p, c.kdepth), c.in.depth_by_refs());
+    launch_lk(h, N, lk_args(h, 3, 0, h->cfg.flow_back, 1, h->d_seqmask.p, c.kdepth), c.in.depth_by_refs(), c.sized);
     h->stats.lk_launches++;
     HIPCHK(hipGetLastError());
     c.ho.up(h->h_cur_pts, h->d_cur_pts, (size_t)N * cap);
@@ -812,7 +1006,8 @@ static void book_after_lk(Call& c) {
         const uint32_t* roi = !h->roi_has.empty() && h->roi_has[q] ? h->roi_bits.data() + (size_t)q * h->roi_words : nullptr;
         int want = 0;
         const gf_box* boxes = h->boxes.empty() ? nullptr : h->boxes[q].data();
-        const LkTally n = after_lk(h->seq[q], par, h->cfg.width, h->cfg.height, h->seq_disk.empty() ? h->disk : h->seq_disk[q], roi, r, row(h->h_centers, b, cap), h->h_ncenters.p + b, &want,
+        const int fw = c.sized ? h->size_plan.w[b] : h->cfg.width, fh = c.sized ? h->size_plan.h[b] : h->cfg.height;   // the sequence's own frame (feature_tracker.cpp:108-109)
+        const LkTally n = after_lk(h->seq[q], par, fw, fh, h->seq_disk.empty() ? h->disk : h->seq_disk[q], roi, r, row(h->h_centers, b, cap), h->h_ncenters.p + b, &want,
                                    boxes, boxes ? (int)h->boxes[q].size() : 0, h->d_cams.p && !h->lift_host && h->cam_on[q]);
         a_levels += n.level_passes; a_iters += n.iterations; a_points += n.points; a_tracked += n.tracked;
         h->h_want.p[b] = want;
@@ -861,13 +1056,13 @@ static int run_detect(Call& c) {
         HIPCHK(hipMemsetAsync(h->d_maxkey.p, 0, N * sizeof(unsigned), h->stream));
         HIPCHK(hipMemsetAsync(h->d_cand_count.p, 0, N * sizeof(int), h->stream));
         if (prof) HIPCHK(hipEventRecord(h->ev[4], h->stream));
-        launch_detect(h, N, detect_args(h));
+        if (c.sized) launch_detect_sized(h, N, detect_args(h), h->size_plan.max_w, h->size_plan.max_h); else launch_detect(h, N, detect_args(h));
         // the sequences that want a handful of corners (every frame but the first ones): one maximum per corner instead of a sort (select_topk_kernel; GF_SELECT_TOPK=0: off)
         int max_want = 0;
         for (int i = 0; i < N; i++) max_want = std::max(max_want, h->h_want.p[i]);
         const bool topk = h->select_topk, sort = !topk || max_want > kTopKMax;
         const SelectArgs S = select_args(h, c.kdepth, topk ? 1 : 0);
-        if (c.in.depth_by_refs()) launch_select<true>(h, N, S, topk, sort); else launch_select<false>(h, N, S, topk, sort);
+        if (c.sized) launch_select_sized(h, N, S, topk, sort); else if (c.in.depth_by_refs()) launch_select<true>(h, N, S, topk, sort); else launch_select<false>(h, N, S, topk, sort);
         HIPCHK(hipGetLastError());
         if (c.lift) if (int rc = launch_lift(c)) return rc;
         ho.up(h->h_out_n, h->d_out_n, N);
@@ -953,6 +1148,7 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
     if (count == 0) return GF_OK;
     Call c{h, count, seq, in, HandOver(h->copy_lists, h->stream)};
     if (h->fmt_any) { plan_call(h, count, seq); c.mixed = !h->plan.homogeneous; }
+    if (h->size_any) { plan_sizes(h, count, seq); c.sized = h->size_plan.sized; if (c.sized) c.mixed = false; }   // the sized front walks the formats itself
     for (int i = 0; i < count; i++) h->h_cur.p[i] = 2 * seq[i] + begin_frame(h->seq[seq[i]], t[i]);   // the new frame goes to the sequence's other pyramid
     if (int rc = publish(c)) return rc;
     if (int rc = launch_front(c)) return rc;
@@ -1005,6 +1201,7 @@ int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out) {
     h->par.assign(h->B, gfseq::of_handle(*cfg));
     h->fmt.assign(h->B, gfseqfmt::of_handle(*cfg));
     h->raw_ch = h->ch;
+    h->sizes.init(cfg->width, cfg->height, h->B);
     h->ident.resize(h->B);
     for (int b = 0; b < h->B; b++) h->ident[b] = b;
     {
@@ -1086,10 +1283,12 @@ static int refs_ready(gf_tracker* h) {   // the first _refs call of a handle: th
     return GF_OK;
 }
 // every entry of a table of `count`, or GF_ERR_INVALID naming the list position; what: "gray", "depth" or "mask"
-static int check_refs(const gf_tracker* h, int count, const int* seq, const gf_frame_ref* refs, size_t row_bytes, bool u16, const char* what) {
+// own_size: bytes per pixel of an image that has the sequence's own frame size where a setter gave it one (0: row_bytes holds whatever the sizes)
+static int check_refs(const gf_tracker* h, int count, const int* seq, const gf_frame_ref* refs, size_t row_bytes, bool u16, const char* what, size_t own_size = 0) {
     const bool own_rows = row_bytes == 0;   // gray frames: a row of each sequence's own format (gf_tracker_set_seq_format)
     for (int i = 0; i < count; i++) {
         if (own_rows) row_bytes = gfseqfmt::row_bytes(h->cfg.width, h->fmt[seq[i]].pixel_format);
+        if (h->size_any && own_size) row_bytes = own_rows ? gfseqfmt::row_bytes(seq_width(h, seq[i]), h->fmt[seq[i]].pixel_format) : (size_t)seq_width(h, seq[i]) * own_size;   // a row of the sequence's own width (gf_tracker_set_seq_size)
         const gfref::Verdict v = gfref::check(refs[i], row_bytes, u16, u16 && !h->par[seq[i]].depth_cam);
         if (v != gfref::kOk)
             return set_err(GF_ERR_INVALID, "%s frame at list position %d (sequence %d): %s (data %p, pitch %zu bytes, a row is %zu bytes)", what, i, seq[i], gfref::verdict_text(v), refs[i].data, refs[i].pitch, row_bytes);
@@ -1105,8 +1304,8 @@ int gf_tracker_track_some_device_refs(gf_tracker* h, int count, const int* seq, 
     if (count == 0) return GF_OK;
     if (!gray) return gf::set_err(GF_ERR_INVALID, "null table of gray frames");
     if (!t || !out || !n_out) return gf::set_err(GF_ERR_INVALID, "null argument");
-    if (int rc = gf::check_refs(h, count, seq, gray, 0, false, "gray")) return rc;
-    if (depth) if (int rc = gf::check_refs(h, count, seq, depth, (size_t)h->cfg.width * 2, true, "depth")) return rc;
+    if (int rc = gf::check_refs(h, count, seq, gray, 0, false, "gray", 1)) return rc;
+    if (depth) if (int rc = gf::check_refs(h, count, seq, depth, (size_t)h->cfg.width * 2, true, "depth", 2)) return rc;
     if (int rc = gf::refs_ready(h)) return rc;
     return gf::track_core(h, count, seq, t, gf::FrameInput::by_refs(gray, depth), out, cap, n_out);
 }
@@ -1122,11 +1321,12 @@ int gf_tracker_track_some(gf_tracker* h, int count, const int* seq, const double
     if (int rc = gf::check_list(h, count, seq)) return rc;
     if (count == 0) return GF_OK;
     if (!t || !gray || !out || !n_out) return gf::set_err(GF_ERR_INVALID, "null argument");
-    bool have_depth = false;
-    if (int rc = gf::check_host_frames(h, count, seq, gray, stride, depth, &have_depth)) return rc;   // refuse before the first copy
+    bool have_depth = false, sized = false;
+    if (int rc = gf::check_host_frames(h, count, seq, gray, stride, depth, dstride, &have_depth, &sized)) return rc;   // refuse before the first copy
     const size_t row = (size_t)h->cfg.width * h->ch;   // bytes of a row of the handle's pixel format
     const int H = h->cfg.height;
-    if (h->fmt_any) { if (int rc = gf::copy_host_frames(h, count, seq, gray, stride, h->d_raw.p, h->stream)) return rc; }
+    if (sized) { if (int rc = gf::copy_host_frames_sized(h, count, seq, gray, stride, h->d_raw.p, h->stream)) return rc; }
+    else if (h->fmt_any) { if (int rc = gf::copy_host_frames(h, count, seq, gray, stride, h->d_raw.p, h->stream)) return rc; }
     else for (int i = 0; i < count; i++) HIPCHK(hipMemcpy2DAsync(h->d_raw.p + (size_t)i * row * H, row, gray[i], stride, row, H, hipMemcpyHostToDevice, h->stream));
     // the depth image stays where it is: its <= max_cnt samples are taken on the host (after_lk, after_detect)
     return gf::track_core(h, count, seq, t, gf::FrameInput::with_host_depth(h->d_raw.p, have_depth ? depth : nullptr, dstride), out, cap, n_out);
@@ -1140,8 +1340,8 @@ int gf_tracker_prefetch_some(gf_tracker* h, int count, const int* seq, const uin
     if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
     if (int rc = gf::check_list(h, count, seq)) return rc;
     if (count > 0 && !gray) return gf::set_err(GF_ERR_INVALID, "null argument");
-    bool have_depth = false;
-    if (int rc = gf::check_host_frames(h, count, seq, gray, stride, depth, &have_depth)) return rc;
+    bool have_depth = false, sized = false;
+    if (int rc = gf::check_host_frames(h, count, seq, gray, stride, depth, dstride, &have_depth, &sized)) return rc;
     const size_t row = (size_t)h->cfg.width * h->ch;   // bytes of a row of the handle's pixel format
     const int H = h->cfg.height;
     if (h->pf_count >= 2) return gf::set_err(GF_ERR_CAPACITY, "two frames are staged already: gf_tracker_track_prefetched has to consume one first");
@@ -1153,9 +1353,10 @@ int gf_tracker_prefetch_some(gf_tracker* h, int count, const int* seq, const uin
     const int slot = (h->pf_head + h->pf_count) & 1;      // a pair no frame in flight uses: track calls return when their frame is done
     uint8_t* raw = slot ? h->d_raw2.p : h->d_raw.p;
     // images that sit back to back in one allocation (a pinned ring of frames) go as ONE copy per plane: 256 separate 2-D copies cost more host time than the bus needs
-    bool contig = (size_t)stride == row && !h->fmt_any;
+    bool contig = (size_t)stride == row && !h->fmt_any && !sized;
     for (int i = 1; i < count && contig; i++) contig = gray[i] == gray[0] + (size_t)i * row * H;
-    if (h->fmt_any) { if (int rc = gf::copy_host_frames(h, count, seq, gray, stride, raw, h->copy_stream)) return rc; }
+    if (sized) { if (int rc = gf::copy_host_frames_sized(h, count, seq, gray, stride, raw, h->copy_stream)) return rc; }
+    else if (h->fmt_any) { if (int rc = gf::copy_host_frames(h, count, seq, gray, stride, raw, h->copy_stream)) return rc; }
     else if (contig && count > 0) HIPCHK(hipMemcpyAsync(raw, gray[0], (size_t)count * row * H, hipMemcpyHostToDevice, h->copy_stream));
     else for (int i = 0; i < count; i++) HIPCHK(hipMemcpy2DAsync(raw + (size_t)i * row * H, row, gray[i], stride, row, H, hipMemcpyHostToDevice, h->copy_stream));
     HIPCHK(hipEventRecord(h->ev_copy[slot], h->copy_stream));
@@ -1222,12 +1423,13 @@ int gf_tracker_set_prediction(gf_tracker* h, int seq, const int* ids, const doub
 int gf_tracker_set_roi(gf_tracker* h, int seq, const uint8_t* mask, int stride) {
     if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
     if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
-    const int W = h->cfg.width, H = h->cfg.height;
+    const int W = gf::seq_width(h, seq), H = gf::seq_height(h, seq);   // the mask is an image of the sequence's own size
     if (mask && stride < W) return gf::set_err(GF_ERR_INVALID, "a mask stride of %d bytes is shorter than a row of %d pixels", stride, W);
     if (!mask && !h->d_roi.p) return GF_OK;   // nothing to clear: the handle stays one that never had a region
     if (int rc = gf::roi_ready(h)) return rc;
     if (mask) {
         uint32_t* t = h->roi_bits.data() + (size_t)seq * h->roi_words;
+        if (gf::seq_has_size(h, seq)) std::fill_n(t, h->roi_words, ~0u);   // the words its own geometry does not reach
         for (int band = 0; band < gfroi::bands(H); band++)
             for (int x = 0; x < W; x++)
                 gfroi::pack_thread(mask, (size_t)stride, W, H, band, x, t);
@@ -1246,6 +1448,11 @@ int gf_tracker_set_roi_some_device(gf_tracker* h, int count, const int* seq, con
         return GF_OK;
     }
     const int W = h->cfg.width, H = h->cfg.height;
+    if (gf::any_has_size(h, count, seq)) {   // masks of the sequences' own sizes, back to back: mask i at the sum of the masks before it
+        gfsize::plan_list(h->size_plan, h->sizes, count, seq);
+        for (int i = 0; i < count; i++) h->h_refs.p[i] = gf_frame_ref{static_cast<const uint8_t*>(d_masks) + h->size_plan.mask_off[i], (size_t)h->size_plan.w[i]};
+        return gf::roi_pack_sized(h, count, seq);
+    }
     HIPCHK(hipMemcpyAsync(h->d_roi_seq.p, seq, (size_t)count * sizeof(int), hipMemcpyHostToDevice, h->stream));
     gf::roi_pack_kernel<<<dim3((W + 255) / 256, gfroi::bands(H), count), 256, 0, h->stream>>>((const uint8_t*)d_masks, h->d_roi_seq.p, W, H, gf::roi_base_table(h), h->roi_words);
     HIPCHK(hipGetLastError());
@@ -1258,10 +1465,11 @@ int gf_tracker_set_roi_some_device_refs(gf_tracker* h, int count, const int* seq
     if (int rc = gf::check_list(h, count, seq)) return rc;
     if (count == 0) return GF_OK;
     const int W = h->cfg.width, H = h->cfg.height;
-    if (int rc = gf::check_refs(h, count, seq, masks, (size_t)W, false, "mask")) return rc;
+    if (int rc = gf::check_refs(h, count, seq, masks, (size_t)W, false, "mask", 1)) return rc;
     if (int rc = gf::roi_ready(h)) return rc;
     if (int rc = gf::refs_ready(h)) return rc;
     for (int i = 0; i < count; i++) h->h_refs.p[i] = masks[i];
+    if (gf::any_has_size(h, count, seq)) { gfsize::plan_list(h->size_plan, h->sizes, count, seq); return gf::roi_pack_sized(h, count, seq); }
     HIPCHK(hipMemcpyAsync(h->d_refs.p, h->h_refs.p, (size_t)count * sizeof(gf_frame_ref), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_roi_seq.p, seq, (size_t)count * sizeof(int), hipMemcpyHostToDevice, h->stream));
     gf::roi_pack_refs_kernel<<<dim3((W + 255) / 256, gfroi::bands(H), count), 256, 0, h->stream>>>(h->d_refs.p, h->d_roi_seq.p, W, H, gf::roi_base_table(h), h->roi_words);
@@ -1272,7 +1480,7 @@ int gf_tracker_set_roi_some_device_refs(gf_tracker* h, int count, const int* seq
 int gf_tracker_get_roi(gf_tracker* h, int seq, uint8_t* mask, int stride, int* has) {
     if (!h || !has) return gf::set_err(GF_ERR_INVALID, "null argument");
     if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
-    const int W = h->cfg.width, H = h->cfg.height;
+    const int W = gf::seq_width(h, seq), H = gf::seq_height(h, seq);   // a mask of the sequence's own size
     if (mask && stride < W) return gf::set_err(GF_ERR_INVALID, "a mask stride of %d bytes is shorter than a row of %d pixels", stride, W);
     const bool base = !h->roi_has.empty() && h->roi_has[seq];
     const int nb = h->boxes.empty() ? 0 : (int)h->boxes[seq].size();
@@ -1449,7 +1657,7 @@ int gf_tracker_set_seq_format(gf_tracker* h, int seq, const gf_tracker_seq_forma
     const gf_tracker_seq_format own = gfseqfmt::of_handle(h->cfg), want = f ? *f : own;
     const int W = h->cfg.width, H = h->cfg.height, B = h->B;
     char msg[256];
-    if (f && !gfseqfmt::fits(W, H, want, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "sequence %d: %s", seq, msg);
+    if (f && !gfseqfmt::fits(gf::seq_width(h, seq), gf::seq_height(h, seq), want, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "sequence %d: %s", seq, msg);   // (rows of the sequence's own width)
     if (!f && !h->fmt_any) return GF_OK;   // nothing to take back: the handle stays one that never set any
     // what a handle created with that format would have, into locals first: a failed allocation changes nothing
     const size_t px = (size_t)W * H;
@@ -1474,6 +1682,72 @@ int gf_tracker_get_seq_format(gf_tracker* h, int seq, gf_tracker_seq_format* out
     if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
     if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
     *out = h->fmt[seq];
+    return GF_OK;
+}
+
+// ---- a frame size per sequence (gf_seq_size.hpp; `row`, `col` of trackImage, feature_tracker.cpp:108-109).  Between frames, with the stream drained.
+namespace gf {
+static int seq_size_ready(gf_tracker* h) {   // the first setter that gives a sequence a size of its own: the table of sizes, the per-call tables, the frame table of the depth samples
+    if (h->d_size_rows.p) return GF_OK;
+    if (int rc = refs_ready(h)) return rc;
+    const size_t B = (size_t)h->B, sub = SizeSub::bytes(B);
+    DevBuf<SizeRow> rows; DevBuf<uint8_t> of, dsub; PinBuf<uint8_t> hof, hsub;
+    HIPCHK(rows.alloc(GF_MAX_SEQ_SIZES)); HIPCHK(of.alloc(B)); HIPCHK(hof.alloc(B)); HIPCHK(dsub.alloc(sub)); HIPCHK(hsub.alloc(sub));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(select_corners_sized_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->select_lds));
+    SizeRow own{};
+    own.G = h->G; own.w = h->cfg.width; own.h = h->cfg.height;
+    HIPCHK(hipMemcpy(rows.p, &own, sizeof own, hipMemcpyHostToDevice));
+    h->size_geom[0] = h->G;
+    h->d_size_rows = std::move(rows); h->d_size_of = std::move(of); h->h_size_of = std::move(hof); h->d_size_sub = std::move(dsub); h->h_size_sub = std::move(hsub);
+    return GF_OK;
+}
+}  // namespace gf
+
+int gf_tracker_set_seq_size(gf_tracker* h, int seq, int width, int height) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    const int W = h->cfg.width, H = h->cfg.height;
+    const bool back = width == 0 && height == 0;
+    char msg[256];
+    if (!back && !gfsize::limits_ok(W, H, width, height, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "sequence %d: %s", seq, msg);
+    if (!back && !gfsize::fits_slot(width, height, W, H)) return gf::set_err(GF_ERR_INVALID, "sequence %d: the pyramid of width %d, height %d does not fit the slot of %d x %d", seq, width, height, W, H);
+    const bool own = back || (width == W && height == H);
+    if (own && !h->size_any) return GF_OK;   // nothing to take back, whatever the sequence's state: the handle stays one that never set any
+    if (h->seq[seq].started) return gf::set_err(GF_ERR_INVALID, "sequence %d has taken a frame: its width and height are fixed until gf_tracker_reset_seq", seq);
+    if (gf::seq_is_staged(h, seq)) return gf::set_err(GF_ERR_INVALID, "sequence %d is listed by a staged frame: gf_tracker_track_prefetched has to consume it first (width, height)", seq);
+    if (!h->roi_has.empty() && h->roi_has[seq]) return gf::set_err(GF_ERR_INVALID, "sequence %d has a region of interest, an image of its present width and height: clear it first (gf_tracker_set_roi with a null mask)", seq);
+    const int r = h->sizes.find(seq, own ? 0 : width, own ? 0 : height);
+    if (r < 0) return gf::set_err(GF_ERR_INVALID, "sequence %d: width %d, height %d would be distinct size %d on the handle, GF_MAX_SEQ_SIZES is %d", seq, width, height, GF_MAX_SEQ_SIZES + 1, GF_MAX_SEQ_SIZES);
+    if (int rc = gf::seq_size_ready(h)) return rc;
+    if (r != 0) {
+        gfsize::Geom g;
+        gfsize::build_geom(width, height, g);
+        gf::SizeRow row{};
+        memcpy(&row.G, &g, sizeof g);
+        row.w = width; row.h = height;
+        HIPCHK(hipMemcpy(h->d_size_rows.p + r, &row, sizeof row, hipMemcpyHostToDevice));
+        h->size_geom[r] = row.G;
+    }
+    h->sizes.move(seq, r, width, height);
+    h->size_any = true;
+    // The sequence's rows of the region tables were written in the geometry of the size it leaves (a compose writes the words of its own frame alone), and the
+    // detector will read them in the new one: the whole rows go back to all ones -- the sequence has no base region here -- whether or not it has boxes, and the
+    // boxes, which stay, are clipped to and composed in the new frame.
+    if (h->d_roi.p) {
+        const size_t off = (size_t)seq * h->roi_words;
+        HIPCHK(hipMemsetAsync(h->d_roi.p + off, 0xff, h->roi_words * sizeof(uint32_t), h->stream));
+        if (h->d_roi_base.p) HIPCHK(hipMemsetAsync(h->d_roi_base.p + off, 0xff, h->roi_words * sizeof(uint32_t), h->stream));
+        if (!h->boxes.empty() && !h->boxes[seq].empty()) { if (int rc = gf::boxes_compose(h, 1, &seq)) return rc; }
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return GF_OK;
+}
+
+int gf_tracker_get_seq_size(gf_tracker* h, int seq, int* width, int* height) {
+    if (!h || !width || !height) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    const int r = h->sizes.row_of[seq];
+    *width = h->sizes.w[r]; *height = h->sizes.h[r];
     return GF_OK;
 }
 
@@ -1512,9 +1786,10 @@ static size_t draw_room(const gf_tracker* h) { return gfdraw::list_capacity(h->c
 static int draw_check(gf_tracker* h, int count, const int* seq, const gf_frame_ref* dst) {
     if (int rc = check_list(h, count, seq)) return rc;
     if (count > 0 && !dst) return set_err(GF_ERR_INVALID, "null table of destinations");
-    const size_t row_bytes = 3 * (size_t)h->cfg.width, room = draw_room(h);
+    const size_t room = draw_room(h);
     for (int i = 0; i < count; i++) {
         const SeqState& s = h->seq[seq[i]];
+        const size_t row_bytes = 3 * (size_t)seq_width(h, seq[i]);   // a picture of the sequence's own size
         if (!s.show_track) return set_err(GF_ERR_INVALID, "list position %d (sequence %d): show_track is off (gf_tracker_set_show_track)", i, seq[i]);
         if (!s.draw_have && !s.draw_why.empty()) return set_err(GF_ERR_INVALID, "list position %d (sequence %d): the list of its last frame was refused: %s", i, seq[i], s.draw_why.c_str());
         if (!s.draw_have) return set_err(GF_ERR_INVALID, "list position %d (sequence %d): no frame recorded since the switch went on, the handle was created or the sequence reset", i, seq[i]);
@@ -1528,20 +1803,28 @@ static int draw_check(gf_tracker* h, int count, const int* seq, const gf_frame_r
 // the checked call: lists that are new since the sequence's last picture go down, then the jobs, one launch, and the host waits
 static int draw_run(gf_tracker* h, int count, const int* seq, const gf_frame_ref* dst) {
     const size_t room = draw_room(h);
-    const LevelGeom g0 = h->G.lv[0];
-    for (int i = 0; i < count; i++) {
+    // a frame size per sequence: one launch per distinct size of the list over that size's members; the jobs lie in the order of the plan's compact table
+    const bool sized = any_has_size(h, count, seq);
+    if (sized) gfsize::plan_list(h->size_plan, h->sizes, count, seq);
+    for (int k = 0; k < count; k++) {
+        const int i = sized ? h->size_plan.member[k] : k;
         const int q = seq[i];
+        const LevelGeom g0 = sized ? h->size_geom[h->size_plan.row[i]].lv[0] : h->G.lv[0];
         SeqState& s = h->seq[q];
         if (!s.draw_sent && !s.draw_list.empty()) {
             memcpy(h->h_draw_prims.p + (size_t)q * room, s.draw_list.data(), s.draw_list.size() * sizeof(gfdraw::Prim));
             HIPCHK(hipMemcpyAsync(h->d_draw_prims.p + (size_t)q * room, h->h_draw_prims.p + (size_t)q * room, s.draw_list.size() * sizeof(gfdraw::Prim), hipMemcpyHostToDevice, h->stream));
         }
         // the background: level 0 of the sequence's newest pyramid, the MONO8 image trackImage tracked on (converted, equalised)
-        h->h_draw_jobs.p[i] = gfdraw::DrawJob{h->d_img.p + (size_t)(2 * q + s.slot) * h->G.img_bytes + g0.img_off, (size_t)g0.stride,
+        h->h_draw_jobs.p[k] = gfdraw::DrawJob{h->d_img.p + (size_t)(2 * q + s.slot) * h->G.img_bytes + g0.img_off, (size_t)g0.stride,
                                               static_cast<uint8_t*>(const_cast<void*>(dst[i].data)), dst[i].pitch, h->d_draw_prims.p + (size_t)q * room, (int)s.draw_list.size(), 0};
     }
     HIPCHK(hipMemcpyAsync(h->d_draw_jobs.p, h->h_draw_jobs.p, (size_t)count * sizeof(gfdraw::DrawJob), hipMemcpyHostToDevice, h->stream));
-    if (int rc = draw_track_launch(h->d_draw_jobs.p, count, h->cfg.width, h->cfg.height, h->stream)) return rc;
+    if (sized) {
+        const gfsize::Plan& p = h->size_plan;
+        for (int g = 0; g < p.n_groups; g++)
+            if (int rc = draw_track_launch(h->d_draw_jobs.p + p.group_first[g], p.group_n[g], h->sizes.w[p.group_row[g]], h->sizes.h[p.group_row[g]], h->stream)) return rc;
+    } else if (int rc = draw_track_launch(h->d_draw_jobs.p, count, h->cfg.width, h->cfg.height, h->stream)) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));   // the images are complete, and the page-locked tables free for the next call
     for (int i = 0; i < count; i++) h->seq[seq[i]].draw_sent = true;   // only now: a call that failed on the way sends its lists again
     return GF_OK;
@@ -1558,14 +1841,16 @@ int gf_tracker_track_image_some_device(gf_tracker* h, int count, const int* seq,
 int gf_tracker_track_image(gf_tracker* h, int seq, uint8_t* dst, int stride) {
     if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
     if (!dst) return gf::set_err(GF_ERR_INVALID, "null destination");
-    const size_t row = 3 * (size_t)h->cfg.width;
-    if (stride < 0 || (size_t)stride < row) return gf::set_err(GF_ERR_INVALID, "a stride of %d bytes is shorter than a row of %d pixels of 3 bytes", stride, h->cfg.width);
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    const int fw = gf::seq_width(h, seq), fh = gf::seq_height(h, seq);   // a picture of the sequence's own size
+    const size_t row = 3 * (size_t)fw;
+    if (stride < 0 || (size_t)stride < row) return gf::set_err(GF_ERR_INVALID, "a stride of %d bytes is shorter than a row of %d pixels of 3 bytes", stride, fw);
     gf_frame_ref ref{dst, row};   // checked as the caller's; rendered into the handle's staging image
     if (int rc = gf::draw_check(h, 1, &seq, &ref)) return rc;
-    HIPCHK(h->d_draw_host.fit(row * h->cfg.height));
+    HIPCHK(h->d_draw_host.fit(row * fh));
     ref.data = h->d_draw_host.p;
     if (int rc = gf::draw_run(h, 1, &seq, &ref)) return rc;
-    HIPCHK(hipMemcpy2D(dst, (size_t)stride, h->d_draw_host.p, row, row, h->cfg.height, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy2D(dst, (size_t)stride, h->d_draw_host.p, row, row, fh, hipMemcpyDeviceToHost));
     return GF_OK;
 }
 

@@ -216,7 +216,9 @@ EXPORTS = ["gf_last_error", "gf_device_count", "gf_set_device", "gf_tracker_crea
            "gf_tracker_set_boxes_some", "gf_tracker_get_boxes", "gf_roi_boxes_batch", "gf_estimator_set_boxes", "gf_draw_track_boxes_batch",
            "gf_tracker_set_seq_format", "gf_tracker_get_seq_format", "gf_cvt_gray_mixed", "gf_cvt_gray_mixed_device",
            "gf_tracker_set_seq_camera", "gf_tracker_get_seq_camera", "gf_camera_lift_batch", "gf_camera_lift_batch_device", "gf_camera_project_batch",
-           "gf_camera_from_yaml", "gf_estimator_cfg_from_yaml_camera", "gf_estimator_set_camera"]
+           "gf_camera_from_yaml", "gf_estimator_cfg_from_yaml_camera", "gf_estimator_set_camera",
+           "gf_tracker_set_seq_size", "gf_tracker_get_seq_size"]
+MAX_SEQ_SIZES = 8   # GF_MAX_SEQ_SIZES
 
 
 def lib():
@@ -268,6 +270,7 @@ class FeatureTracker:
         self.channels = pix_bytes(self.cfg.pixel_format)   # a handle of a format with more than one byte per pixel takes [height, width, bytes] u8 frames wherever a MONO8 handle takes [height, width]
         self.row_bytes = self.cfg.width * self.channels
         self._fmt = {}   # set_seq_format: the sequences that have a format of their own, seq -> (pixel_format, equalize, host_stride)
+        self._size = {}  # set_seq_size: the sequences that have a frame size of their own, seq -> (width, height)
 
     def close(self):
         if getattr(self, "h", None):
@@ -301,14 +304,17 @@ class FeatureTracker:
         seqs, N = self._seqs(seqs)
         ts = np.ascontiguousarray(ts, np.float64)
         assert len(ts) == N and len(imgs) == N and (depths is None or len(depths) == N)
-        if self._fmt:   # formats per sequence (set_seq_format): each frame in its sequence's own shape and row step
+        if self._fmt or self._size:   # formats / sizes per sequence (set_seq_format, set_seq_size): each frame in its sequence's own shape and row step
             imgs, stride = self._host_frames(seqs, imgs, stride)
+            if self._size and depths is not None:
+                depths, dstride = self._sized_depths(seqs, depths, dstride)
         else:
             imgs = [None if i is None else np.ascontiguousarray(i, np.uint8) if stride is None else self._pitched(i, np.uint8, stride) for i in imgs]
         gp = (C.POINTER(C.c_uint8) * max(N, 1))(*[None if i is None else _p(i, C.c_uint8) for i in imgs])
         if depths is not None:
             # (an entry may be None for a sequence whose own depth_cam is 0, set_seq_cfg: its image is not read)
-            depths = [None if d is None else np.ascontiguousarray(d, np.uint16) if dstride is None else self._pitched(d, np.uint16, dstride) for d in depths]
+            if not self._size:
+                depths = [None if d is None else np.ascontiguousarray(d, np.uint16) if dstride is None else self._pitched(d, np.uint16, dstride) for d in depths]
             dp = (C.POINTER(C.c_uint16) * max(N, 1))(*[None if d is None else _p(d, C.c_uint16) for d in depths])
         else:
             dp = None
@@ -383,7 +389,7 @@ class FeatureTracker:
     def trackImageBatch(self, ts, imgs, depths=None, stride=None, dstride=None):
         """stride / dstride: row pitch of the gray (bytes) / depth (u16 elements) images, for frames with padded rows (cv::Mat::step); default: contiguous rows"""
         B = self.cfg.batch
-        if self._fmt:   # formats per sequence: the list form with every sequence listed takes each frame in its own shape
+        if self._fmt or self._size:   # formats / sizes per sequence: the list form with every sequence listed takes each frame in its own shape
             return self.trackImageSome(range(B), ts, imgs, depths, stride, dstride)
         ts = np.ascontiguousarray(ts, np.float64)
         imgs = [np.ascontiguousarray(i, np.uint8) for i in imgs] if stride is None else [self._pitched(i, np.uint8, stride) for i in imgs]
@@ -401,8 +407,12 @@ class FeatureTracker:
 
     def trackImageBatchDevice(self, ts, d_gray_ptr, d_depth_ptr=None, unpack=True, out=None, n_out=None):
         """d_*_ptr: integer device addresses (e.g. torch tensor .data_ptr()) of batch contiguous frames.  out / n_out: the caller's [batch][cap] OBS_DTYPE table
-        and [batch] int32 counts to write into (e.g. one of a ring, while estimators still read the previous frames' tables); default: the tracker's own pair."""
+        and [batch] int32 counts to write into (e.g. one of a ring, while estimators still read the previous frames' tables); default: the tracker's own pair.
+        On a handle with sizes or formats per sequence the frames do NOT lie one handle-sized frame apart: frame b has its own height x width x bytes per pixel
+        and starts where the frames before it end (device_frame_offsets(), device_size_offsets(itemsize=2) for depth), as in trackImageSomeDevice, which serves the call then."""
         B = self.cfg.batch
+        if self._size:
+            return self.trackImageSomeDevice(range(B), ts, d_gray_ptr, d_depth_ptr, unpack, out, n_out)
         ts = np.ascontiguousarray(ts, np.float64)
         if out is None:
             if not hasattr(self, "_out"):
@@ -425,6 +435,8 @@ class FeatureTracker:
         stride, dstride = stride or self.row_bytes, dstride or self.cfg.width
         if seqs is not None:
             seqs, B = self._seqs(seqs)
+        # sizes per sequence: the frames of a block would not lie one stride x height apart -- one address per frame, each of its own height, rows stride apart
+        assert not self._size or (isinstance(gray_addr, (list, tuple)) and (not depth_addr or isinstance(depth_addr, (list, tuple))))
         self._pf_n = getattr(self, "_pf_n", []) + [B]
         ga = list(gray_addr) if isinstance(gray_addr, (list, tuple)) else [gray_addr + b * stride * H for b in range(B)]
         gp = (C.POINTER(C.c_uint8) * B)(*[C.cast(a, C.POINTER(C.c_uint8)) for a in ga])
@@ -469,15 +481,21 @@ class FeatureTracker:
             _chk(lib().gf_tracker_set_roi(self.h, seq, None, 0))
             return
         mask = np.asarray(mask)
-        assert mask.dtype == np.uint8 and mask.shape == (self.cfg.height, self.cfg.width), (mask.dtype, mask.shape)
-        if mask.strides[1] != 1 or mask.strides[0] < self.cfg.width:
+        w, h = self.seq_size(seq)   # the sequence's own frame (set_seq_size)
+        assert mask.dtype == np.uint8 and mask.shape == (h, w), (mask.dtype, mask.shape)
+        if mask.strides[1] != 1 or mask.strides[0] < w:
             mask = np.ascontiguousarray(mask)
         _chk(lib().gf_tracker_set_roi(self.h, seq, _p(mask, C.c_uint8), mask.strides[0]))
 
-    def set_roi_device(self, seqs, d_masks_ptr):
+    def set_roi_device(self, seqs, d_masks_ptr, nbytes=None):
         """gf_tracker_set_roi_some_device: d_masks_ptr = integer device address of len(seqs) tight [height, width] u8 masks back to back, mask i for sequence
-        seqs[i] (complete when the call is made); None / 0 clears the listed sequences"""
+        seqs[i] (complete when the call is made); None / 0 clears the listed sequences.  On a handle with sizes per sequence (set_seq_size) every mask has its
+        sequence's own size and starts where the masks before it end (device_size_offsets).  The library cannot tell a block laid out otherwise -- at the handle's
+        size, say -- from a right one: a pointer carries no size.  nbytes: the bytes the caller's block holds; a check of this wrapper alone, ValueError unless
+        it is the sum of the listed masks"""
         seqs, N = self._seqs(seqs)
+        if d_masks_ptr and nbytes is not None and nbytes != self.device_size_offsets(seqs)[1]:
+            raise ValueError("a block of %d bytes where the masks of the listed sequences, each of its own size, add up to %d" % (nbytes, self.device_size_offsets(seqs)[1]))
         _chk(lib().gf_tracker_set_roi_some_device(self.h, N, _p(seqs, C.c_int), C.c_void_p(d_masks_ptr) if d_masks_ptr else None))
 
     def set_roi_device_refs(self, seqs, mask_refs):
@@ -489,9 +507,10 @@ class FeatureTracker:
 
     def get_roi(self, seq=0):
         """gf_tracker_get_roi: the stored region of sequence `seq` as a [height, width] u8 image of 0 / 255, or None if it has none"""
-        mask = np.zeros((self.cfg.height, self.cfg.width), np.uint8)
+        w, h = self.seq_size(seq)
+        mask = np.zeros((h, w), np.uint8)
         has = C.c_int(0)
-        _chk(lib().gf_tracker_get_roi(self.h, seq, _p(mask, C.c_uint8), self.cfg.width, C.byref(has)))
+        _chk(lib().gf_tracker_get_roi(self.h, seq, _p(mask, C.c_uint8), w, C.byref(has)))
         return mask if has.value else None
 
     def set_boxes(self, boxes, seq=0):
@@ -569,6 +588,56 @@ class FeatureTracker:
         _chk(lib().gf_tracker_get_seq_format(self.h, seq, C.byref(f)))
         return {k: getattr(f, k) for k, _ in TrackerSeqFormat._fields_}
 
+    def set_seq_size(self, seq, width, height):
+        """gf_tracker_set_seq_size: sequence `seq` takes frames of width x height (<= the handle's, which is the capacity); (0, 0): back to the handle's size.
+        From then on the frame-taking methods take, for that sequence, [height, width] u8 frames and u16 depth images.  Refused (GfError) once the sequence has
+        taken a frame, until reset_seq, while a prefetched frame lists it, and while it has a region of interest."""
+        _chk(lib().gf_tracker_set_seq_size(self.h, int(seq), int(width), int(height)))
+        w, h = self.get_seq_size(seq)
+        if (w, h) == (self.cfg.width, self.cfg.height):
+            self._size.pop(int(seq), None)
+        else:
+            self._size[int(seq)] = (w, h)
+
+    def get_seq_size(self, seq):
+        """gf_tracker_get_seq_size: (width, height) in force for sequence `seq` (the handle's unless set_seq_size gave it its own)"""
+        w, h = C.c_int(0), C.c_int(0)
+        _chk(lib().gf_tracker_get_seq_size(self.h, int(seq), C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def seq_size(self, seq):
+        """(width, height) of sequence `seq` as the frame-taking methods expect its arrays"""
+        return self._size.get(int(seq), (self.cfg.width, self.cfg.height))
+
+    def device_size_offsets(self, seqs=None, itemsize=1):
+        """the layout of the tight device entry points on a handle with sizes per sequence: (byte offset of the frame of each listed sequence, total bytes) --
+        frame i has its own height x width x itemsize bytes (1: masks, 2: depth; gray frames: device_frame_offsets, which knows their formats) and starts where
+        the frames listed before it end"""
+        seqs = range(self.cfg.batch) if seqs is None else seqs
+        sizes = [self.seq_size(q)[0] * self.seq_size(q)[1] * itemsize for q in seqs]
+        offs = [int(o) for o in np.concatenate([[0], np.cumsum(sizes)])]
+        return offs[:-1], offs[-1]
+
+    def _sized_depths(self, seqs, depths, dstride):
+        """the depth images of a list on a handle with sizes per sequence: every image u16 [h, w] of its own sequence, its rows the call's dstride (u16 elements;
+        default: the widest listed row) apart; an image whose rows lie otherwise is copied into one that fits"""
+        shapes = [self.seq_size(q) for q in seqs]
+        dstride = dstride or max([w for w, _ in shapes] + [1])
+        out = []
+        for (w, h), d in zip(shapes, depths):
+            if d is None:
+                out.append(None)
+                continue
+            d = np.asarray(d)
+            if d.dtype != np.uint16 or d.shape != (h, w):
+                raise ValueError("a depth image of shape %s %s where its sequence takes u16 [%d, %d]" % (d.shape, d.dtype, h, w))
+            if d.strides != (2 * dstride, 2) and dstride >= w:
+                buf = np.zeros((h, dstride), np.uint16)
+                buf[:, :w] = d
+                d = buf[:, :w]
+            out.append(d)
+        return out, dstride
+
     def seq_pixel_format(self, seq):
         """the pixel format in force for sequence `seq` (the handle's own unless set_seq_format gave it one)"""
         return self._fmt.get(int(seq), (self.cfg.pixel_format,))[0]
@@ -577,14 +646,14 @@ class FeatureTracker:
         """the layout of the tight device entry points on a handle with formats per sequence: (byte offset of the frame of each listed sequence, total bytes) --
         frame i has height x width x bytes per pixel of seqs[i] bytes and starts where the frames listed before it end"""
         seqs = range(self.cfg.batch) if seqs is None else seqs
-        sizes = [self.cfg.height * self.cfg.width * pix_bytes(self.seq_pixel_format(q)) for q in seqs]
+        sizes = [self.seq_size(q)[0] * self.seq_size(q)[1] * pix_bytes(self.seq_pixel_format(q)) for q in seqs]
         offs = [int(o) for o in np.concatenate([[0], np.cumsum(sizes)])]
         return offs[:-1], offs[-1]
 
     def _host_frames(self, seqs, imgs, stride):
         """the host frames of a list on a handle with formats per sequence: each as u8 rows that lie its sequence's host_stride apart, or the call's stride
         (default: the widest listed row) where it has none; a frame whose rows lie otherwise is copied into one that fits"""
-        rows = [None if i is None else _frame_rows(i, self.seq_pixel_format(q), self.cfg.width, self.cfg.height) for q, i in zip(seqs, imgs)]
+        rows = [None if i is None else _frame_rows(i, self.seq_pixel_format(q), *self.seq_size(q)) for q, i in zip(seqs, imgs)]
         own = [self._fmt.get(int(q), (0, 0, 0))[2] for q in seqs]
         if stride is None:
             stride = max([r.shape[1] for r, o in zip(rows, own) if r is not None and not o] + [self.cfg.width])
@@ -608,8 +677,9 @@ class FeatureTracker:
     def track_image(self, seq=0):
         """gf_tracker_track_image: getTrackImage() of sequence `seq` as a [height, width, 3] u8 array in the reference's channel order (bgr8) -- the frame it
         last took with a dot per feature and an arrow back to where LK tracked it from"""
-        out = np.empty((self.cfg.height, self.cfg.width, 3), np.uint8)
-        _chk(lib().gf_tracker_track_image(self.h, seq, _p(out, C.c_uint8), 3 * self.cfg.width))
+        w, h = self.seq_size(seq)
+        out = np.empty((h, w, 3), np.uint8)
+        _chk(lib().gf_tracker_track_image(self.h, seq, _p(out, C.c_uint8), 3 * w))
         return out
 
     def track_image_device(self, seqs, dst_refs):

@@ -248,7 +248,7 @@ int gf_roi_boxes_batch(int batch, int width, int height, const int* first, const
  * host entry points the depth[i] of a listed sequence with depth_cam == 0 is not read and may be NULL.
  * The handle's cfg is also the capacity: 1 <= max_cnt <= cfg.max_cnt (the point arrays are that wide), cfg.min_dist <= min_dist <= 128 (the handle's min_dist
  * sized the selection grid and the sort area when it was created), fx, fy > 0, flow_back and depth_cam 0 or 1.  So a mixed handle is created with the largest
- * count and the tightest spacing of its fleet, and allocates nothing further for the point tables.  Width, height, equalize and pixel_format stay per handle.
+ * count and the tightest spacing of its fleet, and allocates nothing further for the point tables.  Equalize and pixel_format have their own setter (gf_tracker_set_seq_format), width and height theirs (gf_tracker_set_seq_size).
  * The parameters are fixed while a sequence holds tracking state, as they are in the reference after construction: once the sequence has taken a frame the
  * setter is refused until gf_tracker_reset_seq.  The tables (one circle table row per sequence, two small lists per call) are allocated when the first
  * parameters of a handle are set; a handle that sets none allocates and launches nothing for them.  Refused with GF_ERR_INVALID, a message that names the
@@ -293,6 +293,34 @@ typedef struct gf_tracker_seq_format {
 int gf_tracker_set_seq_format(gf_tracker* h, int seq, const gf_tracker_seq_format* f);
 /* rosNodeTest.cpp:238-261 per sequence: what is in force for seq (the handle's values for a sequence that was never set) */
 int gf_tracker_get_seq_format(gf_tracker* h, int seq, gf_tracker_seq_format* out);
+/* A frame size per sequence: `row`, `col` of FeatureTracker::trackImage (feature_tracker.cpp:108-109) for the sequence, where they are not the handle's.  A
+ * sequence that was never set has gf_tracker_cfg.width x height, and a handle on which the setter is never called allocates, copies, records and launches
+ * exactly what it did without it.  With a size of its own, a tracker call for that sequence is trackImage on frames of width x height: the observations, ids,
+ * gf_tracker_get_state and the track image are the bits of a handle created with cfg.width = width, cfg.height = height and otherwise the same settings -- the
+ * pyramid's levels, borders and stop rule, inBorder, the grey check and the depth sample, setMask's image, the detector's strips and bands and the selection
+ * grid -- in the launches it shares with its neighbours: LK, the detector, the selection and the region kernels serve every size in one launch
+ * (gf_tracker_stats.lk_launches is that of a homogeneous call); the pyramid, the conversion, CLAHE and the track image run once per distinct size among the
+ * listed sequences, the pyramid on the route a handle of that size takes (gf_tracker_stats.pyr_*).
+ * The handle's cfg is the capacity, as with max_cnt: 32 <= width <= cfg.width, 32 <= height <= cfg.height, width % 4 == 0; the sequence's pyramid slots, its
+ * row of the region table and its share of the frame buffers stay where they are and as large as they are.  At most GF_MAX_SEQ_SIZES distinct sizes are in
+ * force on a handle at a time, the handle's own included.  (0, 0) returns the sequence to the handle's size.
+ * Everything of the sequence that is an image has its size.  Gray and depth frames: on the host list entry points and gf_tracker_prefetch_some `stride` (or the
+ * sequence's host_stride) must be at least a row of its own width and format and `dstride` at least its own width; on the tight device entry points the frames
+ * lie back to back in list order, frame i has its own height x width x bytes per pixel (depth: x 2), so its offset is the sum of the frames listed before it;
+ * on the _refs entry points the pitch must be at least a row of its own width.  The region setters take masks of the sequence's size (tight device lists at
+ * prefix-sum offsets, _refs masks with a pitch of at least the own width), gf_tracker_get_roi returns one, the boxes are clipped to it, and
+ * gf_tracker_track_image* work on a picture of it.  A call with a shorter stride or pitch is refused naming the list position, and changes nothing.  A tight
+ * device list laid out otherwise (at the handle's size, say) cannot be told from a right one, since a pointer carries no size: the layout is the caller's.
+ * A setting, like gf_tracker_seq_cfg: fixed while the sequence holds tracking state (refused once it has taken a frame, until gf_tracker_reset_seq, which
+ * keeps it), refused while a frame staged by gf_tracker_prefetch_* lists the sequence and while the sequence has a region of interest, an image of the old size
+ * (clear it first); exclusion boxes stay, clipped to and composed in the new frame.  On a handle that never gave a sequence a size, (0, 0) and the handle's
+ * own size change nothing and are accepted in every state.  The first setter of a handle allocates the table of sizes and the tables of a call; GF_ERR_HIP and nothing changed
+ * if that fails.  Refused with GF_ERR_INVALID, a message that names the field, and nothing changed: a null handle, seq out of range, a size outside the
+ * limits, a ninth distinct size, and the state conditions above. */
+#define GF_MAX_SEQ_SIZES 8
+int gf_tracker_set_seq_size(gf_tracker* h, int seq, int width, int height);
+/* feature_tracker.cpp:108-109 per sequence: the size in force for seq (the handle's for a sequence that was never set) */
+int gf_tracker_get_seq_size(gf_tracker* h, int seq, int* width, int* height);
 /* A camera model per sequence: what FeatureTracker::readIntrinsicParameter (feature_tracker.cpp:745-759) gets from CameraFactory::generateCameraFromYamlFile --
  * camodocal's PINHOLE (PinholeCamera), MEI (CataCamera) or KANNALA_BRANDT (EquidistantCamera); PINHOLE_FULL and SCARAMUZZA are not built.  liftProjective
  * (undistortedPts, feature_tracker.cpp:797-808) and spaceToPlane (setPrediction, :1006-1027) of the sequence then are that model's: PinholeCamera.cc:450-542,
