@@ -1204,8 +1204,10 @@ __device__ __forceinline__ void ba_linearize_misc_body(Win w, int which, int whi
     double* sJw = sJi + (size_t)d.W * kMJi;       // [W][9][33]
     double* sW = sJw + (size_t)d.W * kMJw + (size_t)min(wave, nscr - 1) * kMScr;
     const int* imu_i = w.imu_i + (size_t)b * d.W; const int* wh_i = w.wh_i + (size_t)b * d.W;
-    auto imu_on = [&](int k) -> bool { return frame_filter != 1 || imu_i[k] == 0; };
-    auto wh_on = [&](int k) -> bool { return frame_filter != 1 || wh_i[k] == 0; };
+    // MARGIN_OLD takes the factors of interval 0 only, and of those the ones with sum_dt < 10 (estimator.cpp:3354-3375; the layout of the pass, gf_ba.hip pack_slot, leaves
+    // the blocks of a longer one without columns)
+    auto imu_on = [&](int k) -> bool { return frame_filter != 1 || (imu_i[k] == 0 && w.imu_data[((size_t)b * d.W + k) * IMU_STRIDE2] < 10.0); };
+    auto wh_on = [&](int k) -> bool { return frame_filter != 1 || (wh_i[k] == 0 && w.wh_data[((size_t)b * d.W + k) * WH_STRIDE] < 10.0); };
     GF_WSTAMP(64);
     for (int q = tid; q < nimu * kMJi; q += 64 * kMW) sJi[q] = 0.0;
     for (int q = tid; q < nwh * kMJw; q += 64 * kMW) sJw[q] = 0.0;

@@ -985,8 +985,165 @@ def main_gnss_models():
     print("wrote", path, os.path.getsize(path), "bytes,", len(tuples), "tuples")
 
 
+# ---------------------------------------------------------------- visual / IMU / wheel hard cases (tests/factor_hard_cases.py): new fixtures only, the formulas are the ones above
+def _imu_pre(w, k):
+    pre = {"sum_dt": mpf(w["imu_sum_dt"][k]), "delta_p": vec(w["imu_delta_p"][3 * k:3 * k + 3]), "delta_v": vec(w["imu_delta_v"][3 * k:3 * k + 3]),
+           "delta_q": tuple(mpf(x) for x in w["imu_delta_q"][4 * k:4 * k + 4]), "lin_ba": vec(w["imu_lin_ba"][3 * k:3 * k + 3]), "lin_bg": vec(w["imu_lin_bg"][3 * k:3 * k + 3]),
+           "jacobian": M(15, 15), "covariance": M(15, 15)}
+    for a in range(15):
+        for c in range(15):
+            pre["jacobian"][a, c] = mpf(w["imu_jacobian"][225 * k + 15 * a + c]); pre["covariance"][a, c] = mpf(w["imu_covariance"][225 * k + 15 * a + c])
+    return pre
+
+
+def _wheel_pre(w, k):
+    pre = {"delta_p": vec(w["wh_delta_p"][3 * k:3 * k + 3]), "delta_q": tuple(mpf(x) for x in w["wh_delta_q"][4 * k:4 * k + 4]), "jacobian": M(6, 3), "covariance": M(6, 6),
+           "lin": [mpf(x) for x in w["wh_lin"][4 * k:4 * k + 4]], "lin_vel": vec(w["wh_lin_vel"][3 * k:3 * k + 3]), "lin_gyr": vec(w["wh_lin_gyr"][3 * k:3 * k + 3]),
+           "vel_1": vec(w["wh_vel_1"][3 * k:3 * k + 3]), "gyr_1": vec(w["wh_gyr_1"][3 * k:3 * k + 3])}
+    for a in range(6):
+        for c in range(3):
+            pre["jacobian"][a, c] = mpf(w["wh_jacobian"][18 * k + 3 * a + c])
+        for c in range(6):
+            pre["covariance"][a, c] = mpf(w["wh_covariance"][36 * k + 6 * a + c])
+    return pre
+
+
+def factor_own_columns(w, ids, family):
+    """single-factor windows: the one factor of `family` (its list holds nothing else), r and J as it hands them to the normal equations (the visual factor after the Huber
+    corrector), and for every column only this factor feeds -- visual: the feature's inverse depth and td; IMU: the two speed-bias blocks; wheel: the wheel extrinsic, sx, sy,
+    sw, td_wheel -- every term J_row,col r_row of g, their sum at 60 digits and the sum of their absolute values"""
+    import gfwindow as gw
+    pose = [pose_of(w["para_Pose"][7 * i:7 * i + 7]) for i in range(int(w["W"]) + 1)]
+    sb = [vec(w["para_SpeedBias"][9 * i:9 * i + 9]) for i in range(int(w["W"]) + 1)]
+    if family == "visual":
+        assert int(w["n_visual"]) == 1
+        f, i, j = int(w["vis_feature"][0]), int(w["vis_i"][0]), int(w["vis_j"][0])
+        r, J = visual_factor(pose[i], pose[j], pose_of(w["para_Ex_Pose"]), mpf(w["para_Feature"][f]), mpf(w["para_Td"][0]), vec(w["vis_pts_i"][0:3]), vec(w["vis_pts_j"][0:3]),
+                             vec(w["vis_vel_i"][0:2]), vec(w["vis_vel_j"][0:2]), mpf(w["vis_td_i"][0]), mpf(w["vis_td_j"][0]), mpf(w["vis_sqrt_info"]))
+        sq = sum(x * x for x in r)
+        _, r, J = huber_correct(r, J)
+        blocks = [(gw.bid(gw.POSE, i), J["pi"]), (gw.bid(gw.POSE, j), J["pj"]), (gw.bid(gw.EX_POSE), J["ex"]), (gw.bid(gw.FEATURE, f), J["f"]), (gw.bid(gw.TD), J["td"])]
+        own, extra = [gw.bid(gw.FEATURE, f), gw.bid(gw.TD)], {"frames": [i, j], "sq_before_the_corrector": float(sq)}
+    elif family == "imu":
+        assert int(w["n_imu"]) == 1
+        i = int(w["imu_i"][0])
+        r, J = imu_factor(pose[i], sb[i], pose[i + 1], sb[i + 1], _imu_pre(w, 0), vec(w["G"]))
+        blocks = [(gw.bid(gw.POSE, i), J["pi"]), (gw.bid(gw.SPEEDBIAS, i), J["sbi"]), (gw.bid(gw.POSE, i + 1), J["pj"]), (gw.bid(gw.SPEEDBIAS, i + 1), J["sbj"])]
+        own, extra = [gw.bid(gw.SPEEDBIAS, i), gw.bid(gw.SPEEDBIAS, i + 1)], {"frames": [i, i + 1]}
+    else:
+        assert int(w["n_wheel"]) == 1
+        i = int(w["wh_i"][0])
+        r, J = wheel_factor(pose[i], pose[i + 1], pose_of(w["para_Ex_Pose_wheel"]), mpf(w["para_Ix"][0]), mpf(w["para_Ix"][1]), mpf(w["para_Ix"][2]), mpf(w["para_Td_wheel"][0]), _wheel_pre(w, 0))
+        blocks = [(gw.bid(gw.POSE, i), J["pi"]), (gw.bid(gw.POSE, i + 1), J["pj"]), (gw.bid(gw.EX_WHEEL), J["exw"]), (gw.bid(gw.SX), J["sx"]), (gw.bid(gw.SY), J["sy"]), (gw.bid(gw.SW), J["sw"]),
+                  (gw.bid(gw.TD_WHEEL), J["tdw"])]
+        own, extra = [gw.bid(gw.EX_WHEEL), gw.bid(gw.SX), gw.bid(gw.SY), gw.bid(gw.SW), gw.bid(gw.TD_WHEEL)], {"frames": [i, i + 1]}
+    cols = []
+    for b, Jm in blocks:
+        if b not in own or b not in ids:
+            continue
+        for q in range(Jm.cols):
+            terms = [Jm[row, q] * r[row] for row in range(Jm.rows)]
+            cols.append({"block": int(b), "offset": q, "column": ids.index(b) + q, "g": float(sum(terms)), "abs_sum": float(sum(abs(t) for t in terms)), "terms": [float(t) for t in terms]})
+    out = {"family": family, "r": [float(x) for x in r], "J": {str(int(b)): [[float(Jm[row, q]) for q in range(Jm.cols)] for row in range(Jm.rows)] for b, Jm in blocks}, "own_columns": cols}
+    out.update(extra)
+    return out
+
+
+def main_factor_hard(names):
+    """python tests/golden/make_ref_golden.py factor_hard [case ...]: ref_window_factor_<case>, ref_marg_old_factor_<case>, ref_solve_factor_<case> and the single-factor windows
+    of tests/factor_hard_cases.py.  The oracle's distance from every new fixture goes into profiles/factor_hard_census.json (`measured`)."""
+    import gzip
+    import time
+    import oracle_py as O
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, HERE)
+    import factor_hard_cases as FH
+    measured = {}
+
+    def dump(path, fx):
+        with gzip.GzipFile(path, "wb", mtime=0) as f:
+            f.write(json.dumps(fx).encode())
+        print("   wrote", path, os.path.getsize(path), "bytes", flush=True)
+
+    for case in (names or list(FH.ALL)):
+        kind, solved = FH.ALL[case][3], FH.ALL[case][4]
+        w = FH.window_of(case, O)
+        t0 = time.time()
+        if kind == "marg":
+            O.ba_solve(w, 4)
+            w.finalize()
+            g = marg_golden(w, 0)
+            n = g["n"]
+            JtJ = np.array([[float(g["JtJ"][a, c]) for c in range(n)] for a in range(n)])
+            Jtr = np.array([float(g["Jtr"][a]) for a in range(n)])
+            po = O.ba_marginalize(w.copy(), 0)
+            Jo = po["J"].reshape(n, n)
+            sc = np.sqrt(np.maximum(np.diag(JtJ), 1e-300))
+            dev = (float(np.abs((Jo.T @ Jo - JtJ) / np.outer(sc, sc)).max()), float(np.abs(Jo.T @ po["r"] - Jtr).max() / np.abs(Jtr).max()))
+            near = [x for x in g["eigenvalues_kept"] if 1e-12 < abs(x) < 1e-4][:8]
+            print("%s: %d dropped + %d kept columns; kept eigenvalues around the 1e-8 cut: %s; oracle vs 60 digits: J^T J scaled %.2e, J^T r rel %.2e  (%.0f s)"
+                  % (case, g["m"], n, ["%.1e" % x for x in near], dev[0], dev[1], time.time() - t0), flush=True)
+            fx = {"about": "MARGIN_OLD prior of a window of tests/factor_hard_cases.py by the reference's route at 60 digits (tests/golden/make_ref_golden.py factor_hard); layout as ref_marg_old_with_prior",
+                  "window": {k: (to_list(v) if isinstance(v, np.ndarray) else v) for k, v in dict(w).items()}, "mode": 0, "kept": [int(x) for x in g["kept"]], "m": int(g["m"]), "n": int(n),
+                  "JtJ_lower": [float(JtJ[a, c]) for a in range(n) for c in range(a + 1)], "Jtr": Jtr.tolist(), "eigenvalues_kept": g["eigenvalues_kept"]}
+            measured[case] = {"oracle_JtJ_scaled": float("%.3g" % dev[0]), "oracle_Jtr_rel": float("%.3g" % dev[1]), "kept_eigenvalues_near_cut": [float("%.3g" % x) for x in near]}
+            dump(os.path.join(HERE, "ref_marg_old_factor_" + case[5:] + ".json.gz"), fx)
+            continue
+        lin = O.ba_linearize(w.copy())
+        ids = [int(x) for x in lin["ids"]]
+        H, g, cost = window_normal_equations(w, ids)
+        n = len(ids)
+        Hd = np.array([[float(H[a, c]) for c in range(n)] for a in range(n)])
+        gd = np.array([float(g[a]) for a in range(n)])
+        hs = np.sqrt(np.outer(np.abs(np.diag(Hd)), np.abs(np.diag(Hd)))) + 1e-300
+        dev = (abs(lin["cost"] - float(cost)) / float(cost), float(np.abs((lin["H"] - Hd) / hs).max()), float(np.abs(lin["g"] - gd).max() / np.abs(gd).max()))
+        print("%s: %d columns (%d eliminated), %d visual / %d IMU / %d wheel factors, prior %d; oracle vs 60 digits: cost rel %.2e, H scaled %.2e, g rel %.2e  (%.0f s)"
+              % (case, n, lin["n_e"], w["n_visual"], w["n_imu"], w["n_wheel"], w["prior_n"], dev[0], dev[1], dev[2], time.time() - t0), flush=True)
+        fx = {"about": "normal equations of a window of tests/factor_hard_cases.py from the reference's formulas at 60 digits (tests/golden/make_ref_golden.py factor_hard); layout as ref_window_wheel",
+              "window": {k: (to_list(v) if isinstance(v, np.ndarray) else v) for k, v in dict(w).items()},
+              "ids": ids, "n_f": int(lin["n_f"]), "n_e": int(lin["n_e"]), "H_lower": [float(Hd[a, c]) for a in range(n) for c in range(a + 1)], "g": gd.tolist(), "cost": float(cost),
+              "cost_30_digits": mp.nstr(cost, 30)}
+        measured[case] = {"oracle_cost_rel": float("%.3g" % dev[0]), "oracle_H_scaled": float("%.3g" % dev[1]), "oracle_g_rel": float("%.3g" % dev[2])}
+        if kind == "single":
+            fx["factor"] = factor_own_columns(w, ids, FH.SINGLE_FAMILY[case])
+            worst = max(abs(lin["g"][c["column"]] - c["g"]) / c["abs_sum"] for c in fx["factor"]["own_columns"])
+            measured[case]["oracle_g_own_columns_rel_abs_sum"] = float("%.3g" % worst)
+            print("   the factor's own columns of g (%d), oracle vs 60 digits relative to the sum of absolute terms: %.2e" % (len(fx["factor"]["own_columns"]), worst), flush=True)
+        if case == "turned":      # the same window in the world frame it was turned from: the cost is the same number
+            wu = FH.window_of("unturned", O)
+            lu = O.ba_linearize(wu.copy())
+            cu = window_normal_equations(wu, [int(x) for x in lu["ids"]])[2]
+            measured[case]["cost_vs_unturned_rel_60_digits"] = float("%.3g" % float(abs(cost - cu) / cu))
+            measured[case]["oracle_cost_vs_unturned_rel"] = float("%.3g" % (abs(lin["cost"] - lu["cost"]) / lu["cost"]))
+            print("   cost against the unturned window's: 60 digits %.2e (the turned inputs are rounded to doubles), oracle %.2e"
+                  % (measured[case]["cost_vs_unturned_rel_60_digits"], measured[case]["oracle_cost_vs_unturned_rel"]), flush=True)
+        dump(os.path.join(HERE, "ref_window_factor_" + case + ".json.gz"), fx)
+        if solved:
+            import make_ref_solve_golden as S
+            import gfwindow as gw
+            x, info = S.solve(w, ids, 8)
+            a = w.copy()
+            so = O.ba_solve(a, 8)
+            P, Pe = a["para_Pose"].reshape(-1, 7), x["para_Pose"].reshape(-1, 7)
+            dq = 2 * min(np.abs(P[:, 3:] - Pe[:, 3:]).max(), np.abs(P[:, 3:] + Pe[:, 3:]).max())
+            other = max(float(np.abs(np.asarray(a[k]) - np.asarray(x[k])).max()) for k in gw.STATE_KEYS if k != "para_Pose" and len(a[k]))
+            print("   solve at 60 digits: %d iterations, %d successful, termination %d (oracle %d, %d, %d); oracle vs 60 digits: position %.2e m, rotation %.2e rad, other blocks %.2e  (%.0f s)"
+                  % (info["iterations"], info["successful_steps"], info["termination"], so["iterations"], so["successful_steps"], so["termination"], np.abs(P[:, :3] - Pe[:, :3]).max(), dq, other,
+                     time.time() - t0), flush=True)
+            measured[case]["oracle_solve"] = {"position_m": float("%.3g" % np.abs(P[:, :3] - Pe[:, :3]).max()), "rotation_rad": float("%.3g" % dq), "other_blocks": float("%.3g" % other)}
+            dump(os.path.join(HERE, "ref_solve_factor_" + case + ".json.gz"),
+                 {"about": "state of the window tests/golden/ref_window_factor_%s.json.gz after the reference's solve (DENSE_SCHUR, DOGLEG, 8 iterations), every iterate at 60 digits "
+                           "(tests/golden/make_ref_solve_golden.py solve, run by make_ref_golden.py factor_hard)" % case,
+                  "window": "ref_window_factor_" + case, "state": {k: np.asarray(x[k]).reshape(-1).tolist() for k in gw.STATE_KEYS}, "summary": info})
+    m = FH.committed().get("measured", {})       # figures of cases not regenerated in this call stay
+    m.setdefault("oracle_vs_60_digits", {}).update(measured)
+    FH.write(FH.census_document(O, measured=m))
+
+
 if __name__ == "__main__":
-    if sys.argv[1:2] == ["gnss_models"]:
+    if sys.argv[1:2] == ["factor_hard"]:
+        main_factor_hard(sys.argv[2:])
+    elif sys.argv[1:2] == ["gnss_models"]:
         main_gnss_models()
     elif sys.argv[1:2] == ["gnss_hard"]:
         main_gnss_hard(sys.argv[2:])
