@@ -6,7 +6,7 @@
 // (pyramids, Scharr, LK forward/reverse, mask rasterisation, Shi-Tomasi, candidate sort and min-distance selection, depth sampling) runs in the kernels of
 // gf_lk_kernels.hpp / gf_detect_kernels.hpp.  This file owns the handle, its tables and streams, and the order of a frame.  track_core runs these stages:
 //   publish        the call's list and frame table where the first kernels read them, over the bus or by copy
-//   launch_front   conversion, equalisation, pyramid; the frames_unaligned count
+//   launch_front   conversion, equalisation, pyramid; the frames_unaligned count; then the depth registration of the sequences that have one (launch_depth_reg)
 //   run_lk         stage_points per sequence, tables down, one or two LK launches, tables up; the host waits
 //   redo_fallback  LK from scratch for the predicted sequences with fewer than 10 forward successes
 //   book_after_lk  per sequence on the pool (after_lk): reduction by status, setMask, the corners wanted
@@ -36,6 +36,7 @@
 #include "gf_detect_kernels.hpp"
 #include "gf_lk_kernels.hpp"
 #include "gf_copy_list.hpp"
+#include "gf_depth_reg_stage.hpp"
 #include "gf_frame_ref.hpp"
 #include "gf_host_cpus.hpp"
 #include "gf_hip_own.hpp"
@@ -265,6 +266,16 @@ struct gf_tracker {
     DevBuf<uint8_t> d_size_of; PinBuf<uint8_t> h_size_of;
     DevBuf<uint8_t> d_size_sub; PinBuf<uint8_t> h_size_sub;
 
+    // A depth registration per sequence (gf_depth_reg.hpp; gf_tracker_set_seq_depth_reg), the eighth thing addressed by SEQUENCE.  Everything here is obtained by
+    // the first setter of the handle: dreg_on[seq] / dreg[seq], the registration as it was set; d_dreg, [B] registered frames of cfg.width x cfg.height counts, a
+    // sequence's frame written at its colour size in force, rows tight; dreg_stage, the z-buffer ([B] slots by list position) and the table of a call's jobs;
+    // ev_dreg around the two kernels of a call, read when the stream is drained.
+    std::vector<uint8_t> dreg_on; std::vector<gf_depth_reg> dreg;
+    DevBuf<uint16_t> d_dreg;
+    DepthRegStage dreg_stage;
+    Event ev_dreg[2];
+    long long dreg_launches = 0, dreg_frames = 0; double dreg_ms = 0;
+
     std::unique_ptr<HostPool> pool;
 };
 static_assert(gfsize::kPad == gf::kPad && gfsize::kWin == gf::kWin && gfsize::kMaxLevels == gf::kMaxLevels, "gf_seq_size.hpp restates the pyramid's constants");
@@ -388,6 +399,17 @@ static int check_list(gf_tracker* h, int count, const int* seq) {
         if (h->listed[seq[i]]) return set_err(GF_ERR_INVALID, "sequence %d is listed twice", seq[i]);
         h->listed[seq[i]] = 1;
     }
+    return GF_OK;
+}
+
+// The entry points that do not serve a depth registration (gf_tracker_set_seq_depth_reg; everything but the _refs forms): a call with depth that lists a
+// sequence which has one is refused before anything is copied, launched or changed.  seq: checked by check_list.
+static int refuse_registered(const gf_tracker* h, const char* who, int count, const int* seq, bool with_depth) {
+    if (!with_depth || h->dreg_on.empty()) return GF_OK;
+    for (int i = 0; i < count; i++)
+        if (h->dreg_on[seq[i]])
+            return set_err(GF_ERR_INVALID, "%s: sequence %d (list position %d) has a depth registration, which takes its raw depth frame on gf_tracker_track_some_device_refs / "
+                           "gf_tracker_track_batch_device_refs only; this entry point serves it without depth", who, seq[i], i);
     return GF_OK;
 }
 
@@ -725,6 +747,7 @@ struct Call {
     bool sized = false;                   // a listed sequence has a frame size that is not the handle's: the call goes through h->size_plan and the sized forms
     bool size_of_down = false;            // the bytes that name each position's size are still wanted on the device: with the first copy list that leaves
     const uint8_t* sub = nullptr;         // the compact per-size tables (SizeSub) where the front's launches read them: h_size_sub over the bus, or d_size_sub
+    int n_reg = 0;                        // listed sequences whose raw depth frame this call registers (publish fills their jobs, launch_depth_reg runs them)
     void lap(double& acc) { const auto n = std::chrono::steady_clock::now(); acc += std::chrono::duration<double, std::milli>(n - tp).count(); tp = n; }
     void add_refs() {
         if (refs_down) { ho.down(h->d_refs, h->h_refs, (size_t)2 * h->B); refs_down = false; }
@@ -744,6 +767,25 @@ static int publish(Call& c) {
     if (in.gray_refs) {
         for (int i = 0; i < c.N; i++) { h->h_refs.p[i] = in.gray_refs[i]; h->h_refs.p[h->B + i] = in.depth_refs ? in.depth_refs[i] : gf_frame_ref{nullptr, 0}; }
         if (in.depth_refs) c.kdepth = reinterpret_cast<const uint16_t*>(h->d_refs.p + h->B);   // what the _refs forms of LK and the selection read in the place of tight frames
+        // a depth registration per sequence (gf_depth_reg.hpp): the entry is the RAW frame; the table names the handle's registered frame in its place, and the
+        // job goes to launch_depth_reg.  A sequence without a depth camera is never registered (its entry is never sampled).
+        if (in.depth_refs && !h->dreg_on.empty()) {
+            const size_t slot = (size_t)h->cfg.width * h->cfg.height, zslot = gfdreg::zwords_of(h->cfg.width, h->cfg.height);
+            for (int i = 0; i < c.N; i++) {
+                const int q = c.seq[i];
+                if (!h->dreg_on[q]) continue;
+                if (!h->par[q].depth_cam || !in.depth_refs[i].data) { h->h_refs.p[h->B + i] = gf_frame_ref{nullptr, 0}; continue; }   // a raw frame is no frame of the colour size: nothing samples it
+                const gf_tracker_seq_cfg& par = h->par[q];
+                const double proj[4] = {par.fx, par.fy, par.cx, par.cy}, dist[4] = {par.k1, par.k2, par.p1, par.p2};
+                gfdreg::Job& j = h->dreg_stage.h_jobs.p[c.n_reg++];
+                j.src = static_cast<const uint8_t*>(in.depth_refs[i].data); j.src_pitch = in.depth_refs[i].pitch;
+                j.wd = h->dreg[q].width; j.hd = h->dreg[q].height; j.wc = seq_width(h, q); j.hc = seq_height(h, q);
+                j.dst = reinterpret_cast<uint8_t*>(h->d_dreg.p + (size_t)q * slot); j.dst_pitch = (size_t)j.wc * 2;
+                j.zoff = (size_t)i * zslot;
+                j.p = gfdreg::params_of(h->dreg[q], proj, dist);
+                h->h_refs.p[h->B + i] = gf_frame_ref{j.dst, j.dst_pitch};
+            }
+        }
     }
     const bool over_bus = h->copy_lists && h->h_cur.hd;
     if (!over_bus) HIPCHK(hipMemcpyAsync(h->d_cur.p, h->h_cur.p, (size_t)c.N * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -905,6 +947,15 @@ static int launch_front(Call& c) {
         if (refs_narrow < 0) { refs_narrow = 0; for (int i = 0; i < N; i++) refs_narrow += gfref::unaligned(reinterpret_cast<uintptr_t>(c.in.gray_refs[i].data), c.in.gray_refs[i].pitch, refs_widest) ? 1 : 0; }
         h->stats.frames_unaligned += refs_narrow;
     }
+    return GF_OK;
+}
+
+// The raw depth frames of the call's registered sequences to their colour cameras (gf_depth_reg.hip): two launches for all of them, behind the pyramid and ahead
+// of LK, the first kernel that samples depth.
+static int launch_depth_reg(Call& c) {
+    gf_tracker* h = c.h;
+    if (int rc = depth_reg_launch(h->dreg_stage, c.n_reg, h->stream, h->ev_dreg[0], h->ev_dreg[1])) return rc;
+    h->dreg_launches += 2; h->dreg_frames += c.n_reg;
     return GF_OK;
 }
 
@@ -1152,11 +1203,13 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
     for (int i = 0; i < count; i++) h->h_cur.p[i] = 2 * seq[i] + begin_frame(h->seq[seq[i]], t[i]);   // the new frame goes to the sequence's other pyramid
     if (int rc = publish(c)) return rc;
     if (int rc = launch_front(c)) return rc;
+    if (c.n_reg) if (int rc = launch_depth_reg(c)) return rc;
     if (int rc = run_lk(c)) return rc;
     if (int rc = redo_fallback(c)) return rc;
     book_after_lk(c);
     if (int rc = run_detect(c)) return rc;
     h->box_pending = false;   // the stream is drained: a box setter's staging has been read
+    if (c.n_reg) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, h->ev_dreg[0], h->ev_dreg[1])); h->dreg_ms += ms; }
     if (h->profiling) if (int rc = read_profile(c)) return rc;
     if (c.any_want) if (int rc = check_candidates(c)) return rc;
     if (int rc = book_after_detect(c, out, cap_out, n_out)) return rc;
@@ -1269,6 +1322,7 @@ int gf_tracker_track_some_device(gf_tracker* h, int count, const int* seq, const
     if (int rc = gf::check_list(h, count, seq)) return rc;
     if (count == 0) return GF_OK;
     if (!t || !d_gray || !out || !n_out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (int rc = gf::refuse_registered(h, "gf_tracker_track_some_device", count, seq, d_depth != nullptr)) return rc;
     return gf::track_core(h, count, seq, t, gf::FrameInput::device((const uint8_t*)d_gray, (const uint16_t*)d_depth), out, cap, n_out);
 }
 
@@ -1289,9 +1343,11 @@ static int check_refs(const gf_tracker* h, int count, const int* seq, const gf_f
     for (int i = 0; i < count; i++) {
         if (own_rows) row_bytes = gfseqfmt::row_bytes(h->cfg.width, h->fmt[seq[i]].pixel_format);
         if (h->size_any && own_size) row_bytes = own_rows ? gfseqfmt::row_bytes(seq_width(h, seq[i]), h->fmt[seq[i]].pixel_format) : (size_t)seq_width(h, seq[i]) * own_size;   // a row of the sequence's own width (gf_tracker_set_seq_size)
-        const gfref::Verdict v = gfref::check(refs[i], row_bytes, u16, u16 && !h->par[seq[i]].depth_cam);
+        const bool raw_depth = u16 && !h->dreg_on.empty() && h->dreg_on[seq[i]];   // the raw frame of the sequence's depth camera (gf_tracker_set_seq_depth_reg)
+        const size_t need = raw_depth ? (size_t)h->dreg[seq[i]].width * 2 : row_bytes;
+        const gfref::Verdict v = gfref::check(refs[i], need, u16, u16 && !h->par[seq[i]].depth_cam);
         if (v != gfref::kOk)
-            return set_err(GF_ERR_INVALID, "%s frame at list position %d (sequence %d): %s (data %p, pitch %zu bytes, a row is %zu bytes)", what, i, seq[i], gfref::verdict_text(v), refs[i].data, refs[i].pitch, row_bytes);
+            return set_err(GF_ERR_INVALID, "%s frame at list position %d (sequence %d): %s (data %p, pitch %zu bytes, a row is %zu bytes)", raw_depth ? "raw depth" : what, i, seq[i], gfref::verdict_text(v), refs[i].data, refs[i].pitch, need);
     }
     return GF_OK;
 }
@@ -1321,6 +1377,7 @@ int gf_tracker_track_some(gf_tracker* h, int count, const int* seq, const double
     if (int rc = gf::check_list(h, count, seq)) return rc;
     if (count == 0) return GF_OK;
     if (!t || !gray || !out || !n_out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (int rc = gf::refuse_registered(h, "gf_tracker_track_some", count, seq, depth != nullptr)) return rc;
     bool have_depth = false, sized = false;
     if (int rc = gf::check_host_frames(h, count, seq, gray, stride, depth, dstride, &have_depth, &sized)) return rc;   // refuse before the first copy
     const size_t row = (size_t)h->cfg.width * h->ch;   // bytes of a row of the handle's pixel format
@@ -1340,6 +1397,7 @@ int gf_tracker_prefetch_some(gf_tracker* h, int count, const int* seq, const uin
     if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
     if (int rc = gf::check_list(h, count, seq)) return rc;
     if (count > 0 && !gray) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (int rc = gf::refuse_registered(h, "gf_tracker_prefetch_some", count, seq, depth != nullptr)) return rc;
     bool have_depth = false, sized = false;
     if (int rc = gf::check_host_frames(h, count, seq, gray, stride, depth, dstride, &have_depth, &sized)) return rc;
     const size_t row = (size_t)h->cfg.width * h->ch;   // bytes of a row of the handle's pixel format
@@ -1383,17 +1441,20 @@ int gf_tracker_track_prefetched(gf_tracker* h, const double* t, gf_feature_obs* 
 int gf_tracker_track_batch_device(gf_tracker* h, const double* t, const void* d_gray, const void* d_depth, gf_feature_obs* out, int cap,
                                   int* n_out) {
     if (!h || !t || !d_gray || !out || !n_out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (int rc = gf::refuse_registered(h, "gf_tracker_track_batch_device", h->B, h->ident.data(), d_depth != nullptr)) return rc;
     return gf_tracker_track_some_device(h, h->B, h->ident.data(), t, d_gray, d_depth, out, cap, n_out);
 }
 
 int gf_tracker_track_batch(gf_tracker* h, const double* t, const uint8_t* const* gray, int stride, const uint16_t* const* depth, int dstride,
                            gf_feature_obs* out, int cap, int* n_out) {
     if (!h || !t || !gray || !out || !n_out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (int rc = gf::refuse_registered(h, "gf_tracker_track_batch", h->B, h->ident.data(), depth != nullptr)) return rc;
     return gf_tracker_track_some(h, h->B, h->ident.data(), t, gray, stride, depth, dstride, out, cap, n_out);
 }
 
 int gf_tracker_prefetch_batch(gf_tracker* h, const uint8_t* const* gray, int stride, const uint16_t* const* depth, int dstride) {
     if (!h || !gray) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (int rc = gf::refuse_registered(h, "gf_tracker_prefetch_batch", h->B, h->ident.data(), depth != nullptr)) return rc;
     return gf_tracker_prefetch_some(h, h->B, h->ident.data(), gray, stride, depth, dstride);
 }
 
@@ -1411,6 +1472,7 @@ int gf_tracker_track(gf_tracker* h, int seq, double t, const uint8_t* gray, int 
     if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
     const uint8_t* g[1] = {gray};
     const uint16_t* d[1] = {depth};
+    if (seq >= 0 && seq < h->B) if (int rc = gf::refuse_registered(h, "gf_tracker_track", 1, &seq, depth != nullptr)) return rc;
     return gf_tracker_track_some(h, 1, &seq, &t, g, stride, depth ? d : nullptr, dstride, out, cap, n_out);
 }
 
@@ -1627,6 +1689,8 @@ int gf_tracker_set_seq_camera(gf_tracker* h, int seq, const gf_camera_model* m) 
     gfcam::Camera checked;
     char msg[320];
     if (!gfcam::prepare(*m, checked, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "sequence %d: %s", seq, msg);
+    if (m->model != GF_CAMERA_PINHOLE && !h->dreg_on.empty() && h->dreg_on[seq])
+        return gf::set_err(GF_ERR_INVALID, "sequence %d has a depth registration (gf_tracker_set_seq_depth_reg), which projects through a GF_CAMERA_PINHOLE only: clear it before a %s camera is set", seq, gfcam::model_name(m->model));
     if (m->model == GF_CAMERA_PINHOLE) {   // the eight camera fields of the sequence's parameters, through their own setter
         gf_tracker_seq_cfg want = h->par[seq];
         want.fx = m->proj[0]; want.fy = m->proj[1]; want.cx = m->proj[2]; want.cy = m->proj[3];
@@ -1748,6 +1812,55 @@ int gf_tracker_get_seq_size(gf_tracker* h, int seq, int* width, int* height) {
     if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
     const int r = h->sizes.row_of[seq];
     *width = h->sizes.w[r]; *height = h->sizes.h[r];
+    return GF_OK;
+}
+
+// ---- a depth registration per sequence (gf_depth_reg.hpp; the driver's aligned_depth_to_color, config/realsense/m2dgrp.yaml:23).  Between frames, with the stream drained.
+namespace gf {
+static int seq_depth_reg_ready(gf_tracker* h) {   // the first setter of a handle: the registered frames and the z-buffer at the handle's capacity, the call's table, the two events
+    if (h->d_dreg.p) return GF_OK;
+    const size_t B = (size_t)h->B;
+    DevBuf<uint16_t> frames; DepthRegStage stage; Event ev[2];
+    HIPCHK(frames.alloc(B * h->cfg.width * h->cfg.height));
+    if (int rc = depth_reg_fit(stage, B, B * gfdreg::zwords_of(h->cfg.width, h->cfg.height))) return rc;
+    for (auto& e : ev) HIPCHK(hipEventCreate(&e.e));
+    h->dreg_on.assign(B, 0); h->dreg.assign(B, gf_depth_reg{});
+    h->d_dreg = std::move(frames);
+    h->dreg_stage.z = std::move(stage.z); h->dreg_stage.d_jobs = std::move(stage.d_jobs); h->dreg_stage.h_jobs = std::move(stage.h_jobs); h->dreg_stage.primed = false;
+    for (int i = 0; i < 2; i++) std::swap(h->ev_dreg[i].e, ev[i].e);
+    return GF_OK;
+}
+}  // namespace gf
+
+int gf_tracker_set_seq_depth_reg(gf_tracker* h, int seq, const gf_depth_reg* reg) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    char msg[320];
+    if (reg && !gfdreg::check(*reg, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "sequence %d: %s", seq, msg);
+    if (!reg && h->dreg_on.empty()) return GF_OK;   // nothing to take back, whatever the sequence's state: the handle stays one that never set any
+    if (h->seq[seq].started) return gf::set_err(GF_ERR_INVALID, "sequence %d has taken a frame: its depth registration is fixed until gf_tracker_reset_seq", seq);
+    if (gf::seq_is_staged(h, seq)) return gf::set_err(GF_ERR_INVALID, "sequence %d is listed by a staged frame: gf_tracker_track_prefetched has to consume it first (depth registration)", seq);
+    if (reg && !h->cam_on.empty() && h->cam_on[seq])
+        return gf::set_err(GF_ERR_INVALID, "sequence %d has a %s camera (gf_tracker_set_seq_camera); depth is registered to a GF_CAMERA_PINHOLE only: set one first", seq, gfcam::model_name(h->cam_model[seq].model));
+    if (int rc = gf::seq_depth_reg_ready(h)) return rc;
+    h->dreg_on[seq] = reg ? 1 : 0;
+    h->dreg[seq] = reg ? *reg : gf_depth_reg{};
+    return GF_OK;
+}
+
+int gf_tracker_get_seq_depth_reg(gf_tracker* h, int seq, gf_depth_reg* out, int* has) {
+    if (!h || !has) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    *has = !h->dreg_on.empty() && h->dreg_on[seq] ? 1 : 0;
+    if (*has && out) *out = h->dreg[seq];
+    return GF_OK;
+}
+
+int gf_tracker_get_depth_reg_stats(gf_tracker* h, long long* launches, long long* frames, double* kernel_ms) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (launches) *launches = h->dreg_launches;
+    if (frames) *frames = h->dreg_frames;
+    if (kernel_ms) *kernel_ms = h->dreg_ms;
     return GF_OK;
 }
 
@@ -1875,7 +1988,7 @@ int gf_tracker_get_state(gf_tracker* h, int seq, int* ids, int* track_cnt, float
 
 int gf_tracker_set_profiling(gf_tracker* h, int enable) { if (!h) return gf::set_err(GF_ERR_INVALID, "null handle"); h->profiling = enable != 0; return GF_OK; }
 int gf_tracker_get_stats(gf_tracker* h, gf_tracker_stats* out) { if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument"); *out = h->stats; return GF_OK; }
-int gf_tracker_reset_stats(gf_tracker* h) { if (!h) return gf::set_err(GF_ERR_INVALID, "null handle"); h->stats = gf_tracker_stats{}; return GF_OK; }
+int gf_tracker_reset_stats(gf_tracker* h) { if (!h) return gf::set_err(GF_ERR_INVALID, "null handle"); h->stats = gf_tracker_stats{}; h->dreg_launches = h->dreg_frames = 0; h->dreg_ms = 0; return GF_OK; }
 
 // ------------------------------------------------------------------ building blocks for parity tests
 static int tmp_handle(int width, int height, int max_cnt, int min_dist, std::unique_ptr<gf_tracker>& own) {

@@ -194,6 +194,55 @@ def camera_project(cams, xyz):
     return [uv[first[b]:first[b + 1]] for b in range(len(cams))]
 
 
+class DepthReg(C.Structure):
+    """gf_depth_reg: a raw depth stream and its pose relative to the colour camera -- width x height counts of `scale` metres through the pinhole fx fy cx cy,
+    P_colour = R P_depth + T (R row-major, T in metres)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("scale", C.c_double), ("R", C.c_double * 9), ("T", C.c_double * 3)]
+
+    @classmethod
+    def make(cls, width, height, fx, fy, cx, cy, scale=0.001, R=(1, 0, 0, 0, 1, 0, 0, 0, 1), T=(0, 0, 0)):
+        r = cls()
+        r.width, r.height = int(width), int(height)
+        r.fx, r.fy, r.cx, r.cy, r.scale = float(fx), float(fy), float(cx), float(cy), float(scale)
+        r.R[:] = [float(v) for v in np.asarray(R, np.float64).reshape(-1)]
+        r.T[:] = [float(v) for v in T]
+        return r
+
+    def as_dict(self):
+        return {"width": self.width, "height": self.height, "fx": self.fx, "fy": self.fy, "cx": self.cx, "cy": self.cy, "scale": self.scale, "R": list(self.R), "T": list(self.T)}
+
+
+assert C.sizeof(DepthReg) == 144
+
+
+def _depth_reg_tables(regs, colours, colour_sizes):
+    n = len(regs)
+    assert len(colours) == n and len(colour_sizes) == n
+    wh = np.ascontiguousarray(colour_sizes, np.int32).reshape(n, 2)
+    return (DepthReg * max(n, 1))(*regs), (CameraModel * max(n, 1))(*colours), wh
+
+
+def depth_register_device(src_refs, regs, colours, colour_sizes, dst_refs, stream=0):
+    """gf_depth_register_batch_device: entry b's raw depth frame src_refs[b] = (device address, pitch) registered by regs[b] (DepthReg) to the PINHOLE colours[b]
+    (CameraModel) of colour_sizes[b] = (width, height) into dst_refs[b], which is written; two launches on `stream` whatever the batch, returns when they have run"""
+    r, c, wh = _depth_reg_tables(regs, colours, colour_sizes)
+    assert len(src_refs) == len(regs) and len(dst_refs) == len(regs)
+    _chk(lib().gf_depth_register_batch_device(frame_refs(src_refs), r, c, _p(wh, C.c_int), frame_refs(dst_refs), len(regs), C.c_void_p(stream) if stream else None))
+
+
+def depth_register(depths, regs, colours, colour_sizes):
+    """gf_depth_register_batch: depths[b] ([height, width] u16, rows may be padded) registered by regs[b] to the PINHOLE colours[b] of colour_sizes[b] =
+    (width, height), staged through device memory -> list of [height, width] u16 frames of the colour sizes"""
+    r, c, wh = _depth_reg_tables(regs, colours, colour_sizes)
+    src = [d if (d.dtype == np.uint16 and d.ndim == 2 and d.strides[1] == 2 and d.strides[0] >= 2 * d.shape[1]) else np.ascontiguousarray(d, np.uint16) for d in depths]
+    assert all(s.shape == (g.height, g.width) for s, g in zip(src, regs)), "a depth frame is not [height, width] of its registration"
+    out = [np.zeros((int(h), int(w)), np.uint16) for w, h in wh]
+    _chk(lib().gf_depth_register_batch(frame_refs([(s.ctypes.data, s.strides[0]) for s in src]), r, c, _p(wh, C.c_int),
+                                       frame_refs([(o.ctypes.data, o.strides[0]) for o in out]), len(regs)))
+    return out
+
+
 def camera_from_yaml(calib_file):
     """gf_camera_from_yaml: a camodocal calibration file (PINHOLE, MEI, KANNALA_BRANDT) -> CameraModel"""
     m = CameraModel()
@@ -217,7 +266,8 @@ EXPORTS = ["gf_last_error", "gf_device_count", "gf_set_device", "gf_tracker_crea
            "gf_tracker_set_seq_format", "gf_tracker_get_seq_format", "gf_cvt_gray_mixed", "gf_cvt_gray_mixed_device",
            "gf_tracker_set_seq_camera", "gf_tracker_get_seq_camera", "gf_camera_lift_batch", "gf_camera_lift_batch_device", "gf_camera_project_batch",
            "gf_camera_from_yaml", "gf_estimator_cfg_from_yaml_camera", "gf_estimator_set_camera",
-           "gf_tracker_set_seq_size", "gf_tracker_get_seq_size"]
+           "gf_tracker_set_seq_size", "gf_tracker_get_seq_size",
+           "gf_tracker_set_seq_depth_reg", "gf_tracker_get_seq_depth_reg", "gf_tracker_get_depth_reg_stats", "gf_depth_register_batch", "gf_depth_register_batch_device"]
 MAX_SEQ_SIZES = 8   # GF_MAX_SEQ_SIZES
 
 
@@ -562,6 +612,25 @@ class FeatureTracker:
         m = CameraModel()
         _chk(lib().gf_tracker_get_seq_camera(self.h, seq, C.byref(m)))
         return m
+
+    def set_seq_depth_reg(self, seq, reg):
+        """gf_tracker_set_seq_depth_reg: sequence `seq` gets the depth registration `reg` (DepthReg; None clears it): on trackImageSomeDeviceRefs /
+        trackImageBatchDeviceRefs its depth ref is the RAW frame of the depth camera, registered to its colour camera on the device ahead of the depth samples;
+        every other frame-taking method refuses it with depth.  Refused (GfError) once the sequence has taken a frame, until reset_seq, while a prefetched frame
+        lists it, and while its camera is no PINHOLE."""
+        _chk(lib().gf_tracker_set_seq_depth_reg(self.h, int(seq), None if reg is None else C.byref(reg)))
+
+    def get_seq_depth_reg(self, seq):
+        """gf_tracker_get_seq_depth_reg: the DepthReg of sequence `seq`, None if it has none"""
+        r, has = DepthReg(), C.c_int(0)
+        _chk(lib().gf_tracker_get_seq_depth_reg(self.h, int(seq), C.byref(r), C.byref(has)))
+        return r if has.value else None
+
+    def depth_reg_stats(self):
+        """gf_tracker_get_depth_reg_stats: dict of launches (two per call that registered a frame), frames, kernel_ms (hipEvent time of the two kernels, summed)"""
+        n, f, ms = C.c_longlong(0), C.c_longlong(0), C.c_double(0)
+        _chk(lib().gf_tracker_get_depth_reg_stats(self.h, C.byref(n), C.byref(f), C.byref(ms)))
+        return {"launches": n.value, "frames": f.value, "kernel_ms": ms.value}
 
     def set_seq_format(self, seq, pixel_format=None, equalize=None, host_stride=0):
         """gf_tracker_set_seq_format: sequence `seq` takes frames of `pixel_format` (PIX_*) and is equalised or not, whatever the handle's cfg says; a field left

@@ -130,6 +130,21 @@ class FeatureTracker {
     }
 #endif
 
+    // The depth camera's raw stream registered to the colour camera on the device (gf_tracker_set_seq_depth_reg) in the place of the driver's
+    // aligned_depth_to_color (config/realsense/m2dgrp.yaml:23): with a registration set, the depth image of trackImage(double, const gf_frame_ref&, ...) is the
+    // RAW frame of the depth camera, reg.height rows of reg.width counts, and the host-image forms of trackImage refuse a depth image.  seq: this class holds one
+    // sequence, 0.  Before the first trackImage or after it, under the library's rules for the setter (refused once a frame was taken; the camera must be a PINHOLE).
+    void setDepthRegistration(int seq, const gf_depth_reg& reg) {
+        if (seq != 0) throw std::runtime_error("setDepthRegistration: a FeatureTracker holds one sequence, 0");
+        if (h_) check(gf_tracker_set_seq_depth_reg(h_, 0, &reg));
+        depth_reg_ = reg; has_depth_reg_ = true;
+    }
+    void clearDepthRegistration(int seq) {
+        if (seq != 0) throw std::runtime_error("clearDepthRegistration: a FeatureTracker holds one sequence, 0");
+        if (h_) check(gf_tracker_set_seq_depth_reg(h_, 0, nullptr));
+        has_depth_reg_ = false;
+    }
+
     // SHOW_TRACK (parameters.cpp:202; feature_tracker.cpp:304-305): on, every trackImage leaves the picture getTrackImage returns (gf_tracker_set_show_track).
     // Any time; the first frame after it went on already gives a complete picture.
     void setShowTrack(bool on) {
@@ -226,6 +241,7 @@ class FeatureTracker {
     int pixel_format_ = GF_PIX_MONO8;
     std::vector<uint8_t> roi_;   // a region of interest set before the handle exists (tight rows)
     std::vector<gf_box> boxes_;  // exclusion boxes set before the handle exists
+    gf_depth_reg depth_reg_{}; bool has_depth_reg_ = false;   // setDepthRegistration, kept for a handle that does not exist yet
     static void check(int rc) { if (rc != GF_OK) throw std::runtime_error(std::string("groundfusion_hip: ") + gf_last_error()); }
     void create(int w, int h) {
         gf_tracker_cfg c{};
@@ -239,6 +255,7 @@ class FeatureTracker {
         if (!roi_.empty()) { check(gf_tracker_set_roi(h_, 0, roi_.data(), col)); roi_.clear(); }
         if (!boxes_.empty()) { const std::vector<gf_box> b = std::move(boxes_); boxes_.clear(); setBoxes(b.data(), (int)b.size()); }
         if (show_track_) setShowTrack(true);
+        if (has_depth_reg_) check(gf_tracker_set_seq_depth_reg(h_, 0, &depth_reg_));
     }
     void refresh() {
         const int cap = (MAX_CNT + 3) & ~3;

@@ -365,6 +365,53 @@ int gf_camera_project_batch(const gf_camera_model* cams, int batch, const int* f
  * EquidistantCamera.cc:146-182): model_type (missing: PINHOLE), projection_parameters, distortion_parameters, mirror_parameters.xi.  A missing numeric key reads
  * as 0 like every cv::FileNode, so a missing focal parameter is refused by name; PINHOLE_FULL and SCARAMUZZA are refused by name. */
 int gf_camera_from_yaml(const char* calib_file, gf_camera_model* out);
+/* Depth registration: the raw frame of a depth camera brought to the colour camera on the device -- what the camera driver's `align` filter does on the host for
+ * /camera/aligned_depth_to_color/image_raw, the topic every shipped configuration subscribes to (config/realsense/m2dgrp.yaml:23), as a definition of this
+ * repository (csrc/gf_depth_reg.hpp; DESIGN.md section 4, "Depth registration").  width x height u16 counts of `scale` metres each, seen through the undistorted
+ * pinhole fx fy cx cy, are lifted, moved by P_colour = R P_depth + T (R row-major, T in metres) and projected through the colour PINHOLE with its distortion; each
+ * depth pixel covers the colour pixels whose centre lies in the half-open box between the images of its two corners (nothing if that box is wider or higher than
+ * 8 pixels), with floor(Pz / 0.001 + 0.5) millimetres along the colour camera's axis; a colour pixel takes the smallest value that reaches it, 0 (no
+ * measurement) if none does.  The identity registration (same size and intrinsics, R = I, T = 0, scale = 0.001) returns its input.  A count of 0, a point not in
+ * front of the colour camera, a coordinate that is not finite and a value outside 1 .. 65535 contribute nothing.
+ * Refused wherever a registration is taken (GF_ERR_INVALID, the message naming the field): width or height outside 8 .. 4096, a value that is not finite, fx, fy
+ * or scale <= 0, an R with an entry of R R^T - I beyond 1e-6 or with det R <= 0.  Out of scope: a colour camera other than GF_CAMERA_PINHOLE (refused by name), a
+ * distorted depth stream, depth in floating point. */
+typedef struct gf_depth_reg {
+    int32_t width, height;   /* of the raw depth frame */
+    double fx, fy, cx, cy;   /* the depth stream's pinhole (depth streams are rectified) */
+    double scale;            /* metres per count: 0.001 for millimetres, 0.0001 for a D405, 0.00025 for an L515 */
+    double R[9], T[3];       /* depth -> colour: P_colour = R P_depth + T, R row-major, T in metres */
+} gf_depth_reg;
+typedef char gf_depth_reg_is_144_bytes[sizeof(gf_depth_reg) == 144 ? 1 : -1];
+/* The registration as a building block, through the tracker's two kernels: entry b of `batch` has the raw frame d_src[b] (reg[b].height rows of reg[b].width
+ * counts), the registration reg[b], the colour camera colour[b] (GF_CAMERA_PINHOLE) of colour_wh[2 b] x colour_wh[2 b + 1] pixels (each 8 .. 4096), and the
+ * registered frame d_dst[b] of that size.  reg, colour and colour_wh are host tables; sources and destinations are device frames by pointer and pitch (both
+ * even, pitch >= 2 x the width; a refusal names the entry).  d_dst IS WRITTEN, as the dst of gf_tracker_track_image_some_device is: 2 x colour width bytes of each
+ * row, never a byte beyond them.  Entries may have different sizes; the call is two launches on `stream` (a hipStream_t, NULL = the null stream) whatever the
+ * batch, and returns when they have run.  The z-buffer is staging of the library that grows with the largest call and is left primed for the next one. */
+int gf_depth_register_batch_device(const gf_frame_ref* d_src, const gf_depth_reg* reg, const gf_camera_model* colour, const int* colour_wh,
+                                   const gf_frame_ref* d_dst, int batch, void* stream);
+/* The same on host frames by pointer and pitch (copies in, the two launches, copies out; synchronous): for tests and callers without device frames */
+int gf_depth_register_batch(const gf_frame_ref* src, const gf_depth_reg* reg, const gf_camera_model* colour, const int* colour_wh, const gf_frame_ref* dst, int batch);
+/* The registration of seq; reg == NULL clears it.  With one set, the `depth` entry of the sequence on gf_tracker_track_some_device_refs / _track_batch_device_refs
+ * is the RAW frame of the depth camera -- reg->height rows of reg->width counts, pointer and pitch even, pitch >= 2 x reg->width; a call that breaks this is
+ * refused naming the list position -- and the call registers it to the sequence's colour camera (the PINHOLE of its gf_tracker_seq_cfg, at its frame size in
+ * force) into a frame of the handle before anything samples depth: two launches per call for all such sequences, whatever their number and sizes.  LK and the
+ * corner selection then sample that frame, so the call's results are those of the same call on frames registered beforehand by gf_depth_register_batch_device.
+ * A sequence whose depth_cam is 0 may carry a registration; it is never run.  Every other entry point (host images, tight device lists, prefetch) refuses a
+ * call with depth that lists such a sequence (GF_ERR_INVALID, the message naming the entry point and the sequence, nothing changed): host images would put the
+ * raw frame on the bus.  Without depth, and for lists without such a sequence, they behave as before.
+ * A setting like gf_tracker_set_seq_size: refused once the sequence has taken a frame (until gf_tracker_reset_seq, which keeps it), while a frame staged by
+ * gf_tracker_prefetch_* lists it, and while the sequence's camera is not GF_CAMERA_PINHOLE (gf_tracker_set_seq_camera; that setter in turn refuses another model
+ * while a registration is set).  The first setter of a handle allocates the registered frames and the z-buffer at the handle's capacity (cfg.width x cfg.height
+ * per sequence) and the call's table; GF_ERR_HIP and nothing changed if that fails.  A handle on which it is never called allocates, copies and launches
+ * exactly what it did without it. */
+int gf_tracker_set_seq_depth_reg(gf_tracker* h, int seq, const gf_depth_reg* reg);
+/* *has = whether seq has a registration; if so and out != NULL, the registration as it was set */
+int gf_tracker_get_seq_depth_reg(gf_tracker* h, int seq, gf_depth_reg* out, int* has);
+/* The registration's own counters (gf_tracker_stats keeps its layout), each may be NULL: kernel launches (two per tracker call that registered a frame), frames
+ * registered, and the hipEvent time of the two kernels, summed.  gf_tracker_reset_stats zeroes them. */
+int gf_tracker_get_depth_reg_stats(gf_tracker* h, long long* launches, long long* frames, double* kernel_ms);
 /* The track image: SHOW_TRACK and FeatureTracker::getTrackImage() (feature_tracker.cpp:849-905 drawTrack, :1047; what the node publishes as image_track) -- the
  * MONO8 frame trackImage tracked on (after the handle's colour / raw conversion and equalisation) as height x width x 3 bytes in the reference's channel order
  * (labelled bgr8 there), a dot per feature coloured (255 (1 - len), 0, 255 len) by len = min(1, track_cnt / 20), and a green arrow from each feature that LK
