@@ -1,4 +1,4 @@
-// gf_camera.hip — camodocal's PINHOLE, MEI and KANNALA_BRANDT cameras behind the C-ABI: liftProjective on batches of points through camera_lift_kernel
+// gf_camera.hip — camodocal's PINHOLE, MEI, KANNALA_BRANDT, PINHOLE_FULL and SCARAMUZZA cameras behind the C-ABI (the last two through the _ex calls alone): liftProjective on batches of points through camera_lift_kernel
 // (gf_camera_kernels.hpp; undistortedPts, feature_tracker.cpp:797-808) and spaceToPlane on the host (setPrediction, :1006-1027).  The formulas and what a setter
 // refuses: gf_camera_models.hpp.  Used by the tracker (gf_tracker_set_seq_camera) and exported as building blocks.
 #include <hip/hip_runtime.h>
@@ -20,7 +20,8 @@ int camera_lift_launch(const gfcam::LiftArgs& A, int max_n, hipStream_t stream) 
 }
 
 // cams / first of the batch calls: every camera checked into `out`, the offsets from 0 and not decreasing; *max_n: the longest entry
-static int camera_batch_check(const char* who, const gf_camera_model* cams, int batch, const int* first, std::vector<gfcam::Camera>& out, int* max_n) {
+template <class Model>   // gf_camera_model, which holds models 0-2, or gf_camera_model_ex
+static int camera_batch_check(const char* who, const Model* cams, int batch, const int* first, std::vector<gfcam::Camera>& out, int* max_n) {
     if (!cams || !first) return set_err(GF_ERR_INVALID, "%s: null argument", who);
     if (batch < 1) return set_err(GF_ERR_INVALID, "%s: batch %d (must be >= 1)", who, batch);
     if (first[0] != 0) return set_err(GF_ERR_INVALID, "%s: first[0] is %d, not 0", who, first[0]);
@@ -37,9 +38,8 @@ static int camera_batch_check(const char* who, const gf_camera_model* cams, int 
 
 }  // namespace gf
 
-extern "C" {
-
-int gf_camera_lift_batch_device(const gf_camera_model* cams, int batch, const int* first, const float* d_uv, double* d_rays, float* d_un, void* stream) {
+template <class Model>
+static int camera_lift_batch_device(const Model* cams, int batch, const int* first, const float* d_uv, double* d_rays, float* d_un, void* stream) {
     std::vector<gfcam::Camera> prepared;
     int max_n = 0;
     if (int rc = gf::camera_batch_check("camera_lift", cams, batch, first, prepared, &max_n)) return rc;
@@ -61,7 +61,8 @@ int gf_camera_lift_batch_device(const gf_camera_model* cams, int batch, const in
     return GF_OK;
 }
 
-int gf_camera_lift_batch(const gf_camera_model* cams, int batch, const int* first, const float* uv, double* rays, float* un) {
+template <class Model>
+static int camera_lift_batch(const Model* cams, int batch, const int* first, const float* uv, double* rays, float* un) {
     std::vector<gfcam::Camera> prepared;
     int max_n = 0;
     if (int rc = gf::camera_batch_check("camera_lift", cams, batch, first, prepared, &max_n)) return rc;
@@ -73,13 +74,14 @@ int gf_camera_lift_batch(const gf_camera_model* cams, int batch, const int* firs
     HIPCHK(d_uv.fit(2 * n)); HIPCHK(d_un.fit(2 * n));
     if (rays) HIPCHK(d_rays.fit(3 * n));
     HIPCHK(hipMemcpy(d_uv.p, uv, 2 * n * sizeof(float), hipMemcpyHostToDevice));
-    if (int rc = gf_camera_lift_batch_device(cams, batch, first, d_uv.p, rays ? d_rays.p : nullptr, d_un.p, nullptr)) return rc;
+    if (int rc = camera_lift_batch_device(cams, batch, first, d_uv.p, rays ? d_rays.p : nullptr, d_un.p, nullptr)) return rc;
     HIPCHK(hipMemcpy(un, d_un.p, 2 * n * sizeof(float), hipMemcpyDeviceToHost));
     if (rays) HIPCHK(hipMemcpy(rays, d_rays.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
     return GF_OK;
 }
 
-int gf_camera_project_batch(const gf_camera_model* cams, int batch, const int* first, const double* xyz, double* uv) {
+template <class Model>
+static int camera_project_batch(const Model* cams, int batch, const int* first, const double* xyz, double* uv) {
     std::vector<gfcam::Camera> prepared;
     int max_n = 0;
     if (int rc = gf::camera_batch_check("camera_project", cams, batch, first, prepared, &max_n)) return rc;
@@ -88,6 +90,27 @@ int gf_camera_project_batch(const gf_camera_model* cams, int batch, const int* f
     for (int b = 0; b < batch; b++)
         for (int i = first[b]; i < first[b + 1]; i++) gfcam::space_to_plane(prepared[b], xyz + 3 * (size_t)i, uv[2 * (size_t)i], uv[2 * (size_t)i + 1]);
     return GF_OK;
+}
+
+extern "C" {
+
+int gf_camera_lift_batch_device(const gf_camera_model* cams, int batch, const int* first, const float* d_uv, double* d_rays, float* d_un, void* stream) {
+    return camera_lift_batch_device(cams, batch, first, d_uv, d_rays, d_un, stream);
+}
+int gf_camera_lift_batch_device_ex(const gf_camera_model_ex* cams, int batch, const int* first, const float* d_uv, double* d_rays, float* d_un, void* stream) {
+    return camera_lift_batch_device(cams, batch, first, d_uv, d_rays, d_un, stream);
+}
+int gf_camera_lift_batch(const gf_camera_model* cams, int batch, const int* first, const float* uv, double* rays, float* un) {
+    return camera_lift_batch(cams, batch, first, uv, rays, un);
+}
+int gf_camera_lift_batch_ex(const gf_camera_model_ex* cams, int batch, const int* first, const float* uv, double* rays, float* un) {
+    return camera_lift_batch(cams, batch, first, uv, rays, un);
+}
+int gf_camera_project_batch(const gf_camera_model* cams, int batch, const int* first, const double* xyz, double* uv) {
+    return camera_project_batch(cams, batch, first, xyz, uv);
+}
+int gf_camera_project_batch_ex(const gf_camera_model_ex* cams, int batch, const int* first, const double* xyz, double* uv) {
+    return camera_project_batch(cams, batch, first, xyz, uv);
 }
 
 }  // extern "C"

@@ -1,8 +1,8 @@
-// gf_camera_kernels.hpp — liftProjective of camodocal's three camera models on the device (undistortedPts, feature_tracker.cpp:797-808): the formulas are
+// gf_camera_kernels.hpp — liftProjective of camodocal's five camera models on the device (undistortedPts, feature_tracker.cpp:797-808): the formulas are
 // gf_camera_models.hpp, one source with the host.  One thread per point.  A block of one wavefront takes a (list entry, set, chunk of 64 points) triple, so the
 // camera and the branch on its model are wavefront-uniform: the entry's camera is read with scalar loads through an index every lane shares, as cvt_mixed_kernel
-// reads its frame entry, and the turning table of a Kannala-Brandt camera is walked in scalar registers.  No LDS, no scratch ("Camera
-// models", has the register counts).
+// reads its frame entry, and the turning table of a Kannala-Brandt camera, the eight coefficients of a PINHOLE_FULL one and the 11 doubles of a SCARAMUZZA
+// one stay in scalar registers.  No LDS, no scratch ("Camera models", has the register counts).
 #pragma once
 #include <hip/hip_runtime.h>
 

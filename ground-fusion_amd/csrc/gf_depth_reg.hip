@@ -30,8 +30,10 @@ int depth_reg_fit(DepthRegStage& s, size_t jobs, size_t zwords) {
 int depth_reg_launch(DepthRegStage& s, int n, hipStream_t stream, hipEvent_t before, hipEvent_t after) {
     if (n < 1) return GF_OK;
     size_t scatter_items = 0, finish_items = 0;
+    bool full = false;   // an entry with a PINHOLE_FULL colour camera: the scatter kernel's other instance, still one launch
     for (int i = 0; i < n; i++) {
         const gfdreg::Job& j = s.h_jobs.p[i];
+        full |= j.p.model == GF_CAMERA_PINHOLE_FULL;
         scatter_items = std::max(scatter_items, (size_t)j.wd * j.hd);
         finish_items = std::max(finish_items, gfdreg::zwords_of(j.wc, j.hc) / 8);
         if (j.zoff + gfdreg::zwords_of(j.wc, j.hc) > s.z.n || (j.zoff & 7)) return set_err(GF_ERR_INVALID, "depth_register: entry %d leaves the z-buffer", i);
@@ -40,7 +42,8 @@ int depth_reg_launch(DepthRegStage& s, int n, hipStream_t stream, hipEvent_t bef
     s.primed = false;
     HIPCHK(hipMemcpyAsync(s.d_jobs.p, s.h_jobs.p, (size_t)n * sizeof(gfdreg::Job), hipMemcpyHostToDevice, stream));
     if (before) HIPCHK(hipEventRecord(before, stream));
-    gfdreg::depth_scatter_kernel<<<gfdreg::reg_grid(scatter_items, n), gfdreg::kThreads, 0, stream>>>(s.d_jobs.p, s.z.p, n);
+    if (full) gfdreg::depth_scatter_kernel<true><<<gfdreg::reg_grid(scatter_items, n), gfdreg::kThreads, 0, stream>>>(s.d_jobs.p, s.z.p, n);
+    else gfdreg::depth_scatter_kernel<false><<<gfdreg::reg_grid(scatter_items, n), gfdreg::kThreads, 0, stream>>>(s.d_jobs.p, s.z.p, n);
     HIPCHK(hipGetLastError());
     gfdreg::depth_finish_kernel<<<gfdreg::reg_grid(finish_items, n), gfdreg::kThreads, 0, stream>>>(s.d_jobs.p, s.z.p, n);
     HIPCHK(hipGetLastError());
@@ -49,8 +52,15 @@ int depth_reg_launch(DepthRegStage& s, int n, hipStream_t stream, hipEvent_t bef
     return GF_OK;
 }
 
-// what the two batch calls refuse before anything is copied or launched; params: the 25 doubles of every entry
-static int depth_reg_batch_check(const char* who, const gf_frame_ref* src, const gf_depth_reg* reg, const gf_camera_model* colour, const int* colour_wh, const gf_frame_ref* dst, int batch,
+// the colour camera of an entry as either struct carries it; gf_camera_model holds no PINHOLE_FULL
+static const double* full_tail(const gf_camera_model&) { return nullptr; }
+static const double* full_tail(const gf_camera_model_ex& c) { return c.model == GF_CAMERA_PINHOLE_FULL ? c.dist + 4 : nullptr; }
+static const char* colour_models(const gf_camera_model&) { return "a GF_CAMERA_PINHOLE only"; }
+static const char* colour_models(const gf_camera_model_ex&) { return "a GF_CAMERA_PINHOLE or GF_CAMERA_PINHOLE_FULL only"; }
+
+// what the batch calls refuse before anything is copied or launched; params: map()'s doubles of every entry
+template <class Model>
+static int depth_reg_batch_check(const char* who, const gf_frame_ref* src, const gf_depth_reg* reg, const Model* colour, const int* colour_wh, const gf_frame_ref* dst, int batch,
                                  std::vector<gfdreg::Params>& params) {
     if (!src || !reg || !colour || !colour_wh || !dst) return set_err(GF_ERR_INVALID, "%s: null argument", who);
     if (batch < 1) return set_err(GF_ERR_INVALID, "%s: batch %d (must be >= 1)", who, batch);
@@ -60,8 +70,8 @@ static int depth_reg_batch_check(const char* who, const gf_frame_ref* src, const
         if (!gfdreg::check(reg[b], msg, sizeof msg)) return set_err(GF_ERR_INVALID, "%s: entry %d: %s", who, b, msg);
         gfcam::Camera cam;
         if (!gfcam::prepare(colour[b], cam, msg, sizeof msg)) return set_err(GF_ERR_INVALID, "%s: entry %d: colour camera: %s", who, b, msg);
-        if (colour[b].model != GF_CAMERA_PINHOLE)
-            return set_err(GF_ERR_INVALID, "%s: entry %d: the colour camera is %s; depth is registered to a GF_CAMERA_PINHOLE only", who, b, gfcam::model_name(colour[b].model));
+        if (colour[b].model != GF_CAMERA_PINHOLE && !full_tail(colour[b]))
+            return set_err(GF_ERR_INVALID, "%s: entry %d: the colour camera is %s; depth is registered to %s", who, b, gfcam::model_name(colour[b].model), colour_models(colour[b]));
         const int wc = colour_wh[2 * b], hc = colour_wh[2 * b + 1];
         if (wc < gfdreg::kMinSize || wc > gfdreg::kMaxSize || hc < gfdreg::kMinSize || hc > gfdreg::kMaxSize)
             return set_err(GF_ERR_INVALID, "%s: entry %d: colour size %d x %d is outside %d .. %d", who, b, wc, hc, gfdreg::kMinSize, gfdreg::kMaxSize);
@@ -69,16 +79,15 @@ static int depth_reg_batch_check(const char* who, const gf_frame_ref* src, const
         if (v != gfref::kOk) return set_err(GF_ERR_INVALID, "%s: raw depth frame of entry %d: %s (data %p, pitch %zu bytes, a row is %zu bytes)", who, b, gfref::verdict_text(v), src[b].data, src[b].pitch, (size_t)reg[b].width * 2);
         v = gfref::check(dst[b], (size_t)wc * 2, true, false);
         if (v != gfref::kOk) return set_err(GF_ERR_INVALID, "%s: registered frame of entry %d: %s (data %p, pitch %zu bytes, a row is %zu bytes)", who, b, gfref::verdict_text(v), dst[b].data, dst[b].pitch, (size_t)wc * 2);
-        params[b] = gfdreg::params_of(reg[b], colour[b].proj, colour[b].dist);
+        params[b] = gfdreg::params_of(reg[b], colour[b].proj, colour[b].dist, full_tail(colour[b]));
     }
     return GF_OK;
 }
 
 }  // namespace gf
 
-extern "C" {
-
-int gf_depth_register_batch_device(const gf_frame_ref* d_src, const gf_depth_reg* reg, const gf_camera_model* colour, const int* colour_wh, const gf_frame_ref* d_dst, int batch, void* stream) {
+template <class Model>
+static int depth_register_batch_device(const gf_frame_ref* d_src, const gf_depth_reg* reg, const Model* colour, const int* colour_wh, const gf_frame_ref* d_dst, int batch, void* stream) {
     std::vector<gfdreg::Params> params;
     if (int rc = gf::depth_reg_batch_check("depth_register", d_src, reg, colour, colour_wh, d_dst, batch, params)) return rc;
     if (int rc = gf::require_device()) return rc;
@@ -106,7 +115,8 @@ int gf_depth_register_batch_device(const gf_frame_ref* d_src, const gf_depth_reg
     return GF_OK;
 }
 
-int gf_depth_register_batch(const gf_frame_ref* src, const gf_depth_reg* reg, const gf_camera_model* colour, const int* colour_wh, const gf_frame_ref* dst, int batch) {
+template <class Model>
+static int depth_register_batch(const gf_frame_ref* src, const gf_depth_reg* reg, const Model* colour, const int* colour_wh, const gf_frame_ref* dst, int batch) {
     std::vector<gfdreg::Params> params;
     if (int rc = gf::depth_reg_batch_check("depth_register", src, reg, colour, colour_wh, dst, batch, params)) return rc;
     if (int rc = gf::require_device()) return rc;
@@ -127,12 +137,27 @@ int gf_depth_register_batch(const gf_frame_ref* src, const gf_depth_reg* reg, co
         at += (row * reg[b].height + 15) & ~(size_t)15;
         to += (out_row * colour_wh[2 * b + 1] + 15) & ~(size_t)15;
     }
-    if (int rc = gf_depth_register_batch_device(d_src.data(), reg, colour, colour_wh, d_dst.data(), batch, nullptr)) return rc;
+    if (int rc = depth_register_batch_device(d_src.data(), reg, colour, colour_wh, d_dst.data(), batch, nullptr)) return rc;
     for (int b = 0; b < batch; b++) {
         const size_t out_row = (size_t)colour_wh[2 * b] * 2;
         HIPCHK(hipMemcpy2D(const_cast<void*>(dst[b].data), dst[b].pitch, d_dst[b].data, out_row, out_row, colour_wh[2 * b + 1], hipMemcpyDeviceToHost));
     }
     return GF_OK;
+}
+
+extern "C" {
+
+int gf_depth_register_batch_device(const gf_frame_ref* d_src, const gf_depth_reg* reg, const gf_camera_model* colour, const int* colour_wh, const gf_frame_ref* d_dst, int batch, void* stream) {
+    return depth_register_batch_device(d_src, reg, colour, colour_wh, d_dst, batch, stream);
+}
+int gf_depth_register_batch_device_ex(const gf_frame_ref* d_src, const gf_depth_reg* reg, const gf_camera_model_ex* colour, const int* colour_wh, const gf_frame_ref* d_dst, int batch, void* stream) {
+    return depth_register_batch_device(d_src, reg, colour, colour_wh, d_dst, batch, stream);
+}
+int gf_depth_register_batch(const gf_frame_ref* src, const gf_depth_reg* reg, const gf_camera_model* colour, const int* colour_wh, const gf_frame_ref* dst, int batch) {
+    return depth_register_batch(src, reg, colour, colour_wh, dst, batch);
+}
+int gf_depth_register_batch_ex(const gf_frame_ref* src, const gf_depth_reg* reg, const gf_camera_model_ex* colour, const int* colour_wh, const gf_frame_ref* dst, int batch) {
+    return depth_register_batch(src, reg, colour, colour_wh, dst, batch);
 }
 
 }  // extern "C"

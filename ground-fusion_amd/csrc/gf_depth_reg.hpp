@@ -6,7 +6,8 @@
 //
 // One depth pixel (x, y) with count d != 0, z = (double)d * scale:
 //   map(px, py):  X = (px - cx_d) / fx_d * z,  Y = (py - cy_d) / fy_d * z,  P = R (X, Y, z) + T with each row summed as ((R0 X + R1 Y) + R2 z) + T;
-//                 !(P.z > 0): nothing.  (u, v) = gfcam::distort_to_plane(colour pinhole, P.x / P.z, P.y / P.z) -- the projection setPrediction uses.
+//                 !(P.z > 0): nothing.  (u, v) = gfcam::distort_to_plane(colour pinhole, P.x / P.z, P.y / P.z) -- the projection setPrediction uses -- or, for a
+//                 PINHOLE_FULL colour camera, gfcam::full_distort_to_plane, the tail of that model's spaceToPlane.  Nothing else depends on the model.
 //   a = map(x - 0.5, y - 0.5), b = map(x + 0.5, y + 0.5), c = map(x, y); one of them behind the camera or a coordinate that is not finite: nothing.
 //   val = floor(c.Pz / 0.001 + 0.5), millimetres along the colour camera's axis; outside [1, 65535]: nothing.
 //   footprint: the colour pixels whose centre lies in the half-open box of the corners, x0 = ceil(min(a.u, b.u)), x1 = ceil(max(a.u, b.u)) - 1, y alike;
@@ -19,7 +20,7 @@
 #include <stdio.h>
 
 #include "../../include/groundfusion_hip.h"   // gf_depth_reg, gf_camera_model
-#include "gf_camera_models.hpp"               // gfcam::distort_to_plane
+#include "gf_camera_models.hpp"               // gfcam::distort_to_plane, gfcam::full_distort_to_plane
 
 #if defined(__HIPCC__) || defined(__HIP__)
 #define GF_DREG_HD __host__ __device__ inline
@@ -33,20 +34,24 @@ constexpr int kMaxFoot = 8;                   // a footprint wider or higher tha
 constexpr uint32_t kUntouched = 0xFFFFFFFFu;  // what the z-buffer holds where no footprint arrived
 constexpr int kMinSize = 8, kMaxSize = 4096;
 
-// The 25 doubles of one registration as map() reads them: the depth pinhole, the scale, the pose, the colour pinhole with its distortion.
-struct Params { double fxd, fyd, cxd, cyd, scale, R[9], T[3], fx, fy, cx, cy, k1, k2, p1, p2; };
-static_assert(sizeof(Params) == 25 * sizeof(double), "Params is 25 doubles, read as such by the kernel");
+// One registration as map() reads it.  The first 25 doubles: the depth pinhole, the scale, the pose, the colour pinhole with its distortion -- all a PINHOLE
+// colour camera has.  Behind them what a PINHOLE_FULL one adds: k3 .. k6 and the model, which map<false> never reads.
+struct Params { double fxd, fyd, cxd, cyd, scale, R[9], T[3], fx, fy, cx, cy, k1, k2, p1, p2; double k3, k4, k5, k6; int32_t model, reserved; };
+constexpr int kPinholeDoubles = 25;
+static_assert(offsetof(Params, k3) == kPinholeDoubles * sizeof(double) && sizeof(Params) == 30 * sizeof(double), "Params is 25 doubles and the PINHOLE_FULL tail, read as such by the kernel");
 
 struct Mapped { double u, v, Pz; };
-// rule 2.  False: the point is not in front of the colour camera.
-GF_DREG_HD bool map(const Params& p, double px, double py, double z, Mapped& m) {
+// rule 2.  False: the point is not in front of the colour camera.  FULL: the entry may be a PINHOLE_FULL one (a branch on its model, the same for every pixel of
+// the entry); without, p is a PINHOLE entry and its tail is not read.
+template <bool FULL = true> GF_DREG_HD bool map(const Params& p, double px, double py, double z, Mapped& m) {
     const double X = (px - p.cxd) / p.fxd * z;
     const double Y = (py - p.cyd) / p.fyd * z;
     const double Px = ((p.R[0] * X + p.R[1] * Y) + p.R[2] * z) + p.T[0];
     const double Py = ((p.R[3] * X + p.R[4] * Y) + p.R[5] * z) + p.T[1];
     const double Pz = ((p.R[6] * X + p.R[7] * Y) + p.R[8] * z) + p.T[2];
     if (!(Pz > 0.0)) return false;
-    gfcam::distort_to_plane(p.fx, p.fy, p.cx, p.cy, p.k1, p.k2, p.p1, p.p2, Px / Pz, Py / Pz, m.u, m.v);
+    if (FULL && p.model == GF_CAMERA_PINHOLE_FULL) gfcam::full_distort_to_plane(p.fx, p.fy, p.cx, p.cy, p.k1, p.k2, p.p1, p.p2, p.k3, p.k4, p.k5, p.k6, Px / Pz, Py / Pz, m.u, m.v);
+    else gfcam::distort_to_plane(p.fx, p.fy, p.cx, p.cy, p.k1, p.k2, p.p1, p.p2, Px / Pz, Py / Pz, m.u, m.v);
     m.Pz = Pz;
     return true;
 }
@@ -56,11 +61,11 @@ GF_DREG_HD bool finite(double v) { return fabs(v) <= 1.7976931348623157e308; }  
 enum Outcome { kZero = 0, kBehind, kNotFinite, kOutOfRange, kOverBound, kEmpty, kWrites };
 struct Foot { int x0, x1, y0, y1; uint32_t val; };   // inclusive, inside the colour frame
 // rules 1-5 for the depth pixel (x, y) with count d into a colour frame of wc x hc
-GF_DREG_HD Outcome footprint(const Params& p, int wc, int hc, int x, int y, uint16_t d, Foot& f) {
+template <bool FULL = true> GF_DREG_HD Outcome footprint(const Params& p, int wc, int hc, int x, int y, uint16_t d, Foot& f) {
     if (d == 0) return kZero;
     const double z = (double)d * p.scale;
     Mapped a, b, c;
-    if (!map(p, (double)x - 0.5, (double)y - 0.5, z, a) || !map(p, (double)x + 0.5, (double)y + 0.5, z, b) || !map(p, (double)x, (double)y, z, c)) return kBehind;
+    if (!map<FULL>(p, (double)x - 0.5, (double)y - 0.5, z, a) || !map<FULL>(p, (double)x + 0.5, (double)y + 0.5, z, b) || !map<FULL>(p, (double)x, (double)y, z, c)) return kBehind;
     if (!finite(a.u) || !finite(a.v) || !finite(b.u) || !finite(b.v) || !finite(c.u) || !finite(c.v)) return kNotFinite;
     const double val = floor(c.Pz / 0.001 + 0.5);
     if (!(val >= 1.0 && val <= 65535.0)) return kOutOfRange;
@@ -78,9 +83,9 @@ GF_DREG_HD Outcome footprint(const Params& p, int wc, int hc, int x, int y, uint
 
 // What a thread of the scatter kernel does with its depth pixel: rule 6 into a z-buffer of rows `zstride` words apart.  min_into(word, val): the device's atomic
 // minimum, the host's plain one.  At most kMaxFoot x kMaxFoot calls.
-template <class MIN> GF_DREG_HD Outcome scatter_pixel(const Params& p, int wc, int hc, int x, int y, uint16_t d, uint32_t* z, size_t zstride, MIN min_into) {
+template <bool FULL = true, class MIN> GF_DREG_HD Outcome scatter_pixel(const Params& p, int wc, int hc, int x, int y, uint16_t d, uint32_t* z, size_t zstride, MIN min_into) {
     Foot f;
-    const Outcome o = footprint(p, wc, hc, x, y, d, f);
+    const Outcome o = footprint<FULL>(p, wc, hc, x, y, d, f);
     if (o != kWrites) return o;
     for (int v = f.y0; v <= f.y1; v++)
         for (int u = f.x0; u <= f.x1; u++) min_into(z + (size_t)v * zstride + u, f.val);
@@ -132,14 +137,15 @@ inline bool check(const gf_depth_reg& r, char* msg, size_t n) {
     return true;
 }
 
-// the 25 doubles of a checked registration and a colour pinhole (proj = fx fy cx cy, dist = k1 k2 p1 p2)
-inline Params params_of(const gf_depth_reg& r, const double* proj, const double* dist) {
-    Params p;
+// a checked registration and a colour pinhole (proj = fx fy cx cy, dist = k1 k2 p1 p2), or with `full` (k3 k4 k5 k6) a colour PINHOLE_FULL
+inline Params params_of(const gf_depth_reg& r, const double* proj, const double* dist, const double* full = nullptr) {
+    Params p{};
     p.fxd = r.fx; p.fyd = r.fy; p.cxd = r.cx; p.cyd = r.cy; p.scale = r.scale;
     for (int i = 0; i < 9; i++) p.R[i] = r.R[i];
     for (int i = 0; i < 3; i++) p.T[i] = r.T[i];
     p.fx = proj[0]; p.fy = proj[1]; p.cx = proj[2]; p.cy = proj[3];
     p.k1 = dist[0]; p.k2 = dist[1]; p.p1 = dist[2]; p.p2 = dist[3];
+    if (full) { p.k3 = full[0]; p.k4 = full[1]; p.k5 = full[2]; p.k6 = full[3]; p.model = GF_CAMERA_PINHOLE_FULL; }
     return p;
 }
 

@@ -30,11 +30,14 @@ template <int N> __device__ __forceinline__ Job job_at(const Job* __restrict__ j
     for (int i = 0; i < N; i++) u.w[i] = __builtin_amdgcn_readfirstlane(p[i]);
     return u.j;
 }
-constexpr int kJobDwords = sizeof(Job) / 4, kJobHeadDwords = (5 * 8 + 4 * 4) / 4;   // everything / all but the doubles
+constexpr int kJobHeadDwords = (5 * 8 + 4 * 4) / 4;   // all but the doubles
+constexpr int kJobDwords = sizeof(Job) / 4, kJobPinholeDwords = kJobHeadDwords + 2 * kPinholeDoubles;   // everything / all a PINHOLE entry has
 
-__global__ __launch_bounds__(kThreads) void depth_scatter_kernel(const Job* __restrict__ jobs, uint32_t* __restrict__ zbuf, int batch) {
+// FULL: the call lists a PINHOLE_FULL colour camera; every entry then reads its whole Job and branches on its model, the same for the whole block.  Without, the
+// kernel is the one it was before that model: it reads the 25 doubles of a PINHOLE entry and holds no branch.
+template <bool FULL> __global__ __launch_bounds__(kThreads) void depth_scatter_kernel(const Job* __restrict__ jobs, uint32_t* __restrict__ zbuf, int batch) {
     for (int b = blockIdx.y; b < batch; b += gridDim.y) {
-        const Job j = job_at<kJobDwords>(jobs, b);
+        const Job j = job_at<FULL ? kJobDwords : kJobPinholeDwords>(jobs, b);
         const bool dwords = gfref::form(reinterpret_cast<uintptr_t>(j.src), j.src_pitch) >= 4;
         const unsigned per_row = (unsigned)j.wd, items = per_row * (unsigned)j.hd;   // <= 4096 x 4096
         uint32_t* z = zbuf + j.zoff;
@@ -46,7 +49,7 @@ __global__ __launch_bounds__(kThreads) void depth_scatter_kernel(const Job* __re
             uint16_t d;
             if (dwords && (x | 1u) < per_row) d = (uint16_t)(*reinterpret_cast<const uint32_t*>(row + 4 * (size_t)(x >> 1)) >> (16 * (x & 1u)));   // the dword its neighbour lane reads too
             else d = *reinterpret_cast<const uint16_t*>(row + 2 * (size_t)x);                    // the last count of an odd width: the dword would leave the row
-            scatter_pixel(j.p, j.wc, j.hc, (int)x, (int)y, d, z, zs, min_into);
+            scatter_pixel<FULL>(j.p, j.wc, j.hc, (int)x, (int)y, d, z, zs, min_into);
         }
     }
 }

@@ -1963,6 +1963,10 @@ int gf_estimator_set_camera(gf_estimator* e, const gf_camera_model* camera) {
     if (!e || !e->tracker) return gf::set_err(GF_ERR_INVALID, "estimator was created without a tracker (cfg.with_tracker)");
     return gf_tracker_set_seq_camera(e->tracker, 0, camera);
 }
+int gf_estimator_set_camera_ex(gf_estimator* e, const gf_camera_model_ex* camera) {
+    if (!e || !e->tracker) return gf::set_err(GF_ERR_INVALID, "estimator was created without a tracker (cfg.with_tracker)");
+    return gf_tracker_set_seq_camera_ex(e->tracker, 0, camera);
+}
 // the exclusion boxes of the estimator's own tracker (gf_tracker_set_boxes_some on its one sequence): from the next gf_estimator_input_image on; n == 0 clears
 int gf_estimator_set_boxes(gf_estimator* e, const gf_box* boxes, int n) {
     if (!e || !e->tracker) return gf::set_err(GF_ERR_INVALID, "estimator was created without a tracker (cfg.with_tracker)");

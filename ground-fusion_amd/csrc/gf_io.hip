@@ -158,6 +158,11 @@ int gf_show_track_from_yaml(const char* config_file, int* show_track) {
 
 // A camodocal calibration file already parsed (`path` names it in messages): model_type and the keys of the model's readFromYamlFile
 // (PinholeCamera.cc:145-183, CataCamera.cc:160-202, EquidistantCamera.cc:146-182); checked as every setter checks a model (gfcam::prepare).
+static bool iequals(const std::string& a, const char* b) {   // boost::iequals, CameraFactory.cc:111-127
+    size_t i = 0;
+    for (; i < a.size() && b[i]; i++) if (tolower((unsigned char)a[i]) != tolower((unsigned char)b[i])) return false;
+    return i == a.size() && !b[i];
+}
 static int camera_from_doc(const YamlDoc& k, const char* path, gf_camera_model* out) {
     const std::string type = k.has("model_type") ? k.str("model_type") : std::string("PINHOLE");   // CameraFactory.cc: a file without the key is a pinhole
     gf_camera_model m;
@@ -169,8 +174,9 @@ static int camera_from_doc(const YamlDoc& k, const char* path, gf_camera_model* 
         m.model = GF_CAMERA_KANNALA_BRANDT; dist_node = "projection_parameters";
         const char* p[4] = {"mu", "mv", "u0", "v0"}; const char* d[4] = {"k2", "k3", "k4", "k5"}; memcpy(proj, p, sizeof p); memcpy(dist, d, sizeof d);
     }
-    else if (type == "PINHOLE_FULL" || type == "SCARAMUZZA") return gf::set_err(GF_ERR_INVALID, "%s: model_type '%s' is not built (PINHOLE, MEI and KANNALA_BRANDT are)", path, type.c_str());
-    else return gf::set_err(GF_ERR_INVALID, "%s: unknown model_type '%s' (PINHOLE, MEI and KANNALA_BRANDT are built)", path, type.c_str());
+    else if (iequals(type, "PINHOLE_FULL") || iequals(type, "SCARAMUZZA"))
+        return gf::set_err(GF_ERR_INVALID, "%s: model_type '%s' does not fit gf_camera_model (PINHOLE, MEI and KANNALA_BRANDT do): read it with gf_camera_from_yaml_ex", path, type.c_str());
+    else return gf::set_err(GF_ERR_INVALID, "%s: unknown model_type '%s' (camodocal has PINHOLE, MEI, KANNALA_BRANDT, PINHOLE_FULL and SCARAMUZZA)", path, type.c_str());
     for (int i = 0; i < 4; i++) {
         m.proj[i] = k.real(std::string("projection_parameters.") + proj[i]);
         m.dist[i] = k.real(std::string(dist_node) + "." + dist[i]);
@@ -185,6 +191,46 @@ static int camera_from_doc(const YamlDoc& k, const char* path, gf_camera_model* 
     return GF_OK;
 }
 
+// The same for the wide struct: PINHOLE_FULL (PinholeFullCamera.cc:209-249) and SCARAMUZZA (ScaramuzzaCamera.cc:64-105), their model_type compared without regard
+// to case (CameraFactory.cc:119-129); every other file as camera_from_doc reads it.
+static int camera_from_doc_ex(const YamlDoc& k, const char* path, gf_camera_model_ex* out) {
+    const std::string type = k.str("model_type");
+    gf_camera_model_ex m;
+    memset(&m, 0, sizeof m);
+    if (iequals(type, "PINHOLE_FULL")) {
+        m.model = GF_CAMERA_PINHOLE_FULL;
+        const char* p[4] = {"fx", "fy", "cx", "cy"}; const char* d[8] = {"k1", "k2", "p1", "p2", "k3", "k4", "k5", "k6"};
+        for (int i = 0; i < 4; i++) m.proj[i] = k.real(std::string("projection_parameters.") + p[i]);
+        for (int i = 0; i < 8; i++) m.dist[i] = k.real(std::string("distortion_parameters.") + d[i]);
+        for (int i = 0; i < 2; i++)
+            if (!k.has(std::string("projection_parameters.") + p[i])) return gf::set_err(GF_ERR_INVALID, "%s: projection_parameters.%s is missing", path, p[i]);
+    } else if (iequals(type, "SCARAMUZZA")) {
+        m.model = GF_CAMERA_SCARAMUZZA;
+        const char* a[5] = {"ac", "ad", "ae", "cx", "cy"};
+        for (int i = 0; i < 5; i++) m.poly[i] = k.real("poly_parameters.p" + std::to_string(i));
+        for (int i = 0; i < 20; i++) m.inv_poly[i] = k.real("inv_poly_parameters.p" + std::to_string(i));
+        for (int i = 0; i < 5; i++) m.affine[i] = k.real(std::string("affine_parameters.") + a[i]);
+    } else {
+        gf_camera_model n;
+        if (int rc = camera_from_doc(k, path, &n)) return rc;
+        *out = gfcam::widen(n);
+        return GF_OK;
+    }
+    gfcam::Camera checked;
+    char msg[320];
+    if (!gfcam::prepare(m, checked, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "%s: %s", path, msg);
+    *out = m;
+    return GF_OK;
+}
+
+int gf_camera_from_yaml_ex(const char* calib_file, gf_camera_model_ex* out) {
+    if (!calib_file || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    YamlDoc k;
+    std::string err;
+    if (!parse_yaml(calib_file, k, err)) return gf::set_err(GF_ERR_INVALID, "%s: %s", calib_file, err.c_str());
+    return camera_from_doc_ex(k, calib_file, out);
+}
+
 int gf_camera_from_yaml(const char* calib_file, gf_camera_model* out) {
     if (!calib_file || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
     YamlDoc k;
@@ -193,8 +239,8 @@ int gf_camera_from_yaml(const char* calib_file, gf_camera_model* out) {
     return camera_from_doc(k, calib_file, out);
 }
 
-// camera == null: gf_estimator_cfg_from_yaml, which takes a PINHOLE file alone
-static int estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* c, gf_camera_model* camera) {
+// camera == null and wide == null: gf_estimator_cfg_from_yaml, which takes a PINHOLE file alone; at most one of the two is given
+static int estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* c, gf_camera_model* camera, gf_camera_model_ex* wide = nullptr) {
     YamlDoc y;
     std::string err;
     if (!parse_yaml(config_file, y, err)) return gf::set_err(GF_ERR_INVALID, "%s: %s", config_file, err.c_str());
@@ -267,6 +313,15 @@ static int estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* c,
     const std::string cam = (pn == std::string::npos ? std::string(".") : cf.substr(0, pn)) + "/" + y.str("cam0_calib");
     YamlDoc k;
     if (!parse_yaml(cam.c_str(), k, err)) return gf::set_err(GF_ERR_INVALID, "cam0_calib: %s", err.c_str());
+    if (wide) {
+        if (int rc = camera_from_doc_ex(k, cam.c_str(), wide)) return rc;
+        if (wide->model != GF_CAMERA_PINHOLE) {   // valid placeholders as below; a SCARAMUZZA camera has no focal length: 1, and its centre
+            const bool sca = wide->model == GF_CAMERA_SCARAMUZZA;
+            t.fx = sca ? 1.0 : wide->proj[0]; t.fy = sca ? 1.0 : wide->proj[1]; t.cx = sca ? wide->affine[3] : wide->proj[2]; t.cy = sca ? wide->affine[4] : wide->proj[3];
+            t.k1 = t.k2 = t.p1 = t.p2 = 0.0;
+            return GF_OK;
+        }
+    }
     if (camera) {
         if (int rc = camera_from_doc(k, cam.c_str(), camera)) return rc;
         if (camera->model != GF_CAMERA_PINHOLE) {   // valid placeholders: nothing reads them once gf_estimator_set_camera has the model
@@ -292,6 +347,11 @@ int gf_estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* c) {
 int gf_estimator_cfg_from_yaml_camera(const char* config_file, gf_estimator_cfg* c, gf_camera_model* camera) {
     if (!config_file || !c || !camera) return gf::set_err(GF_ERR_INVALID, "null argument");
     return estimator_cfg_from_yaml(config_file, c, camera);
+}
+
+int gf_estimator_cfg_from_yaml_camera_ex(const char* config_file, gf_estimator_cfg* c, gf_camera_model_ex* camera) {
+    if (!config_file || !c || !camera) return gf::set_err(GF_ERR_INVALID, "null argument");
+    return estimator_cfg_from_yaml(config_file, c, nullptr, camera);
 }
 
 int gf_tum_append(const char* path, double t, const double* P, const double* R) {

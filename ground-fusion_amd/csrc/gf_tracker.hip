@@ -240,10 +240,15 @@ struct gf_tracker {
     // first setter that gives a sequence a model other than PINHOLE; a pinhole stays the eight fields of par[seq] and is lifted on the host as ever.  cam_on[seq]:
     // the sequence has such a model, cam_model / cam[seq] as it was set / as the formulas read it, d_cams the same table on the device (a row written by the
     // setter).  Per call, by list position: cam_of (the sequence, or -1 for a pinhole one, which the kernel skips) and the two tables of lifted pairs, for the rows
-    // of LK's points and of the new corners, which come up with the call's last copies.  lift_host (GF_CAMERA_LIFT_HOST=1): none of the per-call tables is used,
-    // after_detect lifts with the same header.
-    bool lift_host = false;
-    std::vector<uint8_t> cam_on; std::vector<gf_camera_model> cam_model; std::vector<gfcam::Camera> cam;
+    // of LK's points and of the new corners, which come up with the call's last copies.  A sequence that is lifted on the host (lifts_on_device false) uses none
+    // of the per-call tables: after_detect lifts it with the same header.
+    int lift_mode = -1;   // GF_CAMERA_LIFT_HOST: unset -1 (each model's measured default: SCARAMUZZA on the host, every other model on the device), 0 all on the device, 1 all on the host
+    long long lift_launches = 0, lift_sequences = 0;   // gf_tracker_get_camera_lift_stats
+    bool lifts_on_device(int q) const {   // sequence q is lifted by the call's launch of camera_lift_kernel
+        if (!d_cams.p || !cam_on[q]) return false;
+        return lift_mode < 0 ? cam_model[q].model != GF_CAMERA_SCARAMUZZA : lift_mode == 0;
+    }
+    std::vector<uint8_t> cam_on; std::vector<gf_camera_model_ex> cam_model; std::vector<gfcam::Camera> cam;
     DevBuf<gfcam::Camera> d_cams;
     DevBuf<int> d_cam_of; PinBuf<int> h_cam_of;
     DevBuf<float2> d_un_lk, d_un_out; PinBuf<float2> h_un_lk, h_un_out;
@@ -741,6 +746,7 @@ struct Call {
     const uint16_t* kdepth = nullptr;     // what LK and the selection sample: tight device depth frames, the device table's depth half (depth_by_refs) or null
     bool any_prev = false, any_pred = false, any_plain = false, any_want = false;
     bool lift = false;                    // a listed sequence has a camera that is lifted on the device (run_detect, book_after_detect)
+    int n_lift = 0;                       // how many of them
     bool mixed = false;                   // a listed sequence runs with a format or switch that is not the handle's own: the front goes through h->plan
     const uint8_t* mix = nullptr;         // the table of a mixed call where the front's kernels read it (h_mix over the bus, or d_mix)
     bool did_cvt = false, did_eq = false; // the call converted / equalised at least one listed sequence (read_profile)
@@ -776,13 +782,14 @@ static int publish(Call& c) {
                 if (!h->dreg_on[q]) continue;
                 if (!h->par[q].depth_cam || !in.depth_refs[i].data) { h->h_refs.p[h->B + i] = gf_frame_ref{nullptr, 0}; continue; }   // a raw frame is no frame of the colour size: nothing samples it
                 const gf_tracker_seq_cfg& par = h->par[q];
+                const bool full = !h->cam_on.empty() && h->cam_on[q];   // with a registration set: a PINHOLE_FULL camera (the two setters see to it)
                 const double proj[4] = {par.fx, par.fy, par.cx, par.cy}, dist[4] = {par.k1, par.k2, par.p1, par.p2};
                 gfdreg::Job& j = h->dreg_stage.h_jobs.p[c.n_reg++];
                 j.src = static_cast<const uint8_t*>(in.depth_refs[i].data); j.src_pitch = in.depth_refs[i].pitch;
                 j.wd = h->dreg[q].width; j.hd = h->dreg[q].height; j.wc = seq_width(h, q); j.hc = seq_height(h, q);
                 j.dst = reinterpret_cast<uint8_t*>(h->d_dreg.p + (size_t)q * slot); j.dst_pitch = (size_t)j.wc * 2;
                 j.zoff = (size_t)i * zslot;
-                j.p = gfdreg::params_of(h->dreg[q], proj, dist);
+                j.p = full ? gfdreg::params_of(h->dreg[q], h->cam_model[q].proj, h->cam_model[q].dist, h->cam_model[q].dist + 4) : gfdreg::params_of(h->dreg[q], proj, dist);
                 h->h_refs.p[h->B + i] = gf_frame_ref{j.dst, j.dst_pitch};
             }
         }
@@ -1059,7 +1066,7 @@ static void book_after_lk(Call& c) {
         const gf_box* boxes = h->boxes.empty() ? nullptr : h->boxes[q].data();
         const int fw = c.sized ? h->size_plan.w[b] : h->cfg.width, fh = c.sized ? h->size_plan.h[b] : h->cfg.height;   // the sequence's own frame (feature_tracker.cpp:108-109)
         const LkTally n = after_lk(h->seq[q], par, fw, fh, h->seq_disk.empty() ? h->disk : h->seq_disk[q], roi, r, row(h->h_centers, b, cap), h->h_ncenters.p + b, &want,
-                                   boxes, boxes ? (int)h->boxes[q].size() : 0, h->d_cams.p && !h->lift_host && h->cam_on[q]);
+                                   boxes, boxes ? (int)h->boxes[q].size() : 0, h->lifts_on_device(q));
         a_levels += n.level_passes; a_iters += n.iterations; a_points += n.points; a_tracked += n.tracked;
         h->h_want.p[b] = want;
         if (h->h_seq_md.p) h->h_seq_md.p[b] = par.min_dist;
@@ -1068,8 +1075,8 @@ static void book_after_lk(Call& c) {
         h->h_out_n.p[b] = 0;
     });
     c.any_want = a_want.load() != 0;
-    if (h->d_cams.p && !h->lift_host)
-        for (int b = 0; b < c.N; b++) { const int q = c.seq[b]; h->h_cam_of.p[b] = h->cam_on[q] ? q : -1; c.lift |= h->cam_on[q] != 0; }
+    if (h->d_cams.p)   // a sequence lifted on the host is not listed: the kernel skips it, and a call that lists none has no launch
+        for (int b = 0; b < c.N; b++) { const int q = c.seq[b]; const bool dev = h->lifts_on_device(q); h->h_cam_of.p[b] = dev ? q : -1; c.lift |= dev; if (dev) c.n_lift++; }
     h->stats.lk_level_passes += a_levels; h->stats.lk_iterations += a_iters; h->stats.lk_points += a_points; h->stats.tracked_features += a_tracked;
 }
 
@@ -1085,6 +1092,7 @@ static int launch_lift(Call& c) {
     A.set[0] = gfcam::LiftSet{pairs(h->d_cur_pts.p), c.any_prev ? h->d_npts.p : nullptr, pairs(h->d_un_lk.p), nullptr};
     A.set[1] = gfcam::LiftSet{pairs(h->d_out_pts.p), c.any_want ? h->d_out_n.p : nullptr, pairs(h->d_un_out.p), nullptr};
     if (!c.any_prev && !c.any_want) return GF_OK;
+    h->lift_launches++; h->lift_sequences += c.n_lift;
     return camera_lift_launch(A, h->cap, h->stream);
 }
 
@@ -1179,9 +1187,9 @@ static int book_after_detect(Call& c, gf_feature_obs* out, int cap_out, int* n_o
     h->pool->parallel_for(c.N, [&](int b) {   // b: list position
         const int q = c.seq[b];
         const DetectRows r{row(h->h_out_pts, b, cap), c.in.kernel_samples(h->h_out_depth, b, cap), h->h_want.p[b] > 0 ? h->h_out_n.p[b] : 0, c.in.host_image(b, h->par[q]), c.in.host_dstride};
-        const bool own = !h->cam_on.empty() && h->cam_on[q];
+        const bool own = !h->cam_on.empty() && h->cam_on[q], dev = own && c.lift && h->lifts_on_device(q);
         const Packed p = after_detect(h->seq[q], h->par[q], r, have_depth, out + (size_t)b * cap_out, cap_out, own ? &h->cam[q] : nullptr,
-                                      own && c.lift ? row(h->h_un_lk, b, cap) : nullptr, own && c.lift ? row(h->h_un_out, b, cap) : nullptr);
+                                      dev ? row(h->h_un_lk, b, cap) : nullptr, dev ? row(h->h_un_out, b, cap) : nullptr);
         if (h->seq[q].show_track) (void)record_track(h->seq[q], h->boxes.empty() ? nullptr : h->boxes[q].data(), h->boxes.empty() ? 0 : (int)h->boxes[q].size());   // a refused list: the sequence has no picture of this frame, and keeps the reason (draw_why)
         if (p.overflow >= 0) a_overflow = p.overflow;
         n_out[b] = p.written;
@@ -1269,7 +1277,7 @@ int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out) {
         h->copy_lists = !(getenv("GF_TRACKER_COPIES") && atoi(getenv("GF_TRACKER_COPIES")) != 0);
         h->pyr_head = !(getenv("GF_PYR_HEAD") && atoi(getenv("GF_PYR_HEAD")) == 0);
         h->select_topk = !(getenv("GF_SELECT_TOPK") && atoi(getenv("GF_SELECT_TOPK")) == 0);
-        if (const char* e = getenv("GF_CAMERA_LIFT_HOST")) h->lift_host = atoi(e) != 0;
+        if (const char* e = getenv("GF_CAMERA_LIFT_HOST")) h->lift_mode = atoi(e) != 0 ? 1 : 0;
         if (const char* e = getenv("GF_LK_POINTS")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) h->lk_points = v; }
     }
     const int W = cfg->width, H = cfg->height, B = h->B, cap = h->cap;
@@ -1674,41 +1682,76 @@ static int seq_camera_ready(gf_tracker* h) {   // the first setter of a model ot
     DevBuf<gfcam::Camera> cams; DevBuf<int> of; PinBuf<int> hof; DevBuf<float2> lk, out; PinBuf<float2> hlk, hout;
     HIPCHK(cams.alloc(B)); HIPCHK(of.alloc(B)); HIPCHK(hof.alloc(B));
     HIPCHK(lk.alloc(B * cap)); HIPCHK(out.alloc(B * cap)); HIPCHK(hlk.alloc(B * cap)); HIPCHK(hout.alloc(B * cap));
-    h->cam_on.assign(B, 0); h->cam_model.assign(B, gf_camera_model{}); h->cam.assign(B, gfcam::Camera{});
+    h->cam_on.assign(B, 0); h->cam_model.assign(B, gf_camera_model_ex{}); h->cam.assign(B, gfcam::Camera{});
     h->d_cams = std::move(cams); h->d_cam_of = std::move(of); h->h_cam_of = std::move(hof);
     h->d_un_lk = std::move(lk); h->d_un_out = std::move(out); h->h_un_lk = std::move(hlk); h->h_un_out = std::move(hout);
     return GF_OK;
 }
 }  // namespace gf
 
-int gf_tracker_set_seq_camera(gf_tracker* h, int seq, const gf_camera_model* m) {
-    if (!h || !m) return gf::set_err(GF_ERR_INVALID, "null argument");
-    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
-    if (h->seq[seq].started) return gf::set_err(GF_ERR_INVALID, "sequence %d has taken a frame: its camera is fixed until gf_tracker_reset_seq", seq);
-    if (gf::seq_is_staged(h, seq)) return gf::set_err(GF_ERR_INVALID, "sequence %d is listed by a staged frame: gf_tracker_track_prefetched has to consume it first", seq);
-    gfcam::Camera checked;
-    char msg[320];
-    if (!gfcam::prepare(*m, checked, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "sequence %d: %s", seq, msg);
-    if (m->model != GF_CAMERA_PINHOLE && !h->dreg_on.empty() && h->dreg_on[seq])
-        return gf::set_err(GF_ERR_INVALID, "sequence %d has a depth registration (gf_tracker_set_seq_depth_reg), which projects through a GF_CAMERA_PINHOLE only: clear it before a %s camera is set", seq, gfcam::model_name(m->model));
-    if (m->model == GF_CAMERA_PINHOLE) {   // the eight camera fields of the sequence's parameters, through their own setter
+namespace gf {
+// both setters behind their checker: `checked` is `m` as gfcam::prepare passed it
+static int seq_camera_set(gf_tracker* h, int seq, const gf_camera_model_ex& m, const gfcam::Camera& checked) {
+    if (m.model != GF_CAMERA_PINHOLE && m.model != GF_CAMERA_PINHOLE_FULL && !h->dreg_on.empty() && h->dreg_on[seq])
+        return gf::set_err(GF_ERR_INVALID, "sequence %d has a depth registration (gf_tracker_set_seq_depth_reg), which projects through a GF_CAMERA_PINHOLE or GF_CAMERA_PINHOLE_FULL only: clear it before a %s camera is set", seq, gfcam::model_name(m.model));
+    if (m.model == GF_CAMERA_PINHOLE) {   // the eight camera fields of the sequence's parameters, through their own setter
         gf_tracker_seq_cfg want = h->par[seq];
-        want.fx = m->proj[0]; want.fy = m->proj[1]; want.cx = m->proj[2]; want.cy = m->proj[3];
-        want.k1 = m->dist[0]; want.k2 = m->dist[1]; want.p1 = m->dist[2]; want.p2 = m->dist[3];
+        want.fx = m.proj[0]; want.fy = m.proj[1]; want.cx = m.proj[2]; want.cy = m.proj[3];
+        want.k1 = m.dist[0]; want.k2 = m.dist[1]; want.p1 = m.dist[2]; want.p2 = m.dist[3];
         if (int rc = gf_tracker_set_seq_cfg(h, seq, &want)) return rc;
         if (!h->cam_on.empty()) h->cam_on[seq] = 0;
         return GF_OK;
     }
     if (int rc = gf::seq_camera_ready(h)) return rc;
     HIPCHK(hipMemcpy(h->d_cams.p + seq, &checked, sizeof checked, hipMemcpyHostToDevice));
-    h->cam[seq] = checked; h->cam_model[seq] = *m; h->cam_on[seq] = 1;
+    h->cam[seq] = checked; h->cam_model[seq] = m; h->cam_on[seq] = 1;
+    return GF_OK;
+}
+static int seq_camera_open(gf_tracker* h, int seq, const void* m) {   // what both setters refuse ahead of the model's own rules
+    if (!h || !m) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    if (h->seq[seq].started) return gf::set_err(GF_ERR_INVALID, "sequence %d has taken a frame: its camera is fixed until gf_tracker_reset_seq", seq);
+    if (gf::seq_is_staged(h, seq)) return gf::set_err(GF_ERR_INVALID, "sequence %d is listed by a staged frame: gf_tracker_track_prefetched has to consume it first", seq);
+    return GF_OK;
+}
+}  // namespace gf
+
+int gf_tracker_set_seq_camera(gf_tracker* h, int seq, const gf_camera_model* m) {
+    if (int rc = gf::seq_camera_open(h, seq, m)) return rc;
+    gfcam::Camera checked;
+    char msg[320];
+    if (!gfcam::prepare(*m, checked, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "sequence %d: %s", seq, msg);
+    return gf::seq_camera_set(h, seq, gfcam::widen(*m), checked);
+}
+
+int gf_tracker_set_seq_camera_ex(gf_tracker* h, int seq, const gf_camera_model_ex* m) {
+    if (int rc = gf::seq_camera_open(h, seq, m)) return rc;
+    gfcam::Camera checked;
+    char msg[320];
+    if (!gfcam::prepare(*m, checked, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "sequence %d: %s", seq, msg);
+    return gf::seq_camera_set(h, seq, *m, checked);
+}
+
+int gf_tracker_get_camera_lift_stats(gf_tracker* h, long long* launches, long long* sequences) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (launches) *launches = h->lift_launches;
+    if (sequences) *sequences = h->lift_sequences;
+    return GF_OK;
+}
+
+int gf_tracker_get_seq_camera_ex(gf_tracker* h, int seq, gf_camera_model_ex* out) {
+    if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    *out = !h->cam_on.empty() && h->cam_on[seq] ? h->cam_model[seq] : gfcam::widen(gfcam::pinhole_of(h->par[seq]));
     return GF_OK;
 }
 
 int gf_tracker_get_seq_camera(gf_tracker* h, int seq, gf_camera_model* out) {
     if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
     if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
-    *out = !h->cam_on.empty() && h->cam_on[seq] ? h->cam_model[seq] : gfcam::pinhole_of(h->par[seq]);
+    if (!h->cam_on.empty() && h->cam_on[seq] && h->cam_model[seq].model > GF_CAMERA_KANNALA_BRANDT)
+        return gf::set_err(GF_ERR_INVALID, "sequence %d has a %s camera, which gf_camera_model cannot carry: use gf_tracker_get_seq_camera_ex", seq, gfcam::model_name(h->cam_model[seq].model));
+    *out = !h->cam_on.empty() && h->cam_on[seq] ? gfcam::narrow(h->cam_model[seq]) : gfcam::pinhole_of(h->par[seq]);
     return GF_OK;
 }
 
@@ -1840,8 +1883,8 @@ int gf_tracker_set_seq_depth_reg(gf_tracker* h, int seq, const gf_depth_reg* reg
     if (!reg && h->dreg_on.empty()) return GF_OK;   // nothing to take back, whatever the sequence's state: the handle stays one that never set any
     if (h->seq[seq].started) return gf::set_err(GF_ERR_INVALID, "sequence %d has taken a frame: its depth registration is fixed until gf_tracker_reset_seq", seq);
     if (gf::seq_is_staged(h, seq)) return gf::set_err(GF_ERR_INVALID, "sequence %d is listed by a staged frame: gf_tracker_track_prefetched has to consume it first (depth registration)", seq);
-    if (reg && !h->cam_on.empty() && h->cam_on[seq])
-        return gf::set_err(GF_ERR_INVALID, "sequence %d has a %s camera (gf_tracker_set_seq_camera); depth is registered to a GF_CAMERA_PINHOLE only: set one first", seq, gfcam::model_name(h->cam_model[seq].model));
+    if (reg && !h->cam_on.empty() && h->cam_on[seq] && h->cam_model[seq].model != GF_CAMERA_PINHOLE_FULL)
+        return gf::set_err(GF_ERR_INVALID, "sequence %d has a %s camera (gf_tracker_set_seq_camera); depth is registered to a GF_CAMERA_PINHOLE or GF_CAMERA_PINHOLE_FULL only: set one first", seq, gfcam::model_name(h->cam_model[seq].model));
     if (int rc = gf::seq_depth_reg_ready(h)) return rc;
     h->dreg_on[seq] = reg ? 1 : 0;
     h->dreg[seq] = reg ? *reg : gf_depth_reg{};
@@ -1988,7 +2031,7 @@ int gf_tracker_get_state(gf_tracker* h, int seq, int* ids, int* track_cnt, float
 
 int gf_tracker_set_profiling(gf_tracker* h, int enable) { if (!h) return gf::set_err(GF_ERR_INVALID, "null handle"); h->profiling = enable != 0; return GF_OK; }
 int gf_tracker_get_stats(gf_tracker* h, gf_tracker_stats* out) { if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument"); *out = h->stats; return GF_OK; }
-int gf_tracker_reset_stats(gf_tracker* h) { if (!h) return gf::set_err(GF_ERR_INVALID, "null handle"); h->stats = gf_tracker_stats{}; h->dreg_launches = h->dreg_frames = 0; h->dreg_ms = 0; return GF_OK; }
+int gf_tracker_reset_stats(gf_tracker* h) { if (!h) return gf::set_err(GF_ERR_INVALID, "null handle"); h->stats = gf_tracker_stats{}; h->dreg_launches = h->dreg_frames = 0; h->dreg_ms = 0; h->lift_launches = h->lift_sequences = 0; return GF_OK; }
 
 // ------------------------------------------------------------------ building blocks for parity tests
 static int tmp_handle(int width, int height, int max_cnt, int min_dist, std::unique_ptr<gf_tracker>& own) {

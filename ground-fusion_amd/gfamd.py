@@ -154,43 +154,93 @@ class CameraModel(C.Structure):
 
 assert C.sizeof(CameraModel) == 80
 
+CAMERA_PINHOLE_FULL, CAMERA_SCARAMUZZA = 3, 4   # valid in CameraModelEx only
+CAMERA_NAMES_EX = dict(CAMERA_NAMES, PINHOLE_FULL=CAMERA_PINHOLE_FULL, SCARAMUZZA=CAMERA_SCARAMUZZA)
+
+
+class CameraModelEx(C.Structure):
+    """gf_camera_model_ex: any of camodocal's five cameras -- proj, dist[:4], xi as CameraModel for models 0-2; PINHOLE_FULL proj = fx fy cx cy, dist = k1 k2 p1 p2
+    k3 k4 k5 k6; SCARAMUZZA poly p0..p4, inv_poly p0..p19, affine = ac ad ae cx cy.  Fields a model does not use are not read."""
+    _fields_ = [("model", C.c_int32), ("reserved", C.c_int32), ("proj", C.c_double * 4), ("dist", C.c_double * 8), ("xi", C.c_double),
+                ("poly", C.c_double * 5), ("inv_poly", C.c_double * 20), ("affine", C.c_double * 5)]
+
+    @classmethod
+    def make(cls, model, proj=(0.0, 0.0, 0.0, 0.0), dist=(), xi=0.0, poly=(), inv_poly=(), affine=()):
+        """model: CAMERA_* or its camodocal name; dist, poly, inv_poly and affine may be shorter than their fields (the rest is 0)"""
+        m = cls()
+        m.model = CAMERA_NAMES_EX[model] if isinstance(model, str) else int(model)
+        m.proj[:] = [float(v) for v in proj]
+        m.xi = float(xi)
+        for field, vals in ((m.dist, dist), (m.poly, poly), (m.inv_poly, inv_poly), (m.affine, affine)):
+            assert len(vals) <= len(field)
+            for i, v in enumerate(vals):
+                field[i] = float(v)
+        return m
+
+    @classmethod
+    def of(cls, cam):
+        """a CameraModel widened (a CameraModelEx as it is)"""
+        if isinstance(cam, cls):
+            return cam
+        m = cls.make(cam.model, cam.proj, cam.dist, cam.xi)
+        m.reserved = cam.reserved
+        return m
+
+    def as_dict(self):
+        return {"model": self.model, "proj": list(self.proj), "dist": list(self.dist), "xi": self.xi, "poly": list(self.poly), "inv_poly": list(self.inv_poly),
+                "affine": list(self.affine)}
+
+
+assert C.sizeof(CameraModelEx) == 352
+
+
+def _wide(cams):
+    return any(isinstance(c, CameraModelEx) for c in cams)
+
+
+def _camera_array(cams):
+    """(gf_camera_model[n] or, if one of them is a CameraModelEx, gf_camera_model_ex[n]; the suffix of the entry points that take it)"""
+    if _wide(cams):
+        return (CameraModelEx * max(len(cams), 1))(*[CameraModelEx.of(c) for c in cams]), "_ex"
+    return (CameraModel * max(len(cams), 1))(*cams), ""
+
 
 def _camera_batch(cams, counts):
-    """(gf_camera_model[batch], first [batch + 1] int32) of a list of CameraModel and the sequences' point counts"""
-    arr = (CameraModel * len(cams))(*cams)
+    """(camera array, first [batch + 1] int32, entry-point suffix) of a list of CameraModel / CameraModelEx and the sequences' point counts"""
+    arr, ex = _camera_array(cams)
     first = np.zeros(len(cams) + 1, np.int32)
     first[1:] = np.cumsum(counts)
-    return arr, first
+    return arr, first, ex
 
 
 def camera_lift(cams, points, rays=True):
     """gf_camera_lift_batch: liftProjective of cams[b] on points[b] ([n_b, 2] float pixels) through the tracker's kernel -> (un, rays): lists of [n_b, 2] float32
     pairs (float)(P.x / P.z), (float)(P.y / P.z) and of [n_b, 3] float64 rays P (rays=False: None, the kernel writes none)"""
     pts = [np.ascontiguousarray(p, np.float32).reshape(-1, 2) for p in points]
-    arr, first = _camera_batch(cams, [len(p) for p in pts])
+    arr, first, ex = _camera_batch(cams, [len(p) for p in pts])
     uv = np.ascontiguousarray(np.concatenate(pts) if pts else np.zeros((0, 2)), np.float32)
     n = len(uv)
     un = np.zeros((n, 2), np.float32)
     ray = np.zeros((n, 3), np.float64) if rays else None
-    _chk(lib().gf_camera_lift_batch(arr, len(cams), _p(first, C.c_int), _p(uv, C.c_float), _p(ray, C.c_double) if rays else None, _p(un, C.c_float)))
+    _chk(getattr(lib(), "gf_camera_lift_batch" + ex)(arr, len(cams), _p(first, C.c_int), _p(uv, C.c_float), _p(ray, C.c_double) if rays else None, _p(un, C.c_float)))
     cut = lambda a: [a[first[b]:first[b + 1]] for b in range(len(cams))]
     return cut(un), (cut(ray) if rays else None)
 
 
 def camera_lift_device(cams, counts, d_uv, d_rays, d_un, stream=0):
     """gf_camera_lift_batch_device: the same on device arrays (integer addresses; d_rays 0 / None: no rays); cams and the sequences' point counts stay on the host"""
-    arr, first = _camera_batch(cams, counts)
-    _chk(lib().gf_camera_lift_batch_device(arr, len(cams), _p(first, C.c_int), C.c_void_p(d_uv), C.c_void_p(d_rays) if d_rays else None, C.c_void_p(d_un),
-                                           C.c_void_p(stream) if stream else None))
+    arr, first, ex = _camera_batch(cams, counts)
+    _chk(getattr(lib(), "gf_camera_lift_batch_device" + ex)(arr, len(cams), _p(first, C.c_int), C.c_void_p(d_uv), C.c_void_p(d_rays) if d_rays else None, C.c_void_p(d_un),
+                                                            C.c_void_p(stream) if stream else None))
 
 
 def camera_project(cams, xyz):
     """gf_camera_project_batch: spaceToPlane of cams[b] on xyz[b] ([n_b, 3]) on the host -> list of [n_b, 2] float64 pixels"""
     pts = [np.ascontiguousarray(p, np.float64).reshape(-1, 3) for p in xyz]
-    arr, first = _camera_batch(cams, [len(p) for p in pts])
+    arr, first, ex = _camera_batch(cams, [len(p) for p in pts])
     flat = np.ascontiguousarray(np.concatenate(pts) if pts else np.zeros((0, 3)), np.float64)
     uv = np.zeros((len(flat), 2), np.float64)
-    _chk(lib().gf_camera_project_batch(arr, len(cams), _p(first, C.c_int), _p(flat, C.c_double), _p(uv, C.c_double)))
+    _chk(getattr(lib(), "gf_camera_project_batch" + ex)(arr, len(cams), _p(first, C.c_int), _p(flat, C.c_double), _p(uv, C.c_double)))
     return [uv[first[b]:first[b + 1]] for b in range(len(cams))]
 
 
@@ -220,33 +270,35 @@ def _depth_reg_tables(regs, colours, colour_sizes):
     n = len(regs)
     assert len(colours) == n and len(colour_sizes) == n
     wh = np.ascontiguousarray(colour_sizes, np.int32).reshape(n, 2)
-    return (DepthReg * max(n, 1))(*regs), (CameraModel * max(n, 1))(*colours), wh
+    arr, ex = _camera_array(colours)   # a CameraModelEx among them (PINHOLE_FULL colour cameras): the _ex entry points
+    return (DepthReg * max(n, 1))(*regs), arr, wh, ex
 
 
 def depth_register_device(src_refs, regs, colours, colour_sizes, dst_refs, stream=0):
-    """gf_depth_register_batch_device: entry b's raw depth frame src_refs[b] = (device address, pitch) registered by regs[b] (DepthReg) to the PINHOLE colours[b]
-    (CameraModel) of colour_sizes[b] = (width, height) into dst_refs[b], which is written; two launches on `stream` whatever the batch, returns when they have run"""
-    r, c, wh = _depth_reg_tables(regs, colours, colour_sizes)
+    """gf_depth_register_batch_device: entry b's raw depth frame src_refs[b] = (device address, pitch) registered by regs[b] (DepthReg) to the colour camera colours[b]
+    (a PINHOLE CameraModel, or a PINHOLE / PINHOLE_FULL CameraModelEx: one such entry takes the call to the _ex entry point) of colour_sizes[b] = (width, height) into dst_refs[b], which is written; two launches on `stream` whatever the batch, returns when they have run"""
+    r, c, wh, ex = _depth_reg_tables(regs, colours, colour_sizes)
     assert len(src_refs) == len(regs) and len(dst_refs) == len(regs)
-    _chk(lib().gf_depth_register_batch_device(frame_refs(src_refs), r, c, _p(wh, C.c_int), frame_refs(dst_refs), len(regs), C.c_void_p(stream) if stream else None))
+    _chk(getattr(lib(), "gf_depth_register_batch_device" + ex)(frame_refs(src_refs), r, c, _p(wh, C.c_int), frame_refs(dst_refs), len(regs), C.c_void_p(stream) if stream else None))
 
 
 def depth_register(depths, regs, colours, colour_sizes):
-    """gf_depth_register_batch: depths[b] ([height, width] u16, rows may be padded) registered by regs[b] to the PINHOLE colours[b] of colour_sizes[b] =
+    """gf_depth_register_batch: depths[b] ([height, width] u16, rows may be padded) registered by regs[b] to the PINHOLE or (CameraModelEx) PINHOLE_FULL colours[b] of colour_sizes[b] =
     (width, height), staged through device memory -> list of [height, width] u16 frames of the colour sizes"""
-    r, c, wh = _depth_reg_tables(regs, colours, colour_sizes)
+    r, c, wh, ex = _depth_reg_tables(regs, colours, colour_sizes)
     src = [d if (d.dtype == np.uint16 and d.ndim == 2 and d.strides[1] == 2 and d.strides[0] >= 2 * d.shape[1]) else np.ascontiguousarray(d, np.uint16) for d in depths]
     assert all(s.shape == (g.height, g.width) for s, g in zip(src, regs)), "a depth frame is not [height, width] of its registration"
     out = [np.zeros((int(h), int(w)), np.uint16) for w, h in wh]
-    _chk(lib().gf_depth_register_batch(frame_refs([(s.ctypes.data, s.strides[0]) for s in src]), r, c, _p(wh, C.c_int),
-                                       frame_refs([(o.ctypes.data, o.strides[0]) for o in out]), len(regs)))
+    _chk(getattr(lib(), "gf_depth_register_batch" + ex)(frame_refs([(s.ctypes.data, s.strides[0]) for s in src]), r, c, _p(wh, C.c_int),
+                                                        frame_refs([(o.ctypes.data, o.strides[0]) for o in out]), len(regs)))
     return out
 
 
-def camera_from_yaml(calib_file):
-    """gf_camera_from_yaml: a camodocal calibration file (PINHOLE, MEI, KANNALA_BRANDT) -> CameraModel"""
-    m = CameraModel()
-    _chk(lib().gf_camera_from_yaml(os.fsencode(calib_file), C.byref(m)))
+def camera_from_yaml(calib_file, cls=CameraModel):
+    """gf_camera_from_yaml: a camodocal calibration file (PINHOLE, MEI, KANNALA_BRANDT) -> CameraModel; cls=CameraModelEx: gf_camera_from_yaml_ex, which also
+    takes PINHOLE_FULL and SCARAMUZZA files -> CameraModelEx"""
+    m = cls()
+    _chk((lib().gf_camera_from_yaml_ex if cls is CameraModelEx else lib().gf_camera_from_yaml)(os.fsencode(calib_file), C.byref(m)))
     return m
 
 
@@ -266,6 +318,8 @@ EXPORTS = ["gf_last_error", "gf_device_count", "gf_set_device", "gf_tracker_crea
            "gf_tracker_set_seq_format", "gf_tracker_get_seq_format", "gf_cvt_gray_mixed", "gf_cvt_gray_mixed_device",
            "gf_tracker_set_seq_camera", "gf_tracker_get_seq_camera", "gf_camera_lift_batch", "gf_camera_lift_batch_device", "gf_camera_project_batch",
            "gf_camera_from_yaml", "gf_estimator_cfg_from_yaml_camera", "gf_estimator_set_camera",
+           "gf_tracker_set_seq_camera_ex", "gf_tracker_get_seq_camera_ex", "gf_camera_lift_batch_ex", "gf_camera_lift_batch_device_ex", "gf_camera_project_batch_ex",
+           "gf_camera_from_yaml_ex", "gf_estimator_cfg_from_yaml_camera_ex", "gf_estimator_set_camera_ex", "gf_depth_register_batch_ex", "gf_depth_register_batch_device_ex", "gf_tracker_get_camera_lift_stats",
            "gf_tracker_set_seq_size", "gf_tracker_get_seq_size",
            "gf_tracker_set_seq_depth_reg", "gf_tracker_get_seq_depth_reg", "gf_tracker_get_depth_reg_stats", "gf_depth_register_batch", "gf_depth_register_batch_device"]
 MAX_SEQ_SIZES = 8   # GF_MAX_SEQ_SIZES
@@ -605,12 +659,13 @@ class FeatureTracker:
     def set_seq_camera(self, seq, camera):
         """gf_tracker_set_seq_camera: sequence `seq` gets the camera `camera` (CameraModel): its lift and its projection are that model's.  Refused (GfError) once
         the sequence has taken a frame, until reset_seq, and while a prefetched frame lists it."""
-        _chk(lib().gf_tracker_set_seq_camera(self.h, seq, C.byref(camera)))
+        _chk((lib().gf_tracker_set_seq_camera_ex if isinstance(camera, CameraModelEx) else lib().gf_tracker_set_seq_camera)(self.h, seq, C.byref(camera)))
 
-    def get_seq_camera(self, seq):
-        """gf_tracker_get_seq_camera: the camera in force for sequence `seq` (the pinhole of its parameters ahead of any setter)"""
-        m = CameraModel()
-        _chk(lib().gf_tracker_get_seq_camera(self.h, seq, C.byref(m)))
+    def get_seq_camera(self, seq, cls=CameraModel):
+        """gf_tracker_get_seq_camera: the camera in force for sequence `seq` (the pinhole of its parameters ahead of any setter); cls=CameraModelEx:
+        gf_tracker_get_seq_camera_ex, which alone can hand back a PINHOLE_FULL or SCARAMUZZA camera"""
+        m = cls()
+        _chk((lib().gf_tracker_get_seq_camera_ex if cls is CameraModelEx else lib().gf_tracker_get_seq_camera)(self.h, seq, C.byref(m)))
         return m
 
     def set_seq_depth_reg(self, seq, reg):
@@ -625,6 +680,12 @@ class FeatureTracker:
         r, has = DepthReg(), C.c_int(0)
         _chk(lib().gf_tracker_get_seq_depth_reg(self.h, int(seq), C.byref(r), C.byref(has)))
         return r if has.value else None
+
+    def camera_lift_stats(self):
+        """gf_tracker_get_camera_lift_stats: dict of launches of camera_lift_kernel by this handle and of the listed sequences they lifted"""
+        n, q = C.c_longlong(0), C.c_longlong(0)
+        _chk(lib().gf_tracker_get_camera_lift_stats(self.h, C.byref(n), C.byref(q)))
+        return {"launches": n.value, "sequences": q.value}
 
     def depth_reg_stats(self):
         """gf_tracker_get_depth_reg_stats: dict of launches (two per call that registered a frame), frames, kernel_ms (hipEvent time of the two kernels, summed)"""
@@ -1432,8 +1493,8 @@ class SlidingWindowEstimator:
         _chk(lib().gf_estimator_set_boxes(self.h, b.ctypes.data_as(C.POINTER(Box)) if len(b) else None, len(b)))
 
     def set_camera(self, camera):
-        """gf_estimator_set_camera: the camera (CameraModel) of the estimator's own tracker, before its first image"""
-        _chk(lib().gf_estimator_set_camera(self.h, C.byref(camera)))
+        """gf_estimator_set_camera / _ex: the camera (CameraModel or CameraModelEx) of the estimator's own tracker, before its first image"""
+        _chk((lib().gf_estimator_set_camera_ex if isinstance(camera, CameraModelEx) else lib().gf_estimator_set_camera)(self.h, C.byref(camera)))
 
     def set_show_track(self, on=True):
         """gf_estimator_set_show_track: SHOW_TRACK of the estimator's own tracker"""
@@ -1525,6 +1586,13 @@ def estimator_cfg_from_yaml(config_file):
     c = EstimatorCfg()
     _chk(lib().gf_estimator_cfg_from_yaml(os.fsencode(config_file), C.byref(c)))
     return c
+
+
+def estimator_cfg_from_yaml_camera_ex(config_file):
+    """gf_estimator_cfg_from_yaml_camera_ex: the same with a cam0_calib file of any of the five models -> (EstimatorCfg, CameraModelEx for set_camera)"""
+    c, m = EstimatorCfg(), CameraModelEx()
+    _chk(lib().gf_estimator_cfg_from_yaml_camera_ex(os.fsencode(config_file), C.byref(c), C.byref(m)))
+    return c, m
 
 
 def estimator_cfg_from_yaml_camera(config_file):

@@ -74,14 +74,14 @@ class Estimator {
     void setParameter() {                          // estimator.cpp:176-211: (re)create with the current cfg
         if (h_) { gf_estimator_destroy(h_); h_ = nullptr; }
         check(gf_estimator_create(&cfg, &h_));
-        if (cfg.with_tracker && camera.model != GF_CAMERA_PINHOLE) check(gf_estimator_set_camera(h_, &camera));   // readIntrinsicParameter, estimator.cpp:200-201
+        if (cfg.with_tracker && camera.model != GF_CAMERA_PINHOLE) check(gf_estimator_set_camera_ex(h_, &camera));   // readIntrinsicParameter, estimator.cpp:200-201
         refresh();
     }
     void clearState() { setParameter(); }          // estimator.cpp:51-174
     // readParameters(config_file) (parameters.cpp:138-558) fills cfg, tracker part included; call setParameter() afterwards as main() does
-    // the cam0_calib file may hold a PINHOLE, MEI or KANNALA_BRANDT camera (gf_estimator_cfg_from_yaml_camera); setParameter() gives it to the tracker
-    void readParameters(const std::string& config_file) { check(gf_estimator_cfg_from_yaml_camera(config_file.c_str(), &cfg, &camera)); }
-    gf_camera_model camera{};                      // m_camera of the estimator's own tracker where it is no pinhole (a pinhole is cfg.tracker's eight fields)
+    // the cam0_calib file may hold any of camodocal's five camera models (gf_estimator_cfg_from_yaml_camera_ex); setParameter() gives it to the tracker
+    void readParameters(const std::string& config_file) { check(gf_estimator_cfg_from_yaml_camera_ex(config_file.c_str(), &cfg, &camera)); }
+    gf_camera_model_ex camera{};                    // m_camera of the estimator's own tracker where it is no pinhole (a pinhole is cfg.tracker's eight fields)
     // VINS_RESULT_PATH: pubOdometry's trajectory file (visualization.cpp:346-357), written by the library after every processed frame
     void setResultPath(const std::string& vio_txt) { need(); check(gf_estimator_set_result_path(h_, vio_txt.c_str())); }
 

@@ -63,12 +63,12 @@ class FeatureTracker {
     FeatureTracker(const FeatureTracker&) = delete;
     FeatureTracker& operator=(const FeatureTracker&) = delete;
 
-    // a camodocal calibration file as CameraFactory::generateCameraFromYamlFile takes it (feature_tracker.cpp:745-759): PINHOLE, MEI or KANNALA_BRANDT
-    // (gf_camera_from_yaml; PINHOLE_FULL and SCARAMUZZA are refused by name); `depth` = depth camera flag
+    // a camodocal calibration file as CameraFactory::generateCameraFromYamlFile takes it (feature_tracker.cpp:745-759): any of its five models
+    // (gf_camera_from_yaml_ex); `depth` = depth camera flag
     void readIntrinsicParameter(const std::vector<std::string>& calib_file, const int depth) {
         if (calib_file.empty()) throw std::runtime_error("readIntrinsicParameter: no calibration file");
         if (h_) throw std::runtime_error("readIntrinsicParameter: call it before the first trackImage");
-        check(gf_camera_from_yaml(calib_file[0].c_str(), &camera_));
+        check(gf_camera_from_yaml_ex(calib_file[0].c_str(), &camera_));
         std::ifstream f(calib_file[0]);   // image_width / image_height are no part of a camera model
         std::string line;
         while (std::getline(f, line)) {
@@ -80,6 +80,7 @@ class FeatureTracker {
             if (key == "image_width:") col = (int)v; else if (key == "image_height:") row = (int)v;
         }
         fx_ = camera_.proj[0]; fy_ = camera_.proj[1]; cx_ = camera_.proj[2]; cy_ = camera_.proj[3];
+        if (camera_.model == GF_CAMERA_SCARAMUZZA) { fx_ = fy_ = 1.0; cx_ = camera_.affine[3]; cy_ = camera_.affine[4]; }   // no focal length: a valid placeholder
         const bool pin = camera_.model == GF_CAMERA_PINHOLE;   // another model: the handle's own pinhole is a valid placeholder that nothing reads
         k1_ = pin ? camera_.dist[0] : 0; k2_ = pin ? camera_.dist[1] : 0; p1_ = pin ? camera_.dist[2] : 0; p2_ = pin ? camera_.dist[3] : 0;
         depth_cam = depth != 0;
@@ -87,7 +88,7 @@ class FeatureTracker {
     }
     void setIntrinsics(int width, int height, double fx, double fy, double cx, double cy, double k1 = 0, double k2 = 0, double p1 = 0, double p2 = 0) {
         col = width; row = height; fx_ = fx; fy_ = fy; cx_ = cx; cy_ = cy; k1_ = k1; k2_ = k2; p1_ = p1; p2_ = p2;
-        camera_ = gf_camera_model{};
+        camera_ = gf_camera_model_ex{};
     }
     // EQUALIZE (rosNodeTest.cpp:256-261): the reference's node runs cv::createCLAHE()->apply on every frame before trackImage; the FeatureTracker class itself
     // never does, so it stays off unless asked for.  On: the same CLAHE (clip 40, 8 x 8 tiles) runs on the device ahead of the pyramid.  Before the first frame.
@@ -236,7 +237,7 @@ class FeatureTracker {
   private:
     gf_tracker* h_ = nullptr;
     double fx_ = 1, fy_ = 1, cx_ = 0, cy_ = 0, k1_ = 0, k2_ = 0, p1_ = 0, p2_ = 0;
-    gf_camera_model camera_{};   // readIntrinsicParameter's model; GF_CAMERA_PINHOLE (also by default): the eight numbers above
+    gf_camera_model_ex camera_{};   // readIntrinsicParameter's model; GF_CAMERA_PINHOLE (also by default): the eight numbers above
     bool equalize_ = false, show_track_ = false;
     int pixel_format_ = GF_PIX_MONO8;
     std::vector<uint8_t> roi_;   // a region of interest set before the handle exists (tight rows)
@@ -251,7 +252,7 @@ class FeatureTracker {
         c.pixel_format = pixel_format_;
         row = c.height; col = c.width;
         check(gf_tracker_create(&c, &h_));
-        if (camera_.model != GF_CAMERA_PINHOLE) check(gf_tracker_set_seq_camera(h_, 0, &camera_));
+        if (camera_.model != GF_CAMERA_PINHOLE) check(gf_tracker_set_seq_camera_ex(h_, 0, &camera_));
         if (!roi_.empty()) { check(gf_tracker_set_roi(h_, 0, roi_.data(), col)); roi_.clear(); }
         if (!boxes_.empty()) { const std::vector<gf_box> b = std::move(boxes_); boxes_.clear(); setBoxes(b.data(), (int)b.size()); }
         if (show_track_) setShowTrack(true);

@@ -322,7 +322,7 @@ int gf_tracker_set_seq_size(gf_tracker* h, int seq, int width, int height);
 /* feature_tracker.cpp:108-109 per sequence: the size in force for seq (the handle's for a sequence that was never set) */
 int gf_tracker_get_seq_size(gf_tracker* h, int seq, int* width, int* height);
 /* A camera model per sequence: what FeatureTracker::readIntrinsicParameter (feature_tracker.cpp:745-759) gets from CameraFactory::generateCameraFromYamlFile --
- * camodocal's PINHOLE (PinholeCamera), MEI (CataCamera) or KANNALA_BRANDT (EquidistantCamera); PINHOLE_FULL and SCARAMUZZA are not built.  liftProjective
+ * camodocal's PINHOLE (PinholeCamera), MEI (CataCamera) or KANNALA_BRANDT (EquidistantCamera); PINHOLE_FULL and SCARAMUZZA need the wide struct gf_camera_model_ex below.  liftProjective
  * (undistortedPts, feature_tracker.cpp:797-808) and spaceToPlane (setPrediction, :1006-1027) of the sequence then are that model's: PinholeCamera.cc:450-542,
  * CataCamera.cc:556-659, EquidistantCamera.cc:428-461 with backprojectSymmetric (:716-818), in double precision (csrc/gf_camera_models.hpp; DESIGN.md
  * section 4, "Camera models").  Pixel coordinates, ids, track counts and depths do not depend on the model.
@@ -363,8 +363,49 @@ int gf_camera_lift_batch_device(const gf_camera_model* cams, int batch, const in
 int gf_camera_project_batch(const gf_camera_model* cams, int batch, const int* first, const double* xyz, double* uv);
 /* A camodocal calibration file (CameraFactory::generateCameraFromYamlFile, CameraFactory.cc; keys as PinholeCamera.cc:145-183, CataCamera.cc:160-202,
  * EquidistantCamera.cc:146-182): model_type (missing: PINHOLE), projection_parameters, distortion_parameters, mirror_parameters.xi.  A missing numeric key reads
- * as 0 like every cv::FileNode, so a missing focal parameter is refused by name; PINHOLE_FULL and SCARAMUZZA are refused by name. */
+ * as 0 like every cv::FileNode, so a missing focal parameter is refused by name; PINHOLE_FULL and SCARAMUZZA are refused by name, pointing at gf_camera_from_yaml_ex. */
 int gf_camera_from_yaml(const char* calib_file, gf_camera_model* out);
+/* All five camodocal models: the three above and PINHOLE_FULL (PinholeFullCamera: OpenCV's rational model k1..k6, p1, p2 -- the only one that holds a calibration
+ * with a k3 or the 8-coefficient factory calibration of a Kinect-class camera) and SCARAMUZZA (OCAMCamera, OCamCalib), which the 80-byte struct cannot carry.
+ * liftProjective and spaceToPlane: PinholeFullCamera.cc:535-607, :623-645 with :754-780; ScaramuzzaCamera.cc:599-622, :632-655 (csrc/gf_camera_models.hpp).
+ *   PINHOLE_FULL  liftProjective is the reference's loop as it runs: nine passes, no error test (its test can never end the loop) -- the ninth iterate, not the
+ *                 true inverse.
+ *   SCARAMUZZA    the reference's arithmetic with its quirks: the ray is (xc, -z) of the uncorrected xc with z a polynomial in the norm of the affine-corrected
+ *                 xc; a ray on the axis projects to a non-finite pixel.
+ * Fields a model does not use are not read.  Refused (GF_ERR_INVALID, the message naming the field): reserved != 0, a model outside 0 .. 4, a value that is read
+ * and is not finite, PINHOLE_FULL with fx or fy <= 0, SCARAMUZZA with ac - ad * ae == 0 (the reference divides by it), and for models 0-2 what gf_camera_model
+ * is refused for.  The calls below behave like the ones without _ex for models 0-2, bit for bit; those keep refusing models 3 and 4. */
+enum { GF_CAMERA_PINHOLE_FULL = 3, GF_CAMERA_SCARAMUZZA = 4 };   /* valid in gf_camera_model_ex only */
+typedef struct gf_camera_model_ex {
+    int32_t model, reserved;      /* reserved 0 */
+    double proj[4];               /* as gf_camera_model | PINHOLE_FULL fx fy cx cy | SCARAMUZZA: not read */
+    double dist[8];               /* models 0-2: the first four as gf_camera_model | PINHOLE_FULL k1 k2 p1 p2 k3 k4 k5 k6 */
+    double xi;                    /* MEI only */
+    double poly[5];               /* SCARAMUZZA poly_parameters p0..p4 */
+    double inv_poly[20];          /* SCARAMUZZA inv_poly_parameters p0..p19 */
+    double affine[5];             /* SCARAMUZZA affine_parameters ac ad ae cx cy */
+} gf_camera_model_ex;
+typedef char gf_camera_model_ex_is_352_bytes[sizeof(gf_camera_model_ex) == 352 ? 1 : -1];
+/* gf_tracker_set_seq_camera for any of the five models.  PINHOLE_FULL sequences are lifted by the same one launch per call as MEI and KANNALA_BRANDT ones,
+ * and so are SCARAMUZZA sequences under GF_CAMERA_LIFT_HOST=0; by default those are lifted on the host (gf_tracker_get_camera_lift_stats below). */
+int gf_tracker_set_seq_camera_ex(gf_tracker* h, int seq, const gf_camera_model_ex* cam);
+/* gf_tracker_get_seq_camera for any model; gf_tracker_get_seq_camera itself refuses a sequence whose camera is PINHOLE_FULL or SCARAMUZZA by name */
+int gf_tracker_get_seq_camera_ex(gf_tracker* h, int seq, gf_camera_model_ex* out);
+/* Where the lift runs, per model, by what was measured (profiles/camera_wide_measure.json): MEI, KANNALA_BRANDT and PINHOLE_FULL sequences on the device,
+ * SCARAMUZZA sequences -- a fifth-degree polynomial per point -- on the host, like PINHOLE ones.  GF_CAMERA_LIFT_HOST (read by gf_tracker_create) overrides it
+ * for every model: 1 all on the host, 0 all on the device.  A sequence lifted on the host is not listed for the kernel; a call lists either some sequence
+ * and has ONE launch of camera_lift_kernel, whatever the mix of models, or none and has no launch.
+ * The lift's own counters (gf_tracker_stats keeps its layout), each may be NULL: launches of camera_lift_kernel by this handle, and listed sequences those
+ * launches lifted, summed.  gf_tracker_reset_stats zeroes them. */
+int gf_tracker_get_camera_lift_stats(gf_tracker* h, long long* launches, long long* sequences);
+/* gf_camera_lift_batch, gf_camera_lift_batch_device and gf_camera_project_batch with cameras of any of the five models */
+int gf_camera_lift_batch_ex(const gf_camera_model_ex* cams, int batch, const int* first, const float* uv, double* rays, float* un);
+int gf_camera_lift_batch_device_ex(const gf_camera_model_ex* cams, int batch, const int* first, const float* d_uv, double* d_rays, float* d_un, void* stream);
+int gf_camera_project_batch_ex(const gf_camera_model_ex* cams, int batch, const int* first, const double* xyz, double* uv);
+/* gf_camera_from_yaml for all five models; model_type is compared without regard to case as CameraFactory.cc:111-129 does.  PINHOLE_FULL keys as
+ * PinholeFullCamera.cc:209-249 (distortion_parameters k1..k6 p1 p2, projection_parameters fx fy cx cy; a missing fx or fy is refused by name), SCARAMUZZA keys
+ * as ScaramuzzaCamera.cc:64-105 (poly_parameters p0..p4, inv_poly_parameters p0..p19, affine_parameters ac ad ae cx cy). */
+int gf_camera_from_yaml_ex(const char* calib_file, gf_camera_model_ex* out);
 /* Depth registration: the raw frame of a depth camera brought to the colour camera on the device -- what the camera driver's `align` filter does on the host for
  * /camera/aligned_depth_to_color/image_raw, the topic every shipped configuration subscribes to (config/realsense/m2dgrp.yaml:23), as a definition of this
  * repository (csrc/gf_depth_reg.hpp; DESIGN.md section 4, "Depth registration").  width x height u16 counts of `scale` metres each, seen through the undistorted
@@ -374,8 +415,8 @@ int gf_camera_from_yaml(const char* calib_file, gf_camera_model* out);
  * measurement) if none does.  The identity registration (same size and intrinsics, R = I, T = 0, scale = 0.001) returns its input.  A count of 0, a point not in
  * front of the colour camera, a coordinate that is not finite and a value outside 1 .. 65535 contribute nothing.
  * Refused wherever a registration is taken (GF_ERR_INVALID, the message naming the field): width or height outside 8 .. 4096, a value that is not finite, fx, fy
- * or scale <= 0, an R with an entry of R R^T - I beyond 1e-6 or with det R <= 0.  Out of scope: a colour camera other than GF_CAMERA_PINHOLE (refused by name), a
- * distorted depth stream, depth in floating point. */
+ * or scale <= 0, an R with an entry of R R^T - I beyond 1e-6 or with det R <= 0.  Out of scope: a colour camera other than GF_CAMERA_PINHOLE or, through the _ex calls and
+ * gf_tracker_set_seq_camera_ex, GF_CAMERA_PINHOLE_FULL (refused by name), a distorted depth stream, depth in floating point. */
 typedef struct gf_depth_reg {
     int32_t width, height;   /* of the raw depth frame */
     double fx, fy, cx, cy;   /* the depth stream's pinhole (depth streams are rectified) */
@@ -393,17 +434,23 @@ int gf_depth_register_batch_device(const gf_frame_ref* d_src, const gf_depth_reg
                                    const gf_frame_ref* d_dst, int batch, void* stream);
 /* The same on host frames by pointer and pitch (copies in, the two launches, copies out; synchronous): for tests and callers without device frames */
 int gf_depth_register_batch(const gf_frame_ref* src, const gf_depth_reg* reg, const gf_camera_model* colour, const int* colour_wh, const gf_frame_ref* dst, int batch);
+/* The two calls above with colour cameras that are GF_CAMERA_PINHOLE or GF_CAMERA_PINHOLE_FULL (every other model is refused by name).  For a PINHOLE_FULL entry
+ * the projection is the tail of that model's spaceToPlane (PinholeFullCamera.cc:630-644 with :754-780) in the place of the pinhole's; footprints, the 8-pixel
+ * bound, the z-buffer and the second kernel are the same.  Still two launches whatever the mix; PINHOLE entries come out as from the calls above, byte for byte. */
+int gf_depth_register_batch_device_ex(const gf_frame_ref* d_src, const gf_depth_reg* reg, const gf_camera_model_ex* colour, const int* colour_wh,
+                                      const gf_frame_ref* d_dst, int batch, void* stream);
+int gf_depth_register_batch_ex(const gf_frame_ref* src, const gf_depth_reg* reg, const gf_camera_model_ex* colour, const int* colour_wh, const gf_frame_ref* dst, int batch);
 /* The registration of seq; reg == NULL clears it.  With one set, the `depth` entry of the sequence on gf_tracker_track_some_device_refs / _track_batch_device_refs
  * is the RAW frame of the depth camera -- reg->height rows of reg->width counts, pointer and pitch even, pitch >= 2 x reg->width; a call that breaks this is
- * refused naming the list position -- and the call registers it to the sequence's colour camera (the PINHOLE of its gf_tracker_seq_cfg, at its frame size in
- * force) into a frame of the handle before anything samples depth: two launches per call for all such sequences, whatever their number and sizes.  LK and the
+ * refused naming the list position -- and the call registers it to the sequence's colour camera (the PINHOLE of its gf_tracker_seq_cfg, or the PINHOLE_FULL
+ * camera gf_tracker_set_seq_camera_ex gave it, at its frame size in force) into a frame of the handle before anything samples depth: two launches per call for all such sequences, whatever their number and sizes.  LK and the
  * corner selection then sample that frame, so the call's results are those of the same call on frames registered beforehand by gf_depth_register_batch_device.
  * A sequence whose depth_cam is 0 may carry a registration; it is never run.  Every other entry point (host images, tight device lists, prefetch) refuses a
  * call with depth that lists such a sequence (GF_ERR_INVALID, the message naming the entry point and the sequence, nothing changed): host images would put the
  * raw frame on the bus.  Without depth, and for lists without such a sequence, they behave as before.
  * A setting like gf_tracker_set_seq_size: refused once the sequence has taken a frame (until gf_tracker_reset_seq, which keeps it), while a frame staged by
- * gf_tracker_prefetch_* lists it, and while the sequence's camera is not GF_CAMERA_PINHOLE (gf_tracker_set_seq_camera; that setter in turn refuses another model
- * while a registration is set).  The first setter of a handle allocates the registered frames and the z-buffer at the handle's capacity (cfg.width x cfg.height
+ * gf_tracker_prefetch_* lists it, and while the sequence's camera is neither GF_CAMERA_PINHOLE nor GF_CAMERA_PINHOLE_FULL (gf_tracker_set_seq_camera / _ex; those
+ * setters in turn refuse another model while a registration is set).  The first setter of a handle allocates the registered frames and the z-buffer at the handle's capacity (cfg.width x cfg.height
  * per sequence) and the call's table; GF_ERR_HIP and nothing changed if that fails.  A handle on which it is never called allocates, copies and launches
  * exactly what it did without it. */
 int gf_tracker_set_seq_depth_reg(gf_tracker* h, int seq, const gf_depth_reg* reg);
@@ -912,6 +959,10 @@ int gf_estimator_cfg_from_yaml_camera(const char* config_file, gf_estimator_cfg*
 /* readIntrinsicParameter (feature_tracker.cpp:745-759) of an estimator that owns its tracker: gf_tracker_set_seq_camera on that tracker's one sequence, before
  * the first gf_estimator_input_image.  GF_ERR_INVALID without a tracker, and as that call refuses. */
 int gf_estimator_set_camera(gf_estimator* h, const gf_camera_model* camera);
+/* The two calls above for all five models (gf_camera_from_yaml_ex, gf_tracker_set_seq_camera_ex).  The placeholders of cfg->tracker for a PINHOLE_FULL file are
+ * its fx fy cx cy; a SCARAMUZZA camera has no focal length: fx = fy = 1 and the centre of its affine parameters. */
+int gf_estimator_cfg_from_yaml_camera_ex(const char* config_file, gf_estimator_cfg* cfg, gf_camera_model_ex* camera);
+int gf_estimator_set_camera_ex(gf_estimator* h, const gf_camera_model_ex* camera);
 /* show_track (SHOW_TRACK, parameters.cpp:202; what makes the node publish getTrackImage, feature_tracker.cpp:849-905 / :1047) of the same file with the same
  * reader; a missing key reads as 0.  gf_estimator_cfg does not carry it: a caller that wants the pictures turns them on (gf_estimator_set_show_track). */
 int gf_show_track_from_yaml(const char* config_file, int* show_track);
