@@ -1980,6 +1980,11 @@ int gf_estimator_set_show_track(gf_estimator* e, int on) {
     const int seq = 0;
     return gf_tracker_set_show_track(e->tracker, 1, &seq, on);
 }
+// rejectWithF (feature_tracker.cpp:711-743) of the estimator's own tracker, on its one sequence: from the next gf_estimator_input_image on; NULL turns it off
+int gf_estimator_set_reject_f(gf_estimator* e, const gf_reject_f_cfg* c) {
+    if (!e || !e->tracker) return gf::set_err(GF_ERR_INVALID, "estimator was created without a tracker (cfg.with_tracker)");
+    return gf_tracker_set_seq_reject_f(e->tracker, 0, c);
+}
 int gf_estimator_get_track_image(gf_estimator* e, uint8_t* dst, int stride) {
     if (!e || !e->tracker) return gf::set_err(GF_ERR_INVALID, "estimator was created without a tracker (cfg.with_tracker)");
     return gf_tracker_track_image(e->tracker, 0, dst, stride);

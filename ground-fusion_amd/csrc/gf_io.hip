@@ -156,6 +156,23 @@ int gf_show_track_from_yaml(const char* config_file, int* show_track) {
     return GF_OK;
 }
 
+// rejectWithF (feature_tracker.cpp:711-743) from a config file: F_threshold (F_THRESHOLD, parameters.cpp:201) and this repository's own switch `reject_with_f`
+// (the reference has none: its call is commented out), a missing key reading as 0 like every cv::FileNode.  A file that turns the switch on without a usable
+// F_threshold is refused by the key's name.
+int gf_reject_f_from_yaml(const char* config_file, gf_reject_f_cfg* out) {
+    if (!config_file || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    YamlDoc y;
+    std::string err;
+    if (!parse_yaml(config_file, y, err)) return gf::set_err(GF_ERR_INVALID, "%s: %s", config_file, err.c_str());
+    gf_reject_f_cfg c{};
+    c.enable = y.integer("reject_with_f") != 0 ? 1 : 0;
+    c.f_threshold = y.real("F_threshold");
+    if (c.enable && !(c.f_threshold > 0.0 && c.f_threshold - c.f_threshold == 0.0))
+        return gf::set_err(GF_ERR_INVALID, "%s: reject_with_f is on but F_threshold is %g (must be finite and > 0)", config_file, c.f_threshold);
+    *out = c;
+    return GF_OK;
+}
+
 // A camodocal calibration file already parsed (`path` names it in messages): model_type and the keys of the model's readFromYamlFile
 // (PinholeCamera.cc:145-183, CataCamera.cc:160-202, EquidistantCamera.cc:146-182); checked as every setter checks a model (gfcam::prepare).
 static bool iequals(const std::string& a, const char* b) {   // boost::iequals, CameraFactory.cc:111-127

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "gf_camera_models.hpp"
+#include "gf_reject_f.hpp"
 #include "gf_roi.hpp"
 #include "gf_seq_cfg.hpp"
 #include "gf_track_draw.hpp"
@@ -37,6 +38,7 @@ struct SeqState {  // per-sequence FeatureTracker members (feature_tracker.h:76-
     std::vector<int> grid_head, grid_next;  // scratch of set_mask_host
     double cur_time = 0, prev_time = 0;
     int n_id = 0;
+    int frames = 0;   // frames the sequence has taken since gf_tracker_create / gf_tracker_reset_seq, the one in progress included: rejectWithF's draws depend on it
     bool hasPrediction = false;
     bool started = false;   // the sequence has taken a frame since gf_tracker_create / gf_tracker_reset_seq: its parameters are fixed (gf_tracker_set_seq_cfg)
     int slot = 1;   // which of the sequence's two pyramids holds its newest frame; flipped when the sequence takes a frame, and only then (the first frame goes to 0)
@@ -160,6 +162,7 @@ inline void remove_outliers(SeqState& s, const int* ids, int n) {  // feature_tr
 inline int begin_frame(SeqState& s, double t) {
     s.cur_time = t; s.cur_pts.clear(); s.cur_depth.clear(); s.lk_row.clear();
     s.started = true;
+    s.frames++;
     return s.slot ^ 1;
 }
 
@@ -197,14 +200,44 @@ struct LkRows {
 };
 struct LkTally { long long level_passes = 0, iterations = 0, points = 0, tracked = 0; };   // what the sequence adds to gf_tracker_stats
 
+// rejectWithF on the host (feature_tracker.cpp:711-743; gf_reject_f.hpp) for one sequence, at the reference's place: on the points LK kept, ahead of track_cnt++
+// and setMask.  status: the sequence's row of status bytes, rewritten in place as the kernel rewrites it on the device.  ran / result: what the stage left.
+struct RejectFHost {
+    gfcam::Camera cam; uint8_t* status;
+    double f_threshold, focal; uint32_t seed;
+    bool ran; gfrf::Result result;
+};
+// The virtual pixels of row i (:722-729): previous and current point lifted with the sequence's camera
+inline gfrf::Cand virtual_pair(const gfcam::Camera& cam, double focal, int width, int height, P2f prev, P2f cur) {
+    gfrf::Cand c; double P[3];
+    gfcam::lift(cam, (double)cur.x, (double)cur.y, P);
+    c.bx = gfrf::virtual_pixel(focal, P[0], P[2], width); c.by = gfrf::virtual_pixel(focal, P[1], P[2], height);
+    gfcam::lift(cam, (double)prev.x, (double)prev.y, P);
+    c.ax = gfrf::virtual_pixel(focal, P[0], P[2], width); c.ay = gfrf::virtual_pixel(focal, P[1], P[2], height);
+    return c;
+}
+inline void reject_f_host(const SeqState& s, int width, int height, const P2f* cur_row, RejectFHost& rf) {
+    const int n = (int)s.prev_pts.size();
+    rf.ran = false;
+    if (n < gfrf::kSample) return;   // as the device form: no job
+    static thread_local std::vector<gfrf::Cand> pairs, cand;
+    static thread_local std::vector<int> row_of;
+    pairs.resize(n); cand.resize(n); row_of.resize(n);
+    for (int i = 0; i < n; i++) pairs[i] = rf.status[i] ? virtual_pair(rf.cam, rf.focal, width, height, s.prev_pts[i], cur_row[i]) : gfrf::Cand{0.f, 0.f, 0.f, 0.f};
+    rf.result = gfrf::reject(pairs.data(), rf.status, n, rf.f_threshold, rf.seed, cand.data(), row_of.data());
+    rf.ran = true;
+}
+
 // After LK (feature_tracker.cpp:170-186): the reduction by status, track_cnt++, setMask and the number of corners the sequence wants.
 // T: the circle of par.min_dist; roi: the sequence's region of interest or null; centers_row / *n_centers: setMask's kept points for the detector;
 // boxes, n_boxes: the sequence's exclusion boxes, as set_mask_host takes them.  keep_rows: the sequence's pairs come from a lift on the device (after_detect's
-// un_lk): every kept point carries the row of LK's table it came from (SeqState::lk_row).
+// un_lk): every kept point carries the row of LK's table it came from (SeqState::lk_row).  rf: rejectWithF runs here (RejectFHost; null: it is off, or ran on the
+// device and the status bytes arrive already changed).
 inline LkTally after_lk(SeqState& s, const gf_tracker_seq_cfg& par, int width, int height, const DiskTable& T, const uint32_t* roi, const LkRows& r,
-                        P2i* centers_row, int* n_centers, int* want, const gf_box* boxes = nullptr, int n_boxes = 0, bool keep_rows = false) {
+                        P2i* centers_row, int* n_centers, int* want, const gf_box* boxes = nullptr, int n_boxes = 0, bool keep_rows = false, RejectFHost* rf = nullptr) {
     LkTally tally;
     const int n = (int)s.prev_pts.size();
+    if (rf) reject_f_host(s, width, height, r.cur_pts, *rf);   // rf->status is r.status: the reduction below reads what the stage left
     if (n > 0) {
         const uint8_t* st = r.status;
         s.cur_pts.resize(n); s.cur_depth.resize(n);

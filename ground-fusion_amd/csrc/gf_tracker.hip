@@ -37,6 +37,7 @@
 #include "gf_lk_kernels.hpp"
 #include "gf_copy_list.hpp"
 #include "gf_depth_reg_stage.hpp"
+#include "gf_reject_f_stage.hpp"
 #include "gf_frame_ref.hpp"
 #include "gf_host_cpus.hpp"
 #include "gf_hip_own.hpp"
@@ -280,6 +281,16 @@ struct gf_tracker {
     DepthRegStage dreg_stage;
     Event ev_dreg[2];
     long long dreg_launches = 0, dreg_frames = 0; double dreg_ms = 0;
+
+    // rejectWithF per sequence (gf_reject_f.hpp; gf_tracker_set_seq_reject_f), the ninth thing addressed by SEQUENCE.  Everything here is obtained by the first
+    // setter of the handle that turns a sequence's switch on: rf_on[seq] / rf[seq], the configuration as it was set; rf_stage, the table of a call's jobs and of
+    // their results ([B] by job); ev_rf around the kernel of a call's first launch and of its second (a predicted sequence that fell back), read when the stream
+    // is drained.  rf_host (GF_REJECT_F_HOST=1): gfrf::reject inside after_lk instead, no launch.
+    std::vector<uint8_t> rf_on; std::vector<gf_reject_f_cfg> rf;
+    RejectFStage rf_stage;
+    Event ev_rf[4];
+    bool rf_host = false;
+    gf_reject_f_stats rf_stats{};
 
     std::unique_ptr<HostPool> pool;
 };
@@ -753,6 +764,9 @@ struct Call {
     bool sized = false;                   // a listed sequence has a frame size that is not the handle's: the call goes through h->size_plan and the sized forms
     bool size_of_down = false;            // the bytes that name each position's size are still wanted on the device: with the first copy list that leaves
     const uint8_t* sub = nullptr;         // the compact per-size tables (SizeSub) where the front's launches read them: h_size_sub over the bus, or d_size_sub
+    std::vector<int> rf_pos;              // list positions of the jobs of the call's launch of reject_f_kernel, in job order (launch_reject_f)
+    std::vector<gfrf::Result> rf_res;     // by list position: what rejectWithF left for the sequence (winner -2: it did not run)
+    int rf_launches = 0;                  // launches of reject_f_kernel in this call: 0, 1, or 2 when a predicted sequence fell back
     int n_reg = 0;                        // listed sequences whose raw depth frame this call registers (publish fills their jobs, launch_depth_reg runs them)
     void lap(double& acc) { const auto n = std::chrono::steady_clock::now(); acc += std::chrono::duration<double, std::milli>(n - tp).count(); tp = n; }
     void add_refs() {
@@ -966,6 +980,47 @@ static int launch_depth_reg(Call& c) {
     return GF_OK;
 }
 
+// rejectWithF (feature_tracker.cpp:711-743; gf_reject_f.hpp) of the listed sequences whose switch is on, in ONE launch behind LK on the tracking stream: the kernel
+// rewrites the status bytes LK left on the device before they come up, so the host reads what it was going to read anyway.  only (may be null): by list position,
+// the sequences of the launch (the second one of a call: those that fell back to the three-level LK).  A sequence with fewer than 8 points has no job: nothing
+// would happen to it.
+static bool seq_rejects(const gf_tracker* h, int q) { return !h->rf_on.empty() && h->rf_on[q]; }
+static gfcam::Camera reject_f_camera(const gf_tracker* h, int q) {   // the camera the sequence is lifted with: its own, or the pinhole of its parameters
+    if (!h->cam_on.empty() && h->cam_on[q]) return h->cam[q];
+    gfcam::Camera cam{}; char msg[320];
+    (void)gfcam::prepare(gfcam::pinhole_of(h->par[q]), cam, msg, sizeof msg);   // checked when the parameters were set
+    return cam;
+}
+static int launch_reject_f(Call& c, const uint8_t* only) {
+    gf_tracker* h = c.h;
+    if (h->rf_on.empty() || h->rf_host) return GF_OK;
+    const int cap = h->cap;
+    c.rf_pos.clear();
+    for (int i = 0; i < c.N; i++) {
+        const int q = c.seq[i], n = h->h_npts.p[i];
+        if (!h->rf_on[q] || n < gfrf::kSample || (only && !only[i])) continue;
+        const gfcam::Camera cam = reject_f_camera(h, q);
+        const gf_reject_f_cfg& f = h->rf[q];
+        reject_f_job(h->rf_stage, (int)c.rf_pos.size(), &cam, h->d_prev_pts.p + (size_t)i * cap, h->d_cur_pts.p + (size_t)i * cap, nullptr, h->d_status.p + (size_t)i * cap, n,
+                     seq_width(h, q), seq_height(h, q), f.f_threshold, f.focal_length == 0.0 ? gfrf::kFocal : f.focal_length,
+                     gfrf::frame_seed(f.seed, (uint32_t)h->seq[q].frames));
+        c.rf_pos.push_back(i);
+    }
+    if (c.rf_pos.empty()) return GF_OK;
+    const int k = 2 * c.rf_launches;
+    if (int rc = reject_f_launch(h->rf_stage, (int)c.rf_pos.size(), h->stream, h->ev_rf[k], h->ev_rf[k + 1])) return rc;
+    c.rf_launches++;
+    h->rf_stats.launches++;
+    return GF_OK;
+}
+// the results of the launch, once the host has waited for the stream
+static void collect_reject_f(Call& c) {
+    if (c.rf_pos.empty()) return;
+    if (c.rf_res.empty()) c.rf_res.assign(c.N, gfrf::Result{0, 0, -2, 0});
+    for (size_t k = 0; k < c.rf_pos.size(); k++) c.rf_res[c.rf_pos[k]] = c.h->rf_stage.h_res.p[k];
+    c.rf_pos.clear();
+}
+
 // Temporal optical flow (feature_tracker.cpp:113-176): the sequences without a prediction in one launch from scratch, those with one in a second from their
 // predictions.  Returns when LK's tables are on the host.
 static int run_lk(Call& c) {
@@ -998,6 +1053,7 @@ static int run_lk(Call& c) {
         if (c.any_pred) { launch_lk(h, N, lk_args(h, 1, 1, h->cfg.flow_back, 1, mask_pred, c.kdepth), c.in.depth_by_refs(), c.sized); h->stats.lk_launches++; }
         HIPCHK(hipGetLastError());
         if (h->profiling) HIPCHK(hipEventRecord(h->ev[3], h->stream));
+        if (int rc = launch_reject_f(c, nullptr)) return rc;
         ho.up(h->h_cur_pts, h->d_cur_pts, (size_t)N * cap);
         ho.up(h->h_status, h->d_status, (size_t)N * cap);
         ho.up(h->h_fwd_status, h->d_fwd_status, (size_t)N * cap);
@@ -1008,6 +1064,7 @@ static int run_lk(Call& c) {
     HIPCHK(hipEventRecord(h->ev[6], h->stream));
     c.lap(h->stats.ms_host_pre);
     HIPCHK(hipEventSynchronize(h->ev[6]));
+    collect_reject_f(c);
     c.lap(h->stats.ms_wait_lk);
     return GF_OK;
 }
@@ -1032,12 +1089,14 @@ static int redo_fallback(Call& c) {
     launch_lk(h, N, lk_args(h, 3, 0, h->cfg.flow_back, 1, h->d_seqmask.p, c.kdepth), c.in.depth_by_refs(), c.sized);
     h->stats.lk_launches++;
     HIPCHK(hipGetLastError());
+    if (int rc = launch_reject_f(c, redo.data())) return rc;   // the first launch judged statuses that this pass replaces
     c.ho.up(h->h_cur_pts, h->d_cur_pts, (size_t)N * cap);
     c.ho.up(h->h_status, h->d_status, (size_t)N * cap);
     c.ho.up(h->h_depth_out, h->d_depth_out, (size_t)N * cap);
     c.ho.up(h->h_counters, h->d_counters, (size_t)N * cap * 2);
     if (int rc = c.ho.flush()) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
+    collect_reject_f(c);
     for (int i = 0; i < N; i++) {
         unsigned* cn = h->h_counters.p + (size_t)i * cap * 2;
         const unsigned* kc = keep_cnt.data() + (size_t)i * cap * 2;
@@ -1056,6 +1115,7 @@ static void book_after_lk(Call& c) {
     const int cap = h->cap;
     std::atomic<long long> a_levels{0}, a_iters{0}, a_points{0}, a_tracked{0};
     std::atomic<int> a_want{0};
+    std::atomic<long long> a_rf_seq{0}, a_rf_cand{0}, a_rf_rej{0}, a_rf_void{0};
     h->pool->parallel_for(c.N, [&](int b) {   // b: list position
         const int q = c.seq[b];
         const gf_tracker_seq_cfg& par = h->par[q];
@@ -1065,8 +1125,16 @@ static void book_after_lk(Call& c) {
         int want = 0;
         const gf_box* boxes = h->boxes.empty() ? nullptr : h->boxes[q].data();
         const int fw = c.sized ? h->size_plan.w[b] : h->cfg.width, fh = c.sized ? h->size_plan.h[b] : h->cfg.height;   // the sequence's own frame (feature_tracker.cpp:108-109)
+        RejectFHost rf{};   // GF_REJECT_F_HOST=1: the stage runs inside after_lk, on the status bytes as they came up
+        const bool rf_here = h->rf_host && seq_rejects(h, q);
+        if (rf_here) {
+            rf.cam = reject_f_camera(h, q); rf.status = h->h_status.p + at;
+            rf.f_threshold = h->rf[q].f_threshold; rf.focal = h->rf[q].focal_length == 0.0 ? gfrf::kFocal : h->rf[q].focal_length;
+            rf.seed = gfrf::frame_seed(h->rf[q].seed, (uint32_t)h->seq[q].frames);
+        }
         const LkTally n = after_lk(h->seq[q], par, fw, fh, h->seq_disk.empty() ? h->disk : h->seq_disk[q], roi, r, row(h->h_centers, b, cap), h->h_ncenters.p + b, &want,
-                                   boxes, boxes ? (int)h->boxes[q].size() : 0, h->lifts_on_device(q));
+                                   boxes, boxes ? (int)h->boxes[q].size() : 0, h->lifts_on_device(q), rf_here ? &rf : nullptr);
+        if (rf_here && rf.ran) { a_rf_seq++; a_rf_cand += rf.result.m; a_rf_rej += rf.result.rejected; if (rf.result.m >= gfrf::kSample && rf.result.winner < 0) a_rf_void++; }
         a_levels += n.level_passes; a_iters += n.iterations; a_points += n.points; a_tracked += n.tracked;
         h->h_want.p[b] = want;
         if (h->h_seq_md.p) h->h_seq_md.p[b] = par.min_dist;
@@ -1075,6 +1143,9 @@ static void book_after_lk(Call& c) {
         h->h_out_n.p[b] = 0;
     });
     c.any_want = a_want.load() != 0;
+    for (const gfrf::Result& r : c.rf_res)   // the device form: what the call's launches left, a sequence that fell back counted once
+        if (r.winner != -2) { a_rf_seq++; a_rf_cand += r.m; a_rf_rej += r.rejected; if (r.m >= gfrf::kSample && r.winner < 0) a_rf_void++; }
+    h->rf_stats.sequences += a_rf_seq; h->rf_stats.candidates += a_rf_cand; h->rf_stats.rejected += a_rf_rej; h->rf_stats.no_model += a_rf_void;
     if (h->d_cams.p)   // a sequence lifted on the host is not listed: the kernel skips it, and a call that lists none has no launch
         for (int b = 0; b < c.N; b++) { const int q = c.seq[b]; const bool dev = h->lifts_on_device(q); h->h_cam_of.p[b] = dev ? q : -1; c.lift |= dev; if (dev) c.n_lift++; }
     h->stats.lk_level_passes += a_levels; h->stats.lk_iterations += a_iters; h->stats.lk_points += a_points; h->stats.tracked_features += a_tracked;
@@ -1218,6 +1289,7 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
     if (int rc = run_detect(c)) return rc;
     h->box_pending = false;   // the stream is drained: a box setter's staging has been read
     if (c.n_reg) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, h->ev_dreg[0], h->ev_dreg[1])); h->dreg_ms += ms; }
+    for (int k = 0; k < c.rf_launches; k++) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, h->ev_rf[2 * k], h->ev_rf[2 * k + 1])); h->rf_stats.kernel_ms += ms; }
     if (h->profiling) if (int rc = read_profile(c)) return rc;
     if (c.any_want) if (int rc = check_candidates(c)) return rc;
     if (int rc = book_after_detect(c, out, cap_out, n_out)) return rc;
@@ -1278,6 +1350,7 @@ int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out) {
         h->pyr_head = !(getenv("GF_PYR_HEAD") && atoi(getenv("GF_PYR_HEAD")) == 0);
         h->select_topk = !(getenv("GF_SELECT_TOPK") && atoi(getenv("GF_SELECT_TOPK")) == 0);
         if (const char* e = getenv("GF_CAMERA_LIFT_HOST")) h->lift_mode = atoi(e) != 0 ? 1 : 0;
+        if (const char* e = getenv("GF_REJECT_F_HOST")) h->rf_host = atoi(e) != 0;
         if (const char* e = getenv("GF_LK_POINTS")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) h->lk_points = v; }
     }
     const int W = cfg->width, H = cfg->height, B = h->B, cap = h->cap;
@@ -1907,6 +1980,44 @@ int gf_tracker_get_depth_reg_stats(gf_tracker* h, long long* launches, long long
     return GF_OK;
 }
 
+// ---- rejectWithF per sequence (gf_reject_f.hpp; feature_tracker.cpp:711-743).  Between frames, at any time.
+int gf_tracker_set_seq_reject_f(gf_tracker* h, int seq, const gf_reject_f_cfg* c) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    const bool on = c && c->enable;
+    char msg[200];
+    if (on && !gfrf::check_cfg(c->f_threshold, c->focal_length, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "sequence %d: rejectWithF: %s", seq, msg);
+    if (!on && h->rf_on.empty()) return GF_OK;   // nothing to take back: the handle stays one that never set any
+    if (gf::seq_is_staged(h, seq)) return gf::set_err(GF_ERR_INVALID, "sequence %d is listed by a staged frame: gf_tracker_track_prefetched has to consume it first (rejectWithF)", seq);
+    if (on && h->cap > gfrf::kMaxCandidates) return gf::set_err(GF_ERR_CAPACITY, "sequence %d: rejectWithF takes at most %d points per sequence, the handle holds %d", seq, gfrf::kMaxCandidates, h->cap);
+    if (h->rf_on.empty()) {   // the first setter of the handle: the call's table and the events, into locals first
+        gf::RejectFStage stage; gf::Event ev[4];
+        if (!h->rf_host) {
+            if (int rc = gf::reject_f_fit(stage, (size_t)h->B)) return rc;
+            for (auto& e : ev) HIPCHK(hipEventCreate(&e.e));
+        }
+        h->rf_on.assign(h->B, 0); h->rf.assign(h->B, gf_reject_f_cfg{});
+        h->rf_stage = std::move(stage);
+        for (int i = 0; i < 4; i++) std::swap(h->ev_rf[i].e, ev[i].e);
+    }
+    h->rf_on[seq] = on ? 1 : 0;
+    h->rf[seq] = on ? *c : gf_reject_f_cfg{};
+    return GF_OK;
+}
+
+int gf_tracker_get_seq_reject_f(gf_tracker* h, int seq, gf_reject_f_cfg* out) {
+    if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    *out = !h->rf_on.empty() && h->rf_on[seq] ? h->rf[seq] : gf_reject_f_cfg{};
+    return GF_OK;
+}
+
+int gf_tracker_get_reject_f_stats(gf_tracker* h, gf_reject_f_stats* out) {
+    if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    *out = h->rf_stats;
+    return GF_OK;
+}
+
 int gf_tracker_reset_seq(gf_tracker* h, int seq) {
     if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
     if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
@@ -2031,7 +2142,7 @@ int gf_tracker_get_state(gf_tracker* h, int seq, int* ids, int* track_cnt, float
 
 int gf_tracker_set_profiling(gf_tracker* h, int enable) { if (!h) return gf::set_err(GF_ERR_INVALID, "null handle"); h->profiling = enable != 0; return GF_OK; }
 int gf_tracker_get_stats(gf_tracker* h, gf_tracker_stats* out) { if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument"); *out = h->stats; return GF_OK; }
-int gf_tracker_reset_stats(gf_tracker* h) { if (!h) return gf::set_err(GF_ERR_INVALID, "null handle"); h->stats = gf_tracker_stats{}; h->dreg_launches = h->dreg_frames = 0; h->dreg_ms = 0; h->lift_launches = h->lift_sequences = 0; return GF_OK; }
+int gf_tracker_reset_stats(gf_tracker* h) { if (!h) return gf::set_err(GF_ERR_INVALID, "null handle"); h->stats = gf_tracker_stats{}; h->dreg_launches = h->dreg_frames = 0; h->dreg_ms = 0; h->lift_launches = h->lift_sequences = 0; h->rf_stats = gf_reject_f_stats{}; return GF_OK; }
 
 // ------------------------------------------------------------------ building blocks for parity tests
 static int tmp_handle(int width, int height, int max_cnt, int min_dist, std::unique_ptr<gf_tracker>& own) {

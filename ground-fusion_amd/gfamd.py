@@ -294,6 +294,100 @@ def depth_register(depths, regs, colours, colour_sizes):
     return out
 
 
+REJECT_F_HYPOTHESES = 512   # GF_REJECT_F_HYPOTHESES
+REJECT_F_MAX_PAIRS = 1024   # GF_REJECT_F_MAX_PAIRS
+
+
+class RejectFCfg(C.Structure):
+    """gf_reject_f_cfg: rejectWithF (feature_tracker.cpp:711-743) of a sequence -- the switch, the seed of the draws, F_threshold in virtual pixels and the
+    virtual camera's FOCAL_LENGTH (0: 460)"""
+    _fields_ = [("enable", C.c_int32), ("seed", C.c_uint32), ("f_threshold", C.c_double), ("focal_length", C.c_double)]
+
+    def as_dict(self):
+        return {"enable": self.enable, "seed": self.seed, "f_threshold": self.f_threshold, "focal_length": self.focal_length}
+
+
+class RejectFResult(C.Structure):
+    _fields_ = [("m", C.c_int32), ("rejected", C.c_int32), ("winner", C.c_int32), ("inliers", C.c_int32)]
+
+
+class RejectFStats(C.Structure):
+    _fields_ = [("launches", C.c_longlong), ("sequences", C.c_longlong), ("candidates", C.c_longlong), ("rejected", C.c_longlong), ("no_model", C.c_longlong),
+                ("kernel_ms", C.c_double)]
+
+
+assert C.sizeof(RejectFCfg) == 24 and C.sizeof(RejectFResult) == 16 and C.sizeof(RejectFStats) == 48
+
+
+def _reject_f_tables(sets, thresholds, seeds):
+    sets = [np.ascontiguousarray(s, np.float32).reshape(-1, 4) for s in sets]
+    n = len(sets)
+    first = np.zeros(n + 1, np.int32)
+    first[1:] = np.cumsum([len(s) for s in sets])
+    thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, np.float64), (n,)))
+    sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, np.uint32), (n,)))
+    pairs = np.concatenate(sets) if n else np.zeros((0, 4), np.float32)
+    return n, first, np.ascontiguousarray(pairs), thr, sd
+
+
+def _reject_f_out(first, status, res):
+    return ([status[first[b]:first[b + 1]].copy() for b in range(len(first) - 1)],
+            [{"m": r.m, "rejected": r.rejected, "winner": r.winner, "inliers": r.inliers} for r in res])
+
+
+def reject_f(sets, thresholds=1.0, seeds=0, host=False):
+    """gf_reject_f_batch (host=True: gf_reject_f_batch_host, gfrf::reject without a device): sets[b] is [m_b, 4] float32 virtual-pixel pairs ax ay bx by
+    (at most REJECT_F_MAX_PAIRS), with a threshold and a seed each (scalars are shared) -> (list of uint8 status arrays, list of result dicts)"""
+    n, first, pairs, thr, sd = _reject_f_tables(sets, thresholds, seeds)
+    status = np.zeros(max(int(first[-1]), 1), np.uint8)
+    res = (RejectFResult * max(n, 1))()
+    f = lib().gf_reject_f_batch_host if host else lib().gf_reject_f_batch
+    _chk(f(n, _p(first, C.c_int), _p(pairs, C.c_float) if len(pairs) else None, _p(thr, C.c_double), _p(sd, C.c_uint), _p(status, C.c_uint8), res))
+    return _reject_f_out(first, status, res)
+
+
+def reject_f_device(counts, d_pairs, d_status, thresholds=1.0, seeds=0, stream=0):
+    """gf_reject_f_batch_device: set b holds counts[b] pairs, back to back at the device address d_pairs (4 floats each); d_status (device address) gets a byte per
+    pair.  One launch; returns the list of result dicts"""
+    n = len(counts)
+    first = np.zeros(n + 1, np.int32)
+    first[1:] = np.cumsum(counts)
+    thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, np.float64), (n,)))
+    sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, np.uint32), (n,)))
+    res = (RejectFResult * max(n, 1))()
+    _chk(lib().gf_reject_f_batch_device(n, _p(first, C.c_int), C.cast(C.c_void_p(d_pairs), C.POINTER(C.c_float)), _p(thr, C.c_double), _p(sd, C.c_uint),
+                                        C.cast(C.c_void_p(d_status), C.POINTER(C.c_uint8)), res, C.c_void_p(stream) if stream else None))
+    return [{"m": r.m, "rejected": r.rejected, "winner": r.winner, "inliers": r.inliers} for r in res[:n]]
+
+
+def reject_f_pixels(cams, sizes, prev_uv, cur_uv, thresholds=1.0, focal_lengths=0.0, seeds=0, host=False):
+    """gf_reject_f_pixels_batch (host=True: _host): set b is the pixel rows prev_uv[b], cur_uv[b] ([m_b, 2] float32) of a sizes[b] = (width, height) frame seen
+    through cams[b] (CameraModel or CameraModelEx), lifted inside the kernel as the tracker's launch lifts them -> (list of uint8 status arrays, result dicts)"""
+    n = len(cams)
+    prev = [np.ascontiguousarray(p, np.float32).reshape(-1, 2) for p in prev_uv]
+    cur = [np.ascontiguousarray(p, np.float32).reshape(-1, 2) for p in cur_uv]
+    assert len(prev) == len(cur) == len(sizes) == n and all(len(a) == len(b) for a, b in zip(prev, cur))
+    first = np.zeros(n + 1, np.int32)
+    first[1:] = np.cumsum([len(p) for p in prev])
+    bc = lambda v, t: np.ascontiguousarray(np.broadcast_to(np.asarray(v, t), (n,)))
+    thr, foc, sd = bc(thresholds, np.float64), bc(focal_lengths, np.float64), bc(seeds, np.uint32)
+    wh = np.ascontiguousarray(sizes, np.int32).reshape(-1)
+    arr = (CameraModelEx * max(n, 1))(*[c if isinstance(c, CameraModelEx) else CameraModelEx.of(c) for c in cams])
+    p, c = np.ascontiguousarray(np.concatenate(prev)), np.ascontiguousarray(np.concatenate(cur))
+    status = np.zeros(max(int(first[-1]), 1), np.uint8)
+    res = (RejectFResult * max(n, 1))()
+    f = lib().gf_reject_f_pixels_batch_host if host else lib().gf_reject_f_pixels_batch
+    _chk(f(n, _p(first, C.c_int), arr, _p(wh, C.c_int), _p(p, C.c_float), _p(c, C.c_float), _p(thr, C.c_double), _p(foc, C.c_double), _p(sd, C.c_uint), _p(status, C.c_uint8), res))
+    return _reject_f_out(first, status, res)
+
+
+def reject_f_from_yaml(config_file):
+    """gf_reject_f_from_yaml: F_threshold and this repository's `reject_with_f` switch of a config file -> RejectFCfg"""
+    c = RejectFCfg()
+    _chk(lib().gf_reject_f_from_yaml(os.fsencode(config_file), C.byref(c)))
+    return c
+
+
 def camera_from_yaml(calib_file, cls=CameraModel):
     """gf_camera_from_yaml: a camodocal calibration file (PINHOLE, MEI, KANNALA_BRANDT) -> CameraModel; cls=CameraModelEx: gf_camera_from_yaml_ex, which also
     takes PINHOLE_FULL and SCARAMUZZA files -> CameraModelEx"""
@@ -321,7 +415,9 @@ EXPORTS = ["gf_last_error", "gf_device_count", "gf_set_device", "gf_tracker_crea
            "gf_tracker_set_seq_camera_ex", "gf_tracker_get_seq_camera_ex", "gf_camera_lift_batch_ex", "gf_camera_lift_batch_device_ex", "gf_camera_project_batch_ex",
            "gf_camera_from_yaml_ex", "gf_estimator_cfg_from_yaml_camera_ex", "gf_estimator_set_camera_ex", "gf_depth_register_batch_ex", "gf_depth_register_batch_device_ex", "gf_tracker_get_camera_lift_stats",
            "gf_tracker_set_seq_size", "gf_tracker_get_seq_size",
-           "gf_tracker_set_seq_depth_reg", "gf_tracker_get_seq_depth_reg", "gf_tracker_get_depth_reg_stats", "gf_depth_register_batch", "gf_depth_register_batch_device"]
+           "gf_tracker_set_seq_depth_reg", "gf_tracker_get_seq_depth_reg", "gf_tracker_get_depth_reg_stats", "gf_depth_register_batch", "gf_depth_register_batch_device",
+           "gf_tracker_set_seq_reject_f", "gf_tracker_get_seq_reject_f", "gf_tracker_get_reject_f_stats", "gf_reject_f_batch", "gf_reject_f_batch_device",
+           "gf_reject_f_batch_host", "gf_reject_f_from_yaml", "gf_estimator_set_reject_f", "gf_reject_f_pixels_batch", "gf_reject_f_pixels_batch_host"]
 MAX_SEQ_SIZES = 8   # GF_MAX_SEQ_SIZES
 
 
@@ -680,6 +776,28 @@ class FeatureTracker:
         r, has = DepthReg(), C.c_int(0)
         _chk(lib().gf_tracker_get_seq_depth_reg(self.h, int(seq), C.byref(r), C.byref(has)))
         return r if has.value else None
+
+    def set_seq_reject_f(self, seq, cfg=None, **fields):
+        """gf_tracker_set_seq_reject_f: rejectWithF (feature_tracker.cpp:711-743) of sequence `seq`: a RejectFCfg, or its fields by name (f_threshold=1.0,
+        seed=0, focal_length=0 for 460; enable defaults to 1); None with no fields turns it off.  Allowed between frames at any time; refused (GfError) for a bad
+        threshold and while a prefetched frame lists the sequence."""
+        if cfg is None and fields:
+            cfg = RejectFCfg(int(fields.pop("enable", 1)), int(fields.pop("seed", 0)), float(fields.pop("f_threshold", 1.0)), float(fields.pop("focal_length", 0.0)))
+            if fields:
+                raise TypeError("unknown RejectFCfg fields: %s" % sorted(fields))
+        _chk(lib().gf_tracker_set_seq_reject_f(self.h, int(seq), None if cfg is None else C.byref(cfg)))
+
+    def get_seq_reject_f(self, seq):
+        """gf_tracker_get_seq_reject_f: the RejectFCfg of sequence `seq` (enable == 0: off)"""
+        c = RejectFCfg()
+        _chk(lib().gf_tracker_get_seq_reject_f(self.h, int(seq), C.byref(c)))
+        return c
+
+    def reject_f_stats(self):
+        """gf_tracker_get_reject_f_stats: dict of launches, sequences, candidates, rejected, no_model, kernel_ms"""
+        s = RejectFStats()
+        _chk(lib().gf_tracker_get_reject_f_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in RejectFStats._fields_}
 
     def camera_lift_stats(self):
         """gf_tracker_get_camera_lift_stats: dict of launches of camera_lift_kernel by this handle and of the listed sequences they lifted"""
@@ -1495,6 +1613,10 @@ class SlidingWindowEstimator:
     def set_camera(self, camera):
         """gf_estimator_set_camera / _ex: the camera (CameraModel or CameraModelEx) of the estimator's own tracker, before its first image"""
         _chk((lib().gf_estimator_set_camera_ex if isinstance(camera, CameraModelEx) else lib().gf_estimator_set_camera)(self.h, C.byref(camera)))
+
+    def set_reject_f(self, cfg=None):
+        """gf_estimator_set_reject_f: rejectWithF of the estimator's own tracker (RejectFCfg; None: off)"""
+        _chk(lib().gf_estimator_set_reject_f(self.h, None if cfg is None else C.byref(cfg)))
 
     def set_show_track(self, on=True):
         """gf_estimator_set_show_track: SHOW_TRACK of the estimator's own tracker"""

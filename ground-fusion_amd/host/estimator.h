@@ -152,6 +152,13 @@ class Estimator {
     // SHOW_TRACK and getTrackImage of the estimator's own tracker (FeatureTracker::setShowTrack / getTrackImage; gf_estimator_set_show_track,
     // gf_estimator_get_track_image): the picture of the last inputImage, rows x cols x 3 bytes (bgr8)
     void setShowTrack(bool on) { need(); check(gf_estimator_set_show_track(h_, on ? 1 : 0)); }
+    // rejectWithF of the estimator's own tracker (FeatureTracker::setRejectWithF; feature_tracker.cpp:711-743, gf_estimator_set_reject_f)
+    void setRejectWithF(bool on, double F_THRESHOLD = 1.0) {
+        need();
+        gf_reject_f_cfg c{};
+        c.enable = on ? 1 : 0; c.f_threshold = F_THRESHOLD;
+        check(gf_estimator_set_reject_f(h_, on ? &c : nullptr));
+    }
     void getTrackImage(std::vector<uint8_t>& store, ImageView<uint8_t>& view) {
         need();
         const int W = cfg.tracker.width, H = cfg.tracker.height;

@@ -153,6 +153,14 @@ class FeatureTracker {
         const int seq = 0;
         if (h_) check(gf_tracker_set_show_track(h_, 1, &seq, on ? 1 : 0));
     }
+    // rejectWithF (feature_tracker.cpp:711-743), which the reference leaves commented out at :183 and :454: on, every trackImage drops the points LK kept that
+    // lie further than F_THRESHOLD virtual pixels (parameters.cpp:201) from the epipolar line of the best of 512 eight-point models
+    // (gf_tracker_set_seq_reject_f; the definition is this library's).  Any time between frames.
+    void setRejectWithF(bool on, double F_THRESHOLD = 1.0) {
+        reject_f_ = gf_reject_f_cfg{};
+        reject_f_.enable = on ? 1 : 0; reject_f_.f_threshold = F_THRESHOLD;
+        if (h_) check(gf_tracker_set_seq_reject_f(h_, 0, on ? &reject_f_ : nullptr));
+    }
     // getTrackImage (feature_tracker.cpp:1047; drawTrack :849-905): the frame of the last trackImage with a dot per feature, coloured from blue to red by track
     // length, and a green arrow back to where the feature was one frame earlier -- rows x cols x 3 bytes in the reference's channel order (bgr8), rendered on
     // the device (gf_tracker_track_image).  Without OpenCV: into `store`, with `view` describing it (stride 3 x cols bytes, GF_PIX_BGR8).
@@ -243,6 +251,7 @@ class FeatureTracker {
     std::vector<uint8_t> roi_;   // a region of interest set before the handle exists (tight rows)
     std::vector<gf_box> boxes_;  // exclusion boxes set before the handle exists
     gf_depth_reg depth_reg_{}; bool has_depth_reg_ = false;   // setDepthRegistration, kept for a handle that does not exist yet
+    gf_reject_f_cfg reject_f_{};                              // setRejectWithF, likewise
     static void check(int rc) { if (rc != GF_OK) throw std::runtime_error(std::string("groundfusion_hip: ") + gf_last_error()); }
     void create(int w, int h) {
         gf_tracker_cfg c{};
@@ -257,6 +266,7 @@ class FeatureTracker {
         if (!boxes_.empty()) { const std::vector<gf_box> b = std::move(boxes_); boxes_.clear(); setBoxes(b.data(), (int)b.size()); }
         if (show_track_) setShowTrack(true);
         if (has_depth_reg_) check(gf_tracker_set_seq_depth_reg(h_, 0, &depth_reg_));
+        if (reject_f_.enable) check(gf_tracker_set_seq_reject_f(h_, 0, &reject_f_));
     }
     void refresh() {
         const int cap = (MAX_CNT + 3) & ~3;

@@ -459,6 +459,72 @@ int gf_tracker_get_seq_depth_reg(gf_tracker* h, int seq, gf_depth_reg* out, int*
 /* The registration's own counters (gf_tracker_stats keeps its layout), each may be NULL: kernel launches (two per tracker call that registered a frame), frames
  * registered, and the hipEvent time of the two kernels, summed.  gf_tracker_reset_stats zeroes them. */
 int gf_tracker_get_depth_reg_stats(gf_tracker* h, long long* launches, long long* frames, double* kernel_ms);
+/* rejectWithF: FeatureTracker::rejectWithF (feature_tracker.cpp:711-743; F_threshold, parameters.cpp:201), the epipolar outlier test between LK and the back
+ * end, as a definition of this repository (csrc/gf_reject_f.hpp; DESIGN.md section 4, "rejectWithF"): cv::findFundamentalMat(FM_RANSAC) cannot be restated bit
+ * for bit.  The points LK kept are lifted with the sequence's camera to virtual pixels FOCAL_LENGTH X / Z + width / 2, FOCAL_LENGTH Y / Z + height / 2
+ * (:722-729); GF_REJECT_F_HYPOTHESES eight-point models are drawn by a counter-based hash, solved by Hartley normalisation and Gaussian elimination with full
+ * pivoting in double, and scored by the larger of the two squared epipolar distances against f_threshold^2; the outliers of the model with the most inliers
+ * (ties: the first) lose their status.  Fewer than 8 candidates, or no valid model (a camera at rest with bit-identical points): nothing is rejected -- OpenCV
+ * would return an empty matrix and the reference would drop every point.  Host (GF_REJECT_F_HOST=1, read at gf_tracker_create), kernel and the numpy
+ * restatement of the tests give the same bytes. */
+#define GF_REJECT_F_HYPOTHESES 512
+#define GF_REJECT_F_MAX_PAIRS 1024   /* pairs of one set of the building blocks; points of a sequence whose switch is on */
+/* Field order: enable, seed, f_threshold, focal_length -- the two 32-bit fields first, 24 bytes without padding.  Initialise by field name. */
+typedef struct gf_reject_f_cfg {
+    int32_t enable;          /* 0: off (the reference leaves the call commented out at feature_tracker.cpp:183 and :454) */
+    uint32_t seed;           /* of the draws; mixed with the number of frames the sequence has taken since create / gf_tracker_reset_seq */
+    double f_threshold;      /* F_THRESHOLD in virtual pixels (parameters.cpp:201; 1.0 in every shipped configuration): finite, > 0 */
+    double focal_length;     /* FOCAL_LENGTH of the virtual camera (parameters.h:23); 0 means 460 */
+} gf_reject_f_cfg;
+typedef struct gf_reject_f_result {   /* of one set */
+    int32_t m;          /* candidates: pairs with status 1 and finite coordinates */
+    int32_t rejected;   /* status bytes cleared, pairs with a non-finite coordinate included */
+    int32_t winner;     /* the winning hypothesis, -1: none (m < 8 or every hypothesis void) */
+    int32_t inliers;    /* its inliers */
+} gf_reject_f_result;
+typedef struct gf_reject_f_stats {   /* gf_tracker_stats keeps its layout */
+    long long launches;     /* of reject_f_kernel: one per tracker call that lists a sequence with the switch on and 8 or more points, two where a predicted sequence fell back to the three-level LK (:131-132) */
+    long long sequences;    /* sequence frames the stage ran on */
+    long long candidates, rejected;
+    long long no_model;     /* of those with 8 or more candidates: every hypothesis void, nothing rejected */
+    double kernel_ms;       /* hipEvent time of the kernel, summed (0 under GF_REJECT_F_HOST=1) */
+} gf_reject_f_stats;
+/* rejectWithF of seq (feature_tracker.cpp:711-743); c == NULL or c->enable == 0 turns it off.  From then on every entry point that takes frames (host images,
+ * tight device lists, _refs, prefetched, _some, _sized) applies the stage to the sequence's points behind LK, ahead of track_cnt++ and setMask as the reference
+ * orders them at :170-186: one more launch on the tracking stream per call whatever the number of such sequences, which rewrites the status bytes before the
+ * host reads them.  Allowed between frames at any time.  Refused (GF_ERR_INVALID, the message naming the field, nothing changed): f_threshold not finite or
+ * <= 0, focal_length not finite or < 0, a sequence that a frame staged by gf_tracker_prefetch_* lists; GF_ERR_CAPACITY on a handle whose sequences hold more
+ * than GF_REJECT_F_MAX_PAIRS points.  The first setter of a handle that turns a switch on allocates the call's table; a handle on which it is never called
+ * allocates, copies and launches exactly what it did without it. */
+int gf_tracker_set_seq_reject_f(gf_tracker* h, int seq, const gf_reject_f_cfg* c);
+/* the configuration of seq as it was set; enable == 0 and zeros if it is off (feature_tracker.cpp:711-743) */
+int gf_tracker_get_seq_reject_f(gf_tracker* h, int seq, gf_reject_f_cfg* out);
+/* the stage's own counters (feature_tracker.cpp:711-743); gf_tracker_reset_stats zeroes them */
+int gf_tracker_get_reject_f_stats(gf_tracker* h, gf_reject_f_stats* out);
+/* The stage as a building block (feature_tracker.cpp:731-736, the findFundamentalMat call), through the tracker's kernel: set b of n has the virtual-pixel pairs
+ * pairs[4 first[b] .. 4 first[b + 1]) as ax ay bx by (a: previous frame, b: current), at most GF_REJECT_F_MAX_PAIRS of them, the threshold f_threshold[b] and
+ * the seed seed[b], used as it is.  first, f_threshold, seed and results (may be NULL) are host tables; d_pairs and d_status are device memory.  d_status IS
+ * WRITTEN: one byte per pair, 1 kept, 0 rejected.  One launch on `stream` (a hipStream_t, NULL = the null stream) whatever n; returns when it has run.  The call's job table is one
+ * per process behind a lock held until the launch has run: calls from several threads or on several streams run one after another. */
+int gf_reject_f_batch_device(int n, const int* first, const float* d_pairs, const double* f_threshold, const unsigned* seed, uint8_t* d_status, gf_reject_f_result* results,
+                             void* stream);
+/* The same on host memory (copy in, the launch, copy out; synchronous): for tests and callers without device memory */
+int gf_reject_f_batch(int n, const int* first, const float* pairs, const double* f_threshold, const unsigned* seed, uint8_t* status, gf_reject_f_result* results);
+/* The stage on PIXEL rows (feature_tracker.cpp:711-743 whole: the lift of :722-729 and the findFundamentalMat call), as the tracker launches it: set b has the
+ * previous and current points prev_uv / cur_uv [2 first[b] .. 2 first[b + 1]) of a wh[2 b] x wh[2 b + 1] frame seen through cams[b] (any of the five models), a
+ * threshold, a FOCAL_LENGTH (0: 460) and a seed, used as it is.  All tables are host memory; one launch, with every camera's lift inside the kernel.  _host:
+ * the same through gfrf::reject and the shared lift on the host, no device needed; equal byte for byte for the models whose lift has no transcendental
+ * (PINHOLE, MEI, PINHOLE_FULL, SCARAMUZZA), while a KANNALA_BRANDT set may differ in a borderline point. */
+int gf_reject_f_pixels_batch(int n, const int* first, const gf_camera_model_ex* cams, const int* wh, const float* prev_uv, const float* cur_uv, const double* f_threshold,
+                             const double* focal_length, const unsigned* seed, uint8_t* status, gf_reject_f_result* results);
+int gf_reject_f_pixels_batch_host(int n, const int* first, const gf_camera_model_ex* cams, const int* wh, const float* prev_uv, const float* cur_uv, const double* f_threshold,
+                                  const double* focal_length, const unsigned* seed, uint8_t* status, gf_reject_f_result* results);
+/* F_threshold (F_THRESHOLD, parameters.cpp:201; feature_tracker.cpp:711-743) of a config file, and `reject_with_f`, a key of this repository's (absent or 0: off;
+ * the reference has no switch of its own, its call is commented out) into out->f_threshold and out->enable; seed and focal_length are 0.  Refused by the
+ * key's name: the switch on without a finite F_threshold > 0. */
+int gf_reject_f_from_yaml(const char* config_file, gf_reject_f_cfg* out);
+/* The same sets through gfrf::reject on the host, no device needed: the fallback (GF_REJECT_F_HOST=1) and the yardstick of the two calls above */
+int gf_reject_f_batch_host(int n, const int* first, const float* pairs, const double* f_threshold, const unsigned* seed, uint8_t* status, gf_reject_f_result* results);
 /* The track image: SHOW_TRACK and FeatureTracker::getTrackImage() (feature_tracker.cpp:849-905 drawTrack, :1047; what the node publishes as image_track) -- the
  * MONO8 frame trackImage tracked on (after the handle's colour / raw conversion and equalisation) as height x width x 3 bytes in the reference's channel order
  * (labelled bgr8 there), a dot per feature coloured (255 (1 - len), 0, 255 len) by len = min(1, track_cnt / 20), and a green arrow from each feature that LK
@@ -891,6 +957,9 @@ int gf_estimator_set_boxes(gf_estimator* h, const gf_box* boxes, int n);
  * without a tracker, and as those calls refuse. */
 int gf_estimator_set_show_track(gf_estimator* h, int on);
 int gf_estimator_get_track_image(gf_estimator* h, uint8_t* dst, int stride);
+/* rejectWithF (feature_tracker.cpp:711-743) of an estimator that owns its tracker: gf_tracker_set_seq_reject_f on its one sequence, from the next
+ * gf_estimator_input_image on; NULL turns it off.  Refused for an estimator created without a tracker. */
+int gf_estimator_set_reject_f(gf_estimator* h, const gf_reject_f_cfg* c);
 int gf_estimator_set_state(gf_estimator* h, int frame_count, int solver_flag, const double* Ps, const double* Rs, const double* Vs,
                            const double* Bas, const double* Bgs);
 int gf_estimator_get_features(gf_estimator* h, int cap, int* id, int* start_frame, int* n_obs, double* estimated_depth, int* estimate_flag,

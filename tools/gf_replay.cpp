@@ -17,6 +17,9 @@
 //                                                                   camera frame -- what the node publishes as image_track (feature_tracker.cpp:849-905, :1047) -- as
 //                                                                   <dir>/<frame index, six digits>.ppm (binary PPM, so R, G, B: the picture's bgr8 bytes reversed).
 //                                                                   Without it a `show_track: 1` of the config does nothing: the reference's imshow has no counterpart
+//   --reject-f                                                      with any single-process form: rejectWithF (feature_tracker.cpp:711-743) behind LK, with the
+//                                                                   config's F_threshold (parameters.cpp:201), whatever its `reject_with_f` key says
+//                                                                   (gf_reject_f_from_yaml, gf_estimator_set_reject_f).  Without the flag the key decides
 // reads the reference's own YAML configuration (parameters.cpp key names), replays the recorded IMU / wheel / RGB / depth messages of
 // <dataset dir> (layout in host/replay_node.h) through FeatureTracker::trackImage and Estimator::processImage on the GPU, and writes the
 // trajectory file the reference writes (output_path/vio.txt, TUM format) — to <vio.txt> when given, else to `output_path` of the config.
@@ -111,7 +114,7 @@ static void write_track_ppm(gf::Estimator& estimator, const std::string& dir, lo
 }
 
 static void replay_one(const char* config, const std::string& source, bool from_bag, const std::string& out, gf::Estimator& estimator, bool quiet, bool device_gray = false,
-                       const std::string& roi = std::string(), const std::string& track_images = std::string(), const std::vector<TimedBox>* boxes = nullptr) {
+                       const std::string& roi = std::string(), const std::string& track_images = std::string(), const std::vector<TimedBox>* boxes = nullptr, bool reject_f = false) {
     estimator.readParameters(config);
     if (device_gray) {   // the tracker is created for the encoding of the colour topic: one handle has one format
         const int fmt = gf::ReplayNode<gf::Estimator>::bag_image_format(source, yaml_string(config, "image0_topic"));
@@ -123,6 +126,15 @@ static void replay_one(const char* config, const std::string& source, bool from_
     estimator.setParameter();
     estimator.setResultPath(out);
     if (!roi.empty()) set_roi_from_pgm(estimator, roi);
+    {   // rejectWithF: the flag, or the config's own switch
+        gf_reject_f_cfg rf{};
+        if (gf_reject_f_from_yaml(config, &rf) != GF_OK) throw std::runtime_error(std::string("--reject-f: ") + gf_last_error());
+        if (reject_f) {
+            if (!(rf.f_threshold > 0)) throw std::runtime_error(std::string("--reject-f: ") + config + " has no F_threshold > 0");
+            rf.enable = 1;
+        }
+        if (rf.enable) estimator.setRejectWithF(true, rf.f_threshold);
+    }
     gf::ReplayNode<gf::Estimator> node(estimator);
     const std::string wr = yaml_string(config, "w_replace");
     node.w_replace = wr.empty() ? 0 : atoi(wr.c_str());
@@ -260,6 +272,14 @@ int main(int argc, char** argv) {
             for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
             argc -= 2; i--;
         }
+    bool reject_f = false;   // --reject-f, anywhere on the line
+    for (int i = 1; i < argc; i++)
+        if (std::string(argv[i]) == "--reject-f") {
+            reject_f = true;
+            for (int j = i; j + 1 < argc; j++) argv[j] = argv[j + 1];
+            argc -= 1; i--;
+        }
+    if (reject_f && argc >= 2 && std::string(argv[1]) == "--ranks") { fprintf(stderr, "gf_replay: --reject-f goes with the single-process forms\n"); return 2; }
     std::string track_images;   // --track-images <dir>, anywhere on the line
     for (int i = 1; i < argc; i++)
         if (std::string(argv[i]) == "--track-images") {
@@ -311,13 +331,13 @@ int main(int argc, char** argv) {
         return rc;
     }
     const bool from_bag = argc >= 4 && std::string(argv[2]) == "--bag";
-    if (argc < 3 || (from_bag && argc < 4)) { fprintf(stderr, "usage: %s [--roi <mask.pgm>] [--boxes <file>] [--track-images <dir>] <config.yaml> <dataset dir> [<vio.txt>]\n       %s [--device-gray] [--roi <mask.pgm>] [--boxes <file>] [--track-images <dir>] <config.yaml> --bag <recording.bag> [<vio.txt>]\n       %s --ranks N <config.yaml> <dataset dir> ...\n", argv[0], argv[0], argv[0]); return 2; }
+    if (argc < 3 || (from_bag && argc < 4)) { fprintf(stderr, "usage: %s [--roi <mask.pgm>] [--boxes <file>] [--track-images <dir>] [--reject-f] <config.yaml> <dataset dir> [<vio.txt>]\n       %s [--device-gray] [--roi <mask.pgm>] [--boxes <file>] [--track-images <dir>] [--reject-f] <config.yaml> --bag <recording.bag> [<vio.txt>]\n       %s --ranks N <config.yaml> <dataset dir> ...\n", argv[0], argv[0], argv[0]); return 2; }
     if (device_gray && !from_bag) { fprintf(stderr, "gf_replay: --device-gray goes with --bag (PGM frames are MONO8 already)\n"); return 2; }
     const int out_arg = from_bag ? 4 : 3;
     try {
         gf::Estimator estimator;
         const std::string out = argc > out_arg ? argv[out_arg] : yaml_string(argv[1], "output_path") + "/vio.txt";
-        replay_one(argv[1], from_bag ? argv[3] : argv[2], from_bag, out, estimator, false, device_gray, roi, track_images, boxes_file.empty() ? nullptr : &boxes);
+        replay_one(argv[1], from_bag ? argv[3] : argv[2], from_bag, out, estimator, false, device_gray, roi, track_images, boxes_file.empty() ? nullptr : &boxes, reject_f);
         if (estimator.cfg.gnss_enable) {   // gnss_result.txt of the reference carries the ECEF / ENU position; here as one closing line
             int gi[8]; double yaw, anc[3], ecef[3], enu[3];
             if (gf_estimator_get_gnss_state(estimator.handle(), gi, nullptr, nullptr, &yaw, anc, ecef, enu) == GF_OK) {
