@@ -13,11 +13,13 @@ namespace gfcam {
 constexpr int kLiftThreads = 64;   // one wavefront: no wavefront spans two entries
 __global__ __launch_bounds__(kLiftThreads) void camera_lift_kernel(const LiftArgs A) {
     const unsigned chunks = gridDim.x / (unsigned)A.n_sets, s = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
-    const LiftSet S = A.set[s ? 1 : 0];
+    const LiftSet S = A.set[s < (unsigned)kLiftSets ? s : 0];
+    const Camera* cams = S.cams ? S.cams : A.cams;
+    const int* cam_of = S.cams ? S.cam_of : A.cam_of;
     for (int b = blockIdx.y; b < A.batch; b += gridDim.y) {
-        const int q = A.cam_of ? A.cam_of[b] : b;
+        const int q = cam_of ? cam_of[b] : b;
         if (q < 0) continue;
-        const Camera& cam = A.cams[q];
+        const Camera& cam = cams[q];
         size_t at; int n;
         if (A.first) { at = (size_t)A.first[b]; n = A.first[b + 1] - A.first[b]; }
         else { at = (size_t)b * A.cap; n = S.n ? min(S.n[b], A.cap) : 0; }

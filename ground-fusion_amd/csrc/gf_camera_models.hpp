@@ -233,10 +233,11 @@ GF_CAM_HD void space_to_plane(const Camera& c, const double* P, double& u, doubl
 
 // ---- what camera_lift_kernel (gf_camera_kernels.hpp) is launched with, for the translation units that launch it without holding it
 struct alignas(8) Pair { float x, y; };   // a float pair as it lies in the tables (the device side's float2)
-constexpr int kLiftSets = 2;              // the tracker lifts two tables per call: LK's points and the new corners
+constexpr int kLiftSets = 3;              // the tracker lifts up to three tables per call: LK's points, the new corners, and the right points of its stereo sequences
 // One table of points per list entry.  With LiftArgs::first the points of entry b are pts[first[b] .. first[b + 1]) (n is not read); without, row b of `cap`
 // points of which n[b] are lifted (n == nullptr: none).
-struct LiftSet { const Pair* pts; const int* n; Pair* un; double* rays; };   // rays: 3 doubles per point, or null
+// cams / cam_of: the set's own cameras and list (the right cameras of the stereo branch), or null: LiftArgs's
+struct LiftSet { const Pair* pts; const int* n; Pair* un; double* rays; const struct Camera* cams = nullptr; const int* cam_of = nullptr; };   // rays: 3 doubles per point, or null
 struct LiftArgs {
     const Camera* cams;    // the checked cameras (gfcam::prepare)
     const int* cam_of;     // [batch] which camera entry b has, < 0: the entry is skipped; null: cams[b]

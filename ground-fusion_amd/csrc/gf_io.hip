@@ -256,6 +256,29 @@ int gf_camera_from_yaml(const char* calib_file, gf_camera_model* out) {
     return camera_from_doc(k, calib_file, out);
 }
 
+// The stereo branch (feature_tracker.cpp:259-303) from a config file: `num_of_cam: 2` turns the switch on (parameters.cpp:424-431) and `cam1_calib` names the
+// right camera's calibration file beside the config file (:433-436: configPath + "/" + cam1Calib), read as gf_camera_from_yaml_ex reads one.  Any other
+// num_of_cam leaves the switch off and reads no second file; a missing key reads as 0 like every cv::FileNode.
+int gf_stereo_from_yaml(const char* config_file, gf_stereo_cfg* out) {
+    if (!config_file || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    YamlDoc y;
+    std::string err;
+    if (!parse_yaml(config_file, y, err)) return gf::set_err(GF_ERR_INVALID, "%s: %s", config_file, err.c_str());
+    gf_stereo_cfg c;
+    memset(&c, 0, sizeof c);
+    if (y.integer("num_of_cam") == 2) {
+        if (!y.has("cam1_calib")) return gf::set_err(GF_ERR_INVALID, "%s: num_of_cam is 2 but cam1_calib is missing", config_file);
+        const std::string cfg = config_file, dir = cfg.find_last_of('/') == std::string::npos ? std::string(".") : cfg.substr(0, cfg.find_last_of('/'));
+        const std::string calib = dir + "/" + y.str("cam1_calib");
+        YamlDoc k;
+        if (!parse_yaml(calib.c_str(), k, err)) return gf::set_err(GF_ERR_INVALID, "%s (cam1_calib of %s): %s", calib.c_str(), config_file, err.c_str());
+        if (int rc = camera_from_doc_ex(k, calib.c_str(), &c.right)) return rc;
+        c.enable = 1;
+    }
+    *out = c;
+    return GF_OK;
+}
+
 // camera == null and wide == null: gf_estimator_cfg_from_yaml, which takes a PINHOLE file alone; at most one of the two is given
 static int estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* c, gf_camera_model* camera, gf_camera_model_ex* wide = nullptr) {
     YamlDoc y;

@@ -50,6 +50,11 @@ struct SeqState {  // per-sequence FeatureTracker members (feature_tracker.h:76-
     std::vector<std::pair<int, P2f>> draw_from;
     std::vector<gfdraw::Prim> draw_list;
     std::string draw_why;   // why the builder refused the newest frame's list (then draw_have is false); empty otherwise
+    // The stereo branch (feature_tracker.cpp:259-303; stereo_stage below): the right-hand members of feature_tracker.h:85-89.  Nothing here is touched by a
+    // sequence without a right camera, or by a frame that comes without a right image.
+    std::vector<int> ids_right;
+    std::vector<P2f> cur_right_pts, cur_un_right_pts, right_pts_velocity;
+    std::vector<std::pair<int, P2f>> cur_un_right_pts_map, prev_un_right_pts_map;
 };
 
 static inline int cvRoundf(float v) { return (int)lrintf(v); }
@@ -113,24 +118,26 @@ inline void set_mask_host(int width, int height, SeqState& s, const DiskTable& T
     }
 }
 
-inline void pts_velocity(SeqState& s) {  // feature_tracker.cpp:810-847
-    const size_t n = s.ids.size();
-    s.pts_velocity.resize(n);
-    s.cur_un_pts_map.resize(n);
-    for (size_t i = 0; i < n; i++) s.cur_un_pts_map[i] = {s.ids[i], s.cur_un_pts[i]};
-    std::sort(s.cur_un_pts_map.begin(), s.cur_un_pts_map.end(), [](const std::pair<int, P2f>& a, const std::pair<int, P2f>& b) { return a.first < b.first; });
-    if (!s.prev_un_pts_map.empty()) {
-        const double dt = s.cur_time - s.prev_time;
+// ptsVelocity (feature_tracker.cpp:810-847) on any of the tracker's lists: cur_map is rebuilt from ids and pts, the velocities are taken against prev_map over dt
+inline void pts_velocity_of(const std::vector<int>& ids, const std::vector<P2f>& pts, std::vector<std::pair<int, P2f>>& cur_map,
+                            const std::vector<std::pair<int, P2f>>& prev_map, double dt, std::vector<P2f>& vel) {
+    const size_t n = ids.size();
+    vel.resize(n);
+    cur_map.resize(n);
+    for (size_t i = 0; i < n; i++) cur_map[i] = {ids[i], pts[i]};
+    std::sort(cur_map.begin(), cur_map.end(), [](const std::pair<int, P2f>& a, const std::pair<int, P2f>& b) { return a.first < b.first; });
+    if (!prev_map.empty()) {
         for (size_t i = 0; i < n; i++) {
-            const int id = s.ids[i];
-            auto it = std::lower_bound(s.prev_un_pts_map.begin(), s.prev_un_pts_map.end(), id, [](const std::pair<int, P2f>& a, int v) { return a.first < v; });
-            if (it != s.prev_un_pts_map.end() && it->first == id) {
-                const double vx = (s.cur_un_pts[i].x - it->second.x) / dt, vy = (s.cur_un_pts[i].y - it->second.y) / dt;
-                s.pts_velocity[i] = {(float)vx, (float)vy};
-            } else s.pts_velocity[i] = {0.f, 0.f};
+            const int id = ids[i];
+            auto it = std::lower_bound(prev_map.begin(), prev_map.end(), id, [](const std::pair<int, P2f>& a, int v) { return a.first < v; });
+            if (it != prev_map.end() && it->first == id) {
+                const double vx = (pts[i].x - it->second.x) / dt, vy = (pts[i].y - it->second.y) / dt;
+                vel[i] = {(float)vx, (float)vy};
+            } else vel[i] = {0.f, 0.f};
         }
-    } else for (size_t i = 0; i < n; i++) s.pts_velocity[i] = {0.f, 0.f};
+    } else for (size_t i = 0; i < n; i++) vel[i] = {0.f, 0.f};
 }
+inline void pts_velocity(SeqState& s) { pts_velocity_of(s.ids, s.cur_un_pts, s.cur_un_pts_map, s.prev_un_pts_map, s.cur_time - s.prev_time, s.pts_velocity); }
 
 // cam: the sequence's camera where it is no pinhole (gf_tracker_set_seq_camera); null: the pinhole of par
 inline void set_prediction(SeqState& s, const gf_tracker_seq_cfg& par, const int* ids, const double* xyz, int n, const gfcam::Camera* cam = nullptr) {  // feature_tracker.cpp:1006-1027
@@ -277,13 +284,41 @@ struct DetectRows {
 };
 struct Packed { int written; int overflow; };   // observations written; or overflow >= 0: that many features did not fit cap_out, none written
 
+// What the stereo kernel left for the sequence (gf_stereo_kernels.hpp), by position in cur_pts -- the tracked survivors in setMask's order, then the new corners:
+// the right point of every one and the status the reduction reads (:280; the forward status alone without FLOW_BACK).  cam: the right camera.  un_right: the
+// pairs a lift on the device left for the same rows, or null: the right camera's lift runs here, per kept point.
+struct StereoRows { const P2f* right_pts; const uint8_t* status; const gfcam::Camera* cam; const P2f* un_right; };
+
+// The stereo branch of trackImage (feature_tracker.cpp:259-303) behind undistortedPts and ptsVelocity of the left (:210-211) and ahead of the roll-over (:307-312),
+// for a frame that came with a right image: the right-hand lists are cleared (:261-265); if cur_pts is not empty, ids_right = ids, cur_right_pts and ids_right are
+// reduced by the status (:286-288; the left lists are not touched), the kept points are lifted through the right camera (:298) and their velocities taken against
+// the map of the last frame that ran the stage, over this frame's cur_time - prev_time (:299); then prev_un_right_pts_map = cur_un_right_pts_map (:302), also where
+// cur_pts was empty.
+inline void stereo_stage(SeqState& s, const StereoRows& r) {
+    s.ids_right.clear(); s.cur_right_pts.clear(); s.cur_un_right_pts.clear(); s.right_pts_velocity.clear(); s.cur_un_right_pts_map.clear();
+    const size_t n = s.cur_pts.size();
+    if (n > 0) {
+        for (size_t i = 0; i < n; i++) {
+            if (!r.status[i]) continue;
+            s.ids_right.push_back(s.ids[i]); s.cur_right_pts.push_back(r.right_pts[i]);
+            if (r.un_right) s.cur_un_right_pts.push_back(r.un_right[i]);
+            else { double P[3]; P2f o; gfcam::lift_pair(*r.cam, (double)r.right_pts[i].x, (double)r.right_pts[i].y, P, o.x, o.y); s.cur_un_right_pts.push_back(o); }
+        }
+        pts_velocity_of(s.ids_right, s.cur_un_right_pts, s.cur_un_right_pts_map, s.prev_un_right_pts_map, s.cur_time - s.prev_time, s.right_pts_velocity);
+    }
+    s.prev_un_right_pts_map = s.cur_un_right_pts_map;
+}
+
 // After the detection (feature_tracker.cpp:85-93, 210-211, 322-368): addPoints, undistortedPts, ptsVelocity, the roll-over of prev_* and of the pyramid slot,
 // and the featureFrame into out[0 .. cap_out).  have_depth: the call came with depth images.
 // cam: the sequence's camera where it is no pinhole (gf_tracker_set_seq_camera); null: the pinhole of par, lifted here as ever.  un_lk / un_out: the pairs a
 // lift on the device left for the rows of LK's table and of the detection's (a tracked point picks its own by the row it came from, a new corner by position);
 // both null: the model's lift runs here, per point.
+// stereo: the frame came with a right image for a sequence that has a right camera (stereo_stage runs at its place, and one observation per entry of ids_right
+// follows the left ones: camera_id 1, the right point's pair, pixel and velocity, and the mono loop's -2.4 in the eighth field; the reference's second left
+// observation, which would read the right image as depth (:344-368), is not reproduced); null: the stage is skipped and the right-hand state stays as it is.
 inline Packed after_detect(SeqState& s, const gf_tracker_seq_cfg& par, const DetectRows& r, bool have_depth, gf_feature_obs* out, int cap_out,
-                           const gfcam::Camera* cam = nullptr, const P2f* un_lk = nullptr, const P2f* un_out = nullptr) {
+                           const gfcam::Camera* cam = nullptr, const P2f* un_lk = nullptr, const P2f* un_out = nullptr, const StereoRows* stereo = nullptr) {
     const size_t n_tracked = s.cur_pts.size();
     for (int i = 0; i < r.out_n; i++) {
         const P2f p = r.out_pts[i];
@@ -295,6 +330,7 @@ inline Packed after_detect(SeqState& s, const gf_tracker_seq_cfg& par, const Det
     else if (un_lk && un_out) for (size_t i = 0; i < s.cur_pts.size(); i++) s.cur_un_pts.push_back(i < n_tracked ? un_lk[s.lk_row[i]] : un_out[i - n_tracked]);
     else for (auto& p : s.cur_pts) { double P[3]; P2f o; gfcam::lift_pair(*cam, (double)p.x, (double)p.y, P, o.x, o.y); s.cur_un_pts.push_back(o); }
     pts_velocity(s);
+    if (stereo) stereo_stage(s, *stereo);
     s.prev_pts = s.cur_pts; s.prev_un_pts = s.cur_un_pts; s.prev_un_pts_map.swap(s.cur_un_pts_map); s.prev_time = s.cur_time;
     s.hasPrediction = false;
     s.slot ^= 1;   // the pyramid written in this call is the sequence's previous frame from here on
@@ -302,7 +338,15 @@ inline Packed after_detect(SeqState& s, const gf_tracker_seq_cfg& par, const Det
     // depth_cam set but no depth image: neither packing loop of the reference runs (feature_tracker.cpp:320 `depth_cam == 0`, :344 `!_img1.empty()`):
     // the returned featureFrame is empty, the tracker state has advanced all the same
     if (par.depth_cam && !have_depth) return {0, -1};
-    if (n > cap_out) return {0, n};
+    const int n_right = stereo ? (int)s.ids_right.size() : 0;
+    if (n + n_right > cap_out) return {0, n + n_right};   // the overflow rule holds for the sum
+    for (int i = 0; i < n_right; i++) {
+        gf_feature_obs* o = out + n + i;
+        o->id = s.ids_right[i]; o->camera_id = 1;
+        o->v[0] = s.cur_un_right_pts[i].x; o->v[1] = s.cur_un_right_pts[i].y; o->v[2] = 1; o->v[3] = s.cur_right_pts[i].x; o->v[4] = s.cur_right_pts[i].y;
+        o->v[5] = s.right_pts_velocity[i].x; o->v[6] = s.right_pts_velocity[i].y;
+        o->v[7] = -2.4;
+    }
     for (int i = 0; i < n; i++) {
         gf_feature_obs* o = out + i;
         o->id = s.ids[i]; o->camera_id = 0;
@@ -310,7 +354,7 @@ inline Packed after_detect(SeqState& s, const gf_tracker_seq_cfg& par, const Det
         o->v[5] = s.pts_velocity[i].x; o->v[6] = s.pts_velocity[i].y;
         o->v[7] = par.depth_cam ? (double)(int)s.cur_depth[i] / 1000 : -2.4;
     }
-    return {n, -1};
+    return {n + n_right, -1};
 }
 
 // After after_detect, for a sequence whose show_track is on (drawTrack, feature_tracker.cpp:849-905): the frame's primitive list from what the frame left -- a dot

@@ -35,6 +35,7 @@
 #include "gf_comm.hpp"
 #include "gf_detect_kernels.hpp"
 #include "gf_lk_kernels.hpp"
+#include "gf_stereo_kernels.hpp"
 #include "gf_copy_list.hpp"
 #include "gf_depth_reg_stage.hpp"
 #include "gf_reject_f_stage.hpp"
@@ -292,6 +293,35 @@ struct gf_tracker {
     bool rf_host = false;
     gf_reject_f_stats rf_stats{};
 
+    // A right camera per sequence (gf_tracker_set_seq_stereo; the stereo branch of trackImage, feature_tracker.cpp:259-303; gf_stereo_kernels.hpp), the tenth thing
+    // addressed by SEQUENCE.  Everything here is obtained by the first setter of the handle that turns a sequence's switch on: st_on[seq] / st_cfg[seq] / st_cam[seq],
+    // the configuration as it was set and the right camera as the lift reads it; d_rimg, one right pyramid per sequence, the handle's slots apart; the table of
+    // sizes where no size setter got it (the kernel reads a SizeRow per block).  Per call, by list position: st_right_of (the sequence, whose right pyramid the
+    // call built, or -1), st_left_of (the call's cur_of), st_size_of, st_fb, st_ntr / st_row (the tracked survivors in final order as rows of LK's table, uploaded
+    // with setMask's hand-over), and the kernel's outputs st_pts / st_status, which come up with the call's last copies.  st_refs / st_cur: the right frames and
+    // their pyramids in the compact order of the pyramid launches (one per distinct size of the call).
+    std::vector<uint8_t> st_on; std::vector<gf_stereo_cfg> st_cfg; std::vector<gfcam::Camera> st_cam;
+    DevBuf<uint8_t> d_rimg;
+    DevBuf<int> d_st_right_of, d_st_left_of, d_st_ntr, d_st_row, d_st_cur; PinBuf<int> h_st_right_of, h_st_left_of, h_st_ntr, h_st_row, h_st_cur;
+    DevBuf<uint8_t> d_st_size_of, d_st_fb, d_st_status, d_st_fwd; PinBuf<uint8_t> h_st_size_of, h_st_fb, h_st_status;
+    DevBuf<float2> d_st_pts; PinBuf<float2> h_st_pts;
+    DevBuf<gf_frame_ref> d_st_refs; PinBuf<gf_frame_ref> h_st_refs;
+    // the right cameras by sequence as the lift kernel reads them (a row written by the setter), the list of a call's right lifts on the device (the sequence, or -1:
+    // a PINHOLE right camera, lifted on the host as a pinhole ever is, or a model GF_CAMERA_LIFT_HOST keeps there), the counts the stereo kernel leaves for the lift,
+    // and the lifted pairs by position in cur_pts, which come up with the right points
+    DevBuf<gfcam::Camera> d_st_cams; DevBuf<int> d_st_cam_of, d_st_n; PinBuf<int> h_st_cam_of;
+    DevBuf<float2> d_st_un; PinBuf<float2> h_st_un;
+    bool right_lifts_on_device(int q) const {   // the route the model takes today (lifts_on_device)
+        const int m = st_cfg[q].right.model;
+        if (m == GF_CAMERA_PINHOLE) return false;
+        return lift_mode < 0 ? m != GF_CAMERA_SCARAMUZZA : lift_mode == 0;
+    }
+    // the right eye's CLAHE (the node equalises both eyes, rosNodeTest.cpp:256-261), obtained by the first setter that makes a stereo sequence an equalising one:
+    // the equalised right frames the pyramid reads, their LUTs, and the dense table of a call's sources
+    DevBuf<uint8_t> d_st_eq, d_st_eq_lut; DevBuf<gf_frame_ref> d_st_eqsrc; PinBuf<gf_frame_ref> h_st_eqsrc;
+    gf_stereo_stats st_stats{};
+    bool stereo_on(int q) const { return !st_on.empty() && st_on[q]; }
+
     std::unique_ptr<HostPool> pool;
 };
 static_assert(gfsize::kPad == gf::kPad && gfsize::kWin == gf::kWin && gfsize::kMaxLevels == gf::kMaxLevels, "gf_seq_size.hpp restates the pyramid's constants");
@@ -306,10 +336,11 @@ namespace gf {
 // refs (the _refs entry points, MONO8 without equalisation): the frames lie at refs[i] instead (device-readable table; d_raw_frames is not read).  The kernel
 // follows the sizes as before and each block takes the load form its own frame's pointer and pitch allow.  *widest: the widest piece of the launched first reader.
 // geom (a frame size per sequence, gf_seq_size.hpp): the geometry of the `count` frames where it is not the handle's; the pyramids still lie the handle's slots apart.
-static int launch_pyramid(gf_tracker* h, const uint8_t* d_raw_frames, int count, const int* cur_of, const gf_frame_ref* refs = nullptr, int* widest = nullptr, const PyrGeom* geom = nullptr) {
+static int launch_pyramid(gf_tracker* h, const uint8_t* d_raw_frames, int count, const int* cur_of, const gf_frame_ref* refs = nullptr, int* widest = nullptr, const PyrGeom* geom = nullptr,
+                          uint8_t* img_base = nullptr) {   // img_base: the pyramids cur_of counts in, where they are not the handle's pairs (the right pyramids of the stereo branch)
     const PyrGeom& G = geom ? *geom : h->G;
     const size_t seq_img = h->G.img_bytes;   // distance between two pyramids, whichever sequence and slot they belong to
-    uint8_t* img = h->d_img.p;
+    uint8_t* img = img_base ? img_base : h->d_img.p;
     const LevelGeom g0 = G.lv[0];
     const bool v16 = !((g0.w | g0.stride | (int)(((size_t)g0.w * g0.h) & 15) | (int)(seq_img & 15) | (int)((g0.img_off - kPad * g0.stride - kPad) & 15)) & 15) &&
                      !(((refs ? 0 : reinterpret_cast<uintptr_t>(d_raw_frames)) | reinterpret_cast<uintptr_t>(img)) & 15);
@@ -421,6 +452,11 @@ static int check_list(gf_tracker* h, int count, const int* seq) {
 // The entry points that do not serve a depth registration (gf_tracker_set_seq_depth_reg; everything but the _refs forms): a call with depth that lists a
 // sequence which has one is refused before anything is copied, launched or changed.  seq: checked by check_list.
 static int refuse_registered(const gf_tracker* h, const char* who, int count, const int* seq, bool with_depth) {
+    if (with_depth && !h->st_on.empty())   // the stereo branch likewise: the second image of a stereo sequence is its right frame, which travels by gf_frame_ref only
+        for (int i = 0; i < count; i++)
+            if (h->st_on[seq[i]])
+                return set_err(GF_ERR_INVALID, "%s: sequence %d (list position %d) is a stereo sequence, which takes its right frame on gf_tracker_track_some_device_refs / "
+                               "gf_tracker_track_batch_device_refs only; this entry point serves it without a second image, as a mono frame", who, seq[i], i);
     if (!with_depth || h->dreg_on.empty()) return GF_OK;
     for (int i = 0; i < count; i++)
         if (h->dreg_on[seq[i]])
@@ -768,6 +804,8 @@ struct Call {
     std::vector<gfrf::Result> rf_res;     // by list position: what rejectWithF left for the sequence (winner -2: it did not run)
     int rf_launches = 0;                  // launches of reject_f_kernel in this call: 0, 1, or 2 when a predicted sequence fell back
     int n_reg = 0;                        // listed sequences whose raw depth frame this call registers (publish fills their jobs, launch_depth_reg runs them)
+    int n_st_lift = 0;                    // how many of them have their right points lifted by the call's launch of camera_lift_kernel
+    int n_stereo = 0;                     // listed stereo sequences that came with a right frame: the stage runs for them (publish, launch_right_pyramids, launch_stereo)
     void lap(double& acc) { const auto n = std::chrono::steady_clock::now(); acc += std::chrono::duration<double, std::milli>(n - tp).count(); tp = n; }
     void add_refs() {
         if (refs_down) { ho.down(h->d_refs, h->h_refs, (size_t)2 * h->B); refs_down = false; }
@@ -787,6 +825,16 @@ static int publish(Call& c) {
     if (in.gray_refs) {
         for (int i = 0; i < c.N; i++) { h->h_refs.p[i] = in.gray_refs[i]; h->h_refs.p[h->B + i] = in.depth_refs ? in.depth_refs[i] : gf_frame_ref{nullptr, 0}; }
         if (in.depth_refs) c.kdepth = reinterpret_cast<const uint16_t*>(h->d_refs.p + h->B);   // what the _refs forms of LK and the selection read in the place of tight frames
+        // a right camera per sequence: the entry is the RIGHT frame, 8-bit.  It leaves the table the depth samples read (the sequence has no depth camera) and goes
+        // to the stage's own, by list position until launch_right_pyramids orders it
+        if (!h->st_on.empty())
+            for (int i = 0; i < c.N; i++) {
+                const int q = c.seq[i];
+                h->h_st_right_of.p[i] = -1;
+                if (!h->st_on[q]) continue;
+                h->h_refs.p[h->B + i] = gf_frame_ref{nullptr, 0};
+                if (in.depth_refs && in.depth_refs[i].data) { h->h_st_right_of.p[i] = q; c.n_stereo++; }
+            }
         // a depth registration per sequence (gf_depth_reg.hpp): the entry is the RAW frame; the table names the handle's registered frame in its place, and the
         // job goes to launch_depth_reg.  A sequence without a depth camera is never registered (its entry is never sampled).
         if (in.depth_refs && !h->dreg_on.empty()) {
@@ -1021,6 +1069,92 @@ static void collect_reject_f(Call& c) {
     c.rf_pos.clear();
 }
 
+static int stereo_lk_launch(const SizeRow* rows, const uint8_t* size_of, size_t slot_bytes, const StereoLkArgs& A, int count, hipStream_t stream);
+
+// The right pyramids of the call's stereo sequences that came with a right frame (feature_tracker.cpp:273 builds them inside calcOpticalFlowPyrLK): behind the
+// front, by the pyramid route a frame of that size takes, one pass of launch_pyramid per distinct size among them, into d_rimg (pyramid q of sequence q).
+static int launch_right_pyramids(Call& c) {
+    gf_tracker* h = c.h;
+    const bool bus = h->copy_lists && h->h_st_cur.hd && h->h_st_refs.hd;
+    int first[GF_MAX_SEQ_SIZES + 1] = {0}, k = 0;
+    int eq_n[GF_MAX_SEQ_SIZES] = {0}, eq_first[GF_MAX_SEQ_SIZES] = {0}, n_eq = 0;
+    size_t eq_at[GF_MAX_SEQ_SIZES] = {0}, eq_bytes = 0;
+    for (int r = 0; r < GF_MAX_SEQ_SIZES; r++) {   // the compact tables, size by size
+        first[r] = k;
+        for (int i = 0; i < c.N; i++) {
+            const int q = c.seq[i];
+            if (h->h_st_right_of.p[i] < 0 || h->sizes.row_of[q] != r) continue;
+            h->h_st_cur.p[k] = q; h->h_st_refs.p[k] = c.in.depth_refs[i];
+            if (h->fmt[q].equalize) {   // the pyramid reads the equalised frame: slot n_eq of the dense table, tight rows of the sequence's own width
+                const size_t px = (size_t)seq_width(h, q) * seq_height(h, q);
+                if (eq_n[r] == 0) { eq_first[r] = n_eq; eq_at[r] = eq_bytes; }
+                h->h_st_eqsrc.p[n_eq] = c.in.depth_refs[i];
+                h->h_st_refs.p[k] = gf_frame_ref{h->d_st_eq.p + eq_bytes, (size_t)seq_width(h, q)};
+                eq_n[r]++; n_eq++; eq_bytes += px;
+            }
+            k++;
+        }
+    }
+    first[GF_MAX_SEQ_SIZES] = k;
+    if (n_eq) {   // CLAHE over the list, once per distinct size, as the sized front runs it
+        const bool ebus = h->copy_lists && h->h_st_eqsrc.hd;
+        if (!ebus) HIPCHK(hipMemcpyAsync(h->d_st_eqsrc.p, h->h_st_eqsrc.p, (size_t)n_eq * sizeof(gf_frame_ref), hipMemcpyHostToDevice, h->stream));
+        const gf_frame_ref* src = ebus ? h->h_st_eqsrc.hd : h->d_st_eqsrc.p;
+        for (int r = 0; r < GF_MAX_SEQ_SIZES; r++) {
+            if (!eq_n[r]) continue;
+            if (int rc = clahe_launch_refs(src + eq_first[r], h->d_st_eq.p + eq_at[r], h->d_st_eq_lut.p + clahe_lut_bytes(eq_first[r], kClaheTiles, kClaheTiles), eq_n[r], h->sizes.w[r], h->sizes.h[r],
+                                           kClaheClip, kClaheTiles, kClaheTiles, h->stream)) return rc;
+        }
+    }
+    if (!bus) {
+        HIPCHK(hipMemcpyAsync(h->d_st_cur.p, h->h_st_cur.p, (size_t)k * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->d_st_refs.p, h->h_st_refs.p, (size_t)k * sizeof(gf_frame_ref), hipMemcpyHostToDevice, h->stream));
+    }
+    const int* cur = bus ? h->h_st_cur.hd : h->d_st_cur.p;
+    const gf_frame_ref* refs = bus ? h->h_st_refs.hd : h->d_st_refs.p;
+    for (int r = 0; r < GF_MAX_SEQ_SIZES; r++) {
+        const int n = first[r + 1] - first[r];
+        if (n < 1) continue;
+        if (int rc = launch_pyramid(h, nullptr, n, cur + first[r], refs + first[r], nullptr, r == 0 ? nullptr : &h->size_geom[r], h->d_rimg.p)) return rc;
+    }
+    h->st_stats.right_pyramids += k;
+    return GF_OK;
+}
+
+// The stereo tables that go down with setMask's hand-over (the copy list in front of the detection, or one of their own), and the ONE launch of the stereo kernel
+// for all stereo sequences of the call, behind the selection kernel whose output table and counts it reads.
+static void stereo_down(Call& c) {
+    gf_tracker* h = c.h;
+    const int N = c.N;
+    for (int i = 0; i < N; i++) {
+        const int q = c.seq[i];
+        h->h_st_left_of.p[i] = h->h_cur.p[i]; h->h_st_size_of.p[i] = (uint8_t)h->sizes.row_of[q]; h->h_st_fb.p[i] = (uint8_t)(h->par[q].flow_back ? 1 : 0);
+        if (h->h_st_right_of.p[i] < 0) h->h_st_ntr.p[i] = 0;
+        const bool dev = h->h_st_right_of.p[i] >= 0 && h->right_lifts_on_device(q);
+        h->h_st_cam_of.p[i] = dev ? q : -1;
+        if (dev) c.n_st_lift++;
+    }
+    if (c.n_st_lift) c.ho.down(h->d_st_cam_of, h->h_st_cam_of, N);
+    c.ho.down(h->d_st_right_of, h->h_st_right_of, N); c.ho.down(h->d_st_left_of, h->h_st_left_of, N); c.ho.down(h->d_st_size_of, h->h_st_size_of, N);
+    c.ho.down(h->d_st_fb, h->h_st_fb, N); c.ho.down(h->d_st_ntr, h->h_st_ntr, N); c.ho.down(h->d_st_row, h->h_st_row, (size_t)N * h->cap);
+}
+static int launch_stereo(Call& c) {
+    gf_tracker* h = c.h;
+    StereoLkArgs A{};
+    A.left = h->d_img.p; A.left_of = h->d_st_left_of.p; A.right = h->d_rimg.p; A.right_of = h->d_st_right_of.p; A.cap = h->cap;
+    A.n_tracked = h->d_st_ntr.p; A.row = h->d_st_row.p; A.lk_pts = h->d_cur_pts.p; A.n_new = h->d_out_n.p; A.new_pts = h->d_out_pts.p;
+    A.flow_back_of = h->d_st_fb.p; A.right_pts = h->d_st_pts.p; A.status = h->d_st_status.p; A.fwd_status = h->d_st_fwd.p; A.n_points = h->d_st_n.p;
+    if (int rc = stereo_lk_launch(h->d_size_rows.p, h->d_st_size_of.p, h->G.img_bytes, A, c.N, h->stream)) return rc;
+    h->st_stats.launches++;
+    return GF_OK;
+}
+static void stereo_up(Call& c) {
+    gf_tracker* h = c.h;
+    c.ho.up(h->h_st_pts, h->d_st_pts, (size_t)c.N * h->cap);
+    c.ho.up(h->h_st_status, h->d_st_status, (size_t)c.N * h->cap);
+    if (c.n_st_lift) c.ho.up(h->h_st_un, h->d_st_un, (size_t)c.N * h->cap);
+}
+
 // Temporal optical flow (feature_tracker.cpp:113-176): the sequences without a prediction in one launch from scratch, those with one in a second from their
 // predictions.  Returns when LK's tables are on the host.
 static int run_lk(Call& c) {
@@ -1133,7 +1267,13 @@ static void book_after_lk(Call& c) {
             rf.seed = gfrf::frame_seed(h->rf[q].seed, (uint32_t)h->seq[q].frames);
         }
         const LkTally n = after_lk(h->seq[q], par, fw, fh, h->seq_disk.empty() ? h->disk : h->seq_disk[q], roi, r, row(h->h_centers, b, cap), h->h_ncenters.p + b, &want,
-                                   boxes, boxes ? (int)h->boxes[q].size() : 0, h->lifts_on_device(q), rf_here ? &rf : nullptr);
+                                   boxes, boxes ? (int)h->boxes[q].size() : 0, h->lifts_on_device(q) || (c.n_stereo && h->h_st_right_of.p[b] >= 0), rf_here ? &rf : nullptr);
+        if (c.n_stereo && h->h_st_right_of.p[b] >= 0) {   // the tracked survivors in setMask's order, as rows of LK's table: the stereo kernel's first source
+            const SeqState& s = h->seq[q];
+            int* rows = h->h_st_row.p + at;
+            for (size_t k = 0; k < s.lk_row.size(); k++) rows[k] = s.lk_row[k];
+            h->h_st_ntr.p[b] = (int)s.lk_row.size();
+        }
         if (rf_here && rf.ran) { a_rf_seq++; a_rf_cand += rf.result.m; a_rf_rej += rf.result.rejected; if (rf.result.m >= gfrf::kSample && rf.result.winner < 0) a_rf_void++; }
         a_levels += n.level_passes; a_iters += n.iterations; a_points += n.points; a_tracked += n.tracked;
         h->h_want.p[b] = want;
@@ -1162,8 +1302,12 @@ static int launch_lift(Call& c) {
     A.cams = h->d_cams.p; A.cam_of = h->d_cam_of.p; A.first = nullptr; A.cap = h->cap; A.batch = c.N; A.n_sets = 2;
     A.set[0] = gfcam::LiftSet{pairs(h->d_cur_pts.p), c.any_prev ? h->d_npts.p : nullptr, pairs(h->d_un_lk.p), nullptr};
     A.set[1] = gfcam::LiftSet{pairs(h->d_out_pts.p), c.any_want ? h->d_out_n.p : nullptr, pairs(h->d_un_out.p), nullptr};
-    if (!c.any_prev && !c.any_want) return GF_OK;
-    h->lift_launches++; h->lift_sequences += c.n_lift;
+    // the right points of the call's stereo sequences, where the stereo kernel left them: one more list entry of the same launch, with the right cameras
+    const gfcam::LiftSet right{pairs(h->d_st_pts.p), h->d_st_n.p, pairs(h->d_st_un.p), nullptr, h->d_st_cams.p, h->d_st_cam_of.p};
+    if (!c.lift) { A.n_sets = 1; A.set[0] = right; }   // no left camera is lifted on the device: the right set alone, which brings its own cameras and list (A.cams / A.cam_of may be null tables then and are not read)
+    else if (c.n_st_lift) { A.n_sets = 3; A.set[2] = right; }
+    if (!c.n_st_lift && !c.any_prev && !c.any_want) return GF_OK;
+    h->lift_launches++; h->lift_sequences += c.n_lift + c.n_st_lift;
     return camera_lift_launch(A, h->cap, h->stream);
 }
 
@@ -1182,6 +1326,7 @@ static int run_detect(Call& c) {
         if (h->d_seq_md.p) ho.down(h->d_seq_md, h->h_seq_md, N);
         ho.down(h->d_out_n, h->h_out_n, N);   // zeros (book_after_lk): a sequence that neither selection kernel serves reads 0, not an earlier call's count
         if (c.lift) ho.down(h->d_cam_of, h->h_cam_of, N);
+        if (c.n_stereo) stereo_down(c);
         if (int rc = ho.flush()) return rc;
         HIPCHK(hipMemsetAsync(h->d_maxkey.p, 0, N * sizeof(unsigned), h->stream));
         HIPCHK(hipMemsetAsync(h->d_cand_count.p, 0, N * sizeof(int), h->stream));
@@ -1194,7 +1339,9 @@ static int run_detect(Call& c) {
         const SelectArgs S = select_args(h, c.kdepth, topk ? 1 : 0);
         if (c.sized) launch_select_sized(h, N, S, topk, sort); else if (c.in.depth_by_refs()) launch_select<true>(h, N, S, topk, sort); else launch_select<false>(h, N, S, topk, sort);
         HIPCHK(hipGetLastError());
-        if (c.lift) if (int rc = launch_lift(c)) return rc;
+        if (c.n_stereo) if (int rc = launch_stereo(c)) return rc;
+        if (c.lift || c.n_st_lift) if (int rc = launch_lift(c)) return rc;
+        if (c.n_stereo) stereo_up(c);
         ho.up(h->h_out_n, h->d_out_n, N);
         ho.up(h->h_out_pts, h->d_out_pts, (size_t)N * cap);
         ho.up(h->h_out_depth, h->d_out_depth, (size_t)N * cap);
@@ -1203,11 +1350,14 @@ static int run_detect(Call& c) {
         if (int rc = ho.flush()) return rc;
     }
     if (prof && !c.any_want) HIPCHK(hipEventRecord(h->ev[4], h->stream));
-    if (c.lift && !c.any_want) {   // no sequence wants corners: the tracked points alone
-        ho.down(h->d_cam_of, h->h_cam_of, N);
+    if ((c.lift || c.n_stereo) && !c.any_want) {   // no sequence wants corners: the tracked points alone (the counts of new corners go down as the zeros book_after_lk wrote)
+        if (c.lift) ho.down(h->d_cam_of, h->h_cam_of, N);
+        if (c.n_stereo) { stereo_down(c); ho.down(h->d_out_n, h->h_out_n, N); }
         if (int rc = ho.flush()) return rc;
-        if (int rc = launch_lift(c)) return rc;
-        ho.up(h->h_un_lk, h->d_un_lk, (size_t)N * cap);
+        if (c.n_stereo) if (int rc = launch_stereo(c)) return rc;
+        if (c.lift || c.n_st_lift) if (int rc = launch_lift(c)) return rc;
+        if (c.lift) ho.up(h->h_un_lk, h->d_un_lk, (size_t)N * cap);
+        if (c.n_stereo) stereo_up(c);
         if (int rc = ho.flush()) return rc;
     }
     if (prof) HIPCHK(hipEventRecord(h->ev[5], h->stream));
@@ -1254,13 +1404,17 @@ static int book_after_detect(Call& c, gf_feature_obs* out, int cap_out, int* n_o
     const int cap = h->cap;
     const bool have_depth = c.in.have_depth();
     std::atomic<int> a_overflow{-1};
-    std::atomic<long long> a_out{0};
+    std::atomic<long long> a_out{0}, a_st_points{0}, a_st_matched{0};
     h->pool->parallel_for(c.N, [&](int b) {   // b: list position
         const int q = c.seq[b];
         const DetectRows r{row(h->h_out_pts, b, cap), c.in.kernel_samples(h->h_out_depth, b, cap), h->h_want.p[b] > 0 ? h->h_out_n.p[b] : 0, c.in.host_image(b, h->par[q]), c.in.host_dstride};
         const bool own = !h->cam_on.empty() && h->cam_on[q], dev = own && c.lift && h->lifts_on_device(q);
-        const Packed p = after_detect(h->seq[q], h->par[q], r, have_depth, out + (size_t)b * cap_out, cap_out, own ? &h->cam[q] : nullptr,
-                                      dev ? row(h->h_un_lk, b, cap) : nullptr, dev ? row(h->h_un_out, b, cap) : nullptr);
+        const bool stereo = c.n_stereo && h->h_st_right_of.p[b] >= 0;   // the frame came with a right image: the stage runs (after_detect, at the reference's place)
+        const StereoRows sr{stereo ? row(h->h_st_pts, b, cap) : nullptr, stereo ? h->h_st_status.p + (size_t)b * cap : nullptr, stereo ? &h->st_cam[q] : nullptr,
+                            stereo && h->h_st_cam_of.p[b] >= 0 ? row(h->h_st_un, b, cap) : nullptr};
+        const Packed p = after_detect(h->seq[q], h->par[q], r, have_depth && !h->stereo_on(q), out + (size_t)b * cap_out, cap_out, own ? &h->cam[q] : nullptr,
+                                      dev ? row(h->h_un_lk, b, cap) : nullptr, dev ? row(h->h_un_out, b, cap) : nullptr, stereo ? &sr : nullptr);
+        if (stereo) { a_st_points += (long long)h->seq[q].prev_pts.size(); a_st_matched += (long long)h->seq[q].ids_right.size(); }
         if (h->seq[q].show_track) (void)record_track(h->seq[q], h->boxes.empty() ? nullptr : h->boxes[q].data(), h->boxes.empty() ? 0 : (int)h->boxes[q].size());   // a refused list: the sequence has no picture of this frame, and keeps the reason (draw_why)
         if (p.overflow >= 0) a_overflow = p.overflow;
         n_out[b] = p.written;
@@ -1268,6 +1422,7 @@ static int book_after_detect(Call& c, gf_feature_obs* out, int cap_out, int* n_o
     });
     if (a_overflow.load() >= 0) return set_err(GF_ERR_CAPACITY, "output capacity %d < %d features", cap_out, a_overflow.load());
     h->stats.output_features += a_out;
+    if (c.n_stereo) { h->st_stats.calls++; h->st_stats.points += a_st_points; h->st_stats.matched += a_st_matched; }
     return GF_OK;
 }
 
@@ -1283,6 +1438,7 @@ static int track_core(gf_tracker* h, int count, const int* seq, const double* t,
     if (int rc = publish(c)) return rc;
     if (int rc = launch_front(c)) return rc;
     if (c.n_reg) if (int rc = launch_depth_reg(c)) return rc;
+    if (c.n_stereo) if (int rc = launch_right_pyramids(c)) return rc;
     if (int rc = run_lk(c)) return rc;
     if (int rc = redo_fallback(c)) return rc;
     book_after_lk(c);
@@ -1426,6 +1582,13 @@ static int check_refs(const gf_tracker* h, int count, const int* seq, const gf_f
         if (h->size_any && own_size) row_bytes = own_rows ? gfseqfmt::row_bytes(seq_width(h, seq[i]), h->fmt[seq[i]].pixel_format) : (size_t)seq_width(h, seq[i]) * own_size;   // a row of the sequence's own width (gf_tracker_set_seq_size)
         const bool raw_depth = u16 && !h->dreg_on.empty() && h->dreg_on[seq[i]];   // the raw frame of the sequence's depth camera (gf_tracker_set_seq_depth_reg)
         const size_t need = raw_depth ? (size_t)h->dreg[seq[i]].width * 2 : row_bytes;
+        if (u16 && h->stereo_on(seq[i])) {   // the second entry of a stereo sequence is its right frame: 8-bit, any pointer or pitch, or null (`_img1.empty()`)
+            const size_t rrow = (size_t)seq_width(h, seq[i]);
+            const gfref::Verdict rv = gfref::check(refs[i], rrow, false, true);
+            if (rv != gfref::kOk)
+                return set_err(GF_ERR_INVALID, "right frame at list position %d (sequence %d): %s (data %p, pitch %zu bytes, a row is %zu bytes)", i, seq[i], gfref::verdict_text(rv), refs[i].data, refs[i].pitch, rrow);
+            continue;
+        }
         const gfref::Verdict v = gfref::check(refs[i], need, u16, u16 && !h->par[seq[i]].depth_cam);
         if (v != gfref::kOk)
             return set_err(GF_ERR_INVALID, "%s frame at list position %d (sequence %d): %s (data %p, pitch %zu bytes, a row is %zu bytes)", raw_depth ? "raw depth" : what, i, seq[i], gfref::verdict_text(v), refs[i].data, refs[i].pitch, need);
@@ -1730,6 +1893,7 @@ int gf_tracker_set_seq_cfg(gf_tracker* h, int seq, const gf_tracker_seq_cfg* c) 
     const gf_tracker_seq_cfg want = c ? *c : gfseq::of_handle(h->cfg);
     char msg[256];
     if (c && !gfseq::fits(h->cfg, want, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "sequence %d: %s", seq, msg);
+    if (want.depth_cam && h->stereo_on(seq)) return gf::set_err(GF_ERR_INVALID, "sequence %d is a stereo sequence (gf_tracker_set_seq_stereo): stereo and depth_cam exclude each other", seq);
     if (!c && !h->d_seq_disk.p) return GF_OK;   // nothing to take back: the handle stays one that never set any
     if (int rc = gf::seq_cfg_ready(h)) return rc;
     gf::DiskTable row;
@@ -1829,6 +1993,7 @@ int gf_tracker_get_seq_camera(gf_tracker* h, int seq, gf_camera_model* out) {
 }
 
 // ---- a pixel format and an equalise switch per sequence (gf_seq_format.hpp; rosNodeTest.cpp:238-261 per camera).  Between frames, with the stream drained.
+namespace gf { static int stereo_eq_ready(gf_tracker* h); }
 int gf_tracker_set_seq_format(gf_tracker* h, int seq, const gf_tracker_seq_format* f) {
     if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
     if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
@@ -1838,6 +2003,8 @@ int gf_tracker_set_seq_format(gf_tracker* h, int seq, const gf_tracker_seq_forma
     const int W = h->cfg.width, H = h->cfg.height, B = h->B;
     char msg[256];
     if (f && !gfseqfmt::fits(gf::seq_width(h, seq), gf::seq_height(h, seq), want, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "sequence %d: %s", seq, msg);   // (rows of the sequence's own width)
+    if (h->stereo_on(seq) && want.pixel_format != GF_PIX_MONO8)
+        return gf::set_err(GF_ERR_INVALID, "sequence %d is a stereo sequence (gf_tracker_set_seq_stereo): it takes GF_PIX_MONO8 frames only, got pixel format %d", seq, want.pixel_format);
     if (!f && !h->fmt_any) return GF_OK;   // nothing to take back: the handle stays one that never set any
     // what a handle created with that format would have, into locals first: a failed allocation changes nothing
     const size_t px = (size_t)W * H;
@@ -1853,6 +2020,7 @@ int gf_tracker_set_seq_format(gf_tracker* h, int seq, const gf_tracker_seq_forma
     if (need_eq) { h->d_eq = std::move(eq); h->d_eq_lut = std::move(lut); }
     if (need_raw) { h->d_raw = std::move(raw); if (h->d_raw2.p) h->d_raw2 = std::move(raw2); h->raw_ch = ch; }   // nothing is staged and the stream is drained: no frame is lost
     if (need_mix) { h->d_mix = std::move(dmix); h->h_mix = std::move(hmix); }
+    if (h->stereo_on(seq) && want.equalize) if (int rc = gf::stereo_eq_ready(h)) return rc;   // the node equalises both eyes
     h->fmt[seq] = want;
     h->fmt_any = true;
     return GF_OK;
@@ -1953,6 +2121,7 @@ int gf_tracker_set_seq_depth_reg(gf_tracker* h, int seq, const gf_depth_reg* reg
     if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
     char msg[320];
     if (reg && !gfdreg::check(*reg, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "sequence %d: %s", seq, msg);
+    if (reg && h->stereo_on(seq)) return gf::set_err(GF_ERR_INVALID, "sequence %d is a stereo sequence (gf_tracker_set_seq_stereo): stereo and a depth registration exclude each other", seq);
     if (!reg && h->dreg_on.empty()) return GF_OK;   // nothing to take back, whatever the sequence's state: the handle stays one that never set any
     if (h->seq[seq].started) return gf::set_err(GF_ERR_INVALID, "sequence %d has taken a frame: its depth registration is fixed until gf_tracker_reset_seq", seq);
     if (gf::seq_is_staged(h, seq)) return gf::set_err(GF_ERR_INVALID, "sequence %d is listed by a staged frame: gf_tracker_track_prefetched has to consume it first (depth registration)", seq);
@@ -2015,6 +2184,78 @@ int gf_tracker_get_seq_reject_f(gf_tracker* h, int seq, gf_reject_f_cfg* out) {
 int gf_tracker_get_reject_f_stats(gf_tracker* h, gf_reject_f_stats* out) {
     if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
     *out = h->rf_stats;
+    return GF_OK;
+}
+
+// ---- a right camera per sequence (the stereo branch, feature_tracker.cpp:259-303; gf_stereo_kernels.hpp).  Between frames, with the stream drained.
+namespace gf {
+static int seq_stereo_ready(gf_tracker* h) {   // the first setter of a handle that turns a switch on: the right pyramids, the table of sizes, the call's tables
+    if (h->d_rimg.p) return GF_OK;
+    if (int rc = seq_size_ready(h)) return rc;   // the kernel reads a SizeRow per block: the table of sizes (row 0: the handle's own), and with it the frame table
+    const size_t B = (size_t)h->B, rows = B * h->cap;
+    DevBuf<uint8_t> rimg, dsz, dfb, dst, dfw; PinBuf<uint8_t> hsz, hfb, hst;
+    DevBuf<int> dro, dlo, dnt, drw, dcu; PinBuf<int> hro, hlo, hnt, hrw, hcu;
+    DevBuf<float2> dpt, dun; PinBuf<float2> hpt, hun; DevBuf<gf_frame_ref> drf; PinBuf<gf_frame_ref> hrf;
+    DevBuf<gfcam::Camera> dcm; DevBuf<int> dco, dsn; PinBuf<int> hco;
+    HIPCHK(dun.alloc(rows)); HIPCHK(hun.alloc(rows)); HIPCHK(dcm.alloc(B)); HIPCHK(dco.alloc(B)); HIPCHK(dsn.alloc(B)); HIPCHK(hco.alloc(B));
+    HIPCHK(rimg.alloc(B * h->G.img_bytes));
+    HIPCHK(dsz.alloc(B)); HIPCHK(dfb.alloc(B)); HIPCHK(dst.alloc(rows)); HIPCHK(dfw.alloc(rows)); HIPCHK(hsz.alloc(B)); HIPCHK(hfb.alloc(B)); HIPCHK(hst.alloc(rows));
+    HIPCHK(dro.alloc(B)); HIPCHK(dlo.alloc(B)); HIPCHK(dnt.alloc(B)); HIPCHK(drw.alloc(rows)); HIPCHK(dcu.alloc(B));
+    HIPCHK(hro.alloc(B)); HIPCHK(hlo.alloc(B)); HIPCHK(hnt.alloc(B)); HIPCHK(hrw.alloc(rows)); HIPCHK(hcu.alloc(B));
+    HIPCHK(dpt.alloc(rows)); HIPCHK(hpt.alloc(rows)); HIPCHK(drf.alloc(B)); HIPCHK(hrf.alloc(B));
+    h->d_rimg = std::move(rimg); h->d_st_size_of = std::move(dsz); h->d_st_fb = std::move(dfb); h->d_st_status = std::move(dst); h->d_st_fwd = std::move(dfw);
+    h->h_st_size_of = std::move(hsz); h->h_st_fb = std::move(hfb); h->h_st_status = std::move(hst);
+    h->d_st_right_of = std::move(dro); h->d_st_left_of = std::move(dlo); h->d_st_ntr = std::move(dnt); h->d_st_row = std::move(drw); h->d_st_cur = std::move(dcu);
+    h->h_st_right_of = std::move(hro); h->h_st_left_of = std::move(hlo); h->h_st_ntr = std::move(hnt); h->h_st_row = std::move(hrw); h->h_st_cur = std::move(hcu);
+    h->d_st_pts = std::move(dpt); h->h_st_pts = std::move(hpt); h->d_st_refs = std::move(drf); h->h_st_refs = std::move(hrf);
+    h->d_st_un = std::move(dun); h->h_st_un = std::move(hun); h->d_st_cams = std::move(dcm); h->d_st_cam_of = std::move(dco); h->d_st_n = std::move(dsn); h->h_st_cam_of = std::move(hco);
+    h->st_on.assign(B, 0); h->st_cfg.assign(B, gf_stereo_cfg{}); h->st_cam.assign(B, gfcam::Camera{});
+    return GF_OK;
+}
+static int stereo_eq_ready(gf_tracker* h) {   // the first stereo sequence that equalises: the right eye's frames, LUTs and table of sources
+    if (h->d_st_eq.p) return GF_OK;
+    const size_t B = (size_t)h->B;
+    DevBuf<uint8_t> eq, lut; DevBuf<gf_frame_ref> ds; PinBuf<gf_frame_ref> hs;
+    HIPCHK(eq.alloc(B * h->cfg.width * h->cfg.height)); HIPCHK(lut.alloc(clahe_lut_bytes((int)B, kClaheTiles, kClaheTiles))); HIPCHK(ds.alloc(B)); HIPCHK(hs.alloc(B));
+    h->d_st_eq = std::move(eq); h->d_st_eq_lut = std::move(lut); h->d_st_eqsrc = std::move(ds); h->h_st_eqsrc = std::move(hs);
+    return GF_OK;
+}
+}  // namespace gf
+
+int gf_tracker_set_seq_stereo(gf_tracker* h, int seq, const gf_stereo_cfg* c) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    if (c && c->enable != 0 && c->enable != 1) return gf::set_err(GF_ERR_INVALID, "sequence %d: gf_stereo_cfg.enable must be 0 or 1, got %d", seq, c->enable);
+    if (c && c->reserved != 0) return gf::set_err(GF_ERR_INVALID, "sequence %d: gf_stereo_cfg.reserved must be 0, got %d", seq, c->reserved);
+    const bool on = c && c->enable;
+    gfcam::Camera cam{};
+    char msg[320];
+    if (on && !gfcam::prepare(c->right, cam, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "sequence %d, right camera: %s", seq, msg);
+    if (!on && h->st_on.empty()) return GF_OK;   // nothing to take back, whatever the sequence's state: the handle stays one that never set any
+    if (h->seq[seq].started) return gf::set_err(GF_ERR_INVALID, "sequence %d has taken a frame: its right camera is fixed until gf_tracker_reset_seq", seq);
+    if (gf::seq_is_staged(h, seq)) return gf::set_err(GF_ERR_INVALID, "sequence %d is listed by a staged frame: gf_tracker_track_prefetched has to consume it first (stereo)", seq);
+    if (on && h->par[seq].depth_cam) return gf::set_err(GF_ERR_INVALID, "sequence %d has a depth camera (depth_cam 1): its second image is a depth frame, not a right frame; stereo and depth_cam exclude each other", seq);
+    if (on && !h->dreg_on.empty() && h->dreg_on[seq]) return gf::set_err(GF_ERR_INVALID, "sequence %d has a depth registration: stereo and a depth registration exclude each other", seq);
+    if (on && h->fmt[seq].pixel_format != GF_PIX_MONO8) return gf::set_err(GF_ERR_INVALID, "sequence %d has pixel format %d: a stereo sequence takes GF_PIX_MONO8 frames only", seq, h->fmt[seq].pixel_format);
+    if (int rc = gf::seq_stereo_ready(h)) return rc;
+    if (on && h->fmt[seq].equalize) if (int rc = gf::stereo_eq_ready(h)) return rc;
+    if (on) HIPCHK(hipMemcpy(h->d_st_cams.p + seq, &cam, sizeof cam, hipMemcpyHostToDevice));
+    h->st_on[seq] = on ? 1 : 0;
+    h->st_cfg[seq] = on ? *c : gf_stereo_cfg{};
+    h->st_cam[seq] = cam;
+    return GF_OK;
+}
+
+int gf_tracker_get_seq_stereo(gf_tracker* h, int seq, gf_stereo_cfg* out) {
+    if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    *out = h->stereo_on(seq) ? h->st_cfg[seq] : gf_stereo_cfg{};
+    return GF_OK;
+}
+
+int gf_tracker_get_stereo_stats(gf_tracker* h, gf_stereo_stats* out) {
+    if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    *out = h->st_stats;
     return GF_OK;
 }
 
@@ -2142,7 +2383,7 @@ int gf_tracker_get_state(gf_tracker* h, int seq, int* ids, int* track_cnt, float
 
 int gf_tracker_set_profiling(gf_tracker* h, int enable) { if (!h) return gf::set_err(GF_ERR_INVALID, "null handle"); h->profiling = enable != 0; return GF_OK; }
 int gf_tracker_get_stats(gf_tracker* h, gf_tracker_stats* out) { if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument"); *out = h->stats; return GF_OK; }
-int gf_tracker_reset_stats(gf_tracker* h) { if (!h) return gf::set_err(GF_ERR_INVALID, "null handle"); h->stats = gf_tracker_stats{}; h->dreg_launches = h->dreg_frames = 0; h->dreg_ms = 0; h->lift_launches = h->lift_sequences = 0; h->rf_stats = gf_reject_f_stats{}; return GF_OK; }
+int gf_tracker_reset_stats(gf_tracker* h) { if (!h) return gf::set_err(GF_ERR_INVALID, "null handle"); h->stats = gf_tracker_stats{}; h->dreg_launches = h->dreg_frames = 0; h->dreg_ms = 0; h->lift_launches = h->lift_sequences = 0; h->rf_stats = gf_reject_f_stats{}; h->st_stats = gf_stereo_stats{}; return GF_OK; }
 
 // ------------------------------------------------------------------ building blocks for parity tests
 static int tmp_handle(int width, int height, int max_cnt, int min_dist, std::unique_ptr<gf_tracker>& own) {
@@ -2190,6 +2431,111 @@ int gf_lk_track(const uint8_t* prev, const uint8_t* next, int width, int height,
     }
     if (iterations) *iterations = it;
     return GF_OK;
+}
+
+// ---- the stereo branch's left-to-right LK (feature_tracker.cpp:259-303; gf_stereo_kernels.hpp) on pairs of frames: the building block of the parity tests
+namespace gf {
+// one launch of stereo_lk_sized_kernel over `count` list positions whose point rows are `cap` long
+static int stereo_lk_launch(const SizeRow* rows, const uint8_t* size_of, size_t slot_bytes, const StereoLkArgs& A, int count, hipStream_t stream) {
+    if (count < 1 || A.cap < 1) return GF_OK;
+    stereo_lk_sized_kernel<<<dim3((A.cap + 3) / 4, count), 256, 0, stream>>>(rows, size_of, slot_bytes, A);
+    HIPCHK(hipGetLastError());
+    return GF_OK;
+}
+
+static int stereo_match_check(const char* who, const void* left, const void* right, int count, const int* first, const float* pts_xy, const uint8_t* flow_back,
+                              const float* right_xy, const uint8_t* status, int* most) {
+    if (!left || !right || !first || !flow_back) return set_err(GF_ERR_INVALID, "%s: null argument", who);
+    if (count < 1) return set_err(GF_ERR_INVALID, "%s: %d pairs (must be >= 1)", who, count);
+    if (first[0] != 0) return set_err(GF_ERR_INVALID, "%s: first[0] is %d, not 0", who, first[0]);
+    *most = 0;
+    for (int b = 0; b < count; b++) {
+        const int m = first[b + 1] - first[b];
+        if (m < 0) return set_err(GF_ERR_INVALID, "%s: first[%d] = %d is below first[%d] = %d", who, b + 1, first[b + 1], b, first[b]);
+        *most = std::max(*most, m);
+    }
+    if (first[count] > 0 && (!pts_xy || !right_xy || !status)) return set_err(GF_ERR_INVALID, "%s: null point table", who);
+    return GF_OK;
+}
+
+// d_left, d_right: `count` tight MONO8 frames each, on the device.  A handle of `count` sequences lives for the call: pair b's left frame goes to pyramid 2 b,
+// its right frame to pyramid 2 b + 1, by the route a frame of that size takes in the tracker.  The points go through both of the kernel's sources, as a tracker
+// call's do: the first half of a pair's list as rows of LK's table (stored there in reverse order, so that the gather moves every one), the rest as new corners.
+static int stereo_match_run(const uint8_t* d_left, const uint8_t* d_right, int count, int width, int height, const int* first, const float* pts_xy, const uint8_t* flow_back,
+                            float* right_xy, uint8_t* status, uint8_t* fwd_status, int most) {
+    gf_tracker_cfg c{};
+    c.width = width; c.height = height; c.batch = count; c.max_cnt = std::max(most, 1); c.min_dist = 30; c.fx = c.fy = 1;
+    gf_tracker* raw = nullptr;
+    if (int rc = gf_tracker_create(&c, &raw)) return rc;
+    std::unique_ptr<gf_tracker> own(raw);   // the handle lives for this call
+    gf_tracker* h = raw;
+    const int cap = h->cap;
+    const size_t rows_n = (size_t)count * cap;
+    DevBuf<SizeRow> d_rows; DevBuf<uint8_t> d_size_of; DevBuf<int> d_row; DevBuf<float2> d_right_pts; PinBuf<int> h_row; PinBuf<float2> h_right_pts;
+    HIPCHK(d_rows.alloc(1)); HIPCHK(d_size_of.alloc(count)); HIPCHK(d_row.alloc(rows_n)); HIPCHK(d_right_pts.alloc(rows_n)); HIPCHK(h_row.alloc(rows_n)); HIPCHK(h_right_pts.alloc(rows_n));
+    SizeRow sr{};
+    sr.G = h->G; sr.w = width; sr.h = height;
+    HIPCHK(hipMemcpy(d_rows.p, &sr, sizeof sr, hipMemcpyHostToDevice));
+    for (int b = 0; b < count; b++) {
+        const int n = first[b + 1] - first[b], nt = n / 2;
+        h->h_cur.p[b] = 2 * b; h->h_det.p[b] = 2 * b + 1;
+        h->h_npts.p[b] = nt; h->h_out_n.p[b] = n - nt;
+        h->h_seqmask.p[b] = flow_back[b] ? 1 : 0;
+        const float* p = pts_xy + 2 * (size_t)first[b];
+        for (int k = 0; k < nt; k++) { h_row.p[(size_t)b * cap + k] = nt - 1 - k; h->h_cur_pts.p[(size_t)b * cap + (nt - 1 - k)] = make_float2(p[2 * k], p[2 * k + 1]); }
+        for (int k = nt; k < n; k++) h->h_out_pts.p[(size_t)b * cap + (k - nt)] = make_float2(p[2 * k], p[2 * k + 1]);
+    }
+    HIPCHK(hipMemcpyAsync(h->d_cur.p, h->h_cur.p, count * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_det.p, h->h_det.p, count * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_npts.p, h->h_npts.p, count * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_out_n.p, h->h_out_n.p, count * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_seqmask.p, h->h_seqmask.p, count, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_row.p, h_row.p, rows_n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_cur_pts.p, h->h_cur_pts.p, rows_n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_out_pts.p, h->h_out_pts.p, rows_n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
+    if (int rc = launch_pyramid(h, d_left, count, h->d_cur.p)) return rc;
+    if (int rc = launch_pyramid(h, d_right, count, h->d_det.p)) return rc;
+    StereoLkArgs A{};
+    A.left = h->d_img.p; A.left_of = h->d_cur.p; A.right = h->d_img.p; A.right_of = h->d_det.p; A.cap = cap;
+    A.n_tracked = h->d_npts.p; A.row = d_row.p; A.lk_pts = h->d_cur_pts.p; A.n_new = h->d_out_n.p; A.new_pts = h->d_out_pts.p;
+    A.flow_back_of = h->d_seqmask.p; A.right_pts = d_right_pts.p; A.status = h->d_status.p; A.fwd_status = h->d_fwd_status.p;
+    if (int rc = stereo_lk_launch(d_rows.p, d_size_of.p, h->G.img_bytes, A, count, h->stream)) return rc;
+    HIPCHK(hipMemcpyAsync(h_right_pts.p, d_right_pts.p, rows_n * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->h_status.p, h->d_status.p, rows_n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(h->h_fwd_status.p, h->d_fwd_status.p, rows_n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int b = 0; b < count; b++)
+        for (int k = 0, n = first[b + 1] - first[b]; k < n; k++) {
+            const size_t at = (size_t)b * cap + k, o = (size_t)first[b] + k;
+            right_xy[2 * o] = h_right_pts.p[at].x; right_xy[2 * o + 1] = h_right_pts.p[at].y;
+            status[o] = h->h_status.p[at];
+            if (fwd_status) fwd_status[o] = h->h_fwd_status.p[at];
+        }
+    return GF_OK;
+}
+}  // namespace gf
+
+int gf_stereo_match_batch_device(const void* d_left, const void* d_right, int count, int width, int height, const int* first, const float* pts_xy, const uint8_t* flow_back,
+                                 float* right_xy, uint8_t* status, uint8_t* fwd_status) {
+    int most = 0;
+    if (int rc = gf::stereo_match_check("gf_stereo_match_batch_device", d_left, d_right, count, first, pts_xy, flow_back, right_xy, status, &most)) return rc;
+    if ((reinterpret_cast<uintptr_t>(d_left) | reinterpret_cast<uintptr_t>(d_right)) & 3)
+        return gf::set_err(GF_ERR_INVALID, "gf_stereo_match_batch_device: frames at %p and %p, not on 4-byte boundaries", d_left, d_right);
+    return gf::stereo_match_run(static_cast<const uint8_t*>(d_left), static_cast<const uint8_t*>(d_right), count, width, height, first, pts_xy, flow_back, right_xy, status, fwd_status, most);
+}
+
+int gf_stereo_match_batch(const uint8_t* left, const uint8_t* right, int count, int width, int height, const int* first, const float* pts_xy, const uint8_t* flow_back,
+                          float* right_xy, uint8_t* status, uint8_t* fwd_status) {
+    int most = 0;
+    if (int rc = gf::stereo_match_check("gf_stereo_match_batch", left, right, count, first, pts_xy, flow_back, right_xy, status, &most)) return rc;
+    if (width < 1 || height < 1) return gf::set_err(GF_ERR_INVALID, "gf_stereo_match_batch: width %d, height %d", width, height);
+    if (int rc = gf::require_device()) return rc;
+    const size_t bytes = (size_t)count * width * height;
+    gf::DevBuf<uint8_t> dl, dr;
+    HIPCHK(dl.fit(bytes)); HIPCHK(dr.fit(bytes));
+    HIPCHK(hipMemcpy(dl.p, left, bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dr.p, right, bytes, hipMemcpyHostToDevice));
+    return gf::stereo_match_run(dl.p, dr.p, count, width, height, first, pts_xy, flow_back, right_xy, status, fwd_status, most);
 }
 
 int gf_pyramid_level(const uint8_t* img, int width, int height, int level, uint8_t* out, int16_t* deriv_xy) {

@@ -319,6 +319,18 @@ class RejectFStats(C.Structure):
 assert C.sizeof(RejectFCfg) == 24 and C.sizeof(RejectFResult) == 16 and C.sizeof(RejectFStats) == 48
 
 
+class StereoCfg(C.Structure):
+    """gf_stereo_cfg: the stereo branch (feature_tracker.cpp:259-303) of a sequence -- the switch and the right camera"""
+    _fields_ = [("enable", C.c_int32), ("reserved", C.c_int32), ("right", CameraModelEx)]
+
+
+class StereoStats(C.Structure):
+    _fields_ = [("calls", C.c_longlong), ("launches", C.c_longlong), ("points", C.c_longlong), ("matched", C.c_longlong), ("right_pyramids", C.c_longlong)]
+
+
+assert C.sizeof(StereoCfg) == 360 and C.sizeof(StereoStats) == 40
+
+
 def _reject_f_tables(sets, thresholds, seeds):
     sets = [np.ascontiguousarray(s, np.float32).reshape(-1, 4) for s in sets]
     n = len(sets)
@@ -385,6 +397,13 @@ def reject_f_from_yaml(config_file):
     """gf_reject_f_from_yaml: F_threshold and this repository's `reject_with_f` switch of a config file -> RejectFCfg"""
     c = RejectFCfg()
     _chk(lib().gf_reject_f_from_yaml(os.fsencode(config_file), C.byref(c)))
+    return c
+
+
+def stereo_from_yaml(config_file):
+    """gf_stereo_from_yaml: `num_of_cam: 2` and `cam1_calib` of a config file -> StereoCfg (enable == 0 for any other num_of_cam)"""
+    c = StereoCfg()
+    _chk(lib().gf_stereo_from_yaml(os.fsencode(config_file), C.byref(c)))
     return c
 
 
@@ -799,6 +818,33 @@ class FeatureTracker:
         _chk(lib().gf_tracker_get_reject_f_stats(self.h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in RejectFStats._fields_}
 
+    def set_seq_stereo(self, seq, right=None):
+        """gf_tracker_set_seq_stereo: sequence `seq` gets a right camera (a CameraModel / CameraModelEx, or a StereoCfg) and with it the stereo branch of trackImage
+        (feature_tracker.cpp:259-303); None turns it off.  Before the sequence's first frame.  Its right frame is the second gf_frame_ref of its list position
+        on trackImageSomeDeviceRefs / trackImageBatchDeviceRefs.  A frame of a stereo sequence returns up to two observations per feature, so the first call that
+        turns a switch on DOUBLES self.cap, the row length of every `out` array (one allocated before with the old g.cap no longer fits: allocate after the
+        setters).  The unpacked form (ids, obs) of the frame-taking methods carries no camera id: the right observations are the rows behind the first occurrence
+        of a repeated id; with unpack=False, out[i]["camera_id"] tells the eyes apart."""
+        cfg = right if isinstance(right, StereoCfg) or right is None else StereoCfg(1, 0, CameraModelEx.of(right))
+        _chk(lib().gf_tracker_set_seq_stereo(self.h, int(seq), None if cfg is None else C.byref(cfg)))
+        if cfg is not None and cfg.enable and not getattr(self, "_stereo", False):   # a frame of a stereo sequence returns up to two observations per feature
+            self._stereo, self.cap = True, 2 * self.cap
+            for name in ("_out", "_n"):
+                if hasattr(self, name):
+                    delattr(self, name)
+
+    def get_seq_stereo(self, seq):
+        """gf_tracker_get_seq_stereo: the StereoCfg of sequence `seq` (enable == 0: off)"""
+        c = StereoCfg()
+        _chk(lib().gf_tracker_get_seq_stereo(self.h, int(seq), C.byref(c)))
+        return c
+
+    def stereo_stats(self):
+        """gf_tracker_get_stereo_stats: dict of calls, launches, points, matched, right_pyramids"""
+        s = StereoStats()
+        _chk(lib().gf_tracker_get_stereo_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in StereoStats._fields_}
+
     def camera_lift_stats(self):
         """gf_tracker_get_camera_lift_stats: dict of launches of camera_lift_kernel by this handle and of the listed sequences they lifted"""
         n, q = C.c_longlong(0), C.c_longlong(0)
@@ -1123,6 +1169,48 @@ def lk_track(prev, nxt, prev_pts, next_pts=None, max_level=3):
     _chk(lib().gf_lk_track(_p(prev, C.c_uint8), _p(nxt, C.c_uint8), w, h, _p(pp, C.c_float), _p(npn, C.c_float), _p(st, C.c_uint8),
                            len(pp), max_level, int(use_init), C.byref(it)))
     return npn, st, it.value
+
+
+EXPORTS += ["gf_stereo_match_batch", "gf_stereo_match_batch_device", "gf_tracker_set_seq_stereo", "gf_tracker_get_seq_stereo", "gf_tracker_get_stereo_stats", "gf_stereo_from_yaml"]
+
+
+def _stereo_tables(pts, flow_back):
+    """the point lists of a batch as gf_stereo_match_batch takes them: first[count + 1], the points back to back, a switch per pair"""
+    pts = [np.ascontiguousarray(p, np.float32).reshape(-1, 2) for p in pts]
+    first = np.zeros(len(pts) + 1, np.int32)
+    first[1:] = np.cumsum([len(p) for p in pts])
+    allp = np.ascontiguousarray(np.concatenate(pts) if pts else np.zeros((0, 2), np.float32), np.float32)
+    fb = np.ascontiguousarray(np.broadcast_to(np.asarray(flow_back, np.uint8), (len(pts),)), np.uint8)
+    n = max(int(first[-1]), 1)   # never a zero-length buffer behind a pointer
+    return pts, first, allp, fb, np.zeros((n, 2), np.float32), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+
+
+def _stereo_out(first, right, st, fwd):
+    return [(right[a:b].copy(), st[a:b].copy(), fwd[a:b].copy()) for a, b in zip(first[:-1], first[1:])]
+
+
+def stereo_match(left, right, pts, flow_back=1):
+    """gf_stereo_match_batch: left, right [count, h, w] u8 (or lists of frames of one size), pts a list of [n_b, 2] point lists, flow_back one switch or one per
+    pair -> per pair (right_pts [n_b, 2] float32, status [n_b] u8, fwd_status [n_b] u8)"""
+    left = np.ascontiguousarray(np.stack([np.asarray(f, np.uint8) for f in left]))
+    right = np.ascontiguousarray(np.stack([np.asarray(f, np.uint8) for f in right]))
+    if left.shape != right.shape or left.ndim != 3 or len(left) != len(pts):
+        raise GfError("stereo_match: %s left frames, %s right frames, %d point lists" % (left.shape, right.shape, len(pts)))
+    count, h, w = left.shape
+    _, first, allp, fb, out, st, fwd = _stereo_tables(pts, flow_back)
+    _chk(lib().gf_stereo_match_batch(_p(left, C.c_uint8), _p(right, C.c_uint8), count, w, h, _p(first, C.c_int), _p(allp, C.c_float), _p(fb, C.c_uint8),
+                                     _p(out, C.c_float), _p(st, C.c_uint8), _p(fwd, C.c_uint8)))
+    return _stereo_out(first, out, st, fwd)
+
+
+def stereo_match_device(d_left, d_right, count, width, height, pts, flow_back=1):
+    """gf_stereo_match_batch_device on integer device addresses of `count` tight frames each (e.g. torch tensor .data_ptr()); the point lists and results as stereo_match's"""
+    if count != len(pts):
+        raise GfError("stereo_match_device: %d pairs, %d point lists" % (count, len(pts)))
+    _, first, allp, fb, out, st, fwd = _stereo_tables(pts, flow_back)
+    _chk(lib().gf_stereo_match_batch_device(C.c_void_p(d_left), C.c_void_p(d_right), count, width, height, _p(first, C.c_int), _p(allp, C.c_float), _p(fb, C.c_uint8),
+                                            _p(out, C.c_float), _p(st, C.c_uint8), _p(fwd, C.c_uint8)))
+    return _stereo_out(first, out, st, fwd)
 
 
 def good_features(img, max_corners, min_dist=30, mask=None):

@@ -84,7 +84,12 @@ class FeatureTracker {
         const bool pin = camera_.model == GF_CAMERA_PINHOLE;   // another model: the handle's own pinhole is a valid placeholder that nothing reads
         k1_ = pin ? camera_.dist[0] : 0; k2_ = pin ? camera_.dist[1] : 0; p1_ = pin ? camera_.dist[2] : 0; p2_ = pin ? camera_.dist[3] : 0;
         depth_cam = depth != 0;
-        if (calib_file.size() == 2) stereo_cam = true;
+        if (calib_file.size() == 2) {   // the right camera (m_camera[1], feature_tracker.cpp:751-752): the stereo branch, gf_tracker_set_seq_stereo
+            stereo_ = gf_stereo_cfg{};
+            check(gf_camera_from_yaml_ex(calib_file[1].c_str(), &stereo_.right));
+            stereo_.enable = 1;
+            stereo_cam = true;
+        }
     }
     void setIntrinsics(int width, int height, double fx, double fy, double cx, double cy, double k1 = 0, double k2 = 0, double p1 = 0, double p2 = 0) {
         col = width; row = height; fx_ = fx; fy_ = fy; cx_ = cx; cy_ = cy; k1_ = k1; k2_ = k2; p1_ = p1; p2_ = p2;
@@ -183,6 +188,9 @@ class FeatureTracker {
         if (!h_) { pixel_format_ = _img.pixel_format; create(_img.cols, _img.rows); }
         // one handle has one format (a camera does not change its encoding): the first frame decides, as it decides the size
         if (_img.pixel_format != pixel_format_) throw std::runtime_error("trackImage: the image's pixel format differs from the first frame's");
+        if (stereo_cam && !_img1.empty())
+            throw std::runtime_error("trackImage: a stereo tracker takes its right image where it lies on the device, trackImage(double, const gf_frame_ref&, const gf_frame_ref&); "
+                                     "a host image pair is not served (without a second image the frame is tracked as a mono frame)");
         std::vector<gf_feature_obs> out((size_t)((MAX_CNT + 3) & ~3));
         int n = 0;
         check(gf_tracker_track(h_, 0, _cur_time, _img.data, _img.stride, _img1.empty() ? nullptr : _img1.data, _img1.stride, out.data(), (int)out.size(), &n));
@@ -197,12 +205,14 @@ class FeatureTracker {
     }
     // The same frame where it already lives on the device (gf_tracker_track_some_device_refs): _img = device pointer of row 0 and bytes from row to row of a
     // row x col image in pixel_format (any alignment: the luma plane of a decoder's NV12 surface, a crop of a wider image), _img1 = the u16 depth image likewise
-    // or {nullptr, 0}.  The frame size must be known (readIntrinsicParameter / setIntrinsics): a device pointer carries none.  Neither image is ever written.
+    // or {nullptr, 0}; for a stereo tracker (readIntrinsicParameter with two files) _img1 is the RIGHT image, 8-bit, of the same size, and the frame returns the
+    // camera_id 1 observations behind the left ones (feature_tracker.cpp:259-303).  The frame size must be known (readIntrinsicParameter / setIntrinsics): a
+    // device pointer carries none.  Neither image is ever written.
     FeatureFrame trackImage(double _cur_time, const gf_frame_ref& _img, const gf_frame_ref& _img1 = gf_frame_ref{nullptr, 0}, int pixel_format = GF_PIX_MONO8) {
         if (!row || !col) throw std::runtime_error("trackImage: the frame size is not known yet (readIntrinsicParameter / setIntrinsics)");
         if (!h_) { pixel_format_ = pixel_format; create(col, row); }
         if (pixel_format != pixel_format_) throw std::runtime_error("trackImage: the image's pixel format differs from the first frame's");
-        std::vector<gf_feature_obs> out((size_t)((MAX_CNT + 3) & ~3));
+        std::vector<gf_feature_obs> out((size_t)((MAX_CNT + 3) & ~3) * (stereo_cam ? 2 : 1));   // both eyes
         int n = 0;
         const int seq = 0;
         check(gf_tracker_track_some_device_refs(h_, 1, &seq, &_cur_time, &_img, _img1.data ? &_img1 : nullptr, out.data(), (int)out.size(), &n));
@@ -252,6 +262,7 @@ class FeatureTracker {
     std::vector<gf_box> boxes_;  // exclusion boxes set before the handle exists
     gf_depth_reg depth_reg_{}; bool has_depth_reg_ = false;   // setDepthRegistration, kept for a handle that does not exist yet
     gf_reject_f_cfg reject_f_{};                              // setRejectWithF, likewise
+    gf_stereo_cfg stereo_{};                                  // readIntrinsicParameter's second file, likewise
     static void check(int rc) { if (rc != GF_OK) throw std::runtime_error(std::string("groundfusion_hip: ") + gf_last_error()); }
     void create(int w, int h) {
         gf_tracker_cfg c{};
@@ -267,6 +278,7 @@ class FeatureTracker {
         if (show_track_) setShowTrack(true);
         if (has_depth_reg_) check(gf_tracker_set_seq_depth_reg(h_, 0, &depth_reg_));
         if (reject_f_.enable) check(gf_tracker_set_seq_reject_f(h_, 0, &reject_f_));
+        if (stereo_.enable) check(gf_tracker_set_seq_stereo(h_, 0, &stereo_));
     }
     void refresh() {
         const int cap = (MAX_CNT + 3) & ~3;

@@ -396,7 +396,9 @@ int gf_tracker_get_seq_camera_ex(gf_tracker* h, int seq, gf_camera_model_ex* out
  * for every model: 1 all on the host, 0 all on the device.  A sequence lifted on the host is not listed for the kernel; a call lists either some sequence
  * and has ONE launch of camera_lift_kernel, whatever the mix of models, or none and has no launch.
  * The lift's own counters (gf_tracker_stats keeps its layout), each may be NULL: launches of camera_lift_kernel by this handle, and listed sequences those
- * launches lifted, summed.  gf_tracker_reset_stats zeroes them. */
+ * launches lifted, summed.  A stereo sequence (gf_tracker_set_seq_stereo) whose RIGHT camera is lifted on the device is one more list entry of the same launch
+ * and counts as one more listed sequence: `sequences` sums left and right lifts, and a call in which only right cameras are lifted still has its one launch.
+ * gf_tracker_reset_stats zeroes them. */
 int gf_tracker_get_camera_lift_stats(gf_tracker* h, long long* launches, long long* sequences);
 /* gf_camera_lift_batch, gf_camera_lift_batch_device and gf_camera_project_batch with cameras of any of the five models */
 int gf_camera_lift_batch_ex(const gf_camera_model_ex* cams, int batch, const int* first, const float* uv, double* rays, float* un);
@@ -501,7 +503,48 @@ int gf_tracker_set_seq_reject_f(gf_tracker* h, int seq, const gf_reject_f_cfg* c
 int gf_tracker_get_seq_reject_f(gf_tracker* h, int seq, gf_reject_f_cfg* out);
 /* the stage's own counters (feature_tracker.cpp:711-743); gf_tracker_reset_stats zeroes them */
 int gf_tracker_get_reject_f_stats(gf_tracker* h, gf_reject_f_stats* out);
-/* The stage as a building block (feature_tracker.cpp:731-736, the findFundamentalMat call), through the tracker's kernel: set b of n has the virtual-pixel pairs
+
+/* ---- a right camera per sequence: the stereo branch of trackImage (feature_tracker.cpp:259-303, kept there as VINS-Fusion wrote it, commented out; its place is
+ * behind undistortedPts / ptsVelocity of the left, :210-211, and ahead of the roll-over, :307-312).  DESIGN.md section 4, "Stereo", is the definition. */
+typedef struct gf_stereo_cfg {
+    int enable;                 /* 1: the sequence has a right camera (stereo_cam, feature_tracker.cpp:751-752) */
+    int reserved;               /* must be 0 */
+    gf_camera_model_ex right;   /* m_camera[1] (:298): the camera cur_right_pts is lifted through */
+} gf_stereo_cfg;
+typedef struct gf_stereo_stats {
+    long long calls;            /* tracker calls that ran the stage for at least one sequence */
+    long long launches;         /* launches of the stereo kernel (one per such call) */
+    long long points;           /* points submitted: cur_pts of every sequence and frame the stage ran for (:273) */
+    long long matched;          /* points kept: entries of ids_right (:286-288) */
+    long long right_pyramids;   /* right pyramids built */
+} gf_stereo_stats;
+/* The switch and the right camera of seq, before its first frame like the other per-sequence setters (c == NULL or enable == 0: off).  A stereo sequence takes
+ * its right frame (`_img1`, :259) where the reference's travels: the second gf_frame_ref of its list position on gf_tracker_track_some_device_refs /
+ * gf_tracker_track_batch_device_refs, 8-bit, of the sequence's own size, with any pointer or pitch (the "even" rule stays for depth entries).  An entry with
+ * data == NULL is `_img1.empty()`: the stage is skipped for that frame and the right-hand state stays as it is, so the next frame with a right image takes its
+ * velocities against the map of the last frame that ran the stage, over the newest dt.  With a right frame the call returns the left observations as ever, then
+ * one observation per entry of ids_right in that order: camera_id 1, v = (x_un_right, y_un_right, 1, u_right, v_right, vx_right, vy_right, -2.4); n_out counts
+ * both and the capacity rule holds for the sum.  Forward LK from the left frame to the right on all of cur_pts and, with the sequence's own FLOW_BACK, the
+ * reverse pass and the 0.5 px test (:273-284) run in ONE launch per call for all its stereo sequences, behind the corner selection; the right camera's lift
+ * (:298) takes the route its model takes on the left: PINHOLE on the host, the others as one more list entry of the call's camera_lift_kernel launch
+ * (GF_CAMERA_LIFT_HOST is honoured).  A sequence that equalises equalises both eyes (rosNodeTest.cpp:256-261).  On the host-image, tight and prefetch entry points a stereo sequence listed without a second image is a mono frame; with one the
+ * call is refused by name, nothing changed.  Refused by name, nothing changed: a sequence that has taken a frame or is listed by a staged one, reserved != 0,
+ * a right camera gf_camera_model_ex's rules refuse, stereo together with depth_cam or a depth registration, and a pixel format other than GF_PIX_MONO8.
+ * gf_tracker_set_seq_cfg / _format / _depth_reg refuse the same
+ * combinations from their side.  removeOutliers and setPrediction act on the left lists only; gf_tracker_reset_seq clears the right-hand state.  The first
+ * setter of a handle that turns a switch on allocates the right pyramids and the call's tables; a handle on which it is never called allocates, copies and
+ * launches exactly what it did without it. */
+int gf_tracker_set_seq_stereo(gf_tracker* h, int seq, const gf_stereo_cfg* c);
+/* the configuration of seq as it was set; enable == 0 and zeros if it is off (feature_tracker.cpp:259) */
+int gf_tracker_get_seq_stereo(gf_tracker* h, int seq, gf_stereo_cfg* out);
+/* the stage's own counters (feature_tracker.cpp:259-303); gf_tracker_reset_stats zeroes them */
+int gf_tracker_get_stereo_stats(gf_tracker* h, gf_stereo_stats* out);
+/* The switch and the right camera from a config file (feature_tracker.cpp:259; parameters.cpp:424-436): `num_of_cam: 2` turns the switch on and `cam1_calib` names
+ * the right camera's calibration file beside the config file, read as gf_camera_from_yaml_ex reads one; any other num_of_cam: enable == 0 and zeros, no second
+ * file is read.  GF_ERR_INVALID, naming the file and the key: num_of_cam 2 without cam1_calib, a calibration file that cannot be read or that
+ * gf_camera_from_yaml_ex refuses. */
+int gf_stereo_from_yaml(const char* config_file, gf_stereo_cfg* out);
+/* rejectWithF as a building block (feature_tracker.cpp:731-736, the findFundamentalMat call), through the tracker's kernel: set b of n has the virtual-pixel pairs
  * pairs[4 first[b] .. 4 first[b + 1]) as ax ay bx by (a: previous frame, b: current), at most GF_REJECT_F_MAX_PAIRS of them, the threshold f_threshold[b] and
  * the seed seed[b], used as it is.  first, f_threshold, seed and results (may be NULL) are host tables; d_pairs and d_status are device memory.  d_status IS
  * WRITTEN: one byte per pair, 1 kept, 0 rejected.  One launch on `stream` (a hipStream_t, NULL = the null stream) whatever n; returns when it has run.  The call's job table is one
@@ -616,6 +659,21 @@ int gf_tracker_reset_stats(gf_tracker* h);
 int gf_lk_track(const uint8_t* prev, const uint8_t* next, int width, int height, const float* prev_pts,
                 float* next_pts, uint8_t* status, int n, int max_level, int use_initial_flow,
                 long long* iterations);
+/* The left-to-right matching of the stereo branch of FeatureTracker::trackImage (feature_tracker.cpp:259-303, kept there commented out), steps 2 and 3:
+ *   cv::calcOpticalFlowPyrLK(cur_img, rightImg, cur_pts, cur_right_pts, status, err, cv::Size(21, 21), 3)                     (:273)
+ * and, for a pair with FLOW_BACK,
+ *   cv::calcOpticalFlowPyrLK(rightImg, cur_img, cur_right_pts, reverseLeftPts, statusRightLeft, err, cv::Size(21, 21), 3)     (:277)
+ *   status[i] = status[i] && statusRightLeft[i] && inBorder(cur_right_pts[i]) && distance(cur_pts[i], reverseLeftPts[i]) <= 0.5   (:278-284)
+ * with the default criteria (30 iterations / 0.01) and no initial flow in either direction; without FLOW_BACK the status is the forward pass's alone and a
+ * right point may lie outside the image.  `count` pairs of tight width x height MONO8 frames, back to back in `left` and `right`; the points of pair b are
+ * pts_xy[2 first[b] .. 2 first[b + 1]) (first[0] = 0, [count + 1] entries), flow_back[b] its switch.  right_xy, status and fwd_status (the forward pass alone;
+ * may be null) are indexed like pts_xy.  One launch of the stereo kernel (stereo_lk_sized_kernel: one wavefront per point, lk_solve in both directions) for all
+ * pairs; a pair's points reach it through both of its sources, rows of an LK table and a list of new corners.  Width a multiple of 4, both sizes >= 32
+ * (gf_tracker_create's limits).  Synchronous.  The _device form takes the frames as device pointers on 4-byte boundaries; every other table is host memory. */
+int gf_stereo_match_batch(const uint8_t* left, const uint8_t* right, int count, int width, int height, const int* first, const float* pts_xy,
+                          const uint8_t* flow_back, float* right_xy, uint8_t* status, uint8_t* fwd_status);
+int gf_stereo_match_batch_device(const void* d_left, const void* d_right, int count, int width, int height, const int* first, const float* pts_xy,
+                                 const uint8_t* flow_back, float* right_xy, uint8_t* status, uint8_t* fwd_status);
 /* cv::goodFeaturesToTrack(img, corners, max_corners, 0.01, min_dist, mask) as called at feature_tracker.cpp:198 */
 int gf_good_features(const uint8_t* img, int width, int height, const uint8_t* mask, int max_corners,
                      int min_dist, float* corners_xy, int* n_out);
