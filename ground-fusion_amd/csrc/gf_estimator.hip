@@ -1985,6 +1985,42 @@ int gf_estimator_set_reject_f(gf_estimator* e, const gf_reject_f_cfg* c) {
     if (!e || !e->tracker) return gf::set_err(GF_ERR_INVALID, "estimator was created without a tracker (cfg.with_tracker)");
     return gf_tracker_set_seq_reject_f(e->tracker, 0, c);
 }
+// A stereo rig on the estimator's own tracker: its one sequence gets the right camera and the depth its matches determine (gf_tracker_set_seq_stereo,
+// gf_tracker_set_seq_stereo_depth), before the first frame.  The observations carry a depth, so the estimator must read one (cfg.depth 1), and the second image is
+// a right frame, so the tracker has no depth camera (cfg.tracker.depth_cam 0).  right_obs is forced to 0: addFeatureCheckParallax takes every entry of a frame as
+// a left observation, so it must see one per feature.
+int gf_estimator_set_stereo_depth(gf_estimator* e, const gf_stereo_cfg* stereo, const gf_stereo_depth_cfg* depth) {
+    if (!e || !e->tracker) return gf::set_err(GF_ERR_INVALID, "estimator was created without a tracker (cfg.with_tracker)");
+    if (!stereo || !depth) return gf::set_err(GF_ERR_INVALID, "gf_estimator_set_stereo_depth: null argument");
+    if (e->cfg.depth != 1) return gf::set_err(GF_ERR_INVALID, "gf_estimator_set_stereo_depth: cfg.depth is %d: the observations of a stereo-depth tracker carry a depth, which the estimator reads with cfg.depth = 1", e->cfg.depth);
+    if (e->cfg.tracker.depth_cam != 0) return gf::set_err(GF_ERR_INVALID, "gf_estimator_set_stereo_depth: cfg.tracker.depth_cam is %d: the second image of a stereo rig is a right frame, not a depth frame (cfg.tracker.depth_cam = 0)", e->cfg.tracker.depth_cam);
+    gf_stereo_cfg before;
+    if (int rc = gf_tracker_get_seq_stereo(e->tracker, 0, &before)) return rc;
+    if (int rc = gf_tracker_set_seq_stereo(e->tracker, 0, stereo)) return rc;
+    gf_stereo_depth_cfg d = *depth;
+    d.right_obs = 0;
+    if (int rc = gf_tracker_set_seq_stereo_depth(e->tracker, 0, &d)) {
+        const std::string why = gf_last_error();   // the right camera goes back to what it was: a refused call changes nothing
+        (void)gf_tracker_set_seq_stereo(e->tracker, 0, &before);
+        return gf::set_err(rc, "%s", why.c_str());
+    }
+    return GF_OK;
+}
+// Estimator::inputImage (EST:213-242) on frames that lie on the device, by reference: img1 is the depth frame of an RGB-D estimator or the right frame of a stereo
+// one (NULL or data == NULL: none).  The every-second-frame rule of multiple_thread as gf_estimator_input_image.
+int gf_estimator_input_image_refs(gf_estimator* e, double t, const gf_frame_ref* img0, const gf_frame_ref* img1, gf_feature_obs* out, int cap, int* n_out) {
+    if (!e || !e->tracker) return gf::set_err(GF_ERR_INVALID, "estimator was created without a tracker (cfg.with_tracker)");
+    if (!img0) return gf::set_err(GF_ERR_INVALID, "gf_estimator_input_image_refs: null argument");
+    std::vector<gf_feature_obs> tmp;
+    if (!out) { cap = 2 * (e->cfg.tracker.max_cnt + 8); tmp.resize(cap); out = tmp.data(); }
+    int n = 0;
+    const int seq = 0;
+    if (int rc = gf_tracker_track_some_device_refs(e->tracker, 1, &seq, &t, img0, img1 && img1->data ? img1 : nullptr, out, cap, &n)) return rc;
+    if (n_out) *n_out = n;
+    e->inputImageCnt++;
+    if (e->cfg.multiple_thread && e->inputImageCnt % 2 != 0) return GF_OK;
+    return gf_estimator_input_feature(e, t, out, n);
+}
 int gf_estimator_get_track_image(gf_estimator* e, uint8_t* dst, int stride) {
     if (!e || !e->tracker) return gf::set_err(GF_ERR_INVALID, "estimator was created without a tracker (cfg.with_tracker)");
     return gf_tracker_track_image(e->tracker, 0, dst, stride);

@@ -23,6 +23,7 @@
 #include "../host/rosbag_reader.h"
 #include "gf_camera_models.hpp"
 #include "gf_dmath.hpp"
+#include "gf_stereo_depth.hpp"
 
 namespace gf { int set_err(int code, const char* fmt, ...); }
 
@@ -279,8 +280,38 @@ int gf_stereo_from_yaml(const char* config_file, gf_stereo_cfg* out) {
     return GF_OK;
 }
 
-// camera == null and wide == null: gf_estimator_cfg_from_yaml, which takes a PINHOLE file alone; at most one of the two is given
-static int estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* c, gf_camera_model* camera, gf_camera_model_ex* wide = nullptr) {
+// The stereo depth (gf_stereo_depth.hpp) from a config file: for `num_of_cam: 2` the rig is inverse(body_T_cam0) * body_T_cam1 (parameters.cpp:445-463 reads the
+// two, through the reader of the estimator's extrinsics), max_depth is the file's depth_threshold (an `int` in the reference, parameters.cpp:172), and the other
+// gates, which the reference has no keys for, are this repository's defaults (gfsd::kMinParallax, kMaxEpipolar, kMinDepth); right_obs is 1.  Any other
+// num_of_cam: enable == 0 and zeros.  Refused by the key's or the field's name: a missing transform, a depth_threshold the setter would refuse.
+int gf_stereo_depth_from_yaml(const char* config_file, gf_stereo_depth_cfg* out) {
+    if (!config_file || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    YamlDoc y;
+    std::string err;
+    if (!parse_yaml(config_file, y, err)) return gf::set_err(GF_ERR_INVALID, "%s: %s", config_file, err.c_str());
+    gf_stereo_depth_cfg c;
+    memset(&c, 0, sizeof c);
+    if (y.integer("num_of_cam") == 2) {
+        double R0[9], t0[3], R1[9], t1[3];
+        if (!take_transform(y, "body_T_cam0", R0, t0, err) || !take_transform(y, "body_T_cam1", R1, t1, err)) return gf::set_err(GF_ERR_INVALID, "%s: %s", config_file, err.c_str());
+        for (int i = 0; i < 3; i++) {   // R = R0^T R1, t = R0^T (t1 - t0)
+            for (int j = 0; j < 3; j++) c.R[3 * i + j] = (R0[i] * R1[j] + R0[3 + i] * R1[3 + j]) + R0[6 + i] * R1[6 + j];
+            c.t[i] = (R0[i] * (t1[0] - t0[0]) + R0[3 + i] * (t1[1] - t0[1])) + R0[6 + i] * (t1[2] - t0[2]);
+        }
+        c.enable = 1; c.right_obs = 1;
+        c.min_parallax = gfsd::kMinParallax; c.max_epipolar = gfsd::kMaxEpipolar; c.min_depth = gfsd::kMinDepth;
+        c.max_depth = (double)y.integer("depth_threshold");
+        char msg[320];
+        if (!gfsd::check(c, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "%s: %s (max_depth is depth_threshold, the rig inverse(body_T_cam0) * body_T_cam1)", config_file, msg);
+    }
+    *out = c;
+    return GF_OK;
+}
+
+// camera == null and wide == null: gf_estimator_cfg_from_yaml, which takes a PINHOLE file alone; at most one of the two is given.  stereo: num_of_cam 2 is
+// accepted (gf_estimator_cfg_from_yaml_stereo): the second image is a right frame, so the tracker has no depth camera while the estimator's `depth` stays as the
+// file says
+static int estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* c, gf_camera_model* camera, gf_camera_model_ex* wide = nullptr, bool stereo = false) {
     YamlDoc y;
     std::string err;
     if (!parse_yaml(config_file, y, err)) return gf::set_err(GF_ERR_INVALID, "%s: %s", config_file, err.c_str());
@@ -288,7 +319,8 @@ static int estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* c,
     const char* unsupported[] = {"use_line", "use_yolo", "plane", "use_motion"};
     for (const char* k : unsupported)
         if (y.integer(k) != 0) return gf::set_err(GF_ERR_INVALID, "%s: `%s: %d` is outside the built path (DESIGN.md, out of scope)", config_file, k, y.integer(k));
-    if (y.integer("num_of_cam") != 1) return gf::set_err(GF_ERR_INVALID, "%s: num_of_cam must be 1 (RGB-D), got %d", config_file, y.integer("num_of_cam"));
+    const bool two = stereo && y.integer("num_of_cam") == 2;
+    if (!two && y.integer("num_of_cam") != 1) return gf::set_err(GF_ERR_INVALID, "%s: num_of_cam must be 1 (RGB-D), got %d", config_file, y.integer("num_of_cam"));
     memset(c, 0, sizeof(*c));
     c->window_size = 10;          // WINDOW_SIZE, parameters.h:24 (compile-time in the reference)
     c->max_features = 512;        // capacity; NUM_OF_F = 1000 (parameters.h:25) only sizes para_Feature, max_cnt bounds what a window holds
@@ -343,7 +375,7 @@ static int estimator_cfg_from_yaml(const char* config_file, gf_estimator_cfg* c,
     t.height = y.integer("image_height"); t.width = y.integer("image_width");   // ROW / COL
     t.batch = 1;
     t.max_cnt = y.integer("max_cnt"); t.min_dist = y.integer("min_dist"); t.flow_back = y.integer("flow_back");
-    t.depth_cam = c->depth;
+    t.depth_cam = two ? 0 : c->depth;          // a stereo rig's second image is a right frame: the depth comes from the matches (gf_estimator_set_stereo_depth)
     t.equalize = y.integer("equalize") != 0;   // EQUALIZE (parameters.cpp:169): CLAHE on every frame before trackImage (rosNodeTest.cpp:256-261)
     t.pixel_format = GF_PIX_MONO8;             // no key: the reference's node converts every message to MONO8 itself (rosNodeTest.cpp:238-254); a caller with colour frames sets it
     c->with_tracker = 1;
@@ -392,6 +424,18 @@ int gf_estimator_cfg_from_yaml_camera(const char* config_file, gf_estimator_cfg*
 int gf_estimator_cfg_from_yaml_camera_ex(const char* config_file, gf_estimator_cfg* c, gf_camera_model_ex* camera) {
     if (!config_file || !c || !camera) return gf::set_err(GF_ERR_INVALID, "null argument");
     return estimator_cfg_from_yaml(config_file, c, nullptr, camera);
+}
+
+// The same for a stereo rig: `num_of_cam: 2` is accepted, the right camera comes back as gf_stereo_from_yaml reads it and the rig and gates as
+// gf_stereo_depth_from_yaml does, for gf_estimator_set_stereo_depth.  With num_of_cam 1 both come back switched off.
+int gf_estimator_cfg_from_yaml_stereo(const char* config_file, gf_estimator_cfg* c, gf_camera_model_ex* left_camera, gf_stereo_cfg* stereo, gf_stereo_depth_cfg* stereo_depth) {
+    if (!config_file || !c || !left_camera || !stereo || !stereo_depth) return gf::set_err(GF_ERR_INVALID, "null argument");
+    gf_estimator_cfg cfg; gf_camera_model_ex cam; gf_stereo_cfg st; gf_stereo_depth_cfg sd;   // into locals first: a refused file changes nothing
+    if (int rc = estimator_cfg_from_yaml(config_file, &cfg, nullptr, &cam, true)) return rc;
+    if (int rc = gf_stereo_from_yaml(config_file, &st)) return rc;
+    if (int rc = gf_stereo_depth_from_yaml(config_file, &sd)) return rc;
+    *c = cfg; *left_camera = cam; *stereo = st; *stereo_depth = sd;
+    return GF_OK;
 }
 
 int gf_tum_append(const char* path, double t, const double* P, const double* R) {

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "gf_camera_models.hpp"
+#include "gf_stereo_depth.hpp"
 #include "gf_reject_f.hpp"
 #include "gf_roi.hpp"
 #include "gf_seq_cfg.hpp"
@@ -288,13 +289,31 @@ struct Packed { int written; int overflow; };   // observations written; or over
 // the right point of every one and the status the reduction reads (:280; the forward status alone without FLOW_BACK).  cam: the right camera.  un_right: the
 // pairs a lift on the device left for the same rows, or null: the right camera's lift runs here, per kept point.
 struct StereoRows { const P2f* right_pts; const uint8_t* status; const gfcam::Camera* cam; const P2f* un_right; };
+// What a sequence whose left observations carry the depth its matches determine (gf_stereo_depth.hpp) brings to after_detect, with or without a right frame.
+// depth_mm / why: what stereo_depth_kernel left for the frame, by position in cur_pts; both null: left (the left camera as the kernel would read it) and rig are
+// set and the host computes.  right_obs: the camera_id 1 observations are still emitted.  census (may be null): [gfsd::kReasons] counts by reason, added to.
+struct StereoDepthRows { const uint16_t* depth_mm; const uint8_t* why; const gfcam::Camera* left; const gfsd::Rig* rig; bool right_obs; long long* census; };
 
 // The stereo branch of trackImage (feature_tracker.cpp:259-303) behind undistortedPts and ptsVelocity of the left (:210-211) and ahead of the roll-over (:307-312),
 // for a frame that came with a right image: the right-hand lists are cleared (:261-265); if cur_pts is not empty, ids_right = ids, cur_right_pts and ids_right are
 // reduced by the status (:286-288; the left lists are not touched), the kept points are lifted through the right camera (:298) and their velocities taken against
 // the map of the last frame that ran the stage, over this frame's cur_time - prev_time (:299); then prev_un_right_pts_map = cur_un_right_pts_map (:302), also where
 // cur_pts was empty.
-inline void stereo_stage(SeqState& s, const StereoRows& r) {
+// sd (gf_tracker_set_seq_stereo_depth): the depth each match determines goes into cur_depth, where a depth camera's sample travels -- read from the kernel's rows,
+// or computed here by the same function (GF_STEREO_DEPTH_HOST=1) from the points the kernel would have gathered -- ahead of everything else: the left lists are
+// not reduced by the stage, so position i of the rows is feature i.
+inline void stereo_stage(SeqState& s, const StereoRows& r, const StereoDepthRows* sd = nullptr) {
+    if (sd) {
+        const size_t m = s.cur_pts.size();
+        s.cur_depth.resize(m);
+        for (size_t i = 0; i < m; i++) {
+            gfsd::Depth d;
+            if (sd->depth_mm) d = gfsd::Depth{sd->depth_mm[i], sd->why[i]};
+            else d = gfsd::depth_of(*sd->left, *r.cam, *sd->rig, s.cur_pts[i].x, s.cur_pts[i].y, r.right_pts[i].x, r.right_pts[i].y, r.status[i]);
+            s.cur_depth[i] = d.mm;
+            if (sd->census) sd->census[d.why < gfsd::kReasons ? d.why : 0]++;
+        }
+    }
     s.ids_right.clear(); s.cur_right_pts.clear(); s.cur_un_right_pts.clear(); s.right_pts_velocity.clear(); s.cur_un_right_pts_map.clear();
     const size_t n = s.cur_pts.size();
     if (n > 0) {
@@ -317,8 +336,11 @@ inline void stereo_stage(SeqState& s, const StereoRows& r) {
 // stereo: the frame came with a right image for a sequence that has a right camera (stereo_stage runs at its place, and one observation per entry of ids_right
 // follows the left ones: camera_id 1, the right point's pair, pixel and velocity, and the mono loop's -2.4 in the eighth field; the reference's second left
 // observation, which would read the right image as depth (:344-368), is not reproduced); null: the stage is skipped and the right-hand state stays as it is.
+// sd: the sequence's left observations carry the depth its matches determine (StereoDepthRows): the eighth field is the depth-camera expression on cur_depth,
+// 0 for every feature of a frame without a right image; without right_obs the camera_id 1 observations are not emitted and do not count against cap_out.
 inline Packed after_detect(SeqState& s, const gf_tracker_seq_cfg& par, const DetectRows& r, bool have_depth, gf_feature_obs* out, int cap_out,
-                           const gfcam::Camera* cam = nullptr, const P2f* un_lk = nullptr, const P2f* un_out = nullptr, const StereoRows* stereo = nullptr) {
+                           const gfcam::Camera* cam = nullptr, const P2f* un_lk = nullptr, const P2f* un_out = nullptr, const StereoRows* stereo = nullptr,
+                           const StereoDepthRows* sd = nullptr) {
     const size_t n_tracked = s.cur_pts.size();
     for (int i = 0; i < r.out_n; i++) {
         const P2f p = r.out_pts[i];
@@ -330,7 +352,8 @@ inline Packed after_detect(SeqState& s, const gf_tracker_seq_cfg& par, const Det
     else if (un_lk && un_out) for (size_t i = 0; i < s.cur_pts.size(); i++) s.cur_un_pts.push_back(i < n_tracked ? un_lk[s.lk_row[i]] : un_out[i - n_tracked]);
     else for (auto& p : s.cur_pts) { double P[3]; P2f o; gfcam::lift_pair(*cam, (double)p.x, (double)p.y, P, o.x, o.y); s.cur_un_pts.push_back(o); }
     pts_velocity(s);
-    if (stereo) stereo_stage(s, *stereo);
+    if (stereo) stereo_stage(s, *stereo, sd);
+    else if (sd) s.cur_depth.assign(s.cur_pts.size(), (uint16_t)0);   // no right image: no match determines a depth
     s.prev_pts = s.cur_pts; s.prev_un_pts = s.cur_un_pts; s.prev_un_pts_map.swap(s.cur_un_pts_map); s.prev_time = s.cur_time;
     s.hasPrediction = false;
     s.slot ^= 1;   // the pyramid written in this call is the sequence's previous frame from here on
@@ -338,7 +361,7 @@ inline Packed after_detect(SeqState& s, const gf_tracker_seq_cfg& par, const Det
     // depth_cam set but no depth image: neither packing loop of the reference runs (feature_tracker.cpp:320 `depth_cam == 0`, :344 `!_img1.empty()`):
     // the returned featureFrame is empty, the tracker state has advanced all the same
     if (par.depth_cam && !have_depth) return {0, -1};
-    const int n_right = stereo ? (int)s.ids_right.size() : 0;
+    const int n_right = stereo && (!sd || sd->right_obs) ? (int)s.ids_right.size() : 0;
     if (n + n_right > cap_out) return {0, n + n_right};   // the overflow rule holds for the sum
     for (int i = 0; i < n_right; i++) {
         gf_feature_obs* o = out + n + i;
@@ -352,7 +375,7 @@ inline Packed after_detect(SeqState& s, const gf_tracker_seq_cfg& par, const Det
         o->id = s.ids[i]; o->camera_id = 0;
         o->v[0] = s.cur_un_pts[i].x; o->v[1] = s.cur_un_pts[i].y; o->v[2] = 1; o->v[3] = s.cur_pts[i].x; o->v[4] = s.cur_pts[i].y;
         o->v[5] = s.pts_velocity[i].x; o->v[6] = s.pts_velocity[i].y;
-        o->v[7] = par.depth_cam ? (double)(int)s.cur_depth[i] / 1000 : -2.4;
+        o->v[7] = par.depth_cam || sd ? (double)(int)s.cur_depth[i] / 1000 : -2.4;
     }
     return {n + n_right, -1};
 }

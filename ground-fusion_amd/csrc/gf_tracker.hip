@@ -36,6 +36,7 @@
 #include "gf_detect_kernels.hpp"
 #include "gf_lk_kernels.hpp"
 #include "gf_stereo_kernels.hpp"
+#include "gf_stereo_depth.hpp"
 #include "gf_copy_list.hpp"
 #include "gf_depth_reg_stage.hpp"
 #include "gf_reject_f_stage.hpp"
@@ -66,6 +67,8 @@ int cvt_launch_mixed(const gf_frame_ref* d_refs, const int* d_formats, const gf_
 int draw_track_launch(const gfdraw::DrawJob* d_jobs, int count, int w, int h, hipStream_t stream);
 // gf_camera.hip: liftProjective of the listed entries' cameras (gf_tracker_set_seq_camera), one launch
 int camera_lift_launch(const gfcam::LiftArgs& A, int max_n, hipStream_t stream);
+// gf_stereo_depth.hip: the depth the matches of the listed positions determine (gf_tracker_set_seq_stereo_depth), one launch
+int stereo_depth_launch(const gfsd::Args& A, int max_n, hipStream_t stream);
 constexpr double kClaheClip = 40.0;   // cv::createCLAHE() defaults (rosNodeTest.cpp:258)
 constexpr int kClaheTiles = 8;
 
@@ -321,6 +324,21 @@ struct gf_tracker {
     DevBuf<uint8_t> d_st_eq, d_st_eq_lut; DevBuf<gf_frame_ref> d_st_eqsrc; PinBuf<gf_frame_ref> h_st_eqsrc;
     gf_stereo_stats st_stats{};
     bool stereo_on(int q) const { return !st_on.empty() && st_on[q]; }
+
+    // The depth a stereo sequence's matches determine (gf_tracker_set_seq_stereo_depth; gf_stereo_depth.hpp), the eleventh thing addressed by SEQUENCE.  Everything
+    // here is obtained by the first setter of the handle that turns a switch on: sd_on[seq] / sd_cfg[seq], the configuration as it was set; d_sd_entries, by
+    // SEQUENCE, what stereo_depth_kernel reads for a position through the stereo stage's own list (st_right_of names the sequence): both cameras, the rig and the
+    // gates, on == 0 for a sequence without the switch; sd_entry, page-locked, what each row held when it last went down (gfsd::Entry has no padding, so equal bytes
+    // are equal entries; a camera set after this setter makes the row go down
+    // again, with the call that first finds it changed).  Per call, by list position: the kernel's outputs sd_mm / sd_why, which come up with the right points.
+    // sd_host (GF_STEREO_DEPTH_HOST=1): gfsd::depth_of inside stereo_stage instead, no launch.
+    std::vector<uint8_t> sd_on; std::vector<gf_stereo_depth_cfg> sd_cfg;
+    DevBuf<gfsd::Entry> d_sd_entries; PinBuf<gfsd::Entry> sd_entry;
+    DevBuf<uint16_t> d_sd_mm; PinBuf<uint16_t> h_sd_mm;
+    DevBuf<uint8_t> d_sd_why; PinBuf<uint8_t> h_sd_why;
+    bool sd_host = false;
+    gf_stereo_depth_stats sd_stats{};
+    bool stereo_depth_on(int q) const { return !sd_on.empty() && sd_on[q]; }
 
     std::unique_ptr<HostPool> pool;
 };
@@ -806,6 +824,7 @@ struct Call {
     int n_reg = 0;                        // listed sequences whose raw depth frame this call registers (publish fills their jobs, launch_depth_reg runs them)
     int n_st_lift = 0;                    // how many of them have their right points lifted by the call's launch of camera_lift_kernel
     int n_stereo = 0;                     // listed stereo sequences that came with a right frame: the stage runs for them (publish, launch_right_pyramids, launch_stereo)
+    int n_sd = 0;                         // how many of them carry the depth their matches determine (gf_tracker_set_seq_stereo_depth): launch_stereo_depth, stereo_up
     void lap(double& acc) { const auto n = std::chrono::steady_clock::now(); acc += std::chrono::duration<double, std::milli>(n - tp).count(); tp = n; }
     void add_refs() {
         if (refs_down) { ho.down(h->d_refs, h->h_refs, (size_t)2 * h->B); refs_down = false; }
@@ -833,7 +852,7 @@ static int publish(Call& c) {
                 h->h_st_right_of.p[i] = -1;
                 if (!h->st_on[q]) continue;
                 h->h_refs.p[h->B + i] = gf_frame_ref{nullptr, 0};
-                if (in.depth_refs && in.depth_refs[i].data) { h->h_st_right_of.p[i] = q; c.n_stereo++; }
+                if (in.depth_refs && in.depth_refs[i].data) { h->h_st_right_of.p[i] = q; c.n_stereo++; if (h->stereo_depth_on(q)) c.n_sd++; }
             }
         // a depth registration per sequence (gf_depth_reg.hpp): the entry is the RAW frame; the table names the handle's registered frame in its place, and the
         // job goes to launch_depth_reg.  A sequence without a depth camera is never registered (its entry is never sampled).
@@ -1148,10 +1167,40 @@ static int launch_stereo(Call& c) {
     h->st_stats.launches++;
     return GF_OK;
 }
+// The depth the call's matches determine (gf_stereo_depth.hpp), for the listed stereo sequences whose switch is on: ONE launch of stereo_depth_kernel behind the
+// stereo kernel, whose right points and status bytes it reads where that kernel left them and whose gather of the left points it repeats.  The positions are
+// named by the stereo stage's own list (d_st_right_of: the sequence, or -1), so nothing more goes down with the call; a sequence's row of d_sd_entries goes down
+// here only where a setter changed what it is made of since it last did (the sequence's first frame, as a rule).
+static gfsd::Entry stereo_depth_entry(const gf_tracker* h, int q) {   // what the sequence's depths are made of, as things stand: its two cameras, the rig, the gates
+    gfsd::Entry e{};
+    e.left = reject_f_camera(h, q); e.right = h->st_cam[q]; e.rig = gfsd::rig_of(h->sd_cfg[q]); e.on = 1;
+    return e;
+}
+static gfcam::Pair* pairs(float2* p);
+static int launch_stereo_depth(Call& c) {
+    gf_tracker* h = c.h;
+    if (!c.n_sd || h->sd_host) return GF_OK;
+    for (int i = 0; i < c.N; i++) {
+        const int q = c.seq[i];
+        if (h->h_st_right_of.p[i] < 0 || !h->sd_on[q]) continue;
+        const gfsd::Entry e = stereo_depth_entry(h, q);
+        if (memcmp(&e, h->sd_entry.p + q, sizeof e) == 0) continue;   // no padding in an Entry (gf_stereo_depth.hpp): the bytes are the value
+        h->sd_entry.p[q] = e;
+        HIPCHK(hipMemcpyAsync(h->d_sd_entries.p + q, h->sd_entry.p + q, sizeof e, hipMemcpyHostToDevice, h->stream));
+    }
+    gfsd::Args A{};
+    A.entries = h->d_sd_entries.p; A.entry_of = h->d_st_right_of.p; A.first = nullptr; A.cap = h->cap; A.count = c.N;
+    A.n_tracked = h->d_st_ntr.p; A.row = h->d_st_row.p; A.lk_pts = pairs(h->d_cur_pts.p); A.n_new = h->d_out_n.p; A.new_pts = pairs(h->d_out_pts.p);
+    A.right_pts = pairs(h->d_st_pts.p); A.status = h->d_st_status.p; A.depth_mm = h->d_sd_mm.p; A.why = h->d_sd_why.p;
+    if (int rc = stereo_depth_launch(A, h->cap, h->stream)) return rc;
+    h->sd_stats.launches++;
+    return GF_OK;
+}
 static void stereo_up(Call& c) {
     gf_tracker* h = c.h;
     c.ho.up(h->h_st_pts, h->d_st_pts, (size_t)c.N * h->cap);
     c.ho.up(h->h_st_status, h->d_st_status, (size_t)c.N * h->cap);
+    if (c.n_sd && !h->sd_host) { c.ho.up(h->h_sd_mm, h->d_sd_mm, (size_t)c.N * h->cap); c.ho.up(h->h_sd_why, h->d_sd_why, (size_t)c.N * h->cap); }
     if (c.n_st_lift) c.ho.up(h->h_st_un, h->d_st_un, (size_t)c.N * h->cap);
 }
 
@@ -1340,6 +1389,7 @@ static int run_detect(Call& c) {
         if (c.sized) launch_select_sized(h, N, S, topk, sort); else if (c.in.depth_by_refs()) launch_select<true>(h, N, S, topk, sort); else launch_select<false>(h, N, S, topk, sort);
         HIPCHK(hipGetLastError());
         if (c.n_stereo) if (int rc = launch_stereo(c)) return rc;
+        if (c.n_sd) if (int rc = launch_stereo_depth(c)) return rc;
         if (c.lift || c.n_st_lift) if (int rc = launch_lift(c)) return rc;
         if (c.n_stereo) stereo_up(c);
         ho.up(h->h_out_n, h->d_out_n, N);
@@ -1355,6 +1405,7 @@ static int run_detect(Call& c) {
         if (c.n_stereo) { stereo_down(c); ho.down(h->d_out_n, h->h_out_n, N); }
         if (int rc = ho.flush()) return rc;
         if (c.n_stereo) if (int rc = launch_stereo(c)) return rc;
+        if (c.n_sd) if (int rc = launch_stereo_depth(c)) return rc;
         if (c.lift || c.n_st_lift) if (int rc = launch_lift(c)) return rc;
         if (c.lift) ho.up(h->h_un_lk, h->d_un_lk, (size_t)N * cap);
         if (c.n_stereo) stereo_up(c);
@@ -1405,6 +1456,8 @@ static int book_after_detect(Call& c, gf_feature_obs* out, int cap_out, int* n_o
     const bool have_depth = c.in.have_depth();
     std::atomic<int> a_overflow{-1};
     std::atomic<long long> a_out{0}, a_st_points{0}, a_st_matched{0};
+    std::atomic<long long> a_sd[gfsd::kReasons];
+    for (auto& a : a_sd) a = 0;
     h->pool->parallel_for(c.N, [&](int b) {   // b: list position
         const int q = c.seq[b];
         const DetectRows r{row(h->h_out_pts, b, cap), c.in.kernel_samples(h->h_out_depth, b, cap), h->h_want.p[b] > 0 ? h->h_out_n.p[b] : 0, c.in.host_image(b, h->par[q]), c.in.host_dstride};
@@ -1412,9 +1465,17 @@ static int book_after_detect(Call& c, gf_feature_obs* out, int cap_out, int* n_o
         const bool stereo = c.n_stereo && h->h_st_right_of.p[b] >= 0;   // the frame came with a right image: the stage runs (after_detect, at the reference's place)
         const StereoRows sr{stereo ? row(h->h_st_pts, b, cap) : nullptr, stereo ? h->h_st_status.p + (size_t)b * cap : nullptr, stereo ? &h->st_cam[q] : nullptr,
                             stereo && h->h_st_cam_of.p[b] >= 0 ? row(h->h_st_un, b, cap) : nullptr};
+        // the depth the matches determine (gf_tracker_set_seq_stereo_depth): the kernel's rows, or with GF_STEREO_DEPTH_HOST=1 the same function inside stereo_stage
+        const bool sd_on = h->stereo_depth_on(q), sd_dev = sd_on && stereo && !h->sd_host;
+        long long census[gfsd::kReasons] = {0};
+        gfcam::Camera sd_left{}; gfsd::Rig sd_rig{};
+        if (sd_on && stereo && h->sd_host) { sd_left = reject_f_camera(h, q); sd_rig = gfsd::rig_of(h->sd_cfg[q]); }
+        const StereoDepthRows sdr{sd_dev ? h->h_sd_mm.p + (size_t)b * cap : nullptr, sd_dev ? h->h_sd_why.p + (size_t)b * cap : nullptr, &sd_left, &sd_rig,
+                                  sd_on && h->sd_cfg[q].right_obs != 0, census};
         const Packed p = after_detect(h->seq[q], h->par[q], r, have_depth && !h->stereo_on(q), out + (size_t)b * cap_out, cap_out, own ? &h->cam[q] : nullptr,
-                                      dev ? row(h->h_un_lk, b, cap) : nullptr, dev ? row(h->h_un_out, b, cap) : nullptr, stereo ? &sr : nullptr);
+                                      dev ? row(h->h_un_lk, b, cap) : nullptr, dev ? row(h->h_un_out, b, cap) : nullptr, stereo ? &sr : nullptr, sd_on ? &sdr : nullptr);
         if (stereo) { a_st_points += (long long)h->seq[q].prev_pts.size(); a_st_matched += (long long)h->seq[q].ids_right.size(); }
+        if (sd_on && stereo) for (int k = 0; k < gfsd::kReasons; k++) a_sd[k] += census[k];
         if (h->seq[q].show_track) (void)record_track(h->seq[q], h->boxes.empty() ? nullptr : h->boxes[q].data(), h->boxes.empty() ? 0 : (int)h->boxes[q].size());   // a refused list: the sequence has no picture of this frame, and keeps the reason (draw_why)
         if (p.overflow >= 0) a_overflow = p.overflow;
         n_out[b] = p.written;
@@ -1423,6 +1484,13 @@ static int book_after_detect(Call& c, gf_feature_obs* out, int cap_out, int* n_o
     if (a_overflow.load() >= 0) return set_err(GF_ERR_CAPACITY, "output capacity %d < %d features", cap_out, a_overflow.load());
     h->stats.output_features += a_out;
     if (c.n_stereo) { h->st_stats.calls++; h->st_stats.points += a_st_points; h->st_stats.matched += a_st_matched; }
+    if (c.n_sd) {
+        gf_stereo_depth_stats& s = h->sd_stats;
+        s.calls++;
+        for (int k = 0; k < gfsd::kReasons; k++) s.points += a_sd[k];
+        s.with_depth += a_sd[gfsd::kOk]; s.no_match += a_sd[gfsd::kNoMatch]; s.lift += a_sd[gfsd::kLift]; s.parallax += a_sd[gfsd::kParallax];
+        s.behind += a_sd[gfsd::kBehind]; s.epipolar += a_sd[gfsd::kEpipolar]; s.range += a_sd[gfsd::kRange];
+    }
     return GF_OK;
 }
 
@@ -1507,6 +1575,7 @@ int gf_tracker_create(const gf_tracker_cfg* cfg, gf_tracker** out) {
         h->select_topk = !(getenv("GF_SELECT_TOPK") && atoi(getenv("GF_SELECT_TOPK")) == 0);
         if (const char* e = getenv("GF_CAMERA_LIFT_HOST")) h->lift_mode = atoi(e) != 0 ? 1 : 0;
         if (const char* e = getenv("GF_REJECT_F_HOST")) h->rf_host = atoi(e) != 0;
+        if (const char* e = getenv("GF_STEREO_DEPTH_HOST")) h->sd_host = atoi(e) != 0;
         if (const char* e = getenv("GF_LK_POINTS")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) h->lk_points = v; }
     }
     const int W = cfg->width, H = cfg->height, B = h->B, cap = h->cap;
@@ -2243,6 +2312,59 @@ int gf_tracker_set_seq_stereo(gf_tracker* h, int seq, const gf_stereo_cfg* c) {
     h->st_on[seq] = on ? 1 : 0;
     h->st_cfg[seq] = on ? *c : gf_stereo_cfg{};
     h->st_cam[seq] = cam;
+    if (!on && h->stereo_depth_on(seq)) return gf_tracker_set_seq_stereo_depth(h, seq, nullptr);   // no right camera, no match, no depth
+    return GF_OK;
+}
+
+// ---- the depth a stereo sequence's matches determine (gf_stereo_depth.hpp; gf_stereo_depth_kernels.hpp).  Between frames, with the stream drained.
+namespace gf {
+static int seq_stereo_depth_ready(gf_tracker* h) {   // the first setter of a handle that turns a switch on: the table of entries and the call's two output tables
+    if (h->d_sd_entries.p) return GF_OK;
+    const size_t B = (size_t)h->B, rows = B * h->cap;
+    DevBuf<gfsd::Entry> de; PinBuf<gfsd::Entry> he; DevBuf<uint16_t> dm; PinBuf<uint16_t> hm; DevBuf<uint8_t> dw; PinBuf<uint8_t> hw;
+    HIPCHK(de.alloc(B)); HIPCHK(he.alloc(B)); HIPCHK(dm.alloc(rows)); HIPCHK(hm.alloc(rows)); HIPCHK(dw.alloc(rows)); HIPCHK(hw.alloc(rows));
+    HIPCHK(hipMemset(de.p, 0, B * sizeof(gfsd::Entry)));   // on == 0: a stereo sequence without the switch leaves the kernel at once
+    h->d_sd_entries = std::move(de); h->d_sd_mm = std::move(dm); h->h_sd_mm = std::move(hm); h->d_sd_why = std::move(dw); h->h_sd_why = std::move(hw);
+    memset(he.p, 0, B * sizeof(gfsd::Entry));
+    h->sd_entry = std::move(he);
+    h->sd_on.assign(B, 0); h->sd_cfg.assign(B, gf_stereo_depth_cfg{});
+    return GF_OK;
+}
+}  // namespace gf
+
+int gf_tracker_set_seq_stereo_depth(gf_tracker* h, int seq, const gf_stereo_depth_cfg* c) {
+    if (!h) return gf::set_err(GF_ERR_INVALID, "null handle");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    if (c && c->enable != 0 && c->enable != 1) return gf::set_err(GF_ERR_INVALID, "sequence %d: gf_stereo_depth_cfg.enable must be 0 or 1, got %d", seq, c->enable);
+    if (c && c->right_obs != 0 && c->right_obs != 1) return gf::set_err(GF_ERR_INVALID, "sequence %d: gf_stereo_depth_cfg.right_obs must be 0 or 1, got %d", seq, c->right_obs);
+    const bool on = c && c->enable;
+    char msg[320];
+    if (on && !gfsd::check(*c, msg, sizeof msg)) return gf::set_err(GF_ERR_INVALID, "sequence %d: %s", seq, msg);
+    if (!on && h->sd_on.empty()) return GF_OK;   // nothing to take back, whatever the sequence's state: the handle stays one that never set any
+    if (h->seq[seq].started) return gf::set_err(GF_ERR_INVALID, "sequence %d has taken a frame: its stereo depth is fixed until gf_tracker_reset_seq", seq);
+    if (gf::seq_is_staged(h, seq)) return gf::set_err(GF_ERR_INVALID, "sequence %d is listed by a staged frame: gf_tracker_track_prefetched has to consume it first (stereo depth)", seq);
+    if (on && !h->stereo_on(seq)) return gf::set_err(GF_ERR_INVALID, "sequence %d has no right camera: gf_tracker_set_seq_stereo comes first, a depth needs a match (stereo depth)", seq);
+    if (int rc = gf::seq_stereo_depth_ready(h)) return rc;
+    gfsd::Entry e;   // on == 0
+    memset(&e, 0, sizeof e);
+    if (on) { e.left = gf::reject_f_camera(h, seq); e.right = h->st_cam[seq]; e.rig = gfsd::rig_of(*c); e.on = 1; }
+    HIPCHK(hipMemcpy(h->d_sd_entries.p + seq, &e, sizeof e, hipMemcpyHostToDevice));
+    h->sd_entry.p[seq] = e;
+    h->sd_on[seq] = on ? 1 : 0;
+    h->sd_cfg[seq] = on ? *c : gf_stereo_depth_cfg{};
+    return GF_OK;
+}
+
+int gf_tracker_get_seq_stereo_depth(gf_tracker* h, int seq, gf_stereo_depth_cfg* out) {
+    if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    if (seq < 0 || seq >= h->B) return gf::set_err(GF_ERR_INVALID, "sequence %d of a handle of %d", seq, h->B);
+    *out = h->stereo_depth_on(seq) ? h->sd_cfg[seq] : gf_stereo_depth_cfg{};
+    return GF_OK;
+}
+
+int gf_tracker_get_stereo_depth_stats(gf_tracker* h, gf_stereo_depth_stats* out) {
+    if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument");
+    *out = h->sd_stats;
     return GF_OK;
 }
 
@@ -2383,7 +2505,7 @@ int gf_tracker_get_state(gf_tracker* h, int seq, int* ids, int* track_cnt, float
 
 int gf_tracker_set_profiling(gf_tracker* h, int enable) { if (!h) return gf::set_err(GF_ERR_INVALID, "null handle"); h->profiling = enable != 0; return GF_OK; }
 int gf_tracker_get_stats(gf_tracker* h, gf_tracker_stats* out) { if (!h || !out) return gf::set_err(GF_ERR_INVALID, "null argument"); *out = h->stats; return GF_OK; }
-int gf_tracker_reset_stats(gf_tracker* h) { if (!h) return gf::set_err(GF_ERR_INVALID, "null handle"); h->stats = gf_tracker_stats{}; h->dreg_launches = h->dreg_frames = 0; h->dreg_ms = 0; h->lift_launches = h->lift_sequences = 0; h->rf_stats = gf_reject_f_stats{}; h->st_stats = gf_stereo_stats{}; return GF_OK; }
+int gf_tracker_reset_stats(gf_tracker* h) { if (!h) return gf::set_err(GF_ERR_INVALID, "null handle"); h->stats = gf_tracker_stats{}; h->dreg_launches = h->dreg_frames = 0; h->dreg_ms = 0; h->lift_launches = h->lift_sequences = 0; h->rf_stats = gf_reject_f_stats{}; h->st_stats = gf_stereo_stats{}; h->sd_stats = gf_stereo_depth_stats{}; return GF_OK; }
 
 // ------------------------------------------------------------------ building blocks for parity tests
 static int tmp_handle(int width, int height, int max_cnt, int min_dist, std::unique_ptr<gf_tracker>& own) {

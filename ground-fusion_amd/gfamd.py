@@ -330,6 +330,38 @@ class StereoStats(C.Structure):
 
 assert C.sizeof(StereoCfg) == 360 and C.sizeof(StereoStats) == 40
 
+# GF_STEREO_DEPTH_*: what became of a point, in the order the gates are tested
+STEREO_DEPTH_WHY = {"no_match": 1, "lift": 2, "parallax": 3, "behind": 4, "epipolar": 5, "range": 6, "ok": 7}
+STEREO_DEPTH_MIN_PARALLAX, STEREO_DEPTH_MAX_EPIPOLAR, STEREO_DEPTH_MIN_DEPTH = 1e-3, 10.0 / 460.0, 0.1   # the defaults of the gates ("Stereo depth")
+
+
+class StereoDepthCfg(C.Structure):
+    """gf_stereo_depth_cfg: the depth a stereo sequence's matches determine -- the switch, whether the camera_id 1 observations are still emitted, the rig
+    p_left = R p_right + t (R row-major), and the gates: the sine of the least ray angle, the largest normalised-plane distance in the right eye, the depth range
+    in metres (max_depth <= 65.535)"""
+    _fields_ = [("enable", C.c_int32), ("right_obs", C.c_int32), ("R", C.c_double * 9), ("t", C.c_double * 3), ("min_parallax", C.c_double), ("max_epipolar", C.c_double),
+                ("min_depth", C.c_double), ("max_depth", C.c_double)]
+
+    @classmethod
+    def make(cls, R, t, max_depth, min_depth=STEREO_DEPTH_MIN_DEPTH, min_parallax=STEREO_DEPTH_MIN_PARALLAX, max_epipolar=STEREO_DEPTH_MAX_EPIPOLAR, right_obs=1, enable=1):
+        c = cls()
+        c.enable, c.right_obs = int(enable), int(right_obs)
+        c.R[:] = [float(v) for v in np.asarray(R, np.float64).reshape(9)]
+        c.t[:] = [float(v) for v in np.asarray(t, np.float64).reshape(3)]
+        c.min_parallax, c.max_epipolar, c.min_depth, c.max_depth = float(min_parallax), float(max_epipolar), float(min_depth), float(max_depth)
+        return c
+
+    def as_dict(self):
+        return {"enable": self.enable, "right_obs": self.right_obs, "R": list(self.R), "t": list(self.t), "min_parallax": self.min_parallax,
+                "max_epipolar": self.max_epipolar, "min_depth": self.min_depth, "max_depth": self.max_depth}
+
+
+class StereoDepthStats(C.Structure):
+    _fields_ = [(k, C.c_longlong) for k in ("calls", "launches", "points", "with_depth", "no_match", "lift", "parallax", "behind", "epipolar", "range")]
+
+
+assert C.sizeof(StereoDepthCfg) == 136 and C.sizeof(StereoDepthStats) == 80
+
 
 def _reject_f_tables(sets, thresholds, seeds):
     sets = [np.ascontiguousarray(s, np.float32).reshape(-1, 4) for s in sets]
@@ -404,6 +436,57 @@ def stereo_from_yaml(config_file):
     """gf_stereo_from_yaml: `num_of_cam: 2` and `cam1_calib` of a config file -> StereoCfg (enable == 0 for any other num_of_cam)"""
     c = StereoCfg()
     _chk(lib().gf_stereo_from_yaml(os.fsencode(config_file), C.byref(c)))
+    return c
+
+
+def _stereo_depth_tables(left, right, cfgs, counts):
+    n = len(left)
+    assert len(right) == len(cfgs) == len(counts) == n
+    first = np.zeros(n + 1, np.int32)
+    first[1:] = np.cumsum(counts)
+    wide = lambda cams: (CameraModelEx * max(n, 1))(*[CameraModelEx.of(c) for c in cams])
+    return n, first, wide(left), wide(right), (StereoDepthCfg * max(n, 1))(*cfgs)
+
+
+def stereo_depth(left, right, cfgs, left_uv, right_uv, status, host=False):
+    """gf_stereo_depth_batch (host=True: gf_stereo_depth_batch_host, the same function on the CPU, no device): set b has the cameras left[b], right[b] (CameraModel /
+    CameraModelEx), the rig and gates cfgs[b] (StereoDepthCfg), and the matches left_uv[b], right_uv[b] ([m_b, 2] float32 pixels) with status[b] ([m_b] bytes)
+    -> (list of uint16 millimetre arrays, list of uint8 reason arrays, STEREO_DEPTH_WHY)"""
+    l = [np.ascontiguousarray(p, np.float32).reshape(-1, 2) for p in left_uv]
+    r = [np.ascontiguousarray(p, np.float32).reshape(-1, 2) for p in right_uv]
+    st = [np.ascontiguousarray(s, np.uint8).reshape(-1) for s in status]
+    assert all(len(a) == len(b) == len(c) for a, b, c in zip(l, r, st))
+    n, first, la, ra, ca = _stereo_depth_tables(left, right, cfgs, [len(p) for p in l])
+    cat = lambda v, shape, t: np.ascontiguousarray(np.concatenate(v) if v else np.zeros(shape, t))
+    lu, ru, s = cat(l, (0, 2), np.float32), cat(r, (0, 2), np.float32), cat(st, (0,), np.uint8)
+    rows = max(int(first[-1]), 1)
+    mm, why = np.zeros(rows, np.uint16), np.zeros(rows, np.uint8)
+    f = lib().gf_stereo_depth_batch_host if host else lib().gf_stereo_depth_batch
+    _chk(f(n, _p(first, C.c_int), la, ra, ca, _p(lu, C.c_float), _p(ru, C.c_float), _p(s, C.c_uint8), _p(mm, C.c_uint16), _p(why, C.c_uint8)))
+    cut = lambda a: [a[first[b]:first[b + 1]].copy() for b in range(n)]
+    return cut(mm), cut(why)
+
+
+def stereo_depth_host(left, right, cfgs, left_uv, right_uv, status):
+    """gf_stereo_depth_batch_host: stereo_depth(..., host=True)"""
+    return stereo_depth(left, right, cfgs, left_uv, right_uv, status, host=True)
+
+
+def stereo_depth_device(left, right, cfgs, counts, d_left_uv, d_right_uv, d_status, d_depth_mm, d_why, stream=0):
+    """gf_stereo_depth_batch_device: set b holds counts[b] matches, back to back at the device addresses d_left_uv / d_right_uv (2 floats each) and d_status (a
+    byte each); d_depth_mm (uint16 each) and d_why (a byte each) are written.  One launch; cameras, configurations and counts stay on the host"""
+    n, first, la, ra, ca = _stereo_depth_tables(left, right, cfgs, counts)
+    fp = lambda a: C.cast(C.c_void_p(a), C.POINTER(C.c_float))
+    _chk(lib().gf_stereo_depth_batch_device(n, _p(first, C.c_int), la, ra, ca, fp(d_left_uv), fp(d_right_uv), C.cast(C.c_void_p(d_status), C.POINTER(C.c_uint8)),
+                                            C.cast(C.c_void_p(d_depth_mm), C.POINTER(C.c_uint16)), C.cast(C.c_void_p(d_why), C.POINTER(C.c_uint8)),
+                                            C.c_void_p(stream) if stream else None))
+
+
+def stereo_depth_from_yaml(config_file):
+    """gf_stereo_depth_from_yaml: the rig inverse(body_T_cam0) * body_T_cam1, depth_threshold as max_depth and the default gates of a `num_of_cam: 2` config file
+    -> StereoDepthCfg (enable == 0 for any other num_of_cam)"""
+    c = StereoDepthCfg()
+    _chk(lib().gf_stereo_depth_from_yaml(os.fsencode(config_file), C.byref(c)))
     return c
 
 
@@ -845,6 +928,23 @@ class FeatureTracker:
         _chk(lib().gf_tracker_get_stereo_stats(self.h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in StereoStats._fields_}
 
+    def set_seq_stereo_depth(self, seq, cfg=None):
+        """gf_tracker_set_seq_stereo_depth: the left observations of stereo sequence `seq` carry the depth its matches determine (a StereoDepthCfg; None turns it
+        off).  Before the sequence's first frame, after set_seq_stereo.  With cfg.right_obs == 0 the camera_id 1 observations are not emitted."""
+        _chk(lib().gf_tracker_set_seq_stereo_depth(self.h, int(seq), None if cfg is None else C.byref(cfg)))
+
+    def get_seq_stereo_depth(self, seq):
+        """gf_tracker_get_seq_stereo_depth: the StereoDepthCfg of sequence `seq` (enable == 0: off)"""
+        c = StereoDepthCfg()
+        _chk(lib().gf_tracker_get_seq_stereo_depth(self.h, int(seq), C.byref(c)))
+        return c
+
+    def stereo_depth_stats(self):
+        """gf_tracker_get_stereo_depth_stats: dict of calls, launches, points, with_depth and a count per reason"""
+        s = StereoDepthStats()
+        _chk(lib().gf_tracker_get_stereo_depth_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in StereoDepthStats._fields_}
+
     def camera_lift_stats(self):
         """gf_tracker_get_camera_lift_stats: dict of launches of camera_lift_kernel by this handle and of the listed sequences they lifted"""
         n, q = C.c_longlong(0), C.c_longlong(0)
@@ -1171,6 +1271,8 @@ def lk_track(prev, nxt, prev_pts, next_pts=None, max_level=3):
     return npn, st, it.value
 
 
+EXPORTS += ["gf_tracker_set_seq_stereo_depth", "gf_tracker_get_seq_stereo_depth", "gf_tracker_get_stereo_depth_stats", "gf_stereo_depth_batch", "gf_stereo_depth_batch_device",
+            "gf_stereo_depth_batch_host", "gf_stereo_depth_from_yaml", "gf_estimator_set_stereo_depth", "gf_estimator_input_image_refs", "gf_estimator_cfg_from_yaml_stereo"]
 EXPORTS += ["gf_stereo_match_batch", "gf_stereo_match_batch_device", "gf_tracker_set_seq_stereo", "gf_tracker_get_seq_stereo", "gf_tracker_get_stereo_stats", "gf_stereo_from_yaml"]
 
 
@@ -1706,6 +1808,25 @@ class SlidingWindowEstimator:
         """gf_estimator_set_reject_f: rejectWithF of the estimator's own tracker (RejectFCfg; None: off)"""
         _chk(lib().gf_estimator_set_reject_f(self.h, None if cfg is None else C.byref(cfg)))
 
+    def set_stereo_depth(self, stereo, depth):
+        """gf_estimator_set_stereo_depth: the estimator's own tracker becomes a stereo one whose left observations carry the depth its matches determine (stereo: a
+        StereoCfg, or the right camera as a CameraModel / CameraModelEx; depth: a StereoDepthCfg, whose right_obs is forced to 0).  Before the first image; needs
+        cfg.depth == 1 and cfg.tracker.depth_cam == 0"""
+        st = stereo if isinstance(stereo, StereoCfg) else StereoCfg(1, 0, CameraModelEx.of(stereo))
+        _chk(lib().gf_estimator_set_stereo_depth(self.h, C.byref(st), C.byref(depth)))
+
+    def inputImageRefs(self, t, img0, img1=None):
+        """gf_estimator_input_image_refs: inputImage on device frames by reference -- img0, img1 = (device address of row 0, bytes from row to row); img1 is the
+        depth frame of an RGB-D estimator or the right frame of a stereo one, None: none.  Returns the frame's observations as (ids, camera ids, [n, 8])"""
+        cap = 2 * (self.cfg.tracker.max_cnt + 8)
+        out = np.zeros(cap, OBS_DTYPE)
+        n = C.c_int(0)
+        r0 = FrameRef(int(img0[0]), int(img0[1]))
+        r1 = None if img1 is None else FrameRef(int(img1[0]), int(img1[1]))
+        _chk(lib().gf_estimator_input_image_refs(self.h, C.c_double(t), C.byref(r0), None if r1 is None else C.byref(r1), out.ctypes.data_as(C.POINTER(FeatureObs)), cap, C.byref(n)))
+        o = out[:n.value]
+        return o["id"].copy(), o["camera_id"].copy(), o["v"].copy()
+
     def set_show_track(self, on=True):
         """gf_estimator_set_show_track: SHOW_TRACK of the estimator's own tracker"""
         _chk(lib().gf_estimator_set_show_track(self.h, int(bool(on))))
@@ -1803,6 +1924,14 @@ def estimator_cfg_from_yaml_camera_ex(config_file):
     c, m = EstimatorCfg(), CameraModelEx()
     _chk(lib().gf_estimator_cfg_from_yaml_camera_ex(os.fsencode(config_file), C.byref(c), C.byref(m)))
     return c, m
+
+
+def estimator_cfg_from_yaml_stereo(config_file):
+    """gf_estimator_cfg_from_yaml_stereo: readParameters that accepts `num_of_cam: 2` -> (EstimatorCfg, the left CameraModelEx for set_camera, StereoCfg,
+    StereoDepthCfg for set_stereo_depth); with num_of_cam 1 the last two come back switched off"""
+    c, m, st, sd = EstimatorCfg(), CameraModelEx(), StereoCfg(), StereoDepthCfg()
+    _chk(lib().gf_estimator_cfg_from_yaml_stereo(os.fsencode(config_file), C.byref(c), C.byref(m), C.byref(st), C.byref(sd)))
+    return c, m, st, sd
 
 
 def estimator_cfg_from_yaml_camera(config_file):

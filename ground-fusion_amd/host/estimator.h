@@ -144,6 +144,17 @@ class Estimator {
         check(gf_estimator_input_image(h_, t, _img.data, _img.stride, _img1.empty() ? nullptr : _img1.data, _img1.stride, nullptr, 0, nullptr));
         refresh();
     }
+    // inputImage on frames that lie on the device, by reference (gf_estimator_input_image_refs): _img1 is the depth frame of an RGB-D estimator or the right frame
+    // of a stereo one (setStereoDepth); {nullptr, 0}: none
+    void inputImage(double t, const gf_frame_ref& _img, const gf_frame_ref& _img1 = gf_frame_ref{nullptr, 0}) {
+        need();
+        check(gf_estimator_input_image_refs(h_, t, &_img, _img1.data ? &_img1 : nullptr, nullptr, 0, nullptr));
+        refresh();
+    }
+    // a stereo rig on the estimator's own tracker (gf_estimator_set_stereo_depth): the right camera, and the rig and gates of the depth its matches determine, which
+    // the back end takes as an RGB-D depth.  After setParameter(), before the first inputImage; cfg.depth must be 1 and cfg.tracker.depth_cam 0
+    // (gf_estimator_cfg_from_yaml_stereo fills all three from a `num_of_cam: 2` config file)
+    void setStereoDepth(const gf_stereo_cfg& stereo, const gf_stereo_depth_cfg& depth) { need(); check(gf_estimator_set_stereo_depth(h_, &stereo, &depth)); }
     // the region of interest of the estimator's own tracker (FeatureTracker::setRegionOfInterest, gf_estimator_set_roi): rows x cols bytes of cfg.tracker's frame
     // size, non-zero = allowed, nullptr clears; from the next inputImage on
     void setRegionOfInterest(const uint8_t* mask, int stride) { need(); check(gf_estimator_set_roi(h_, mask, stride)); }

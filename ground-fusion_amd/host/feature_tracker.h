@@ -91,6 +91,20 @@ class FeatureTracker {
             stereo_cam = true;
         }
     }
+    // two calibration files plus the rig between the eyes: a stereo tracker whose LEFT observations carry the depth its matches determine in their eighth field
+    // (gf_tracker_set_seq_stereo_depth; DESIGN.md section 4, "Stereo depth").  rig: R, t with p_left = R p_right + t, the gates, right_obs
+    // (gf_stereo_depth_from_yaml reads one from a config file)
+    void readIntrinsicParameter(const std::vector<std::string>& calib_file, const int depth, const gf_stereo_depth_cfg& rig) {
+        if (calib_file.size() != 2) throw std::runtime_error("readIntrinsicParameter: a rig needs the calibration files of both eyes");
+        readIntrinsicParameter(calib_file, depth);
+        setStereoDepth(rig);
+    }
+    // the same switch on its own: before the first trackImage, for a tracker that has a right camera (readIntrinsicParameter with two files)
+    void setStereoDepth(const gf_stereo_depth_cfg& rig) {
+        if (!stereo_cam) throw std::runtime_error("setStereoDepth: the tracker has no right camera (readIntrinsicParameter with two files comes first)");
+        if (h_) check(gf_tracker_set_seq_stereo_depth(h_, 0, &rig));
+        stereo_depth_ = rig;
+    }
     void setIntrinsics(int width, int height, double fx, double fy, double cx, double cy, double k1 = 0, double k2 = 0, double p1 = 0, double p2 = 0) {
         col = width; row = height; fx_ = fx; fy_ = fy; cx_ = cx; cy_ = cy; k1_ = k1; k2_ = k2; p1_ = p1; p2_ = p2;
         camera_ = gf_camera_model_ex{};
@@ -263,6 +277,7 @@ class FeatureTracker {
     gf_depth_reg depth_reg_{}; bool has_depth_reg_ = false;   // setDepthRegistration, kept for a handle that does not exist yet
     gf_reject_f_cfg reject_f_{};                              // setRejectWithF, likewise
     gf_stereo_cfg stereo_{};                                  // readIntrinsicParameter's second file, likewise
+    gf_stereo_depth_cfg stereo_depth_{};                      // setStereoDepth, likewise
     static void check(int rc) { if (rc != GF_OK) throw std::runtime_error(std::string("groundfusion_hip: ") + gf_last_error()); }
     void create(int w, int h) {
         gf_tracker_cfg c{};
@@ -279,6 +294,7 @@ class FeatureTracker {
         if (has_depth_reg_) check(gf_tracker_set_seq_depth_reg(h_, 0, &depth_reg_));
         if (reject_f_.enable) check(gf_tracker_set_seq_reject_f(h_, 0, &reject_f_));
         if (stereo_.enable) check(gf_tracker_set_seq_stereo(h_, 0, &stereo_));
+        if (stereo_depth_.enable) check(gf_tracker_set_seq_stereo_depth(h_, 0, &stereo_depth_));
     }
     void refresh() {
         const int cap = (MAX_CNT + 3) & ~3;

@@ -1149,6 +1149,83 @@ int gf_ros_decode_odometry(const unsigned char* data, size_t len, double* t, dou
  * getDepthImageFromMsg (:265-286): the payload relabelled MONO16; two bytes per pixel in host order.  pixels == NULL only queries t / width / height. */
 int gf_ros_decode_image(const unsigned char* data, size_t len, int depth, double* t, int* width, int* height, void* pixels, size_t cap_bytes);
 
+/* ---- stereo depth: the depth a stereo sequence's left-to-right match determines, in the eighth field of its LEFT observations -- where the reference's stereo
+ * branch emits the left observations with a depth read out of the right image as if it were 16-bit millimetres (feature_tracker.cpp:344-368), which is not
+ * reproduced.  With it a stereo sequence looks to everything behind the tracker like a depth-camera sequence (triangulateWithDepth, feature_manager.cpp:773).
+ * DESIGN.md section 4, "Stereo depth", is the definition (csrc/gf_stereo_depth.hpp): both pixels lifted in double through the sequence's two cameras,
+ * a = P_l / P_l.z, b = P_r / P_r.z, d = R b, the closed-form minimum of |s a - t - u d|^2, depth = rint(1000 s) millimetres behind six gates. */
+typedef struct gf_stereo_depth_cfg {
+    int enable;        /* 1: left observations of a frame with a right image carry the triangulated depth */
+    int right_obs;     /* 1: the camera_id 1 observations follow as today; 0: they are not emitted (n_out counts the left ones only) */
+    double R[9], t[3]; /* p_left = R p_right + t: inverse(body_T_cam0) * body_T_cam1 */
+    double min_parallax, max_epipolar;   /* sine of the ray angle; normalised-plane distance in the right eye */
+    double min_depth, max_depth;         /* metres; max_depth <= 65.535 */
+} gf_stereo_depth_cfg;
+/* what became of a point, in the order the gates are tested (the first that fires names the reason); every reason but GF_STEREO_DEPTH_OK yields depth 0 */
+enum {
+    GF_STEREO_DEPTH_NO_MATCH = 1,  /* status 0 */
+    GF_STEREO_DEPTH_LIFT = 2,      /* a ray component that is not finite, P_l.z <= 0 or P_r.z <= 0 */
+    GF_STEREO_DEPTH_PARALLAX = 3,  /* aa dd - ad^2 <= min_parallax^2 aa dd */
+    GF_STEREO_DEPTH_BEHIND = 4,    /* s <= 0 or u <= 0 */
+    GF_STEREO_DEPTH_EPIPOLAR = 5,  /* q = R^T (s a - t): q.z <= 0 or (q.x - b.x q.z)^2 + (q.y - b.y q.z)^2 > max_epipolar^2 q.z^2 */
+    GF_STEREO_DEPTH_RANGE = 6,     /* rint(1000 s) outside [1000 min_depth, min(1000 max_depth, 65535)] */
+    GF_STEREO_DEPTH_OK = 7
+};
+typedef struct gf_stereo_depth_stats {
+    long long calls;       /* tracker calls that ran the stage for at least one sequence */
+    long long launches;    /* launches of stereo_depth_kernel (one per such call; none with GF_STEREO_DEPTH_HOST=1) */
+    long long points;      /* points the stage saw: cur_pts of every sequence and frame it ran for */
+    long long with_depth;  /* of them, GF_STEREO_DEPTH_OK */
+    long long no_match, lift, parallax, behind, epipolar, range;   /* the others, by reason */
+} gf_stereo_depth_stats;
+/* The switch, the rig and the gates of seq, before its first frame like the other per-sequence setters (c == NULL or enable == 0: off).  With the switch on, a
+ * frame that comes with a right image returns its left observations with v[7] = (double)(int)depth_mm / 1000, the depth-camera expression; a frame handed a null
+ * right entry carries 0 there for every feature; the right observations, where emitted (right_obs 1), keep -2.4.  With right_obs 0 an output sized for one eye
+ * suffices.  The arithmetic runs in ONE launch of stereo_depth_kernel per call for all such sequences, behind the stereo kernel on the same stream; its rows come
+ * up with the call's last copies, and the call gains no synchronisation and no copy of its own.  GF_STEREO_DEPTH_HOST=1 (read at gf_tracker_create) runs the same
+ * function on the host instead, no launch; the results are the same bit for bit except through a KANNALA_BRANDT camera.  Refused by name (GF_ERR_INVALID),
+ * nothing changed: a sequence without gf_tracker_set_seq_stereo, a sequence that has taken a frame or is listed by a staged one, a field that is not finite, R
+ * further than 1e-9 from orthonormal with determinant +1, t == 0, a gate that is not positive, min_depth >= max_depth, max_depth > 65.535, enable or right_obs
+ * outside {0, 1}.  Turning stereo off on the sequence (gf_tracker_set_seq_stereo) turns this off.  A handle on which it is never called allocates, copies and
+ * launches exactly what it did without it. */
+int gf_tracker_set_seq_stereo_depth(gf_tracker* h, int seq, const gf_stereo_depth_cfg* c);
+/* the configuration of seq as it was set; enable == 0 and zeros if it is off */
+int gf_tracker_get_seq_stereo_depth(gf_tracker* h, int seq, gf_stereo_depth_cfg* out);
+/* the stage's own counters; gf_tracker_reset_stats zeroes them */
+int gf_tracker_get_stereo_depth_stats(gf_tracker* h, gf_stereo_depth_stats* out);
+/* The definition as a building block, through the tracker's kernel: set b of n has the cameras left[b] and right[b], the rig and gates of cfg[b] (enable and
+ * right_obs are checked and otherwise not read), and the points [first[b] .. first[b + 1]): left_uv / right_uv two floats each, status a byte each.  depth_mm
+ * (millimetres, 0 without a depth) and why (GF_STEREO_DEPTH_*) ARE WRITTEN, one per point.  n, first, left, right and cfg are host tables.  _device: the point
+ * tables are device memory; one launch on `stream` (a hipStream_t, NULL = the null stream) whatever n, returns when it has run.  Without suffix: host tables,
+ * copy in, the launch, copy out.  _host: the same function on the CPU, no device needed.  Refused (GF_ERR_INVALID, naming the set and the field): what the
+ * setter refuses in a cfg, a camera gf_camera_model_ex's rules refuse, first[] not ascending from 0. */
+int gf_stereo_depth_batch_device(int n, const int* first, const gf_camera_model_ex* left, const gf_camera_model_ex* right, const gf_stereo_depth_cfg* cfg,
+                                 const float* d_left_uv, const float* d_right_uv, const uint8_t* d_status, uint16_t* d_depth_mm, uint8_t* d_why, void* stream);
+int gf_stereo_depth_batch(int n, const int* first, const gf_camera_model_ex* left, const gf_camera_model_ex* right, const gf_stereo_depth_cfg* cfg,
+                          const float* left_uv, const float* right_uv, const uint8_t* status, uint16_t* depth_mm, uint8_t* why);
+int gf_stereo_depth_batch_host(int n, const int* first, const gf_camera_model_ex* left, const gf_camera_model_ex* right, const gf_stereo_depth_cfg* cfg,
+                               const float* left_uv, const float* right_uv, const uint8_t* status, uint16_t* depth_mm, uint8_t* why);
+/* The rig and the gates from a config file: for `num_of_cam: 2`, R and t are inverse(body_T_cam0) * body_T_cam1 (parameters.cpp:445-463, read as the estimator's
+ * extrinsics are), max_depth is the file's depth_threshold, right_obs is 1, and the gates the reference has no key for get this repository's defaults:
+ * min_parallax 1e-3 (about half a pixel of disparity at FOCAL_LENGTH 460), max_epipolar 10 / 460 (triangulateWithDepth's residual bound), min_depth 0.1 (below
+ * it the estimator skips a depth).  Any other num_of_cam: enable == 0 and zeros.  GF_ERR_INVALID, naming the key or the field: a missing transform, and what the
+ * setter refuses (a depth_threshold of 0 or beyond 65). */
+int gf_stereo_depth_from_yaml(const char* config_file, gf_stereo_depth_cfg* out);
+/* A stereo rig on an estimator that owns its tracker (cfg.with_tracker): gf_tracker_set_seq_stereo and gf_tracker_set_seq_stereo_depth on that tracker's one
+ * sequence, before the first frame, with right_obs forced to 0 so that the back end sees one observation per feature.  From then on the estimator behaves as an
+ * RGB-D one whose depths come from the matches (triangulateWithDepth, the SfM initialisation with depth, movingConsistencyCheckW); stereo reprojection factors are
+ * not built.  Refused by name (GF_ERR_INVALID), nothing changed: no tracker, cfg.depth != 1 (the observations carry a depth), cfg.tracker.depth_cam != 0 (the
+ * second image is a right frame), and what the two setters refuse. */
+int gf_estimator_set_stereo_depth(gf_estimator* h, const gf_stereo_cfg* stereo, const gf_stereo_depth_cfg* depth);
+/* Estimator::inputImage (estimator.cpp:213-242) on device frames by reference (gf_tracker_track_some_device_refs on the estimator's own tracker): img1 is the
+ * depth frame of an RGB-D estimator or the right frame of a stereo one; NULL or data == NULL: none.  out / cap / n_out and the every-second-frame rule under
+ * multiple_thread as gf_estimator_input_image. */
+int gf_estimator_input_image_refs(gf_estimator* h, double t, const gf_frame_ref* img0, const gf_frame_ref* img1, gf_feature_obs* out, int cap, int* n_out);
+/* readParameters for a stereo rig: gf_estimator_cfg_from_yaml_camera_ex that ACCEPTS `num_of_cam: 2` (cfg->tracker.depth_cam is then 0 whatever `depth` says),
+ * with the right camera as gf_stereo_from_yaml and the rig as gf_stereo_depth_from_yaml read them.  With num_of_cam 1 both come back switched off.  The other
+ * gf_estimator_cfg_from_yaml* entry points keep refusing num_of_cam 2. */
+int gf_estimator_cfg_from_yaml_stereo(const char* config_file, gf_estimator_cfg* cfg, gf_camera_model_ex* left_camera, gf_stereo_cfg* stereo, gf_stereo_depth_cfg* stereo_depth);
+
 #ifdef __cplusplus
 }
 #endif
